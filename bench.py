@@ -22,6 +22,8 @@ SURVEY 8d's bytes -- the north star's kernel -- and the same CG kernels on the N
 path -- one byte per entry -- so the general CSR kernels are measured beside it on the same matrix), `cpu_baseline` (the
 oracle's C restatement on the host cores + the torch-CPU generic loop, bounded samples).  `traffic` comes from committed
 rocprofv3 --pmc passes and is quoted only when they were taken on the library build that is running (hipk_build_id).
+`--dump-outputs DIR` writes what the last timed step returned (x, info) as DIR/<name>.npy (dump_outputs): the inputs are
+fixed by the arguments, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -43,6 +45,8 @@ NX = 2000
 # in this run (PMC needs rocprofv3 attached); stamped with the commit it was taken at and dropped when the kernel differs
 PMC_FILES = ("r03_pmc_kernels.json",)
 STATS_FILE = "r03_bench_kernel_stats.json"   # tools/kernel_stats_to_json.py: rocprofv3 --kernel-trace --stats of this command
+DUMP_BYTES = 64 * 1024 * 1024   # --dump-outputs writes at most this much in all
+DUMP_SAMPLE = 1 << 20           # rows of x written when the whole vector does not fit DUMP_BYTES
 
 
 def parse():
@@ -58,7 +62,12 @@ def parse():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-iters", type=int, default=6000)
     ap.add_argument("--no-n64m", action="store_true", help="skip the N = 64 M (HBM-resident) roofline leg")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (x, info) as DIR/<name>.npy")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def free_port():
@@ -187,6 +196,34 @@ def load_pmc(build_id):
     return None, {}, "no counter profile committed for this round"
 
 
+def dump_outputs(out_dir, x, info, row0, n_global, rank, use_dist):
+    """--dump-outputs: what the last timed cg() returned to its caller, as <out_dir>/<name>.npy (rank 0 writes).
+    x.npy: the solution (float64), or, when the whole vector exceeds DUMP_BYTES, x_sample.npy holding the rows of a fixed
+    seeded sample of DUMP_SAMPLE rows whose global row numbers are in x_sample_rows.npy; info.npy: cg's info.
+    Row-partitioned runs gather the ranks' rows (x holds this rank's rows row0 ...) in global order."""
+    import numpy as np
+    xl = x.detach().reshape(-1).double().cpu().numpy()
+    rows = None
+    if n_global * 8 > DUMP_BYTES - 4096:
+        rows = np.sort(np.random.default_rng(0).choice(n_global, DUMP_SAMPLE, replace=False))
+        xl = xl[rows[(rows >= row0) & (rows < row0 + xl.size)] - row0]
+    if use_dist:
+        import torch.distributed as dist
+        parts = [None] * dist.get_world_size()
+        dist.all_gather_object(parts, (row0, xl))
+        xl = np.concatenate([p[1] for p in sorted(parts, key=lambda p: p[0])])
+    if rank != 0:
+        return
+    assert xl.size == (n_global if rows is None else rows.size), (xl.size, n_global)
+    os.makedirs(out_dir, exist_ok=True)
+    if rows is None:
+        np.save(os.path.join(out_dir, "x.npy"), xl)
+    else:
+        np.save(os.path.join(out_dir, "x_sample.npy"), xl)
+        np.save(os.path.join(out_dir, "x_sample_rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(out_dir, "info.npy"), np.array([info], dtype=np.float64))
+
+
 def main():
     args = parse()
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -291,6 +328,9 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = tt.item()
     x, info, st = last
+    n_global = nx * nx if (strong or not use_dist) else nx * nx * world
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, x, info, r0 if use_dist else 0, n_global, rank, use_dist)
 
     # ---- roofline leg: each kernel of the CG iteration timed INSIDE the solver loop by start/stop events bound to its
     # dispatch (params.profile selects the kernel; hipk_solve.h: hipExtLaunchKernel): the dispatch's own begin/end
@@ -542,7 +582,6 @@ def main():
                 "csr_formula_bytes": prob.spmv_bytes, "effective_GBps_on_csr_bytes": prob.spmv_bytes / (ms * 1e-3) / 1e9}
 
     if rank == 0:
-        n_global = nx * nx if (strong or not use_dist) else nx * nx * world
         if strong:
             value = iters_total / dt
             unit = f"it/s (CG iterations of the ONE N={n_global} system, all ranks together)"

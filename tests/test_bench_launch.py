@@ -31,6 +31,38 @@ def test_self_launch_spawns_ranks_and_propagates_failure():
     assert not [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
 
 
+def test_steps_below_one_is_refused():
+    """ms_per_step divides by --steps: zero timed steps is an argument error, not a result line."""
+    p = _run(["--steps", "0"], timeout=120)
+    assert p.returncode == 2 and "--steps must be >= 1" in p.stderr
+    assert not [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_are_the_last_solve_and_repeat(tmp_path):
+    """--dump-outputs DIR: x.npy / info.npy of the last timed step; x solves the benchmarked system, and a second run with
+    the same arguments writes the same bits."""
+    import numpy as np
+    import torch
+    from pytorch_sparse_solver.utils.matrix_utils import create_poisson_2d_csr
+    dumps = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        p = _run(["--steps", "2", "--warmup", "0", "--nx", "128", "--no-cpu-baseline", "--dump-outputs", str(d)])
+        assert p.returncode == 0, p.stderr[-2000:]
+        line = json.loads(p.stdout.strip().splitlines()[-1])
+        assert line["steps"] == 2 and line["ms_per_step"] > 0
+        assert sorted(os.listdir(d)) == ["info.npy", "x.npy"]
+        dumps.append((np.load(d / "x.npy"), np.load(d / "info.npy")))
+    (x, info), (x2, info2) = dumps
+    assert x.dtype == np.float64 and x.shape == (128 * 128,) and info.tolist() == [0.0]
+    assert np.array_equal(x, x2) and np.array_equal(info, info2)
+    A = create_poisson_2d_csr(128, 128)
+    b = np.ones(128 * 128)
+    r = b - (A @ torch.from_numpy(x)).numpy()
+    assert np.linalg.norm(r) <= 1e-5 * np.linalg.norm(b)   # cg(tol=1e-6) stops on the true residual
+
+
 @pytest.mark.gpu
 def test_bench_line_default_and_dist_rehearsal():
     """Small grids: the N = 1 line (roofline + kernels; cpu_baseline skipped off the headline size) and the row-partitioned
