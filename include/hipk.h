@@ -135,6 +135,13 @@ int hipk_csr_spmv_path(hipk_csr_t h);
  * as the profiler prints it, e.g. "hipk_spmv_sell_wide_kernel<5,1>"; "" before the first launch.  Measurement scripts label
  * their per-kernel figures with it instead of guessing the dispatch. */
 const char *hipk_last_spmv_kernel(void);
+/* The loop that finished the calling thread's most recent hipk_{cg,pcg,bicgstab,pbicgstab,gmres,pgmres}_solve (also the _cb
+ * forms): the one-launch instantiation of mid-size systems, e.g. "hipk_cg_mid_kernel<double,9,1,false>" or
+ * "hipk_gm_mid_kernel<float,7,true>"; the whole-loop kernel of small systems, e.g. "hipk_cg_solve_lds_kernel"; or
+ * "launch sequence" (kernels launched per iteration, also when the loop ran no iteration).  When a one-launch kernel handed
+ * the solve back (its workgroups were not all resident), the chain shows it: "hipk_cg_mid_kernel<double,5,1,false> ->
+ * launch sequence".  "" before the first solve. */
+const char *hipk_last_solve_path(void);
 /* mode 0: automatic (default); 1: never use the coded forms (A/B measurements, parity tests).
  * Environment: HIPK_SPMV_CODED=0 at creation time skips building the coded forms altogether,
  * HIPK_SPMV_OFFSET_CODED=0 only the offset-coded one. */

@@ -103,6 +103,7 @@ def lib():
                                   ctypes.c_int, ctypes.c_int, sp]
         L.orc32_gmres_jacobi.argtypes = [i64, ip, ip, fp, fp, fp, fp, ctypes.c_double, ctypes.c_double, ctypes.c_int, i64,
                                          ctypes.c_int, ctypes.c_int, sp]
+        L.orc32_bicgstab_jacobi.argtypes = [i64, ip, ip, fp, fp, fp, fp, ctypes.c_double, ctypes.c_double, i64, sp]
         L.orc32_set_threads.argtypes = [ctypes.c_int]
         _lib = L
     return _lib
@@ -358,6 +359,31 @@ def gmres32(crow, col, val, b, x0=None, tol=1e-5, atol=0.0, restart=20, maxiter=
     rc = lib().orc32_gmres(b.size, _i(crow), _i(col), _f(val), _f(b), _f(x), float(tol), float(atol), int(restart),
                            -1 if maxiter is None else int(maxiter), method, 1 if gpu_tolerances else 0,
                            ctypes.byref(st))
+    if rc != 0:
+        raise ValueError("oracle gmres supports 1 <= restart <= 127")
+    return _result(x, st)
+
+
+def bicgstab_jacobi32(crow, col, val, dinv, b, x0=None, tol=1e-5, atol=0.0, maxiter=None) -> OracleResult:
+    """bicgstab_jacobi with fp32 storage: restates hipk_pbicgstab_solve on fp32 tensors."""
+    crow, col, val, b, x = _prep32(crow, col, val, b, x0)
+    dinv = _f32(dinv)
+    st = _Stats()
+    lib().orc32_bicgstab_jacobi(b.size, _i(crow), _i(col), _f(val), _f(dinv), _f(b), _f(x), float(tol), float(atol),
+                                -1 if maxiter is None else int(maxiter), ctypes.byref(st))
+    return _result(x, st)
+
+
+def gmres_jacobi32(crow, col, val, dinv, b, x0=None, tol=1e-5, atol=0.0, restart=20, maxiter=None,
+                   solve_method="batched", gpu_tolerances=False) -> OracleResult:
+    """gmres_jacobi with fp32 storage: restates hipk_pgmres_solve on fp32 tensors."""
+    crow, col, val, b, x = _prep32(crow, col, val, b, x0)
+    dinv = _f32(dinv)
+    st = _Stats()
+    method = {"batched": 0, "incremental": 1}[solve_method]
+    rc = lib().orc32_gmres_jacobi(b.size, _i(crow), _i(col), _f(val), _f(dinv), _f(b), _f(x), float(tol), float(atol),
+                                  int(restart), -1 if maxiter is None else int(maxiter), method,
+                                  1 if gpu_tolerances else 0, ctypes.byref(st))
     if rc != 0:
         raise ValueError("oracle gmres supports 1 <= restart <= 127")
     return _result(x, st)

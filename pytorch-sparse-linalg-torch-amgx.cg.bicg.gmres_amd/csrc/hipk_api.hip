@@ -23,6 +23,14 @@ void hipk_set_error(const char *fmt, ...) {
 extern "C" const char *hipk_last_error(void) { return g_err; }
 static thread_local char g_spmv_kernel[96] = "";
 extern "C" const char *hipk_last_spmv_kernel(void) { return g_spmv_kernel; }
+static thread_local char g_solve_path[160] = "";
+extern "C" const char *hipk_last_solve_path(void) { return g_solve_path; }
+void hipk_set_solve_path(const char *from, const char *last) {
+    if (from && from[0])
+        snprintf(g_solve_path, sizeof(g_solve_path), "%s -> %s", from, last);
+    else
+        snprintf(g_solve_path, sizeof(g_solve_path), "%s", last);
+}
 #define HIPK_NOTE_KERNEL(...) snprintf(g_spmv_kernel, sizeof(g_spmv_kernel), __VA_ARGS__)
 #if __has_include("hipk_build_id.h")   // written by the Makefile (sha1 over the sources); absent in ad-hoc compiles of this file
 #include "hipk_build_id.h"

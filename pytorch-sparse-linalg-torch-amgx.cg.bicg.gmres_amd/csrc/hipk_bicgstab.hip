@@ -682,6 +682,18 @@ extern "C" size_t hipk_pbicgstab_work_bytes(int64_t n, int dtype) {
     return hipk_bicgstab_work_bytes(n, dtype) + 2 * vec;  // + phat, shat
 }
 
+// the name of a one-launch instantiation the dispatch below selects (hipk_last_solve_path): by its address
+template <typename T>
+static const char *hipk_bi_mid_name(void (*k)(hipk_bi_mid_args)) {
+#define HIPK_MID_NAME(W, PRE)                                                                                              \
+    if (k == hipk_bi_mid_kernel<T, W, PRE>)                                                                            \
+        return sizeof(T) == 8 ? "hipk_bi_mid_kernel<double," #W "," #PRE ">" : "hipk_bi_mid_kernel<float," #W "," #PRE ">";
+    HIPK_MID_NAME(5, false) HIPK_MID_NAME(7, false) HIPK_MID_NAME(9, false) HIPK_MID_NAME(12, false)
+    HIPK_MID_NAME(5, true) HIPK_MID_NAME(7, true) HIPK_MID_NAME(9, true) HIPK_MID_NAME(12, true)
+#undef HIPK_MID_NAME
+    return "hipk_bi_mid_kernel<?>";
+}
+
 // cb != null (PRE = false): the preconditioner is the CALLER's device code -- cb(user, in, out) enqueues out = M(in) on
 // `stream` -- applied where the Jacobi variant scales in-kernel: phat = M(p) before the first SpMV, shat = M(s) before the
 // second (TSL:908, 922), M(b - A x) for the final test (TSL:1007).  Same kernels, same order of operations.
@@ -707,6 +719,9 @@ static int hipk_bicgstab_solve_t(hipk_csr_s *A, const T *dinv, const T *b, T *x,
     const float tolf = (float)prm->tol, atolf = (float)prm->atol;
     const double tol2 = (double)(tolf * tolf), atol_sq = (double)(atolf * atolf);
     const int64_t check = prm->check_every > 0 ? prm->check_every : 32;
+    hipk_set_solve_path(nullptr, "");
+    char handed[128] = "";   // the one-launch loops that handed this solve back
+    const char *mid_name = "";
 
     hipk_event_pair whole;
     HIPK_CHECK_HIP(whole.create());
@@ -775,6 +790,7 @@ static int hipk_bicgstab_solve_t(hipk_csr_s *A, const T *dinv, const T *b, T *x,
                                              : A->max_row_len <= 7 ? hipk_bi_mid_kernel<T, 7, PRE>
                                              : A->max_row_len <= 9 ? hipk_bi_mid_kernel<T, 9, PRE>
                                                                    : hipk_bi_mid_kernel<T, 12, PRE>;
+        mid_name = hipk_bi_mid_name<T>(mid_kern);
         size_t lds = 0;
         hipk_mid_plan plan;
         memset(&plan, 0, sizeof(plan));
@@ -834,6 +850,7 @@ static int hipk_bicgstab_solve_t(hipk_csr_s *A, const T *dinv, const T *b, T *x,
                         return HIPK_ERR_HIP;
                     }
                     if (!getenv("HIPK_TEST_LDS_NOT_RESIDENT")) mid_failed = true;   // not co-resident; this launch modified nothing
+                    hipk_path_add(handed, mid_name);
                     mid_loop = false;
                     break;
                 }
@@ -908,6 +925,7 @@ static int hipk_bicgstab_solve_t(hipk_csr_s *A, const T *dinv, const T *b, T *x,
                     continue;
                 }
                 if (!getenv("HIPK_TEST_LDS_NOT_RESIDENT")) lds_loop_failed = true;   // not co-resident; this launch modified nothing: the launch sequence below takes over
+                hipk_path_add(handed, "hipk_bi_solve_lds_kernel");
                 if (it > 0) {
                     // ... from iteration `it` of an EARLIER launch: the vectors and scalars are in memory, but part_rr / part_rhr hold
                     // that launch's 8 g SUB-partials, not the g chunk partials the direction kernel folds.  Recompute them from r
@@ -922,6 +940,7 @@ static int hipk_bicgstab_solve_t(hipk_csr_s *A, const T *dinv, const T *b, T *x,
             if (hs0.stop_it <= it || it >= maxiter) break;
         }
     }
+    hipk_set_solve_path(handed, mid_loop ? mid_name : lds_loop ? "hipk_bi_solve_lds_kernel" : "launch sequence");
     if (mid_loop) lds_loop = true;   // finished in the one-launch loop
     for (; !lds_loop && it < maxiter; ++it) {
         HIPK_CHECK_HIP(pace.gate(it, stream, &stop));

@@ -937,6 +937,20 @@ extern "C" size_t hipk_cg_work_bytes(int64_t n, int dtype) {
     return 256 + hipk_scratch_bytes() + 3 * vec + (mid ? (ll - vec) + kMidSlotBytes : 0);
 }
 
+// the name of a one-launch instantiation the dispatch sites below select (hipk_last_solve_path): by its address, so that the
+// name is the kernel that was launched
+template <typename T>
+static const char *hipk_cg_mid_name(void (*k)(hipk_cg_mid_args)) {
+#define HIPK_MID_NAME(W, NCH, PRE)                                                                                         \
+    if (k == hipk_cg_mid_kernel<T, W, NCH, PRE>)                                                                       \
+        return sizeof(T) == 8 ? "hipk_cg_mid_kernel<double," #W "," #NCH "," #PRE ">" : "hipk_cg_mid_kernel<float," #W "," #NCH "," #PRE ">";
+    HIPK_MID_NAME(5, 1, false) HIPK_MID_NAME(7, 1, false) HIPK_MID_NAME(9, 1, false) HIPK_MID_NAME(12, 1, false)
+    HIPK_MID_NAME(5, 2, false) HIPK_MID_NAME(7, 2, false)
+    HIPK_MID_NAME(5, 1, true) HIPK_MID_NAME(7, 1, true) HIPK_MID_NAME(9, 1, true) HIPK_MID_NAME(12, 1, true)
+#undef HIPK_MID_NAME
+    return "hipk_cg_mid_kernel<?>";
+}
+
 template <typename T>
 static int hipk_cg_solve_t(hipk_csr_s *A, const T *b, T *x, char *work, const hipk_params *prm, hipk_stats *st,
                            hipStream_t stream) {
@@ -953,6 +967,9 @@ static int hipk_cg_solve_t(hipk_csr_s *A, const T *b, T *x, char *work, const hi
     T *Ap = (T *)((char *)p + vec);
 
     const int64_t maxiter = (prm->maxiter < 0) ? 10 * n : prm->maxiter;  // TSL:982-984
+    hipk_set_solve_path(nullptr, "");
+    char handed[128] = "";   // the one-launch loops that handed this solve back
+    const char *mid_name = "";
     // torch.square(torch.tensor(tol)): python floats become fp32 tensors (TSL:816-817)
     const float tolf = (float)prm->tol, atolf = (float)prm->atol;
     const double tol2 = (double)(tolf * tolf), atol_sq = (double)(atolf * atolf);
@@ -1032,6 +1049,7 @@ static int hipk_cg_solve_t(hipk_csr_s *A, const T *b, T *x, char *work, const hi
                         : A->max_row_len <= 9 ? hipk_cg_mid_kernel<T, 9, 1>
                                               : hipk_cg_mid_kernel<T, 12, 1>)
                      : (A->max_row_len <= 5 ? hipk_cg_mid_kernel<T, 5, 2> : hipk_cg_mid_kernel<T, 7, 2>);
+        mid_name = hipk_cg_mid_name<T>(mid_kern);
         const int mid_threads = 1024, mid_grid = (gm.g + nch - 1) / nch;
         if (nch == 2 && A->max_row_len > 7) mid_loop = false;   // four rows per thread: at most 7 entries each in registers
         size_t lds = 0;
@@ -1099,6 +1117,7 @@ static int hipk_cg_solve_t(hipk_csr_s *A, const T *b, T *x, char *work, const hi
                         return HIPK_ERR_HIP;
                     }
                     if (!getenv("HIPK_TEST_LDS_NOT_RESIDENT")) mid_failed = true;   // not co-resident; nothing was modified
+                    hipk_path_add(handed, mid_name);
                     mid_loop = false;
                     break;
                 }
@@ -1171,6 +1190,7 @@ static int hipk_cg_solve_t(hipk_csr_s *A, const T *b, T *x, char *work, const hi
                     continue;
                 }
                 if (!getenv("HIPK_TEST_LDS_NOT_RESIDENT")) lds_loop_failed = true;   // not co-resident; nothing was modified: the launch sequence below takes over
+                hipk_path_add(handed, "hipk_cg_solve_lds_kernel");
                 lds_loop = false;
                 break;
             }
@@ -1178,6 +1198,7 @@ static int hipk_cg_solve_t(hipk_csr_s *A, const T *b, T *x, char *work, const hi
             if (hs0.stop_it <= it || it >= maxiter) break;
         }
     }
+    hipk_set_solve_path(handed, mid_loop ? mid_name : lds_loop ? "hipk_cg_solve_lds_kernel" : "launch sequence");
     if (mid_loop) lds_loop = true;   // finished in the one-launch loop: none of the launch sequences below runs
     // launch-bound mid-size systems: TWO launches per iteration (hipk_cg2_spmv_kernel / hipk_cg2_update_kernel above)
     constexpr int kCap2 = sizeof(T) == 8 ? 1280 : 2048;
@@ -1706,6 +1727,9 @@ static int hipk_pcg_solve_t(hipk_csr_s *A, const T *dinv, const T *b, T *x, char
     const float tolf = (float)prm->tol, atolf = (float)prm->atol;
     const double tol2 = (double)(tolf * tolf), atol_sq = (double)(atolf * atolf);
     const int64_t check = prm->check_every > 0 ? prm->check_every : 64;
+    hipk_set_solve_path(nullptr, "");
+    char handed[128] = "";   // the one-launch loops that handed this solve back
+    const char *mid_name = "";
 
     hipk_event_pair whole;
     HIPK_CHECK_HIP(whole.create());
@@ -1760,6 +1784,7 @@ static int hipk_pcg_solve_t(hipk_csr_s *A, const T *dinv, const T *b, T *x, char
                                              : A->max_row_len <= 7 ? hipk_cg_mid_kernel<T, 7, 1, true>
                                              : A->max_row_len <= 9 ? hipk_cg_mid_kernel<T, 9, 1, true>
                                                                    : hipk_cg_mid_kernel<T, 12, 1, true>;
+        mid_name = hipk_cg_mid_name<T>(mid_kern);
         size_t lds = 0;
         hipk_mid_plan plan;
         memset(&plan, 0, sizeof(plan));
@@ -1821,6 +1846,7 @@ static int hipk_pcg_solve_t(hipk_csr_s *A, const T *dinv, const T *b, T *x, char
                         return HIPK_ERR_HIP;
                     }
                     if (!getenv("HIPK_TEST_LDS_NOT_RESIDENT")) mid_failed = true;   // this launch modified nothing
+                    hipk_path_add(handed, mid_name);
                     if (it > 0) {   // as below: <r,z> lives in scal->gamma[it & 1]; the launch sequence folds it from part_z[it & 1]
                         HIPK_CHECK_HIP(hipMemsetAsync(part_z[it & 1], 0, (size_t)gm.g * sizeof(double), stream));
                         HIPK_CHECK_HIP(hipMemcpyAsync(part_z[it & 1], &scal->gamma[it & 1], sizeof(double), hipMemcpyDeviceToDevice, stream));
@@ -1894,6 +1920,7 @@ static int hipk_pcg_solve_t(hipk_csr_s *A, const T *dinv, const T *b, T *x, char
                     continue;
                 }
                 if (!getenv("HIPK_TEST_LDS_NOT_RESIDENT")) lds_loop_failed = true;   // this launch modified nothing: the launch sequence below takes over
+                hipk_path_add(handed, "hipk_cg_solve_lds_kernel");
                 if (it > 0) {
                     // ... from iteration `it` of an EARLIER launch: x, r, p are in memory, but <r,z> only as scal->gamma[it & 1]
                     // (part_z[1] was the kernel's sub-partial scratch), while the launch sequence folds it from the chunk
@@ -1908,6 +1935,7 @@ static int hipk_pcg_solve_t(hipk_csr_s *A, const T *dinv, const T *b, T *x, char
             if (hs0.stop_it <= it || it >= maxiter) break;
         }
     }
+    hipk_set_solve_path(handed, mid_loop ? mid_name : lds_loop ? "hipk_cg_solve_lds_kernel" : "launch sequence");
     if (mid_loop) lds_loop = true;   // finished in the one-launch loop
     for (; !lds_loop && it < maxiter; ++it) {
         HIPK_CHECK_HIP(pace.gate(it, stream, &stop));

@@ -29,6 +29,13 @@
 
 // ---------------------------------------------------------------- error plumbing
 void hipk_set_error(const char *fmt, ...);
+// the loop that finished this thread's last solve (hipk_last_solve_path): `last`, or `from -> last` when `from` handed back
+void hipk_set_solve_path(const char *from, const char *last);
+// appends `name` to the chain of loops that handed a solve back ("a -> b")
+static inline void hipk_path_add(char (&chain)[128], const char *name) {
+    const size_t l = strlen(chain);
+    snprintf(chain + l, sizeof(chain) - l, l ? " -> %s" : "%s", name);
+}
 
 #define HIPK_CHECK_HIP(expr)                                                          \
     do {                                                                              \

@@ -2158,6 +2158,18 @@ __global__ __launch_bounds__(HIPK_THREADS) void hipk_gm_scaled_sq_kernel(int64_t
     if (threadIdx.x == 0) part[c] = acc;
 }
 
+// the name of a one-launch instantiation the dispatch below selects (hipk_last_solve_path): by its address
+template <typename T>
+static const char *hipk_gm_mid_name(void (*k)(hipk_gm_mid_args)) {
+#define HIPK_MID_NAME(W, PRE)                                                                                              \
+    if (k == hipk_gm_mid_kernel<T, W, PRE>)                                                                            \
+        return sizeof(T) == 8 ? "hipk_gm_mid_kernel<double," #W "," #PRE ">" : "hipk_gm_mid_kernel<float," #W "," #PRE ">";
+    HIPK_MID_NAME(5, false) HIPK_MID_NAME(7, false) HIPK_MID_NAME(9, false) HIPK_MID_NAME(12, false)
+    HIPK_MID_NAME(5, true) HIPK_MID_NAME(7, true) HIPK_MID_NAME(9, true) HIPK_MID_NAME(12, true)
+#undef HIPK_MID_NAME
+    return "hipk_gm_mid_kernel<?>";
+}
+
 // dinv != nullptr: left Jacobi preconditioning -- every A(.) is followed by M(.) = dinv .* (.) (TSL:351, 791, 766), applied
 // by the SpMV epilogue (HIPK_SPMV_SCALE) before its fused dots; ptol from ||M b|| (TSL:750).  Mirrored by orc_gmres_jacobi.
 // cb != nullptr (dinv == nullptr): M is the CALLER's device code, cb(user, in, out) enqueues out = M(in) on `stream`.  It runs
@@ -2188,6 +2200,9 @@ static int hipk_gmres_solve_t(hipk_csr_s *A, const T *dinv, const T *b, T *x, ch
     // guards (`_safe_normalize`, breakdown threshold) use the eps of the working dtype, as torch.finfo(dtype) would
     const double eps_t = (sizeof(T) == 8) ? HIPK_EPS64 : HIPK_EPS32;
     const int64_t maxiter = (prm->maxiter < 0) ? 10 * n : prm->maxiter;  // TSL:719-721
+    hipk_set_solve_path(nullptr, "");
+    char handed[128] = "";   // the one-launch kernels that handed this solve back
+    const char *last_cycle = "launch sequence";   // what ran the last restart cycle (none ran: the launch sequence's start and end)
 
     hipk_event_pair whole;
     HIPK_CHECK_HIP(whole.create());
@@ -2326,6 +2341,11 @@ static int hipk_gmres_solve_t(hipk_csr_s *A, const T *dinv, const T *b, T *x, ch
         }
         if (mid_cycle) cyc = cyc_lds = false;   // (9 .. 32 chunks: instead of the whole-solve kernel)
     }
+    const char *mid_name = hipk_gm_mid_name<T>(mid_kern);
+    // the kernel a cycle enqueued below runs in (hipk_last_solve_path)
+    auto cycle_kernel = [&]() -> const char * {
+        return mid_cycle ? mid_name : !cyc ? "launch sequence" : cyc_lds ? "hipk_gm_solve_lds_kernel" : "hipk_gm_cycle_small_kernel";
+    };
     // multi-dot with up to 32 columns per workgroup (w read ONCE per step; 0, the default: groups of 8, w re-read per group).  Same
     // box, alternating, N = 4 M (profiles/r03_gmres_history.md): GMRES(30) 6.67-6.70 vs 6.64-6.66 ms per cycle, GMRES(50) 16.50 vs
     // 16.38, GMRES(100) 60.1-60.2 vs 59.5-59.8 -- the re-reads of w are Infinity-Cache hits (FETCH_SIZE counts them: the 1.15 x of
@@ -2509,6 +2529,7 @@ static int hipk_gmres_solve_t(hipk_csr_s *A, const T *dinv, const T *b, T *x, ch
                 break;
             }
             if (!getenv("HIPK_TEST_LDS_NOT_RESIDENT")) mid_failed = true;
+            hipk_path_add(handed, mid_name);
             mid_cycle = false;
             continue;
         }
@@ -2521,10 +2542,12 @@ static int hipk_gmres_solve_t(hipk_csr_s *A, const T *dinv, const T *b, T *x, ch
                 cyc_local = false;      // its workgroups were spread over several XCDs: hand-offs at agent scope from now on
             } else {
                 if (cyc_lds && !getenv("HIPK_TEST_LDS_NOT_RESIDENT")) lds_cycle_failed = true;
+                hipk_path_add(handed, cycle_kernel());
                 cyc = cyc_lds = false;
             }
             continue;
         }
+        last_cycle = cycle_kernel();
         if (cyc && cyc_lds) {  // hipk_gm_solve_lds_kernel ran whole cycles, loop test included
             cycles += hs->rep_cycles;
             matvecs += hs->rep_matvecs;
@@ -2584,6 +2607,7 @@ static int hipk_gmres_solve_t(hipk_csr_s *A, const T *dinv, const T *b, T *x, ch
     }
     free(hs);
     if (rc != HIPK_OK) return rc;
+    hipk_set_solve_path(handed, last_cycle);
     if ((cyc || cyc_lds) && getenv("HIPK_GM_STAMPS")) {  // diagnostic build-in: where workgroup 0 of the cycle kernel spent its shader clocks
         unsigned long long st8[16];
         HIPK_CHECK_HIP(hipMemcpyAsync(st8, part_spare + 1600, sizeof(st8), hipMemcpyDeviceToHost, stream));

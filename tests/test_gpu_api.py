@@ -902,10 +902,18 @@ def test_cg_mid_one_launch_is_bit_identical(hipk, oracle, monkeypatch):
              (create_poisson_2d_csr(300, 300, device=DEV), dict(tol=1e-8), {"HIPK_CG_LAUNCH_ITS": "7"}),
              (create_poisson_2d_csr(300, 300, device=DEV), dict(tol=1e-8), {"HIPK_TEST_LDS_NOT_RESIDENT": "1"}),
              (create_poisson_2d_csr(300, 300, device=DEV), dict(tol=1e-8), {"HIPK_CG_LAUNCH_ITS": "7", "HIPK_TEST_LDS_NOT_RESIDENT": "2"})]
+    # the instantiation each case is meant for, (W, chunks per workgroup); None: not taken by design (maxiter = 0)
+    mid_for = [(5, 1)] * 5 + [(5, 2), (7, 1), (7, 1), (12, 1)] + [(5, 1)] * 3 + [None] + [(5, 1)] * 4
     for idx, (A, kw, env) in enumerate(cases):
       for dt in (torch.float64, torch.float32):   # fp32 storage: the kernel's T = float (tolerances it can reach, bounded iterations)
         Ad = A if dt == torch.float64 else torch.sparse_csr_tensor(A.crow_indices(), A.col_indices(), A.values().float(), size=A.shape)
         kwd = kw if dt == torch.float64 else {**kw, "tol": max(kw["tol"], 1e-4), "maxiter": min(kw.get("maxiter", 300) or 300, 300)}
+        tn = "double" if dt == torch.float64 else "float"
+        # (fp32: maxiter 0 became 300 above)
+        want = "launch sequence" if mid_for[idx] is None and kwd.get("maxiter") == 0 else \
+            "hipk_cg_mid_kernel<%s,%d,%d,false>" % ((tn,) + (mid_for[idx] or (5, 1)))
+        if "HIPK_TEST_LDS_NOT_RESIDENT" in env:
+            want += " -> launch sequence"   # (44 chunks: no whole-loop kernel to take over)
         h = hipk.handle_for(Ad)
         n = A.shape[0]
         g = torch.Generator(device=DEV).manual_seed(idx)
@@ -924,6 +932,8 @@ def test_cg_mid_one_launch_is_bit_identical(hipk, oracle, monkeypatch):
                     monkeypatch.delenv(k, raising=False)
             x = torch.zeros_like(b) if x0 is None else x0.clone()
             st = hipk.solve("cg", h, b, x, atol=0.0, **{"maxiter": None, **kwd})
+            path = hipk.last_solve_path()
+            assert (path == want) if mid == "1" else ("_mid_kernel" not in path), (idx, dt, mid, path)
             out.append((x.clone(), st.iterations, st.matvecs, st.info, st.residual_norm, st.recurrence_rs))
         assert torch.equal(out[0][0], out[1][0]) and out[0][1:] == out[1][1:], (idx, dt, out[0][1:], out[1][1:])
         if idx == 13:
@@ -938,6 +948,14 @@ def test_cg_mid_one_launch_is_bit_identical(hipk, oracle, monkeypatch):
       for dt in (torch.float64, torch.float32):
         Ad = A if dt == torch.float64 else torch.sparse_csr_tensor(A.crow_indices(), A.col_indices(), A.values().float(), size=A.shape)
         kwd = kw if dt == torch.float64 else {**kw, "tol": max(kw["tol"], 1e-4), "maxiter": min(kw.get("maxiter", 300) or 300, 300)}
+        tn = "double" if dt == torch.float64 else "float"
+        if kwd.get("maxiter") == 0 or (idx == 6 and dt == torch.float64):
+            # idx 6: three windows of 26 tiles (the 3-D stencil's planes 2304 rows apart) exceed the LDS of the fp64 loop
+            want = "launch sequence"
+        else:
+            want = "hipk_cg_mid_kernel<%s,%d,1,true>" % (tn, (mid_for[idx] or (5, 1))[0])
+            if "HIPK_TEST_LDS_NOT_RESIDENT" in env:
+                want += " -> launch sequence"
         h = hipk.handle_for(Ad)
         n = A.shape[0]
         Ac = A.cpu()
@@ -959,6 +977,8 @@ def test_cg_mid_one_launch_is_bit_identical(hipk, oracle, monkeypatch):
                     monkeypatch.delenv(k, raising=False)
             x = torch.zeros_like(b) if x0 is None else x0.clone()
             st = hipk.solve_pcg(h, dinv, b, x, atol=0.0, **{"maxiter": None, **kwd})
+            path = hipk.last_solve_path()
+            assert (path == want) if mid == "1" else ("_mid_kernel" not in path), ("jacobi", idx, dt, mid, path)
             out.append((x.clone(), st.iterations, st.matvecs, st.info, st.residual_norm, st.recurrence_rs))
         assert torch.equal(out[0][0], out[1][0]) and out[0][1:] == out[1][1:], ("jacobi", idx, dt, out[0][1:], out[1][1:])
         if idx == 13:
@@ -1015,10 +1035,19 @@ def test_bicgstab_mid_one_launch_is_bit_identical(hipk, oracle, monkeypatch):
              (create_convdiff_2d_csr(300, 300, device=DEV), dict(tol=1e-8), {"HIPK_TEST_LDS_NOT_RESIDENT": "1"}),
              (create_convdiff_2d_csr(300, 300, device=DEV), dict(tol=1e-8), {"HIPK_BICGSTAB_LAUNCH_ITS": "5", "HIPK_TEST_LDS_NOT_RESIDENT": "2"}),
              (create_convdiff_2d_csr(300, 300, device=DEV), dict(tol=1e-30, maxiter=400), {})]       # runs into the iteration bound (or a breakdown)
+    mid_w = [5] * 6 + [7, 12] + [5] * 9   # the instantiation each case is meant for (hipk_bi_mid_kernel<T, W, PRE>)
+
+    def want_path(idx, tn, pre, kw, env):
+        if kw.get("maxiter") == 0:
+            return "launch sequence"   # the one-launch loop needs maxiter > 0
+        p = "hipk_bi_mid_kernel<%s,%d,%s>" % (tn, mid_w[idx], "true" if pre else "false")
+        return p + " -> launch sequence" if "HIPK_TEST_LDS_NOT_RESIDENT" in env else p   # (44 chunks: no whole-loop kernel)
+
     for idx, (A, kw, env) in enumerate(cases):
       for dt in (torch.float64, torch.float32):   # fp32 storage: the kernel's T = float (tolerances it can reach, bounded iterations)
         Ad = A if dt == torch.float64 else torch.sparse_csr_tensor(A.crow_indices(), A.col_indices(), A.values().float(), size=A.shape)
         kw = kw if dt == torch.float64 else {**kw, "tol": max(kw["tol"], 1e-4), "maxiter": min(kw.get("maxiter", 200) or 200, 200)}
+        want = want_path(idx, "double" if dt == torch.float64 else "float", False, kw, env)
         h = hipk.handle_for(Ad)
         n = A.shape[0]
         g = torch.Generator(device=DEV).manual_seed(idx)
@@ -1042,6 +1071,8 @@ def test_bicgstab_mid_one_launch_is_bit_identical(hipk, oracle, monkeypatch):
             x = torch.zeros_like(b) if x0 is None else x0.clone()
             print("bicgstab mid case", idx, "mid" if mid == "1" else "launch sequence", flush=True)   # (-s: which case a hang is in)
             st = hipk.solve("bicgstab", h, b, x, atol=0.0, **{"maxiter": None, **kw})
+            path = hipk.last_solve_path()
+            assert (path == want) if mid == "1" else ("_mid_kernel" not in path), (idx, dt, mid, path)
             out.append((x.clone(), st.iterations, st.matvecs, st.info, st.residual_norm, st.recurrence_rs, st.breakdown))
         assert torch.equal(torch.nan_to_num(out[0][0], nan=0.5), torch.nan_to_num(out[1][0], nan=0.5)), (idx, dt, out[0][1:], out[1][1:])
         assert all(a == b_ or (a != a and b_ != b_) for a, b_ in zip(out[0][1:], out[1][1:])), (idx, dt, out[0][1:], out[1][1:])
@@ -1060,6 +1091,7 @@ def test_bicgstab_mid_one_launch_is_bit_identical(hipk, oracle, monkeypatch):
         dinv = (1.0 / torch.from_numpy(sp.csr_matrix((Ac.values().numpy(), Ac.col_indices().numpy(), Ac.crow_indices().numpy()),
                                                      shape=A.shape).diagonal())).to(DEV)
         g = torch.Generator(device=DEV).manual_seed(300 + idx)
+        want = want_path(idx, "double", True, kw, env)
         b = torch.randn(n, dtype=torch.float64, device=DEV, generator=g)
         x0 = torch.randn(n, dtype=torch.float64, device=DEV, generator=g) if idx % 2 else None
         out = []
@@ -1076,6 +1108,8 @@ def test_bicgstab_mid_one_launch_is_bit_identical(hipk, oracle, monkeypatch):
                     monkeypatch.delenv(k, raising=False)
             x = torch.zeros_like(b) if x0 is None else x0.clone()
             st = hipk.solve_pcg(h, dinv, b, x, atol=0.0, method="bicgstab", **{"maxiter": None, **kw})
+            path = hipk.last_solve_path()
+            assert (path == want) if mid == "1" else ("_mid_kernel" not in path), ("jacobi", idx, mid, path)
             out.append((x.clone(), st.iterations, st.matvecs, st.info, st.residual_norm, st.recurrence_rs, st.breakdown))
         assert torch.equal(torch.nan_to_num(out[0][0], nan=0.5), torch.nan_to_num(out[1][0], nan=0.5)), ("jacobi", idx, out[0][1:], out[1][1:])
         assert all(a == b_ or (a != a and b_ != b_) for a, b_ in zip(out[0][1:], out[1][1:])), ("jacobi", idx, out[0][1:], out[1][1:])
@@ -1124,6 +1158,16 @@ def test_gmres_mid_one_launch_cycle_is_bit_identical(hipk, oracle, monkeypatch):
              (create_convdiff_2d_csr(300, 300, device=DEV), dict(tol=1e-8, restart=15, maxiter=4), {"HIPK_TEST_LDS_NOT_RESIDENT": "2"}),
              (grid3d(64), dict(tol=1e-8, restart=25, maxiter=3), {}),                                             # 128 chunks, three bands of tiles
              (grid3d(45), dict(tol=1e-8, restart=30, maxiter=2, solve_method="incremental"), {})]               # ragged planes
+    mid_w = [5] * 13 + [7, 7]   # the instantiation each case is meant for (hipk_gm_mid_kernel<T, W, PRE>)
+
+    def want_path(idx, tn, pre, kw, env, cycles):
+        if kw.get("maxiter") == 0:
+            return "launch sequence"   # no restart cycle ran
+        p = "hipk_gm_mid_kernel<%s,%d,%s>" % (tn, mid_w[idx], "true" if pre else "false")
+        # the k-th one-launch cycle hands back (44 chunks: the launch sequence takes over), if the solve has a k-th cycle
+        nr = int(env.get("HIPK_TEST_LDS_NOT_RESIDENT", "0"))
+        return p + " -> launch sequence" if 0 < nr <= max(cycles, 1) else p
+
     for idx, (A, kw, env) in enumerate(cases):
       for dt in (torch.float64, torch.float32):   # fp32 storage: the kernel's T = float
         Ad = A if dt == torch.float64 else torch.sparse_csr_tensor(A.crow_indices(), A.col_indices(), A.values().float(), size=A.shape)
@@ -1144,6 +1188,9 @@ def test_gmres_mid_one_launch_cycle_is_bit_identical(hipk, oracle, monkeypatch):
             x = torch.zeros_like(b) if x0 is None else x0.clone()
             print("gmres mid case", idx, dt, "mid" if mid == "1" else "launch sequence", flush=True)
             st = hipk.solve("gmres", h, b, x, atol=0.0, **kwd)
+            path = hipk.last_solve_path()
+            want = want_path(idx, "double" if dt == torch.float64 else "float", False, kwd, env, st.iterations)
+            assert (path == want) if mid == "1" else ("_mid_kernel" not in path), (idx, dt, mid, path)
             out.append((x.clone(), st.iterations, st.matvecs, st.info, st.residual_norm, st.recurrence_rs, st.breakdown))
         assert torch.equal(out[0][0], out[1][0]) and out[0][1:] == out[1][1:], (idx, dt, out[0][1:], out[1][1:])
     # the same with M = diag(d) applied after every A (hipk_gm_mid_kernel<W, PRE>: the row scaling of the SpMV epilogue); a diagonal
@@ -1167,6 +1214,9 @@ def test_gmres_mid_one_launch_cycle_is_bit_identical(hipk, oracle, monkeypatch):
                     monkeypatch.delenv(k, raising=False)
             x = torch.zeros_like(b)
             st = hipk.solve_pgmres(h, dinv, b, x, atol=0.0, **kw)
+            path = hipk.last_solve_path()
+            want = want_path(idx, "double", True, kw, env, st.iterations)
+            assert (path == want) if mid == "1" else ("_mid_kernel" not in path), ("jacobi", idx, mid, path)
             out.append((x.clone(), st.iterations, st.matvecs, st.info, st.residual_norm, st.recurrence_rs, st.breakdown))
         assert torch.equal(out[0][0], out[1][0]) and out[0][1:] == out[1][1:], ("jacobi", idx, out[0][1:], out[1][1:])
     monkeypatch.delenv("HIPK_GMRES_MID", raising=False)
