@@ -318,7 +318,7 @@ struct hipk_bi_lds_args {
     double *part_ss;                // [8 g] sub-partials of <s,s>
     unsigned long long *flag_a, *flag_b, *flag_c;   // [64] each, zeroed before the launch
     int64_t it0, maxiter, max_its;
-    int test_not_resident;   // tests (HIPK_TEST_LDS_NOT_RESIDENT): report the placement check as failed
+    int test_not_resident;   // tests (hipk_test_fail_launch): report the placement check as failed
     int spread;              // more than 64 workgroups: one per block all over the chip (then LOCAL = false)
 };
 static constexpr int kBiRowRegs = 12;
@@ -682,17 +682,17 @@ extern "C" size_t hipk_pbicgstab_work_bytes(int64_t n, int dtype) {
     return hipk_bicgstab_work_bytes(n, dtype) + 2 * vec;  // + phat, shat
 }
 
-// the name of a one-launch instantiation the dispatch below selects (hipk_last_solve_path): by its address
+// the one-launch instantiations the dispatch below selects (hipk_mid_pick), each with the name hipk_last_solve_path reports
+#define HIPK_MID_ROW(W, PRE)                                                                                               \
+    {W, 1, PRE, hipk_bi_mid_kernel<T, W, PRE>,                                                                             \
+     sizeof(T) == 8 ? "hipk_bi_mid_kernel<double," #W "," #PRE ">" : "hipk_bi_mid_kernel<float," #W "," #PRE ">"}
 template <typename T>
-static const char *hipk_bi_mid_name(void (*k)(hipk_bi_mid_args)) {
-#define HIPK_MID_NAME(W, PRE)                                                                                              \
-    if (k == hipk_bi_mid_kernel<T, W, PRE>)                                                                            \
-        return sizeof(T) == 8 ? "hipk_bi_mid_kernel<double," #W "," #PRE ">" : "hipk_bi_mid_kernel<float," #W "," #PRE ">";
-    HIPK_MID_NAME(5, false) HIPK_MID_NAME(7, false) HIPK_MID_NAME(9, false) HIPK_MID_NAME(12, false)
-    HIPK_MID_NAME(5, true) HIPK_MID_NAME(7, true) HIPK_MID_NAME(9, true) HIPK_MID_NAME(12, true)
-#undef HIPK_MID_NAME
-    return "hipk_bi_mid_kernel<?>";
-}
+static const hipk_mid_entry<hipk_bi_mid_args> hipk_bi_mid_table[] = {
+    HIPK_MID_ROW(5, false), HIPK_MID_ROW(7, false), HIPK_MID_ROW(9, false), HIPK_MID_ROW(12, false),
+    HIPK_MID_ROW(5, true),  HIPK_MID_ROW(7, true),  HIPK_MID_ROW(9, true),  HIPK_MID_ROW(12, true)};
+#undef HIPK_MID_ROW
+// {redo, it_done, stop_it} of a host copy of the scalar block (hipk_resident_run)
+static hipk_loop_state hipk_bi_loop_state(const hipk_bi_scal &h) { return {h.redo, h.it_done, h.stop_it}; }
 
 // cb != null (PRE = false): the preconditioner is the CALLER's device code -- cb(user, in, out) enqueues out = M(in) on
 // `stream` -- applied where the Jacobi variant scales in-kernel: phat = M(p) before the first SpMV, shat = M(s) before the
@@ -721,7 +721,6 @@ static int hipk_bicgstab_solve_t(hipk_csr_s *A, const T *dinv, const T *b, T *x,
     const int64_t check = prm->check_every > 0 ? prm->check_every : 32;
     hipk_set_solve_path(nullptr, "");
     char handed[128] = "";   // the one-launch loops that handed this solve back
-    const char *mid_name = "";
 
     hipk_event_pair whole;
     HIPK_CHECK_HIP(whole.create());
@@ -780,84 +779,53 @@ static int hipk_bicgstab_solve_t(hipk_csr_s *A, const T *dinv, const T *b, T *x,
     // launch-bound systems of 9 .. 256 chunks (fp64, M = identity, rows of <= 12 entries within a window around their chunk): the
     // whole loop in one launch, one workgroup per chunk (hipk_bi_mid.h); HIPK_BICGSTAB_MID=0 leaves them to the paths below
     static bool mid_failed = false;
-    bool mid_loop = false;
-    {
-        mid_loop = !ext && gm.g > kMidMinChunks && gm.g <= kBiMidMaxChunks && gm.g <= A->n_cu && gm.ch == HIPK_BASE_CHUNK && A->op_cb == nullptr &&
-                   A->crow != nullptr && A->max_row_len <= 12 && prm->profile == 0 && maxiter > 0 && !mid_failed &&
-                   !(getenv("HIPK_BICGSTAB_MID") && getenv("HIPK_BICGSTAB_MID")[0] == '0') && !getenv("HIPK_BICGSTAB_NO_LDS_LOOP") &&
-                   !getenv("HIPK_BICGSTAB_NO_SMALL");
-        void (*mid_kern)(hipk_bi_mid_args) = A->max_row_len <= 5   ? hipk_bi_mid_kernel<T, 5, PRE>
-                                             : A->max_row_len <= 7 ? hipk_bi_mid_kernel<T, 7, PRE>
-                                             : A->max_row_len <= 9 ? hipk_bi_mid_kernel<T, 9, PRE>
-                                                                   : hipk_bi_mid_kernel<T, 12, PRE>;
-        mid_name = hipk_bi_mid_name<T>(mid_kern);
-        size_t lds = 0;
-        hipk_mid_plan plan;
-        memset(&plan, 0, sizeof(plan));
-        if (mid_loop) {
-            mid_loop = hipk_mid_plan_get(A, 1, stream, &plan);   // the tiles each workgroup's window holds (hipk_mid.h)
-            lds = mid_loop ? hipk_bi_mid_lds_bytes(plan.max_slots * HIPK_TILE, PRE, sizeof(T)) : 0;
-            int occ = 0;
-            mid_loop = mid_loop && plan.max_slots <= kMidPlanSlots && lds <= (size_t)160 * 1024 &&
-                       hipFuncSetAttribute((const void *)mid_kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess &&
-                       hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, mid_kern, 1024, lds) == hipSuccess && (int64_t)occ * A->n_cu >= gm.g;
-            (void)hipGetLastError();
-        }
-        if (mid_loop) {
-            const char *e = getenv("HIPK_BICGSTAB_LAUNCH_ITS");
-            hipk_bi_mid_args ca;
-            ca.n = n;
-            ca.g = gm.g;
-            ca.win = plan.max_slots * HIPK_TILE;
-            ca.plan = plan;
-            ca.crow = A->crow;
-            ca.col = A->col;
-            const size_t ll_bytes = hipk_align_up((size_t)n * 16, 256);
-            ca.val = A->val;
-            ca.x = x;
-            ca.r = r;
-            ca.p = p;
-            ca.q = q;
-            ca.rhat = rhat;
-            ca.dinv = dinv;
-            ca.q_ll = (unsigned long long *)(vbase + 8 * vec);      // behind the eight vectors (hipk_bicgstab_work_bytes)
-            ca.r_ll = (unsigned long long *)(vbase + 8 * vec + ll_bytes);
-            ca.slots = (unsigned long long *)(vbase + 8 * vec + 2 * ll_bytes);
-            ca.part_rr = part_rr;
-            ca.part_rhr = part_rhr;
-            ca.scal = scal;
-            ca.maxiter = maxiter;
-            ca.max_its = e ? atoll(e) : 8192;
-            if (ca.max_its < 1) ca.max_its = 1;
-            ca.slot_stride = gm.g <= 32 ? 1 : 16;
-            ca.xcd_aware = 1;
-            const int fail_launch = getenv("HIPK_TEST_LDS_NOT_RESIDENT") ? (atoi(getenv("HIPK_TEST_LDS_NOT_RESIDENT")) > 1 ? atoi(getenv("HIPK_TEST_LDS_NOT_RESIDENT")) : 1) : 0;
-            int launch_no = 0;
-            hipk_bi_scal hs0;
-            for (;;) {
-                ca.it0 = it;
-                ca.test_not_resident = (++launch_no == fail_launch) ? 1 : 0;
-                HIPK_CHECK_HIP(hipMemsetAsync(ca.q_ll, 0, 2 * ll_bytes, stream));
-                HIPK_CHECK_HIP(hipMemsetAsync(ca.slots, 0, kBiMidSlotBytes, stream));
-                HIPK_CHECK_HIP(hipMemsetAsync(&scal->it_done, 0, sizeof(hipk_bi_scal) - offsetof(hipk_bi_scal, it_done), stream));
-                mid_kern<<<hipk_xcd_grid(gm.g), 1024, lds, stream>>>(ca);
-                HIPK_CHECK_HIP(hipGetLastError());
-                HIPK_CHECK_HIP(hipMemcpyAsync(&hs0, scal, sizeof(hs0), hipMemcpyDeviceToHost, stream));
-                HIPK_CHECK_HIP(hipStreamSynchronize(stream));
-                if (hs0.redo < 0) {
-                    if (hs0.redo == -3) {
-                        hipk_set_error("hipk_bicgstab_solve: a resident workgroup of the one-launch loop stopped arriving");
-                        return HIPK_ERR_HIP;
-                    }
-                    if (!getenv("HIPK_TEST_LDS_NOT_RESIDENT")) mid_failed = true;   // not co-resident; this launch modified nothing
-                    hipk_path_add(handed, mid_name);
-                    mid_loop = false;
-                    break;
-                }
-                it = hs0.it_done;
-                if (hs0.stop_it <= it || it >= maxiter) break;
-            }
-        }
+    const hipk_mid_entry<hipk_bi_mid_args> *mid = hipk_mid_pick(hipk_bi_mid_table<T>, A->max_row_len, 1, PRE);
+    auto mid_lds = [](int slots) { return hipk_bi_mid_lds_bytes(slots * HIPK_TILE, PRE, sizeof(T)); };
+    hipk_mid_plan plan;
+    size_t lds = 0;
+    bool mid_loop = !ext && gm.g > kMidMinChunks && gm.g <= kBiMidMaxChunks && gm.g <= A->n_cu && gm.ch == HIPK_BASE_CHUNK && A->op_cb == nullptr &&
+                    A->crow != nullptr && A->max_row_len <= 12 && prm->profile == 0 && maxiter > 0 && !mid_failed &&
+                    !(getenv("HIPK_BICGSTAB_MID") && getenv("HIPK_BICGSTAB_MID")[0] == '0') && !getenv("HIPK_BICGSTAB_NO_LDS_LOOP") &&
+                    !getenv("HIPK_BICGSTAB_NO_SMALL") && mid && hipk_mid_eligible(A, mid, gm.g, mid_lds, stream, &plan, &lds);
+    if (mid_loop) {
+        hipk_bi_mid_args ca;
+        ca.n = n;
+        ca.g = gm.g;
+        ca.win = plan.max_slots * HIPK_TILE;
+        ca.plan = plan;
+        ca.crow = A->crow;
+        ca.col = A->col;
+        const size_t ll_bytes = hipk_align_up((size_t)n * 16, 256);
+        ca.val = A->val;
+        ca.x = x;
+        ca.r = r;
+        ca.p = p;
+        ca.q = q;
+        ca.rhat = rhat;
+        ca.dinv = dinv;
+        ca.q_ll = (unsigned long long *)(vbase + 8 * vec);      // behind the eight vectors (hipk_bicgstab_work_bytes)
+        ca.r_ll = (unsigned long long *)(vbase + 8 * vec + ll_bytes);
+        ca.slots = (unsigned long long *)(vbase + 8 * vec + 2 * ll_bytes);
+        ca.part_rr = part_rr;
+        ca.part_rhr = part_rhr;
+        ca.scal = scal;
+        ca.maxiter = maxiter;
+        ca.max_its = hipk_env_its("HIPK_BICGSTAB_LAUNCH_ITS", 8192);
+        ca.slot_stride = gm.g <= 32 ? 1 : 16;
+        ca.xcd_aware = 1;
+        auto launch = [&](int64_t it0, int test_not_resident, bool) -> int {
+            ca.it0 = it0;
+            ca.test_not_resident = test_not_resident;
+            HIPK_CHECK_HIP(hipMemsetAsync(ca.q_ll, 0, 2 * ll_bytes, stream));
+            HIPK_CHECK_HIP(hipMemsetAsync(ca.slots, 0, kBiMidSlotBytes, stream));
+            HIPK_CHECK_HIP(hipMemsetAsync(&scal->it_done, 0, sizeof(hipk_bi_scal) - offsetof(hipk_bi_scal, it_done), stream));
+            mid->kern<<<hipk_xcd_grid(gm.g), 1024, lds, stream>>>(ca);
+            return HIPK_OK;
+        };
+        const int run = hipk_resident_run(stream, scal, launch, hipk_bi_loop_state, it, maxiter, nullptr, mid_failed, handed, mid->name,
+                                          "hipk_bicgstab_solve");
+        if (run < 0) return run;
+        mid_loop = run == HIPK_OK;
     }
     // launch-bound systems with short rows, M = identity: the whole loop in one launch (hipk_bi_solve_lds_kernel)
     static bool lds_loop_failed = false;   // its workgroups once failed to meet (a shared device): do not wait for that verdict again
@@ -869,8 +837,7 @@ static int hipk_bicgstab_solve_t(hipk_csr_s *A, const T *dinv, const T *b, T *x,
                     !getenv("HIPK_BICGSTAB_NO_LDS_LOOP") && !(lds_spread && getenv("HIPK_NO_LDS_SPREAD")) && !mid_loop &&
                     it == 0;   // (after a one-launch loop above gave up mid-solve, part_rr / part_rhr hold CHUNK partials: launch sequence)
     if (lds_loop) {
-        bool local = !lds_spread && !getenv("HIPK_BICGSTAB_LOOP_AGENT");
-        const char *e = getenv("HIPK_BICGSTAB_LAUNCH_ITS");
+        bool local = !lds_spread && !getenv("HIPK_BICGSTAB_LOOP_AGENT");   // a -2 (spread over several XCDs): agent-scope hand-offs
         hipk_bi_lds_args<T> ca;
         ca.n = n;
         ca.g = gm.g;
@@ -897,50 +864,29 @@ static int hipk_bicgstab_solve_t(hipk_csr_s *A, const T *dinv, const T *b, T *x,
         ca.spread = lds_spread ? 1 : 0;
         const int lgrid = lds_spread ? kGmSub * gm.g : 8 * kGmSub * gm.g;
         ca.maxiter = maxiter;
-        ca.max_its = e ? atoll(e) : 8192;
-        if (ca.max_its < 1) ca.max_its = 1;
-        // tests: HIPK_TEST_LDS_NOT_RESIDENT=k makes the k-th launch of this solve report its workgroups as not co-resident
-        const int fail_launch = getenv("HIPK_TEST_LDS_NOT_RESIDENT") ? (atoi(getenv("HIPK_TEST_LDS_NOT_RESIDENT")) > 1 ? atoi(getenv("HIPK_TEST_LDS_NOT_RESIDENT")) : 1) : 0;
-        int launch_no = 0;
-        hipk_bi_scal hs0;
-        for (;;) {
-            ca.it0 = it;
-            ca.test_not_resident = (++launch_no == fail_launch) ? 1 : 0;
+        ca.max_its = hipk_env_its("HIPK_BICGSTAB_LAUNCH_ITS", 8192);
+        auto launch = [&](int64_t it0, int test_not_resident, bool loc) -> int {
+            ca.it0 = it0;
+            ca.test_not_resident = test_not_resident;
             HIPK_CHECK_HIP(hipMemsetAsync(ca.flag_a, 0, 3 * kHoMaxWg * sizeof(unsigned long long), stream));
             HIPK_CHECK_HIP(hipMemsetAsync(&scal->it_done, 0, sizeof(hipk_bi_scal) - offsetof(hipk_bi_scal, it_done), stream));
-            if (local)
-                hipk_bi_solve_lds_kernel<T, true, PRE><<<lgrid, HIPK_THREADS, 0, stream>>>(ca);
-            else
-                hipk_bi_solve_lds_kernel<T, false, PRE><<<lgrid, HIPK_THREADS, 0, stream>>>(ca);
-            HIPK_CHECK_HIP(hipGetLastError());
-            HIPK_CHECK_HIP(hipMemcpyAsync(&hs0, scal, sizeof(hs0), hipMemcpyDeviceToHost, stream));
-            HIPK_CHECK_HIP(hipStreamSynchronize(stream));
-            if (hs0.redo < 0) {
-                if (hs0.redo == -3) {
-                    hipk_set_error("hipk_bicgstab_solve: a resident workgroup of the one-launch loop stopped arriving");
-                    return HIPK_ERR_HIP;
-                }
-                if (hs0.redo == -2 && local) {   // spread over several XCDs: agent-scope hand-offs
-                    local = false;
-                    continue;
-                }
-                if (!getenv("HIPK_TEST_LDS_NOT_RESIDENT")) lds_loop_failed = true;   // not co-resident; this launch modified nothing: the launch sequence below takes over
-                hipk_path_add(handed, "hipk_bi_solve_lds_kernel");
-                if (it > 0) {
-                    // ... from iteration `it` of an EARLIER launch: the vectors and scalars are in memory, but part_rr / part_rhr hold
-                    // that launch's 8 g SUB-partials, not the g chunk partials the direction kernel folds.  Recompute them from r
-                    // and rhat (the spec's plain dot: the bits the x-update kernel of the launch sequence would have left)
-                    if ((rc = hipk_launch_dot_parts(n, r, r, A->dtype, part_rr, stream)) != HIPK_OK) return rc;
-                    if ((rc = hipk_launch_dot_parts(n, rhat, r, A->dtype, part_rhr, stream)) != HIPK_OK) return rc;
-                }
-                lds_loop = false;
-                break;
-            }
-            it = hs0.it_done;
-            if (hs0.stop_it <= it || it >= maxiter) break;
+            (loc ? hipk_bi_solve_lds_kernel<T, true, PRE> : hipk_bi_solve_lds_kernel<T, false, PRE>)<<<lgrid, HIPK_THREADS, 0, stream>>>(ca);
+            return HIPK_OK;
+        };
+        // a hand-back (not co-resident; this launch modified nothing): the launch sequence below takes over
+        const int run = hipk_resident_run(stream, scal, launch, hipk_bi_loop_state, it, maxiter, &local, lds_loop_failed, handed,
+                                          "hipk_bi_solve_lds_kernel", "hipk_bicgstab_solve");
+        if (run < 0) return run;
+        if (run == HIPK_HANDED_BACK && it > 0) {
+            // ... from iteration `it` of an EARLIER launch: the vectors and scalars are in memory, but part_rr / part_rhr hold
+            // that launch's 8 g SUB-partials, not the g chunk partials the direction kernel folds.  Recompute them from r
+            // and rhat (the spec's plain dot: the bits the x-update kernel of the launch sequence would have left)
+            if ((rc = hipk_launch_dot_parts(n, r, r, A->dtype, part_rr, stream)) != HIPK_OK) return rc;
+            if ((rc = hipk_launch_dot_parts(n, rhat, r, A->dtype, part_rhr, stream)) != HIPK_OK) return rc;
         }
+        lds_loop = run == HIPK_OK;
     }
-    hipk_set_solve_path(handed, mid_loop ? mid_name : lds_loop ? "hipk_bi_solve_lds_kernel" : "launch sequence");
+    hipk_set_solve_path(handed, mid_loop ? mid->name : lds_loop ? "hipk_bi_solve_lds_kernel" : "launch sequence");
     if (mid_loop) lds_loop = true;   // finished in the one-launch loop
     for (; !lds_loop && it < maxiter; ++it) {
         HIPK_CHECK_HIP(pace.gate(it, stream, &stop));

@@ -686,7 +686,7 @@ struct hipk_cg_lds_args {
     int64_t it0;         // iterations done before this launch
     int64_t maxiter;
     int64_t max_its;     // iteration budget of one launch
-    int test_not_resident;   // tests (HIPK_TEST_LDS_NOT_RESIDENT): report the placement check as failed
+    int test_not_resident;   // tests (hipk_test_fail_launch): report the placement check as failed
     int spread;              // more than 64 workgroups: one per block all over the chip (then LOCAL = false)
 };
 static constexpr int kCgRowRegs = 12;
@@ -937,18 +937,120 @@ extern "C" size_t hipk_cg_work_bytes(int64_t n, int dtype) {
     return 256 + hipk_scratch_bytes() + 3 * vec + (mid ? (ll - vec) + kMidSlotBytes : 0);
 }
 
-// the name of a one-launch instantiation the dispatch sites below select (hipk_last_solve_path): by its address, so that the
-// name is the kernel that was launched
+// the one-launch instantiations the dispatch sites below select (hipk_mid_pick), each with the name hipk_last_solve_path reports.
+// Two chunks per workgroup put four rows on a thread: at most 7 entries each in registers
+#define HIPK_MID_ROW(W, NCH, PRE)                                                                                          \
+    {W, NCH, PRE, hipk_cg_mid_kernel<T, W, NCH, PRE>,                                                                      \
+     sizeof(T) == 8 ? "hipk_cg_mid_kernel<double," #W "," #NCH "," #PRE ">" : "hipk_cg_mid_kernel<float," #W "," #NCH "," #PRE ">"}
 template <typename T>
-static const char *hipk_cg_mid_name(void (*k)(hipk_cg_mid_args)) {
-#define HIPK_MID_NAME(W, NCH, PRE)                                                                                         \
-    if (k == hipk_cg_mid_kernel<T, W, NCH, PRE>)                                                                       \
-        return sizeof(T) == 8 ? "hipk_cg_mid_kernel<double," #W "," #NCH "," #PRE ">" : "hipk_cg_mid_kernel<float," #W "," #NCH "," #PRE ">";
-    HIPK_MID_NAME(5, 1, false) HIPK_MID_NAME(7, 1, false) HIPK_MID_NAME(9, 1, false) HIPK_MID_NAME(12, 1, false)
-    HIPK_MID_NAME(5, 2, false) HIPK_MID_NAME(7, 2, false)
-    HIPK_MID_NAME(5, 1, true) HIPK_MID_NAME(7, 1, true) HIPK_MID_NAME(9, 1, true) HIPK_MID_NAME(12, 1, true)
-#undef HIPK_MID_NAME
-    return "hipk_cg_mid_kernel<?>";
+static const hipk_mid_entry<hipk_cg_mid_args> hipk_cg_mid_table[] = {
+    HIPK_MID_ROW(5, 1, false), HIPK_MID_ROW(7, 1, false), HIPK_MID_ROW(9, 1, false), HIPK_MID_ROW(12, 1, false),
+    HIPK_MID_ROW(5, 2, false), HIPK_MID_ROW(7, 2, false),
+    HIPK_MID_ROW(5, 1, true),  HIPK_MID_ROW(7, 1, true),  HIPK_MID_ROW(9, 1, true),  HIPK_MID_ROW(12, 1, true)};
+#undef HIPK_MID_ROW
+static constexpr int kPcgMidMaxChunks = 256;                                 // one chunk per workgroup, one workgroup per CU
+static constexpr size_t kPcgMidSlotBytes = 3 * (size_t)kMidMaxChunks * 256;   // <p,Ap>, <r,r>, <r,z> slot arrays
+// {redo, it_done, stop_it} of a host copy of hipk_cg_scal / hipk_pcg_scal (hipk_resident_run)
+template <typename S>
+static hipk_loop_state hipk_cg_loop_state(const S &h) {
+    return {h.ctl.redo, h.ctl.it_done, h.stop_it};
+}
+
+// launch-bound mid-size systems: the whole CG loop (PRE: Jacobi PCG, M = diag(dinv)) in one launch, mid's kernel on workgroups of
+// mid->nch chunks, from iteration `it` -- HIPK_OK, HIPK_HANDED_BACK or an error (hipk_resident_run).  plan, lds: hipk_mid_eligible's;
+// r travels as flagged words in Ap + the vector behind it, the chunk-partial slots follow (hipk_cg_work_bytes, hipk_pcg_work_bytes)
+template <typename T, bool PRE, typename S>
+static int hipk_cg_mid_loop(hipk_csr_s *A, S *scal, const hipk_mid_entry<hipk_cg_mid_args> *mid, const hipk_mid_plan &plan, size_t lds,
+                            T *x, T *r, T *p, T *Ap, const T *dinv, const double *rz0_parts, int64_t &it, int64_t maxiter, bool &failed,
+                            char (&handed)[128], const char *entry, hipStream_t stream) {
+    const int g = A->geom.g, grid = (g + mid->nch - 1) / mid->nch;
+    const size_t ll_bytes = hipk_align_up((size_t)A->n_rows * 16, 256);   // r as 16-byte flagged words
+    hipk_cg_mid_args ca;
+    memset(&ca, 0, sizeof(ca));
+    ca.n = A->n_rows;
+    ca.g = g;
+    ca.win = plan.max_slots * HIPK_TILE;
+    ca.plan = plan;
+    ca.crow = A->crow;
+    ca.col = A->col;
+    ca.val = A->val;
+    ca.x = x;
+    ca.r = r;
+    ca.p = p;
+    ca.r_ll = (unsigned long long *)Ap;                          // Ap + the fourth vector: 2 x vec >= 16 n bytes
+    ca.pap_ll = (unsigned long long *)((char *)Ap + ll_bytes);    // behind the flagged words of r
+    ca.rr_ll = ca.pap_ll + (size_t)kMidMaxChunks * 256 / 8;
+    if (PRE) ca.rz_ll = ca.rr_ll + (size_t)kMidMaxChunks * 256 / 8;
+    ca.dinv = dinv;
+    ca.rz0_parts = rz0_parts;
+    // a 256-byte line per chunk partial: every workgroup polls every slot, and packed slots are ONE memory channel's hot spot (same
+    // box, CG, us per iteration, 256 B / 16 B per slot: 5.1 / 5.8 at 79 chunks, 5.4 / 6.6 at 123, 6.8 / 8.2 at 254; 64 B from 257
+    // chunks: 9.65 / 9.95 at 489; 16 B up to 32 chunks: 5.05 / 5.3 at 20) -- HIPK_CG_MID_STRIDE forces (CG)
+    const char *stride = PRE ? nullptr : getenv("HIPK_CG_MID_STRIDE");
+    ca.slot_stride = stride ? atoi(stride) : g <= 32 ? 1 : g <= 256 ? 16 : 4;
+    if (ca.slot_stride < 1 || ca.slot_stride > 16) ca.slot_stride = 16;
+    ca.xcd_aware = PRE || !(getenv("HIPK_CG_MID_XCD") && getenv("HIPK_CG_MID_XCD")[0] == '0');
+    ca.ctl = &scal->ctl;
+    ca.gamma = scal->gamma;
+    ca.atol2 = &scal->atol2;
+    ca.stop_it = &scal->stop_it;
+    ca.maxiter = maxiter;
+    ca.max_its = hipk_env_its("HIPK_CG_LAUNCH_ITS", 16384);
+    auto launch = [&](int64_t it0, int test_not_resident, bool) -> int {
+        ca.it0 = it0;
+        ca.test_not_resident = test_not_resident;
+        HIPK_CHECK_HIP(hipMemsetAsync(ca.r_ll, 0, ll_bytes, stream));
+        HIPK_CHECK_HIP(hipMemsetAsync(ca.pap_ll, 0, PRE ? kPcgMidSlotBytes : kMidSlotBytes, stream));
+        HIPK_CHECK_HIP(hipMemsetAsync(&scal->ctl, 0, sizeof(hipk_lds_ctl), stream));
+        mid->kern<<<hipk_xcd_grid(grid), 1024, lds, stream>>>(ca);   // hipk_xcd_chunk: padded to a multiple of 8
+        return HIPK_OK;
+    };
+    return hipk_resident_run(stream, scal, launch, hipk_cg_loop_state<S>, it, maxiter, nullptr, failed, handed, mid->name, entry);
+}
+
+// launch-bound systems with short rows: the whole CG loop (PRE: Jacobi PCG, M = diag(dinv)) in one launch, hipk_cg_solve_lds_kernel,
+// from iteration `it` -- HIPK_OK, HIPK_HANDED_BACK or an error (hipk_resident_run).  scal: hipk_cg_scal / hipk_pcg_scal; rr_sub,
+// rz_sub: the kernel's sub-partial scratch; flags: 2 x kHoMaxWg hand-off words; failed: the caller's latch
+template <typename T, bool PRE, typename S>
+static int hipk_cg_lds_loop(hipk_csr_s *A, S *scal, T *x, T *r, T *p, T *Ap, const T *dinv, const double *rz0_parts, double *rz_sub,
+                            double *rr_sub, unsigned long long *flags, bool spread, int64_t &it, int64_t maxiter, bool &failed,
+                            char (&handed)[128], const char *entry, hipStream_t stream) {
+    bool local = !spread && !getenv("HIPK_CG_LOOP_AGENT");   // a -2 (spread over several XCDs): agent-scope hand-offs
+    const int g = A->geom.g, lgrid = spread ? kGmSub * g : 8 * kGmSub * g;
+    hipk_cg_lds_args<T> ca;
+    ca.n = A->n_rows;
+    ca.g = g;
+    ca.crow = A->crow;
+    ca.col = A->col;
+    ca.val = (const T *)A->val;
+    ca.x = x;
+    ca.r = r;
+    ca.p = p;
+    ca.Ap = Ap;
+    ca.ctl = &scal->ctl;
+    ca.gamma = scal->gamma;
+    ca.atol2 = &scal->atol2;
+    ca.stop_it = &scal->stop_it;
+    ca.dinv = dinv;
+    ca.rz0_parts = rz0_parts;
+    ca.rz_sub = rz_sub;
+    ca.tile_pp = A->tile_part;
+    ca.rr_sub = rr_sub;
+    ca.flag_a = flags;
+    ca.flag_b = ca.flag_a + kHoMaxWg;
+    ca.spread = spread ? 1 : 0;
+    ca.maxiter = maxiter;
+    ca.max_its = hipk_env_its("HIPK_CG_LAUNCH_ITS", 16384);
+    auto launch = [&](int64_t it0, int test_not_resident, bool loc) -> int {
+        ca.it0 = it0;
+        ca.test_not_resident = test_not_resident;
+        HIPK_CHECK_HIP(hipMemsetAsync(ca.flag_a, 0, 2 * kHoMaxWg * sizeof(unsigned long long), stream));
+        HIPK_CHECK_HIP(hipMemsetAsync(&scal->ctl, 0, sizeof(hipk_lds_ctl), stream));
+        (loc ? hipk_cg_solve_lds_kernel<T, true, PRE> : hipk_cg_solve_lds_kernel<T, false, PRE>)<<<lgrid, HIPK_THREADS, 0, stream>>>(ca);
+        return HIPK_OK;
+    };
+    return hipk_resident_run(stream, scal, launch, hipk_cg_loop_state<S>, it, maxiter, &local, failed, handed, "hipk_cg_solve_lds_kernel",
+                             entry);
 }
 
 template <typename T>
@@ -969,7 +1071,6 @@ static int hipk_cg_solve_t(hipk_csr_s *A, const T *b, T *x, char *work, const hi
     const int64_t maxiter = (prm->maxiter < 0) ? 10 * n : prm->maxiter;  // TSL:982-984
     hipk_set_solve_path(nullptr, "");
     char handed[128] = "";   // the one-launch loops that handed this solve back
-    const char *mid_name = "";
     // torch.square(torch.tensor(tol)): python floats become fp32 tensors (TSL:816-817)
     const float tolf = (float)prm->tol, atolf = (float)prm->atol;
     const double tol2 = (double)(tolf * tolf), atol_sq = (double)(atolf * atolf);
@@ -1036,95 +1137,21 @@ static int hipk_cg_solve_t(hipk_csr_s *A, const T *b, T *x, char *work, const hi
     // one launch, one workgroup per chunk or pair of chunks (hipk_cg_mid.h); HIPK_CG_MID=0 leaves them to the paths below.
     // (At 9 .. 32 chunks it replaces the eight-workgroups-per-chunk kernel below: 5.0 against 10.7 us per iteration at n = 40 000.)
     static bool mid_failed = false;
-    bool mid_loop = false;
-    {
-        mid_loop = it == 0 && gm.g > kMidMinChunks && gm.g <= kMidMaxChunks && gm.ch == HIPK_BASE_CHUNK && A->op_cb == nullptr &&
-                   A->crow != nullptr && A->max_row_len <= 12 && prm->profile == 0 && maxiter > 0 && !mid_failed &&
-                   !(getenv("HIPK_CG_MID") && getenv("HIPK_CG_MID")[0] == '0') && !getenv("HIPK_CG_NO_LDS_LOOP") && !getenv("HIPK_CG_NO_SMALL");
-        // one workgroup of 1024 threads per CU; a chunk each up to n_cu chunks, two each beyond
-        const int nch = gm.g <= A->n_cu ? 1 : 2;
-        void (*mid_kern)(hipk_cg_mid_args) =
-            nch == 1 ? (A->max_row_len <= 5   ? hipk_cg_mid_kernel<T, 5, 1>
-                        : A->max_row_len <= 7 ? hipk_cg_mid_kernel<T, 7, 1>
-                        : A->max_row_len <= 9 ? hipk_cg_mid_kernel<T, 9, 1>
-                                              : hipk_cg_mid_kernel<T, 12, 1>)
-                     : (A->max_row_len <= 5 ? hipk_cg_mid_kernel<T, 5, 2> : hipk_cg_mid_kernel<T, 7, 2>);
-        mid_name = hipk_cg_mid_name<T>(mid_kern);
-        const int mid_threads = 1024, mid_grid = (gm.g + nch - 1) / nch;
-        if (nch == 2 && A->max_row_len > 7) mid_loop = false;   // four rows per thread: at most 7 entries each in registers
-        size_t lds = 0;
-        hipk_mid_plan plan;
-        memset(&plan, 0, sizeof(plan));
-        if (mid_loop) {
-            // once per handle: the 256-column tiles each workgroup's window holds (hipk_mid.h); not for matrices whose rows reach
-            // further than the plan's range, or whose windows do not fit the LDS
-            mid_loop = hipk_mid_plan_get(A, nch, stream, &plan);
-            lds = mid_loop ? hipk_cg_mid_lds_bytes(plan.max_slots * HIPK_TILE, nch, false, sizeof(T)) : 0;
-            int occ = 0;
-            mid_loop = mid_loop && plan.max_slots <= kMidPlanSlots && lds <= (size_t)160 * 1024 &&
-                       hipFuncSetAttribute((const void *)mid_kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess &&
-                       hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, mid_kern, mid_threads, lds) == hipSuccess &&
-                       (int64_t)occ * A->n_cu >= mid_grid;
-            (void)hipGetLastError();
-        }
-        if (mid_loop) {
-            const size_t vec8 = hipk_align_up((size_t)n * 16, 256) / 2;   // half of the flagged words' 16 n bytes
-            const char *e = getenv("HIPK_CG_LAUNCH_ITS");
-            hipk_cg_mid_args ca;
-            memset(&ca, 0, sizeof(ca));
-            ca.n = n;
-            ca.g = gm.g;
-            ca.win = plan.max_slots * HIPK_TILE;
-            ca.plan = plan;
-            ca.crow = A->crow;
-            ca.col = A->col;
-            ca.val = A->val;
-            ca.x = x;
-            ca.r = r;
-            ca.p = p;
-            ca.r_ll = (unsigned long long *)Ap;      // Ap + the fourth vector: 2 x vec >= 16 n bytes
-            ca.pap_ll = (unsigned long long *)((char *)Ap + 2 * vec8);   // behind the four vectors (hipk_cg_work_bytes)
-            ca.rr_ll = ca.pap_ll + kMidSlotBytes / 16;
-            // a 256-byte line per chunk partial: every workgroup polls every slot, and packed slots are ONE memory channel's
-            // hot spot (same box, us per iteration, 256 B / 16 B per slot: 5.1 / 5.8 at 79 chunks, 5.4 / 6.6 at 123, 6.8 / 8.2 at
-            // 254; 64 B from 257 chunks: 9.65 / 9.95 at 489; 16 B up to 32 chunks: 5.05 / 5.3 at 20) -- HIPK_CG_MID_STRIDE forces
-            ca.slot_stride = getenv("HIPK_CG_MID_STRIDE") ? atoi(getenv("HIPK_CG_MID_STRIDE")) : gm.g <= 32 ? 1 : gm.g <= 256 ? 16 : 4;
-            if (ca.slot_stride < 1 || ca.slot_stride > 16) ca.slot_stride = 16;
-            ca.ctl = &scal->ctl;
-            ca.gamma = scal->gamma;
-            ca.atol2 = &scal->atol2;
-            ca.stop_it = &scal->stop_it;
-            ca.maxiter = maxiter;
-            ca.xcd_aware = !(getenv("HIPK_CG_MID_XCD") && getenv("HIPK_CG_MID_XCD")[0] == '0');
-            ca.max_its = e ? atoll(e) : 16384;
-            if (ca.max_its < 1) ca.max_its = 1;
-            const int fail_launch = getenv("HIPK_TEST_LDS_NOT_RESIDENT") ? (atoi(getenv("HIPK_TEST_LDS_NOT_RESIDENT")) > 1 ? atoi(getenv("HIPK_TEST_LDS_NOT_RESIDENT")) : 1) : 0;
-            int launch_no = 0;
-            hipk_cg_scal hs0;
-            for (;;) {
-                ca.it0 = it;
-                ca.test_not_resident = (++launch_no == fail_launch) ? 1 : 0;
-                HIPK_CHECK_HIP(hipMemsetAsync(ca.r_ll, 0, 2 * vec8, stream));
-                HIPK_CHECK_HIP(hipMemsetAsync(ca.pap_ll, 0, kMidSlotBytes, stream));
-                HIPK_CHECK_HIP(hipMemsetAsync(&scal->ctl, 0, sizeof(hipk_lds_ctl), stream));
-                mid_kern<<<hipk_xcd_grid(mid_grid), mid_threads, lds, stream>>>(ca);   // hipk_xcd_chunk: padded to a multiple of 8
-                HIPK_CHECK_HIP(hipGetLastError());
-                HIPK_CHECK_HIP(hipMemcpyAsync(&hs0, scal, sizeof(hs0), hipMemcpyDeviceToHost, stream));
-                HIPK_CHECK_HIP(hipStreamSynchronize(stream));
-                if (hs0.ctl.redo < 0) {
-                    if (hs0.ctl.redo == -3) {
-                        hipk_set_error("hipk_cg_solve: a resident workgroup of the one-launch loop stopped arriving");
-                        return HIPK_ERR_HIP;
-                    }
-                    if (!getenv("HIPK_TEST_LDS_NOT_RESIDENT")) mid_failed = true;   // not co-resident; nothing was modified
-                    hipk_path_add(handed, mid_name);
-                    mid_loop = false;
-                    break;
-                }
-                it = hs0.ctl.it_done;
-                if (hs0.stop_it <= it || it >= maxiter) break;
-            }
-        }
+    // one workgroup of 1024 threads per CU; a chunk each up to n_cu chunks, two each beyond
+    const int nch = gm.g <= A->n_cu ? 1 : 2;
+    const hipk_mid_entry<hipk_cg_mid_args> *mid = hipk_mid_pick(hipk_cg_mid_table<T>, A->max_row_len, nch, false);
+    auto mid_lds = [&](int slots) { return hipk_cg_mid_lds_bytes(slots * HIPK_TILE, nch, false, sizeof(T)); };
+    hipk_mid_plan plan;
+    size_t lds = 0;
+    bool mid_loop = it == 0 && gm.g > kMidMinChunks && gm.g <= kMidMaxChunks && gm.ch == HIPK_BASE_CHUNK && A->op_cb == nullptr &&
+                    A->crow != nullptr && A->max_row_len <= 12 && prm->profile == 0 && maxiter > 0 && !mid_failed &&
+                    !(getenv("HIPK_CG_MID") && getenv("HIPK_CG_MID")[0] == '0') && !getenv("HIPK_CG_NO_LDS_LOOP") && !getenv("HIPK_CG_NO_SMALL") &&
+                    mid && hipk_mid_eligible(A, mid, (gm.g + nch - 1) / nch, mid_lds, stream, &plan, &lds);
+    if (mid_loop) {
+        const int run = hipk_cg_mid_loop<T, false>(A, scal, mid, plan, lds, x, r, p, Ap, nullptr, nullptr, it, maxiter, mid_failed, handed,
+                                                   "hipk_cg_solve", stream);
+        if (run < 0) return run;
+        mid_loop = run == HIPK_OK;
     }
     // launch-bound systems with short rows: the whole loop in one launch (hipk_cg_solve_lds_kernel), bounded iterations per launch
     static bool lds_loop_failed = false;   // its workgroups once failed to meet (a shared device): do not wait for that verdict again
@@ -1135,70 +1162,13 @@ static int hipk_cg_solve_t(hipk_csr_s *A, const T *b, T *x, char *work, const hi
     bool lds_loop = gm.g <= 32 && !getenv("HIPK_CG_NO_SMALL") && gm.ch == HIPK_BASE_CHUNK && A->max_row_len <= kCgRowRegs &&
                     prm->profile == 0 && maxiter > 0 && kGmSub * gm.g <= (lds_spread ? 2 * A->n_cu : 2 * (A->n_cu / 8)) &&
                     !lds_loop_failed && !getenv("HIPK_CG_NO_LDS_LOOP") && !(lds_spread && getenv("HIPK_NO_LDS_SPREAD")) && !mid_loop;
-    if (lds_loop) {
-        bool local = !lds_spread && !getenv("HIPK_CG_LOOP_AGENT");
-        const char *e = getenv("HIPK_CG_LAUNCH_ITS");
-        hipk_cg_lds_args<T> ca;
-        ca.n = n;
-        ca.g = gm.g;
-        ca.crow = A->crow;
-        ca.col = A->col;
-        ca.val = (const T *)A->val;
-        ca.x = x;
-        ca.r = r;
-        ca.p = p;
-        ca.Ap = Ap;
-        ca.ctl = &scal->ctl;
-        ca.gamma = scal->gamma;
-        ca.atol2 = &scal->atol2;
-        ca.stop_it = &scal->stop_it;
-        ca.dinv = nullptr;
-        ca.rz0_parts = nullptr;
-        ca.rz_sub = nullptr;
-        ca.tile_pp = A->tile_part;
-        ca.rr_sub = part_b;
-        ca.flag_a = (unsigned long long *)(part_c + 1024);   // 2 x 512 words
-        ca.flag_b = ca.flag_a + kHoMaxWg;
-        ca.spread = lds_spread ? 1 : 0;
-        const int lgrid = lds_spread ? kGmSub * gm.g : 8 * kGmSub * gm.g;
-        ca.maxiter = maxiter;
-        ca.max_its = e ? atoll(e) : 16384;
-        if (ca.max_its < 1) ca.max_its = 1;
-        // tests: HIPK_TEST_LDS_NOT_RESIDENT=k makes the k-th launch of this solve report its workgroups as not co-resident
-        const int fail_launch = getenv("HIPK_TEST_LDS_NOT_RESIDENT") ? (atoi(getenv("HIPK_TEST_LDS_NOT_RESIDENT")) > 1 ? atoi(getenv("HIPK_TEST_LDS_NOT_RESIDENT")) : 1) : 0;
-        int launch_no = 0;
-        hipk_cg_scal hs0;
-        for (;;) {
-            ca.it0 = it;
-            ca.test_not_resident = (++launch_no == fail_launch) ? 1 : 0;
-            HIPK_CHECK_HIP(hipMemsetAsync(ca.flag_a, 0, 2 * kHoMaxWg * sizeof(unsigned long long), stream));
-            HIPK_CHECK_HIP(hipMemsetAsync(&scal->ctl, 0, sizeof(hipk_lds_ctl), stream));
-            if (local)
-                hipk_cg_solve_lds_kernel<T, true, false><<<lgrid, HIPK_THREADS, 0, stream>>>(ca);
-            else
-                hipk_cg_solve_lds_kernel<T, false, false><<<lgrid, HIPK_THREADS, 0, stream>>>(ca);
-            HIPK_CHECK_HIP(hipGetLastError());
-            HIPK_CHECK_HIP(hipMemcpyAsync(&hs0, scal, sizeof(hs0), hipMemcpyDeviceToHost, stream));
-            HIPK_CHECK_HIP(hipStreamSynchronize(stream));
-            if (hs0.ctl.redo < 0) {
-                if (hs0.ctl.redo == -3) {
-                    hipk_set_error("hipk_cg_solve: a resident workgroup of the one-launch loop stopped arriving");
-                    return HIPK_ERR_HIP;
-                }
-                if (hs0.ctl.redo == -2 && local) {   // spread over several XCDs: agent-scope hand-offs
-                    local = false;
-                    continue;
-                }
-                if (!getenv("HIPK_TEST_LDS_NOT_RESIDENT")) lds_loop_failed = true;   // not co-resident; nothing was modified: the launch sequence below takes over
-                hipk_path_add(handed, "hipk_cg_solve_lds_kernel");
-                lds_loop = false;
-                break;
-            }
-            it = hs0.ctl.it_done;
-            if (hs0.stop_it <= it || it >= maxiter) break;
-        }
+    if (lds_loop) {   // a hand-back (not co-resident; nothing was modified): the launch sequence below takes over
+        const int run = hipk_cg_lds_loop<T, false>(A, scal, x, r, p, Ap, nullptr, nullptr, nullptr, part_b, (unsigned long long *)(part_c + 1024),
+                                                   lds_spread, it, maxiter, lds_loop_failed, handed, "hipk_cg_solve", stream);
+        if (run < 0) return run;
+        lds_loop = run == HIPK_OK;
     }
-    hipk_set_solve_path(handed, mid_loop ? mid_name : lds_loop ? "hipk_cg_solve_lds_kernel" : "launch sequence");
+    hipk_set_solve_path(handed, mid_loop ? mid->name : lds_loop ? "hipk_cg_solve_lds_kernel" : "launch sequence");
     if (mid_loop) lds_loop = true;   // finished in the one-launch loop: none of the launch sequences below runs
     // launch-bound mid-size systems: TWO launches per iteration (hipk_cg2_spmv_kernel / hipk_cg2_update_kernel above)
     constexpr int kCap2 = sizeof(T) == 8 ? 1280 : 2048;
@@ -1536,8 +1506,6 @@ extern "C" int hipk_cgm_direction(int64_t n_local, int chunk_rows, int g_red, vo
 // (16 n more than plain CG: dinv is read by both vector kernels).  Mirrored by orc_pcg_jacobi.
 //   partial slots: a <p,Ap> | b <r,r> | c spare dot of the SpMV | z0, z1 <r,z> ping-pong (read by all workgroups
 //   of the update kernel while the early ones already write the next one) | d <b,b> / <x,x>
-static constexpr int kPcgMidMaxChunks = 256;                                 // one chunk per workgroup, one workgroup per CU
-static constexpr size_t kPcgMidSlotBytes = 3 * (size_t)kMidMaxChunks * 256;   // <p,Ap>, <r,r>, <r,z> slot arrays
 struct hipk_pcg_scal {
     double atol2, bs, res2, xx, rs_last;
     int64_t stop_it;
@@ -1729,7 +1697,6 @@ static int hipk_pcg_solve_t(hipk_csr_s *A, const T *dinv, const T *b, T *x, char
     const int64_t check = prm->check_every > 0 ? prm->check_every : 64;
     hipk_set_solve_path(nullptr, "");
     char handed[128] = "";   // the one-launch loops that handed this solve back
-    const char *mid_name = "";
 
     hipk_event_pair whole;
     HIPK_CHECK_HIP(whole.create());
@@ -1775,89 +1742,23 @@ static int hipk_pcg_solve_t(hipk_csr_s *A, const T *dinv, const T *b, T *x, char
     // launch-bound systems of 9 .. 256 chunks (fp64, rows of <= 12 entries within a window around their chunk): the whole loop in one
     // launch, one workgroup per chunk (hipk_cg_mid_kernel<W, 1, PRE = true>); HIPK_CG_MID=0 leaves them to the paths below
     static bool mid_failed = false;
-    bool mid_loop = false;
-    {
-        mid_loop = gm.g > kMidMinChunks && gm.g <= kPcgMidMaxChunks && gm.g <= A->n_cu && gm.ch == HIPK_BASE_CHUNK && A->op_cb == nullptr &&
-                   A->crow != nullptr && A->max_row_len <= 12 && prm->profile == 0 && maxiter > 0 && !mid_failed &&
-                   !(getenv("HIPK_CG_MID") && getenv("HIPK_CG_MID")[0] == '0') && !getenv("HIPK_CG_NO_LDS_LOOP") && !getenv("HIPK_CG_NO_SMALL");
-        void (*mid_kern)(hipk_cg_mid_args) = A->max_row_len <= 5   ? hipk_cg_mid_kernel<T, 5, 1, true>
-                                             : A->max_row_len <= 7 ? hipk_cg_mid_kernel<T, 7, 1, true>
-                                             : A->max_row_len <= 9 ? hipk_cg_mid_kernel<T, 9, 1, true>
-                                                                   : hipk_cg_mid_kernel<T, 12, 1, true>;
-        mid_name = hipk_cg_mid_name<T>(mid_kern);
-        size_t lds = 0;
-        hipk_mid_plan plan;
-        memset(&plan, 0, sizeof(plan));
-        if (mid_loop) {
-            mid_loop = hipk_mid_plan_get(A, 1, stream, &plan);   // the tiles each workgroup's window holds (hipk_mid.h)
-            lds = mid_loop ? hipk_cg_mid_lds_bytes(plan.max_slots * HIPK_TILE, 1, true, sizeof(T)) : 0;
-            int occ = 0;
-            mid_loop = mid_loop && plan.max_slots <= kMidPlanSlots && lds <= (size_t)160 * 1024 &&
-                       hipFuncSetAttribute((const void *)mid_kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess &&
-                       hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, mid_kern, 1024, lds) == hipSuccess && (int64_t)occ * A->n_cu >= gm.g;
-            (void)hipGetLastError();
+    const hipk_mid_entry<hipk_cg_mid_args> *mid = hipk_mid_pick(hipk_cg_mid_table<T>, A->max_row_len, 1, true);
+    auto mid_lds = [](int slots) { return hipk_cg_mid_lds_bytes(slots * HIPK_TILE, 1, true, sizeof(T)); };
+    hipk_mid_plan plan;
+    size_t lds = 0;
+    bool mid_loop = gm.g > kMidMinChunks && gm.g <= kPcgMidMaxChunks && gm.g <= A->n_cu && gm.ch == HIPK_BASE_CHUNK && A->op_cb == nullptr &&
+                    A->crow != nullptr && A->max_row_len <= 12 && prm->profile == 0 && maxiter > 0 && !mid_failed &&
+                    !(getenv("HIPK_CG_MID") && getenv("HIPK_CG_MID")[0] == '0') && !getenv("HIPK_CG_NO_LDS_LOOP") && !getenv("HIPK_CG_NO_SMALL") &&
+                    mid && hipk_mid_eligible(A, mid, gm.g, mid_lds, stream, &plan, &lds);
+    if (mid_loop) {
+        const int run = hipk_cg_mid_loop<T, true>(A, scal, mid, plan, lds, x, r, p, Ap, dinv, part_z[0], it, maxiter, mid_failed, handed,
+                                                  "hipk_pcg_solve", stream);
+        if (run < 0) return run;
+        if (run == HIPK_HANDED_BACK && it > 0) {   // as below: <r,z> lives in scal->gamma[it & 1]; the launch sequence folds it from part_z[it & 1]
+            HIPK_CHECK_HIP(hipMemsetAsync(part_z[it & 1], 0, (size_t)gm.g * sizeof(double), stream));
+            HIPK_CHECK_HIP(hipMemcpyAsync(part_z[it & 1], &scal->gamma[it & 1], sizeof(double), hipMemcpyDeviceToDevice, stream));
         }
-        if (mid_loop) {
-            const char *e = getenv("HIPK_CG_LAUNCH_ITS");
-            hipk_cg_mid_args ca;
-            memset(&ca, 0, sizeof(ca));
-            ca.n = n;
-            ca.g = gm.g;
-            ca.win = plan.max_slots * HIPK_TILE;
-            ca.plan = plan;
-            ca.crow = A->crow;
-            ca.col = A->col;
-            ca.val = A->val;
-            ca.x = x;
-            ca.r = r;
-            ca.p = p;
-            ca.r_ll = (unsigned long long *)Ap;                          // Ap + the fourth vector: 2 x vec >= 16 n bytes
-            const size_t ll_bytes = hipk_align_up((size_t)n * 16, 256);
-            ca.pap_ll = (unsigned long long *)((char *)Ap + ll_bytes);    // behind the flagged words of r (hipk_pcg_work_bytes)
-            ca.rr_ll = ca.pap_ll + (size_t)kMidMaxChunks * 256 / 8;
-            ca.rz_ll = ca.rr_ll + (size_t)kMidMaxChunks * 256 / 8;
-            ca.dinv = dinv;
-            ca.rz0_parts = part_z[0];
-            ca.slot_stride = gm.g <= 32 ? 1 : 16;
-            ca.xcd_aware = 1;
-            ca.ctl = &scal->ctl;
-            ca.gamma = scal->gamma;
-            ca.atol2 = &scal->atol2;
-            ca.stop_it = &scal->stop_it;
-            ca.maxiter = maxiter;
-            ca.max_its = e ? atoll(e) : 16384;
-            if (ca.max_its < 1) ca.max_its = 1;
-            const int fail_launch = getenv("HIPK_TEST_LDS_NOT_RESIDENT") ? (atoi(getenv("HIPK_TEST_LDS_NOT_RESIDENT")) > 1 ? atoi(getenv("HIPK_TEST_LDS_NOT_RESIDENT")) : 1) : 0;
-            int launch_no = 0;
-            hipk_pcg_scal hs0;
-            for (;;) {
-                ca.it0 = it;
-                ca.test_not_resident = (++launch_no == fail_launch) ? 1 : 0;
-                HIPK_CHECK_HIP(hipMemsetAsync(ca.r_ll, 0, ll_bytes, stream));
-                HIPK_CHECK_HIP(hipMemsetAsync(ca.pap_ll, 0, kPcgMidSlotBytes, stream));
-                HIPK_CHECK_HIP(hipMemsetAsync(&scal->ctl, 0, sizeof(hipk_lds_ctl), stream));
-                mid_kern<<<hipk_xcd_grid(gm.g), 1024, lds, stream>>>(ca);
-                HIPK_CHECK_HIP(hipGetLastError());
-                HIPK_CHECK_HIP(hipMemcpyAsync(&hs0, scal, sizeof(hs0), hipMemcpyDeviceToHost, stream));
-                HIPK_CHECK_HIP(hipStreamSynchronize(stream));
-                if (hs0.ctl.redo < 0) {
-                    if (hs0.ctl.redo == -3) {
-                        hipk_set_error("hipk_pcg_solve: a resident workgroup of the one-launch loop stopped arriving");
-                        return HIPK_ERR_HIP;
-                    }
-                    if (!getenv("HIPK_TEST_LDS_NOT_RESIDENT")) mid_failed = true;   // this launch modified nothing
-                    hipk_path_add(handed, mid_name);
-                    if (it > 0) {   // as below: <r,z> lives in scal->gamma[it & 1]; the launch sequence folds it from part_z[it & 1]
-                        HIPK_CHECK_HIP(hipMemsetAsync(part_z[it & 1], 0, (size_t)gm.g * sizeof(double), stream));
-                        HIPK_CHECK_HIP(hipMemcpyAsync(part_z[it & 1], &scal->gamma[it & 1], sizeof(double), hipMemcpyDeviceToDevice, stream));
-                    }
-                    mid_loop = false;
-                    break;
-                }
-                it = hs0.ctl.it_done;
-                if (hs0.stop_it <= it || it >= maxiter) break;
-            }
-        }
+        mid_loop = run == HIPK_OK;
     }
     // launch-bound systems with short rows: the whole loop in one launch (hipk_cg_solve_lds_kernel<.., PRE = true>)
     static bool lds_loop_failed = false;
@@ -1865,77 +1766,20 @@ static int hipk_pcg_solve_t(hipk_csr_s *A, const T *dinv, const T *b, T *x, char
     bool lds_loop = gm.g <= 32 && gm.ch == HIPK_BASE_CHUNK && A->max_row_len <= kCgRowRegs && prm->profile == 0 && maxiter > 0 &&
                     kGmSub * gm.g <= (lds_spread ? 2 * A->n_cu : 2 * (A->n_cu / 8)) && !lds_loop_failed &&
                     !getenv("HIPK_CG_NO_SMALL") && !getenv("HIPK_CG_NO_LDS_LOOP") && !(lds_spread && getenv("HIPK_NO_LDS_SPREAD")) && !mid_loop;
-    if (lds_loop) {
-        bool local = !lds_spread && !getenv("HIPK_CG_LOOP_AGENT");
-        const char *e = getenv("HIPK_CG_LAUNCH_ITS");
-        hipk_cg_lds_args<T> ca;
-        ca.n = n;
-        ca.g = gm.g;
-        ca.crow = A->crow;
-        ca.col = A->col;
-        ca.val = (const T *)A->val;
-        ca.x = x;
-        ca.r = r;
-        ca.p = p;
-        ca.Ap = Ap;
-        ca.ctl = &scal->ctl;
-        ca.gamma = scal->gamma;
-        ca.atol2 = &scal->atol2;
-        ca.stop_it = &scal->stop_it;
-        ca.dinv = dinv;
-        ca.rz0_parts = part_z[0];
-        ca.rz_sub = part_z[1];
-        ca.tile_pp = A->tile_part;
-        ca.rr_sub = part_b;
-        ca.flag_a = (unsigned long long *)(part_c + 1024);   // 2 x 512 words
-        ca.flag_b = ca.flag_a + kHoMaxWg;
-        ca.spread = lds_spread ? 1 : 0;
-        ca.maxiter = maxiter;
-        ca.max_its = e ? atoll(e) : 16384;
-        if (ca.max_its < 1) ca.max_its = 1;
-        // tests: HIPK_TEST_LDS_NOT_RESIDENT=k makes the k-th launch of this solve report its workgroups as not co-resident
-        const int fail_launch = getenv("HIPK_TEST_LDS_NOT_RESIDENT") ? (atoi(getenv("HIPK_TEST_LDS_NOT_RESIDENT")) > 1 ? atoi(getenv("HIPK_TEST_LDS_NOT_RESIDENT")) : 1) : 0;
-        int launch_no = 0;
-        const int lgrid = lds_spread ? kGmSub * gm.g : 8 * kGmSub * gm.g;
-        hipk_pcg_scal hs0;
-        for (;;) {
-            ca.it0 = it;
-            ca.test_not_resident = (++launch_no == fail_launch) ? 1 : 0;
-            HIPK_CHECK_HIP(hipMemsetAsync(ca.flag_a, 0, 2 * kHoMaxWg * sizeof(unsigned long long), stream));
-            HIPK_CHECK_HIP(hipMemsetAsync(&scal->ctl, 0, sizeof(hipk_lds_ctl), stream));
-            if (local)
-                hipk_cg_solve_lds_kernel<T, true, true><<<lgrid, HIPK_THREADS, 0, stream>>>(ca);
-            else
-                hipk_cg_solve_lds_kernel<T, false, true><<<lgrid, HIPK_THREADS, 0, stream>>>(ca);
-            HIPK_CHECK_HIP(hipGetLastError());
-            HIPK_CHECK_HIP(hipMemcpyAsync(&hs0, scal, sizeof(hs0), hipMemcpyDeviceToHost, stream));
-            HIPK_CHECK_HIP(hipStreamSynchronize(stream));
-            if (hs0.ctl.redo < 0) {
-                if (hs0.ctl.redo == -3) {
-                    hipk_set_error("hipk_pcg_solve: a resident workgroup of the one-launch loop stopped arriving");
-                    return HIPK_ERR_HIP;
-                }
-                if (hs0.ctl.redo == -2 && local) {   // spread over several XCDs: agent-scope hand-offs
-                    local = false;
-                    continue;
-                }
-                if (!getenv("HIPK_TEST_LDS_NOT_RESIDENT")) lds_loop_failed = true;   // this launch modified nothing: the launch sequence below takes over
-                hipk_path_add(handed, "hipk_cg_solve_lds_kernel");
-                if (it > 0) {
-                    // ... from iteration `it` of an EARLIER launch: x, r, p are in memory, but <r,z> only as scal->gamma[it & 1]
-                    // (part_z[1] was the kernel's sub-partial scratch), while the launch sequence folds it from the chunk
-                    // partials part_z[it & 1].  Rebuild that slot as {gamma, 0, 0, ...}: the fold of it is gamma, bit for bit
-                    HIPK_CHECK_HIP(hipMemsetAsync(part_z[it & 1], 0, (size_t)gm.g * sizeof(double), stream));
-                    HIPK_CHECK_HIP(hipMemcpyAsync(part_z[it & 1], &scal->gamma[it & 1], sizeof(double), hipMemcpyDeviceToDevice, stream));
-                }
-                lds_loop = false;
-                break;
-            }
-            it = hs0.ctl.it_done;
-            if (hs0.stop_it <= it || it >= maxiter) break;
+    if (lds_loop) {   // a hand-back (this launch modified nothing): the launch sequence below takes over
+        const int run = hipk_cg_lds_loop<T, true>(A, scal, x, r, p, Ap, dinv, part_z[0], part_z[1], part_b, (unsigned long long *)(part_c + 1024),
+                                                  lds_spread, it, maxiter, lds_loop_failed, handed, "hipk_pcg_solve", stream);
+        if (run < 0) return run;
+        if (run == HIPK_HANDED_BACK && it > 0) {
+            // ... from iteration `it` of an EARLIER launch: x, r, p are in memory, but <r,z> only as scal->gamma[it & 1]
+            // (part_z[1] was the kernel's sub-partial scratch), while the launch sequence folds it from the chunk
+            // partials part_z[it & 1].  Rebuild that slot as {gamma, 0, 0, ...}: the fold of it is gamma, bit for bit
+            HIPK_CHECK_HIP(hipMemsetAsync(part_z[it & 1], 0, (size_t)gm.g * sizeof(double), stream));
+            HIPK_CHECK_HIP(hipMemcpyAsync(part_z[it & 1], &scal->gamma[it & 1], sizeof(double), hipMemcpyDeviceToDevice, stream));
         }
+        lds_loop = run == HIPK_OK;
     }
-    hipk_set_solve_path(handed, mid_loop ? mid_name : lds_loop ? "hipk_cg_solve_lds_kernel" : "launch sequence");
+    hipk_set_solve_path(handed, mid_loop ? mid->name : lds_loop ? "hipk_cg_solve_lds_kernel" : "launch sequence");
     if (mid_loop) lds_loop = true;   // finished in the one-launch loop
     for (; !lds_loop && it < maxiter; ++it) {
         HIPK_CHECK_HIP(pace.gate(it, stream, &stop));

@@ -857,7 +857,7 @@ struct hipk_gm_cyc_args {
     double atol_eff;   //   the loop test `res_norm > atol_eff` (TSL:754),
     long long cycles_left;  // cycles the solve may still run (maxiter - cycles so far),
     long long max_cycles;   // and the cycle budget of one launch
-    int test_not_resident;  // tests (HIPK_TEST_LDS_NOT_RESIDENT): report the workgroups as not co-resident
+    int test_not_resident;  // tests (hipk_test_fail_launch): report the workgroups as not co-resident
     int spread;             // more than 64 workgroups: one per block all over the chip (then LOCAL = false)
     unsigned long long *flag_a, *flag_b;   // [512] each: per-workgroup hand-off flags, zeroed before the launch
     int32_t *bar;      // barrier counter, zeroed by hipk_gm_cycle_init_kernel
@@ -2158,17 +2158,15 @@ __global__ __launch_bounds__(HIPK_THREADS) void hipk_gm_scaled_sq_kernel(int64_t
     if (threadIdx.x == 0) part[c] = acc;
 }
 
-// the name of a one-launch instantiation the dispatch below selects (hipk_last_solve_path): by its address
+// the one-launch instantiations the dispatch below selects (hipk_mid_pick), each with the name hipk_last_solve_path reports
+#define HIPK_MID_ROW(W, PRE)                                                                                               \
+    {W, 1, PRE, hipk_gm_mid_kernel<T, W, PRE>,                                                                             \
+     sizeof(T) == 8 ? "hipk_gm_mid_kernel<double," #W "," #PRE ">" : "hipk_gm_mid_kernel<float," #W "," #PRE ">"}
 template <typename T>
-static const char *hipk_gm_mid_name(void (*k)(hipk_gm_mid_args)) {
-#define HIPK_MID_NAME(W, PRE)                                                                                              \
-    if (k == hipk_gm_mid_kernel<T, W, PRE>)                                                                            \
-        return sizeof(T) == 8 ? "hipk_gm_mid_kernel<double," #W "," #PRE ">" : "hipk_gm_mid_kernel<float," #W "," #PRE ">";
-    HIPK_MID_NAME(5, false) HIPK_MID_NAME(7, false) HIPK_MID_NAME(9, false) HIPK_MID_NAME(12, false)
-    HIPK_MID_NAME(5, true) HIPK_MID_NAME(7, true) HIPK_MID_NAME(9, true) HIPK_MID_NAME(12, true)
-#undef HIPK_MID_NAME
-    return "hipk_gm_mid_kernel<?>";
-}
+static const hipk_mid_entry<hipk_gm_mid_args> hipk_gm_mid_table[] = {
+    HIPK_MID_ROW(5, false), HIPK_MID_ROW(7, false), HIPK_MID_ROW(9, false), HIPK_MID_ROW(12, false),
+    HIPK_MID_ROW(5, true),  HIPK_MID_ROW(7, true),  HIPK_MID_ROW(9, true),  HIPK_MID_ROW(12, true)};
+#undef HIPK_MID_ROW
 
 // dinv != nullptr: left Jacobi preconditioning -- every A(.) is followed by M(.) = dinv .* (.) (TSL:351, 791, 766), applied
 // by the SpMV epilogue (HIPK_SPMV_SCALE) before its fused dots; ptol from ||M b|| (TSL:750).  Mirrored by orc_gmres_jacobi.
@@ -2313,38 +2311,19 @@ static int hipk_gmres_solve_t(hipk_csr_s *A, const T *dinv, const T *b, T *x, ch
     // 33 .. 256 chunks (fp64, no preconditioner, restart <= 31, rows of <= 12 entries within a window around their chunk): the
     // Arnoldi steps of a cycle in ONE launch, one workgroup per chunk (hipk_gm_mid.h); HIPK_GMRES_MID=0 keeps the launches
     static bool mid_failed = false;
-    bool mid_cycle = false;
+    const hipk_mid_entry<hipk_gm_mid_args> *mid = hipk_mid_pick(hipk_gm_mid_table<T>, A->max_row_len, 1, dinv != nullptr);
     hipk_mid_plan mid_plan;
-    memset(&mid_plan, 0, sizeof(mid_plan));
     size_t mid_lds = 0;
-    void (*mid_kern)(hipk_gm_mid_args) = nullptr;
-    {
-        const int mid_min = env_int("HIPK_GMRES_MID_MIN", kGmMidMinChunks);   // (A/B against the whole-solve kernel of 9 .. 32 chunks)
-        mid_cycle = !small && !ext && m <= HIPK_GM_MAXM && gm.g > (mid_min < 8 ? 8 : mid_min) && gm.g <= kGmMidMaxChunks &&
-                    gm.g <= A->n_cu && gm.ch == HIPK_BASE_CHUNK && A->op_cb == nullptr && A->crow != nullptr && A->max_row_len <= 12 &&
-                    prm->profile == 0 && !mid_failed && !(getenv("HIPK_GMRES_MID") && getenv("HIPK_GMRES_MID")[0] == '0') &&
-                    !getenv("HIPK_GMRES_NO_CYCLE");
-        if (dinv)
-            mid_kern = A->max_row_len <= 5 ? hipk_gm_mid_kernel<T, 5, true> : A->max_row_len <= 7 ? hipk_gm_mid_kernel<T, 7, true>
-                       : A->max_row_len <= 9 ? hipk_gm_mid_kernel<T, 9, true> : hipk_gm_mid_kernel<T, 12, true>;
-        else
-            mid_kern = A->max_row_len <= 5 ? hipk_gm_mid_kernel<T, 5> : A->max_row_len <= 7 ? hipk_gm_mid_kernel<T, 7>
-                       : A->max_row_len <= 9 ? hipk_gm_mid_kernel<T, 9> : hipk_gm_mid_kernel<T, 12>;
-        if (mid_cycle) {
-            mid_cycle = hipk_mid_plan_get(A, 1, stream, &mid_plan);   // the tiles each workgroup's window holds (hipk_mid.h)
-            mid_lds = mid_cycle ? hipk_gm_mid_lds_bytes(mid_plan.max_slots * HIPK_TILE, sizeof(T)) : 0;
-            int occ = 0;
-            mid_cycle = mid_cycle && mid_plan.max_slots <= kMidPlanSlots && mid_lds <= (size_t)160 * 1024 &&
-                        hipFuncSetAttribute((const void *)mid_kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mid_lds) == hipSuccess &&
-                        hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, mid_kern, 1024, mid_lds) == hipSuccess && (int64_t)occ * A->n_cu >= gm.g;
-            (void)hipGetLastError();
-        }
-        if (mid_cycle) cyc = cyc_lds = false;   // (9 .. 32 chunks: instead of the whole-solve kernel)
-    }
-    const char *mid_name = hipk_gm_mid_name<T>(mid_kern);
+    const int mid_min = env_int("HIPK_GMRES_MID_MIN", kGmMidMinChunks);   // (A/B against the whole-solve kernel of 9 .. 32 chunks)
+    auto lds_of = [](int slots) { return hipk_gm_mid_lds_bytes(slots * HIPK_TILE, sizeof(T)); };
+    bool mid_cycle = !small && !ext && m <= HIPK_GM_MAXM && gm.g > (mid_min < 8 ? 8 : mid_min) && gm.g <= kGmMidMaxChunks &&
+                     gm.g <= A->n_cu && gm.ch == HIPK_BASE_CHUNK && A->op_cb == nullptr && A->crow != nullptr && A->max_row_len <= 12 &&
+                     prm->profile == 0 && !mid_failed && !(getenv("HIPK_GMRES_MID") && getenv("HIPK_GMRES_MID")[0] == '0') &&
+                     !getenv("HIPK_GMRES_NO_CYCLE") && mid && hipk_mid_eligible(A, mid, gm.g, lds_of, stream, &mid_plan, &mid_lds);
+    if (mid_cycle) cyc = cyc_lds = false;   // (9 .. 32 chunks: instead of the whole-solve kernel)
     // the kernel a cycle enqueued below runs in (hipk_last_solve_path)
     auto cycle_kernel = [&]() -> const char * {
-        return mid_cycle ? mid_name : !cyc ? "launch sequence" : cyc_lds ? "hipk_gm_solve_lds_kernel" : "hipk_gm_cycle_small_kernel";
+        return mid_cycle ? mid->name : !cyc ? "launch sequence" : cyc_lds ? "hipk_gm_solve_lds_kernel" : "hipk_gm_cycle_small_kernel";
     };
     // multi-dot with up to 32 columns per workgroup (w read ONCE per step; 0, the default: groups of 8, w re-read per group).  Same
     // box, alternating, N = 4 M (profiles/r03_gmres_history.md): GMRES(30) 6.67-6.70 vs 6.64-6.66 ms per cycle, GMRES(50) 16.50 vs
@@ -2393,11 +2372,7 @@ static int hipk_gmres_solve_t(hipk_csr_s *A, const T *dinv, const T *b, T *x, ch
             ca.atol_eff = atol_eff;
             ca.cycles_left = maxiter - cycles;
             ca.max_cycles = env_int("HIPK_GM_LAUNCH_CYCLES", 64);
-            {   // tests: HIPK_TEST_LDS_NOT_RESIDENT=k makes the k-th one-launch kernel of this solve report "not co-resident"
-                const char *fe = getenv("HIPK_TEST_LDS_NOT_RESIDENT");
-                const int fail_launch = fe ? (atoi(fe) > 1 ? atoi(fe) : 1) : 0;
-                ca.test_not_resident = (++lds_launch_no == fail_launch) ? 1 : 0;
-            }
+            ca.test_not_resident = (++lds_launch_no == hipk_test_fail_launch()) ? 1 : 0;   // (one count for all one-launch kernels)
             ca.bar = &scal->bar;
             ca.eps = eps_t;
             ca.stamps = getenv("HIPK_GM_STAMPS") ? (unsigned long long *)(part_spare + 1600) : nullptr;
@@ -2435,14 +2410,10 @@ static int hipk_gmres_solve_t(hipk_csr_s *A, const T *dinv, const T *b, T *x, ch
                 ca.eps = eps_t;
                 ca.slot_stride = 16;
                 ca.xcd_aware = 1;
-                {
-                    const char *fe = getenv("HIPK_TEST_LDS_NOT_RESIDENT");
-                    const int fail_launch = fe ? (atoi(fe) > 1 ? atoi(fe) : 1) : 0;
-                    ca.test_not_resident = (++lds_launch_no == fail_launch) ? 1 : 0;
-                }
+                ca.test_not_resident = (++lds_launch_no == hipk_test_fail_launch()) ? 1 : 0;
                 (void)hipMemsetAsync(ca.v_ll, 0, hipk_align_up((size_t)n * 16, 256), stream);
                 (void)hipMemsetAsync(ca.slots, 0, (size_t)kGmMidKinds * gm.g * ca.slot_stride * 16, stream);
-                mid_kern<<<hipk_xcd_grid(gm.g), 1024, mid_lds, stream>>>(ca);
+                mid->kern<<<hipk_xcd_grid(gm.g), 1024, mid_lds, stream>>>(ca);
             }
         }
         for (int k = (cyc || mid_cycle) ? m : k_start; k < m; ++k) {
@@ -2520,29 +2491,31 @@ static int hipk_gmres_solve_t(hipk_csr_s *A, const T *dinv, const T *b, T *x, ch
             rc = HIPK_ERR_HIP;
             break;
         }
-        if (hs->redo < 0 && mid_cycle) {
+        const hipk_redo_verdict verdict = hipk_redo_classify(hs->redo, cyc_lds && cyc_local);
+        if (verdict != HIPK_REDO_RAN && mid_cycle) {
             // the workgroups of the one-launch step loop did not all arrive (nothing of the cycle is kept) or one of its hand-offs
             // never completed
-            if (hs->redo == -3) {
+            if (verdict == HIPK_REDO_ERROR) {
                 hipk_set_error("hipk_gmres_solve: a resident workgroup of the one-launch cycle stopped arriving");
                 rc = HIPK_ERR_HIP;
                 break;
             }
-            if (!getenv("HIPK_TEST_LDS_NOT_RESIDENT")) mid_failed = true;
-            hipk_path_add(handed, mid_name);
+            hipk_hand_back(mid_failed, handed, mid->name);
             mid_cycle = false;
             continue;
         }
-        if (hs->redo < 0) {
+        if (verdict != HIPK_REDO_RAN) {
             // the resident workgroups of a one-launch cycle did not all arrive (the device is shared and they were not
             // co-resident): nothing of the cycle is kept -- column 0 is untouched -- and this solve goes on with one launch
             // per kernel
             if (getenv("HIPK_GM_STAMPS")) fprintf(stderr, "hipk_gmres_solve: one-launch cycle abandoned (workgroups not co-resident)\n");
-            if (hs->redo == -2 && cyc_lds && cyc_local) {
+            if (verdict == HIPK_REDO_AGENT) {
                 cyc_local = false;      // its workgroups were spread over several XCDs: hand-offs at agent scope from now on
             } else {
-                if (cyc_lds && !getenv("HIPK_TEST_LDS_NOT_RESIDENT")) lds_cycle_failed = true;
-                hipk_path_add(handed, cycle_kernel());
+                if (cyc_lds)
+                    hipk_hand_back(lds_cycle_failed, handed, cycle_kernel());
+                else
+                    hipk_path_add(handed, cycle_kernel());
                 cyc = cyc_lds = false;
             }
             continue;

@@ -1,6 +1,7 @@
-// hipk_mid.h -- building blocks of the one-launch solver loops for mid-size systems (hipk_cg_mid.h, hipk_bi_mid.h): flagged
-// 16-byte words for hand-offs between resident workgroups, the polled fold of chunk partials, one-barrier block folds, the
-// matrix's reach beyond a reduction chunk.  See hipk_cg_mid.h for the scheme.
+// hipk_mid.h -- building blocks of the one-launch solver loops for mid-size systems (hipk_cg_mid.h, hipk_bi_mid.h, hipk_gm_mid.h):
+// flagged 16-byte words for hand-offs between resident workgroups, the polled fold of chunk partials, one-barrier block folds, the
+// matrix's reach beyond a reduction chunk; on the host, the choice of an instantiation and the check that it can run.  See
+// hipk_cg_mid.h for the scheme.
 #ifndef HIPK_MID_H
 #define HIPK_MID_H
 #include "hipk_handoff.h"
@@ -180,6 +181,39 @@ static inline bool hipk_mid_plan_get(hipk_csr_s *A, int nch, hipStream_t stream,
     out->needed = (const unsigned char *)(m + o_needed);
     out->max_slots = A->mid_plan_max_slots;
     return true;
+}
+
+// ---- host: which instantiation, and can it run ------------------------------------------------------------------------------
+// a row of a loop family's selection table: the instantiation for rows of <= w entries, nch chunks per workgroup, with (pre) or
+// without the Jacobi preconditioner, and its name as hipk_last_solve_path reports it
+template <typename Args>
+struct hipk_mid_entry {
+    int w, nch;
+    bool pre;
+    void (*kern)(Args);
+    const char *name;
+};
+// the narrowest entry for rows of max_row_len entries, nch chunks per workgroup and `pre`; null: the family has none
+template <typename Args, size_t N>
+static inline const hipk_mid_entry<Args> *hipk_mid_pick(const hipk_mid_entry<Args> (&table)[N], int max_row_len, int nch, bool pre) {
+    for (const hipk_mid_entry<Args> &e : table)
+        if (e.nch == nch && e.pre == pre && max_row_len <= e.w) return &e;
+    return nullptr;
+}
+// whether e's kernel can run on handle A as `grid` co-resident workgroups of 1024 threads: the window plan exists (computed once
+// per handle; not for matrices whose rows reach further than the plan's range) and holds <= kMidPlanSlots tiles, and the LDS
+// lds_of(plan->max_slots) fits a compute unit's 160 KiB.  Fills *plan (when true) and *lds.
+template <typename Args, typename LdsFn>
+static inline bool hipk_mid_eligible(hipk_csr_s *A, const hipk_mid_entry<Args> *e, int grid, LdsFn &&lds_of, hipStream_t stream,
+                                     hipk_mid_plan *plan, size_t *lds) {
+    bool ok = hipk_mid_plan_get(A, e->nch, stream, plan);
+    *lds = ok ? lds_of(plan->max_slots) : 0;
+    int occ = 0;
+    ok = ok && plan->max_slots <= kMidPlanSlots && *lds <= (size_t)160 * 1024 &&
+         hipFuncSetAttribute((const void *)e->kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)*lds) == hipSuccess &&
+         hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, e->kern, 1024, *lds) == hipSuccess && (int64_t)occ * A->n_cu >= grid;
+    (void)hipGetLastError();
+    return ok;
 }
 
 // thread t's share of the G flagged chunk partials in the spec's order (hipk_reduce_parts: t, t + 256; the tree follows);

@@ -288,3 +288,67 @@ static inline void hipk_finish_isolve_stats(hipk_stats *st, const hipk_params *p
     const bool failed = isnan(st->x_norm) || (st->residual_norm > st->threshold);
     st->info = failed ? -1 : 0;
 }
+
+// ---- the one-launch loops (hipk_*_solve_lds_kernel, hipk_*_mid_kernel): launches, read-back, hand-back ---------------------
+// tests: HIPK_TEST_LDS_NOT_RESIDENT=k makes the k-th launch of a one-launch loop report its workgroups as not co-resident (0: unset)
+static inline int hipk_test_fail_launch() {
+    const char *e = getenv("HIPK_TEST_LDS_NOT_RESIDENT");
+    return e ? (atoi(e) > 1 ? atoi(e) : 1) : 0;
+}
+// iterations per launch of a one-launch loop: the switch `name` (HIPK_*_LAUNCH_ITS) or dflt, at least 1
+static inline int64_t hipk_env_its(const char *name, int64_t dflt) {
+    const char *e = getenv(name);
+    const int64_t v = e ? atoll(e) : dflt;
+    return v < 1 ? 1 : v;
+}
+// what a launch's redo word says: >= 0 the launch ran; -3 a resident workgroup stopped arriving (an error); -2 with `local`: its
+// workgroups were spread over several XCDs (launch again with agent-scope hand-offs); else not co-resident, nothing was modified
+enum hipk_redo_verdict { HIPK_REDO_RAN, HIPK_REDO_AGENT, HIPK_REDO_HAND_BACK, HIPK_REDO_ERROR };
+static inline hipk_redo_verdict hipk_redo_classify(int32_t redo, bool local) {
+    if (redo >= 0) return HIPK_REDO_RAN;
+    if (redo == -3) return HIPK_REDO_ERROR;
+    return (redo == -2 && local) ? HIPK_REDO_AGENT : HIPK_REDO_HAND_BACK;
+}
+// a loop handed the solve back: its caller's process-wide latch `failed` is set (do not wait for that verdict again) unless a
+// test provoked it, and `name` joins the chain hipk_last_solve_path reports
+static inline void hipk_hand_back(bool &failed, char (&handed)[128], const char *name) {
+    if (!getenv("HIPK_TEST_LDS_NOT_RESIDENT")) failed = true;
+    hipk_path_add(handed, name);
+}
+
+struct hipk_loop_state { int32_t redo; int64_t it_done, stop_it; };
+static constexpr int HIPK_HANDED_BACK = 1;   // hipk_resident_run: the loop handed the solve back at iteration `it`
+
+// Runs a one-launch loop of CG, PCG or BiCGStab from iteration `it` until it stops (HIPK_OK), hands the solve back
+// (HIPK_HANDED_BACK) or fails (an error code; `entry` names the solver in the message).  launch(it0, test_not_resident, local)
+// enqueues one launch -- the loop's memsets and its kernel -- and returns HIPK_OK or an error; the scalar block S is read back
+// after it and state(S) gives {redo, it_done, stop_it}.  local: null for a loop without a one-XCD form.
+template <typename S, typename Launch, typename State>
+static int hipk_resident_run(hipStream_t stream, const S *scal, Launch &&launch, State &&state, int64_t &it, int64_t maxiter, bool *local,
+                             bool &failed, char (&handed)[128], const char *name, const char *entry) {
+    const int fail_launch = hipk_test_fail_launch();
+    int launch_no = 0, rc;
+    S hs;
+    for (;;) {
+        if ((rc = launch(it, (++launch_no == fail_launch) ? 1 : 0, local && *local)) != HIPK_OK) return rc;
+        HIPK_CHECK_HIP(hipGetLastError());
+        HIPK_CHECK_HIP(hipMemcpyAsync(&hs, scal, sizeof(hs), hipMemcpyDeviceToHost, stream));
+        HIPK_CHECK_HIP(hipStreamSynchronize(stream));
+        const hipk_loop_state s = state(hs);
+        const hipk_redo_verdict v = hipk_redo_classify(s.redo, local && *local);
+        if (v == HIPK_REDO_ERROR) {
+            hipk_set_error("%s: a resident workgroup of the one-launch loop stopped arriving", entry);
+            return HIPK_ERR_HIP;
+        }
+        if (v == HIPK_REDO_AGENT) {
+            *local = false;
+            continue;
+        }
+        if (v == HIPK_REDO_HAND_BACK) {
+            hipk_hand_back(failed, handed, name);
+            return HIPK_HANDED_BACK;
+        }
+        it = s.it_done;
+        if (s.stop_it <= it || it >= maxiter) return HIPK_OK;
+    }
+}
