@@ -386,6 +386,28 @@ int hipk_dist_gmres_solve(hipk_csr_t A_local, const hipk_dist_plan *plan, const 
                           void *x_ext, void *work, size_t work_bytes, const hipk_params *prm, hipk_stats *st,
                           hipk_stream_t stream);
 
+/* The three row-partitioned loops with the Jacobi preconditioner M = diag(dinv): the same plan / collective structs and
+ * conventions as above, bit for bit the iterates, counts and `info` of hipk_pcg_solve / hipk_pbicgstab_solve / hipk_pgmres_solve
+ * on the whole system.  `dinv_ext`: device, n_ext doubles -- the reciprocal diagonal of this rank's rows, then its entries at
+ * the halo positions (the owners' values, in the plan's ghost order).  CG reads the halo tail (it forms z = dinv .* r on the
+ * ghost rows); BiCGStab and GMRES read the first n_local entries.
+ *   CG       : two collective launches per iteration, as hipk_dist_cg_solve; the second carries the <r,r> and <r,z> partials
+ *              and the halo of r in one group.  The fused exchanges of hipk_rccl.fused are not taken.
+ *   BiCGStab : the halos of phat = M p and shat = M s instead of p and s; five collective launches per iteration.
+ *   GMRES    : left preconditioning, w = M (A v_k); restart <= 31. */
+size_t hipk_dist_pcg_work_bytes(const hipk_dist_plan *plan);
+int hipk_dist_pcg_solve(hipk_csr_t A_local, const hipk_dist_plan *plan, const hipk_rccl *coll, const void *dinv_ext,
+                        const void *b_local, void *x_ext, void *work, size_t work_bytes, const hipk_params *prm,
+                        hipk_stats *st, hipk_stream_t stream);
+size_t hipk_dist_pbicgstab_work_bytes(const hipk_dist_plan *plan);
+int hipk_dist_pbicgstab_solve(hipk_csr_t A_local, const hipk_dist_plan *plan, const hipk_rccl *coll, const void *dinv_ext,
+                              const void *b_local, void *x_ext, void *work, size_t work_bytes, const hipk_params *prm,
+                              hipk_stats *st, hipk_stream_t stream);
+size_t hipk_dist_pgmres_work_bytes(const hipk_dist_plan *plan, int restart);
+int hipk_dist_pgmres_solve(hipk_csr_t A_local, const hipk_dist_plan *plan, const hipk_rccl *coll, const void *dinv_ext,
+                           const void *b_local, void *x_ext, void *work, size_t work_bytes, const hipk_params *prm,
+                           hipk_stats *st, hipk_stream_t stream);
+
 /* ---- EXPERIMENTAL peer-to-peer exchange provider for the loop above (csrc/hipk_p2p.hip) ---------------------------------
  * Each rank owns a device mailbox that every peer maps through HIP IPC; an all-gather is ONE small kernel per rank (publish
  * blocks store into the peers' mailboxes, collect blocks wait on per-source sequence flags).  No reference counterpart.

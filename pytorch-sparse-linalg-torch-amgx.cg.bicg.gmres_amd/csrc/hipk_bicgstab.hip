@@ -1026,13 +1026,18 @@ extern "C" int hipk_pbicgstab_solve_cb(hipk_csr_t A, hipk_precond_fn M, void *us
 //   of s | SpMV t, all-gather <t,s>, <t,t> (one group) | K5
 // -- five collective launches (CG: two).  Conventions of hipk_dist_cg_solve (csrc/hipk_dist.hip): fixed batches, the stop word
 // read one batch late, identical decisions on all ranks without an agreement collective.
+// PRE (hipk_dist_pbicgstab_solve, M = diag(dinv)): the PRE instances of K1 / K3 / K5 as in hipk_pbicgstab_solve; the SpMVs multiply
+// phat = dinv .* p and shat = dinv .* s, so their halos are exchanged instead of those of p and s (ghost values: the owner's bits),
+// and `info` comes from ||M (b - A x)|| (the scaled residual SpMV).  The same five collective launches per iteration.
 #include <vector>
+
+#include "hipk_dist_xchg.h"
 
 struct hipk_dbi_layout {
     size_t scal, part_a, part_b, spare, g_rr, g_rhr, g_rq, g_ss, g_ts, g_tt, g_bb, out4, send_buf, slab_loc, slab_all;
-    size_t r, rhat, p, q, s, t, total;
+    size_t r, rhat, p, q, s, t, phat, shat, total;
 };
-static hipk_dbi_layout hipk_dbi_make_layout(const hipk_dist_plan *pl) {
+static hipk_dbi_layout hipk_dbi_make_layout(const hipk_dist_plan *pl, bool pre) {
     hipk_dbi_layout L;
     size_t o = 0;
     auto take = [&](size_t bytes) {
@@ -1063,19 +1068,25 @@ static hipk_dbi_layout hipk_dbi_make_layout(const hipk_dist_plan *pl) {
     L.q = take(nloc * 8);
     L.s = take(next * 8);
     L.t = take(next * 8);   // also the x-halo scratch of the residual SpMVs
+    L.phat = pre ? take(next * 8) : L.p;   // PRE: the SpMV inputs, with their halo tails
+    L.shat = pre ? take(next * 8) : L.s;
     L.total = o;
     return L;
 }
 extern "C" size_t hipk_dist_bicgstab_work_bytes(const hipk_dist_plan *plan) {
     if (!plan || plan->world < 1 || plan->per < 1) return 0;
-    return hipk_dbi_make_layout(plan).total;
+    return hipk_dbi_make_layout(plan, false).total;
+}
+extern "C" size_t hipk_dist_pbicgstab_work_bytes(const hipk_dist_plan *plan) {
+    if (!plan || plan->world < 1 || plan->per < 1) return 0;
+    return hipk_dbi_make_layout(plan, true).total;
 }
 
 #define HIPK_DBI_NCCL(expr, what)                                                          \
     do {                                                                                   \
         const int _r = (expr);                                                             \
         if (_r != 0) {                                                                     \
-            hipk_set_error("hipk_dist_bicgstab_solve: %s failed (ncclResult %d)", what, _r); \
+            hipk_set_error("%s: %s failed (ncclResult %d)", who, what, _r);                \
             return HIPK_ERR_HIP;                                                           \
         }                                                                                  \
     } while (0)
@@ -1085,9 +1096,11 @@ extern "C" size_t hipk_dist_bicgstab_work_bytes(const hipk_dist_plan *plan) {
         if (_rc != HIPK_OK) return _rc; \
     } while (0)
 
-extern "C" int hipk_dist_bicgstab_solve(hipk_csr_t A, const hipk_dist_plan *pl, const hipk_rccl *cc, const void *b_local, void *x_ext,
-                                        void *work, size_t work_bytes, const hipk_params *prm, hipk_stats *st, hipk_stream_t stream_) {
+template <bool PRE>
+static int hipk_dist_bicgstab_t(hipk_csr_t A, const hipk_dist_plan *pl, const hipk_rccl *cc, const double *dinv, const void *b_local,
+                                void *x_ext, void *work, size_t work_bytes, const hipk_params *prm, hipk_stats *st, hipk_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
+    const char *who = PRE ? "hipk_dist_pbicgstab_solve" : "hipk_dist_bicgstab_solve";
     HIPK_REQUIRE(A && pl && cc && b_local && x_ext && work && prm && st, HIPK_ERR_ARG, "null argument");
     HIPK_REQUIRE(A->dtype == HIPK_F64, HIPK_ERR_UNSUPPORTED, "the row-partitioned solver is fp64");
     HIPK_REQUIRE(pl->world >= 1 && pl->rank >= 0 && pl->rank < pl->world, HIPK_ERR_ARG, "rank / world");
@@ -1100,7 +1113,7 @@ extern "C" int hipk_dist_bicgstab_solve(hipk_csr_t A, const hipk_dist_plan *pl, 
                  HIPK_ERR_ARG, "missing collective entry points");
     HIPK_REQUIRE((((uintptr_t)work) & 255u) == 0 && hipk_aligned16(x_ext) && hipk_aligned16(b_local), HIPK_ERR_ALIGN,
                  "work must be 256-byte, x / b 16-byte aligned");
-    const hipk_dbi_layout L = hipk_dbi_make_layout(pl);
+    const hipk_dbi_layout L = hipk_dbi_make_layout(pl, PRE);
     HIPK_REQUIRE(work_bytes >= L.total, HIPK_ERR_WORKSPACE, "work too small");
     memset(st, 0, sizeof(*st));
     typedef double T;
@@ -1112,7 +1125,7 @@ extern "C" int hipk_dist_bicgstab_solve(hipk_csr_t A, const hipk_dist_plan *pl, 
     double *g_bb = (double *)(wk + L.g_bb), *out4 = (double *)(wk + L.out4);
     double *send_buf = (double *)(wk + L.send_buf), *slab_loc = (double *)(wk + L.slab_loc), *slab_all = (double *)(wk + L.slab_all);
     T *r = (T *)(wk + L.r), *rhat = (T *)(wk + L.rhat), *p = (T *)(wk + L.p), *q = (T *)(wk + L.q), *s = (T *)(wk + L.s);
-    T *t = (T *)(wk + L.t);
+    T *t = (T *)(wk + L.t), *phat = (T *)(wk + L.phat), *shat = (T *)(wk + L.shat);   // (= p, s without PRE)
     T *x = (T *)x_ext;
     const T *b = (const T *)b_local;
     const int64_t n = pl->n_local, n_ext = pl->n_ext;
@@ -1199,17 +1212,17 @@ extern "C" int hipk_dist_bicgstab_solve(hipk_csr_t A, const hipk_dist_plan *pl, 
     while (it < maxiter) {
         const int64_t end = (it + batch < maxiter) ? it + batch : maxiter;
         for (; it < end; ++it) {
-            hipk_bi_direction_kernel<T, false><<<grid, HIPK_THREADS, 0, stream>>>(n, ch, G, scal, it, g_rr, g_rhr, r, q, p, nullptr, p);
-            HIPK_DBI_TRY(exchange(p, nullptr, nullptr));
-            HIPK_DBI_TRY(hipk_spmv_ex(A, p, q, MODE_DOT_W, rhat, nullptr, part_a, spare, stop_dev, it, stream));
+            hipk_bi_direction_kernel<T, PRE><<<grid, HIPK_THREADS, 0, stream>>>(n, ch, G, scal, it, g_rr, g_rhr, r, q, p, dinv, phat);
+            HIPK_DBI_TRY(exchange(phat, nullptr, nullptr));
+            HIPK_DBI_TRY(hipk_spmv_ex(A, phat, q, MODE_DOT_W, rhat, nullptr, part_a, spare, stop_dev, it, stream));
             HIPK_DBI_TRY(gather(part_a, g_rq));
-            hipk_bi_supdate_kernel<T, false, false><<<grid, HIPK_THREADS, 0, stream>>>(n, ch, G, scal, it, g_rhr, g_rq, r, q, s, part_a,
-                                                                                      nullptr, s, 0);
-            HIPK_DBI_TRY(exchange(s, part_a, g_ss));
-            HIPK_DBI_TRY(hipk_spmv_ex(A, s, t, MODE_DOT_W | MODE_DOT_YY, s, nullptr, part_a, part_b, stop_dev, it, stream));
+            hipk_bi_supdate_kernel<T, PRE, false><<<grid, HIPK_THREADS, 0, stream>>>(n, ch, G, scal, it, g_rhr, g_rq, r, q, s, part_a,
+                                                                                    dinv, shat, 0);
+            HIPK_DBI_TRY(exchange(shat, part_a, g_ss));
+            HIPK_DBI_TRY(hipk_spmv_ex(A, shat, t, MODE_DOT_W | MODE_DOT_YY, s, nullptr, part_a, part_b, stop_dev, it, stream));
             HIPK_DBI_TRY(gather2(part_a, g_ts, part_b, g_tt));
-            hipk_bi_xupdate_kernel<T, false, false><<<grid, HIPK_THREADS, 0, stream>>>(n, ch, G, scal, it, maxiter, g_ss, g_ts, g_tt, p, s, t,
-                                                                                      rhat, x, r, part_a, part_b, s, 0);
+            hipk_bi_xupdate_kernel<T, PRE, false><<<grid, HIPK_THREADS, 0, stream>>>(n, ch, G, scal, it, maxiter, g_ss, g_ts, g_tt, phat, s,
+                                                                                    t, rhat, x, r, part_a, part_b, shat, 0);
             HIPK_DBI_TRY(gather2(part_a, g_rr, part_b, g_rhr));
         }
         HIPK_CHECK_HIP(hipGetLastError());
@@ -1222,9 +1235,12 @@ extern "C" int hipk_dist_bicgstab_solve(hipk_csr_t A, const hipk_dist_plan *pl, 
     }
     HIPK_CHECK_HIP(poll.drain(&stop));
 
-    // ---- TSL:1007-1014: true residual and ||x|| decide info
+    // ---- TSL:1007-1014: true residual (PRE: ||M (b - A x)||, the row scaling in the SpMV epilogue) and ||x|| decide info
     HIPK_DBI_TRY(exchange(x, nullptr, nullptr));
-    HIPK_DBI_TRY(hipk_spmv_ex(A, x, t, MODE_RESID | MODE_DOT_YY, nullptr, b, spare, part_a, nullptr, 0, stream));
+    if (PRE)
+        HIPK_DBI_TRY(hipk_dist_spmv(A, x, t, MODE_RESID | MODE_DOT_YY, nullptr, b, dinv, spare, part_a, nullptr, 0, stream));
+    else
+        HIPK_DBI_TRY(hipk_spmv_ex(A, x, t, MODE_RESID | MODE_DOT_YY, nullptr, b, spare, part_a, nullptr, 0, stream));
     HIPK_DBI_TRY(gather(part_a, g_ss));
     HIPK_DBI_TRY(hipk_reduce_parts(g_ss, G, out4 + 0, stream));
     HIPK_DBI_TRY(hipk_dot_parts(n, ch, x, x, HIPK_F64, part_a, stream));
@@ -1244,4 +1260,17 @@ extern "C" int hipk_dist_bicgstab_solve(hipk_csr_t A, const hipk_dist_plan *pl, 
     HIPK_CHECK_HIP(hipEventElapsedTime(&ms, whole.a, whole.b));
     st->solve_ms = ms;
     return HIPK_OK;
+}
+
+extern "C" int hipk_dist_bicgstab_solve(hipk_csr_t A, const hipk_dist_plan *pl, const hipk_rccl *cc, const void *b_local, void *x_ext,
+                                        void *work, size_t work_bytes, const hipk_params *prm, hipk_stats *st, hipk_stream_t stream) {
+    return hipk_dist_bicgstab_t<false>(A, pl, cc, nullptr, b_local, x_ext, work, work_bytes, prm, st, stream);
+}
+
+extern "C" int hipk_dist_pbicgstab_solve(hipk_csr_t A, const hipk_dist_plan *pl, const hipk_rccl *cc, const void *dinv,
+                                         const void *b_local, void *x_ext, void *work, size_t work_bytes, const hipk_params *prm,
+                                         hipk_stats *st, hipk_stream_t stream) {
+    const int rc = hipk_dist_check(A, pl, cc, dinv, b_local, x_ext, work, prm, st);
+    if (rc != HIPK_OK) return rc;
+    return hipk_dist_bicgstab_t<true>(A, pl, cc, (const double *)dinv, b_local, x_ext, work, work_bytes, prm, st, stream);
 }

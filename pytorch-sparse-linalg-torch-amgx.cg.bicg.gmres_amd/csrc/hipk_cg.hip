@@ -1845,6 +1845,176 @@ extern "C" int hipk_pcg_solve(hipk_csr_t A, const void *dinv, const void *b, voi
                                    (hipStream_t)stream);
 }
 
+// =====================================================================================================================
+// Row-partitioned CG with the Jacobi preconditioner, the loop of one rank in C: the launch sequence of hipk_pcg_solve on the row
+// block, with the conventions of hipk_dist_cg_solve (csrc/hipk_dist.hip: fixed batches, the stop word read one batch late, the
+// same collectives on every rank).  Every kernel folds the gathered partials of ALL ranks in global chunk order, so the iterates
+// are bitwise those of hipk_pcg_solve on the whole system.  Per iteration, on the solver's stream:
+//   SpMV p -> Ap, <p,Ap> | all-gather <p,Ap> | update (r, <r,r>, <r,z>) | ONE group: all-gather <r,r> + all-gather <r,z> + the
+//   halo of r | direction over n_ext (x, p = z + beta p, stop test)
+// -- two collective launches, as plain CG.  The direction kernel forms z = dinv .* r on the ghost rows as well, from the exchanged
+// r and the caller's dinv tail: the owner's operands, the owner's bits.  <r,z> lives in a ping-pong pair of gathered arrays by
+// iteration parity: the update kernel reads the old one while the direction kernel reads both.
+#include "hipk_dist_xchg.h"
+
+struct hipk_dpcg_layout {
+    size_t scal, part_loc, part_rz, spare, g_pAp, g_rr, g_bb, g_xx, g_rz0, g_rz1, send_buf, slab_loc, slab_all, p, r, Ap, total;
+};
+static hipk_dpcg_layout hipk_dpcg_make_layout(const hipk_dist_plan *pl) {
+    hipk_dpcg_layout L;
+    size_t o = 0;
+    auto take = [&](size_t bytes) {
+        const size_t at = o;
+        o += hipk_align_up(bytes, 256);
+        return at;
+    };
+    const size_t per = (size_t)pl->per, W = (size_t)pl->world;
+    const size_t next = (size_t)(pl->n_ext > 0 ? pl->n_ext : 1), nloc = (size_t)(pl->n_local > 0 ? pl->n_local : 1);
+    L.scal = take(256);
+    L.part_loc = take(per * 8);
+    L.part_rz = take(per * 8);
+    L.spare = take(per * 8);
+    L.g_pAp = take(W * per * 8);
+    L.g_rr = take(W * per * 8);
+    L.g_bb = take(W * per * 8);
+    L.g_xx = take(W * per * 8);
+    L.g_rz0 = take(W * per * 8);
+    L.g_rz1 = take(W * per * 8);
+    L.send_buf = take((size_t)(pl->n_send > 0 ? pl->n_send : 1) * 8);
+    L.slab_loc = take((size_t)(pl->slab > 0 ? pl->slab : 1) * 8);
+    L.slab_all = take((size_t)(pl->slab > 0 ? pl->slab : 1) * W * 8);
+    L.p = take(next * 8);
+    L.r = take(next * 8);
+    L.Ap = take(nloc * 8);
+    L.total = o;
+    return L;
+}
+
+extern "C" size_t hipk_dist_pcg_work_bytes(const hipk_dist_plan *plan) {
+    if (!plan || plan->world < 1 || plan->per < 1) return 0;
+    return hipk_dpcg_make_layout(plan).total;
+}
+
+int hipk_dist_check(hipk_csr_s *A, const hipk_dist_plan *pl, const hipk_rccl *cc, const void *dinv, const void *b_local,
+                    void *x_ext, void *work, const hipk_params *prm, hipk_stats *st) {
+    HIPK_REQUIRE(A && pl && cc && dinv && b_local && x_ext && work && prm && st, HIPK_ERR_ARG, "null argument");
+    HIPK_REQUIRE(A->dtype == HIPK_F64, HIPK_ERR_UNSUPPORTED, "the row-partitioned solver is fp64");
+    HIPK_REQUIRE(pl->world >= 1 && pl->rank >= 0 && pl->rank < pl->world, HIPK_ERR_ARG, "rank / world");
+    HIPK_REQUIRE(pl->n_local > 0 && pl->n_local == A->n_rows && pl->n_ext >= pl->n_local, HIPK_ERR_ARG,
+                 "every rank must own rows (n_local > 0) and n_ext >= n_local");
+    HIPK_REQUIRE(pl->per >= 1 && (int64_t)pl->per * pl->world >= pl->g_red && pl->g_red >= 1 && pl->g_red <= HIPK_MAX_PARTS,
+                 HIPK_ERR_ARG, "partial-sum geometry");
+    HIPK_REQUIRE((pl->n_local + pl->chunk_rows - 1) / pl->chunk_rows <= pl->per, HIPK_ERR_ARG, "more local chunks than `per`");
+    HIPK_REQUIRE(cc->all_gather && cc->group_start && cc->group_end && (pl->world == 1 || pl->halo_mode == 0 || (cc->send && cc->recv)),
+                 HIPK_ERR_ARG, "missing collective entry points");
+    HIPK_REQUIRE((((uintptr_t)work) & 255u) == 0 && hipk_aligned16(x_ext) && hipk_aligned16(b_local) && hipk_aligned16(dinv),
+                 HIPK_ERR_ALIGN, "work must be 256-byte, x / b / dinv 16-byte aligned");
+    return HIPK_OK;
+}
+
+extern "C" int hipk_dist_pcg_solve(hipk_csr_t A, const hipk_dist_plan *pl, const hipk_rccl *cc, const void *dinv_ext,
+                                   const void *b_local, void *x_ext, void *work, size_t work_bytes, const hipk_params *prm,
+                                   hipk_stats *st, hipk_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    int rc = hipk_dist_check(A, pl, cc, dinv_ext, b_local, x_ext, work, prm, st);
+    if (rc != HIPK_OK) return rc;
+    const hipk_dpcg_layout L = hipk_dpcg_make_layout(pl);
+    HIPK_REQUIRE(work_bytes >= L.total, HIPK_ERR_WORKSPACE, "work too small");
+    memset(st, 0, sizeof(*st));
+    typedef double T;
+    char *wk = (char *)work;
+    hipk_pcg_scal *scal = (hipk_pcg_scal *)(wk + L.scal);
+    double *part_loc = (double *)(wk + L.part_loc), *part_rz = (double *)(wk + L.part_rz), *spare = (double *)(wk + L.spare);
+    double *g_pAp = (double *)(wk + L.g_pAp), *g_rr = (double *)(wk + L.g_rr), *g_bb = (double *)(wk + L.g_bb);
+    double *g_xx = (double *)(wk + L.g_xx);
+    double *g_rz[2] = {(double *)(wk + L.g_rz0), (double *)(wk + L.g_rz1)};
+    T *p = (T *)(wk + L.p), *r = (T *)(wk + L.r), *Ap = (T *)(wk + L.Ap);
+    T *x = (T *)x_ext;
+    const T *b = (const T *)b_local, *dinv = (const T *)dinv_ext;
+    const int64_t n = pl->n_local, n_ext = pl->n_ext;
+    const int ch = pl->chunk_rows, G = pl->g_red;
+    const int grid = (int)((n + ch - 1) / ch), grid_ext = (int)((n_ext + ch - 1) / ch);
+    const int64_t maxiter = (prm->maxiter < 0) ? 10 * pl->n_global : prm->maxiter;   // TSL:982-984
+    const float tolf = (float)prm->tol, atolf = (float)prm->atol;
+    const double tol2 = (double)(tolf * tolf), atol_sq = (double)(atolf * atolf);
+    const int64_t *stop_dev = &scal->stop_it;
+    hipk_dist_xchg xc{pl, cc, stream, (double *)(wk + L.send_buf), (double *)(wk + L.slab_loc), (double *)(wk + L.slab_all),
+                      "hipk_dist_pcg_solve", false};
+    xc.init();
+#define HIPK_DPCG_TRY(expr)               \
+    do {                                  \
+        const int _rc = (expr);           \
+        if (_rc != HIPK_OK) return _rc;   \
+    } while (0)
+
+    hipk_event_pair whole;
+    HIPK_CHECK_HIP(whole.create());
+    HIPK_CHECK_HIP(hipEventRecord(whole.a, stream));
+    HIPK_CHECK_HIP(hipMemsetAsync(wk, 0, L.total, stream));
+    if (n_ext > n) HIPK_CHECK_HIP(hipMemsetAsync(x + n, 0, (size_t)(n_ext - n) * 8, stream));
+
+    // ---- r0 = b - A x0, <r0,r0>; <b,b>; z0 = M r0, p0 = z0, gamma0 = <r0,z0> (TSL:815-826); the halo of p0 from its owners
+    HIPK_DPCG_TRY(xc.run(x, nullptr, nullptr));
+    HIPK_DPCG_TRY(hipk_dist_spmv(A, x, r, HIPK_SPMV_RESID | HIPK_SPMV_DOT_YY, nullptr, b, nullptr, spare, part_loc, nullptr, 0, stream));
+    HIPK_DPCG_TRY(xc.run(nullptr, part_loc, g_rr));
+    HIPK_DPCG_TRY(hipk_dot_parts(n, ch, b, b, HIPK_F64, part_loc, stream));
+    HIPK_DPCG_TRY(xc.run(nullptr, part_loc, g_bb));
+    hipk_pcg_start_kernel<T><<<grid, HIPK_THREADS, 0, stream>>>(n, ch, G, scal, g_rr, g_bb, r, dinv, p, part_rz, tol2, atol_sq,
+                                                                 maxiter, nullptr);
+    HIPK_CHECK_HIP(hipGetLastError());
+    HIPK_DPCG_TRY(xc.run(p, part_rz, g_rz[0]));
+
+    // ---- the loop: fixed batches, the stop word read one batch late (two reads in flight)
+    const int64_t batch = prm->check_every > 0 ? prm->check_every : 16;
+    hipk_poller poll(A->host_poll);
+    HIPK_CHECK_HIP(poll.create());
+    int64_t it = 0, stop = INT64_MAX;
+    while (it < maxiter) {
+        const int64_t end = (it + batch < maxiter) ? it + batch : maxiter;
+        for (; it < end; ++it) {
+            double *rz_old = g_rz[it & 1], *rz_new = g_rz[(it + 1) & 1];
+            HIPK_DPCG_TRY(hipk_dist_spmv(A, p, Ap, HIPK_SPMV_DOT_W, p, nullptr, nullptr, part_loc, spare, stop_dev, it, stream));
+            HIPK_DPCG_TRY(xc.run(nullptr, part_loc, g_pAp));
+            hipk_pcg_update_kernel<T><<<grid, HIPK_THREADS, 0, stream>>>(n, ch, G, scal, it, g_pAp, rz_old, Ap, dinv, r, part_loc,
+                                                                          part_rz);
+            HIPK_DPCG_TRY(xc.run(r, part_loc, g_rr, part_rz, rz_new));
+            hipk_pcg_direction_kernel<T><<<grid_ext, HIPK_THREADS, 0, stream>>>(n_ext, ch, G, scal, it, maxiter, g_pAp, rz_old, rz_new,
+                                                                                 g_rr, r, dinv, p, x);
+        }
+        HIPK_CHECK_HIP(hipGetLastError());
+        HIPK_CHECK_HIP(poll.post(stop_dev, it, stream));
+        if (poll.count == 2) {
+            HIPK_CHECK_HIP(hipEventSynchronize(poll.ev[poll.head]));
+            poll.harvest(&stop);
+        }
+        if (stop <= it - batch) break;   // the batch BEFORE the one just enqueued had already reached the stop
+    }
+    HIPK_CHECK_HIP(poll.drain(&stop));
+
+    // ---- TSL:1007-1014 with M: ||M (b - A x)||, ||x||
+    HIPK_DPCG_TRY(xc.run(x, nullptr, nullptr));
+    HIPK_DPCG_TRY(hipk_dist_spmv(A, x, Ap, HIPK_SPMV_RESID, nullptr, b, nullptr, spare, spare, nullptr, 0, stream));
+    hipk_pcg_resnorm_kernel<T><<<grid, HIPK_THREADS, 0, stream>>>(n, ch, Ap, dinv, part_loc);
+    HIPK_CHECK_HIP(hipGetLastError());
+    HIPK_DPCG_TRY(xc.run(nullptr, part_loc, g_rr));
+    HIPK_DPCG_TRY(hipk_dot_parts(n, ch, x, x, HIPK_F64, part_loc, stream));
+    HIPK_DPCG_TRY(xc.run(nullptr, part_loc, g_xx));
+    hipk_pcg_final_kernel<<<1, HIPK_THREADS, 0, stream>>>(scal, G, g_rr, g_xx);
+    HIPK_CHECK_HIP(hipGetLastError());
+    hipk_pcg_scal hs;
+    HIPK_CHECK_HIP(hipEventRecord(whole.b, stream));
+    HIPK_CHECK_HIP(hipMemcpyAsync(&hs, scal, sizeof(hs), hipMemcpyDeviceToHost, stream));
+    HIPK_CHECK_HIP(hipStreamSynchronize(stream));
+    const int64_t iterations = (hs.stop_it < it) ? hs.stop_it : it;
+    hipk_finish_isolve_stats(st, prm, hs.bs, hs.res2, hs.xx, iterations, iterations + 2);
+    st->recurrence_rs = hs.rs_last;
+    float ms = 0.f;
+    HIPK_CHECK_HIP(hipEventElapsedTime(&ms, whole.a, whole.b));
+    st->solve_ms = ms;
+#undef HIPK_DPCG_TRY
+    return HIPK_OK;
+}
+
 #ifdef HIPK_GM_STAMPS
 // diagnostic twin only: per-workgroup phase time sums of the last hipk_cg_mid_kernel launch (hipk_cg_mid.h)
 extern "C" int hipk_debug_mid_stamps(unsigned long long *out, size_t count) {

@@ -2702,7 +2702,11 @@ extern "C" int hipk_pgmres_solve_cb(hipk_csr_t A, hipk_precond_fn M, void *user,
 //   halo of v_k | SpMV, all-gather ||w||^2 | multi-dot, all-gather of its k+1 columns (one group) | h-reduce | update, all-gather ||q||^2
 //   | [CGS2 decision, second pass: the same three again -- device no-ops when not wanted, the collectives still pair up] | normalise
 // The cycle's small least-squares problem is solved by every rank's host from its own (identical) copy of H.
-// Conventions of hipk_dist_cg_solve (csrc/hipk_dist.hip): same plan / collective structs, fp64, M = identity.
+// Conventions of hipk_dist_cg_solve (csrc/hipk_dist.hip): same plan / collective structs, fp64.
+// dinv != null (hipk_dist_pgmres_solve): left Jacobi preconditioning as in hipk_pgmres_solve -- every SpMV (Arnoldi products, the
+// residuals) carries the row scaling in its epilogue, so its fused ||w||^2 partials are those of the scaled vector; ptol from ||M b||
+// (TSL:750).  The same exchanges as without it.
+#include "hipk_dist_xchg.h"
 static size_t hipk_dgm_vec_bytes(const hipk_dist_plan *pl) {
     return hipk_align_up((size_t)(pl->n_ext > 0 ? pl->n_ext : 1) * sizeof(double), 256);
 }
@@ -2715,9 +2719,10 @@ extern "C" size_t hipk_dist_gmres_work_bytes(const hipk_dist_plan *plan, int res
            hipk_align_up(slab * (size_t)plan->world * 8, 256);
 }
 
-extern "C" int hipk_dist_gmres_solve(hipk_csr_t A, const hipk_dist_plan *pl, const hipk_rccl *cc, const void *b_local, void *x_ext,
-                                     void *work_, size_t work_bytes, const hipk_params *prm, hipk_stats *st, hipk_stream_t stream_) {
+static int hipk_dist_gmres_t(hipk_csr_t A, const hipk_dist_plan *pl, const hipk_rccl *cc, const double *dinv, const void *b_local,
+                             void *x_ext, void *work_, size_t work_bytes, const hipk_params *prm, hipk_stats *st, hipk_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
+    const char *who = dinv ? "hipk_dist_pgmres_solve" : "hipk_dist_gmres_solve";
     HIPK_REQUIRE(A && pl && cc && b_local && x_ext && work_ && prm && st, HIPK_ERR_ARG, "null argument");
     HIPK_REQUIRE(A->dtype == HIPK_F64, HIPK_ERR_UNSUPPORTED, "the row-partitioned solver is fp64");
     HIPK_REQUIRE(prm->restart >= 1 && prm->restart <= HIPK_GM_MAXM, HIPK_ERR_ARG, "restart must be in [1, 31]");
@@ -2768,7 +2773,7 @@ extern "C" int hipk_dist_gmres_solve(hipk_csr_t A, const hipk_dist_plan *pl, con
     do {                                                                                \
         const int _r = (expr);                                                          \
         if (_r != 0) {                                                                  \
-            hipk_set_error("hipk_dist_gmres_solve: %s failed (ncclResult %d)", what, _r); \
+            hipk_set_error("%s: %s failed (ncclResult %d)", who, what, _r);               \
             return HIPK_ERR_HIP;                                                        \
         }                                                                               \
     } while (0)
@@ -2818,7 +2823,10 @@ extern "C" int hipk_dist_gmres_solve(hipk_csr_t A, const hipk_dist_plan *pl, con
     // residual = b - A x0 into column 0, unit residual + norm (TSL:791-792); <b,b>
     auto residual = [&]() -> int {
         HIPK_DGM_TRY(halo(x));
-        HIPK_DGM_TRY(hipk_spmv_ex(A, x, V, MODE_RESID | MODE_DOT_YY, nullptr, b, part_spare + c0, part_res + c0, nullptr, 0, stream));
+        if (dinv)   // M (b - A x0), its squared norm (TSL:791)
+            HIPK_DGM_TRY(hipk_dist_spmv(A, x, V, MODE_RESID | MODE_DOT_YY, nullptr, b, dinv, part_spare + c0, part_res + c0, nullptr, 0, stream));
+        else
+            HIPK_DGM_TRY(hipk_spmv_ex(A, x, V, MODE_RESID | MODE_DOT_YY, nullptr, b, part_spare + c0, part_res + c0, nullptr, 0, stream));
         HIPK_DGM_TRY(complete(part_res));
         hipk_gm_resnorm_kernel<T><<<gl, HIPK_THREADS, 0, stream>>>(n, ch, G, scal, V, part_res, part_bb, eps_t);
         return hipGetLastError() == hipSuccess ? HIPK_OK : HIPK_ERR_HIP;
@@ -2840,7 +2848,19 @@ extern "C" int hipk_dist_gmres_solve(hipk_csr_t A, const hipk_dist_plan *pl, con
     const double adaptive = (cand > prm->tol) ? cand : (double)(float)prm->tol;
     const double base_atol = (double)(float)(eps * (prm->gpu_tolerances ? 1000 : 100) * ng);
     const double atol_eff = hipk_tmax(adaptive * b_norm, hipk_tmax((double)(float)prm->atol, base_atol));
-    const double ptol = b_norm * hipk_tmin(1.0, atol_eff / b_norm);
+    double mb_norm = b_norm;  // ||M b|| (TSL:750)
+    if (dinv) {
+        hipk_gm_scaled_sq_kernel<T><<<gl, HIPK_THREADS, 0, stream>>>(n, ch, b, dinv, part_spare + c0);
+        HIPK_CHECK_HIP(hipGetLastError());
+        HIPK_DGM_TRY(complete(part_spare));
+        double *mb_dev = part_xx;  // the <x,x> slot is unused until the end of the solve
+        HIPK_DGM_TRY(hipk_reduce_parts(part_spare, G, mb_dev, stream));
+        double mb2 = 0.0;
+        HIPK_CHECK_HIP(hipMemcpyAsync(&mb2, mb_dev, sizeof(double), hipMemcpyDeviceToHost, stream));
+        HIPK_CHECK_HIP(hipStreamSynchronize(stream));
+        mb_norm = hipk_norm_from_sq(mb2);
+    }
+    const double ptol = mb_norm * hipk_tmin(1.0, atol_eff / b_norm);
 
     std::vector<unsigned char> hs_store(sizeof(hipk_gm_scal));
     hipk_gm_scal *hs = (hipk_gm_scal *)hs_store.data();
@@ -2852,7 +2872,11 @@ extern "C" int hipk_dist_gmres_solve(hipk_csr_t A, const hipk_dist_plan *pl, con
         for (int k = 0; k < m; ++k) {
             T *vk = V + (int64_t)k * ldv, *w = V + (int64_t)(k + 1) * ldv;
             HIPK_DGM_TRY(halo(vk));
-            HIPK_DGM_TRY(hipk_spmv_ex(A, vk, w, MODE_DOT_YY, nullptr, nullptr, part_spare + c0, part_ww + c0, &scal->stop_step, k, stream));
+            if (dinv)   // w = M (A v_k), ||w||^2 of the scaled vector (TSL:351-352)
+                HIPK_DGM_TRY(hipk_dist_spmv(A, vk, w, MODE_DOT_YY, nullptr, nullptr, dinv, part_spare + c0, part_ww + c0, &scal->stop_step, k,
+                                            stream));
+            else
+                HIPK_DGM_TRY(hipk_spmv_ex(A, vk, w, MODE_DOT_YY, nullptr, nullptr, part_spare + c0, part_ww + c0, &scal->stop_step, k, stream));
             HIPK_DGM_TRY(complete(part_ww));
             for (int pass = 0; pass < 2; ++pass) {
                 if (pass == 1) hipk_gm_decide_kernel<<<1, HIPK_THREADS, 0, stream>>>(scal, k, G, part_qq, eps_t);
@@ -2901,7 +2925,10 @@ extern "C" int hipk_dist_gmres_solve(hipk_csr_t A, const hipk_dist_plan *pl, con
 
     // TSL:766-773
     HIPK_DGM_TRY(halo(x));
-    HIPK_DGM_TRY(hipk_spmv_ex(A, x, tmp, MODE_RESID | MODE_DOT_YY, nullptr, b, part_spare + c0, part_res + c0, nullptr, 0, stream));
+    if (dinv)
+        HIPK_DGM_TRY(hipk_dist_spmv(A, x, tmp, MODE_RESID | MODE_DOT_YY, nullptr, b, dinv, part_spare + c0, part_res + c0, nullptr, 0, stream));
+    else
+        HIPK_DGM_TRY(hipk_spmv_ex(A, x, tmp, MODE_RESID | MODE_DOT_YY, nullptr, b, part_spare + c0, part_res + c0, nullptr, 0, stream));
     HIPK_DGM_TRY(complete(part_res));
     ++matvecs;
     HIPK_DGM_TRY(hipk_dot_parts(n, ch, x, x, HIPK_F64, part_xx + c0, stream));
@@ -2927,6 +2954,23 @@ extern "C" int hipk_dist_gmres_solve(hipk_csr_t A, const hipk_dist_plan *pl, con
 #undef HIPK_DGM_NCCL
 #undef HIPK_DGM_TRY
     return HIPK_OK;
+}
+
+extern "C" int hipk_dist_gmres_solve(hipk_csr_t A, const hipk_dist_plan *pl, const hipk_rccl *cc, const void *b_local, void *x_ext,
+                                     void *work, size_t work_bytes, const hipk_params *prm, hipk_stats *st, hipk_stream_t stream) {
+    return hipk_dist_gmres_t(A, pl, cc, nullptr, b_local, x_ext, work, work_bytes, prm, st, stream);
+}
+
+extern "C" size_t hipk_dist_pgmres_work_bytes(const hipk_dist_plan *plan, int restart) {
+    return hipk_dist_gmres_work_bytes(plan, restart);
+}
+
+extern "C" int hipk_dist_pgmres_solve(hipk_csr_t A, const hipk_dist_plan *pl, const hipk_rccl *cc, const void *dinv, const void *b_local,
+                                      void *x_ext, void *work, size_t work_bytes, const hipk_params *prm, hipk_stats *st,
+                                      hipk_stream_t stream) {
+    const int rc = hipk_dist_check(A, pl, cc, dinv, b_local, x_ext, work, prm, st);
+    if (rc != HIPK_OK) return rc;
+    return hipk_dist_gmres_t(A, pl, cc, (const double *)dinv, b_local, x_ext, work, work_bytes, prm, st, stream);
 }
 
 #ifdef HIPK_GM_STAMPS

@@ -79,6 +79,7 @@ class HaloPlan:
         dev = col_global.device
         owned = (col_global >= part.row0) & (col_global < part.row1)
         ghosts = torch.unique(col_global[~owned])                     # sorted global ids I need
+        self.ghosts = ghosts                                          # (halo position k holds global entry ghosts[k])
         self.n_ghost = int(ghosts.numel())
         owners = part.owner_of(ghosts)
         self.recv_splits = torch.bincount(owners, minlength=part.world).tolist() if self.n_ghost else [0] * part.world
@@ -353,6 +354,8 @@ class DistStats:
     x_norm: float
     threshold: float
     method: str = ""
+    preconditioner: str = ""     # "jacobi": M = diag(A)^-1 (residual_norm is then ||M (b - A x)||, as on one device)
+    solve_ms: float = 0.0        # the C-driven loops: device time of the solve (events around it on the solver's stream)
 
 
 class DistProblem:
@@ -488,9 +491,10 @@ def native_loop_ok(prob: DistProblem) -> bool:
 
 
 def _dist_cg_native(prob: DistProblem, x0_local, tol, atol, maxiter, check_every, solver: str = "cg", restart: int = 0,
-                    solve_method: str = "batched"):
+                    solve_method: str = "batched", dinv: Optional[torch.Tensor] = None):
     """One call into libhipk.so runs the whole loop of this rank (csrc/hipk_dist.hip): the host enqueues fixed batches
-    of iterations and reads the device stop word one batch late -- no Python between the kernels."""
+    of iterations and reads the device stop word one batch late -- no Python between the kernels.  `dinv`: the Jacobi
+    preconditioner's reciprocal diagonal with its halo tail (n_ext doubles, `jacobi_dinv_ext`) -- the hipk_dist_p*_solve loops."""
     import os
     from . import _hipk
     L, part, pl = _hipk.lib(), prob.part, prob.plan
@@ -519,13 +523,14 @@ def _dist_cg_native(prob: DistProblem, x0_local, tol, atol, maxiter, check_every
     x = prob.ops.zeros(n_ext)
     if x0_local is not None:
         x[:n] = x0_local
+    pre = "p" if dinv is not None else ""
+    if pre:
+        assert dinv.dtype == torch.float64 and dinv.numel() == max(prob.n_ext, 1) and dinv.device == x.device and dinv.is_contiguous()
+    solve_fn = getattr(L, f"hipk_dist_{pre}{solver}_solve")
     if solver == "gmres":
-        solve_fn = L.hipk_dist_gmres_solve
-        wb = int(L.hipk_dist_gmres_work_bytes(ctypes.byref(plan), int(restart)))
+        wb = int(getattr(L, f"hipk_dist_{pre}gmres_work_bytes")(ctypes.byref(plan), int(restart)))
     else:
-        work_bytes_fn, solve_fn = {"cg": (L.hipk_dist_cg_work_bytes, L.hipk_dist_cg_solve),
-                                   "bicgstab": (L.hipk_dist_bicgstab_work_bytes, L.hipk_dist_bicgstab_solve)}[solver]
-        wb = int(work_bytes_fn(ctypes.byref(plan)))
+        wb = int(getattr(L, f"hipk_dist_{pre}{solver}_work_bytes")(ctypes.byref(plan)))
     work = torch.empty(wb, dtype=torch.uint8, device=dev)
     prm = _hipk.Params()
     prm.tol, prm.atol = float(tol), float(atol)
@@ -537,45 +542,77 @@ def _dist_cg_native(prob: DistProblem, x0_local, tol, atol, maxiter, check_every
         prm.gpu_tolerances = 1          # the reference's `device.type == 'cuda'` tolerance branch (TSL:737-740)
     st = _hipk.Stats()
     with torch.cuda.device(dev):
-        rcode = solve_fn(prob.A["h"], ctypes.byref(plan), ctypes.byref(coll), prob.b.data_ptr(), x.data_ptr(),
+        pre_args = (dinv.data_ptr(),) if pre else ()
+        rcode = solve_fn(prob.A["h"], ctypes.byref(plan), ctypes.byref(coll), *pre_args, prob.b.data_ptr(), x.data_ptr(),
                          work.data_ptr(), wb, ctypes.byref(prm), ctypes.byref(st),
                          torch.cuda.current_stream(dev).cuda_stream)
-    _hipk._check(rcode, f"hipk_dist_{solver}_solve")
+    _hipk._check(rcode, f"hipk_dist_{pre}{solver}_solve")
     if getattr(prob, "p2p", None) is not None and prob.p2p.failed():
         raise RuntimeError("hipk_p2p: a rank never published its part of an exchange (wait bound hit); results discarded")
     return x[:n], int(st.info), DistStats(int(st.iterations), int(st.matvecs), int(st.info), st.b_norm, st.residual_norm,
-                                          st.x_norm, st.threshold)
+                                          st.x_norm, st.threshold, preconditioner="jacobi" if pre else "", solve_ms=float(st.solve_ms))
+
+
+def _need_native(prob: DistProblem, what: str) -> None:
+    if not native_loop_ok(prob):
+        raise RuntimeError(f"{what} needs the C-driven loop: HIP kernels, a collective provider and rows on every rank")
+
+
+def jacobi_dinv_ext(prob: DistProblem, dinv: torch.Tensor) -> torch.Tensor:
+    """The Jacobi preconditioner of the hipk_dist_p*_solve loops: this rank's reciprocal diagonal followed by its entries at
+    the halo positions (n_ext doubles on the rank's device).  `dinv` is either the rank's own rows (n_local entries, a
+    `JacobiPreconditioner` of the RowBlockCSR) -- the halo tail then comes from the owners through the halo plan, a collective
+    every rank makes -- or the whole vector (n_global entries, from a replicated global matrix), of which the rank takes its rows
+    and its ghost columns.  Either way the tail holds the owners' bits."""
+    part, pl = prob.part, prob.plan
+    n, dev = part.n_local, prob.ops.device
+    ext = torch.zeros(max(prob.n_ext, 1), dtype=torch.float64, device=dev)
+    if dinv.numel() == part.n_global:
+        ext[:n] = dinv[part.row0:part.row1].to(device=dev, dtype=torch.float64)
+        if pl.n_ghost:
+            ext[n:n + pl.n_ghost] = dinv[pl.ghosts.to(dinv.device)].to(device=dev, dtype=torch.float64)
+    else:
+        assert dinv.numel() == n, (dinv.numel(), n)
+        ext[:n] = dinv.to(device=dev, dtype=torch.float64)
+        if part.world > 1:
+            prob.halo_exchange(ext)
+    return ext
 
 
 def dist_bicgstab(prob: DistProblem, x0_local: Optional[torch.Tensor] = None, *, tol: float = 1e-5, atol: float = 0.0,
-                  maxiter: Optional[int] = None, check_every: int = 16):
+                  maxiter: Optional[int] = None, check_every: int = 16, dinv: Optional[torch.Tensor] = None):
     """Row-partitioned BiCGStab (`hipk_dist_bicgstab_solve`): returns (x_local, info, DistStats); bit for bit the iterates of the
     single-device `bicgstab`.  Only the C-driven loop exists (HIP kernels + a collective struct: direct RCCL, the mailboxes, or a
-    test's stand-ins) -- there is no backend-agnostic Python form of this solver."""
-    if not native_loop_ok(prob):
-        raise RuntimeError("dist_bicgstab needs the C-driven loop: HIP kernels, a collective provider and rows on every rank")
-    return _dist_cg_native(prob, x0_local, tol, atol, maxiter, check_every, solver="bicgstab")
+    test's stand-ins) -- there is no backend-agnostic Python form of this solver.  `dinv` (`jacobi_dinv_ext`): the Jacobi
+    preconditioned loop (`hipk_dist_pbicgstab_solve`), bit for bit `bicgstab(A, b, M=JacobiPreconditioner(A))`."""
+    _need_native(prob, "dist_bicgstab")
+    return _dist_cg_native(prob, x0_local, tol, atol, maxiter, check_every, solver="bicgstab", dinv=dinv)
 
 
 def dist_gmres(prob: DistProblem, x0_local: Optional[torch.Tensor] = None, *, tol: float = 1e-5, atol: float = 0.0,
-               restart: int = 20, maxiter: Optional[int] = None, solve_method: str = "batched"):
+               restart: int = 20, maxiter: Optional[int] = None, solve_method: str = "batched", dinv: Optional[torch.Tensor] = None):
     """Row-partitioned GMRES (`hipk_dist_gmres_solve`): returns (x_local, info, DistStats with iterations = restart cycles); bit
-    for bit the iterates of the single-device `gmres` on a CUDA tensor.  C-driven loop only, restart <= 31."""
-    if not native_loop_ok(prob):
-        raise RuntimeError("dist_gmres needs the C-driven loop: HIP kernels, a collective provider and rows on every rank")
+    for bit the iterates of the single-device `gmres` on a CUDA tensor.  C-driven loop only, restart <= 31.  `dinv`
+    (`jacobi_dinv_ext`): left Jacobi preconditioning (`hipk_dist_pgmres_solve`)."""
+    _need_native(prob, "dist_gmres")
     if solve_method not in ("batched", "incremental"):
         raise ValueError(f"invalid solve_method {solve_method}, must be either 'batched' or 'incremental'")
     if not 1 <= int(restart) <= 31:
         raise ValueError("dist_gmres: restart must be in [1, 31]")
-    return _dist_cg_native(prob, x0_local, tol, atol, maxiter, 0, solver="gmres", restart=restart, solve_method=solve_method)
+    return _dist_cg_native(prob, x0_local, tol, atol, maxiter, 0, solver="gmres", restart=restart, solve_method=solve_method,
+                           dinv=dinv)
 
 
 def dist_cg(prob: DistProblem, x0_local: Optional[torch.Tensor] = None, *, tol: float = 1e-5, atol: float = 0.0,
-            maxiter: Optional[int] = None, check_every: int = 32):
+            maxiter: Optional[int] = None, check_every: int = 32, dinv: Optional[torch.Tensor] = None):
     """Row-partitioned CG; returns (x_local, info, DistStats). Same stopping rule, same `info` rule and,
     bit for bit, the same iterates as the single-device solve.  On GPUs with direct RCCL the whole loop runs in C
     (`_dist_cg_native`); the Python loop below is the backend-agnostic form (CPU test double, torch.distributed
-    collectives, ranks without rows)."""
+    collectives, ranks without rows).  `dinv` (`jacobi_dinv_ext`): the Jacobi preconditioned loop (`hipk_dist_pcg_solve`), bit
+    for bit `cg(A, b, M=JacobiPreconditioner(A))`; it runs in C only."""
+    if dinv is not None:
+        _need_native(prob, "dist_cg with a Jacobi preconditioner")
+        return _dist_cg_native(prob, x0_local, tol, atol, maxiter, min(check_every, 16), dinv=dinv)
     if native_loop_ok(prob):
         return _dist_cg_native(prob, x0_local, tol, atol, maxiter, min(check_every, 16))
     ops, part, group = prob.ops, prob.part, prob.group
@@ -671,7 +708,13 @@ class RowBlockCSR:
     `info` is the same on every rank.  Rows are split on reduction-chunk boundaries of the GLOBAL problem (`RowPartition`), so
     the iterates are bitwise those of the single-device solve.  The halo plan, the device matrix (coded SpMV form included) and
     the communicator are built on the first solve and reused by later ones (repeated solves with one matrix: the LDC caller).
-    `M` (preconditioners), PyTrees, complex operands and autograd are not available on this operand (ValueError)."""
+
+    `M` may be a `JacobiPreconditioner`, built from this operand (`JacobiPreconditioner(A)`: the diagonal of the rank's own rows)
+    or from the replicated global matrix; both give the same bits, those of the single-device solve with
+    `M=JacobiPreconditioner(A_global)`.  Its reciprocal diagonal with the halo entries is formed on the first solve with it and
+    reused while the same preconditioner object is passed.  The Jacobi solves run on the C-driven loops only
+    (`hipk_dist_p*_solve`; RuntimeError without them).  Any other `M` (callables, `BlockJacobiPreconditioner`, matrices),
+    PyTrees, complex operands and autograd are not available on this operand (ValueError)."""
     _hipk_row_block = True
 
     def __init__(self, crow_local: torch.Tensor, col_global: torch.Tensor, values: torch.Tensor, n_global: int, *,
@@ -695,6 +738,7 @@ class RowBlockCSR:
         self.dtype, self.device = values.dtype, values.device
         self.group = group
         self._ops, self._problem_cls, self._prob = ops, problem_cls, None
+        self._jacobi = None          # (preconditioner, its dinv tensor, dinv with the halo tail): the cache of `_jacobi_ext`
         self.last_stats: Optional[DistStats] = None
 
     # ---- which rows a rank owns
@@ -730,7 +774,30 @@ class RowBlockCSR:
         self._prob.b = b_local.contiguous()
         return self._prob
 
-    def solve(self, method: str, b_local, x0_local=None, *, tol=1e-5, atol=0.0, maxiter=None, restart=20, solve_method="batched"):
+    def check_preconditioner(self, M) -> None:
+        """ValueError unless M is a JacobiPreconditioner of this global system (the one `M` a row-partitioned solve takes)."""
+        from .module_a.preconditioners import JacobiPreconditioner
+        if not isinstance(M, JacobiPreconditioner):
+            raise ValueError("preconditioners other than JacobiPreconditioner are not available on a RowBlockCSR (row-partitioned) "
+                             f"operand (got {type(M).__name__})")
+        if tuple(M.shape) != self.shape:
+            raise ValueError(f"JacobiPreconditioner of shape {tuple(M.shape)} for the {self.shape[0]} x {self.shape[1]} system")
+        rows = getattr(M, "row_range", None)
+        if rows is None and M.dinv.numel() != self.shape[0]:
+            raise ValueError(f"JacobiPreconditioner with {M.dinv.numel()} diagonal entries for the {self.shape[0]}-row system")
+        if rows is not None and tuple(rows) != (self.part.row0, self.part.row1):
+            raise ValueError(f"JacobiPreconditioner of rows {tuple(rows)} for the row block [{self.part.row0}, {self.part.row1})")
+
+    def _jacobi_ext(self, prob: "DistProblem", M) -> torch.Tensor:
+        c = self._jacobi
+        if c is None or c[0] is not M or c[1] is not M.dinv:
+            c = self._jacobi = (M, M.dinv, jacobi_dinv_ext(prob, M.dinv.detach()))
+        return c[2]
+
+    def solve(self, method: str, b_local, x0_local=None, *, tol=1e-5, atol=0.0, maxiter=None, restart=20, solve_method="batched",
+              M=None):
+        if M is not None:
+            self.check_preconditioner(M)
         if not isinstance(b_local, torch.Tensor) or b_local.ndim != 1 or b_local.numel() != self.part.n_local:
             raise ValueError(f"RowBlockCSR: b must be this rank's slice of the right-hand side ({self.part.n_local} entries, rows "
                              f"[{self.part.row0}, {self.part.row1}))")
@@ -738,22 +805,29 @@ class RowBlockCSR:
             raise ValueError(f"arrays in x0 and b must have matching shapes: {getattr(x0_local, 'shape', None)} vs {b_local.shape}")
         if b_local.device != self.val.device:
             raise ValueError("RowBlockCSR: b lives on another device than the matrix block")
+        if method not in ("cg", "bicgstab", "gmres"):
+            raise ValueError(f"Method '{method}' not available on a RowBlockCSR operand. Use: ['cg', 'bicgstab', 'gmres']")
         prob = self.problem(b_local.detach().to(torch.float64))
         x0 = None if x0_local is None else x0_local.detach().to(torch.float64)
+        dinv = None
+        if M is not None:
+            # before any collective of the preconditioner: the decision is the same on every rank (native_loop_ok is)
+            _need_native(prob, f"a Jacobi-preconditioned row-partitioned {method}")
+            dinv = self._jacobi_ext(prob, M)
         if method == "cg":
-            x, info, st = dist_cg(prob, x0, tol=tol, atol=atol, maxiter=maxiter)
+            x, info, st = dist_cg(prob, x0, tol=tol, atol=atol, maxiter=maxiter, dinv=dinv)
         elif method == "bicgstab":
-            x, info, st = dist_bicgstab(prob, x0, tol=tol, atol=atol, maxiter=maxiter)
-        elif method == "gmres":
-            x, info, st = dist_gmres(prob, x0, tol=tol, atol=atol, restart=restart, maxiter=maxiter, solve_method=solve_method)
+            x, info, st = dist_bicgstab(prob, x0, tol=tol, atol=atol, maxiter=maxiter, dinv=dinv)
         else:
-            raise ValueError(f"Method '{method}' not available on a RowBlockCSR operand. Use: ['cg', 'bicgstab', 'gmres']")
+            x, info, st = dist_gmres(prob, x0, tol=tol, atol=atol, restart=restart, maxiter=maxiter, solve_method=solve_method,
+                                     dinv=dinv)
         st.method = method
         self.last_stats = st
         return x.clone(), int(info), st
 
     def relative_residual(self) -> float:
-        """||b - A x|| / ||b|| of the GLOBAL system for the last solve's x (its true-residual epilogue, TSL:1007-1014 / 766-773)."""
+        """||b - A x|| / ||b|| of the GLOBAL system for the last solve's x (its true-residual epilogue, TSL:1007-1014 / 766-773);
+        after a Jacobi-preconditioned solve ||M (b - A x)|| / ||b||, the quantity that epilogue tests (TSL:1007)."""
         st = self.last_stats
         return float("nan") if st is None else (st.residual_norm / st.b_norm if st.b_norm > 0 else float("inf"))
 

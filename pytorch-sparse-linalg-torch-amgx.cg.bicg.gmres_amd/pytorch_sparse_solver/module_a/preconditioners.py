@@ -3,7 +3,9 @@
 The reference takes any callable `M`.  A `JacobiPreconditioner` IS such a callable (`M(v) = v / diag(A)`), so it
 works on every path and with the reference's own solvers; on the HIP fast path `cg` recognises it and runs the
 preconditioned iteration device-resident (`hipk_pcg_solve`: the scaling is fused into the update and direction
-kernels, 16 n extra bytes per iteration instead of a separate pass) -- SURVEY 8f-3.
+kernels, 16 n extra bytes per iteration instead of a separate pass) -- SURVEY 8f-3.  On a `RowBlockCSR` (one rank's rows of a
+global system) `JacobiPreconditioner(A)` holds the rank's slice of the reciprocal diagonal, and the row-partitioned
+cg / bicgstab / gmres run it in their C-driven loops (`hipk_dist_p*_solve`).
 """
 import torch
 
@@ -29,10 +31,44 @@ def _diagonal(A: torch.Tensor) -> torch.Tensor:
     return _diagonal(A.to_sparse_csr())
 
 
+def _row_block_diagonal(A) -> torch.Tensor:
+    """The diagonal of a RowBlockCSR's rows: the entries with global column row0 + i of local row i (duplicates add)."""
+    crow, col, val = A.crow, A.col, A.val
+    n, row0 = A.part.n_local, A.part.row0
+    rows = torch.repeat_interleave(torch.arange(n, device=val.device), crow[1:] - crow[:-1])
+    on = col == rows + row0
+    d = torch.zeros(n, dtype=val.dtype, device=val.device)
+    return d.index_add_(0, rows[on], val[on])
+
+
+def _all_ranks_ok(A, ok: bool) -> bool:
+    """MIN all-reduce of a flag over the RowBlockCSR's process group: a failing check on one rank fails on every rank, so no
+    rank goes on into the solve's set-up collectives while another has raised."""
+    import torch.distributed as dist
+    if A.part.world == 1 or not dist.is_initialized():
+        return ok
+    dev = A.val.device if dist.get_backend(A.group) == "nccl" else torch.device("cpu")
+    t = torch.tensor([1 if ok else 0], dtype=torch.int32, device=dev)
+    dist.all_reduce(t, op=dist.ReduceOp.MIN, group=A.group)
+    return bool(t.item())
+
+
 class JacobiPreconditioner:
-    """M(v) = v / diag(A).  `dinv` is the reciprocal diagonal, computed once (one rounding per entry)."""
+    """M(v) = v / diag(A).  `dinv` is the reciprocal diagonal, computed once (one rounding per entry).
+
+    `A` may be a `RowBlockCSR`: every rank of its process group builds the preconditioner from its block (a collective: a zero
+    on the diagonal of any rank's rows makes every rank raise).  `dinv` is then the rank's slice (rows `row_range`), `shape` the
+    global one, and M applies to the rank's slices of vectors."""
 
     def __init__(self, A: torch.Tensor):
+        if getattr(A, "_hipk_row_block", False) is True:
+            d = _row_block_diagonal(A)
+            if not _all_ranks_ok(A, not bool((d == 0).any())):
+                raise ValueError("JacobiPreconditioner: zero on the diagonal (of some rank's rows of the RowBlockCSR)")
+            self.dinv = torch.reciprocal(d)
+            self.shape = tuple(A.shape)
+            self.row_range = (A.part.row0, A.part.row1)
+            return
         if not (isinstance(A, torch.Tensor) and A.ndim == 2 and A.shape[0] == A.shape[1]):
             raise ValueError("JacobiPreconditioner needs a square matrix tensor")
         d = _diagonal(A.detach())

@@ -505,12 +505,16 @@ def _is_row_block(A) -> bool:
 
 def _dist_solve(kind: str, A, b, x0, tol, atol, maxiter, M, restart=20, solve_method='batched'):
     """cg / bicgstab / gmres on a RowBlockCSR operand: the row-partitioned solvers (distributed.py, csrc/hipk_dist.hip) behind the
-    reference's call surface.  Returns this rank's slice of x and the (rank-independent) info."""
-    if M is not None and M is not _identity:
-        raise ValueError(f"{kind}: preconditioners are not available on a RowBlockCSR (row-partitioned) operand")
+    reference's call surface.  Returns this rank's slice of x and the (rank-independent) info.  `M` may be a JacobiPreconditioner
+    (of the operand or of the global matrix): the Jacobi forms of the row-partitioned loops."""
+    if M is _identity:
+        M = None
+    if M is not None and _jacobi_of(M) is None:
+        raise ValueError(f"{kind}: preconditioners other than JacobiPreconditioner are not available on a RowBlockCSR "
+                         f"(row-partitioned) operand")
     if kind == 'gmres' and solve_method not in ('batched', 'incremental'):
         raise ValueError(f"Unsupported solve_method: {solve_method}")
-    x, info, st = A.solve(kind, b, x0, tol=tol, atol=atol, maxiter=maxiter, restart=restart, solve_method=solve_method)
+    x, info, st = A.solve(kind, b, x0, tol=tol, atol=atol, maxiter=maxiter, restart=restart, solve_method=solve_method, M=M)
     _set_stats(st)
     return x, info
 
