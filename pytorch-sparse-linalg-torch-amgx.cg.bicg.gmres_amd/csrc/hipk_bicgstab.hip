@@ -1029,8 +1029,6 @@ extern "C" int hipk_pbicgstab_solve_cb(hipk_csr_t A, hipk_precond_fn M, void *us
 // PRE (hipk_dist_pbicgstab_solve, M = diag(dinv)): the PRE instances of K1 / K3 / K5 as in hipk_pbicgstab_solve; the SpMVs multiply
 // phat = dinv .* p and shat = dinv .* s, so their halos are exchanged instead of those of p and s (ghost values: the owner's bits),
 // and `info` comes from ||M (b - A x)|| (the scaled residual SpMV).  The same five collective launches per iteration.
-#include <vector>
-
 #include "hipk_dist_xchg.h"
 
 struct hipk_dbi_layout {
@@ -1039,12 +1037,7 @@ struct hipk_dbi_layout {
 };
 static hipk_dbi_layout hipk_dbi_make_layout(const hipk_dist_plan *pl, bool pre) {
     hipk_dbi_layout L;
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        const size_t at = o;
-        o += hipk_align_up(bytes, 256);
-        return at;
-    };
+    hipk_carve take;
     const size_t per = (size_t)pl->per, W = (size_t)pl->world;
     const size_t next = (size_t)(pl->n_ext > 0 ? pl->n_ext : 1), nloc = (size_t)(pl->n_local > 0 ? pl->n_local : 1);
     L.scal = take(256);
@@ -1070,7 +1063,7 @@ static hipk_dbi_layout hipk_dbi_make_layout(const hipk_dist_plan *pl, bool pre) 
     L.t = take(next * 8);   // also the x-halo scratch of the residual SpMVs
     L.phat = pre ? take(next * 8) : L.p;   // PRE: the SpMV inputs, with their halo tails
     L.shat = pre ? take(next * 8) : L.s;
-    L.total = o;
+    L.total = take.o;
     return L;
 }
 extern "C" size_t hipk_dist_bicgstab_work_bytes(const hipk_dist_plan *plan) {
@@ -1082,37 +1075,11 @@ extern "C" size_t hipk_dist_pbicgstab_work_bytes(const hipk_dist_plan *plan) {
     return hipk_dbi_make_layout(plan, true).total;
 }
 
-#define HIPK_DBI_NCCL(expr, what)                                                          \
-    do {                                                                                   \
-        const int _r = (expr);                                                             \
-        if (_r != 0) {                                                                     \
-            hipk_set_error("%s: %s failed (ncclResult %d)", who, what, _r);                \
-            return HIPK_ERR_HIP;                                                           \
-        }                                                                                  \
-    } while (0)
-#define HIPK_DBI_TRY(expr)              \
-    do {                                \
-        const int _rc = (expr);         \
-        if (_rc != HIPK_OK) return _rc; \
-    } while (0)
-
 template <bool PRE>
 static int hipk_dist_bicgstab_t(hipk_csr_t A, const hipk_dist_plan *pl, const hipk_rccl *cc, const double *dinv, const void *b_local,
                                 void *x_ext, void *work, size_t work_bytes, const hipk_params *prm, hipk_stats *st, hipk_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    const char *who = PRE ? "hipk_dist_pbicgstab_solve" : "hipk_dist_bicgstab_solve";
-    HIPK_REQUIRE(A && pl && cc && b_local && x_ext && work && prm && st, HIPK_ERR_ARG, "null argument");
-    HIPK_REQUIRE(A->dtype == HIPK_F64, HIPK_ERR_UNSUPPORTED, "the row-partitioned solver is fp64");
-    HIPK_REQUIRE(pl->world >= 1 && pl->rank >= 0 && pl->rank < pl->world, HIPK_ERR_ARG, "rank / world");
-    HIPK_REQUIRE(pl->n_local > 0 && pl->n_local == A->n_rows && pl->n_ext >= pl->n_local, HIPK_ERR_ARG,
-                 "every rank must own rows (n_local > 0) and n_ext >= n_local");
-    HIPK_REQUIRE(pl->per >= 1 && (int64_t)pl->per * pl->world >= pl->g_red && pl->g_red >= 1 && pl->g_red <= HIPK_MAX_PARTS,
-                 HIPK_ERR_ARG, "partial-sum geometry");
-    HIPK_REQUIRE((pl->n_local + pl->chunk_rows - 1) / pl->chunk_rows <= pl->per, HIPK_ERR_ARG, "more local chunks than `per`");
-    HIPK_REQUIRE(cc->all_gather && cc->group_start && cc->group_end && (pl->world == 1 || pl->halo_mode == 0 || (cc->send && cc->recv)),
-                 HIPK_ERR_ARG, "missing collective entry points");
-    HIPK_REQUIRE((((uintptr_t)work) & 255u) == 0 && hipk_aligned16(x_ext) && hipk_aligned16(b_local), HIPK_ERR_ALIGN,
-                 "work must be 256-byte, x / b 16-byte aligned");
+    HIPK_TRY(hipk_dist_check(A, pl, cc, PRE, dinv, b_local, x_ext, work, prm, st));
     const hipk_dbi_layout L = hipk_dbi_make_layout(pl, PRE);
     HIPK_REQUIRE(work_bytes >= L.total, HIPK_ERR_WORKSPACE, "work too small");
     memset(st, 0, sizeof(*st));
@@ -1123,7 +1090,6 @@ static int hipk_dist_bicgstab_t(hipk_csr_t A, const hipk_dist_plan *pl, const hi
     double *g_rr = (double *)(wk + L.g_rr), *g_rhr = (double *)(wk + L.g_rhr), *g_rq = (double *)(wk + L.g_rq);
     double *g_ss = (double *)(wk + L.g_ss), *g_ts = (double *)(wk + L.g_ts), *g_tt = (double *)(wk + L.g_tt);
     double *g_bb = (double *)(wk + L.g_bb), *out4 = (double *)(wk + L.out4);
-    double *send_buf = (double *)(wk + L.send_buf), *slab_loc = (double *)(wk + L.slab_loc), *slab_all = (double *)(wk + L.slab_all);
     T *r = (T *)(wk + L.r), *rhat = (T *)(wk + L.rhat), *p = (T *)(wk + L.p), *q = (T *)(wk + L.q), *s = (T *)(wk + L.s);
     T *t = (T *)(wk + L.t), *phat = (T *)(wk + L.phat), *shat = (T *)(wk + L.shat);   // (= p, s without PRE)
     T *x = (T *)x_ext;
@@ -1134,8 +1100,10 @@ static int hipk_dist_bicgstab_t(hipk_csr_t A, const hipk_dist_plan *pl, const hi
     const int64_t maxiter = (prm->maxiter < 0) ? 10 * pl->n_global : prm->maxiter;   // TSL:982-984
     const float tolf = (float)prm->tol, atolf = (float)prm->atol;
     const double tol2 = (double)(tolf * tolf), atol_sq = (double)(atolf * atolf);
-    const int NCCL_F64 = 8;
-    enum { MODE_DOT_W = 1, MODE_DOT_YY = 2, MODE_RESID = 4 };
+    const int64_t *stop_dev = &scal->stop_it;
+    // grouped(): each exchange of the loop is one group at world > 1, whatever it carries
+    const hipk_dist_xchg xc(pl, cc, stream, (double *)(wk + L.send_buf), (double *)(wk + L.slab_loc), (double *)(wk + L.slab_all),
+                            PRE ? "hipk_dist_pbicgstab_solve" : "hipk_dist_bicgstab_solve");
 
     hipk_event_pair whole;
     HIPK_CHECK_HIP(whole.create());
@@ -1143,110 +1111,44 @@ static int hipk_dist_bicgstab_t(hipk_csr_t A, const hipk_dist_plan *pl, const hi
     HIPK_CHECK_HIP(hipMemsetAsync(wk, 0, L.total, stream));
     if (n_ext > n) HIPK_CHECK_HIP(hipMemsetAsync(x + n, 0, (size_t)(n_ext - n) * 8, stream));
 
-    auto gather = [&](const double *src, double *dst) -> int {
-        HIPK_DBI_NCCL(cc->all_gather(src, dst, (size_t)per, NCCL_F64, cc->comm, stream), "all_gather(partials)");
-        return HIPK_OK;
-    };
-    bool need_pack = false;
-    for (int peer = 0; peer < W; ++peer)
-        if (pl->send_counts[peer] > 0 && !(pl->send_first && pl->send_first[peer] >= 0)) need_pack = true;
-    auto halo_p2p_calls = [&](double *v) -> int {
-        size_t so = 0, ro = 0;
-        for (int peer = 0; peer < W; ++peer) {
-            const size_t ns = (size_t)pl->send_counts[peer], nr = (size_t)pl->recv_counts[peer];
-            const bool direct = pl->send_first && pl->send_first[peer] >= 0;
-            if (ns) HIPK_DBI_NCCL(cc->send(direct ? v + pl->send_first[peer] : send_buf + so, ns, NCCL_F64, peer, cc->comm, stream), "send(halo)");
-            if (nr) HIPK_DBI_NCCL(cc->recv(v + n + ro, nr, NCCL_F64, peer, cc->comm, stream), "recv(halo)");
-            so += ns;
-            ro += nr;
-        }
-        return HIPK_OK;
-    };
-    // the peers' entries this rank's rows reference -> v[n .. n_ext), optionally with all-gathers of partials in the same group
-    auto exchange = [&](double *v, const double *ps0, double *pd0) -> int {
-        if (W == 1) {
-            if (ps0) HIPK_DBI_TRY(gather(ps0, pd0));
-            return HIPK_OK;
-        }
-        const bool halo = v != nullptr && !(pl->n_send == 0 && pl->n_ghost == 0 && pl->halo_mode == 1);
-        if (halo && pl->halo_mode == 1 && pl->n_send && need_pack)
-            HIPK_DBI_TRY(hipk_gather(pl->n_send, pl->send_idx_dev, v, send_buf, HIPK_F64, stream));
-        if (halo && pl->halo_mode == 0 && pl->n_send)
-            HIPK_DBI_TRY(hipk_gather(pl->n_send, pl->send_idx_dev, v, slab_loc, HIPK_F64, stream));
-        HIPK_DBI_NCCL(cc->group_start(), "group_start");
-        if (ps0) HIPK_DBI_NCCL(cc->all_gather(ps0, pd0, (size_t)per, NCCL_F64, cc->comm, stream), "all_gather(partials)");
-        if (halo && pl->halo_mode == 1) HIPK_DBI_TRY(halo_p2p_calls(v));
-        if (halo && pl->halo_mode == 0)
-            HIPK_DBI_NCCL(cc->all_gather(slab_loc, slab_all, (size_t)pl->slab, NCCL_F64, cc->comm, stream), "all_gather(halo slabs)");
-        HIPK_DBI_NCCL(cc->group_end(), "group_end");
-        if (halo && pl->halo_mode == 0 && pl->n_ghost)
-            HIPK_DBI_TRY(hipk_gather(pl->n_ghost, pl->ghost_src_dev, slab_all, v + n, HIPK_F64, stream));
-        return HIPK_OK;
-    };
-    auto gather2 = [&](const double *a0, double *d0, const double *a1, double *d1) -> int {
-        if (W > 1) HIPK_DBI_NCCL(cc->group_start(), "group_start");
-        HIPK_DBI_NCCL(cc->all_gather(a0, d0, (size_t)per, NCCL_F64, cc->comm, stream), "all_gather(partials)");
-        HIPK_DBI_NCCL(cc->all_gather(a1, d1, (size_t)per, NCCL_F64, cc->comm, stream), "all_gather(partials)");
-        if (W > 1) HIPK_DBI_NCCL(cc->group_end(), "group_end");
-        return HIPK_OK;
-    };
-
     // ---- r0 = b - A x0 with <r0,r0>; <b,b>; rhat = p = q = r0, <rhat,r0> = <r0,r0>   (TSL:870-890)
     // (x carries its halo tail for the residual forms; t doubles as nothing here: x_ext is the caller's n_ext vector)
-    HIPK_DBI_TRY(exchange(x, nullptr, nullptr));
-    HIPK_DBI_TRY(hipk_spmv_ex(A, x, r, MODE_RESID | MODE_DOT_YY, nullptr, b, spare, part_a, nullptr, 0, stream));
-    HIPK_DBI_TRY(gather(part_a, g_rr));
-    HIPK_DBI_TRY(hipk_dot_parts(n, ch, b, b, HIPK_F64, part_a, stream));
-    HIPK_DBI_TRY(gather(part_a, g_bb));
+    HIPK_TRY(xc.grouped(x, nullptr, nullptr));
+    HIPK_TRY(hipk_spmv_ex(A, x, r, HIPK_SPMV_RESID | HIPK_SPMV_DOT_YY, nullptr, b, spare, part_a, nullptr, 0, stream));
+    HIPK_TRY(xc.parts(part_a, g_rr));
+    HIPK_TRY(hipk_dot_parts(n, ch, b, b, HIPK_F64, part_a, stream));
+    HIPK_TRY(xc.parts(part_a, g_bb));
     HIPK_CHECK_HIP(hipMemcpyAsync(g_rhr, g_rr, (size_t)W * per * 8, hipMemcpyDeviceToDevice, stream));
     hipk_bi_start_kernel<T><<<grid, HIPK_THREADS, 0, stream>>>(n, ch, G, scal, g_rr, g_bb, spare, r, rhat, p, q, tol2, atol_sq, maxiter,
                                                                 nullptr);
     HIPK_CHECK_HIP(hipGetLastError());
 
-    // ---- the loop: fixed batches, the stop word read one batch late (two reads in flight)
-    int64_t batch = prm->check_every > 0 ? prm->check_every : 16;
-    hipk_poller poll(A->host_poll);
-    HIPK_CHECK_HIP(poll.create());
-    const int64_t *stop_dev = &scal->stop_it;
+    // ---- the loop: fixed batches, the stop word read one batch late (hipk_dist_batches)
     int64_t it = 0, stop = INT64_MAX;
-    while (it < maxiter) {
-        const int64_t end = (it + batch < maxiter) ? it + batch : maxiter;
-        for (; it < end; ++it) {
-            hipk_bi_direction_kernel<T, PRE><<<grid, HIPK_THREADS, 0, stream>>>(n, ch, G, scal, it, g_rr, g_rhr, r, q, p, dinv, phat);
-            HIPK_DBI_TRY(exchange(phat, nullptr, nullptr));
-            HIPK_DBI_TRY(hipk_spmv_ex(A, phat, q, MODE_DOT_W, rhat, nullptr, part_a, spare, stop_dev, it, stream));
-            HIPK_DBI_TRY(gather(part_a, g_rq));
-            hipk_bi_supdate_kernel<T, PRE, false><<<grid, HIPK_THREADS, 0, stream>>>(n, ch, G, scal, it, g_rhr, g_rq, r, q, s, part_a,
-                                                                                    dinv, shat, 0);
-            HIPK_DBI_TRY(exchange(shat, part_a, g_ss));
-            HIPK_DBI_TRY(hipk_spmv_ex(A, shat, t, MODE_DOT_W | MODE_DOT_YY, s, nullptr, part_a, part_b, stop_dev, it, stream));
-            HIPK_DBI_TRY(gather2(part_a, g_ts, part_b, g_tt));
-            hipk_bi_xupdate_kernel<T, PRE, false><<<grid, HIPK_THREADS, 0, stream>>>(n, ch, G, scal, it, maxiter, g_ss, g_ts, g_tt, phat, s,
-                                                                                    t, rhat, x, r, part_a, part_b, shat, 0);
-            HIPK_DBI_TRY(gather2(part_a, g_rr, part_b, g_rhr));
-        }
-        HIPK_CHECK_HIP(hipGetLastError());
-        HIPK_CHECK_HIP(poll.post(stop_dev, it, stream));
-        if (poll.count == 2) {
-            HIPK_CHECK_HIP(hipEventSynchronize(poll.ev[poll.head]));
-            poll.harvest(&stop);
-        }
-        if (stop <= it - batch) break;
-    }
-    HIPK_CHECK_HIP(poll.drain(&stop));
+    HIPK_TRY(hipk_dist_batches(prm, A->host_poll, stop_dev, maxiter, stream, it, stop, [&](int64_t it) -> int {
+        hipk_bi_direction_kernel<T, PRE><<<grid, HIPK_THREADS, 0, stream>>>(n, ch, G, scal, it, g_rr, g_rhr, r, q, p, dinv, phat);
+        HIPK_TRY(xc.grouped(phat, nullptr, nullptr));
+        HIPK_TRY(hipk_spmv_ex(A, phat, q, HIPK_SPMV_DOT_W, rhat, nullptr, part_a, spare, stop_dev, it, stream));
+        HIPK_TRY(xc.parts(part_a, g_rq));
+        hipk_bi_supdate_kernel<T, PRE, false><<<grid, HIPK_THREADS, 0, stream>>>(n, ch, G, scal, it, g_rhr, g_rq, r, q, s, part_a,
+                                                                                dinv, shat, 0);
+        HIPK_TRY(xc.grouped(shat, part_a, g_ss));
+        HIPK_TRY(hipk_spmv_ex(A, shat, t, HIPK_SPMV_DOT_W | HIPK_SPMV_DOT_YY, s, nullptr, part_a, part_b, stop_dev, it, stream));
+        HIPK_TRY(xc.grouped(nullptr, part_a, g_ts, part_b, g_tt));
+        hipk_bi_xupdate_kernel<T, PRE, false><<<grid, HIPK_THREADS, 0, stream>>>(n, ch, G, scal, it, maxiter, g_ss, g_ts, g_tt, phat, s,
+                                                                                t, rhat, x, r, part_a, part_b, shat, 0);
+        return xc.grouped(nullptr, part_a, g_rr, part_b, g_rhr);
+    }));
 
     // ---- TSL:1007-1014: true residual (PRE: ||M (b - A x)||, the row scaling in the SpMV epilogue) and ||x|| decide info
-    HIPK_DBI_TRY(exchange(x, nullptr, nullptr));
-    if (PRE)
-        HIPK_DBI_TRY(hipk_dist_spmv(A, x, t, MODE_RESID | MODE_DOT_YY, nullptr, b, dinv, spare, part_a, nullptr, 0, stream));
-    else
-        HIPK_DBI_TRY(hipk_spmv_ex(A, x, t, MODE_RESID | MODE_DOT_YY, nullptr, b, spare, part_a, nullptr, 0, stream));
-    HIPK_DBI_TRY(gather(part_a, g_ss));
-    HIPK_DBI_TRY(hipk_reduce_parts(g_ss, G, out4 + 0, stream));
-    HIPK_DBI_TRY(hipk_dot_parts(n, ch, x, x, HIPK_F64, part_a, stream));
-    HIPK_DBI_TRY(gather(part_a, g_ts));
-    HIPK_DBI_TRY(hipk_reduce_parts(g_ts, G, out4 + 1, stream));
-    HIPK_DBI_TRY(hipk_reduce_parts(g_bb, G, out4 + 2, stream));
+    HIPK_TRY(xc.grouped(x, nullptr, nullptr));
+    HIPK_TRY(hipk_dist_spmv(A, x, t, HIPK_SPMV_RESID | HIPK_SPMV_DOT_YY, nullptr, b, dinv, spare, part_a, nullptr, 0, stream));
+    HIPK_TRY(xc.parts(part_a, g_ss));
+    HIPK_TRY(hipk_reduce_parts(g_ss, G, out4 + 0, stream));
+    HIPK_TRY(hipk_dot_parts(n, ch, x, x, HIPK_F64, part_a, stream));
+    HIPK_TRY(xc.parts(part_a, g_ts));
+    HIPK_TRY(hipk_reduce_parts(g_ts, G, out4 + 1, stream));
+    HIPK_TRY(hipk_reduce_parts(g_bb, G, out4 + 2, stream));
     double h4[4] = {0, 0, 0, 0};
     hipk_bi_scal hs;
     HIPK_CHECK_HIP(hipEventRecord(whole.b, stream));
@@ -1270,7 +1172,5 @@ extern "C" int hipk_dist_bicgstab_solve(hipk_csr_t A, const hipk_dist_plan *pl, 
 extern "C" int hipk_dist_pbicgstab_solve(hipk_csr_t A, const hipk_dist_plan *pl, const hipk_rccl *cc, const void *dinv,
                                          const void *b_local, void *x_ext, void *work, size_t work_bytes, const hipk_params *prm,
                                          hipk_stats *st, hipk_stream_t stream) {
-    const int rc = hipk_dist_check(A, pl, cc, dinv, b_local, x_ext, work, prm, st);
-    if (rc != HIPK_OK) return rc;
     return hipk_dist_bicgstab_t<true>(A, pl, cc, (const double *)dinv, b_local, x_ext, work, work_bytes, prm, st, stream);
 }

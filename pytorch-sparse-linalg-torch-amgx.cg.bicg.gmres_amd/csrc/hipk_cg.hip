@@ -1862,12 +1862,7 @@ struct hipk_dpcg_layout {
 };
 static hipk_dpcg_layout hipk_dpcg_make_layout(const hipk_dist_plan *pl) {
     hipk_dpcg_layout L;
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        const size_t at = o;
-        o += hipk_align_up(bytes, 256);
-        return at;
-    };
+    hipk_carve take;
     const size_t per = (size_t)pl->per, W = (size_t)pl->world;
     const size_t next = (size_t)(pl->n_ext > 0 ? pl->n_ext : 1), nloc = (size_t)(pl->n_local > 0 ? pl->n_local : 1);
     L.scal = take(256);
@@ -1886,7 +1881,7 @@ static hipk_dpcg_layout hipk_dpcg_make_layout(const hipk_dist_plan *pl) {
     L.p = take(next * 8);
     L.r = take(next * 8);
     L.Ap = take(nloc * 8);
-    L.total = o;
+    L.total = take.o;
     return L;
 }
 
@@ -1895,29 +1890,11 @@ extern "C" size_t hipk_dist_pcg_work_bytes(const hipk_dist_plan *plan) {
     return hipk_dpcg_make_layout(plan).total;
 }
 
-int hipk_dist_check(hipk_csr_s *A, const hipk_dist_plan *pl, const hipk_rccl *cc, const void *dinv, const void *b_local,
-                    void *x_ext, void *work, const hipk_params *prm, hipk_stats *st) {
-    HIPK_REQUIRE(A && pl && cc && dinv && b_local && x_ext && work && prm && st, HIPK_ERR_ARG, "null argument");
-    HIPK_REQUIRE(A->dtype == HIPK_F64, HIPK_ERR_UNSUPPORTED, "the row-partitioned solver is fp64");
-    HIPK_REQUIRE(pl->world >= 1 && pl->rank >= 0 && pl->rank < pl->world, HIPK_ERR_ARG, "rank / world");
-    HIPK_REQUIRE(pl->n_local > 0 && pl->n_local == A->n_rows && pl->n_ext >= pl->n_local, HIPK_ERR_ARG,
-                 "every rank must own rows (n_local > 0) and n_ext >= n_local");
-    HIPK_REQUIRE(pl->per >= 1 && (int64_t)pl->per * pl->world >= pl->g_red && pl->g_red >= 1 && pl->g_red <= HIPK_MAX_PARTS,
-                 HIPK_ERR_ARG, "partial-sum geometry");
-    HIPK_REQUIRE((pl->n_local + pl->chunk_rows - 1) / pl->chunk_rows <= pl->per, HIPK_ERR_ARG, "more local chunks than `per`");
-    HIPK_REQUIRE(cc->all_gather && cc->group_start && cc->group_end && (pl->world == 1 || pl->halo_mode == 0 || (cc->send && cc->recv)),
-                 HIPK_ERR_ARG, "missing collective entry points");
-    HIPK_REQUIRE((((uintptr_t)work) & 255u) == 0 && hipk_aligned16(x_ext) && hipk_aligned16(b_local) && hipk_aligned16(dinv),
-                 HIPK_ERR_ALIGN, "work must be 256-byte, x / b / dinv 16-byte aligned");
-    return HIPK_OK;
-}
-
 extern "C" int hipk_dist_pcg_solve(hipk_csr_t A, const hipk_dist_plan *pl, const hipk_rccl *cc, const void *dinv_ext,
                                    const void *b_local, void *x_ext, void *work, size_t work_bytes, const hipk_params *prm,
                                    hipk_stats *st, hipk_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    int rc = hipk_dist_check(A, pl, cc, dinv_ext, b_local, x_ext, work, prm, st);
-    if (rc != HIPK_OK) return rc;
+    HIPK_TRY(hipk_dist_check(A, pl, cc, true, dinv_ext, b_local, x_ext, work, prm, st));
     const hipk_dpcg_layout L = hipk_dpcg_make_layout(pl);
     HIPK_REQUIRE(work_bytes >= L.total, HIPK_ERR_WORKSPACE, "work too small");
     memset(st, 0, sizeof(*st));
@@ -1938,14 +1915,8 @@ extern "C" int hipk_dist_pcg_solve(hipk_csr_t A, const hipk_dist_plan *pl, const
     const float tolf = (float)prm->tol, atolf = (float)prm->atol;
     const double tol2 = (double)(tolf * tolf), atol_sq = (double)(atolf * atolf);
     const int64_t *stop_dev = &scal->stop_it;
-    hipk_dist_xchg xc{pl, cc, stream, (double *)(wk + L.send_buf), (double *)(wk + L.slab_loc), (double *)(wk + L.slab_all),
-                      "hipk_dist_pcg_solve", false};
-    xc.init();
-#define HIPK_DPCG_TRY(expr)               \
-    do {                                  \
-        const int _rc = (expr);           \
-        if (_rc != HIPK_OK) return _rc;   \
-    } while (0)
+    const hipk_dist_xchg xc(pl, cc, stream, (double *)(wk + L.send_buf), (double *)(wk + L.slab_loc), (double *)(wk + L.slab_all),
+                            "hipk_dist_pcg_solve");
 
     hipk_event_pair whole;
     HIPK_CHECK_HIP(whole.create());
@@ -1954,51 +1925,37 @@ extern "C" int hipk_dist_pcg_solve(hipk_csr_t A, const hipk_dist_plan *pl, const
     if (n_ext > n) HIPK_CHECK_HIP(hipMemsetAsync(x + n, 0, (size_t)(n_ext - n) * 8, stream));
 
     // ---- r0 = b - A x0, <r0,r0>; <b,b>; z0 = M r0, p0 = z0, gamma0 = <r0,z0> (TSL:815-826); the halo of p0 from its owners
-    HIPK_DPCG_TRY(xc.run(x, nullptr, nullptr));
-    HIPK_DPCG_TRY(hipk_dist_spmv(A, x, r, HIPK_SPMV_RESID | HIPK_SPMV_DOT_YY, nullptr, b, nullptr, spare, part_loc, nullptr, 0, stream));
-    HIPK_DPCG_TRY(xc.run(nullptr, part_loc, g_rr));
-    HIPK_DPCG_TRY(hipk_dot_parts(n, ch, b, b, HIPK_F64, part_loc, stream));
-    HIPK_DPCG_TRY(xc.run(nullptr, part_loc, g_bb));
+    HIPK_TRY(xc.run(x));
+    HIPK_TRY(hipk_dist_spmv(A, x, r, HIPK_SPMV_RESID | HIPK_SPMV_DOT_YY, nullptr, b, nullptr, spare, part_loc, nullptr, 0, stream));
+    HIPK_TRY(xc.parts(part_loc, g_rr));
+    HIPK_TRY(hipk_dot_parts(n, ch, b, b, HIPK_F64, part_loc, stream));
+    HIPK_TRY(xc.parts(part_loc, g_bb));
     hipk_pcg_start_kernel<T><<<grid, HIPK_THREADS, 0, stream>>>(n, ch, G, scal, g_rr, g_bb, r, dinv, p, part_rz, tol2, atol_sq,
                                                                  maxiter, nullptr);
     HIPK_CHECK_HIP(hipGetLastError());
-    HIPK_DPCG_TRY(xc.run(p, part_rz, g_rz[0]));
+    HIPK_TRY(xc.run(p, part_rz, g_rz[0]));
 
-    // ---- the loop: fixed batches, the stop word read one batch late (two reads in flight)
-    const int64_t batch = prm->check_every > 0 ? prm->check_every : 16;
-    hipk_poller poll(A->host_poll);
-    HIPK_CHECK_HIP(poll.create());
+    // ---- the loop: fixed batches, the stop word read one batch late (hipk_dist_batches)
     int64_t it = 0, stop = INT64_MAX;
-    while (it < maxiter) {
-        const int64_t end = (it + batch < maxiter) ? it + batch : maxiter;
-        for (; it < end; ++it) {
-            double *rz_old = g_rz[it & 1], *rz_new = g_rz[(it + 1) & 1];
-            HIPK_DPCG_TRY(hipk_dist_spmv(A, p, Ap, HIPK_SPMV_DOT_W, p, nullptr, nullptr, part_loc, spare, stop_dev, it, stream));
-            HIPK_DPCG_TRY(xc.run(nullptr, part_loc, g_pAp));
-            hipk_pcg_update_kernel<T><<<grid, HIPK_THREADS, 0, stream>>>(n, ch, G, scal, it, g_pAp, rz_old, Ap, dinv, r, part_loc,
-                                                                          part_rz);
-            HIPK_DPCG_TRY(xc.run(r, part_loc, g_rr, part_rz, rz_new));
-            hipk_pcg_direction_kernel<T><<<grid_ext, HIPK_THREADS, 0, stream>>>(n_ext, ch, G, scal, it, maxiter, g_pAp, rz_old, rz_new,
-                                                                                 g_rr, r, dinv, p, x);
-        }
-        HIPK_CHECK_HIP(hipGetLastError());
-        HIPK_CHECK_HIP(poll.post(stop_dev, it, stream));
-        if (poll.count == 2) {
-            HIPK_CHECK_HIP(hipEventSynchronize(poll.ev[poll.head]));
-            poll.harvest(&stop);
-        }
-        if (stop <= it - batch) break;   // the batch BEFORE the one just enqueued had already reached the stop
-    }
-    HIPK_CHECK_HIP(poll.drain(&stop));
+    HIPK_TRY(hipk_dist_batches(prm, A->host_poll, stop_dev, maxiter, stream, it, stop, [&](int64_t it) -> int {
+        double *rz_old = g_rz[it & 1], *rz_new = g_rz[(it + 1) & 1];
+        HIPK_TRY(hipk_dist_spmv(A, p, Ap, HIPK_SPMV_DOT_W, p, nullptr, nullptr, part_loc, spare, stop_dev, it, stream));
+        HIPK_TRY(xc.parts(part_loc, g_pAp));
+        hipk_pcg_update_kernel<T><<<grid, HIPK_THREADS, 0, stream>>>(n, ch, G, scal, it, g_pAp, rz_old, Ap, dinv, r, part_loc, part_rz);
+        HIPK_TRY(xc.run(r, part_loc, g_rr, part_rz, rz_new));
+        hipk_pcg_direction_kernel<T><<<grid_ext, HIPK_THREADS, 0, stream>>>(n_ext, ch, G, scal, it, maxiter, g_pAp, rz_old, rz_new,
+                                                                             g_rr, r, dinv, p, x);
+        return HIPK_OK;
+    }));
 
     // ---- TSL:1007-1014 with M: ||M (b - A x)||, ||x||
-    HIPK_DPCG_TRY(xc.run(x, nullptr, nullptr));
-    HIPK_DPCG_TRY(hipk_dist_spmv(A, x, Ap, HIPK_SPMV_RESID, nullptr, b, nullptr, spare, spare, nullptr, 0, stream));
+    HIPK_TRY(xc.run(x));
+    HIPK_TRY(hipk_dist_spmv(A, x, Ap, HIPK_SPMV_RESID, nullptr, b, nullptr, spare, spare, nullptr, 0, stream));
     hipk_pcg_resnorm_kernel<T><<<grid, HIPK_THREADS, 0, stream>>>(n, ch, Ap, dinv, part_loc);
     HIPK_CHECK_HIP(hipGetLastError());
-    HIPK_DPCG_TRY(xc.run(nullptr, part_loc, g_rr));
-    HIPK_DPCG_TRY(hipk_dot_parts(n, ch, x, x, HIPK_F64, part_loc, stream));
-    HIPK_DPCG_TRY(xc.run(nullptr, part_loc, g_xx));
+    HIPK_TRY(xc.parts(part_loc, g_rr));
+    HIPK_TRY(hipk_dot_parts(n, ch, x, x, HIPK_F64, part_loc, stream));
+    HIPK_TRY(xc.parts(part_loc, g_xx));
     hipk_pcg_final_kernel<<<1, HIPK_THREADS, 0, stream>>>(scal, G, g_rr, g_xx);
     HIPK_CHECK_HIP(hipGetLastError());
     hipk_pcg_scal hs;
@@ -2011,7 +1968,6 @@ extern "C" int hipk_dist_pcg_solve(hipk_csr_t A, const hipk_dist_plan *pl, const
     float ms = 0.f;
     HIPK_CHECK_HIP(hipEventElapsedTime(&ms, whole.a, whole.b));
     st->solve_ms = ms;
-#undef HIPK_DPCG_TRY
     return HIPK_OK;
 }
 

@@ -55,6 +55,13 @@ static inline void hipk_path_add(char (&chain)[128], const char *name) {
         }                                                                             \
     } while (0)
 
+// passes a failed hipk status (the callee has set the error text) up unchanged
+#define HIPK_TRY(expr)                  \
+    do {                                \
+        const int _rc = (expr);         \
+        if (_rc != HIPK_OK) return _rc; \
+    } while (0)
+
 static inline bool hipk_aligned16(const void *p) { return (((uintptr_t)p) & 15u) == 0; }
 
 // ---------------------------------------------------------------- chunk geometry

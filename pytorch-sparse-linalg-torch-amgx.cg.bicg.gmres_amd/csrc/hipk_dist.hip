@@ -17,15 +17,13 @@
 // other, and the number of collectives issued is identical on every rank (iterations past the stop are no-ops on the
 // device; their collectives still pair up).  The RCCL entry points come in as function pointers resolved from the
 // librccl that created the communicator (no link-time dependency; tests plug host-staged stand-ins in).
+//
+// The exchanges, the batch loop and the workspace carver are shared with the other five row-partitioned loops (csrc/
+// hipk_dist_xchg.h); their argument checks, hipk_dist_check, are defined here.
 #include <stdlib.h>
 
-#include <vector>
-
-#include "hipk_common.h"
+#include "hipk_dist_xchg.h"
 #include "hipk_fx.h"
-#include "hipk_solve.h"
-
-static inline size_t hipk_al(size_t v) { return hipk_align_up(v, 256); }
 
 struct hipk_dist_layout {
     size_t scal, part_loc, spare, g_pAp, g_rr, g_bb, out4, fx_loc, send_buf, slab_loc, slab_all, p, r, Ap, total;
@@ -33,12 +31,7 @@ struct hipk_dist_layout {
 
 static hipk_dist_layout hipk_dist_make_layout(const hipk_dist_plan *pl) {
     hipk_dist_layout L;
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        const size_t at = o;
-        o += hipk_al(bytes);
-        return at;
-    };
+    hipk_carve take;
     const size_t per = (size_t)pl->per, W = (size_t)pl->world;
     const size_t next = (size_t)(pl->n_ext > 0 ? pl->n_ext : 1), nloc = (size_t)(pl->n_local > 0 ? pl->n_local : 1);
     L.scal = take(256);
@@ -55,7 +48,7 @@ static hipk_dist_layout hipk_dist_make_layout(const hipk_dist_plan *pl) {
     L.p = take(next * 8);
     L.r = take(next * 8);
     L.Ap = take(nloc * 8);
-    L.total = o;
+    L.total = take.o;
     return L;
 }
 
@@ -64,36 +57,29 @@ extern "C" size_t hipk_dist_cg_work_bytes(const hipk_dist_plan *plan) {
     return hipk_dist_make_layout(plan).total;
 }
 
-#define HIPK_NCCL(expr, what)                                                        \
-    do {                                                                             \
-        const int _r = (expr);                                                       \
-        if (_r != 0) {                                                               \
-            hipk_set_error("hipk_dist_cg_solve: %s failed (ncclResult %d)", what, _r); \
-            return HIPK_ERR_HIP;                                                     \
-        }                                                                            \
-    } while (0)
-#define HIPK_TRY(expr)                  \
-    do {                                \
-        const int _rc = (expr);         \
-        if (_rc != HIPK_OK) return _rc; \
-    } while (0)
-
-extern "C" int hipk_dist_cg_solve(hipk_csr_t A, const hipk_dist_plan *pl, const hipk_rccl *cc, const void *b_local,
-                                  void *x_ext, void *work, size_t work_bytes, const hipk_params *prm, hipk_stats *st,
-                                  hipk_stream_t stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    HIPK_REQUIRE(A && pl && cc && b_local && x_ext && work && prm && st, HIPK_ERR_ARG, "null argument");
+int hipk_dist_check(const hipk_csr_s *A, const hipk_dist_plan *pl, const hipk_rccl *cc, bool pre, const void *dinv,
+                    const void *b_local, const void *x_ext, const void *work, const hipk_params *prm, const hipk_stats *st,
+                    const char *geometry) {
+    HIPK_REQUIRE(A && pl && cc && (dinv || !pre) && b_local && x_ext && work && prm && st, HIPK_ERR_ARG, "null argument");
     HIPK_REQUIRE(A->dtype == HIPK_F64, HIPK_ERR_UNSUPPORTED, "the row-partitioned solver is fp64");
     HIPK_REQUIRE(pl->world >= 1 && pl->rank >= 0 && pl->rank < pl->world, HIPK_ERR_ARG, "rank / world");
     HIPK_REQUIRE(pl->n_local > 0 && pl->n_local == A->n_rows && pl->n_ext >= pl->n_local, HIPK_ERR_ARG,
                  "every rank must own rows (n_local > 0) and n_ext >= n_local");
     HIPK_REQUIRE(pl->per >= 1 && (int64_t)pl->per * pl->world >= pl->g_red && pl->g_red >= 1 && pl->g_red <= HIPK_MAX_PARTS,
-                 HIPK_ERR_ARG, "partial-sum geometry");
+                 HIPK_ERR_ARG, geometry ? geometry : "partial-sum geometry");
     HIPK_REQUIRE((pl->n_local + pl->chunk_rows - 1) / pl->chunk_rows <= pl->per, HIPK_ERR_ARG, "more local chunks than `per`");
     HIPK_REQUIRE(cc->all_gather && cc->group_start && cc->group_end && (pl->world == 1 || pl->halo_mode == 0 || (cc->send && cc->recv)),
                  HIPK_ERR_ARG, "missing collective entry points");
-    HIPK_REQUIRE((((uintptr_t)work) & 255u) == 0 && hipk_aligned16(x_ext) && hipk_aligned16(b_local), HIPK_ERR_ALIGN,
-                 "work must be 256-byte, x / b 16-byte aligned");
+    HIPK_REQUIRE((((uintptr_t)work) & 255u) == 0 && hipk_aligned16(x_ext) && hipk_aligned16(b_local) && (!pre || hipk_aligned16(dinv)),
+                 HIPK_ERR_ALIGN, pre ? "work must be 256-byte, x / b / dinv 16-byte aligned" : "work must be 256-byte, x / b 16-byte aligned");
+    return HIPK_OK;
+}
+
+extern "C" int hipk_dist_cg_solve(hipk_csr_t A, const hipk_dist_plan *pl, const hipk_rccl *cc, const void *b_local,
+                                  void *x_ext, void *work, size_t work_bytes, const hipk_params *prm, hipk_stats *st,
+                                  hipk_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    HIPK_TRY(hipk_dist_check(A, pl, cc, false, nullptr, b_local, x_ext, work, prm, st));
     const hipk_dist_layout L = hipk_dist_make_layout(pl);
     HIPK_REQUIRE(work_bytes >= L.total, HIPK_ERR_WORKSPACE, "work too small");
     memset(st, 0, sizeof(*st));
@@ -103,7 +89,6 @@ extern "C" int hipk_dist_cg_solve(hipk_csr_t A, const hipk_dist_plan *pl, const 
     double *part_loc = (double *)(wk + L.part_loc), *spare = (double *)(wk + L.spare);
     double *g_pAp = (double *)(wk + L.g_pAp), *g_rr = (double *)(wk + L.g_rr), *g_bb = (double *)(wk + L.g_bb);
     double *out4 = (double *)(wk + L.out4);
-    double *send_buf = (double *)(wk + L.send_buf), *slab_loc = (double *)(wk + L.slab_loc), *slab_all = (double *)(wk + L.slab_all);
     double *p = (double *)(wk + L.p), *r = (double *)(wk + L.r), *Ap = (double *)(wk + L.Ap);
     double *x = (double *)x_ext;
     const double *b = (const double *)b_local;
@@ -111,8 +96,8 @@ extern "C" int hipk_dist_cg_solve(hipk_csr_t A, const hipk_dist_plan *pl, const 
     const int ch = pl->chunk_rows, G = pl->g_red, per = pl->per, W = pl->world;
     const int64_t *stop_dev = (const int64_t *)((char *)scal + 48);   // hipk_cg_scal::stop_it
     const int64_t maxiter = (prm->maxiter < 0) ? 10 * pl->n_global : prm->maxiter;   // TSL:982-984
-    const int NCCL_F64 = 8;
-    enum { MODE_DOT_W = 1, MODE_DOT_YY = 2, MODE_RESID = 4 };
+    const hipk_dist_xchg xc(pl, cc, stream, (double *)(wk + L.send_buf), (double *)(wk + L.slab_loc), (double *)(wk + L.slab_all),
+                            "hipk_dist_cg_solve");
 
     hipk_event_pair whole;
     HIPK_CHECK_HIP(whole.create());
@@ -122,76 +107,18 @@ extern "C" int hipk_dist_cg_solve(hipk_csr_t A, const hipk_dist_plan *pl, const 
     HIPK_CHECK_HIP(hipMemsetAsync(r, 0, (size_t)n_ext * 8, stream));
     if (n_ext > n) HIPK_CHECK_HIP(hipMemsetAsync(x + n, 0, (size_t)(n_ext - n) * 8, stream));
 
-    auto gather_parts = [&](double *dst) -> int {
-        HIPK_NCCL(cc->all_gather(part_loc, dst, (size_t)per, NCCL_F64, cc->comm, stream), "all_gather(partials)");
-        return HIPK_OK;
-    };
-    // the peers' entries this rank's rows reference -> v[n .. n_ext)   (neighbour send/recv pairs, one group)
-    // contiguous send ranges go out straight from the vector; the pack kernel runs only if some peer's list is scattered
-    bool need_pack = false;
-    for (int peer = 0; peer < W; ++peer)
-        if (pl->send_counts[peer] > 0 && !(pl->send_first && pl->send_first[peer] >= 0)) need_pack = true;
-    auto halo_p2p_calls = [&](double *v) -> int {
-        size_t so = 0, ro = 0;
-        for (int peer = 0; peer < W; ++peer) {
-            const size_t ns = (size_t)pl->send_counts[peer], nr = (size_t)pl->recv_counts[peer];
-            const bool direct = pl->send_first && pl->send_first[peer] >= 0;
-            if (ns) HIPK_NCCL(cc->send(direct ? v + pl->send_first[peer] : send_buf + so, ns, NCCL_F64, peer, cc->comm, stream), "send(halo)");
-            if (nr) HIPK_NCCL(cc->recv(v + n + ro, nr, NCCL_F64, peer, cc->comm, stream), "recv(halo)");
-            so += ns;
-            ro += nr;
-        }
-        return HIPK_OK;
-    };
-    auto halo_exchange = [&](double *v) -> int {   // stand-alone form (setup and the final residual)
-        if (W == 1 || (pl->n_send == 0 && pl->n_ghost == 0 && pl->halo_mode == 1)) return HIPK_OK;
-        if (pl->halo_mode == 1) {
-            if (pl->n_send && need_pack) HIPK_TRY(hipk_gather(pl->n_send, pl->send_idx_dev, v, send_buf, HIPK_F64, stream));
-            HIPK_NCCL(cc->group_start(), "group_start");
-            HIPK_TRY(halo_p2p_calls(v));
-            HIPK_NCCL(cc->group_end(), "group_end");
-        } else {
-            if (pl->n_send) HIPK_TRY(hipk_gather(pl->n_send, pl->send_idx_dev, v, slab_loc, HIPK_F64, stream));
-            HIPK_NCCL(cc->all_gather(slab_loc, slab_all, (size_t)pl->slab, NCCL_F64, cc->comm, stream), "all_gather(halo slabs)");
-            if (pl->n_ghost) HIPK_TRY(hipk_gather(pl->n_ghost, pl->ghost_src_dev, slab_all, v + n, HIPK_F64, stream));
-        }
-        return HIPK_OK;
-    };
-    // partials of <r,r> and the halo of r in ONE group
-    auto gather_parts_and_halo = [&](double *dst, double *v) -> int {
-        if (W == 1) return gather_parts(dst);
-        if (pl->halo_mode == 1) {
-            if (pl->n_send && need_pack) HIPK_TRY(hipk_gather(pl->n_send, pl->send_idx_dev, v, send_buf, HIPK_F64, stream));
-            HIPK_NCCL(cc->group_start(), "group_start");
-            HIPK_NCCL(cc->all_gather(part_loc, dst, (size_t)per, NCCL_F64, cc->comm, stream), "all_gather(partials)");
-            HIPK_TRY(halo_p2p_calls(v));
-            HIPK_NCCL(cc->group_end(), "group_end");
-        } else {
-            if (pl->n_send) HIPK_TRY(hipk_gather(pl->n_send, pl->send_idx_dev, v, slab_loc, HIPK_F64, stream));
-            HIPK_NCCL(cc->group_start(), "group_start");
-            HIPK_NCCL(cc->all_gather(part_loc, dst, (size_t)per, NCCL_F64, cc->comm, stream), "all_gather(partials)");
-            HIPK_NCCL(cc->all_gather(slab_loc, slab_all, (size_t)pl->slab, NCCL_F64, cc->comm, stream), "all_gather(halo slabs)");
-            HIPK_NCCL(cc->group_end(), "group_end");
-            if (pl->n_ghost) HIPK_TRY(hipk_gather(pl->n_ghost, pl->ghost_src_dev, slab_all, v + n, HIPK_F64, stream));
-        }
-        return HIPK_OK;
-    };
-
     // ---- r0 = b - A x0, <r0,r0>; <b,b> (TSL:815-826); halos of x and r0 explicitly once
-    HIPK_TRY(halo_exchange(x));
-    HIPK_TRY(hipk_spmv_ex(A, x, r, MODE_RESID | MODE_DOT_YY, nullptr, b, spare, part_loc, nullptr, 0, stream));
-    HIPK_TRY(gather_parts(g_rr));
+    HIPK_TRY(xc.run(x));
+    HIPK_TRY(hipk_spmv_ex(A, x, r, HIPK_SPMV_RESID | HIPK_SPMV_DOT_YY, nullptr, b, spare, part_loc, nullptr, 0, stream));
+    HIPK_TRY(xc.parts(part_loc, g_rr));
     HIPK_TRY(hipk_dot_parts(n, ch, b, b, HIPK_F64, part_loc, stream));
-    HIPK_TRY(gather_parts(g_bb));
-    HIPK_TRY(halo_exchange(r));
+    HIPK_TRY(xc.parts(part_loc, g_bb));
+    HIPK_TRY(xc.run(r));
     HIPK_TRY(hipk_cg_start(n, ch, G, scal, g_rr, g_bb, r, p, HIPK_F64, prm->tol, prm->atol, maxiter, stream));
     if (n_ext > n)   // p0 = r0 on the halo as well
         HIPK_CHECK_HIP(hipMemcpyAsync(p + n, r + n, (size_t)(n_ext - n) * 8, hipMemcpyDeviceToDevice, stream));
 
-    // ---- the loop: fixed batches, the stop word read one batch late (two reads in flight)
-    int64_t batch = prm->check_every > 0 ? prm->check_every : 16;
-    hipk_poller poll(A->host_poll);
-    HIPK_CHECK_HIP(poll.create());
+    // ---- the loop: fixed batches, the stop word read one batch late (hipk_dist_batches)
     int64_t it = 0, stop = INT64_MAX;
     // HIPK_DIST_OVERLAP=1 (opt-in): x += alpha p leaves the direction kernel and runs on a SIDE STREAM while the second collective
     // of the iteration (the <r,r> partials + the halo of r) is in flight -- it needs alpha (first collective) and the old p only;
@@ -244,10 +171,9 @@ extern "C" int hipk_dist_cg_solve(hipk_csr_t A, const hipk_dist_plan *pl, const 
             if (on) hipk_p2p_fx_end((hipk_p2p_s *)cc->fused, (unsigned long long)it);
         }
     } fx_release{cc, fused, it};
-    while (it < maxiter) {
-        const int64_t end = (it + batch < maxiter) ? it + batch : maxiter;
-        for (; fused && it < end; ++it) {
-            HIPK_TRY(hipk_spmv_ex(A, p, Ap, MODE_DOT_W, p, nullptr, part_loc, spare, stop_dev, it, stream));
+    HIPK_TRY(hipk_dist_batches(prm, A->host_poll, stop_dev, maxiter, stream, it, stop, [&](int64_t it) -> int {
+        HIPK_TRY(hipk_spmv_ex(A, p, Ap, HIPK_SPMV_DOT_W, p, nullptr, part_loc, spare, stop_dev, it, stream));
+        if (fused) {
             fx.seq = fx_seq0 + (unsigned long long)it;
             fx.ch = (int)(it & 1);
             fx.kind = 0;
@@ -257,40 +183,29 @@ extern "C" int hipk_dist_cg_solve(hipk_csr_t A, const hipk_dist_plan *pl, const 
             fx.kind = 1;
             fx.parts = spare;        // <r,r> partials (the update kernel's)
             fx.vec = r;
-            HIPK_TRY(hipk_cg_direction_fx(n_ext, n, ch, G, scal, it, maxiter, r, p, x, &fx, stream));
+            return hipk_cg_direction_fx(n_ext, n, ch, G, scal, it, maxiter, r, p, x, &fx, stream);
         }
-        for (; it < end; ++it) {
-            HIPK_TRY(hipk_spmv_ex(A, p, Ap, MODE_DOT_W, p, nullptr, part_loc, spare, stop_dev, it, stream));
-            HIPK_TRY(gather_parts(g_pAp));
-            HIPK_TRY(hipk_cg_update(n, ch, G, scal, it, g_pAp, Ap, r, part_loc, HIPK_F64, stream));
-            if (overlap) {
-                HIPK_CHECK_HIP(hipEventRecord(ev_upd, stream));
-                HIPK_CHECK_HIP(hipStreamWaitEvent(side, ev_upd, 0));
-                HIPK_TRY(hipk_cg_xupdate(n_ext, ch, G, scal, it, g_pAp, p, x, HIPK_F64, side));
-                HIPK_CHECK_HIP(hipEventRecord(ev_x, side));
-            }
-            HIPK_TRY(gather_parts_and_halo(g_rr, r));
-            if (overlap) HIPK_CHECK_HIP(hipStreamWaitEvent(stream, ev_x, 0));   // p is about to be replaced
-            HIPK_TRY(hipk_cg_direction(n_ext, ch, G, scal, it, maxiter, g_pAp, g_rr, r, p, overlap ? nullptr : x, HIPK_F64, stream));
+        HIPK_TRY(xc.parts(part_loc, g_pAp));
+        HIPK_TRY(hipk_cg_update(n, ch, G, scal, it, g_pAp, Ap, r, part_loc, HIPK_F64, stream));
+        if (overlap) {
+            HIPK_CHECK_HIP(hipEventRecord(ev_upd, stream));
+            HIPK_CHECK_HIP(hipStreamWaitEvent(side, ev_upd, 0));
+            HIPK_TRY(hipk_cg_xupdate(n_ext, ch, G, scal, it, g_pAp, p, x, HIPK_F64, side));
+            HIPK_CHECK_HIP(hipEventRecord(ev_x, side));
         }
-        // every rank posts and harvests at the same points: the decision below is a function of values all ranks share
-        HIPK_CHECK_HIP(poll.post(stop_dev, it, stream));
-        if (poll.count == 2) {
-            HIPK_CHECK_HIP(hipEventSynchronize(poll.ev[poll.head]));
-            poll.harvest(&stop);
-        }
-        if (stop <= it - batch) break;   // the batch BEFORE the one just enqueued had already reached the stop
-    }
-    HIPK_CHECK_HIP(poll.drain(&stop));
+        HIPK_TRY(xc.grouped(r, part_loc, g_rr));   // the <r,r> partials and the halo of r in ONE group
+        if (overlap) HIPK_CHECK_HIP(hipStreamWaitEvent(stream, ev_x, 0));   // p is about to be replaced
+        return hipk_cg_direction(n_ext, ch, G, scal, it, maxiter, g_pAp, g_rr, r, p, overlap ? nullptr : x, HIPK_F64, stream);
+    }));
     const int64_t iterations = stop < it ? stop : it;
 
     // ---- TSL:1007-1014: true residual and ||x|| decide info
-    HIPK_TRY(halo_exchange(x));
-    HIPK_TRY(hipk_spmv_ex(A, x, Ap, MODE_RESID | MODE_DOT_YY, nullptr, b, spare, part_loc, nullptr, 0, stream));
-    HIPK_TRY(gather_parts(g_rr));
+    HIPK_TRY(xc.run(x));
+    HIPK_TRY(hipk_spmv_ex(A, x, Ap, HIPK_SPMV_RESID | HIPK_SPMV_DOT_YY, nullptr, b, spare, part_loc, nullptr, 0, stream));
+    HIPK_TRY(xc.parts(part_loc, g_rr));
     HIPK_TRY(hipk_reduce_parts(g_rr, G, out4 + 0, stream));
     HIPK_TRY(hipk_dot_parts(n, ch, x, x, HIPK_F64, part_loc, stream));
-    HIPK_TRY(gather_parts(g_pAp));
+    HIPK_TRY(xc.parts(part_loc, g_pAp));
     HIPK_TRY(hipk_reduce_parts(g_pAp, G, out4 + 1, stream));
     HIPK_TRY(hipk_reduce_parts(g_bb, G, out4 + 2, stream));
     double h4[4] = {0, 0, 0, 0};

@@ -2719,24 +2719,14 @@ extern "C" size_t hipk_dist_gmres_work_bytes(const hipk_dist_plan *plan, int res
            hipk_align_up(slab * (size_t)plan->world * 8, 256);
 }
 
-static int hipk_dist_gmres_t(hipk_csr_t A, const hipk_dist_plan *pl, const hipk_rccl *cc, const double *dinv, const void *b_local,
-                             void *x_ext, void *work_, size_t work_bytes, const hipk_params *prm, hipk_stats *st, hipk_stream_t stream_) {
+static int hipk_dist_gmres_t(bool pre, hipk_csr_t A, const hipk_dist_plan *pl, const hipk_rccl *cc, const double *dinv,
+                             const void *b_local, void *x_ext, void *work_, size_t work_bytes, const hipk_params *prm, hipk_stats *st,
+                             hipk_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    const char *who = dinv ? "hipk_dist_pgmres_solve" : "hipk_dist_gmres_solve";
-    HIPK_REQUIRE(A && pl && cc && b_local && x_ext && work_ && prm && st, HIPK_ERR_ARG, "null argument");
-    HIPK_REQUIRE(A->dtype == HIPK_F64, HIPK_ERR_UNSUPPORTED, "the row-partitioned solver is fp64");
+    static const char *const geometry = "partial-sum geometry (per * world must not exceed 2048)";
+    HIPK_TRY(hipk_dist_check(A, pl, cc, pre, dinv, b_local, x_ext, work_, prm, st, pre ? nullptr : geometry));
     HIPK_REQUIRE(prm->restart >= 1 && prm->restart <= HIPK_GM_MAXM, HIPK_ERR_ARG, "restart must be in [1, 31]");
-    HIPK_REQUIRE(pl->world >= 1 && pl->rank >= 0 && pl->rank < pl->world, HIPK_ERR_ARG, "rank / world");
-    HIPK_REQUIRE(pl->n_local > 0 && pl->n_local == A->n_rows && pl->n_ext >= pl->n_local, HIPK_ERR_ARG,
-                 "every rank must own rows (n_local > 0) and n_ext >= n_local");
-    HIPK_REQUIRE(pl->per >= 1 && (int64_t)pl->per * pl->world >= pl->g_red && pl->g_red >= 1 && pl->g_red <= HIPK_MAX_PARTS &&
-                     (int64_t)pl->per * pl->world <= HIPK_MAX_PARTS,
-                 HIPK_ERR_ARG, "partial-sum geometry (per * world must not exceed 2048)");
-    HIPK_REQUIRE((pl->n_local + pl->chunk_rows - 1) / pl->chunk_rows <= pl->per, HIPK_ERR_ARG, "more local chunks than `per`");
-    HIPK_REQUIRE(cc->all_gather && cc->group_start && cc->group_end && (pl->world == 1 || pl->halo_mode == 0 || (cc->send && cc->recv)),
-                 HIPK_ERR_ARG, "missing collective entry points");
-    HIPK_REQUIRE((((uintptr_t)work_) & 255u) == 0 && hipk_aligned16(x_ext) && hipk_aligned16(b_local), HIPK_ERR_ALIGN,
-                 "work must be 256-byte, x / b 16-byte aligned");
+    HIPK_REQUIRE((int64_t)pl->per * pl->world <= HIPK_MAX_PARTS, HIPK_ERR_ARG, geometry);
     HIPK_REQUIRE(work_bytes >= hipk_dist_gmres_work_bytes(pl, prm->restart), HIPK_ERR_WORKSPACE, "work too small");
     memset(st, 0, sizeof(*st));
     typedef double T;
@@ -2758,30 +2748,14 @@ static int hipk_dist_gmres_t(hipk_csr_t A, const hipk_dist_plan *pl, const hipk_
     T *V = (T *)vbase;
     T *tmp = (T *)(vbase + (size_t)(m + 1) * vec);
     char *cbase = vbase + (size_t)(m + 2) * vec;
-    double *send_buf = (double *)cbase;
     double *slab_loc = (double *)(cbase + hipk_align_up((size_t)(pl->n_send > 0 ? pl->n_send : 1) * 8, 256));
     double *slab_all = (double *)((char *)slab_loc + hipk_align_up((size_t)(pl->slab > 0 ? pl->slab : 1) * 8, 256));
+    const hipk_dist_xchg xc(pl, cc, stream, (double *)cbase, slab_loc, slab_all, pre ? "hipk_dist_pgmres_solve" : "hipk_dist_gmres_solve");
     T *x = (T *)x_ext;
     const T *b = (const T *)b_local;
     const int incremental = (prm->gmres_method == HIPK_GMRES_INCREMENTAL) ? 1 : 0;
     const double eps_t = HIPK_EPS64;
     const int64_t maxiter = (prm->maxiter < 0) ? 10 * pl->n_global : prm->maxiter;  // TSL:719-721
-    const int NCCL_F64 = 8;
-    enum { MODE_DOT_YY = 2, MODE_RESID = 4 };
-
-#define HIPK_DGM_NCCL(expr, what)                                                       \
-    do {                                                                                \
-        const int _r = (expr);                                                          \
-        if (_r != 0) {                                                                  \
-            hipk_set_error("%s: %s failed (ncclResult %d)", who, what, _r);               \
-            return HIPK_ERR_HIP;                                                        \
-        }                                                                               \
-    } while (0)
-#define HIPK_DGM_TRY(expr)              \
-    do {                                \
-        const int _rc = (expr);         \
-        if (_rc != HIPK_OK) return _rc; \
-    } while (0)
 
     hipk_event_pair whole;
     HIPK_CHECK_HIP(whole.create());
@@ -2789,51 +2763,18 @@ static int hipk_dist_gmres_t(hipk_csr_t A, const hipk_dist_plan *pl, const hipk_
     HIPK_CHECK_HIP(hipMemsetAsync(work, 0, hipk_dist_gmres_work_bytes(pl, m), stream));
     if (n_ext > n) HIPK_CHECK_HIP(hipMemsetAsync(x + n, 0, (size_t)(n_ext - n) * 8, stream));
 
-    // in-place all-gather of a global partial array: every rank wrote its `per` entries at arr + c0
-    auto complete = [&](double *arr) -> int {
-        HIPK_DGM_NCCL(cc->all_gather(arr + c0, arr, (size_t)per, NCCL_F64, cc->comm, stream), "all_gather(partials)");
-        return HIPK_OK;
-    };
-    bool need_pack = false;
-    for (int peer = 0; peer < W; ++peer)
-        if (pl->send_counts[peer] > 0 && !(pl->send_first && pl->send_first[peer] >= 0)) need_pack = true;
-    auto halo = [&](double *v) -> int {   // the peers' entries this rank's rows reference -> v[n .. n_ext)
-        if (W == 1 || (pl->n_send == 0 && pl->n_ghost == 0 && pl->halo_mode == 1)) return HIPK_OK;
-        if (pl->halo_mode == 1) {
-            if (pl->n_send && need_pack) HIPK_DGM_TRY(hipk_gather(pl->n_send, pl->send_idx_dev, v, send_buf, HIPK_F64, stream));
-            HIPK_DGM_NCCL(cc->group_start(), "group_start");
-            size_t so = 0, ro = 0;
-            for (int peer = 0; peer < W; ++peer) {
-                const size_t ns = (size_t)pl->send_counts[peer], nr = (size_t)pl->recv_counts[peer];
-                const bool direct = pl->send_first && pl->send_first[peer] >= 0;
-                if (ns) HIPK_DGM_NCCL(cc->send(direct ? v + pl->send_first[peer] : send_buf + so, ns, NCCL_F64, peer, cc->comm, stream), "send(halo)");
-                if (nr) HIPK_DGM_NCCL(cc->recv(v + n + ro, nr, NCCL_F64, peer, cc->comm, stream), "recv(halo)");
-                so += ns;
-                ro += nr;
-            }
-            HIPK_DGM_NCCL(cc->group_end(), "group_end");
-        } else {
-            if (pl->n_send) HIPK_DGM_TRY(hipk_gather(pl->n_send, pl->send_idx_dev, v, slab_loc, HIPK_F64, stream));
-            HIPK_DGM_NCCL(cc->all_gather(slab_loc, slab_all, (size_t)pl->slab, NCCL_F64, cc->comm, stream), "all_gather(halo slabs)");
-            if (pl->n_ghost) HIPK_DGM_TRY(hipk_gather(pl->n_ghost, pl->ghost_src_dev, slab_all, v + n, HIPK_F64, stream));
-        }
-        return HIPK_OK;
-    };
-
     // residual = b - A x0 into column 0, unit residual + norm (TSL:791-792); <b,b>
     auto residual = [&]() -> int {
-        HIPK_DGM_TRY(halo(x));
-        if (dinv)   // M (b - A x0), its squared norm (TSL:791)
-            HIPK_DGM_TRY(hipk_dist_spmv(A, x, V, MODE_RESID | MODE_DOT_YY, nullptr, b, dinv, part_spare + c0, part_res + c0, nullptr, 0, stream));
-        else
-            HIPK_DGM_TRY(hipk_spmv_ex(A, x, V, MODE_RESID | MODE_DOT_YY, nullptr, b, part_spare + c0, part_res + c0, nullptr, 0, stream));
-        HIPK_DGM_TRY(complete(part_res));
+        HIPK_TRY(xc.run(x));
+        // with dinv: M (b - A x0), its squared norm (TSL:791)
+        HIPK_TRY(hipk_dist_spmv(A, x, V, HIPK_SPMV_RESID | HIPK_SPMV_DOT_YY, nullptr, b, dinv, part_spare + c0, part_res + c0, nullptr, 0, stream));
+        HIPK_TRY(xc.parts(part_res));
         hipk_gm_resnorm_kernel<T><<<gl, HIPK_THREADS, 0, stream>>>(n, ch, G, scal, V, part_res, part_bb, eps_t);
         return hipGetLastError() == hipSuccess ? HIPK_OK : HIPK_ERR_HIP;
     };
-    HIPK_DGM_TRY(hipk_dot_parts(n, ch, b, b, HIPK_F64, part_bb + c0, stream));
-    HIPK_DGM_TRY(complete(part_bb));
-    HIPK_DGM_TRY(residual());
+    HIPK_TRY(hipk_dot_parts(n, ch, b, b, HIPK_F64, part_bb + c0, stream));
+    HIPK_TRY(xc.parts(part_bb));
+    HIPK_TRY(residual());
     int64_t matvecs = 1;
     double head[2];
     HIPK_CHECK_HIP(hipMemcpyAsync(head, scal, sizeof(head), hipMemcpyDeviceToHost, stream));
@@ -2852,9 +2793,9 @@ static int hipk_dist_gmres_t(hipk_csr_t A, const hipk_dist_plan *pl, const hipk_
     if (dinv) {
         hipk_gm_scaled_sq_kernel<T><<<gl, HIPK_THREADS, 0, stream>>>(n, ch, b, dinv, part_spare + c0);
         HIPK_CHECK_HIP(hipGetLastError());
-        HIPK_DGM_TRY(complete(part_spare));
+        HIPK_TRY(xc.parts(part_spare));
         double *mb_dev = part_xx;  // the <x,x> slot is unused until the end of the solve
-        HIPK_DGM_TRY(hipk_reduce_parts(part_spare, G, mb_dev, stream));
+        HIPK_TRY(hipk_reduce_parts(part_spare, G, mb_dev, stream));
         double mb2 = 0.0;
         HIPK_CHECK_HIP(hipMemcpyAsync(&mb2, mb_dev, sizeof(double), hipMemcpyDeviceToHost, stream));
         HIPK_CHECK_HIP(hipStreamSynchronize(stream));
@@ -2871,23 +2812,21 @@ static int hipk_dist_gmres_t(hipk_csr_t A, const hipk_dist_plan *pl, const hipk_
         hipk_gm_cycle_init_kernel<<<1, HIPK_THREADS, 0, stream>>>(scal, incremental, ptol);
         for (int k = 0; k < m; ++k) {
             T *vk = V + (int64_t)k * ldv, *w = V + (int64_t)(k + 1) * ldv;
-            HIPK_DGM_TRY(halo(vk));
-            if (dinv)   // w = M (A v_k), ||w||^2 of the scaled vector (TSL:351-352)
-                HIPK_DGM_TRY(hipk_dist_spmv(A, vk, w, MODE_DOT_YY, nullptr, nullptr, dinv, part_spare + c0, part_ww + c0, &scal->stop_step, k,
-                                            stream));
-            else
-                HIPK_DGM_TRY(hipk_spmv_ex(A, vk, w, MODE_DOT_YY, nullptr, nullptr, part_spare + c0, part_ww + c0, &scal->stop_step, k, stream));
-            HIPK_DGM_TRY(complete(part_ww));
+            HIPK_TRY(xc.run(vk));
+            // with dinv: w = M (A v_k), ||w||^2 of the scaled vector (TSL:351-352)
+            HIPK_TRY(hipk_dist_spmv(A, vk, w, HIPK_SPMV_DOT_YY, nullptr, nullptr, dinv, part_spare + c0, part_ww + c0, &scal->stop_step, k,
+                                    stream));
+            HIPK_TRY(xc.parts(part_ww));
             for (int pass = 0; pass < 2; ++pass) {
                 if (pass == 1) hipk_gm_decide_kernel<<<1, HIPK_THREADS, 0, stream>>>(scal, k, G, part_qq, eps_t);
                 const int mg = gl * (k / 8 + 1);
                 hipk_gm_multidot_stream_kernel<T, 8><<<mg, HIPK_THREADS, 0, stream>>>(n, ch, scal, k, pass, V, ldv, w, part_md + c0, gl, nres);
-                if (W > 1) HIPK_DGM_NCCL(cc->group_start(), "group_start");
-                for (int j = 0; j <= k; ++j) HIPK_DGM_TRY(complete(part_md + (size_t)j * HIPK_MAX_PARTS));
-                if (W > 1) HIPK_DGM_NCCL(cc->group_end(), "group_end");
+                if (W > 1) HIPK_TRY(xc.group_start());   // (also for k = 0)
+                for (int j = 0; j <= k; ++j) HIPK_TRY(xc.parts(part_md + (size_t)j * HIPK_MAX_PARTS));
+                if (W > 1) HIPK_TRY(xc.group_end());
                 hipk_gm_hreduce_kernel<<<k + 1, HIPK_THREADS, 0, stream>>>(scal, k, pass, G, part_md);
                 hipk_gm_update_stream_kernel<T, HIPK_GM_LDH><<<gl, HIPK_THREADS, 0, stream>>>(n, ch, scal, k, pass, V, ldv, w, part_qq + c0, nres);
-                HIPK_DGM_TRY(complete(part_qq));
+                HIPK_TRY(xc.parts(part_qq));
             }
             hipk_gm_normalize_kernel<T><<<gl, HIPK_THREADS, 0, stream>>>(n, ch, G, scal, k, w, part_qq, part_ww, eps_t, 0, 0);
         }
@@ -2913,7 +2852,7 @@ static int hipk_dist_gmres_t(hipk_csr_t A, const hipk_dist_plan *pl, const hipk_
             }
             hipk_gm_xupdate_kernel<T><<<gl, HIPK_THREADS, 0, stream>>>(n, ch, k, V, ldv, x, yy);
         }
-        HIPK_DGM_TRY(residual());
+        HIPK_TRY(residual());
         ++matvecs;
         if (hipMemcpyAsync(head, scal, sizeof(head), hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) {
             hipk_set_error("hipk_dist_gmres_solve: HIP failure at the end of a restart cycle");
@@ -2924,15 +2863,12 @@ static int hipk_dist_gmres_t(hipk_csr_t A, const hipk_dist_plan *pl, const hipk_
     }
 
     // TSL:766-773
-    HIPK_DGM_TRY(halo(x));
-    if (dinv)
-        HIPK_DGM_TRY(hipk_dist_spmv(A, x, tmp, MODE_RESID | MODE_DOT_YY, nullptr, b, dinv, part_spare + c0, part_res + c0, nullptr, 0, stream));
-    else
-        HIPK_DGM_TRY(hipk_spmv_ex(A, x, tmp, MODE_RESID | MODE_DOT_YY, nullptr, b, part_spare + c0, part_res + c0, nullptr, 0, stream));
-    HIPK_DGM_TRY(complete(part_res));
+    HIPK_TRY(xc.run(x));
+    HIPK_TRY(hipk_dist_spmv(A, x, tmp, HIPK_SPMV_RESID | HIPK_SPMV_DOT_YY, nullptr, b, dinv, part_spare + c0, part_res + c0, nullptr, 0, stream));
+    HIPK_TRY(xc.parts(part_res));
     ++matvecs;
-    HIPK_DGM_TRY(hipk_dot_parts(n, ch, x, x, HIPK_F64, part_xx + c0, stream));
-    HIPK_DGM_TRY(complete(part_xx));
+    HIPK_TRY(hipk_dot_parts(n, ch, x, x, HIPK_F64, part_xx + c0, stream));
+    HIPK_TRY(xc.parts(part_xx));
     hipk_gm_final_kernel<<<1, HIPK_THREADS, 0, stream>>>(scal, G, part_res, part_xx);
     HIPK_CHECK_HIP(hipGetLastError());
     double fin[4];
@@ -2951,14 +2887,12 @@ static int hipk_dist_gmres_t(hipk_csr_t A, const hipk_dist_plan *pl, const hipk_
     float ms = 0.f;
     HIPK_CHECK_HIP(hipEventElapsedTime(&ms, whole.a, whole.b));
     st->solve_ms = ms;
-#undef HIPK_DGM_NCCL
-#undef HIPK_DGM_TRY
     return HIPK_OK;
 }
 
 extern "C" int hipk_dist_gmres_solve(hipk_csr_t A, const hipk_dist_plan *pl, const hipk_rccl *cc, const void *b_local, void *x_ext,
                                      void *work, size_t work_bytes, const hipk_params *prm, hipk_stats *st, hipk_stream_t stream) {
-    return hipk_dist_gmres_t(A, pl, cc, nullptr, b_local, x_ext, work, work_bytes, prm, st, stream);
+    return hipk_dist_gmres_t(false, A, pl, cc, nullptr, b_local, x_ext, work, work_bytes, prm, st, stream);
 }
 
 extern "C" size_t hipk_dist_pgmres_work_bytes(const hipk_dist_plan *plan, int restart) {
@@ -2968,9 +2902,7 @@ extern "C" size_t hipk_dist_pgmres_work_bytes(const hipk_dist_plan *plan, int re
 extern "C" int hipk_dist_pgmres_solve(hipk_csr_t A, const hipk_dist_plan *pl, const hipk_rccl *cc, const void *dinv, const void *b_local,
                                       void *x_ext, void *work, size_t work_bytes, const hipk_params *prm, hipk_stats *st,
                                       hipk_stream_t stream) {
-    const int rc = hipk_dist_check(A, pl, cc, dinv, b_local, x_ext, work, prm, st);
-    if (rc != HIPK_OK) return rc;
-    return hipk_dist_gmres_t(A, pl, cc, (const double *)dinv, b_local, x_ext, work, work_bytes, prm, st, stream);
+    return hipk_dist_gmres_t(true, A, pl, cc, (const double *)dinv, b_local, x_ext, work, work_bytes, prm, st, stream);
 }
 
 #ifdef HIPK_GM_STAMPS

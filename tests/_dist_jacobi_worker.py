@@ -50,22 +50,48 @@ def _from_block(self, crow, col_global, val, b_local, part, ops):
 
 
 class StagedCounting(HostStagedNative):
-    """Host-staged collectives; counts the group_end calls the C-driven loop makes."""
+    """Host-staged collectives; records every collective call the C-driven loop makes, in order: ("group_start",),
+    ("group_end",), ("all_gather", count, in_place), ("send", count, peer), ("recv", count, peer).  fail_nth = n: the n-th
+    all_gather from then on returns ncclResult 7 instead of running."""
 
     def __init__(self, crow, col_global, val, b_local, part, ops, group=None):
         _from_block(self, crow, col_global, val, b_local, part, ops)
-        self.group_ends = 0
+        self.calls, self.fail_nth = [], None
 
     def coll_struct(self):
-        if getattr(self, "_counted", None) is None:
+        if getattr(self, "_recorded", None) is None:
             coll = super().coll_struct()
-            inner = self._cbs[1]
+            g_start, g_end, a_gather, c_send, c_recv = self._cbs
+            rank, calls = self.part.rank, self.calls
+
+            def group_start():
+                calls.append(("group_start",))
+                return g_start()
 
             def group_end():
-                self.group_ends += 1
-                return inner()
-            self._counted = _hipk.COLL_GROUP_FN(group_end)
-            coll.group_end = ctypes.cast(self._counted, ctypes.c_void_p).value
+                calls.append(("group_end",))
+                return g_end()
+
+            def all_gather(send, recv, count, dtype, comm, stream):
+                calls.append(("all_gather", int(count), send == recv + rank * count * 8))   # in place: arr + rank * per -> arr
+                if self.fail_nth is not None:
+                    self.fail_nth -= 1
+                    if self.fail_nth == 0:
+                        self.fail_nth = None
+                        return 7
+                return a_gather(send, recv, count, dtype, comm, stream)
+
+            def send(buf, count, dtype, peer, comm, stream):
+                calls.append(("send", int(count), int(peer)))
+                return c_send(buf, count, dtype, peer, comm, stream)
+
+            def recv(buf, count, dtype, peer, comm, stream):
+                calls.append(("recv", int(count), int(peer)))
+                return c_recv(buf, count, dtype, peer, comm, stream)
+            self._recorded = (_hipk.COLL_GROUP_FN(group_start), _hipk.COLL_GROUP_FN(group_end),
+                              _hipk.COLL_ALLGATHER_FN(all_gather), _hipk.COLL_SENDRECV_FN(send), _hipk.COLL_SENDRECV_FN(recv))
+            addr = lambda f: ctypes.cast(f, ctypes.c_void_p).value   # noqa: E731
+            coll.group_start, coll.group_end, coll.all_gather, coll.send, coll.recv = [addr(f) for f in self._recorded]
         return self._coll
 
 
@@ -128,7 +154,7 @@ def hip_task(a, rank, world):
     n = A.shape[0]
     r0, r1 = pss.RowBlockCSR.row_range(n)
     dev = torch.device("cuda", 0)
-    from pytorch_sparse_solver.distributed import HipOps, dist_cg
+    from pytorch_sparse_solver.distributed import HipOps
     cls = FusedMailbox if a.get("comm") == "fused" else StagedCounting
     Arb = pss.RowBlockCSR.from_global_csr(A.to(dev), ops=HipOps(dev), problem_cls=cls)
     b_loc = b[r0:r1].to(dev)
@@ -148,15 +174,17 @@ def hip_task(a, rank, world):
     x2, info2 = getattr(module_a, method)(Arb, b_loc, x0=x_loc, M=P, **kw)     # cached plan and dinv, warm start
     st2 = module_a.get_last_stats()
     counts = None
-    if a.get("count"):                 # group_end calls per iteration: Jacobi CG against plain CG on this partition
-        prob, dinv = Arb._prob, Arb._jacobi[2]
-        c = {}
-        for pre in (False, True):
-            for k in (3, 8):
-                before = prob.group_ends
-                dist_cg(prob, tol=0.0, maxiter=k, dinv=dinv if pre else None)
-                c[f"{'p' if pre else ''}cg_{k}"] = prob.group_ends - before
-        counts = c
+    if a.get("count"):                 # every collective call of the six C loops on this partition, at two maxiter values each
+        prob, dinv, pl = Arb._prob, Arb._jacobi[2], Arb._prob.plan
+        traces = {}
+        for solver, ks in (("cg", (3, 8)), ("bicgstab", (3, 8)), ("gmres", (1, 2))):
+            for pre in ("", "p"):
+                for k in ks:
+                    before = len(prob.calls)
+                    _dist_fn(solver)(prob, tol=0.0, maxiter=k, dinv=dinv if pre else None, **_GMRES_KW.get(solver, {}))
+                    traces[f"{pre}{solver}_{k}"] = prob.calls[before:]
+        counts = {"traces": traces, "per": prob.part.per, "n_send": pl.n_send, "n_ghost": pl.n_ghost, "slab": pl.slab,
+                  "send_counts": [int(v) for v in pl.send_splits], "recv_counts": [int(v) for v in pl.recv_splits]}
     kname = _hipk.CsrHandle.last_spmv_kernel()
     pieces = [None] * world
     dist.all_gather_object(pieces, (r0, x_loc.cpu().numpy().copy(), int(info), st.iterations, st.residual_norm,
@@ -190,12 +218,73 @@ def hip_task(a, rank, world):
             "spmv_kernel": [p[10] for p in pieces], "n_local": [int(p[1].size) for p in pieces]}
 
 
+_GMRES_KW = {"gmres": {"restart": 3}}
+
+
+def _dist_fn(solver):
+    from pytorch_sparse_solver import distributed
+    return getattr(distributed, "dist_" + solver)
+
+
+def entry_status(prob, solver, dinv, spoil=None, fail_nth=None):
+    """One dist_<solver> call on `prob` (tol 0, 4 iterations or cycles).  spoil(args) spoils one argument of its
+    hipk_dist_*_solve call first; fail_nth = n makes the n-th all_gather return ncclResult 7.  Returns the entry point's status
+    and hipk_last_error()."""
+    L = _hipk.lib()
+    name = f"hipk_dist_{'p' if dinv is not None else ''}{solver}_solve"
+    entry, seen = getattr(L, name), []
+
+    def call(*args):
+        args = list(args)
+        if spoil is not None:
+            spoil(args)
+        seen.append(entry(*args))
+        return seen[-1]
+    setattr(L, name, call)
+    prob.fail_nth = fail_nth
+    try:
+        _dist_fn(solver)(prob, tol=0.0, maxiter=4, dinv=dinv, **_GMRES_KW.get(solver, {}))
+    except _hipk.HipkError:
+        pass
+    finally:
+        setattr(L, name, entry)
+        prob.fail_nth = None
+    torch.cuda.synchronize()
+    return seen[0], L.hipk_last_error().decode()
+
+
+def hip_errors_task(a, rank, world):
+    """World 1, host-staged collectives: the status and error text of each of the six entry points for a failed all_gather
+    and for single bad arguments."""
+    A, b = global_system("vardiff", a["nx"], a["ny"])
+    dev = torch.device("cuda", 0)
+    from pytorch_sparse_solver.distributed import HipOps
+    Arb = pss.RowBlockCSR.from_global_csr(A.to(dev), ops=HipOps(dev), problem_cls=StagedCounting)
+    module_a.cg(Arb, b.to(dev), M=JacobiPreconditioner(Arb), maxiter=2)    # builds the problem and the dinv cache
+    prob, dinv = Arb._prob, Arb._jacobi[2]
+    out = {}
+    for solver in ("cg", "bicgstab", "gmres"):
+        for pre in ("", "p"):
+            d, k = (dinv, 1) if pre else (None, 0)   # the argument list of hipk_dist_p*_solve has dinv at 3
+            cases = {"nccl": dict(fail_nth=a["fail_nth"]),
+                     "null": dict(spoil=lambda v, k=k: v.__setitem__(3 + k, None)),                 # b_local
+                     "work": dict(spoil=lambda v, k=k: v.__setitem__(6 + k, v[6 + k] - 8)),         # work_bytes
+                     "align": dict(spoil=lambda v, k=k: v.__setitem__(4 + k, v[4 + k] + 8)),        # x_ext
+                     "rank": dict(spoil=lambda v: setattr(v[1]._obj, "rank", v[1]._obj.world))}
+            if solver == "gmres":
+                cases["restart"] = dict(spoil=lambda v, k=k: setattr(v[7 + k]._obj, "restart", 32))
+            if pre:
+                cases["dinv"] = dict(spoil=lambda v: v.__setitem__(3, None))
+            out[pre + solver] = {case: entry_status(prob, solver, d, **kw) for case, kw in cases.items()}
+    return out
+
+
 def main():
     task, out, args = sys.argv[1], sys.argv[2], json.loads(sys.argv[3])
     dist.init_process_group("gloo")
     rank, world = dist.get_rank(), dist.get_world_size()
-    if task == "hip":
-        res = hip_task(args, rank, world)
+    if task.startswith("hip"):
+        res = (hip_task if task == "hip" else hip_errors_task)(args, rank, world)
         if rank == 0:
             with open(out, "w") as f:
                 json.dump(res, f)

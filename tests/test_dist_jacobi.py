@@ -131,17 +131,74 @@ def test_row_partitioned_jacobi_solves_shared_gpu(world, kind, nx, ny, solver, p
     _check(r, maxiter)
 
 
+def _expected_traces(c, world, halo):
+    """The collective calls of one rank's six C loops, per solver: (set-up, one iteration or cycle, final) blocks, built from the
+    halo mode and this rank's peer counts.  A halo is the neighbour send/recv pairs (p2p) or one all-gather of padded slabs; a
+    p2p rank with nothing to send or receive has none.  GMRES completes its global partial arrays in place, with restart 3."""
+    GS, GE = ["group_start"], ["group_end"]
+    ag, agi = ["all_gather", c["per"], False], ["all_gather", c["per"], True]
+    H = []
+    if world > 1 and halo == "allgather":
+        H = [["all_gather", c["slab"], False]]
+    elif world > 1:
+        for peer, (ns, nr) in enumerate(zip(c["send_counts"], c["recv_counts"])):
+            H += ([["send", ns, peer]] if ns else []) + ([["recv", nr, peer]] if nr else [])
+
+    def group(calls, when=world > 1):
+        return [GS] + calls + [GE] if when else calls
+    alone = group(H, bool(H) and halo == "p2p")          # a stand-alone halo exchange: the pairs in a group, the slabs alone
+    cg = (alone + [ag, ag] + alone, [ag] + group([ag] + H), alone + [ag, ag])
+    pcg = (alone + [ag, ag] + group([ag] + H, world > 1 and bool(H)), [ag] + group([ag, ag] + H), alone + [ag, ag])
+    bi = (group(H) + [ag, ag], group(H) + [ag] + group([ag] + H) + group([ag, ag]) + group([ag, ag]), group(H) + [ag, ag])
+    cycle = []
+    for k in range(3):
+        cycle += alone + [agi] + 2 * (group([agi] * (k + 1)) + [agi])
+    cycle += alone + [agi]                                   # the residual after the cycle
+    gm_final = alone + [agi, agi]
+    return {"cg": cg, "pcg": pcg, "bicgstab": bi, "pbicgstab": bi,
+            "gmres": ([agi] + alone + [agi], cycle, gm_final), "pgmres": ([agi] + alone + [agi, agi], cycle, gm_final)}
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("world,halo", [(2, "p2p"), (3, "allgather")])
 def test_row_partitioned_jacobi_cg_keeps_the_collective_count(world, halo, tmp_path):
-    """The <r,z> partials ride in the group of the <r,r> partials and the halo of r: a Jacobi CG iteration makes exactly as many
+    """Every collective call of the six row-partitioned loops (cg, bicgstab, gmres, plain and with Jacobi), in order, on every
+    rank: the set-up block, one identical block per iteration (GMRES: per restart cycle) at two maxiter values, the final block.
+    The <r,z> partials ride in the group of the <r,r> partials and the halo of r: a Jacobi CG iteration makes exactly as many
     group_end calls as a plain CG iteration on the same partition."""
     args = {"kind": "vardiff", "nx": 96, "ny": 64, "solver": "cg", "pmode": "local", "entry": "module_a", "tol": 1e-8,
             "maxiter": -1, "count": True}
     r = _run(world, "hip", args, tmp_path, env_extra={"HIPK_DIST_HALO": halo})
     _check(r)
     for c in r["counts"]:
-        assert c["pcg_8"] - c["pcg_3"] == c["cg_8"] - c["cg_3"] == 5, c      # one grouped exchange per iteration
+        tr = c["traces"]
+        for name, (setup, step, final) in _expected_traces(c, world, halo).items():
+            for k in ((1, 2) if name.endswith("gmres") else (3, 8)):
+                assert tr[f"{name}_{k}"] == setup + k * step + final, (name, k, c)
+        ends = {name: sum(call == ["group_end"] for call in calls) for name, calls in tr.items()}
+        assert ends["pcg_8"] - ends["pcg_3"] == ends["cg_8"] - ends["cg_3"] == 5, ends      # one grouped exchange per iteration
+
+
+@pytest.mark.gpu
+def test_row_partitioned_entry_points_report_errors_at_world_1(tmp_path):
+    """World 1, host-staged collectives, all six entry points: a failed all_gather returns HIPK_ERR_HIP with the entry point's
+    ncclResult text; a single bad argument returns its code and message."""
+    r = _run(1, "hip_errors", {"nx": 24, "ny": 20, "fail_nth": 4}, tmp_path)
+    ARG, HIP, ALIGN, WORKSPACE = -1, -2, -3, -5
+    for solver in ("cg", "bicgstab", "gmres"):
+        for pre in ("", "p"):
+            got = r[pre + solver]
+            assert got["nccl"] == [HIP, f"hipk_dist_{pre}{solver}_solve: all_gather(partials) failed (ncclResult 7)"], got
+            want = {"null": (ARG, "null argument"), "work": (WORKSPACE, "work too small"), "rank": (ARG, "rank / world"),
+                    "align": (ALIGN, "work must be 256-byte, x / b / dinv 16-byte aligned" if pre else
+                              "work must be 256-byte, x / b 16-byte aligned")}
+            if solver == "gmres":
+                want["restart"] = (ARG, "restart must be in [1, 31]")
+            if pre:
+                want["dinv"] = (ARG, "null argument")
+            assert set(got) == set(want) | {"nccl"}, got
+            for case, (code, text) in want.items():
+                assert got[case][0] == code and got[case][1].endswith(": " + text), (pre + solver, case, got[case])
 
 
 @pytest.mark.gpu
