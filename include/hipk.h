@@ -225,6 +225,21 @@ int hipk_pgmres_solve(hipk_csr_t A, const void *dinv, const void *b, void *x, vo
 size_t hipk_pbicgstab_work_bytes(int64_t n, int dtype);
 int hipk_pbicgstab_solve(hipk_csr_t A, const void *dinv, const void *b, void *x, void *work, size_t work_bytes,
                          const hipk_params *prm, hipk_stats *st, hipk_stream_t stream);
+/* ---- many right-hand sides: k systems on one matrix, the matrix read once per block iteration ------------------------
+ * Column j of the result is bit for bit hipk_cg_solve / hipk_pcg_solve (solver 0) or hipk_bicgstab_solve / hipk_pbicgstab_solve
+ * (solver 1) of column j: the same params, the same per-column stats (st: k entries, iterations, matvecs, info, breakdown,
+ * norms), each column stopping at its own iteration.  B (n x k, leading dimension ldb >= k) and X (n x k, ldx >= k; x0 in,
+ * x out) are row-major device arrays of the matrix' dtype; dinv is NULL (M = identity) or the Jacobi vector.  Columns run in
+ * blocks of at most 16 with all per-column scratch in `work` (hipk_multi_work_bytes(n, k, dtype, solver, precond), 256-byte
+ * aligned; the handle's own scratch is not used).  *block_spmvs = the block-SpMV launches that did work, summed over the
+ * blocks.  hipk_last_solve_path() reports "hipk_cg_multi launch sequence" / "hipk_bicgstab_multi launch sequence".  CSR
+ * handles only (not hipk_op_create). */
+size_t hipk_multi_work_bytes(int64_t n, int k, int dtype, int solver, int precond);
+int hipk_cg_solve_multi(hipk_csr_t A, const void *dinv, int k, const void *B, int64_t ldb, void *X, int64_t ldx, void *work,
+                        size_t work_bytes, const hipk_params *prm, hipk_stats *st, int64_t *block_spmvs, hipk_stream_t stream);
+int hipk_bicgstab_solve_multi(hipk_csr_t A, const void *dinv, int k, const void *B, int64_t ldb, void *X, int64_t ldx, void *work,
+                              size_t work_bytes, const hipk_params *prm, hipk_stats *st, int64_t *block_spmvs,
+                              hipk_stream_t stream);
 /* Placement probe for systems whose vectors live in HBM (N >> 8 M rows): the memory shape of the CG direction step (reads r, p, x;
  * writes p, x) on the three vectors, storing back the bits it loaded (safe on live data); *us_out = the fastest of `reps` (<= 16)
  * timed passes in microseconds.  40 n bytes (fp64) per pass.  On MI355X such a step runs at one of two discrete speeds depending on

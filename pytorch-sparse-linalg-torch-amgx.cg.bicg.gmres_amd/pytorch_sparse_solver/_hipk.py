@@ -48,6 +48,8 @@ SYMBOLS = [
     # experimental mailbox exchange provider for that loop
     "hipk_p2p_create", "hipk_p2p_create2", "hipk_p2p_export", "hipk_p2p_connect", "hipk_p2p_destroy", "hipk_p2p_error",
     "hipk_p2p_group_start", "hipk_p2p_group_end", "hipk_p2p_all_gather",
+    # many right-hand sides per matrix read
+    "hipk_multi_work_bytes", "hipk_cg_solve_multi", "hipk_bicgstab_solve_multi",
 ]
 
 
@@ -247,6 +249,11 @@ def lib():
     L.hipk_p2p_destroy.argtypes = [vp]
     L.hipk_p2p_error.argtypes = [vp]
     L.hipk_p2p_all_gather.argtypes = [vp, vp, ctypes.c_size_t, i32, vp, vp]
+    L.hipk_multi_work_bytes.argtypes = [i64, i32, i32, i32, i32]
+    L.hipk_multi_work_bytes.restype = ctypes.c_size_t
+    for name in ("cg", "bicgstab"):
+        getattr(L, f"hipk_{name}_solve_multi").argtypes = [vp, vp, i32, vp, i64, vp, i64, vp, ctypes.c_size_t, ctypes.POINTER(Params),
+                                                          ctypes.POINTER(Stats), ctypes.POINTER(i64), vp]
     _lib = L
     return L
 
@@ -683,6 +690,57 @@ def solve_pcg(h: CsrHandle, dinv: torch.Tensor, b: torch.Tensor, x: torch.Tensor
                       threshold=st.threshold, recurrence_rs=st.recurrence_rs, solve_ms=st.solve_ms,
                       spmv_ms_avg=st.spmv_ms_avg, spmv_profiled=st.spmv_profiled,
                       dispatch_span_ms_avg=st.dispatch_span_ms_avg)
+
+
+@dataclass
+class MultiSolveStats:
+    """Side channel of cg_multi / bicgstab_multi: one SolveStats per column, the block-SpMV launches that did work (summed over
+    the blocks of at most 16 columns; 0 when the columns ran one by one) and the solve time."""
+    method: str
+    columns: list
+    block_spmvs: int
+    solve_ms: float
+
+
+MULTI_MAX_BLOCK = 16   # columns per block of hipk_{cg,bicgstab}_solve_multi
+
+
+def multi_work_bytes(n: int, k: int, dtype: torch.dtype, method: str, precond: bool) -> int:
+    return int(lib().hipk_multi_work_bytes(int(n), int(k), _dtype_code(dtype), 0 if method == "cg" else 1, 1 if precond else 0))
+
+
+def solve_multi(method: str, h: CsrHandle, dinv: Optional[torch.Tensor], B: torch.Tensor, X: torch.Tensor, *, tol: float,
+                atol: float, maxiter: Optional[int], check_every: int = 0) -> MultiSolveStats:
+    """hipk_{cg,bicgstab}_solve_multi: B, X row-major (n, k) of the handle's dtype; X holds X0 on entry and the solution on return.
+    dinv: None (M = identity) or the Jacobi vector."""
+    if h.shape[0] != h.shape[1]:
+        raise ValueError(f"linear operator must be a square matrix, but has shape: {h.shape}")
+    n, k = int(B.shape[0]), int(B.shape[1])
+    for t in (B, X):
+        assert t.is_contiguous() and t.dtype == h.dtype and t.shape == (h.n, k) and t.device == h.device
+    if dinv is not None:
+        assert dinv.is_contiguous() and dinv.dtype == h.dtype and dinv.numel() == h.n and dinv.device == h.device
+    prm = Params()
+    prm.tol, prm.atol = float(tol), float(atol)
+    prm.maxiter = -1 if maxiter is None else int(maxiter)
+    prm.check_every = int(check_every)
+    prm.gpu_tolerances = 1
+    L = lib()
+    wb = multi_work_bytes(n, k, h.dtype, method, dinv is not None)
+    work = torch.empty(wb, dtype=torch.uint8, device=h.device)
+    st = (Stats * k)()
+    spmvs = ctypes.c_int64(0)
+    with h._lock, torch.cuda.device(h.device):
+        rc = getattr(L, f"hipk_{method}_solve_multi")(h.ptr, None if dinv is None else dinv.data_ptr(), k, B.data_ptr(), k,
+                                                      X.data_ptr(), k, work.data_ptr(), wb, ctypes.byref(prm), st,
+                                                      ctypes.byref(spmvs), _stream(h.device))
+    _check(rc, f"hipk_{method}_solve_multi")
+    name = method if dinv is None else {"cg": "pcg_jacobi", "bicgstab": "pbicgstab_jacobi"}[method]
+    cols = [SolveStats(method=name, iterations=c.iterations, matvecs=c.matvecs, info=c.info, breakdown=c.breakdown,
+                       b_norm=c.b_norm, residual_norm=c.residual_norm, x_norm=c.x_norm, threshold=c.threshold,
+                       recurrence_rs=c.recurrence_rs, solve_ms=c.solve_ms, spmv_ms_avg=0.0, spmv_profiled=0) for c in st]
+    ms = sum(st[j].solve_ms for j in range(0, k, MULTI_MAX_BLOCK))
+    return MultiSolveStats(method=f"{method}_multi", columns=cols, block_spmvs=int(spmvs.value), solve_ms=ms)
 
 
 def solve_pgmres(h: CsrHandle, dinv: torch.Tensor, b: torch.Tensor, x: torch.Tensor, *, tol: float, atol: float,
