@@ -393,13 +393,25 @@ int hipk_dist_bicgstab_solve(hipk_csr_t A_local, const hipk_dist_plan *plan, con
                              void *x_ext, void *work, size_t work_bytes, const hipk_params *prm, hipk_stats *st,
                              hipk_stream_t stream);
 
-/* Row-partitioned GMRES (TSL:641-803; params.restart <= 31, params.gmres_method, params.gpu_tolerances as hipk_gmres_solve): the
+/* Row-partitioned GMRES (TSL:641-803; params.restart <= 31 -- 32 .. 255: hipk_dist_gmres_wide_solve below --, params.gmres_method,
+ * params.gpu_tolerances as hipk_gmres_solve): the
  * kernels of the large-system path with in-place all-gathers of their chunk partials and the halo of v_k before each SpMV; bit for
  * bit the iterates, cycle and operator-application counts of hipk_gmres_solve on the whole system.  per * world <= 2048. */
 size_t hipk_dist_gmres_work_bytes(const hipk_dist_plan *plan, int restart);
 int hipk_dist_gmres_solve(hipk_csr_t A_local, const hipk_dist_plan *plan, const hipk_rccl *coll, const void *b_local,
                           void *x_ext, void *work, size_t work_bytes, const hipk_params *prm, hipk_stats *st,
                           hipk_stream_t stream);
+
+/* Row-partitioned GMRES at params.restart 32 .. 255 (any other restart: HIPK_ERR_ARG "restart must be in [32, 255]", and the
+ * work-bytes functions return 0).  Arguments, plan / collective structs and the bitwise contract of hipk_dist_gmres_solve; H, R
+ * and the Givens pairs live in the workspace as in hipk_gmres_solve beyond restart 31.  The multi-dot partials of an Arnoldi
+ * step travel in ONE in-place all-gather of (k + 1) * per doubles per CGS pass, whatever k: per step the halo of v_k, then
+ * all-gathers of per, (k + 1) per, per, (k + 1) per, per doubles.  hipk_dist_pgmres_wide_solve: the Jacobi form, arguments of
+ * hipk_dist_pgmres_solve. */
+size_t hipk_dist_gmres_wide_work_bytes(const hipk_dist_plan *plan, int restart);
+int hipk_dist_gmres_wide_solve(hipk_csr_t A_local, const hipk_dist_plan *plan, const hipk_rccl *coll, const void *b_local,
+                               void *x_ext, void *work, size_t work_bytes, const hipk_params *prm, hipk_stats *st,
+                               hipk_stream_t stream);
 
 /* The three row-partitioned loops with the Jacobi preconditioner M = diag(dinv): the same plan / collective structs and
  * conventions as above, bit for bit the iterates, counts and `info` of hipk_pcg_solve / hipk_pbicgstab_solve / hipk_pgmres_solve
@@ -409,7 +421,7 @@ int hipk_dist_gmres_solve(hipk_csr_t A_local, const hipk_dist_plan *plan, const 
  *   CG       : two collective launches per iteration, as hipk_dist_cg_solve; the second carries the <r,r> and <r,z> partials
  *              and the halo of r in one group.  The fused exchanges of hipk_rccl.fused are not taken.
  *   BiCGStab : the halos of phat = M p and shat = M s instead of p and s; five collective launches per iteration.
- *   GMRES    : left preconditioning, w = M (A v_k); restart <= 31. */
+ *   GMRES    : left preconditioning, w = M (A v_k); restart <= 31 (32 .. 255: hipk_dist_pgmres_wide_solve). */
 size_t hipk_dist_pcg_work_bytes(const hipk_dist_plan *plan);
 int hipk_dist_pcg_solve(hipk_csr_t A_local, const hipk_dist_plan *plan, const hipk_rccl *coll, const void *dinv_ext,
                         const void *b_local, void *x_ext, void *work, size_t work_bytes, const hipk_params *prm,
@@ -422,6 +434,11 @@ size_t hipk_dist_pgmres_work_bytes(const hipk_dist_plan *plan, int restart);
 int hipk_dist_pgmres_solve(hipk_csr_t A_local, const hipk_dist_plan *plan, const hipk_rccl *coll, const void *dinv_ext,
                            const void *b_local, void *x_ext, void *work, size_t work_bytes, const hipk_params *prm,
                            hipk_stats *st, hipk_stream_t stream);
+/* ... and at restart 32 .. 255 (see hipk_dist_gmres_wide_solve). */
+size_t hipk_dist_pgmres_wide_work_bytes(const hipk_dist_plan *plan, int restart);
+int hipk_dist_pgmres_wide_solve(hipk_csr_t A_local, const hipk_dist_plan *plan, const hipk_rccl *coll, const void *dinv_ext,
+                                const void *b_local, void *x_ext, void *work, size_t work_bytes, const hipk_params *prm,
+                                hipk_stats *st, hipk_stream_t stream);
 
 /* ---- EXPERIMENTAL peer-to-peer exchange provider for the loop above (csrc/hipk_p2p.hip) ---------------------------------
  * Each rank owns a device mailbox that every peer maps through HIP IPC; an all-gather is ONE small kernel per rank (publish

@@ -49,6 +49,10 @@ struct hipk_dist_xchg {
     }
     // in place: this rank's partials are already at arr + rank * per
     int parts(double *arr) const { return parts(arr + (size_t)pl->rank * pl->per, arr); }
+    // in place, one call of `count` doubles per rank: this rank's block is at arr + rank * count (the wide GMRES multi-dot)
+    int block(double *arr, size_t count) const {
+        return nccl(cc->all_gather(arr + (size_t)pl->rank * count, arr, count, NCCL_F64, cc->comm, stream), "all_gather(partials)");
+    }
     // ONE step of exchanges: the all-gathers of up to two partial arrays (src -> dst) and the halo of v (v may be null).  run():
     // two or more collective calls go into one group; grouped(): a group at world > 1 whatever the calls.  v = x alone is the
     // stand-alone halo exchange (a group around the send/recv pairs; the slab all-gather on its own).

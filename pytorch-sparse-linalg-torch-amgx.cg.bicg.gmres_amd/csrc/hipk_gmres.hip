@@ -529,6 +529,71 @@ __global__ __launch_bounds__(HIPK_THREADS) HIPK_SGPR80 void hipk_gm_multidot_str
     }
 }
 
+// The multi-dot of the row-partitioned loop at restart > 31 (hipk_dist_gmres_wide_solve): the eight-column form above
+// (groups of eight columns, workgroup b takes chunk b % g of group b / g, the same per-column order and tree) with this rank's
+// k + 1 columns of partials as ONE contiguous block, column j at part + j * per (part = blk + rank (k + 1) per), so that a
+// single all-gather of (k + 1) per doubles completes blk as [rank][j][chunk] whatever k.  Read back by
+// hipk_gm_hreduce_packed_kernel.  A kernel of its own: a run-time column stride in the kernel above changes the code of its
+// other instantiations (the single-device launch sequence's 16- and 32-column forms).
+template <typename T>
+__global__ __launch_bounds__(HIPK_THREADS) HIPK_SGPR80 void hipk_gm_multidot_packed_kernel(
+    int64_t n, int ch, hipk_gm_scal *__restrict__ scal, int k, int pass, const T *__restrict__ V, int64_t ldv,
+    const T *__restrict__ w, double *__restrict__ part, int per, int g, int nres) {
+    if (k >= scal->stop_step) return;
+    if (pass == 1 && !scal->pass2) return;
+    const int grp = blockIdx.x / g, c = blockIdx.x % g;
+    __shared__ double sbuf[8 * HIPK_THREADS];
+    const int j0 = 8 * grp;
+    double acc[8];
+#pragma unroll
+    for (int b = 0; b < 8; ++b) acc[b] = 0.0;
+    hipk_chunk_loop<T, 1>(n, ch, c, [&](int64_t i, int nv) {
+        constexpr int VEC = hipk_vec<T>::VEC;
+        T wv[VEC];
+        hipk_ld<T>(w, i, nv, wv);
+        T vv[8][VEC];
+#pragma unroll
+        for (int b = 0; b < 8; ++b)
+            if (j0 + b <= k) {
+                if (j0 + b < nres) hipk_ld<T>(V + (int64_t)(j0 + b) * ldv, i, nv, vv[b]);
+                else hipk_ld_nt_vec<T>(V + (int64_t)(j0 + b) * ldv, i, nv, vv[b]);
+            }
+#pragma unroll
+        for (int b = 0; b < 8; ++b)
+            if (j0 + b <= k) {
+#pragma unroll
+                for (int e = 0; e < VEC; ++e)
+                    if (e < nv) acc[b] = fma((double)vv[b][e], (double)wv[e], acc[b]);
+            }
+    });
+    hipk_block_sumN<8>(acc, sbuf);
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int b = 0; b < 8; ++b)
+            if (j0 + b <= k) part[(size_t)(j0 + b) * per + c] = acc[b];
+    }
+}
+
+// hvec[j] from the packed block of hipk_gm_multidot_packed_kernel: global chunk c (of rank c / per) of column j is at
+// blk[(c / per) (k + 1) per + j per + c % per].  The terms, their order and the tree are hipk_reduce_parts' over c in [0, g), so
+// h has the bits of hipk_gm_hreduce_kernel on the global partial array.  One workgroup per j.
+__global__ __launch_bounds__(HIPK_THREADS) void hipk_gm_hreduce_packed_kernel(hipk_gm_scal *__restrict__ scal, int k, int pass,
+                                                                              int g, int per, const double *__restrict__ blk) {
+    if (k >= scal->stop_step) return;
+    if (pass == 1 && !scal->pass2) return;
+    __shared__ double sbuf[HIPK_THREADS];
+    const int t = threadIdx.x, j = blockIdx.x;
+    const size_t rank_stride = (size_t)(k + 1) * per;
+    double acc = 0.0;
+#pragma unroll
+    for (int q = 0; q < HIPK_MAX_PARTS / HIPK_THREADS; ++q) {
+        const int c = t + q * HIPK_THREADS;
+        if (c < g) acc = acc + blk[(size_t)(c / per) * rank_stride + (size_t)j * per + (c % per)];
+    }
+    const double h = hipk_block_sum(acc, sbuf);
+    if (t == 0) scal->v.hvec[j] = h;
+}
+
 // q = w - V h in place, partials of <q,q>; rvec += h   (TSL:302-305).  grid = g.
 // KC = compile-time bound on the live columns (8: the first eight Arnoldi steps, one round of column loads and few enough
 // registers for 8 workgroups per CU -- those steps are latency-bound; 32: the general form; 256: restart > 31, batches in a run-time loop).
@@ -2706,28 +2771,48 @@ extern "C" int hipk_pgmres_solve_cb(hipk_csr_t A, hipk_precond_fn M, void *user,
 // dinv != null (hipk_dist_pgmres_solve): left Jacobi preconditioning as in hipk_pgmres_solve -- every SpMV (Arnoldi products, the
 // residuals) carries the row scaling in its epilogue, so its fused ||w||^2 partials are those of the scaled vector; ptol from ||M b||
 // (TSL:750).  The same exchanges as without it.
+//
+// wide (hipk_dist_{p,}gmres_wide_solve, restart 32 .. 255): the same loop with two differences only.
+//  * H, R, the Givens pairs, beta, h and r live in the workspace block of the single-device loop at restart > 31 (hipk_gm_view,
+//    hipk_gm_big_doubles(m) doubles behind the header); the host solves the cycle's least squares from a copy of that block.
+//  * The multi-dot partials travel in ONE all-gather per CGS pass whatever k: the k + 1 columns of this rank are one contiguous
+//    block at blk + rank (k + 1) per (hipk_gm_multidot_packed_kernel), completed in place as [rank][j][chunk] and folded by
+//    hipk_gm_hreduce_packed_kernel in the order and tree of hipk_gm_hreduce_kernel.  Per Arnoldi step: the halo of v_k, then
+//    all-gathers of per, (k + 1) per, per, (k + 1) per, per doubles -- 5 m + halos per cycle, where the column-by-column form
+//    would make m (m + 1) + 3 m.
 #include "hipk_dist_xchg.h"
 static size_t hipk_dgm_vec_bytes(const hipk_dist_plan *pl) {
     return hipk_align_up((size_t)(pl->n_ext > 0 ? pl->n_ext : 1) * sizeof(double), 256);
 }
+// workspace of either form at restart m (hipk_gm_big_doubles(m) is 0 up to 31)
+static size_t hipk_dgm_work_bytes(const hipk_dist_plan *plan, int m) {
+    const size_t slab = (size_t)(plan->slab > 0 ? plan->slab : 1);
+    return kGmHeader + hipk_gm_big_doubles(m) * sizeof(double) + (size_t)(kGmSlots + m + 1) * HIPK_MAX_PARTS * sizeof(double) +
+           (size_t)(m + 2) * hipk_dgm_vec_bytes(plan) + hipk_align_up((size_t)(plan->n_send > 0 ? plan->n_send : 1) * 8, 256) +
+           hipk_align_up(slab * 8, 256) + hipk_align_up(slab * (size_t)plan->world * 8, 256);
+}
 extern "C" size_t hipk_dist_gmres_work_bytes(const hipk_dist_plan *plan, int restart) {
     if (!plan || plan->world < 1 || plan->per < 1) return 0;
-    const int m = restart < 1 ? 1 : (restart > HIPK_GM_MAXM ? HIPK_GM_MAXM : restart);
-    const size_t slab = (size_t)(plan->slab > 0 ? plan->slab : 1);
-    return kGmHeader + (size_t)(kGmSlots + m + 1) * HIPK_MAX_PARTS * sizeof(double) + (size_t)(m + 2) * hipk_dgm_vec_bytes(plan) +
-           hipk_align_up((size_t)(plan->n_send > 0 ? plan->n_send : 1) * 8, 256) + hipk_align_up(slab * 8, 256) +
-           hipk_align_up(slab * (size_t)plan->world * 8, 256);
+    return hipk_dgm_work_bytes(plan, restart < 1 ? 1 : (restart > HIPK_GM_MAXM ? HIPK_GM_MAXM : restart));
+}
+extern "C" size_t hipk_dist_gmres_wide_work_bytes(const hipk_dist_plan *plan, int restart) {
+    if (!plan || plan->world < 1 || plan->per < 1 || restart <= HIPK_GM_MAXM || restart > HIPK_GM_MAXM_BIG) return 0;
+    return hipk_dgm_work_bytes(plan, restart);
 }
 
-static int hipk_dist_gmres_t(bool pre, hipk_csr_t A, const hipk_dist_plan *pl, const hipk_rccl *cc, const double *dinv,
+static int hipk_dist_gmres_t(bool pre, bool wide, hipk_csr_t A, const hipk_dist_plan *pl, const hipk_rccl *cc, const double *dinv,
                              const void *b_local, void *x_ext, void *work_, size_t work_bytes, const hipk_params *prm, hipk_stats *st,
                              hipk_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     static const char *const geometry = "partial-sum geometry (per * world must not exceed 2048)";
     HIPK_TRY(hipk_dist_check(A, pl, cc, pre, dinv, b_local, x_ext, work_, prm, st, pre ? nullptr : geometry));
-    HIPK_REQUIRE(prm->restart >= 1 && prm->restart <= HIPK_GM_MAXM, HIPK_ERR_ARG, "restart must be in [1, 31]");
+    if (wide)
+        HIPK_REQUIRE(prm->restart > HIPK_GM_MAXM && prm->restart <= HIPK_GM_MAXM_BIG, HIPK_ERR_ARG, "restart must be in [32, 255]");
+    else
+        HIPK_REQUIRE(prm->restart >= 1 && prm->restart <= HIPK_GM_MAXM, HIPK_ERR_ARG, "restart must be in [1, 31]");
     HIPK_REQUIRE((int64_t)pl->per * pl->world <= HIPK_MAX_PARTS, HIPK_ERR_ARG, geometry);
-    HIPK_REQUIRE(work_bytes >= hipk_dist_gmres_work_bytes(pl, prm->restart), HIPK_ERR_WORKSPACE, "work too small");
+    const size_t need = hipk_dgm_work_bytes(pl, prm->restart);
+    HIPK_REQUIRE(work_bytes >= need, HIPK_ERR_WORKSPACE, "work too small");
     memset(st, 0, sizeof(*st));
     typedef double T;
     char *work = (char *)work_;
@@ -2739,18 +2824,24 @@ static int hipk_dist_gmres_t(bool pre, hipk_csr_t A, const hipk_dist_plan *pl, c
     const size_t vec = hipk_dgm_vec_bytes(pl);
     const int64_t ldv = (int64_t)(vec / sizeof(T));
     hipk_gm_scal *scal = (hipk_gm_scal *)work;
-    double *parts = (double *)(work + kGmHeader);
+    const size_t big_n = hipk_gm_big_doubles(m);          // wide: the cycle's small arrays (0 up to restart 31)
+    double *big = big_n ? (double *)(work + kGmHeader) : nullptr;
+    std::vector<double> big_host(big_n);
+    double *parts = (double *)(work + kGmHeader + big_n * sizeof(double));
     double *part_ww = parts, *part_qq = parts + HIPK_MAX_PARTS, *part_res = parts + 2 * HIPK_MAX_PARTS;
     double *part_bb = parts + 3 * HIPK_MAX_PARTS, *part_xx = parts + 4 * HIPK_MAX_PARTS;
     double *part_spare = parts + 5 * HIPK_MAX_PARTS;
     double *part_md = parts + (size_t)kGmSlots * HIPK_MAX_PARTS;
-    char *vbase = work + kGmHeader + (size_t)(kGmSlots + m + 1) * HIPK_MAX_PARTS * sizeof(double);
+    char *vbase = (char *)parts + (size_t)(kGmSlots + m + 1) * HIPK_MAX_PARTS * sizeof(double);
     T *V = (T *)vbase;
     T *tmp = (T *)(vbase + (size_t)(m + 1) * vec);
     char *cbase = vbase + (size_t)(m + 2) * vec;
     double *slab_loc = (double *)(cbase + hipk_align_up((size_t)(pl->n_send > 0 ? pl->n_send : 1) * 8, 256));
     double *slab_all = (double *)((char *)slab_loc + hipk_align_up((size_t)(pl->slab > 0 ? pl->slab : 1) * 8, 256));
-    const hipk_dist_xchg xc(pl, cc, stream, (double *)cbase, slab_loc, slab_all, pre ? "hipk_dist_pgmres_solve" : "hipk_dist_gmres_solve");
+    const char *who = wide ? (pre ? "hipk_dist_pgmres_wide_solve" : "hipk_dist_gmres_wide_solve")
+                           : (pre ? "hipk_dist_pgmres_solve" : "hipk_dist_gmres_solve");
+    const char *loop = wide ? who : "hipk_dist_gmres_solve";   // the name in the texts of a HIP failure
+    const hipk_dist_xchg xc(pl, cc, stream, (double *)cbase, slab_loc, slab_all, who);
     T *x = (T *)x_ext;
     const T *b = (const T *)b_local;
     const int incremental = (prm->gmres_method == HIPK_GMRES_INCREMENTAL) ? 1 : 0;
@@ -2760,7 +2851,7 @@ static int hipk_dist_gmres_t(bool pre, hipk_csr_t A, const hipk_dist_plan *pl, c
     hipk_event_pair whole;
     HIPK_CHECK_HIP(whole.create());
     HIPK_CHECK_HIP(hipEventRecord(whole.a, stream));
-    HIPK_CHECK_HIP(hipMemsetAsync(work, 0, hipk_dist_gmres_work_bytes(pl, m), stream));
+    HIPK_CHECK_HIP(hipMemsetAsync(work, 0, need, stream));
     if (n_ext > n) HIPK_CHECK_HIP(hipMemsetAsync(x + n, 0, (size_t)(n_ext - n) * 8, stream));
 
     // residual = b - A x0 into column 0, unit residual + norm (TSL:791-792); <b,b>
@@ -2803,13 +2894,16 @@ static int hipk_dist_gmres_t(bool pre, hipk_csr_t A, const hipk_dist_plan *pl, c
     }
     const double ptol = mb_norm * hipk_tmin(1.0, atol_eff / b_norm);
 
-    std::vector<unsigned char> hs_store(sizeof(hipk_gm_scal));
-    hipk_gm_scal *hs = (hipk_gm_scal *)hs_store.data();
+    std::vector<unsigned char> hs_buf(sizeof(hipk_gm_scal));
+    hipk_gm_scal *hs = (hipk_gm_scal *)hs_buf.data();
     const int nres = 5;
     int64_t cycles = 0;
     int happy = 0;
     while (cycles < maxiter && res_norm > atol_eff) {
-        hipk_gm_cycle_init_kernel<<<1, HIPK_THREADS, 0, stream>>>(scal, incremental, ptol);
+        if (wide)
+            hipk_gm_cycle_init_kernel<<<1, HIPK_THREADS, 0, stream>>>(scal, incremental, ptol, big, m);
+        else
+            hipk_gm_cycle_init_kernel<<<1, HIPK_THREADS, 0, stream>>>(scal, incremental, ptol);
         for (int k = 0; k < m; ++k) {
             T *vk = V + (int64_t)k * ldv, *w = V + (int64_t)(k + 1) * ldv;
             HIPK_TRY(xc.run(vk));
@@ -2820,42 +2914,66 @@ static int hipk_dist_gmres_t(bool pre, hipk_csr_t A, const hipk_dist_plan *pl, c
             for (int pass = 0; pass < 2; ++pass) {
                 if (pass == 1) hipk_gm_decide_kernel<<<1, HIPK_THREADS, 0, stream>>>(scal, k, G, part_qq, eps_t);
                 const int mg = gl * (k / 8 + 1);
-                hipk_gm_multidot_stream_kernel<T, 8><<<mg, HIPK_THREADS, 0, stream>>>(n, ch, scal, k, pass, V, ldv, w, part_md + c0, gl, nres);
-                if (W > 1) HIPK_TRY(xc.group_start());   // (also for k = 0)
-                for (int j = 0; j <= k; ++j) HIPK_TRY(xc.parts(part_md + (size_t)j * HIPK_MAX_PARTS));
-                if (W > 1) HIPK_TRY(xc.group_end());
-                hipk_gm_hreduce_kernel<<<k + 1, HIPK_THREADS, 0, stream>>>(scal, k, pass, G, part_md);
-                hipk_gm_update_stream_kernel<T, HIPK_GM_LDH><<<gl, HIPK_THREADS, 0, stream>>>(n, ch, scal, k, pass, V, ldv, w, part_qq + c0, nres);
+                if (wide) {   // this rank's k + 1 columns as one block at blk + rank (k + 1) per, one in-place all-gather
+                    const size_t cnt = (size_t)(k + 1) * per;
+                    hipk_gm_multidot_packed_kernel<T><<<mg, HIPK_THREADS, 0, stream>>>(n, ch, scal, k, pass, V, ldv, w,
+                                                                                          part_md + pl->rank * cnt, per, gl, nres);
+                    HIPK_TRY(xc.block(part_md, cnt));
+                    hipk_gm_hreduce_packed_kernel<<<k + 1, HIPK_THREADS, 0, stream>>>(scal, k, pass, G, per, part_md);
+                } else {
+                    hipk_gm_multidot_stream_kernel<T, 8><<<mg, HIPK_THREADS, 0, stream>>>(n, ch, scal, k, pass, V, ldv, w, part_md + c0, gl, nres);
+                    if (W > 1) HIPK_TRY(xc.group_start());   // (also for k = 0)
+                    for (int j = 0; j <= k; ++j) HIPK_TRY(xc.parts(part_md + (size_t)j * HIPK_MAX_PARTS));
+                    if (W > 1) HIPK_TRY(xc.group_end());
+                    hipk_gm_hreduce_kernel<<<k + 1, HIPK_THREADS, 0, stream>>>(scal, k, pass, G, part_md);
+                }
+                if (k < HIPK_GM_LDH)
+                    hipk_gm_update_stream_kernel<T, HIPK_GM_LDH><<<gl, HIPK_THREADS, 0, stream>>>(n, ch, scal, k, pass, V, ldv, w, part_qq + c0, nres);
+                else
+                    hipk_gm_update_stream_kernel<T, HIPK_GM_MAXM_BIG + 1><<<gl, HIPK_THREADS, 0, stream>>>(n, ch, scal, k, pass, V, ldv, w,
+                                                                                                        part_qq + c0, nres);
                 HIPK_TRY(xc.parts(part_qq));
             }
             hipk_gm_normalize_kernel<T><<<gl, HIPK_THREADS, 0, stream>>>(n, ch, G, scal, k, w, part_qq, part_ww, eps_t, 0, 0);
         }
         if (hipGetLastError() != hipSuccess || hipMemcpyAsync(hs, scal, sizeof(*hs), hipMemcpyDeviceToHost, stream) != hipSuccess ||
+            (big_n && hipMemcpyAsync(big_host.data(), big, big_n * sizeof(double), hipMemcpyDeviceToHost, stream) != hipSuccess) ||
             hipStreamSynchronize(stream) != hipSuccess) {
-            hipk_set_error("hipk_dist_gmres_solve: HIP failure inside a restart cycle");
+            hipk_set_error("%s: HIP failure inside a restart cycle", loop);
             return HIPK_ERR_HIP;
         }
         const int k = (int)hs->steps_done;
         matvecs += k;
         if (hs->breakdown) happy = 1;
-        hipk_gm_y yy;
-        memset(&yy, 0, sizeof(yy));
+        hipk_gm_yN<HIPK_GM_MAXM_BIG + 1> yb;
+        memset(&yb, 0, sizeof(yb));
         if (k > 0) {
+            // the cycle's small arrays: the struct's own (ld 32) or the workspace block's host copy (hipk_gm_cycle_init_kernel's layout)
+            const int ldh = big_n ? hipk_gm_big_ld(m) : HIPK_GM_LDH;
+            const double *Hh = big_n ? big_host.data() : hs->H;
+            const double *Rh = big_n ? Hh + (size_t)(m + 2) * ldh : hs->R;
+            const double *bvh = big_n ? Rh + (size_t)ldh * ldh + 2 * ldh : hs->beta_vec;
             if (!incremental) {
-                hipk_lstsq_normal(hs->H, HIPK_GM_LDH, k, res_norm, yy.y);
+                hipk_lstsq_normal(Hh, ldh, k, res_norm, yb.y);
             } else {
                 for (int i = k - 1; i >= 0; --i) {  // solve_triangular, TSL:630
-                    double sacc = hs->beta_vec[i];
-                    for (int p = i + 1; p < k; ++p) sacc = fma(-hs->R[i * HIPK_GM_LDH + p], yy.y[p], sacc);
-                    yy.y[i] = sacc / hs->R[i * HIPK_GM_LDH + i];
+                    double sacc = bvh[i];
+                    for (int p = i + 1; p < k; ++p) sacc = fma(-Rh[i * ldh + p], yb.y[p], sacc);
+                    yb.y[i] = sacc / Rh[i * ldh + i];
                 }
             }
-            hipk_gm_xupdate_kernel<T><<<gl, HIPK_THREADS, 0, stream>>>(n, ch, k, V, ldv, x, yy);
+            if (k <= HIPK_GM_LDH) {
+                hipk_gm_y yy;
+                memcpy(yy.y, yb.y, sizeof(yy.y));
+                hipk_gm_xupdate_kernel<T><<<gl, HIPK_THREADS, 0, stream>>>(n, ch, k, V, ldv, x, yy);
+            } else {
+                hipk_gm_xupdate_kernel<T, HIPK_GM_MAXM_BIG + 1><<<gl, HIPK_THREADS, 0, stream>>>(n, ch, k, V, ldv, x, yb);
+            }
         }
         HIPK_TRY(residual());
         ++matvecs;
         if (hipMemcpyAsync(head, scal, sizeof(head), hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) {
-            hipk_set_error("hipk_dist_gmres_solve: HIP failure at the end of a restart cycle");
+            hipk_set_error("%s: HIP failure at the end of a restart cycle", loop);
             return HIPK_ERR_HIP;
         }
         res_norm = head[0];
@@ -2892,7 +3010,7 @@ static int hipk_dist_gmres_t(bool pre, hipk_csr_t A, const hipk_dist_plan *pl, c
 
 extern "C" int hipk_dist_gmres_solve(hipk_csr_t A, const hipk_dist_plan *pl, const hipk_rccl *cc, const void *b_local, void *x_ext,
                                      void *work, size_t work_bytes, const hipk_params *prm, hipk_stats *st, hipk_stream_t stream) {
-    return hipk_dist_gmres_t(false, A, pl, cc, nullptr, b_local, x_ext, work, work_bytes, prm, st, stream);
+    return hipk_dist_gmres_t(false, false, A, pl, cc, nullptr, b_local, x_ext, work, work_bytes, prm, st, stream);
 }
 
 extern "C" size_t hipk_dist_pgmres_work_bytes(const hipk_dist_plan *plan, int restart) {
@@ -2902,7 +3020,22 @@ extern "C" size_t hipk_dist_pgmres_work_bytes(const hipk_dist_plan *plan, int re
 extern "C" int hipk_dist_pgmres_solve(hipk_csr_t A, const hipk_dist_plan *pl, const hipk_rccl *cc, const void *dinv, const void *b_local,
                                       void *x_ext, void *work, size_t work_bytes, const hipk_params *prm, hipk_stats *st,
                                       hipk_stream_t stream) {
-    return hipk_dist_gmres_t(true, A, pl, cc, (const double *)dinv, b_local, x_ext, work, work_bytes, prm, st, stream);
+    return hipk_dist_gmres_t(true, false, A, pl, cc, (const double *)dinv, b_local, x_ext, work, work_bytes, prm, st, stream);
+}
+
+extern "C" int hipk_dist_gmres_wide_solve(hipk_csr_t A, const hipk_dist_plan *pl, const hipk_rccl *cc, const void *b_local, void *x_ext,
+                                          void *work, size_t work_bytes, const hipk_params *prm, hipk_stats *st, hipk_stream_t stream) {
+    return hipk_dist_gmres_t(false, true, A, pl, cc, nullptr, b_local, x_ext, work, work_bytes, prm, st, stream);
+}
+
+extern "C" size_t hipk_dist_pgmres_wide_work_bytes(const hipk_dist_plan *plan, int restart) {
+    return hipk_dist_gmres_wide_work_bytes(plan, restart);
+}
+
+extern "C" int hipk_dist_pgmres_wide_solve(hipk_csr_t A, const hipk_dist_plan *pl, const hipk_rccl *cc, const void *dinv,
+                                           const void *b_local, void *x_ext, void *work, size_t work_bytes, const hipk_params *prm,
+                                           hipk_stats *st, hipk_stream_t stream) {
+    return hipk_dist_gmres_t(true, true, A, pl, cc, (const double *)dinv, b_local, x_ext, work, work_bytes, prm, st, stream);
 }
 
 #ifdef HIPK_GM_STAMPS

@@ -45,6 +45,9 @@ SYMBOLS = [
     # ... the same three loops with the Jacobi preconditioner
     "hipk_dist_pcg_work_bytes", "hipk_dist_pcg_solve", "hipk_dist_pbicgstab_work_bytes", "hipk_dist_pbicgstab_solve",
     "hipk_dist_pgmres_work_bytes", "hipk_dist_pgmres_solve",
+    # ... row-partitioned GMRES at restart 32 .. 255
+    "hipk_dist_gmres_wide_work_bytes", "hipk_dist_gmres_wide_solve",
+    "hipk_dist_pgmres_wide_work_bytes", "hipk_dist_pgmres_wide_solve",
     # experimental mailbox exchange provider for that loop
     "hipk_p2p_create", "hipk_p2p_create2", "hipk_p2p_export", "hipk_p2p_connect", "hipk_p2p_destroy", "hipk_p2p_error",
     "hipk_p2p_group_start", "hipk_p2p_group_end", "hipk_p2p_all_gather",
@@ -230,16 +233,18 @@ def lib():
     L.hipk_dist_bicgstab_work_bytes.restype = ctypes.c_size_t
     L.hipk_dist_bicgstab_solve.argtypes = [vp, ctypes.POINTER(DistPlan), ctypes.POINTER(Rccl), vp, vp, vp, ctypes.c_size_t,
                                            ctypes.POINTER(Params), ctypes.POINTER(Stats), vp]
-    L.hipk_dist_gmres_work_bytes.argtypes = [ctypes.POINTER(DistPlan), i32]
-    L.hipk_dist_gmres_work_bytes.restype = ctypes.c_size_t
-    L.hipk_dist_gmres_solve.argtypes = [vp, ctypes.POINTER(DistPlan), ctypes.POINTER(Rccl), vp, vp, vp, ctypes.c_size_t,
-                                        ctypes.POINTER(Params), ctypes.POINTER(Stats), vp]
+    for name in ("gmres", "gmres_wide"):
+        getattr(L, f"hipk_dist_{name}_work_bytes").argtypes = [ctypes.POINTER(DistPlan), i32]
+        getattr(L, f"hipk_dist_{name}_work_bytes").restype = ctypes.c_size_t
+        getattr(L, f"hipk_dist_{name}_solve").argtypes = [vp, ctypes.POINTER(DistPlan), ctypes.POINTER(Rccl), vp, vp, vp,
+                                                          ctypes.c_size_t, ctypes.POINTER(Params), ctypes.POINTER(Stats), vp]
     for name in ("pcg", "pbicgstab"):
         getattr(L, f"hipk_dist_{name}_work_bytes").argtypes = [ctypes.POINTER(DistPlan)]
         getattr(L, f"hipk_dist_{name}_work_bytes").restype = ctypes.c_size_t
-    L.hipk_dist_pgmres_work_bytes.argtypes = [ctypes.POINTER(DistPlan), i32]
-    L.hipk_dist_pgmres_work_bytes.restype = ctypes.c_size_t
-    for name in ("pcg", "pbicgstab", "pgmres"):   # + dinv_ext after the collective struct
+    for name in ("pgmres", "pgmres_wide"):
+        getattr(L, f"hipk_dist_{name}_work_bytes").argtypes = [ctypes.POINTER(DistPlan), i32]
+        getattr(L, f"hipk_dist_{name}_work_bytes").restype = ctypes.c_size_t
+    for name in ("pcg", "pbicgstab", "pgmres", "pgmres_wide"):   # + dinv_ext after the collective struct
         getattr(L, f"hipk_dist_{name}_solve").argtypes = [vp, ctypes.POINTER(DistPlan), ctypes.POINTER(Rccl), vp, vp, vp, vp,
                                                           ctypes.c_size_t, ctypes.POINTER(Params), ctypes.POINTER(Stats), vp]
     L.hipk_p2p_create.argtypes = [ctypes.POINTER(vp), i32, i32, ctypes.c_size_t]

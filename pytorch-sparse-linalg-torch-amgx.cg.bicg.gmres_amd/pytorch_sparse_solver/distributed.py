@@ -356,6 +356,7 @@ class DistStats:
     method: str = ""
     preconditioner: str = ""     # "jacobi": M = diag(A)^-1 (residual_norm is then ||M (b - A x)||, as on one device)
     solve_ms: float = 0.0        # the C-driven loops: device time of the solve (events around it on the solver's stream)
+    breakdown: int = 0           # the C-driven loops: hipk_stats.breakdown (GMRES: a Krylov space closed inside a cycle)
 
 
 class DistProblem:
@@ -420,10 +421,11 @@ class DistProblem:
         # "fused": the mailboxes also carry the fused area -- the two exchanges of a CG iteration are made by its update /
         # direction kernels themselves, no collective launch inside the loop (csrc/hipk_fx.h); set-up and the final residual go
         # through the mailbox all-gather.  Built and tested with ranks sharing one GPU; over xGMI unmeasured, so RCCL stays default.
+        # The mailboxes take the largest exchange: the multi-dot block of GMRES at restart 255, (k + 1) * per <= 256 * per doubles.
         self.p2p = None
         if want in ("p2p", "fused") and isinstance(ops, HipOps) and (part.world == 1 or dist.is_initialized()):
             fx = want == "fused"
-            self.p2p = P2PComm(part.rank, part.world, ops.device, max(part.per, self.plan.slab), group,
+            self.p2p = P2PComm(part.rank, part.world, ops.device, max(256 * part.per, self.plan.slab), group,
                                fx_per=part.per if fx else 0, fx_ghost_cap=self.plan.ghost_cap if fx else 0)
             self.comm_kind = "p2p-mailbox, exchanges fused into the CG kernels" if fx else "p2p-mailbox"
 
@@ -526,9 +528,11 @@ def _dist_cg_native(prob: DistProblem, x0_local, tol, atol, maxiter, check_every
     pre = "p" if dinv is not None else ""
     if pre:
         assert dinv.dtype == torch.float64 and dinv.numel() == max(prob.n_ext, 1) and dinv.device == x.device and dinv.is_contiguous()
+    if solver == "gmres" and int(restart) > 31:
+        solver = "gmres_wide"       # restart 32 .. 255: H in the workspace, one all-gather per CGS pass (hipk_dist_gmres_wide_solve)
     solve_fn = getattr(L, f"hipk_dist_{pre}{solver}_solve")
-    if solver == "gmres":
-        wb = int(getattr(L, f"hipk_dist_{pre}gmres_work_bytes")(ctypes.byref(plan), int(restart)))
+    if solver.startswith("gmres"):
+        wb = int(getattr(L, f"hipk_dist_{pre}{solver}_work_bytes")(ctypes.byref(plan), int(restart)))
     else:
         wb = int(getattr(L, f"hipk_dist_{pre}{solver}_work_bytes")(ctypes.byref(plan)))
     work = torch.empty(wb, dtype=torch.uint8, device=dev)
@@ -536,7 +540,7 @@ def _dist_cg_native(prob: DistProblem, x0_local, tol, atol, maxiter, check_every
     prm.tol, prm.atol = float(tol), float(atol)
     prm.maxiter = -1 if maxiter is None else int(maxiter)
     prm.check_every = int(check_every)
-    if solver == "gmres":
+    if solver.startswith("gmres"):
         prm.restart = int(restart)
         prm.gmres_method = {"batched": 0, "incremental": 1}[solve_method]
         prm.gpu_tolerances = 1          # the reference's `device.type == 'cuda'` tolerance branch (TSL:737-740)
@@ -550,7 +554,8 @@ def _dist_cg_native(prob: DistProblem, x0_local, tol, atol, maxiter, check_every
     if getattr(prob, "p2p", None) is not None and prob.p2p.failed():
         raise RuntimeError("hipk_p2p: a rank never published its part of an exchange (wait bound hit); results discarded")
     return x[:n], int(st.info), DistStats(int(st.iterations), int(st.matvecs), int(st.info), st.b_norm, st.residual_norm,
-                                          st.x_norm, st.threshold, preconditioner="jacobi" if pre else "", solve_ms=float(st.solve_ms))
+                                          st.x_norm, st.threshold, preconditioner="jacobi" if pre else "", solve_ms=float(st.solve_ms),
+                                          breakdown=int(st.breakdown))
 
 
 def _need_native(prob: DistProblem, what: str) -> None:
@@ -592,13 +597,15 @@ def dist_bicgstab(prob: DistProblem, x0_local: Optional[torch.Tensor] = None, *,
 def dist_gmres(prob: DistProblem, x0_local: Optional[torch.Tensor] = None, *, tol: float = 1e-5, atol: float = 0.0,
                restart: int = 20, maxiter: Optional[int] = None, solve_method: str = "batched", dinv: Optional[torch.Tensor] = None):
     """Row-partitioned GMRES (`hipk_dist_gmres_solve`): returns (x_local, info, DistStats with iterations = restart cycles); bit
-    for bit the iterates of the single-device `gmres` on a CUDA tensor.  C-driven loop only, restart <= 31.  `dinv`
-    (`jacobi_dinv_ext`): left Jacobi preconditioning (`hipk_dist_pgmres_solve`)."""
+    for bit the iterates of the single-device `gmres` on a CUDA tensor.  C-driven loop only, restart 1 .. 255: up to 31 the
+    loop with H in its header block, 32 .. 255 `hipk_dist_gmres_wide_solve` (H in the workspace, one all-gather of the multi-dot
+    partials per CGS pass whatever the step).  `dinv` (`jacobi_dinv_ext`): left Jacobi preconditioning
+    (`hipk_dist_pgmres_solve` / `hipk_dist_pgmres_wide_solve`)."""
     _need_native(prob, "dist_gmres")
     if solve_method not in ("batched", "incremental"):
         raise ValueError(f"invalid solve_method {solve_method}, must be either 'batched' or 'incremental'")
-    if not 1 <= int(restart) <= 31:
-        raise ValueError("dist_gmres: restart must be in [1, 31]")
+    if not 1 <= int(restart) <= 255:
+        raise ValueError("dist_gmres: restart must be in [1, 255]")
     return _dist_cg_native(prob, x0_local, tol, atol, maxiter, 0, solver="gmres", restart=restart, solve_method=solve_method,
                            dinv=dinv)
 

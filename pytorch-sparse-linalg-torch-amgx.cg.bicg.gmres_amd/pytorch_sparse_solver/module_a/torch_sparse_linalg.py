@@ -685,7 +685,8 @@ def gmres(A: Union[torch.Tensor, Callable[[Any], Any]], b: Any, x0: Optional[Any
           solve_method: str = 'batched') -> Tuple[Any, Optional[int]]:
     """Restarted GMRES (TSL:641-784). `maxiter` counts restart cycles; `solve_method` is
     'batched' (least squares by normal equations at the end of a cycle) or 'incremental'
-    (Givens QR with early exit inside a cycle). Returns `(x, info)`.  `A` may be a `RowBlockCSR` (see `cg`; restart <= 31 there)."""
+    (Givens QR with early exit inside a cycle). Returns `(x, info)`.  `A` may be a `RowBlockCSR` (see `cg`; restart 1 .. 255
+    there, ValueError beyond)."""
     if _is_row_block(A):
         return _dist_solve('gmres', A, b, x0, tol, atol, maxiter, M, restart=restart, solve_method=solve_method)
     diff = _use_implicit_diff(A, b)
