@@ -185,9 +185,9 @@ static hipError_t hipk_build_coded(hipk_csr_s *h, hipStream_t stream) {
     if (e != hipSuccess) return e;
 
     // layout of the code bytes: sliced-ELL planes when the padding stays small, else CSR order + row lengths
-    const char *lay = getenv("HIPK_SPMV_CODED_LAYOUT");
+    const bool lay_csr = hipk_sw_word_is("HIPK_SPMV_CODED_LAYOUT", "csr");
     // (the persistent sliced-ELL kernel needs n_rows <= n_cols and 32-bit byte offsets into x)
-    const bool want_sell = (OFFS_ONLY || !(lay && strcmp(lay, "csr") == 0)) && nc <= HIPK_SELL_PAD &&
+    const bool want_sell = (OFFS_ONLY || !lay_csr) && nc <= HIPK_SELL_PAD &&
                            h->n_rows <= h->n_cols && (uint64_t)h->n_cols * sizeof(T) < (1ull << 32);
     if (OFFS_ONLY && !want_sell) return hipSuccess;  // the offset-coded form exists in the sliced-ELL layout only
     const int ntiles = (int)((h->n_rows + HIPK_TILE - 1) / HIPK_TILE);
@@ -242,8 +242,7 @@ static hipError_t hipk_build_coded(hipk_csr_s *h, hipStream_t stream) {
                 e = hipGetLastError();
             }
             // tiles whose rows all carry the same code bytes (constant-coefficient stencils: all but the grid-line ends)
-            const char *uenv = getenv("HIPK_SPMV_UNIFORM");
-            if (e == hipSuccess && !(uenv && uenv[0] == '0')) {
+            if (e == hipSuccess && hipk_sw_enabled("HIPK_SPMV_UNIFORM")) {
                 int *ucount = nullptr;
                 e = hipMalloc((void **)&h->tile_ucode, sizeof(unsigned long long) * (size_t)ntiles + 2 * sizeof(int));
                 if (e == hipSuccess) {
@@ -263,8 +262,7 @@ static hipError_t hipk_build_coded(hipk_csr_s *h, hipStream_t stream) {
                 // free for the marker.  OPT-IN (HIPK_SPMV_MASKED=1): bit-identical, but measured SLOWER where it was meant to help
                 // (N = 4 M: 15.7-16.2 vs 14.6-14.9 us stand-alone, CG 17.6 vs 17.97 k it/s; N = 1.96 M: equal;
                 // profiles/r03_spmv_wide_stamps.md section 4)
-                const char *menv = getenv("HIPK_SPMV_MASKED");
-                if (e == hipSuccess && !OFFS_ONLY && sizeof(T) == 8 && nc <= 254 && menv && menv[0] == '1') {
+                if (e == hipSuccess && !OFFS_ONLY && sizeof(T) == 8 && nc <= 254 && hipk_sw_force("HIPK_SPMV_MASKED", false)) {
                     int *mcount = nullptr;
                     e = hipMalloc((void **)&h->tile_wcode, sizeof(unsigned long long) * (size_t)ntiles + 2 * sizeof(int));
                     if (e == hipSuccess) e = hipMalloc((void **)&h->row_mask, (size_t)ntiles * HIPK_TILE + 16);
@@ -452,25 +450,23 @@ extern "C" int hipk_csr_create_ex(hipk_csr_t *out, int64_t n_rows, int64_t n_col
         h->n_huge = cnt_h;
     }
     // coded form: short rows everywhere, mean row below the row-per-wavefront threshold, not disabled by the environment
-    h->sell_chunked = 2;  // chunk-per-workgroup form when sell_chunked * chunks >= resident workgroups (0: never)
-    if (const char *sc = getenv("HIPK_SPMV_SELL_CHUNKED")) h->sell_chunked = atoi(sc) < 0 ? 0 : (atoi(sc) == 1 ? 2 : atoi(sc));
-    h->sell_loop = 1;  // persistent sliced-ELL kernel: grid = sell_loop x the resident workgroups
-    if (const char *sl = getenv("HIPK_SPMV_SELL_LOOP")) h->sell_loop = atoi(sl) < 1 ? 1 : (atoi(sl) > 4 ? 4 : atoi(sl));
+    // chunk-per-workgroup form when sell_chunked * chunks >= resident workgroups (0: never; a 1 reads as 2)
+    h->sell_chunked = (int)hipk_sw_int("HIPK_SPMV_SELL_CHUNKED", 2, 0, INT32_MAX);
+    if (h->sell_chunked == 1) h->sell_chunked = 2;
+    h->sell_loop = (int)hipk_sw_int("HIPK_SPMV_SELL_LOOP", 1, 1, 4);  // persistent sliced-ELL kernel: grid = sell_loop x the resident workgroups
     {
         hipDeviceProp_t prop;
         h->n_cu = (hipGetDeviceProperties(&prop, h->device) == hipSuccess && prop.multiProcessorCount > 0)
                       ? prop.multiProcessorCount : 256;
     }
-    const char *env = getenv("HIPK_SPMV_CODED");
-    if (n_rows > 0 && nnz > 0 && h->max_row_len <= HIPK_LONG_ROW && !(env && env[0] == '0')) {
+    if (n_rows > 0 && nnz > 0 && h->max_row_len <= HIPK_LONG_ROW && hipk_sw_enabled("HIPK_SPMV_CODED")) {
         e = (dtype == HIPK_F64) ? hipk_build_coded<double, false>(h, stream) : hipk_build_coded<float, false>(h, stream);
         if (e != hipSuccess) (void)hipGetLastError();  // e.g. out of memory: stay on the plain kernels
         if (h->n_codes == 0) {
             // too many distinct (offset, value) pairs: try offsets alone, values kept per entry (9 B instead of 12 B per
             // entry, no row pointers) -- HIPK_SPMV_OFFSET_CODED=0 skips it
             hipk_drop_coded(h);
-            const char *oc = getenv("HIPK_SPMV_OFFSET_CODED");
-            if (!(oc && oc[0] == '0')) {
+            if (hipk_sw_enabled("HIPK_SPMV_OFFSET_CODED")) {
                 e = (dtype == HIPK_F64) ? hipk_build_coded<double, true>(h, stream) : hipk_build_coded<float, true>(h, stream);
                 if (e != hipSuccess) (void)hipGetLastError();
             }
@@ -678,7 +674,7 @@ int hipk_launch_spmv(const hipk_csr_s *h, const hipk_spmv_args &a_, hipStream_t 
             void (*kern)(hipk_spmv_args) = nullptr;
             int lgrid = 0;
             bool chunked = false, strided = false;
-            static const bool no_plan_cache = getenv("HIPK_SPMV_NO_PLAN_CACHE") != nullptr;
+            static const bool no_plan_cache = hipk_sw_present("HIPK_SPMV_NO_PLAN_CACHE");
             const hipk_spmv_plan *pl = nullptr;
             for (int i = 0; i < h->n_plans && !no_plan_cache; ++i)
                 if (h->plans[i].mode == a.mode && h->plans[i].ch == a.ch && h->plans[i].g == a.g) pl = &h->plans[i];
@@ -706,13 +702,13 @@ int hipk_launch_spmv(const hipk_csr_s *h, const hipk_spmv_args &a_, hipStream_t 
                 // one workgroup per reduction chunk when the chunks about fill the machine in one round
                 // (default: the chunks fill at least half of the slots; a quarter where the two-rows-per-lane kernel applies --
                 // N = 1.96 M Poisson: 28.2 -> 30.2 k CG it/s, no gain below a quarter)
-                static const bool chunked_env = getenv("HIPK_SPMV_SELL_CHUNKED") != nullptr;
+                static const bool chunked_env = hipk_sw_present("HIPK_SPMV_SELL_CHUNKED");
                 const bool wide_ok = h->dtype == HIPK_F64 && h->tile_ucode && 2 * (h->n_uniform_tiles + h->n_masked_tiles) >= ntiles && h->coded_layout == 2 &&
                                      (h->sell_w == 4 || h->sell_w == 5 || h->sell_w == 8);
                 const int cfac = (!chunked_env && wide_ok && h->sell_chunked == 2) ? 4 : h->sell_chunked;
                 chunked = h->sell_chunked != 0 && tpc <= HIPK_SELL_MAX_TPC && a.g <= slots && cfac * a.g >= slots;
-                static const bool no_mode = getenv("HIPK_SPMV_SELL_NO_MODE") != nullptr;
-                const bool no_wide = getenv("HIPK_SPMV_SELL_NO_WIDE") != nullptr;  // read per launch: in-process A/B (tools/gmres_variants.py)
+                static const bool no_mode = hipk_sw_present("HIPK_SPMV_SELL_NO_MODE");
+                const bool no_wide = hipk_sw_present("HIPK_SPMV_SELL_NO_WIDE");  // read per launch: in-process A/B (tools/gmres_variants.py)
                 constexpr int both = HIPK_SPMV_DOT_W | HIPK_SPMV_DOT_YY;
                 // uniform tiles two rows per lane (hipk_spmv_sell_wide_kernel; fp64, most tiles uniform), mode bits compiled in for
                 // the CG loop's form, the Arnoldi step's, BiCGStab's t = A s with <t, s> and <t, t> (TSL:925-927), plain y = A x
@@ -742,8 +738,7 @@ int hipk_launch_spmv(const hipk_csr_s *h, const hipk_spmv_args &a_, hipStream_t 
                 // slower at N = 4 M (8 tiles per chunk, 56.6 -> 58.7: one more launch): not taken there.
                 // HIPK_SPMV_SELL_STRIDED=0|1 forces (read per launch: in-process A/B, tools/walk_probe.py)
                 if (wide_ok && !no_wide && h->sell_chunked != 0) {
-                    const char *se = getenv("HIPK_SPMV_SELL_STRIDED");
-                    if (se ? atoi(se) != 0 : tpc >= (chunked ? 16 : 32)) {
+                    if (hipk_sw_int("HIPK_SPMV_SELL_STRIDED", tpc >= (chunked ? 16 : 32)) != 0) {
                         char pname[96];
                         kern = pick_wide(1, pname, sizeof(pname));
                         lgrid = hipk_xcd_grid((ntiles + HIPK_SELL_GROUP - 1) / HIPK_SELL_GROUP);
@@ -758,8 +753,7 @@ int hipk_launch_spmv(const hipk_csr_s *h, const hipk_spmv_args &a_, hipStream_t 
                 // switch forces it for any layout (tests, A/B)
                 a.group_tiles = 0;
                 if (!strided && h->sell_chunked != 0) {
-                    const char *se = getenv("HIPK_SPMV_SELL_STRIDED");
-                    if (se ? atoi(se) != 0 : (h->coded_layout == 3 && tpc >= 32)) {
+                    if (hipk_sw_int("HIPK_SPMV_SELL_STRIDED", h->coded_layout == 3 && tpc >= 32) != 0) {
                         kern = (h->dtype == HIPK_F64) ? HIPK_PICK_LOOP(double, true) : HIPK_PICK_LOOP(float, true);
                         a.group_tiles = HIPK_SELL_GROUP;
                         lgrid = hipk_xcd_grid((ntiles + HIPK_SELL_GROUP - 1) / HIPK_SELL_GROUP);
@@ -775,7 +769,7 @@ int hipk_launch_spmv(const hipk_csr_s *h, const hipk_spmv_args &a_, hipStream_t 
                     HIPK_NOTE_KERNEL("hipk_spmv_sell_loop_kernel<%s,%d,true,%s,%s>", tname, uw, vls, uni);
                     char pname[96];
                     // pair codes with an exact tile size: two tiles per loop trip (hipk_spmv_sell_pair_kernel)
-                    static const bool no_pair = getenv("HIPK_SPMV_SELL_NO_PAIR") != nullptr;
+                    static const bool no_pair = hipk_sw_present("HIPK_SPMV_SELL_NO_PAIR");
                     if (!no_pair && h->coded_layout == 2 && (h->sell_w == 4 || h->sell_w == 5 || h->sell_w == 8)) {
 #define HIPK_PICK_PAIR_U(T, U) \
         (h->sell_w == 5 ? hipk_spmv_sell_pair_kernel<T, 5, U> : h->sell_w == 8 ? hipk_spmv_sell_pair_kernel<T, 8, U> : hipk_spmv_sell_pair_kernel<T, 4, U>)

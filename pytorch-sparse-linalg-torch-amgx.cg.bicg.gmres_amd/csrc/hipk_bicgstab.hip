@@ -697,6 +697,59 @@ static hipk_loop_state hipk_bi_loop_state(const hipk_bi_scal &h) { return {h.red
 // cb != null (PRE = false): the preconditioner is the CALLER's device code -- cb(user, in, out) enqueues out = M(in) on
 // `stream` -- applied where the Jacobi variant scales in-kernel: phat = M(p) before the first SpMV, shat = M(s) before the
 // second (TSL:908, 922), M(b - A x) for the final test (TSL:1007).  Same kernels, same order of operations.
+// ---- which paths a bicgstab solve takes (PRE: Jacobi; ext: the caller's M through a callback): the only place that knows
+// BiCGStab's switches and size limits.  Two steps, because a mid loop that handed the solve back changes what the LDS loop may do:
+//   hipk_bi_path_begin   before the iteration loop: small and the mid loop
+//   hipk_bi_path_lds     after the mid loop (mid_done: it finished the solve), at iteration `it`: the LDS loop
+// What is left is the five-launch sequence (small picks its kernels).
+struct hipk_bi_path {
+    bool small = false;      // <= 8 reduction chunks: both SpMVs skip their combine launch, the consumers fold the tile sums
+    bool mid = false;        // hipk_bi_mid_kernel: the whole loop in one launch, one workgroup per chunk (hipk_bi_mid.h)
+    const hipk_mid_entry<hipk_bi_mid_args> *mid_entry = nullptr;
+    hipk_mid_plan mid_plan;
+    size_t mid_lds = 0;
+    bool lds_loop = false;   // hipk_bi_solve_lds_kernel: the whole loop in one launch, eight workgroups per chunk
+    bool spread = false;     // ... spread over the chip (more than 64 workgroups) instead of on ONE XCD
+    bool local = false;      // ... hand-offs through that XCD's L2 (a -2 of the kernel: agent scope from then on)
+    int64_t max_its = 0;     // iterations one launch of either loop may run
+};
+
+template <typename T, bool PRE>
+static hipk_bi_path hipk_bi_path_begin(hipk_csr_s *A, const hipk_params *prm, bool ext, int64_t maxiter, bool mid_failed, hipStream_t stream) {
+    const int g = A->geom.g;
+    hipk_bi_path path;
+    path.small = g <= 8 && !hipk_sw_present("HIPK_BICGSTAB_NO_SMALL");
+    // launch-bound systems of 9 .. 256 chunks (fp64, M = identity or Jacobi, rows of <= 12 entries within a window around their
+    // chunk): one workgroup per chunk, one per CU; HIPK_BICGSTAB_MID=0 leaves them to the paths below
+    path.mid_entry = hipk_mid_pick(hipk_bi_mid_table<T>, A->max_row_len, 1, PRE);
+    auto mid_lds = [](int slots) { return hipk_bi_mid_lds_bytes(slots * HIPK_TILE, PRE, sizeof(T)); };
+    // (hipk_mid_eligible last: it builds the handle's window plan on the stream and queries occupancy)
+    path.mid = !ext && g > kMidMinChunks && g <= kBiMidMaxChunks && g <= A->n_cu && A->geom.ch == HIPK_BASE_CHUNK && A->op_cb == nullptr &&
+               A->crow != nullptr && A->max_row_len <= 12 && prm->profile == 0 && maxiter > 0 && !mid_failed &&
+               hipk_sw_enabled("HIPK_BICGSTAB_MID") && !hipk_sw_present("HIPK_BICGSTAB_NO_LDS_LOOP") && !hipk_sw_present("HIPK_BICGSTAB_NO_SMALL") &&
+               path.mid_entry && hipk_mid_eligible(A, path.mid_entry, g, mid_lds, stream, &path.mid_plan, &path.mid_lds);
+    if (path.mid) path.max_its = hipk_sw_int("HIPK_BICGSTAB_LAUNCH_ITS", 8192, 1);
+    return path;
+}
+
+// launch-bound systems with short rows, M = identity or Jacobi: up to 64 workgroups (8 chunks) on ONE XCD; up to 32 chunks
+// (n <= 65536) spread over the chip, two workgroups per compute unit.  lds_failed: its workgroups once failed to meet (a shared
+// device): do not wait for that verdict again.  it == 0: after the mid loop gave up mid-solve, part_rr / part_rhr hold CHUNK
+// partials, which only the launch sequence folds
+static void hipk_bi_path_lds(hipk_bi_path &path, const hipk_csr_s *A, const hipk_params *prm, bool ext, int64_t maxiter, bool mid_done,
+                             int64_t it, bool lds_failed) {
+    const int g = A->geom.g;
+    path.spread = kGmSub * g > 64;
+    path.lds_loop = g <= 32 && !hipk_sw_present("HIPK_BICGSTAB_NO_SMALL") && !ext && A->geom.ch == HIPK_BASE_CHUNK &&
+                    A->max_row_len <= kBiRowRegs && prm->profile == 0 && maxiter > 0 &&
+                    kGmSub * g <= (path.spread ? 2 * A->n_cu : 2 * (A->n_cu / 8)) && !lds_failed &&
+                    !hipk_sw_present("HIPK_BICGSTAB_NO_LDS_LOOP") && !(path.spread && hipk_sw_present("HIPK_NO_LDS_SPREAD")) && !mid_done && it == 0;
+    if (path.lds_loop) {
+        path.local = !path.spread && !hipk_sw_present("HIPK_BICGSTAB_LOOP_AGENT");
+        path.max_its = hipk_sw_int("HIPK_BICGSTAB_LAUNCH_ITS", 8192, 1);
+    }
+}
+
 template <typename T, bool PRE>
 static int hipk_bicgstab_solve_t(hipk_csr_s *A, const T *dinv, const T *b, T *x, char *work, const hipk_params *prm,
                                  hipk_stats *st, hipStream_t stream, hipk_precond_fn cb = nullptr, void *user = nullptr) {
@@ -769,25 +822,21 @@ static int hipk_bicgstab_solve_t(hipk_csr_s *A, const T *dinv, const T *b, T *x,
     stt.part1 = part_tt;
     stt.stop_it = &scal->stop_it;
 
-    // launch-bound systems (<= 8 reduction chunks): both SpMVs skip their combine launch, the consumers fold the tile sums
-    const bool small = gm.g <= 8 && !getenv("HIPK_BICGSTAB_NO_SMALL");
+    // which paths this solve takes (hipk_bi_path above); the latches: a one-launch loop once handed a solve back in this process
+    static bool mid_failed = false, lds_loop_failed = false;
+    hipk_bi_path path = hipk_bi_path_begin<T, PRE>(A, prm, ext, maxiter, mid_failed, stream);
+    const bool small = path.small;
     const int nt = (int)((n + HIPK_TILE - 1) / HIPK_TILE);
     const double *tsum0 = A->tile_part, *tsum1 = A->tile_part + 4 * (size_t)nt;
     sq.skip_combine = stt.skip_combine = small ? 1 : 0;
 
     int64_t it = 0, stop = INT64_MAX;
-    // launch-bound systems of 9 .. 256 chunks (fp64, M = identity, rows of <= 12 entries within a window around their chunk): the
-    // whole loop in one launch, one workgroup per chunk (hipk_bi_mid.h); HIPK_BICGSTAB_MID=0 leaves them to the paths below
-    static bool mid_failed = false;
-    const hipk_mid_entry<hipk_bi_mid_args> *mid = hipk_mid_pick(hipk_bi_mid_table<T>, A->max_row_len, 1, PRE);
-    auto mid_lds = [](int slots) { return hipk_bi_mid_lds_bytes(slots * HIPK_TILE, PRE, sizeof(T)); };
-    hipk_mid_plan plan;
-    size_t lds = 0;
-    bool mid_loop = !ext && gm.g > kMidMinChunks && gm.g <= kBiMidMaxChunks && gm.g <= A->n_cu && gm.ch == HIPK_BASE_CHUNK && A->op_cb == nullptr &&
-                    A->crow != nullptr && A->max_row_len <= 12 && prm->profile == 0 && maxiter > 0 && !mid_failed &&
-                    !(getenv("HIPK_BICGSTAB_MID") && getenv("HIPK_BICGSTAB_MID")[0] == '0') && !getenv("HIPK_BICGSTAB_NO_LDS_LOOP") &&
-                    !getenv("HIPK_BICGSTAB_NO_SMALL") && mid && hipk_mid_eligible(A, mid, gm.g, mid_lds, stream, &plan, &lds);
+    // the whole loop in one launch, one workgroup per chunk (hipk_bi_mid.h)
+    const hipk_mid_entry<hipk_bi_mid_args> *mid = path.mid_entry;
+    bool mid_loop = path.mid;
     if (mid_loop) {
+        const hipk_mid_plan &plan = path.mid_plan;
+        const size_t lds = path.mid_lds;
         hipk_bi_mid_args ca;
         ca.n = n;
         ca.g = gm.g;
@@ -810,7 +859,7 @@ static int hipk_bicgstab_solve_t(hipk_csr_s *A, const T *dinv, const T *b, T *x,
         ca.part_rhr = part_rhr;
         ca.scal = scal;
         ca.maxiter = maxiter;
-        ca.max_its = hipk_env_its("HIPK_BICGSTAB_LAUNCH_ITS", 8192);
+        ca.max_its = path.max_its;
         ca.slot_stride = gm.g <= 32 ? 1 : 16;
         ca.xcd_aware = 1;
         auto launch = [&](int64_t it0, int test_not_resident, bool) -> int {
@@ -827,17 +876,12 @@ static int hipk_bicgstab_solve_t(hipk_csr_s *A, const T *dinv, const T *b, T *x,
         if (run < 0) return run;
         mid_loop = run == HIPK_OK;
     }
-    // launch-bound systems with short rows, M = identity: the whole loop in one launch (hipk_bi_solve_lds_kernel)
-    static bool lds_loop_failed = false;   // its workgroups once failed to meet (a shared device): do not wait for that verdict again
-    // up to 64 workgroups (8 chunks) on ONE XCD; up to 32 chunks (n <= 65536) spread over the chip, two workgroups per compute unit
-    const bool lds_spread = kGmSub * gm.g > 64;
-    bool lds_loop = gm.g <= 32 && !getenv("HIPK_BICGSTAB_NO_SMALL") && !ext && gm.ch == HIPK_BASE_CHUNK &&
-                    A->max_row_len <= kBiRowRegs && prm->profile == 0 && maxiter > 0 &&
-                    kGmSub * gm.g <= (lds_spread ? 2 * A->n_cu : 2 * (A->n_cu / 8)) && !lds_loop_failed &&
-                    !getenv("HIPK_BICGSTAB_NO_LDS_LOOP") && !(lds_spread && getenv("HIPK_NO_LDS_SPREAD")) && !mid_loop &&
-                    it == 0;   // (after a one-launch loop above gave up mid-solve, part_rr / part_rhr hold CHUNK partials: launch sequence)
+    // the whole loop in one launch, eight workgroups per chunk (hipk_bi_solve_lds_kernel)
+    hipk_bi_path_lds(path, A, prm, ext, maxiter, mid_loop, it, lds_loop_failed);
+    const bool lds_spread = path.spread;
+    bool lds_loop = path.lds_loop;
     if (lds_loop) {
-        bool local = !lds_spread && !getenv("HIPK_BICGSTAB_LOOP_AGENT");   // a -2 (spread over several XCDs): agent-scope hand-offs
+        bool local = path.local;   // a -2 (spread over several XCDs): agent-scope hand-offs
         hipk_bi_lds_args<T> ca;
         ca.n = n;
         ca.g = gm.g;
@@ -864,7 +908,7 @@ static int hipk_bicgstab_solve_t(hipk_csr_s *A, const T *dinv, const T *b, T *x,
         ca.spread = lds_spread ? 1 : 0;
         const int lgrid = lds_spread ? kGmSub * gm.g : 8 * kGmSub * gm.g;
         ca.maxiter = maxiter;
-        ca.max_its = hipk_env_its("HIPK_BICGSTAB_LAUNCH_ITS", 8192);
+        ca.max_its = path.max_its;
         auto launch = [&](int64_t it0, int test_not_resident, bool loc) -> int {
             ca.it0 = it0;
             ca.test_not_resident = test_not_resident;

@@ -950,19 +950,111 @@ static const hipk_mid_entry<hipk_cg_mid_args> hipk_cg_mid_table[] = {
 #undef HIPK_MID_ROW
 static constexpr int kPcgMidMaxChunks = 256;                                 // one chunk per workgroup, one workgroup per CU
 static constexpr size_t kPcgMidSlotBytes = 3 * (size_t)kMidMaxChunks * 256;   // <p,Ap>, <r,r>, <r,z> slot arrays
+
+// ---- which paths a cg (PRE = false) or Jacobi pcg (PRE = true) solve takes: the only place that knows CG's switches and size
+// limits.  Three steps, because a loop that handed the solve back changes what the next path may do:
+//   hipk_cg_path_begin   before the iteration loop: small, streams, flat_dir and the mid loop
+//   hipk_cg_path_lds     after the mid loop (mid_done: it finished the solve): the LDS loop
+//   hipk_cg_path_two     after both loops (done: one of them finished), at iteration `it`: the two-launch sequence
+// What is left is the three-launch sequence (small / streams / flat_dir pick its kernels).
+struct hipk_cg_path {
+    bool small = false;        // <= 8 reduction chunks: no combine launch, the vector kernels fold the SpMV's tile sums (plain CG)
+    bool streams = false;      // plain CG: the vector kernels treat every operand as a stream
+    bool flat_dir = false;     // plain CG, with streams: the direction step as a scalars launch + a flat grid
+    bool mid = false;          // hipk_cg_mid_kernel: the whole loop in one launch, a workgroup per nch chunks (hipk_cg_mid.h)
+    const hipk_mid_entry<hipk_cg_mid_args> *mid_entry = nullptr;
+    hipk_mid_plan mid_plan;
+    size_t mid_lds = 0;
+    int nch = 1, slot_stride = 16, xcd_aware = 1;
+    bool lds_loop = false;     // hipk_cg_solve_lds_kernel: the whole loop in one launch, eight workgroups per chunk
+    bool spread = false;       // ... spread over the chip (more than 64 workgroups) instead of on ONE XCD
+    bool local = false;        // ... hand-offs through that XCD's L2 (a -2 of the kernel: agent scope from then on)
+    int64_t max_its = 0;       // iterations one launch of either loop may run
+    bool two_launch = false;   // plain CG: hipk_cg2_spmv_kernel + hipk_cg2_update_kernel per iteration
+};
+
+template <typename T, bool PRE>
+static hipk_cg_path hipk_cg_path_begin(hipk_csr_s *A, const hipk_params *prm, int64_t maxiter, bool mid_failed, hipStream_t stream) {
+    const int64_t n = A->n_rows;
+    const int g = A->geom.g;
+    hipk_cg_path path;
+    if (!PRE) {   // the Jacobi launch sequence has one form: its kernels fold chunk partials and use the default cache policy
+        path.small = g <= 8 && !hipk_sw_present("HIPK_CG_NO_SMALL");
+        // x, r, p, Ap beyond 1.5 x the 256 MiB Infinity Cache (HIPK_CG_STREAMS=0/1 forces the choice: A/B measurements)
+        path.streams = hipk_sw_force("HIPK_CG_STREAMS", 4 * (size_t)n * sizeof(T) > (size_t)384 << 20);
+        // with it, and a vector alone beyond the 256 MiB Infinity Cache, the direction step as a scalars launch + a flat grid
+        // (same vectors, same process, per CG iteration: N = 64 M 1079 -> 1011 us; N = 32 M 473 -> 471; N = 16 M, where p still finds
+        // room in that cache, 237 -> 246: not taken there).  HIPK_CG_FLAT_DIRECTION=0|1 forces (tools/flat_probe.py, tests)
+        path.flat_dir = hipk_sw_force("HIPK_CG_FLAT_DIRECTION", (size_t)n * sizeof(T) > ((size_t)256 << 20));
+    }
+    // launch-bound systems of 9 .. 512 chunks (fp64, rows of <= 12 entries within a window around their chunk): the whole loop in
+    // one launch, one workgroup of 1024 threads per CU; HIPK_CG_MID=0 leaves them to the paths below.
+    // (At 9 .. 32 chunks it replaces the eight-workgroups-per-chunk kernel below: 5.0 against 10.7 us per iteration at n = 40 000.)
+    // PRE: a chunk per workgroup only, so up to n_cu (and 256) chunks -- hipk_cg_mid_table has no PRE rows of two chunks.
+    // plain: a chunk each up to n_cu chunks, two each beyond
+    path.nch = (PRE || g <= A->n_cu) ? 1 : 2;
+    const int nch = path.nch;
+    path.mid_entry = hipk_mid_pick(hipk_cg_mid_table<T>, A->max_row_len, nch, PRE);
+    auto mid_lds = [nch](int slots) { return hipk_cg_mid_lds_bytes(slots * HIPK_TILE, nch, PRE, sizeof(T)); };
+    // (hipk_mid_eligible last: it builds the handle's window plan on the stream and queries occupancy)
+    path.mid = g > kMidMinChunks && g <= (PRE ? kPcgMidMaxChunks : kMidMaxChunks) && (!PRE || g <= A->n_cu) && A->geom.ch == HIPK_BASE_CHUNK &&
+               A->op_cb == nullptr && A->crow != nullptr && A->max_row_len <= 12 && prm->profile == 0 && maxiter > 0 && !mid_failed &&
+               hipk_sw_enabled("HIPK_CG_MID") && !hipk_sw_present("HIPK_CG_NO_LDS_LOOP") && !hipk_sw_present("HIPK_CG_NO_SMALL") &&
+               path.mid_entry && hipk_mid_eligible(A, path.mid_entry, (g + nch - 1) / nch, mid_lds, stream, &path.mid_plan, &path.mid_lds);
+    if (path.mid) {
+        // a 256-byte line per chunk partial: every workgroup polls every slot, and packed slots are ONE memory channel's hot spot (same
+        // box, CG, us per iteration, 256 B / 16 B per slot: 5.1 / 5.8 at 79 chunks, 5.4 / 6.6 at 123, 6.8 / 8.2 at 254; 64 B from 257
+        // chunks: 9.65 / 9.95 at 489; 16 B up to 32 chunks: 5.05 / 5.3 at 20) -- HIPK_CG_MID_STRIDE forces
+        const int stride = g <= 32 ? 1 : g <= 256 ? 16 : 4;
+        // PRE: the two A/B switches of the mid loop are not consulted (historical, kept)
+        path.slot_stride = PRE ? stride : (int)hipk_sw_int("HIPK_CG_MID_STRIDE", stride);
+        if (path.slot_stride < 1 || path.slot_stride > 16) path.slot_stride = 16;
+        path.xcd_aware = PRE || hipk_sw_enabled("HIPK_CG_MID_XCD");
+        path.max_its = hipk_sw_int("HIPK_CG_LAUNCH_ITS", 16384, 1);
+    }
+    return path;
+}
+
+// launch-bound systems with short rows: up to 64 workgroups (8 chunks) on ONE XCD, up to 512 (64 chunks, n <= 131072) spread over
+// the chip, two per compute unit.  (Measured per iteration, one launch vs three launches: 5.5 vs 16 us at 8 chunks, 10.6 vs 19.9
+// at 16, 12.3 vs 16.6 at 32, 18.3 vs 18.3 at 64: the agent-scope hand-offs grow with the workgroup count -- taken up to 32
+// chunks, n <= 65536.)  lds_failed: its workgroups once failed to meet (a shared device): do not wait for that verdict again
+static void hipk_cg_path_lds(hipk_cg_path &path, const hipk_csr_s *A, const hipk_params *prm, int64_t maxiter, bool mid_done, bool lds_failed) {
+    const int g = A->geom.g;
+    path.spread = kGmSub * g > 64;
+    path.lds_loop = g <= 32 && !hipk_sw_present("HIPK_CG_NO_SMALL") && A->geom.ch == HIPK_BASE_CHUNK && A->max_row_len <= kCgRowRegs &&
+                    prm->profile == 0 && maxiter > 0 && kGmSub * g <= (path.spread ? 2 * A->n_cu : 2 * (A->n_cu / 8)) && !lds_failed &&
+                    !hipk_sw_present("HIPK_CG_NO_LDS_LOOP") && !(path.spread && hipk_sw_present("HIPK_NO_LDS_SPREAD")) && !mid_done;
+    if (path.lds_loop) {
+        path.local = !path.spread && !hipk_sw_present("HIPK_CG_LOOP_AGENT");
+        path.max_its = hipk_sw_int("HIPK_CG_LAUNCH_ITS", 16384, 1);
+    }
+}
+
+// launch-bound mid-size systems of plain CG, 33 .. kCg2MaxChunks chunks: TWO launches per iteration, from iteration 0 only (p_0 = r_0
+// sits where its first pass reads it) and with room for a fourth vector in the workspace.  cap2: the kernel's tile capacity
+static void hipk_cg_path_two(hipk_cg_path &path, const hipk_csr_s *A, const hipk_params *prm, bool done, int64_t it, int cap2, size_t vec) {
+    const int g = A->geom.g;
+    path.two_launch = !done && !path.small && g > 32 && g <= kCg2MaxChunks && A->geom.ch == HIPK_BASE_CHUNK && A->op_cb == nullptr &&
+                      A->crow != nullptr && A->max_tile_nnz <= cap2 && A->max_row_len <= HIPK_LONG_ROW && prm->profile == 0 && it == 0 &&
+                      hipk_sw_enabled("HIPK_CG_TWO_LAUNCH") && hipk_cg_work_bytes(A->n_rows, A->dtype) >= 256 + hipk_scratch_bytes() + 4 * vec;
+}
+
 // {redo, it_done, stop_it} of a host copy of hipk_cg_scal / hipk_pcg_scal (hipk_resident_run)
 template <typename S>
 static hipk_loop_state hipk_cg_loop_state(const S &h) {
     return {h.ctl.redo, h.ctl.it_done, h.stop_it};
 }
 
-// launch-bound mid-size systems: the whole CG loop (PRE: Jacobi PCG, M = diag(dinv)) in one launch, mid's kernel on workgroups of
-// mid->nch chunks, from iteration `it` -- HIPK_OK, HIPK_HANDED_BACK or an error (hipk_resident_run).  plan, lds: hipk_mid_eligible's;
+// launch-bound mid-size systems: the whole CG loop (PRE: Jacobi PCG, M = diag(dinv)) in one launch, path.mid_entry's kernel on workgroups
+// of path.nch chunks, from iteration `it` -- HIPK_OK, HIPK_HANDED_BACK or an error (hipk_resident_run);
 // r travels as flagged words in Ap + the vector behind it, the chunk-partial slots follow (hipk_cg_work_bytes, hipk_pcg_work_bytes)
 template <typename T, bool PRE, typename S>
-static int hipk_cg_mid_loop(hipk_csr_s *A, S *scal, const hipk_mid_entry<hipk_cg_mid_args> *mid, const hipk_mid_plan &plan, size_t lds,
-                            T *x, T *r, T *p, T *Ap, const T *dinv, const double *rz0_parts, int64_t &it, int64_t maxiter, bool &failed,
-                            char (&handed)[128], const char *entry, hipStream_t stream) {
+static int hipk_cg_mid_loop(hipk_csr_s *A, S *scal, const hipk_cg_path &path, T *x, T *r, T *p, T *Ap, const T *dinv, const double *rz0_parts,
+                            int64_t &it, int64_t maxiter, bool &failed, char (&handed)[128], const char *entry, hipStream_t stream) {
+    const hipk_mid_entry<hipk_cg_mid_args> *mid = path.mid_entry;
+    const hipk_mid_plan &plan = path.mid_plan;
+    const size_t lds = path.mid_lds;
     const int g = A->geom.g, grid = (g + mid->nch - 1) / mid->nch;
     const size_t ll_bytes = hipk_align_up((size_t)A->n_rows * 16, 256);   // r as 16-byte flagged words
     hipk_cg_mid_args ca;
@@ -983,19 +1075,14 @@ static int hipk_cg_mid_loop(hipk_csr_s *A, S *scal, const hipk_mid_entry<hipk_cg
     if (PRE) ca.rz_ll = ca.rr_ll + (size_t)kMidMaxChunks * 256 / 8;
     ca.dinv = dinv;
     ca.rz0_parts = rz0_parts;
-    // a 256-byte line per chunk partial: every workgroup polls every slot, and packed slots are ONE memory channel's hot spot (same
-    // box, CG, us per iteration, 256 B / 16 B per slot: 5.1 / 5.8 at 79 chunks, 5.4 / 6.6 at 123, 6.8 / 8.2 at 254; 64 B from 257
-    // chunks: 9.65 / 9.95 at 489; 16 B up to 32 chunks: 5.05 / 5.3 at 20) -- HIPK_CG_MID_STRIDE forces (CG)
-    const char *stride = PRE ? nullptr : getenv("HIPK_CG_MID_STRIDE");
-    ca.slot_stride = stride ? atoi(stride) : g <= 32 ? 1 : g <= 256 ? 16 : 4;
-    if (ca.slot_stride < 1 || ca.slot_stride > 16) ca.slot_stride = 16;
-    ca.xcd_aware = PRE || !(getenv("HIPK_CG_MID_XCD") && getenv("HIPK_CG_MID_XCD")[0] == '0');
+    ca.slot_stride = path.slot_stride;
+    ca.xcd_aware = path.xcd_aware;
     ca.ctl = &scal->ctl;
     ca.gamma = scal->gamma;
     ca.atol2 = &scal->atol2;
     ca.stop_it = &scal->stop_it;
     ca.maxiter = maxiter;
-    ca.max_its = hipk_env_its("HIPK_CG_LAUNCH_ITS", 16384);
+    ca.max_its = path.max_its;
     auto launch = [&](int64_t it0, int test_not_resident, bool) -> int {
         ca.it0 = it0;
         ca.test_not_resident = test_not_resident;
@@ -1012,10 +1099,11 @@ static int hipk_cg_mid_loop(hipk_csr_s *A, S *scal, const hipk_mid_entry<hipk_cg
 // from iteration `it` -- HIPK_OK, HIPK_HANDED_BACK or an error (hipk_resident_run).  scal: hipk_cg_scal / hipk_pcg_scal; rr_sub,
 // rz_sub: the kernel's sub-partial scratch; flags: 2 x kHoMaxWg hand-off words; failed: the caller's latch
 template <typename T, bool PRE, typename S>
-static int hipk_cg_lds_loop(hipk_csr_s *A, S *scal, T *x, T *r, T *p, T *Ap, const T *dinv, const double *rz0_parts, double *rz_sub,
-                            double *rr_sub, unsigned long long *flags, bool spread, int64_t &it, int64_t maxiter, bool &failed,
+static int hipk_cg_lds_loop(hipk_csr_s *A, S *scal, const hipk_cg_path &path, T *x, T *r, T *p, T *Ap, const T *dinv, const double *rz0_parts,
+                            double *rz_sub, double *rr_sub, unsigned long long *flags, int64_t &it, int64_t maxiter, bool &failed,
                             char (&handed)[128], const char *entry, hipStream_t stream) {
-    bool local = !spread && !getenv("HIPK_CG_LOOP_AGENT");   // a -2 (spread over several XCDs): agent-scope hand-offs
+    const bool spread = path.spread;
+    bool local = path.local;   // a -2 (spread over several XCDs): agent-scope hand-offs
     const int g = A->geom.g, lgrid = spread ? kGmSub * g : 8 * kGmSub * g;
     hipk_cg_lds_args<T> ca;
     ca.n = A->n_rows;
@@ -1040,7 +1128,7 @@ static int hipk_cg_lds_loop(hipk_csr_s *A, S *scal, T *x, T *r, T *p, T *Ap, con
     ca.flag_b = ca.flag_a + kHoMaxWg;
     ca.spread = spread ? 1 : 0;
     ca.maxiter = maxiter;
-    ca.max_its = hipk_env_its("HIPK_CG_LAUNCH_ITS", 16384);
+    ca.max_its = path.max_its;
     auto launch = [&](int64_t it0, int test_not_resident, bool loc) -> int {
         ca.it0 = it0;
         ca.test_not_resident = test_not_resident;
@@ -1051,6 +1139,46 @@ static int hipk_cg_lds_loop(hipk_csr_s *A, S *scal, T *x, T *r, T *p, T *Ap, con
     };
     return hipk_resident_run(stream, scal, launch, hipk_cg_loop_state<S>, it, maxiter, &local, failed, handed, "hipk_cg_solve_lds_kernel",
                              entry);
+}
+
+// The one-launch section of hipk_cg_solve (PRE = false) and hipk_pcg_solve (PRE = true): the mid loop, else the LDS loop, from
+// iteration `it`; *done when one of them finished the solve, else the caller's launch sequence goes on from `it`.  Records
+// the path hipk_last_solve_path reports.  part_z (PRE): the launch sequence's ping-pong chunk partials of <r,z>; part_z[0] holds
+// those of iteration 0, part_z[1] is the LDS loop's sub-partial scratch.  rr_sub, flags: as hipk_cg_lds_loop's
+template <typename T, bool PRE, typename S>
+static int hipk_cg_one_launch(hipk_csr_s *A, S *scal, hipk_cg_path &path, const hipk_params *prm, T *x, T *r, T *p, T *Ap, const T *dinv,
+                              double *const *part_z, double *rr_sub, unsigned long long *flags, int64_t &it, int64_t maxiter,
+                              bool &mid_failed, bool &lds_failed, char (&handed)[128], const char *entry, hipStream_t stream, bool *done) {
+    // a hand-back at it > 0 (from an EARLIER launch of the loop): x, r, p are in memory, but <r,z> only as scal->gamma[it & 1], while
+    // the Jacobi launch sequence folds it from the chunk partials part_z[it & 1].  Rebuild that slot as {gamma, 0, 0, ...}: the
+    // fold of it is gamma, bit for bit.  (Plain CG's launch sequence reads gamma itself.)
+    auto after = [&](int run) -> int {
+        if (PRE && run == HIPK_HANDED_BACK && it > 0) {
+            HIPK_CHECK_HIP(hipMemsetAsync(part_z[it & 1], 0, (size_t)A->geom.g * sizeof(double), stream));
+            HIPK_CHECK_HIP(hipMemcpyAsync(part_z[it & 1], &scal->gamma[it & 1], sizeof(double), hipMemcpyDeviceToDevice, stream));
+        }
+        return HIPK_OK;
+    };
+    int rc;
+    bool mid_done = false, lds_done = false;
+    if (path.mid) {
+        const int run = hipk_cg_mid_loop<T, PRE>(A, scal, path, x, r, p, Ap, dinv, PRE ? part_z[0] : nullptr, it, maxiter, mid_failed, handed,
+                                                 entry, stream);
+        if (run < 0) return run;
+        if ((rc = after(run)) != HIPK_OK) return rc;
+        mid_done = run == HIPK_OK;
+    }
+    hipk_cg_path_lds(path, A, prm, maxiter, mid_done, lds_failed);
+    if (path.lds_loop) {   // a hand-back (not co-resident; that launch modified nothing): the launch sequence takes over
+        const int run = hipk_cg_lds_loop<T, PRE>(A, scal, path, x, r, p, Ap, dinv, PRE ? part_z[0] : nullptr, PRE ? part_z[1] : nullptr, rr_sub,
+                                                 flags, it, maxiter, lds_failed, handed, entry, stream);
+        if (run < 0) return run;
+        if ((rc = after(run)) != HIPK_OK) return rc;
+        lds_done = run == HIPK_OK;
+    }
+    hipk_set_solve_path(handed, mid_done ? path.mid_entry->name : lds_done ? "hipk_cg_solve_lds_kernel" : "launch sequence");
+    *done = mid_done || lds_done;
+    return HIPK_OK;
 }
 
 template <typename T>
@@ -1118,64 +1246,21 @@ static int hipk_cg_solve_t(hipk_csr_s *A, const T *b, T *x, char *work, const hi
     sa.part0 = part_a;
     sa.part1 = part_c;
     sa.stop_it = &scal->stop_it;
-    // launch-bound systems (<= 8 reduction chunks): no combine launch, the vector kernels fold the SpMV's tile sums
-    const bool small = gm.g <= 8 && !getenv("HIPK_CG_NO_SMALL");
+    // which paths this solve takes (hipk_cg_path above); the latches: a one-launch loop once handed a solve back in this process
+    static bool mid_failed = false, lds_loop_failed = false;
+    hipk_cg_path path = hipk_cg_path_begin<T, false>(A, prm, maxiter, mid_failed, stream);
+    const bool small = path.small, streams = path.streams, flat_dir = path.flat_dir;
     const int ntiles = (int)((n + HIPK_TILE - 1) / HIPK_TILE);
     sa.skip_combine = small ? 1 : 0;
-    // x, r, p, Ap beyond 1.5 x the 256 MiB Infinity Cache: the vector kernels treat every operand as a stream
-    // (HIPK_CG_STREAMS=0/1 forces the choice: A/B measurements)
-    bool streams = 4 * (size_t)n * sizeof(T) > (size_t)384 << 20;
-    if (const char *e = getenv("HIPK_CG_STREAMS")) streams = e[0] == '1';
-    // with it, and a vector alone beyond the 256 MiB Infinity Cache, the direction step as a scalars launch + a flat grid
-    // (same vectors, same process, per CG iteration: N = 64 M 1079 -> 1011 us; N = 32 M 473 -> 471; N = 16 M, where p still finds
-    // room in that cache, 237 -> 246: not taken there).  HIPK_CG_FLAT_DIRECTION=0|1 forces (tools/flat_probe.py, tests)
-    bool flat_dir = (size_t)n * sizeof(T) > ((size_t)256 << 20);
-    if (const char *e = getenv("HIPK_CG_FLAT_DIRECTION")) flat_dir = e[0] == '1';
 
     int64_t it = 0, stop = INT64_MAX;
-    // launch-bound systems of 9 .. 512 chunks (fp64, rows of <= 12 entries within a window around their chunk): the whole loop in
-    // one launch, one workgroup per chunk or pair of chunks (hipk_cg_mid.h); HIPK_CG_MID=0 leaves them to the paths below.
-    // (At 9 .. 32 chunks it replaces the eight-workgroups-per-chunk kernel below: 5.0 against 10.7 us per iteration at n = 40 000.)
-    static bool mid_failed = false;
-    // one workgroup of 1024 threads per CU; a chunk each up to n_cu chunks, two each beyond
-    const int nch = gm.g <= A->n_cu ? 1 : 2;
-    const hipk_mid_entry<hipk_cg_mid_args> *mid = hipk_mid_pick(hipk_cg_mid_table<T>, A->max_row_len, nch, false);
-    auto mid_lds = [&](int slots) { return hipk_cg_mid_lds_bytes(slots * HIPK_TILE, nch, false, sizeof(T)); };
-    hipk_mid_plan plan;
-    size_t lds = 0;
-    bool mid_loop = it == 0 && gm.g > kMidMinChunks && gm.g <= kMidMaxChunks && gm.ch == HIPK_BASE_CHUNK && A->op_cb == nullptr &&
-                    A->crow != nullptr && A->max_row_len <= 12 && prm->profile == 0 && maxiter > 0 && !mid_failed &&
-                    !(getenv("HIPK_CG_MID") && getenv("HIPK_CG_MID")[0] == '0') && !getenv("HIPK_CG_NO_LDS_LOOP") && !getenv("HIPK_CG_NO_SMALL") &&
-                    mid && hipk_mid_eligible(A, mid, (gm.g + nch - 1) / nch, mid_lds, stream, &plan, &lds);
-    if (mid_loop) {
-        const int run = hipk_cg_mid_loop<T, false>(A, scal, mid, plan, lds, x, r, p, Ap, nullptr, nullptr, it, maxiter, mid_failed, handed,
-                                                   "hipk_cg_solve", stream);
-        if (run < 0) return run;
-        mid_loop = run == HIPK_OK;
-    }
-    // launch-bound systems with short rows: the whole loop in one launch (hipk_cg_solve_lds_kernel), bounded iterations per launch
-    static bool lds_loop_failed = false;   // its workgroups once failed to meet (a shared device): do not wait for that verdict again
-    // up to 64 workgroups (8 chunks) on ONE XCD, up to 512 (64 chunks, n <= 131072) spread over the chip, two per compute unit
-    const bool lds_spread = kGmSub * gm.g > 64;
-    // (measured per iteration, one launch vs three launches: 5.5 vs 16 us at 8 chunks, 10.6 vs 19.9 at 16, 12.3 vs 16.6 at 32,
-    // 18.3 vs 18.3 at 64: the agent-scope hand-offs grow with the workgroup count -- taken up to 32 chunks, n <= 65536)
-    bool lds_loop = gm.g <= 32 && !getenv("HIPK_CG_NO_SMALL") && gm.ch == HIPK_BASE_CHUNK && A->max_row_len <= kCgRowRegs &&
-                    prm->profile == 0 && maxiter > 0 && kGmSub * gm.g <= (lds_spread ? 2 * A->n_cu : 2 * (A->n_cu / 8)) &&
-                    !lds_loop_failed && !getenv("HIPK_CG_NO_LDS_LOOP") && !(lds_spread && getenv("HIPK_NO_LDS_SPREAD")) && !mid_loop;
-    if (lds_loop) {   // a hand-back (not co-resident; nothing was modified): the launch sequence below takes over
-        const int run = hipk_cg_lds_loop<T, false>(A, scal, x, r, p, Ap, nullptr, nullptr, nullptr, part_b, (unsigned long long *)(part_c + 1024),
-                                                   lds_spread, it, maxiter, lds_loop_failed, handed, "hipk_cg_solve", stream);
-        if (run < 0) return run;
-        lds_loop = run == HIPK_OK;
-    }
-    hipk_set_solve_path(handed, mid_loop ? mid->name : lds_loop ? "hipk_cg_solve_lds_kernel" : "launch sequence");
-    if (mid_loop) lds_loop = true;   // finished in the one-launch loop: none of the launch sequences below runs
-    // launch-bound mid-size systems: TWO launches per iteration (hipk_cg2_spmv_kernel / hipk_cg2_update_kernel above)
+    bool lds_loop = false;   // finished in a one-launch loop: none of the launch sequences below runs
+    if ((rc = hipk_cg_one_launch<T, false>(A, scal, path, prm, x, r, p, Ap, (const T *)nullptr, nullptr, part_b, (unsigned long long *)(part_c + 1024),
+                                           it, maxiter, mid_failed, lds_loop_failed, handed, "hipk_cg_solve", stream, &lds_loop)) != HIPK_OK)
+        return rc;
     constexpr int kCap2 = sizeof(T) == 8 ? 1280 : 2048;
-    const bool two_launch = !lds_loop && !small && gm.g > 32 && gm.g <= kCg2MaxChunks && gm.ch == HIPK_BASE_CHUNK && A->op_cb == nullptr &&
-                            A->crow != nullptr && A->max_tile_nnz <= kCap2 && A->max_row_len <= HIPK_LONG_ROW && prm->profile == 0 &&
-                            it == 0 && !(getenv("HIPK_CG_TWO_LAUNCH") && getenv("HIPK_CG_TWO_LAUNCH")[0] == '0') &&
-                            hipk_cg_work_bytes(n, A->dtype) >= 256 + hipk_scratch_bytes() + 4 * vec;
+    hipk_cg_path_two(path, A, prm, lds_loop, it, kCap2, vec);
+    const bool two_launch = path.two_launch;
     if (two_launch) {
         T *pbuf[2] = {p, (T *)((char *)Ap + vec)};   // p_0 = r_0 sits in pbuf[0] (start kernel); pass k reads pbuf[k & 1], writes the other
         hipk_cg2_args ca;
@@ -1739,48 +1824,13 @@ static int hipk_pcg_solve_t(hipk_csr_s *A, const T *dinv, const T *b, T *x, char
     sa.stop_it = &scal->stop_it;
 
     int64_t it = 0, stop = INT64_MAX;
-    // launch-bound systems of 9 .. 256 chunks (fp64, rows of <= 12 entries within a window around their chunk): the whole loop in one
-    // launch, one workgroup per chunk (hipk_cg_mid_kernel<W, 1, PRE = true>); HIPK_CG_MID=0 leaves them to the paths below
-    static bool mid_failed = false;
-    const hipk_mid_entry<hipk_cg_mid_args> *mid = hipk_mid_pick(hipk_cg_mid_table<T>, A->max_row_len, 1, true);
-    auto mid_lds = [](int slots) { return hipk_cg_mid_lds_bytes(slots * HIPK_TILE, 1, true, sizeof(T)); };
-    hipk_mid_plan plan;
-    size_t lds = 0;
-    bool mid_loop = gm.g > kMidMinChunks && gm.g <= kPcgMidMaxChunks && gm.g <= A->n_cu && gm.ch == HIPK_BASE_CHUNK && A->op_cb == nullptr &&
-                    A->crow != nullptr && A->max_row_len <= 12 && prm->profile == 0 && maxiter > 0 && !mid_failed &&
-                    !(getenv("HIPK_CG_MID") && getenv("HIPK_CG_MID")[0] == '0') && !getenv("HIPK_CG_NO_LDS_LOOP") && !getenv("HIPK_CG_NO_SMALL") &&
-                    mid && hipk_mid_eligible(A, mid, gm.g, mid_lds, stream, &plan, &lds);
-    if (mid_loop) {
-        const int run = hipk_cg_mid_loop<T, true>(A, scal, mid, plan, lds, x, r, p, Ap, dinv, part_z[0], it, maxiter, mid_failed, handed,
-                                                  "hipk_pcg_solve", stream);
-        if (run < 0) return run;
-        if (run == HIPK_HANDED_BACK && it > 0) {   // as below: <r,z> lives in scal->gamma[it & 1]; the launch sequence folds it from part_z[it & 1]
-            HIPK_CHECK_HIP(hipMemsetAsync(part_z[it & 1], 0, (size_t)gm.g * sizeof(double), stream));
-            HIPK_CHECK_HIP(hipMemcpyAsync(part_z[it & 1], &scal->gamma[it & 1], sizeof(double), hipMemcpyDeviceToDevice, stream));
-        }
-        mid_loop = run == HIPK_OK;
-    }
-    // launch-bound systems with short rows: the whole loop in one launch (hipk_cg_solve_lds_kernel<.., PRE = true>)
-    static bool lds_loop_failed = false;
-    const bool lds_spread = kGmSub * gm.g > 64;
-    bool lds_loop = gm.g <= 32 && gm.ch == HIPK_BASE_CHUNK && A->max_row_len <= kCgRowRegs && prm->profile == 0 && maxiter > 0 &&
-                    kGmSub * gm.g <= (lds_spread ? 2 * A->n_cu : 2 * (A->n_cu / 8)) && !lds_loop_failed &&
-                    !getenv("HIPK_CG_NO_SMALL") && !getenv("HIPK_CG_NO_LDS_LOOP") && !(lds_spread && getenv("HIPK_NO_LDS_SPREAD")) && !mid_loop;
-    if (lds_loop) {   // a hand-back (this launch modified nothing): the launch sequence below takes over
-        const int run = hipk_cg_lds_loop<T, true>(A, scal, x, r, p, Ap, dinv, part_z[0], part_z[1], part_b, (unsigned long long *)(part_c + 1024),
-                                                  lds_spread, it, maxiter, lds_loop_failed, handed, "hipk_pcg_solve", stream);
-        if (run < 0) return run;
-        if (run == HIPK_HANDED_BACK && it > 0) {
-            // ... from iteration `it` of an EARLIER launch: x, r, p are in memory, but <r,z> only as scal->gamma[it & 1]
-            // (part_z[1] was the kernel's sub-partial scratch), while the launch sequence folds it from the chunk
-            // partials part_z[it & 1].  Rebuild that slot as {gamma, 0, 0, ...}: the fold of it is gamma, bit for bit
-            HIPK_CHECK_HIP(hipMemsetAsync(part_z[it & 1], 0, (size_t)gm.g * sizeof(double), stream));
-            HIPK_CHECK_HIP(hipMemcpyAsync(part_z[it & 1], &scal->gamma[it & 1], sizeof(double), hipMemcpyDeviceToDevice, stream));
-        }
-        lds_loop = run == HIPK_OK;
-    }
-    hipk_set_solve_path(handed, mid_loop ? mid->name : lds_loop ? "hipk_cg_solve_lds_kernel" : "launch sequence");
-    if (mid_loop) lds_loop = true;   // finished in the one-launch loop
+    // which paths this solve takes (hipk_cg_path above); the latches: a one-launch loop once handed a solve back in this process
+    static bool mid_failed = false, lds_loop_failed = false;
+    hipk_cg_path path = hipk_cg_path_begin<T, true>(A, prm, maxiter, mid_failed, stream);
+    bool lds_loop = false;   // finished in a one-launch loop
+    if ((rc = hipk_cg_one_launch<T, true>(A, scal, path, prm, x, r, p, Ap, dinv, part_z, part_b, (unsigned long long *)(part_c + 1024), it, maxiter,
+                                          mid_failed, lds_loop_failed, handed, "hipk_pcg_solve", stream, &lds_loop)) != HIPK_OK)
+        return rc;
     for (; !lds_loop && it < maxiter; ++it) {
         HIPK_CHECK_HIP(pace.gate(it, stream, &stop));
         if (stop <= it) break;

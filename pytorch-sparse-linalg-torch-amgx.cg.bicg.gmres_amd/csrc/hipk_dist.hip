@@ -125,8 +125,7 @@ extern "C" int hipk_dist_cg_solve(hipk_csr_t A, const hipk_dist_plan *pl, const 
     // the direction kernel then streams 24 n instead of 40 n bytes behind the collective.  Same operands, same bits.  Not the
     // default: the two cross-stream event dependencies per iteration cost more than the 9 us they can hide (world-1 rehearsal
     // at 4 M rows: 98 us per iteration against 66 fused).
-    const char *ov_env = getenv("HIPK_DIST_OVERLAP");
-    const bool overlap = ov_env ? atoi(ov_env) != 0 : false;
+    const bool overlap = hipk_sw_int("HIPK_DIST_OVERLAP", 0) != 0;
     hipStream_t side = nullptr;
     hipEvent_t ev_upd = nullptr, ev_x = nullptr;
     if (overlap) {
@@ -151,8 +150,7 @@ extern "C" int hipk_dist_cg_solve(hipk_csr_t A, const hipk_dist_plan *pl, const 
     // HIPK_DIST_FUSED=0 keeps the collective entry points.
     hipk_fx fx;
     unsigned long long fx_seq0 = 0;
-    const char *fx_env = getenv("HIPK_DIST_FUSED");
-    bool fused = cc->fused != nullptr && !(fx_env && fx_env[0] == '0') && !overlap && (W == 1 || (pl->send_off_dev && pl->dest_off_dev)) &&
+    bool fused = cc->fused != nullptr && hipk_sw_enabled("HIPK_DIST_FUSED") && !overlap && (W == 1 || (pl->send_off_dev && pl->dest_off_dev)) &&
                  hipk_p2p_fx_begin((hipk_p2p_s *)cc->fused, per, pl->n_ghost, &fx, &fx_seq0) != 0;
     if (fused) {
         fx.send_idx = pl->send_idx_dev;

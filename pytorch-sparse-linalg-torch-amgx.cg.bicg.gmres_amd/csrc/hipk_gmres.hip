@@ -2233,6 +2233,85 @@ static const hipk_mid_entry<hipk_gm_mid_args> hipk_gm_mid_table[] = {
     HIPK_MID_ROW(5, true),  HIPK_MID_ROW(7, true),  HIPK_MID_ROW(9, true),  HIPK_MID_ROW(12, true)};
 #undef HIPK_MID_ROW
 
+// ---- which kernels the restart cycles of a gmres solve run in (m: restart; pre: Jacobi; ext: the caller's M through a callback):
+// the only place that knows GMRES's switches and size limits.  One step: every choice is made before the first cycle; a launch
+// that hands its cycle back only takes forms away (the driver's copies of cyc, cyc_lds, cyc_local, mid_cycle).
+struct hipk_gm_path {
+    bool small = false;       // <= 8 chunks, restart <= 31: fewer launches per Arnoldi step
+    bool wide = false;        // ... with hipk_gm_multidot_wide_kernel / hipk_gm_update_wide_kernel
+    bool cyc = false;         // a restart cycle (cyc_lds: the whole solve) in ONE launch
+    bool lds_spread = false;  // 9 .. 32 chunks: hipk_gm_solve_lds_kernel with its workgroups spread over the chip
+    bool cyc_lds = false;     // cyc in hipk_gm_solve_lds_kernel (basis in LDS, eight workgroups per chunk), else hipk_gm_cycle_small_kernel
+    bool cyc_local = false;   // its hand-offs through the shared L2 of ONE XCD (plain stores; placement verified by the kernel)
+    bool stream_k = false;    // large systems: hipk_gm_*_stream_kernel
+    bool mid_cycle = false;   // hipk_gm_mid_kernel: the Arnoldi steps of a cycle in ONE launch, one workgroup per chunk (hipk_gm_mid.h)
+    const hipk_mid_entry<hipk_gm_mid_args> *mid_entry = nullptr;
+    hipk_mid_plan mid_plan;
+    size_t mid_lds = 0;
+    bool md_wide = false;     // multi-dot with up to 32 columns per workgroup
+    bool split_norm = false;  // normalise step as hipk_gm_hcol_kernel + hipk_gm_scale_kernel
+    int nres = 5;             // basis columns read with the default cache policy (the rest: nt)
+    bool spec = false;        // second CGS pass launched only where predicted
+    bool predict_step0 = true;   // ... and predicted at step 0 from the start (false: learn everything)
+};
+
+template <typename T>
+static hipk_gm_path hipk_gm_path_choose(hipk_csr_s *A, const hipk_params *prm, int m, bool pre, bool ext, bool lds_cycle_failed, bool mid_failed,
+                                        hipStream_t stream) {
+    const hipk_geom gm = A->geom;
+    hipk_gm_path path;
+    // launch-bound systems: fewer launches per step (their kernels keep H in the struct's 32-wide arrays: restart <= 31)
+    const bool small = path.small = gm.g <= 8 && m <= HIPK_GM_MAXM && !hipk_sw_present("HIPK_GMRES_NO_SMALL");
+    path.wide = small && gm.ch == HIPK_BASE_CHUNK && !hipk_sw_present("HIPK_GMRES_NO_WIDE");
+    // small systems with short rows: the whole restart cycle in ONE launch (hipk_gm_cycle_small_kernel)
+    path.cyc = path.wide && !ext && A->max_row_len <= HIPK_LONG_ROW && !hipk_sw_present("HIPK_GMRES_NO_CYCLE");
+    // 9 .. 32 chunks (n <= 65536): the LDS kernel below with its workgroups spread over the chip (agent-scope hand-offs)
+    path.lds_spread = gm.g > 8 && gm.g <= 32 && m <= HIPK_GM_MAXM && gm.ch == HIPK_BASE_CHUNK && !ext && A->max_row_len <= HIPK_LONG_ROW &&
+                      !hipk_sw_present("HIPK_GMRES_NO_SMALL") && !hipk_sw_present("HIPK_GMRES_NO_CYCLE") && !hipk_sw_present("HIPK_NO_LDS_SPREAD");
+    // ... with the basis in LDS and eight workgroups per chunk (hipk_gm_solve_lds_kernel) when m columns of 256 rows fit -- two
+    // workgroups share a compute unit's 160 KB of LDS -- and 8 g workgroups fit ONE XCD (an eighth of the compute units, two
+    // workgroups each), or the chip when spread; a process whose resident workgroups once failed to meet (a shared device) does
+    // not try again: the wait for that verdict takes seconds
+    path.cyc_lds = (path.cyc || path.lds_spread) && hipk_gm_solve_lds_bytes<T>(m) <= 80 * 1024 &&
+                   kGmSub * gm.g <= (path.lds_spread ? 2 * A->n_cu : 2 * (A->n_cu / 8)) && !lds_cycle_failed && !hipk_sw_present("HIPK_GMRES_NO_LDS_CYCLE");
+    if (path.lds_spread) path.cyc = path.cyc_lds;   // beyond 8 chunks there is no one-workgroup-per-chunk kernel to fall back to
+    if (path.cyc_lds) {
+        static bool attr_done[2] = {false, false};   // the launches ask for more than the default 64 KB of dynamic LDS
+        if (!attr_done[sizeof(T) == 8]) {
+            (void)hipFuncSetAttribute((const void *)hipk_gm_solve_lds_kernel<T, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
+            (void)hipFuncSetAttribute((const void *)hipk_gm_solve_lds_kernel<T, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
+            attr_done[sizeof(T) == 8] = true;
+        }
+    }
+    path.cyc_local = !path.lds_spread && !hipk_sw_present("HIPK_GM_CYCLE_AGENT");   // else agent-scope stores
+    path.stream_k = !small && (m > HIPK_GM_MAXM || !hipk_sw_present("HIPK_GMRES_NO_STREAM"));
+    // 33 .. 256 chunks (fp64, M = identity or Jacobi, restart <= 31, rows of <= 12 entries within a window around their chunk):
+    // one workgroup per chunk, one per CU; HIPK_GMRES_MID=0 keeps the launches.  HIPK_GMRES_MID_MIN: A/B against the whole-solve
+    // kernel of 9 .. 32 chunks.  (hipk_mid_eligible last: it builds the handle's window plan on the stream and queries occupancy)
+    path.mid_entry = hipk_mid_pick(hipk_gm_mid_table<T>, A->max_row_len, 1, pre);
+    const int mid_min = (int)hipk_sw_int("HIPK_GMRES_MID_MIN", kGmMidMinChunks);
+    auto lds_of = [](int slots) { return hipk_gm_mid_lds_bytes(slots * HIPK_TILE, sizeof(T)); };
+    path.mid_cycle = !small && !ext && m <= HIPK_GM_MAXM && gm.g > (mid_min < 8 ? 8 : mid_min) && gm.g <= kGmMidMaxChunks &&
+                     gm.g <= A->n_cu && gm.ch == HIPK_BASE_CHUNK && A->op_cb == nullptr && A->crow != nullptr && A->max_row_len <= 12 &&
+                     prm->profile == 0 && !mid_failed && hipk_sw_enabled("HIPK_GMRES_MID") && !hipk_sw_present("HIPK_GMRES_NO_CYCLE") &&
+                     path.mid_entry && hipk_mid_eligible(A, path.mid_entry, gm.g, lds_of, stream, &path.mid_plan, &path.mid_lds);
+    if (path.mid_cycle) path.cyc = path.cyc_lds = false;   // (9 .. 32 chunks: instead of the whole-solve kernel)
+    // multi-dot with up to 32 columns per workgroup (w read ONCE per step; 0, the default: groups of 8, w re-read per group).  Same
+    // box, alternating, N = 4 M (profiles/r03_gmres_history.md): GMRES(30) 6.67-6.70 vs 6.64-6.66 ms per cycle, GMRES(50) 16.50 vs
+    // 16.38, GMRES(100) 60.1-60.2 vs 59.5-59.8 -- the re-reads of w are Infinity-Cache hits (FETCH_SIZE counts them: the 1.15 x of
+    // VERDICT r2), and 113 VGPRs (4 workgroups per CU) cost more than they did.  Kept for the counters, not taken.
+    path.md_wide = hipk_sw_int("HIPK_GM_MD_WIDE", 0) != 0;
+    // normalise step in two launches (HIPK_GM_SPLIT_NORM=0: the one-kernel form) from kGmSplitChunks reduction chunks up: below, a
+    // workgroup's fold of 2 g partials is cheap and the extra launch is not
+    path.split_norm = !small && hipk_sw_int("HIPK_GM_SPLIT_NORM", gm.g >= kGmSplitChunks ? 1 : 0) != 0;
+    path.nres = (int)hipk_sw_int("HIPK_GM_NRES", 5);
+    // large systems: second-pass launches only where a second CGS pass is expected; 0: at every step; 2: learn everything (tests)
+    const int spec = (int)hipk_sw_int("HIPK_GM_SPEC", 1);
+    path.spec = !small && spec != 0;
+    path.predict_step0 = spec != 2;
+    return path;
+}
+
 // dinv != nullptr: left Jacobi preconditioning -- every A(.) is followed by M(.) = dinv .* (.) (TSL:351, 791, 766), applied
 // by the SpMV epilogue (HIPK_SPMV_SCALE) before its fused dots; ptol from ||M b|| (TSL:750).  Mirrored by orc_gmres_jacobi.
 // cb != nullptr (dinv == nullptr): M is the CALLER's device code, cb(user, in, out) enqueues out = M(in) on `stream`.  It runs
@@ -2345,65 +2424,25 @@ static int hipk_gmres_solve_t(hipk_csr_s *A, const T *dinv, const T *b, T *x, ch
     }
     std::vector<double> big_host(big_n);
     int64_t cycles = 0;
-    // launch-bound systems: fewer launches per step (their kernels keep H in the struct's 32-wide arrays: restart <= 31)
-    const bool small = gm.g <= 8 && m <= HIPK_GM_MAXM && !getenv("HIPK_GMRES_NO_SMALL");
-    const bool wide = small && gm.ch == HIPK_BASE_CHUNK && !getenv("HIPK_GMRES_NO_WIDE");  // hipk_gm_update_wide_kernel
-    // small systems with short rows: the whole restart cycle in ONE launch (hipk_gm_cycle_small_kernel)
-    bool cyc = wide && !ext && A->max_row_len <= HIPK_LONG_ROW && !getenv("HIPK_GMRES_NO_CYCLE");
-    // ... with the basis in LDS and eight workgroups per chunk (hipk_gm_solve_lds_kernel) when m columns of 256 rows fit
-    // two workgroups share a compute unit's 160 KB of LDS
-    // ... and 8 g workgroups fit ONE XCD (an eighth of the compute units, two workgroups each); a process whose resident
-    // workgroups once failed to meet (a shared device) does not try again: the wait for that verdict takes seconds
-    static bool lds_cycle_failed = false;
-    // 9 .. 32 chunks (n <= 65536): the same kernel with its workgroups spread over the chip (agent-scope hand-offs)
-    const bool lds_spread = gm.g > 8 && gm.g <= 32 && m <= HIPK_GM_MAXM && gm.ch == HIPK_BASE_CHUNK && !ext && A->max_row_len <= HIPK_LONG_ROW &&
-                            !getenv("HIPK_GMRES_NO_SMALL") && !getenv("HIPK_GMRES_NO_CYCLE") && !getenv("HIPK_NO_LDS_SPREAD");
-    bool cyc_lds = (cyc || lds_spread) && hipk_gm_solve_lds_bytes<T>(m) <= 80 * 1024 &&
-                   kGmSub * gm.g <= (lds_spread ? 2 * A->n_cu : 2 * (A->n_cu / 8)) && !lds_cycle_failed && !getenv("HIPK_GMRES_NO_LDS_CYCLE");
-    if (lds_spread) cyc = cyc_lds;   // beyond 8 chunks there is no one-workgroup-per-chunk kernel to fall back to
-    if (cyc_lds) {
-        static bool attr_done[2] = {false, false};   // the launches ask for more than the default 64 KB of dynamic LDS
-        if (!attr_done[sizeof(T) == 8]) {
-            (void)hipFuncSetAttribute((const void *)hipk_gm_solve_lds_kernel<T, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-            (void)hipFuncSetAttribute((const void *)hipk_gm_solve_lds_kernel<T, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-            attr_done[sizeof(T) == 8] = true;
-        }
-    }
-    // its hand-offs through the shared L2 of ONE XCD (plain stores; placement verified by the kernel), else agent-scope stores
-    bool cyc_local = !lds_spread && !getenv("HIPK_GM_CYCLE_AGENT");
-    auto env_int = [](const char *name, int dflt) { const char *e = getenv(name); return e ? atoi(e) : dflt; };
-    const bool stream_k = !small && (m > HIPK_GM_MAXM || !getenv("HIPK_GMRES_NO_STREAM"));  // large systems: hipk_gm_*_stream_kernel
-    // 33 .. 256 chunks (fp64, no preconditioner, restart <= 31, rows of <= 12 entries within a window around their chunk): the
-    // Arnoldi steps of a cycle in ONE launch, one workgroup per chunk (hipk_gm_mid.h); HIPK_GMRES_MID=0 keeps the launches
-    static bool mid_failed = false;
-    const hipk_mid_entry<hipk_gm_mid_args> *mid = hipk_mid_pick(hipk_gm_mid_table<T>, A->max_row_len, 1, dinv != nullptr);
-    hipk_mid_plan mid_plan;
-    size_t mid_lds = 0;
-    const int mid_min = env_int("HIPK_GMRES_MID_MIN", kGmMidMinChunks);   // (A/B against the whole-solve kernel of 9 .. 32 chunks)
-    auto lds_of = [](int slots) { return hipk_gm_mid_lds_bytes(slots * HIPK_TILE, sizeof(T)); };
-    bool mid_cycle = !small && !ext && m <= HIPK_GM_MAXM && gm.g > (mid_min < 8 ? 8 : mid_min) && gm.g <= kGmMidMaxChunks &&
-                     gm.g <= A->n_cu && gm.ch == HIPK_BASE_CHUNK && A->op_cb == nullptr && A->crow != nullptr && A->max_row_len <= 12 &&
-                     prm->profile == 0 && !mid_failed && !(getenv("HIPK_GMRES_MID") && getenv("HIPK_GMRES_MID")[0] == '0') &&
-                     !getenv("HIPK_GMRES_NO_CYCLE") && mid && hipk_mid_eligible(A, mid, gm.g, lds_of, stream, &mid_plan, &mid_lds);
-    if (mid_cycle) cyc = cyc_lds = false;   // (9 .. 32 chunks: instead of the whole-solve kernel)
+    // which kernels the cycles run in (hipk_gm_path above); the latches: a one-launch cycle once handed a solve back in this process
+    static bool lds_cycle_failed = false, mid_failed = false;
+    const hipk_gm_path path = hipk_gm_path_choose<T>(A, prm, m, dinv != nullptr, ext, lds_cycle_failed, mid_failed, stream);
+    const bool small = path.small, wide = path.wide, lds_spread = path.lds_spread, stream_k = path.stream_k, md_wide = path.md_wide;
+    const bool split_norm = path.split_norm, spec = path.spec;
+    const int gm_nres = path.nres;
+    // a verdict of a launch below takes a one-launch form away for the rest of the solve
+    bool cyc = path.cyc, cyc_lds = path.cyc_lds, cyc_local = path.cyc_local, mid_cycle = path.mid_cycle;
+    const hipk_mid_entry<hipk_gm_mid_args> *mid = path.mid_entry;
+    const hipk_mid_plan &mid_plan = path.mid_plan;
+    const size_t mid_lds = path.mid_lds;
     // the kernel a cycle enqueued below runs in (hipk_last_solve_path)
     auto cycle_kernel = [&]() -> const char * {
         return mid_cycle ? mid->name : !cyc ? "launch sequence" : cyc_lds ? "hipk_gm_solve_lds_kernel" : "hipk_gm_cycle_small_kernel";
     };
-    // multi-dot with up to 32 columns per workgroup (w read ONCE per step; 0, the default: groups of 8, w re-read per group).  Same
-    // box, alternating, N = 4 M (profiles/r03_gmres_history.md): GMRES(30) 6.67-6.70 vs 6.64-6.66 ms per cycle, GMRES(50) 16.50 vs
-    // 16.38, GMRES(100) 60.1-60.2 vs 59.5-59.8 -- the re-reads of w are Infinity-Cache hits (FETCH_SIZE counts them: the 1.15 x of
-    // VERDICT r2), and 113 VGPRs (4 workgroups per CU) cost more than they did.  Kept for the counters, not taken.
-    const bool md_wide = env_int("HIPK_GM_MD_WIDE", 0) != 0;
-    // normalise step as hipk_gm_hcol_kernel + hipk_gm_scale_kernel (HIPK_GM_SPLIT_NORM=0: the one-kernel form)
-    // from kGmSplitChunks reduction chunks up: below, a workgroup's fold of 2 g partials is cheap and the extra launch is not
-    const bool split_norm = !small && env_int("HIPK_GM_SPLIT_NORM", gm.g >= kGmSplitChunks ? 1 : 0) != 0;
-    const int gm_nres = env_int("HIPK_GM_NRES", 5);  // basis columns read with the default cache policy (the rest: nt)
-    // large systems: second-pass launches only at the steps where a second CGS pass is expected (step 0, then every step
-    // that ever asked for one in this solve); a miss is caught on the device and the cycle re-enqueued from that step
-    const bool spec = !small && env_int("HIPK_GM_SPEC", 1) != 0;
+    // spec: second-pass launches only at the steps where a second CGS pass is expected (step 0, then every step that ever asked
+    // for one in this solve); a miss is caught on the device and the cycle re-enqueued from that step
     bool predict[HIPK_GM_MAXM_BIG + 1];
-    for (int j = 0; j <= HIPK_GM_MAXM_BIG; ++j) predict[j] = (j == 0) && env_int("HIPK_GM_SPEC", 1) != 2;  // 2: learn everything (tests)
+    for (int j = 0; j <= HIPK_GM_MAXM_BIG; ++j) predict[j] = (j == 0) && path.predict_step0;
     int happy = 0;
     int lds_launch_no = 0;
     int64_t prof_valid = 0;
@@ -2436,11 +2475,11 @@ static int hipk_gmres_solve_t(hipk_csr_s *A, const T *dinv, const T *b, T *x, ch
             ca.x = x;
             ca.atol_eff = atol_eff;
             ca.cycles_left = maxiter - cycles;
-            ca.max_cycles = env_int("HIPK_GM_LAUNCH_CYCLES", 64);
+            ca.max_cycles = (int)hipk_sw_int("HIPK_GM_LAUNCH_CYCLES", 64);   // (read per launch)
             ca.test_not_resident = (++lds_launch_no == hipk_test_fail_launch()) ? 1 : 0;   // (one count for all one-launch kernels)
             ca.bar = &scal->bar;
             ca.eps = eps_t;
-            ca.stamps = getenv("HIPK_GM_STAMPS") ? (unsigned long long *)(part_spare + 1600) : nullptr;
+            ca.stamps = hipk_sw_present("HIPK_GM_STAMPS") ? (unsigned long long *)(part_spare + 1600) : nullptr;
             if (ca.stamps && cycles == 0) (void)hipMemsetAsync(ca.stamps, 0, 128, stream);
             ca.spread = lds_spread ? 1 : 0;
             ca.flag_a = (unsigned long long *)(part_spare + 512);   // 2 x 512 words
@@ -2573,7 +2612,7 @@ static int hipk_gmres_solve_t(hipk_csr_s *A, const T *dinv, const T *b, T *x, ch
             // the resident workgroups of a one-launch cycle did not all arrive (the device is shared and they were not
             // co-resident): nothing of the cycle is kept -- column 0 is untouched -- and this solve goes on with one launch
             // per kernel
-            if (getenv("HIPK_GM_STAMPS")) fprintf(stderr, "hipk_gmres_solve: one-launch cycle abandoned (workgroups not co-resident)\n");
+            if (hipk_sw_present("HIPK_GM_STAMPS")) fprintf(stderr, "hipk_gmres_solve: one-launch cycle abandoned (workgroups not co-resident)\n");
             if (verdict == HIPK_REDO_AGENT) {
                 cyc_local = false;      // its workgroups were spread over several XCDs: hand-offs at agent scope from now on
             } else {
@@ -2646,7 +2685,7 @@ static int hipk_gmres_solve_t(hipk_csr_s *A, const T *dinv, const T *b, T *x, ch
     free(hs);
     if (rc != HIPK_OK) return rc;
     hipk_set_solve_path(handed, last_cycle);
-    if ((cyc || cyc_lds) && getenv("HIPK_GM_STAMPS")) {  // diagnostic build-in: where workgroup 0 of the cycle kernel spent its shader clocks
+    if ((cyc || cyc_lds) && hipk_sw_present("HIPK_GM_STAMPS")) {  // diagnostic build-in: where workgroup 0 of the cycle kernel spent its shader clocks
         unsigned long long st8[16];
         HIPK_CHECK_HIP(hipMemcpyAsync(st8, part_spare + 1600, sizeof(st8), hipMemcpyDeviceToHost, stream));
         HIPK_CHECK_HIP(hipStreamSynchronize(stream));

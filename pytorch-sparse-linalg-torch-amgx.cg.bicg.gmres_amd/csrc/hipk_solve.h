@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "hipk_common.h"
+#include "hipk_switch.h"
 
 struct hipk_event_pair {
     hipEvent_t a = nullptr, b = nullptr;
@@ -208,17 +209,11 @@ struct hipk_pacer {
     // pinned: the handle's 16-word block; words 0-1 belong to the poller, word 2 is the signal
     hipk_pacer(int64_t *pinned, const int64_t *dev_stop_word, int64_t check_every, int64_t win = 8)
         : poll(pinned), sig(pinned + 2), dev_stop(dev_stop_word), check(check_every), window(win) {
-        const char *e = getenv("HIPK_HOST_SIGNAL");
-        live = !(e && e[0] == '0');
+        live = hipk_sw_enabled("HIPK_HOST_SIGNAL");
         if (!live) sig = nullptr;
-        if (const char *w = getenv("HIPK_PACE_TIMEOUT_US")) {
-            const long v = atol(w);
-            if (v >= 0) timeout_us = v;
-        }
-        if (const char *w = getenv("HIPK_PACE_WINDOW")) {
-            const long v = atol(w);
-            if (v >= 1 && v <= 4096) window = v;
-        }
+        const int64_t t = hipk_sw_int("HIPK_PACE_TIMEOUT_US", timeout_us), w = hipk_sw_int("HIPK_PACE_WINDOW", window);
+        if (t >= 0) timeout_us = t;              // out of range: ignored, not clamped
+        if (w >= 1 && w <= 4096) window = w;
     }
     hipError_t create() {
         if (sig) __atomic_store_n(sig, (int64_t)0, __ATOMIC_RELEASE);  // before the start kernel is enqueued
@@ -292,14 +287,7 @@ static inline void hipk_finish_isolve_stats(hipk_stats *st, const hipk_params *p
 // ---- the one-launch loops (hipk_*_solve_lds_kernel, hipk_*_mid_kernel): launches, read-back, hand-back ---------------------
 // tests: HIPK_TEST_LDS_NOT_RESIDENT=k makes the k-th launch of a one-launch loop report its workgroups as not co-resident (0: unset)
 static inline int hipk_test_fail_launch() {
-    const char *e = getenv("HIPK_TEST_LDS_NOT_RESIDENT");
-    return e ? (atoi(e) > 1 ? atoi(e) : 1) : 0;
-}
-// iterations per launch of a one-launch loop: the switch `name` (HIPK_*_LAUNCH_ITS) or dflt, at least 1
-static inline int64_t hipk_env_its(const char *name, int64_t dflt) {
-    const char *e = getenv(name);
-    const int64_t v = e ? atoll(e) : dflt;
-    return v < 1 ? 1 : v;
+    return hipk_sw_present("HIPK_TEST_LDS_NOT_RESIDENT") ? (int)hipk_sw_int("HIPK_TEST_LDS_NOT_RESIDENT", 1, 1, INT32_MAX) : 0;
 }
 // what a launch's redo word says: >= 0 the launch ran; -3 a resident workgroup stopped arriving (an error); -2 with `local`: its
 // workgroups were spread over several XCDs (launch again with agent-scope hand-offs); else not co-resident, nothing was modified
@@ -312,7 +300,7 @@ static inline hipk_redo_verdict hipk_redo_classify(int32_t redo, bool local) {
 // a loop handed the solve back: its caller's process-wide latch `failed` is set (do not wait for that verdict again) unless a
 // test provoked it, and `name` joins the chain hipk_last_solve_path reports
 static inline void hipk_hand_back(bool &failed, char (&handed)[128], const char *name) {
-    if (!getenv("HIPK_TEST_LDS_NOT_RESIDENT")) failed = true;
+    if (!hipk_sw_present("HIPK_TEST_LDS_NOT_RESIDENT")) failed = true;
     hipk_path_add(handed, name);
 }
 

@@ -13,7 +13,6 @@ n = nx * nx
 b = torch.ones(n, dtype=torch.float64, device="cuda:0")
 t0 = time.perf_counter(); h = _hipk.handle_for(A); torch.cuda.synchronize(); create = time.perf_counter() - t0
 res = {}
-print("HIPK_SPMV_SELL_DEPTH =", os.environ.get("HIPK_SPMV_SELL_DEPTH", "auto"))
 for plain in (False, True):
     h.set_path(plain_only=plain)
     x = torch.zeros_like(b)
