@@ -279,6 +279,22 @@ int hipk_pgmres_solve_cb(hipk_csr_t A, hipk_precond_fn M, void *user, const void
 int hipk_block_jacobi_apply(int64_t n, int block_size, const void *binv_dev, const void *in, void *out, int dtype,
                             hipk_stream_t stream);
 
+/* ---- Chebyshev polynomial preconditioner ---------------------------------------------------
+ * z = p_m(D^-1 A) D^-1 r, m = degree SpMVs (1 .. 32), enqueued on `stream`; never synchronises.  `dinv` is the reciprocal
+ * diagonal (device, the handle's dtype), `coef_host` holds 2 m + 2 doubles on the HOST: c0, c1[1..m], c2[1..m], scale (fp32
+ * handles round them to float once).  Every step is a separate rounding, no fma:
+ *     step 0      d = c0 * (dinv * r),  z = d
+ *     step k      res = dinv * (r - A z)  (the SpMV's residual form and row scaling, its one summation order)
+ *                 d = (c1[k] * d) + (c2[k] * res),  z = z + d;  the last step stores scale * (z + d)
+ * A step is ONE launch where the handle's SpMV family has the Chebyshev epilogue (res never reaches memory, z ping-pongs
+ * between `z` and `work`), else the SpMV into `work` followed by a vector kernel; HIPK_CHEB_FUSED=0 forces the latter.  Same
+ * bits either way.  `work`: 2 * ((n + 3) & ~3) elements (two vectors, each 16-byte aligned); r, z, work, dinv 16-byte aligned and
+ * distinct.  CSR handles only (a handle from
+ * hipk_op_create is refused).  May be called from inside a preconditioner callback of a solve on the same handle: it uses
+ * none of the handle's reduction scratch and does not touch hipk_last_solve_path. */
+int hipk_cheb_apply(hipk_csr_t A, int degree, const void *dinv, const double *coef_host, const void *r, void *z, void *work,
+                    hipk_stream_t stream);
+
 /* ---- step API: externally driven loops (row-partitioned multi-GPU CG) ------------
  * The reference is single-device; the row-partitioned solver (north_star) drives the
  * SAME fused kernels from the host side of each rank and exchanges (a) the x-vector

@@ -598,6 +598,8 @@ int hipk_launch_spmv(const hipk_csr_s *h, const hipk_spmv_args &a_, hipStream_t 
     const int grid = ((ntiles + 7) >> 3) << 3;
     a.tpart0 = h->tile_part;
     a.tpart1 = h->tile_part + 4 * (size_t)ntiles;
+    const bool want_cheb = (a.mode & HIPK_SPMV_CHEB) != 0;   // only as HIPK_SPMV_CHEB_MODE, from hipk_cheb_apply
+    if (want_cheb && (a.mode != HIPK_SPMV_CHEB_MODE || h->op_cb != nullptr)) return HIPK_SPMV_NO_CHEB;
     if (h->op_cb != nullptr) {   // matrix-free operator (hipk_op_create): the caller's product, then the epilogue + combine
         HIPK_NOTE_KERNEL("%s", "operator callback + hipk_op_epilogue_kernel");
         if (h->op_cb(h->op_user, a.x, a.y) != 0) {
@@ -619,6 +621,7 @@ int hipk_launch_spmv(const hipk_csr_s *h, const hipk_spmv_args &a_, hipStream_t 
     }
     // long-row matrices (mean row length >= 48, or rows that do not fit the LDS product buffer): row per wavefront
     const bool rowwave = h->n_rows > 0 && h->nnz / h->n_rows >= 48;
+    if (want_cheb && (rowwave || h->n_huge > 0)) return HIPK_SPMV_NO_CHEB;   // row per wavefront, huge-row pre-pass: no epilogue
     if (!rowwave && h->n_huge > 0) {
         // pre-pass: the few rows that exceed the LDS product buffer, one wavefront each, raw sums into y
         hipk_spmv_args ah = a;
@@ -673,7 +676,7 @@ int hipk_launch_spmv(const hipk_csr_s *h, const hipk_spmv_args &a_, hipStream_t 
             const int tpc = a.ch / 256;
             void (*kern)(hipk_spmv_args) = nullptr;
             int lgrid = 0;
-            bool chunked = false, strided = false;
+            bool chunked = false, strided = false, cheb = false;
             static const bool no_plan_cache = hipk_sw_present("HIPK_SPMV_NO_PLAN_CACHE");
             const hipk_spmv_plan *pl = nullptr;
             for (int i = 0; i < h->n_plans && !no_plan_cache; ++i)
@@ -683,6 +686,7 @@ int hipk_launch_spmv(const hipk_csr_s *h, const hipk_spmv_args &a_, hipStream_t 
                 lgrid = pl->lgrid;
                 chunked = pl->chunked;
                 strided = pl->strided;
+                cheb = pl->cheb;
                 a.group_tiles = pl->group_tiles;
                 memcpy(g_spmv_kernel, pl->name, sizeof(g_spmv_kernel));
             } else {
@@ -712,6 +716,7 @@ int hipk_launch_spmv(const hipk_csr_s *h, const hipk_spmv_args &a_, hipStream_t 
                 constexpr int both = HIPK_SPMV_DOT_W | HIPK_SPMV_DOT_YY;
                 // uniform tiles two rows per lane (hipk_spmv_sell_wide_kernel; fp64, most tiles uniform), mode bits compiled in for
                 // the CG loop's form, the Arnoldi step's, BiCGStab's t = A s with <t, s> and <t, t> (TSL:925-927), plain y = A x
+                bool wide_cheb = false;   // pick_wide returned the Chebyshev instantiation
                 auto pick_wide = [&](int st, char *pname, size_t cap) -> void (*)(hipk_spmv_args) {  // st = the kernel's WALK
                     void (*pk)(hipk_spmv_args) = nullptr;
 #define HIPK_PICK_WIDE_S(M, S) \
@@ -722,10 +727,12 @@ int hipk_launch_spmv(const hipk_csr_s *h, const hipk_spmv_args &a_, hipStream_t 
                     if (a.mode == HIPK_SPMV_DOT_YY && !no_mode) pk = HIPK_PICK_WIDE(HIPK_SPMV_DOT_YY);
                     if (a.mode == both && !no_mode) pk = HIPK_PICK_WIDE(both);
                     if (a.mode == 0 && !no_mode) pk = HIPK_PICK_WIDE(0);
+                    wide_cheb = a.mode == HIPK_SPMV_CHEB_MODE && !no_mode;
+                    if (wide_cheb) pk = HIPK_PICK_WIDE(HIPK_SPMV_CHEB_MODE);
 #undef HIPK_PICK_WIDE
 #undef HIPK_PICK_WIDE_S
                     snprintf(pname, cap, "hipk_spmv_sell_wide_kernel<%d,%d,%d>", h->sell_w,  // the template arguments, as a profiler prints them
-                             (a.mode >= 0 && a.mode <= both && !no_mode) ? a.mode : -1, st);
+                             ((a.mode >= 0 && a.mode <= both && !no_mode) || wide_cheb) ? a.mode : -1, st);
                     return pk;
                 };
                 // grouped walk of that kernel (WALK = 1: one workgroup per 4 consecutive tiles, tile sums through the combine kernel).
@@ -743,6 +750,7 @@ int hipk_launch_spmv(const hipk_csr_s *h, const hipk_spmv_args &a_, hipStream_t 
                         kern = pick_wide(1, pname, sizeof(pname));
                         lgrid = hipk_xcd_grid((ntiles + HIPK_SELL_GROUP - 1) / HIPK_SELL_GROUP);
                         strided = true;
+                        cheb = wide_cheb;
                         HIPK_NOTE_KERNEL("%s", pname);
                     }
                 }
@@ -787,12 +795,16 @@ int hipk_launch_spmv(const hipk_csr_s *h, const hipk_spmv_args &a_, hipStream_t 
                             pk = h->tile_ucode ? hipk_spmv_sell_pair_kernel<double, 5, true, HIPK_SPMV_DOT_YY>
                                                : hipk_spmv_sell_pair_kernel<double, 5, false, HIPK_SPMV_DOT_YY>;
                         snprintf(pname, sizeof(pname), "hipk_spmv_sell_pair_kernel<%s,%d,%s,%d>", tname, h->sell_w, uni, pmode);
-                        if (!no_wide && h->dtype == HIPK_F64 && h->tile_ucode && 2 * (h->n_uniform_tiles + h->n_masked_tiles) >= ntiles)
+                        bool pk_cheb = false;
+                        if (!no_wide && h->dtype == HIPK_F64 && h->tile_ucode && 2 * (h->n_uniform_tiles + h->n_masked_tiles) >= ntiles) {
                             pk = pick_wide(0, pname, sizeof(pname));
+                            pk_cheb = wide_cheb;
+                        }
                         int pocc = 0;  // the pair form holds more registers: take it only if the chunks still run as ONE round of workgroups
                         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&pocc, pk, HIPK_THREADS, 0) == hipSuccess &&
                             (pocc * h->n_cu >= a.g || pocc >= occ)) {
                             kern = pk;
+                            cheb = pk_cheb;
                             HIPK_NOTE_KERNEL("%s", pname);
                         }
 #undef HIPK_PICK_PAIR
@@ -816,9 +828,12 @@ int hipk_launch_spmv(const hipk_csr_s *h, const hipk_spmv_args &a_, hipStream_t 
                     np.group_tiles = a.group_tiles;
                     np.chunked = chunked;
                     np.strided = strided;
+                    np.cheb = cheb;
                     memcpy(np.name, g_spmv_kernel, sizeof(np.name));
                 }
             }
+            if (want_cheb && !cheb) return HIPK_SPMV_NO_CHEB;   // the one-row-per-lane coded kernels have no Chebyshev epilogue
+            if (want_cheb && a.y == nullptr) return HIPK_OK;    // hipk_cheb_apply asking whether the epilogue exists: no launch
             hipk_launch_timed(prof, HIPK_K_SPMV, kern, lgrid, HIPK_THREADS, 0, stream, a);
             if ((!chunked || strided) && !a.skip_combine && (a.mode & (HIPK_SPMV_DOT_W | HIPK_SPMV_DOT_YY))) {
                 hipk_launch_timed(prof, HIPK_K_AUX, hipk_tile_combine_kernel, (a.g + 3) / 4, HIPK_THREADS, 0, stream, (a.mode & HIPK_SPMV_DOT_W) ? a.tpart0 : nullptr, (a.mode & HIPK_SPMV_DOT_YY) ? a.tpart1 : nullptr,
@@ -827,6 +842,7 @@ int hipk_launch_spmv(const hipk_csr_s *h, const hipk_spmv_args &a_, hipStream_t 
             HIPK_CHECK_HIP(hipGetLastError());
             return HIPK_OK;
         }
+        if (want_cheb) return HIPK_SPMV_NO_CHEB;
         HIPK_NOTE_KERNEL("hipk_spmv_coded_kernel<%s,1>", h->dtype == HIPK_F64 ? "double" : "float");
         if (h->dtype == HIPK_F64)
             hipk_launch_timed(prof, HIPK_K_SPMV, hipk_spmv_coded_kernel<double, 1>, cgrid, HIPK_THREADS, lds, stream, a);
@@ -836,6 +852,21 @@ int hipk_launch_spmv(const hipk_csr_s *h, const hipk_spmv_args &a_, hipStream_t 
             hipk_launch_timed(prof, HIPK_K_AUX, hipk_tile_combine_kernel, (a.g + 3) / 4, HIPK_THREADS, 0, stream, (a.mode & HIPK_SPMV_DOT_W) ? a.tpart0 : nullptr, (a.mode & HIPK_SPMV_DOT_YY) ? a.tpart1 : nullptr, a.part0,
                 a.part1, ntiles, a.ch / 256, a.g, a.stop_it, a.it);
         }
+        HIPK_CHECK_HIP(hipGetLastError());
+        return HIPK_OK;
+    }
+    if (want_cheb) {   // the tile kernel's FAST instantiations have a Chebyshev twin; the general one has not
+        const bool f64 = h->dtype == HIPK_F64, shortrows = h->max_row_len <= HIPK_LONG_ROW;
+        if (!shortrows || h->max_tile_nnz > 2048) return HIPK_SPMV_NO_CHEB;
+        const int cap = (f64 && h->max_tile_nnz <= 1280) ? 1280 : 2048;
+        if (a.y == nullptr) return HIPK_OK;   // hipk_cheb_apply asking whether the epilogue exists: no launch
+        HIPK_NOTE_KERNEL("hipk_spmv_cheb_kernel<%s,%d>", f64 ? "double" : "float", cap);
+        if (f64 && cap == 1280)
+            hipk_launch_timed(prof, HIPK_K_SPMV, hipk_spmv_cheb_kernel<double, 1280>, grid, HIPK_THREADS, 0, stream, a);
+        else if (f64)
+            hipk_launch_timed(prof, HIPK_K_SPMV, hipk_spmv_cheb_kernel<double, 2048>, grid, HIPK_THREADS, 0, stream, a);
+        else
+            hipk_launch_timed(prof, HIPK_K_SPMV, hipk_spmv_cheb_kernel<float, 2048>, grid, HIPK_THREADS, 0, stream, a);
         HIPK_CHECK_HIP(hipGetLastError());
         return HIPK_OK;
     }
@@ -930,6 +961,118 @@ extern "C" int hipk_spmv_ex(hipk_csr_t h, const void *x, void *y, int mode, cons
     a.stop_it = stop_dev;
     a.it = it;
     return hipk_launch_spmv(h, a, (hipStream_t)stream);
+}
+
+// ------------------------------------------------------------------ Chebyshev polynomial preconditioner
+// z = p_m(D^-1 A) D^-1 r (include/hipk.h: hipk_cheb_apply has the recurrence and its rounding spec).  Step 0 is hipk_cheb_init_kernel.
+// Step k is ONE launch -- the SpMV with the Chebyshev epilogue (HIPK_SPMV_CHEB: res stays in registers, z_old is gathered from one
+// buffer and z_new stored to the other, so that no row reads a z another workgroup has already replaced) -- where the handle's SpMV
+// family has it: the two-rows-per-lane coded kernel and the tile kernel's FAST instantiations.  Elsewhere, and with
+// HIPK_CHEB_FUSED=0, it is the SpMV's residual form + row scaling into a work vector followed by hipk_cheb_step_kernel: 2 n more
+// elements of traffic per step, the same operations in the same order per row, the same bits.
+template <typename T>
+__global__ __launch_bounds__(HIPK_THREADS) void hipk_cheb_init_kernel(int64_t n, int ch, int g, T c0, const T *__restrict__ dinv,
+                                                                      const T *__restrict__ r, T *__restrict__ d, T *__restrict__ z) {
+    constexpr int VEC = hipk_vec<T>::VEC;
+    const int c = hipk_xcd_chunk(blockIdx.x, g);
+    if (c < 0) return;
+    hipk_chunk_loop<T>(n, ch, c, [&](int64_t i, int nv) {
+        T dv[VEC], rv[VEC], o[VEC];
+        hipk_ld<T>(dinv, i, nv, dv);
+        hipk_ld<T>(r, i, nv, rv);
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) o[k] = c0 * (dv[k] * rv[k]);
+        hipk_st<T>(d, i, nv, o);
+        hipk_st<T>(z, i, nv, o);
+    });
+}
+
+// d = (c1 d) + (c2 res), z = scale (z + d), in place; a reduction chunk per workgroup, 16-byte accesses
+template <typename T>
+__global__ __launch_bounds__(HIPK_THREADS) void hipk_cheb_step_kernel(int64_t n, int ch, int g, T c1, T c2, T scale,
+                                                                      const T *__restrict__ res, T *__restrict__ d, T *__restrict__ z) {
+    constexpr int VEC = hipk_vec<T>::VEC;
+    const int c = hipk_xcd_chunk(blockIdx.x, g);
+    if (c < 0) return;
+    hipk_chunk_loop<T>(n, ch, c, [&](int64_t i, int nv) {
+        T sv[VEC], dv[VEC], zv[VEC];
+        hipk_ld<T>(res, i, nv, sv);
+        hipk_ld<T>(d, i, nv, dv);
+        hipk_ld<T>(z, i, nv, zv);
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) {
+            dv[k] = (c1 * dv[k]) + (c2 * sv[k]);
+            zv[k] = scale * (zv[k] + dv[k]);
+        }
+        hipk_st<T>(d, i, nv, dv);
+        hipk_st<T>(z, i, nv, zv);
+    });
+}
+
+template <typename T>
+static int hipk_cheb_apply_t(const hipk_csr_s *h, int m, const T *dinv, const double *coef, const T *r, T *z, T *work, hipStream_t stream) {
+    const int64_t n = h->n_rows;
+    const int ch = h->geom.ch, g = h->geom.g, vgrid = hipk_xcd_grid(g);
+    T *d = work, *w1 = work + ((n + 3) & ~(int64_t)3);   // w1: the second z buffer (one launch per step) or res (two)
+    const double c0 = coef[0], *c1 = coef, *c2 = coef + m, scale = coef[2 * m + 1];   // c1[k], c2[k], k = 1 .. m
+    hipk_spmv_args a;
+    hipk_fill_spmv_args(h, a, nullptr, nullptr);
+    a.bsub = r;
+    a.dscale = dinv;
+    a.cheb_d = d;
+    bool fused = hipk_sw_enabled("HIPK_CHEB_FUSED");
+    if (fused) {   // does the kernel this handle's SpMV resolves to have the epilogue?  (y = null: nothing is launched)
+        a.mode = HIPK_SPMV_CHEB_MODE;
+        const int rc = hipk_launch_spmv(h, a, stream);
+        if (rc != HIPK_OK && rc != HIPK_SPMV_NO_CHEB) return rc;
+        fused = rc == HIPK_OK;
+    }
+    // one launch per step: z_k lives in z when m - k is even, else in w1 -- z_m is the caller's z without a copy
+    T *zk = (fused && (m & 1)) ? w1 : z;
+    hipk_cheb_init_kernel<T><<<vgrid, HIPK_THREADS, 0, stream>>>(n, ch, g, (T)c0, dinv, r, d, zk);
+    for (int k = 1; k <= m; ++k) {
+        const double sk = (k == m) ? scale : 1.0;
+        if (fused) {
+            T *zn = (zk == z) ? w1 : z;
+            a.mode = HIPK_SPMV_CHEB_MODE;
+            a.x = zk;
+            a.y = zn;
+            a.cheb_c1 = c1[k];
+            a.cheb_c2 = c2[k];
+            a.cheb_scale = sk;
+            HIPK_TRY(hipk_launch_spmv(h, a, stream));
+            zk = zn;
+        } else {
+            a.mode = HIPK_SPMV_RESID | HIPK_SPMV_SCALE;
+            a.x = z;
+            a.y = w1;
+            HIPK_TRY(hipk_launch_spmv(h, a, stream));
+            hipk_cheb_step_kernel<T><<<vgrid, HIPK_THREADS, 0, stream>>>(n, ch, g, (T)c1[k], (T)c2[k], (T)sk, w1, d, z);
+        }
+    }
+    if (!fused) {
+        const size_t l = strlen(g_spmv_kernel);
+        snprintf(g_spmv_kernel + l, sizeof(g_spmv_kernel) - l, " + hipk_cheb_step_kernel<%s>", sizeof(T) == 8 ? "double" : "float");
+    }
+    HIPK_CHECK_HIP(hipGetLastError());
+    return HIPK_OK;
+}
+
+extern "C" int hipk_cheb_apply(hipk_csr_t h, int degree, const void *dinv, const double *coef_host, const void *r, void *z, void *work,
+                               hipk_stream_t stream) {
+    HIPK_REQUIRE(h && dinv && coef_host && r && z && work, HIPK_ERR_ARG, "null argument");
+    HIPK_REQUIRE(h->op_cb == nullptr, HIPK_ERR_UNSUPPORTED, "hipk_cheb_apply needs a CSR handle, not a matrix-free operator");
+    HIPK_REQUIRE(degree >= 1 && degree <= 32, HIPK_ERR_ARG, "degree must be in [1, 32]");
+    HIPK_REQUIRE(h->n_rows == h->n_cols, HIPK_ERR_ARG, "the matrix must be square");
+    HIPK_REQUIRE(hipk_aligned16(dinv) && hipk_aligned16(r) && hipk_aligned16(z) && hipk_aligned16(work), HIPK_ERR_ALIGN,
+                 "dinv/r/z/work must be 16-byte aligned");
+    HIPK_REQUIRE(r != z && r != work && z != work && dinv != z && dinv != work, HIPK_ERR_ARG, "r, z, work and dinv must be distinct");
+    if (h->n_rows == 0) return HIPK_OK;
+    if (h->dtype == HIPK_F64)
+        return hipk_cheb_apply_t<double>(h, degree, (const double *)dinv, coef_host, (const double *)r, (double *)z, (double *)work,
+                                         (hipStream_t)stream);
+    return hipk_cheb_apply_t<float>(h, degree, (const float *)dinv, coef_host, (const float *)r, (float *)z, (float *)work,
+                                    (hipStream_t)stream);
 }
 
 #ifdef HIPK_GM_STAMPS

@@ -1040,6 +1040,9 @@ template <int UNITS, int MODE = -1, int WALK = 0>
 __global__ __launch_bounds__(HIPK_THREADS) HIPK_SGPR80 void hipk_spmv_sell_wide_kernel(hipk_spmv_args a) {
     typedef double T;
     constexpr bool STRIDED = WALK != 0;  // tile sums to the per-tile buffer, no in-kernel fold
+    // MODE = HIPK_SPMV_CHEB_MODE: one Chebyshev step (hipk_cheb_apply) -- a compiled-in mode only, the run-time-mode instantiation
+    // knows nothing of it (a run-time test here would cost every other instantiation registers)
+    constexpr bool CHEB = MODE >= 0 && (MODE & HIPK_SPMV_CHEB) != 0;
     constexpr int G0 = (UNITS + 3) / 4;
     constexpr int NE = UNITS == 5 ? 5 : (UNITS == 4 ? 4 : 8);
     static_assert(UNITS == 4 || UNITS == 5 || UNITS == 8, "exact tile sizes only");
@@ -1126,11 +1129,15 @@ __global__ __launch_bounds__(HIPK_THREADS) HIPK_SGPR80 void hipk_spmv_sell_wide_
             const unsigned bo = (unsigned)(rowx + doff[ck]) * (unsigned)sizeof(T);
             xv[k] = *(const T *)(xb + bo);
         }
-        T ow = (T)0, ob = (T)0, od = (T)0;
+        T ow = (T)0, ob = (T)0, od = (T)0, cd = (T)0, cz = (T)0;
         if (row < n32) {
             if (mode & HIPK_SPMV_DOT_W) ow = ((const T *)a.w)[row];
             if (mode & HIPK_SPMV_RESID) ob = ((const T *)a.bsub)[row];
             if (mode & HIPK_SPMV_SCALE) od = ((const T *)a.dscale)[row];
+            if (CHEB) {
+                cd = ((const T *)a.cheb_d)[row];
+                cz = ((const T *)a.x)[row];
+            }
         }
         T s = (T)0;
 #pragma unroll
@@ -1145,6 +1152,11 @@ __global__ __launch_bounds__(HIPK_THREADS) HIPK_SGPR80 void hipk_spmv_sell_wide_
             T out = s;
             if (mode & HIPK_SPMV_RESID) out = ob - out;
             if (mode & HIPK_SPMV_SCALE) out = od * out;
+            if (CHEB) {  // out is res: d = (c1 d) + (c2 res), z_new = scale (z_old + d)
+                const T dn = (a.cheb_c1 * cd) + (a.cheb_c2 * out);
+                ((T *)a.cheb_d)[row] = dn;
+                out = a.cheb_scale * (cz + dn);
+            }
             y[row] = out;
             if (mode & HIPK_SPMV_DOT_W) d0 = (double)ow * (double)out;
             if (mode & HIPK_SPMV_DOT_YY) d1 = (double)out * (double)out;
@@ -1216,6 +1228,20 @@ __global__ __launch_bounds__(HIPK_THREADS) HIPK_SGPR80 void hipk_spmv_sell_wide_
         }
         if (mode & HIPK_SPMV_RESID) ob = *(const double2 *)((const char *)a.bsub + vo);
         if (mode & HIPK_SPMV_SCALE) od = *(const double2 *)((const char *)a.dscale + vo);
+        // CHEB: d and z_old of the two rows.  The 8-wide tile holds sixteen gathered doubles per lane: there d is requested after
+        // the row sums instead of with the other epilogue operands (67 -> 62 vector registers: eight workgroups per CU stay resident)
+        constexpr bool CHEB_LATE_D = UNITS == 8;
+        double2 cd = {0.0, 0.0}, cz = {0.0, 0.0};
+        if (CHEB) {
+            if (!CHEB_LATE_D) cd = *(const double2 *)((const char *)a.cheb_d + vo);
+            if (kc >= 0) {  // z_old of the rows themselves: the diagonal entry's operand, already loaded
+#pragma unroll
+                for (int k = 0; k < NE; ++k)
+                    if (k == kc) cz = xv[k];
+            } else {
+                cz = *(const double2 *)(xb + vo);
+            }
+        }
         unsigned pm = 0xFFFFu;   // presence of the pattern's entries in rows 2l (low byte) and 2l + 1 (high byte)
         if (masked) pm = *(const unsigned short *)(a.row_mask + r0);
         double2 s = {0.0, 0.0};
@@ -1237,6 +1263,13 @@ __global__ __launch_bounds__(HIPK_THREADS) HIPK_SGPR80 void hipk_spmv_sell_wide_
         if (mode & HIPK_SPMV_SCALE) {
             out.x = od.x * out.x;
             out.y = od.y * out.y;
+        }
+        if (CHEB) {
+            if (CHEB_LATE_D) cd = *(const double2 *)((const char *)a.cheb_d + vo);
+            const double2 dn = {(a.cheb_c1 * cd.x) + (a.cheb_c2 * out.x), (a.cheb_c1 * cd.y) + (a.cheb_c2 * out.y)};
+            *(double2 *)((char *)a.cheb_d + vo) = dn;
+            out.x = a.cheb_scale * (cz.x + dn.x);
+            out.y = a.cheb_scale * (cz.y + dn.y);
         }
         *(double2 *)((char *)y + vo) = out;
         const int slot = i * 4 + 2 * wh + (lane >> 5);

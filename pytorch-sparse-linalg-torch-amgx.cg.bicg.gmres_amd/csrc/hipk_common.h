@@ -95,6 +95,7 @@ struct hipk_spmv_plan {
     void *kern;
     int lgrid, group_tiles;
     bool chunked, strided;
+    bool cheb;   // the kernel has the Chebyshev epilogue compiled in (mode HIPK_SPMV_CHEB_MODE)
     char name[96];
 };
 

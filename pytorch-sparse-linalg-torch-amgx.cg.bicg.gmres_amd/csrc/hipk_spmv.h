@@ -28,6 +28,11 @@
 #define HIPK_SPMV_RESID 4   // out = bsub - A x  instead of A x
 #define HIPK_SPMV_SCALE 8   // out = dscale .* out, after RESID and before the fused dots: left Jacobi preconditioning
                             // M(A v), M(b - A x) of the preconditioned GMRES (TSL:351, 791); internal, not in hipk_spmv_ex
+#define HIPK_SPMV_CHEB 16  // Chebyshev step (hipk_cheb_apply), with RESID and SCALE and no fused dot: res = dscale .* (bsub - A x) stays in
+                           // registers, cheb_d = (c1 * cheb_d) + (c2 * res), y = scale * (x_row + cheb_d); x is z_old, y the OTHER z buffer.
+                           // Compiled-in only (a template flag / MODE value of the kernels that have it); internal, not in hipk_spmv_ex
+#define HIPK_SPMV_CHEB_MODE (HIPK_SPMV_RESID | HIPK_SPMV_SCALE | HIPK_SPMV_CHEB)
+#define HIPK_SPMV_NO_CHEB 1000  // hipk_launch_spmv: the kernel this launch resolves to has no Chebyshev epilogue; nothing was launched
 #define HIPK_LONG_ROW 32    // rows with more nnz are summed by a wavefront (strided + tree)
 
 struct hipk_spmv_args {
@@ -69,6 +74,8 @@ struct hipk_spmv_args {
                             //   launcher), 0 = a workgroup per reduction chunk
     int skip_combine;       // small systems: leave the fused dots as per-wavefront tile sums (hipk_csr_s::tile_part); the
                             //   consumer folds them itself (hipk_fold_tiles8) -- one launch less per SpMV
+    void *cheb_d;           // HIPK_SPMV_CHEB: the direction vector d, updated in place (each row by its own lane)
+    double cheb_c1, cheb_c2, cheb_scale;  //   this step's coefficients; scale = 1 except in the last step
 };
 
 #ifdef __HIPCC__
@@ -89,8 +96,10 @@ __device__ __forceinline__ int hipk_xcd_tile(int b, int ntiles) {
 
 // FAST = true: handle-creation analysis proved that every tile has <= CAP entries and no row more than
 // HIPK_LONG_ROW, so the long-row pass and the general path are compiled out (26 VGPRs instead of 46).
-template <typename T, int CAP, bool FAST>
-__global__ __launch_bounds__(HIPK_THREADS) void hipk_spmv_kernel(hipk_spmv_args a) {
+// CHEB: the Chebyshev epilogue (HIPK_SPMV_CHEB) with the mode bits compiled in -- a separate instantiation
+// (hipk_spmv_cheb_kernel), so that the product kernels keep their registers.
+template <typename T, int CAP, bool FAST, bool CHEB>
+__device__ __forceinline__ void hipk_spmv_tile_body(const hipk_spmv_args &a) {
     constexpr int NI = CAP / HIPK_THREADS;
     static_assert(CAP % HIPK_THREADS == 0, "CAP must be a multiple of the workgroup size");
     static_assert(CAP * sizeof(T) >= 512 * sizeof(double), "prod[] doubles as reduction scratch");
@@ -111,7 +120,7 @@ __global__ __launch_bounds__(HIPK_THREADS) void hipk_spmv_kernel(hipk_spmv_args 
     const T *__restrict__ val = (const T *)a.val;
     const T *__restrict__ x = (const T *)a.x;
     T *y = (T *)a.y;  // not restrict: the general path reads pre-pass results from y before overwriting them
-    const int mode = a.mode;
+    const int mode = CHEB ? (HIPK_SPMV_RESID | HIPK_SPMV_SCALE) : a.mode;
 
     const int64_t r0 = (int64_t)tile * HIPK_TILE;
     const int nr = (int)((a.n - r0 < HIPK_TILE) ? (a.n - r0) : HIPK_TILE);
@@ -122,6 +131,11 @@ __global__ __launch_bounds__(HIPK_THREADS) void hipk_spmv_kernel(hipk_spmv_args 
         if (mode & HIPK_SPMV_DOT_W) wrow = ((const T *)a.w)[r0 + t];
         if (mode & HIPK_SPMV_RESID) brow = ((const T *)a.bsub)[r0 + t];
         if (mode & HIPK_SPMV_SCALE) drow = ((const T *)a.dscale)[r0 + t];
+    }
+    T cheb_d = (T)0, cheb_z = (T)0;  // CHEB: this row's d and z_old
+    if (CHEB && t < nr) {
+        cheb_d = ((const T *)a.cheb_d)[r0 + t];
+        cheb_z = x[r0 + t];
     }
     int crow_t = 0, crow_e = 0;
     if (t < nr) crow_t = crow[r0 + t];
@@ -278,6 +292,11 @@ __global__ __launch_bounds__(HIPK_THREADS) void hipk_spmv_kernel(hipk_spmv_args 
         T out = yrow;
         if (mode & HIPK_SPMV_RESID) out = brow - out;
         if (mode & HIPK_SPMV_SCALE) out = drow * out;
+        if (CHEB) {  // out is res: d = (c1 d) + (c2 res), z_new = scale (z_old + d), every step its own rounding
+            const T dn = ((T)a.cheb_c1 * cheb_d) + ((T)a.cheb_c2 * out);
+            ((T *)a.cheb_d)[r0 + t] = dn;
+            out = (T)a.cheb_scale * (cheb_z + dn);
+        }
         y[r0 + t] = out;
         if (mode & HIPK_SPMV_DOT_W) d0 = (double)wrow * (double)out;
         if (mode & HIPK_SPMV_DOT_YY) d1 = (double)out * (double)out;
@@ -294,6 +313,16 @@ d1 = hipk_wave_sum(d1);
             if (lane == 0) a.tpart1[(size_t)tile * 4 + wave] = d1;
         }
     }
+}
+
+template <typename T, int CAP, bool FAST>
+__global__ __launch_bounds__(HIPK_THREADS) void hipk_spmv_kernel(hipk_spmv_args a) {
+    hipk_spmv_tile_body<T, CAP, FAST, false>(a);
+}
+// one Chebyshev step in one launch, for the matrices hipk_spmv_kernel<T, CAP, true> takes
+template <typename T, int CAP>
+__global__ __launch_bounds__(HIPK_THREADS) void hipk_spmv_cheb_kernel(hipk_spmv_args a) {
+    hipk_spmv_tile_body<T, CAP, true, true>(a);
 }
 
 // ---------------------------------------------------------------------------------------------------

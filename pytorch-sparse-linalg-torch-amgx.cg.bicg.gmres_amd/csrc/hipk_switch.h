@@ -35,6 +35,7 @@ static constexpr hipk_sw_row hipk_switches[] = {
     {"HIPK_SPMV_SELL_NO_WIDE", HIPK_SW_PRESENT, "off", "each SpMV dispatch", "the one-row-per-lane coded kernels instead of the two-rows-per-lane kernel", "tools A/B"},
     {"HIPK_SPMV_SELL_STRIDED", HIPK_SW_INT, "automatic", "each SpMV dispatch", "0 | nonzero: force the chunk walk | the grouped walk of the coded kernels (unset: by tiles per chunk)", "test, tools A/B"},
     {"HIPK_SPMV_SELL_NO_PAIR", HIPK_SW_PRESENT, "off", "first chunked coded SpMV of the process", "the one-tile-per-trip coded kernel instead of the pair kernel", "tools A/B"},
+    {"HIPK_CHEB_FUSED", HIPK_SW_OFF_IF_0, "on", "each hipk_cheb_apply", "0: every Chebyshev step as SpMV + hipk_cheb_step_kernel instead of the SpMV's Chebyshev epilogue (same bits)", "test, tools A/B"},
     // ---- every solve loop (hipk_solve.h)
     {"HIPK_HOST_SIGNAL", HIPK_SW_OFF_IF_0, "on", "each solve", "0: follow the loop with stream-ordered reads of the device stop word instead of the pinned-host signal word", "test"},
     {"HIPK_PACE_TIMEOUT_US", HIPK_SW_INT, "200000", "each solve", "t: microseconds the signal word may stand still before the stream-ordered fallback; negative: ignored", "test"},

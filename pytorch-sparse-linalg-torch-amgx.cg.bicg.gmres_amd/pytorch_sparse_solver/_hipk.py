@@ -31,6 +31,7 @@ SYMBOLS = [
     "hipk_csr_transpose_work_bytes", "hipk_csr_transpose",
     "hipk_chunk_size", "hipk_chunk_count", "hipk_scratch_bytes",
     "hipk_spmv", "hipk_spmv_dot", "hipk_dot", "hipk_axpy", "hipk_xpby", "hipk_block_jacobi_apply",
+    "hipk_cheb_apply",
     "hipk_cg_work_bytes", "hipk_cg_solve", "hipk_pcg_work_bytes", "hipk_pcg_solve", "hipk_pgmres_solve", "hipk_pbicgstab_work_bytes", "hipk_pbicgstab_solve", "hipk_pbicgstab_solve_cb", "hipk_pgmres_solve_cb",
     "hipk_bicgstab_work_bytes", "hipk_bicgstab_solve",
     "hipk_gmres_work_bytes", "hipk_gmres_solve",
@@ -193,6 +194,7 @@ def lib():
     L.hipk_axpy.argtypes = [i64, dbl, vp, vp, i32, vp]
     L.hipk_xpby.argtypes = [i64, vp, dbl, vp, i32, vp]
     L.hipk_block_jacobi_apply.argtypes = [i64, i32, vp, vp, vp, i32, vp]
+    L.hipk_cheb_apply.argtypes = [vp, i32, vp, ctypes.POINTER(ctypes.c_double), vp, vp, vp, vp]
     for name in ("cg", "bicgstab"):
         wb = getattr(L, f"hipk_{name}_work_bytes")
         wb.argtypes = [i64, i32]
@@ -573,6 +575,23 @@ def block_jacobi_apply(binv: torch.Tensor, block_size: int, v: torch.Tensor) -> 
     with torch.cuda.device(v.device):
         _check(lib().hipk_block_jacobi_apply(v.numel(), int(block_size), binv.data_ptr(), v.data_ptr(), out.data_ptr(),
                                              _dtype_code(v.dtype), _stream(v.device)), "hipk_block_jacobi_apply")
+    return out
+
+
+def cheb_apply(h: CsrHandle, degree: int, dinv: torch.Tensor, coef, v: torch.Tensor) -> torch.Tensor:
+    """z = p_m(D^-1 A) D^-1 v on the device (hipk_cheb_apply), enqueued on the current stream.  `coef`: a ctypes array of
+    2 * degree + 2 doubles (c0, c1[1..m], c2[1..m], scale).  Takes no lock and touches none of the handle's reduction scratch:
+    it is what a solve that HOLDS the handle calls as its preconditioner."""
+    assert v.is_cuda and v.dtype == h.dtype and v.device == h.device and v.numel() == h.n and h.shape[0] == h.shape[1]
+    assert dinv.is_contiguous() and dinv.dtype == v.dtype and dinv.device == v.device and dinv.numel() == h.n
+    assert len(coef) == 2 * int(degree) + 2
+    if not v.is_contiguous() or v.data_ptr() % 16:
+        v = v.contiguous().clone()
+    out = torch.empty_like(v)
+    work = torch.empty(2 * ((h.n + 3) & ~3), dtype=v.dtype, device=v.device)   # ordered by the stream, as the launches are
+    with torch.cuda.device(v.device):
+        _check(lib().hipk_cheb_apply(h.ptr, int(degree), dinv.data_ptr(), coef, v.data_ptr(), out.data_ptr(), work.data_ptr(),
+                                     _stream(v.device)), "hipk_cheb_apply")
     return out
 
 

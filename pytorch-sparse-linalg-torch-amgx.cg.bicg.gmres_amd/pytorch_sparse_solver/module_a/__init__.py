@@ -3,8 +3,8 @@
 Same exports as the reference's `module_a/__init__.py:47-63`; CUDA/ROCm tensor inputs run
 on hand-written gfx950 kernels (libhipk.so), everything else on the generic torch path.
 `get_last_stats()` (iteration counts the reference never returns), `JacobiPreconditioner` (a callable for the
-reference's `M` hook that the fast path runs device-resident) and `cg_multi` / `bicgstab_multi` (k right-hand sides per
-matrix read) are the additions.
+reference's `M` hook that the fast path runs device-resident), `ChebyshevPreconditioner` (a polynomial in D^-1 A whose steps
+run in the SpMV kernels' epilogue) and `cg_multi` / `bicgstab_multi` (k right-hand sides per matrix read) are the additions.
 """
 from .torch_sparse_linalg import (
     cg, bicgstab, gmres,
@@ -13,14 +13,14 @@ from .torch_sparse_linalg import (
 )
 from .multi_rhs import cg_multi, bicgstab_multi
 from .torch_tree_util import tree_leaves, tree_map, tree_flatten, tree_unflatten, Partial
-from .preconditioners import BlockJacobiPreconditioner, JacobiPreconditioner
+from .preconditioners import BlockJacobiPreconditioner, ChebyshevPreconditioner, JacobiPreconditioner
 
 __all__ = [
     'cg', 'bicgstab', 'gmres', 'cg_multi', 'bicgstab_multi',
     'cg_differentiable', 'bicgstab_differentiable', 'gmres_differentiable',
     'LinearSolveFunction',
     'tree_leaves', 'tree_map', 'tree_flatten', 'tree_unflatten', 'Partial',
-    'get_last_stats', 'JacobiPreconditioner', 'BlockJacobiPreconditioner',
+    'get_last_stats', 'JacobiPreconditioner', 'BlockJacobiPreconditioner', 'ChebyshevPreconditioner',
 ]
 
 __version__ = '1.0.0'
