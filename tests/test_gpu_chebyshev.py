@@ -1,7 +1,8 @@
 """ChebyshevPreconditioner on the device: hipk_cheb_apply bit for bit against the numpy mirror (tests/_cheb_mirror.py) in both of
 its forms -- one launch per step (the SpMV kernels' Chebyshev epilogue) and SpMV + hipk_cheb_step_kernel -- with the form that ran
 asserted from the kernel note; whole cg / bicgstab / gmres solves against the reference's runs (tests/golden/cheb_*.npz); one
-large solve for the stop logic."""
+large solve for the stop logic.  The epilogue kernels one by one -- every instantiation at ragged sizes, the README's sizes, whole
+solves in which an epilogue kernel runs -- are in tests/test_gpu_chebyshev_kernels.py."""
 import numpy as np
 import pytest
 import torch
