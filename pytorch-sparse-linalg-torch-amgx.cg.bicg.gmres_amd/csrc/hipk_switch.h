@@ -30,11 +30,11 @@ static constexpr hipk_sw_row hipk_switches[] = {
     {"HIPK_SPMV_MASKED", HIPK_SW_FORCE01, "off", "handle creation", "1: build the masked-tile analysis (fp64 pair codes); measured slower", "test"},
     {"HIPK_SPMV_SELL_CHUNKED", HIPK_SW_INT, "2", "handle creation; whether set: first coded SpMV of the process", "k: chunk-per-workgroup form when k x chunks >= resident workgroups; < 0 reads as 0 (never), 1 reads as 2 (quirk, kept); set at all also turns off the factor 4 of the two-rows-per-lane kernel", "test, tools A/B"},
     {"HIPK_SPMV_SELL_LOOP", HIPK_SW_INT, "1", "handle creation", "k: persistent grid = k x the resident workgroups, clamped to 1 .. 4", "test, tools A/B"},
-    {"HIPK_SPMV_NO_PLAN_CACHE", HIPK_SW_PRESENT, "off", "first coded SpMV of the process", "resolve the coded SpMV's dispatch per launch instead of once per (handle, mode, geometry)", "tools A/B"},
-    {"HIPK_SPMV_SELL_NO_MODE", HIPK_SW_PRESENT, "off", "first coded SpMV of the process", "run-time instead of compiled-in mode bits in the pair / two-rows-per-lane kernels", "tools A/B"},
-    {"HIPK_SPMV_SELL_NO_WIDE", HIPK_SW_PRESENT, "off", "each SpMV dispatch", "the one-row-per-lane coded kernels instead of the two-rows-per-lane kernel", "tools A/B"},
+    {"HIPK_SPMV_NO_PLAN_CACHE", HIPK_SW_PRESENT, "off", "first coded SpMV of the process", "resolve the coded SpMV's dispatch per launch instead of once per (handle, mode, geometry)", "test, tools A/B"},
+    {"HIPK_SPMV_SELL_NO_MODE", HIPK_SW_PRESENT, "off", "first coded SpMV of the process", "run-time instead of compiled-in mode bits in the pair / two-rows-per-lane kernels", "test, tools A/B"},
+    {"HIPK_SPMV_SELL_NO_WIDE", HIPK_SW_PRESENT, "off", "each SpMV dispatch", "the one-row-per-lane coded kernels instead of the two-rows-per-lane kernel", "test, tools A/B"},
     {"HIPK_SPMV_SELL_STRIDED", HIPK_SW_INT, "automatic", "each SpMV dispatch", "0 | nonzero: force the chunk walk | the grouped walk of the coded kernels (unset: by tiles per chunk)", "test, tools A/B"},
-    {"HIPK_SPMV_SELL_NO_PAIR", HIPK_SW_PRESENT, "off", "first chunked coded SpMV of the process", "the one-tile-per-trip coded kernel instead of the pair kernel", "tools A/B"},
+    {"HIPK_SPMV_SELL_NO_PAIR", HIPK_SW_PRESENT, "off", "first chunked coded SpMV of the process", "the one-tile-per-trip coded kernel instead of the pair kernel", "test, tools A/B"},
     {"HIPK_CHEB_FUSED", HIPK_SW_OFF_IF_0, "on", "each hipk_cheb_apply", "0: every Chebyshev step as SpMV + hipk_cheb_step_kernel instead of the SpMV's Chebyshev epilogue (same bits)", "test, tools A/B"},
     // ---- every solve loop (hipk_solve.h)
     {"HIPK_HOST_SIGNAL", HIPK_SW_OFF_IF_0, "on", "each solve", "0: follow the loop with stream-ordered reads of the device stop word instead of the pinned-host signal word", "test"},

@@ -300,9 +300,13 @@ def test_uniform_tiles_two_rows_per_lane(hipk, oracle, offsets, strided, masked,
     x, w, b = (torch.randn(n, dtype=torch.float64, device=DEV, generator=g) for _ in range(3))
     assert h.path() == "coded"
     runs = [(0, x, w), (1, x, x), (1, x, w), (2, x, w), (7, x, w), (6, x, w), (3, x, w)]
-    coded = [_spmv_ex_mode(hipk, h, m, xx, ww, b) for m, xx, ww in runs]
-    assert hipk.CsrHandle.last_spmv_kernel().startswith("hipk_spmv_sell_wide_kernel"), hipk.CsrHandle.last_spmv_kernel()
-    assert hipk.CsrHandle.last_spmv_kernel().endswith("," + strided + ">"), hipk.CsrHandle.last_spmv_kernel()
+    # the full note per mode: <tile width in units (3 -> 4, 7 -> 8), compiled-in MODE (0 .. 3; the residual forms -1), WALK>
+    units = {3: 4, 4: 4, 5: 5, 7: 8, 8: 8}[len(offsets)]
+    coded = []
+    for m, xx, ww in runs:
+        coded.append(_spmv_ex_mode(hipk, h, m, xx, ww, b))
+        k = hipk.CsrHandle.last_spmv_kernel()
+        assert k == f"hipk_spmv_sell_wide_kernel<{units},{m if m <= 3 else -1},{strided}>", (m, k)
     h.set_path(plain_only=True)
     plain = [_spmv_ex_mode(hipk, h, m, xx, ww, b) for m, xx, ww in runs]
     assert hipk.CsrHandle.last_spmv_kernel().startswith("hipk_spmv_kernel")
@@ -447,6 +451,9 @@ def test_fp32_storage_poisson_chunk_and_group_walks(hipk, groups, monkeypatch):
     coded = _spmv_ex_all_modes(hipk, h, x, w, b)
     k = hipk.CsrHandle.last_spmv_kernel()
     assert k.startswith("hipk_spmv_sell_") and k.endswith("/groups") == (groups == "1"), k
+    # mode 7 of fp32 pair codes, 5-unit tiles, uniform words: a workgroup per chunk takes the pair kernel, the forced groups the
+    # one-row-per-lane chunk kernel
+    assert k == ("hipk_spmv_sell_pair_kernel<float,5,true,-1>" if groups == "0" else "hipk_spmv_sell_loop_kernel<float,5,true,false,true>/groups"), k
     res = {}
     for plain in (False, True):
         h.set_path(plain_only=plain)

@@ -90,6 +90,18 @@ def test_names_put_into_the_environment_are_rows():
     assert not unknown, f"switches that are neither a row of hipk_switches nor of DESIGN.md's Python block: {unknown}"
 
 
+def test_used_by_says_test_exactly_when_a_test_names_the_switch():
+    """A row's used_by contains `test` exactly when a file under tests/ (other than this one) names the switch in quotes."""
+    me = os.path.abspath(__file__)
+    named = set()
+    for path in glob.glob(os.path.join(ROOT, "tests", "*.py")):
+        if os.path.abspath(path) != me:
+            named |= set(re.findall(r"""["'](HIPK_[A-Z0-9_]+)(?:=[^"']*)?["']""", _read(path)))
+    for name, _kind, _dflt, _read_when, _meaning, used_by in _rows():
+        says = "test" in re.split(r", ", used_by)
+        assert says == (name in named), f"{name}: used_by is '{used_by}', {'a' if name in named else 'no'} file under tests/ names it"
+
+
 def test_design_lists_exactly_the_table():
     rows = _rows()
     c_doc, py_doc = _design_section()
@@ -100,3 +112,6 @@ def test_design_lists_exactly_the_table():
     for name, kind, dflt, _read_when, _meaning, _used in rows:
         m = re.search(r"^\| `%s` \| ([a-z0-9_]+) \| ([^|]*) \|" % name, text, re.M)
         assert m and m.group(1) == KINDS[kind] and m.group(2).strip() == dflt, (name, m and m.groups())
+        # ... and who uses it (the last cell)
+        m = re.search(r"^\| `%s` \|.*\| ([^|]*) \|$" % name, text, re.M)
+        assert m and m.group(1).strip() == _used, (name, m and m.group(1), _used)
