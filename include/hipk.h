@@ -456,6 +456,31 @@ int hipk_dist_pgmres_wide_solve(hipk_csr_t A_local, const hipk_dist_plan *plan, 
                                 const void *b_local, void *x_ext, void *work, size_t work_bytes, const hipk_params *prm,
                                 hipk_stats *st, hipk_stream_t stream);
 
+/* The Chebyshev polynomial preconditioner of the GLOBAL system on a row block, and the row-partitioned CG that runs it (csrc/
+ * hipk_dist_cheb.h).  `degree`, `coef_host` as hipk_cheb_apply (2 m + 2 doubles on the host); `dinv_ext` as in the Jacobi loops
+ * above: n_ext doubles, the rank's reciprocal diagonal and then the owners' entries at the halo positions.  degree outside [1, 32]:
+ * HIPK_ERR_ARG.  fp64; the fused exchanges of hipk_rccl.fused are not taken.
+ *   hipk_dist_cheb_apply : z_ext[0 .. n_local) = this rank's rows of M r, r_ext[0 .. n_local) this rank's rows of r (n_ext doubles
+ *              each; both ghost tails are overwritten).  The recurrence and rounding spec of hipk_cheb_apply on the rectangular
+ *              block handle: step k gathers z_{k-1} over own and ghost columns, a halo exchange fills the ghost tail of z_k before
+ *              step k + 1 -- m halo exchanges (r, z_1 .. z_{m-1}), no reduction.  One launch per step where the block handle's SpMV
+ *              has the Chebyshev epilogue (z ping-pongs between z_ext and the workspace, z_m landing in z_ext), else SpMV +
+ *              hipk_cheb_step_kernel (also with HIPK_CHEB_FUSED=0); hipk_last_spmv_kernel() tells which.  Concatenated over the
+ *              ranks: bit for bit hipk_cheb_apply on the whole matrix.  Every rank calls it; never synchronises.
+ *   hipk_dist_chebcg_solve : CG with that M, arguments and conventions of hipk_dist_pcg_solve; bit for bit the iterates, counts and
+ *              `info` of the single-device cg with M = the Chebyshev preconditioner of the whole matrix (gamma = <r,z>, stop test
+ *              on <r,r>, info from ||M (b - A x)||).  Per iteration m + 2 collective launches: all-gather <p,Ap> | update + step 0
+ *              in one kernel | ONE group: all-gather <r,r> + halo of r | steps 1 .. m with a stand-alone halo of z_k before step
+ *              k + 1 | ONE group: all-gather <r,z> + halo of z_m | direction over n_ext.  hipk_last_solve_path() reports
+ *              "hipk_dist_chebcg launch sequence". */
+size_t hipk_dist_cheb_work_bytes(const hipk_dist_plan *plan);
+int hipk_dist_cheb_apply(hipk_csr_t A_local, const hipk_dist_plan *plan, const hipk_rccl *coll, int degree, const void *dinv_ext,
+                         const double *coef_host, void *r_ext, void *z_ext, void *work, size_t work_bytes, hipk_stream_t stream);
+size_t hipk_dist_chebcg_work_bytes(const hipk_dist_plan *plan);
+int hipk_dist_chebcg_solve(hipk_csr_t A_local, const hipk_dist_plan *plan, const hipk_rccl *coll, int degree, const void *dinv_ext,
+                           const double *coef_host, const void *b_local, void *x_ext, void *work, size_t work_bytes,
+                           const hipk_params *prm, hipk_stats *st, hipk_stream_t stream);
+
 /* ---- EXPERIMENTAL peer-to-peer exchange provider for the loop above (csrc/hipk_p2p.hip) ---------------------------------
  * Each rank owns a device mailbox that every peer maps through HIP IPC; an all-gather is ONE small kernel per rank (publish
  * blocks store into the peers' mailboxes, collect blocks wait on per-source sequence flags).  No reference counterpart.

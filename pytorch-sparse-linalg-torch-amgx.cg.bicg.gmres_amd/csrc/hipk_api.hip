@@ -1009,6 +1009,26 @@ __global__ __launch_bounds__(HIPK_THREADS) void hipk_cheb_step_kernel(int64_t n,
     });
 }
 
+// The two vector kernels for the row-partitioned apply (csrc/hipk_dist_cheb.h): fp64, a row block of n rows in chunks of ch;
+// hipk_note_cheb_step: the kernel note of the two-launch form, as hipk_cheb_apply leaves it.
+int hipk_launch_cheb_init(int64_t n, int ch, double c0, const double *dinv, const double *r, double *d, double *z, hipStream_t stream) {
+    const int g = (int)((n + ch - 1) / ch);
+    hipk_cheb_init_kernel<double><<<hipk_xcd_grid(g), HIPK_THREADS, 0, stream>>>(n, ch, g, c0, dinv, r, d, z);
+    HIPK_CHECK_HIP(hipGetLastError());
+    return HIPK_OK;
+}
+int hipk_launch_cheb_step(int64_t n, int ch, double c1, double c2, double scale, const double *res, double *d, double *z,
+                          hipStream_t stream) {
+    const int g = (int)((n + ch - 1) / ch);
+    hipk_cheb_step_kernel<double><<<hipk_xcd_grid(g), HIPK_THREADS, 0, stream>>>(n, ch, g, c1, c2, scale, res, d, z);
+    HIPK_CHECK_HIP(hipGetLastError());
+    return HIPK_OK;
+}
+void hipk_note_cheb_step(void) {
+    const size_t l = strlen(g_spmv_kernel);
+    snprintf(g_spmv_kernel + l, sizeof(g_spmv_kernel) - l, " + hipk_cheb_step_kernel<double>");
+}
+
 template <typename T>
 static int hipk_cheb_apply_t(const hipk_csr_s *h, int m, const T *dinv, const double *coef, const T *r, T *z, T *work, hipStream_t stream) {
     const int64_t n = h->n_rows;

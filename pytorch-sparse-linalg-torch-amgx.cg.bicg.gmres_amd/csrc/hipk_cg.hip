@@ -2021,6 +2021,9 @@ extern "C" int hipk_dist_pcg_solve(hipk_csr_t A, const hipk_dist_plan *pl, const
     return HIPK_OK;
 }
 
+// Row-partitioned CG with the Chebyshev polynomial preconditioner, and that preconditioner's apply on a row block
+#include "hipk_dist_cheb.h"
+
 #ifdef HIPK_GM_STAMPS
 // diagnostic twin only: per-workgroup phase time sums of the last hipk_cg_mid_kernel launch (hipk_cg_mid.h)
 extern "C" int hipk_debug_mid_stamps(unsigned long long *out, size_t count) {

@@ -466,3 +466,10 @@ static __global__ __launch_bounds__(HIPK_THREADS) void hipk_tile_combine_kernel(
 struct hipk_spmv_profiler;
 int hipk_launch_spmv(const hipk_csr_s *h, const hipk_spmv_args &a, hipStream_t stream,
                      hipk_spmv_profiler *prof = nullptr);
+// hipk_cheb_apply's vector kernels on a row block of n rows in chunks of ch (fp64; hipk_api.hip), for the row-partitioned apply:
+// step 0 (d = c0 * (dinv * r), z = d) and the vector half of a two-launch step (d = (c1 d) + (c2 res), z = scale (z + d));
+// hipk_note_cheb_step appends " + hipk_cheb_step_kernel<double>" to the kernel note, as hipk_cheb_apply does for that form
+int hipk_launch_cheb_init(int64_t n, int ch, double c0, const double *dinv, const double *r, double *d, double *z, hipStream_t stream);
+int hipk_launch_cheb_step(int64_t n, int ch, double c1, double c2, double scale, const double *res, double *d, double *z,
+                          hipStream_t stream);
+void hipk_note_cheb_step(void);

@@ -49,6 +49,8 @@ SYMBOLS = [
     # ... row-partitioned GMRES at restart 32 .. 255
     "hipk_dist_gmres_wide_work_bytes", "hipk_dist_gmres_wide_solve",
     "hipk_dist_pgmres_wide_work_bytes", "hipk_dist_pgmres_wide_solve",
+    # ... the Chebyshev polynomial preconditioner on a row block, and the row-partitioned CG with it
+    "hipk_dist_cheb_work_bytes", "hipk_dist_cheb_apply", "hipk_dist_chebcg_work_bytes", "hipk_dist_chebcg_solve",
     # experimental mailbox exchange provider for that loop
     "hipk_p2p_create", "hipk_p2p_create2", "hipk_p2p_export", "hipk_p2p_connect", "hipk_p2p_destroy", "hipk_p2p_error",
     "hipk_p2p_group_start", "hipk_p2p_group_end", "hipk_p2p_all_gather",
@@ -249,6 +251,13 @@ def lib():
     for name in ("pcg", "pbicgstab", "pgmres", "pgmres_wide"):   # + dinv_ext after the collective struct
         getattr(L, f"hipk_dist_{name}_solve").argtypes = [vp, ctypes.POINTER(DistPlan), ctypes.POINTER(Rccl), vp, vp, vp, vp,
                                                           ctypes.c_size_t, ctypes.POINTER(Params), ctypes.POINTER(Stats), vp]
+    for name in ("cheb", "chebcg"):
+        getattr(L, f"hipk_dist_{name}_work_bytes").argtypes = [ctypes.POINTER(DistPlan)]
+        getattr(L, f"hipk_dist_{name}_work_bytes").restype = ctypes.c_size_t
+    coef = ctypes.POINTER(ctypes.c_double)
+    L.hipk_dist_cheb_apply.argtypes = [vp, ctypes.POINTER(DistPlan), ctypes.POINTER(Rccl), i32, vp, coef, vp, vp, vp, ctypes.c_size_t, vp]
+    L.hipk_dist_chebcg_solve.argtypes = [vp, ctypes.POINTER(DistPlan), ctypes.POINTER(Rccl), i32, vp, coef, vp, vp, vp, ctypes.c_size_t,
+                                         ctypes.POINTER(Params), ctypes.POINTER(Stats), vp]
     L.hipk_p2p_create.argtypes = [ctypes.POINTER(vp), i32, i32, ctypes.c_size_t]
     L.hipk_p2p_create2.argtypes = [ctypes.POINTER(vp), i32, i32, ctypes.c_size_t, i32, i32]
     L.hipk_p2p_export.argtypes = [vp, ctypes.c_char_p]

@@ -354,7 +354,8 @@ class DistStats:
     x_norm: float
     threshold: float
     method: str = ""
-    preconditioner: str = ""     # "jacobi": M = diag(A)^-1 (residual_norm is then ||M (b - A x)||, as on one device)
+    preconditioner: str = ""     # "jacobi": M = diag(A)^-1, "chebyshev": M = p_m(D^-1 A) D^-1 (residual_norm is then ||M (b - A x)||,
+    #                              as on one device)
     solve_ms: float = 0.0        # the C-driven loops: device time of the solve (events around it on the solver's stream)
     breakdown: int = 0           # the C-driven loops: hipk_stats.breakdown (GMRES: a Krylov space closed inside a cycle)
 
@@ -492,16 +493,12 @@ def native_loop_ok(prob: DistProblem) -> bool:
             and part.per * (part.world - 1) < part.g and part.n_local > 0)
 
 
-def _dist_cg_native(prob: DistProblem, x0_local, tol, atol, maxiter, check_every, solver: str = "cg", restart: int = 0,
-                    solve_method: str = "batched", dinv: Optional[torch.Tensor] = None):
-    """One call into libhipk.so runs the whole loop of this rank (csrc/hipk_dist.hip): the host enqueues fixed batches
-    of iterations and reads the device stop word one batch late -- no Python between the kernels.  `dinv`: the Jacobi
-    preconditioner's reciprocal diagonal with its halo tail (n_ext doubles, `jacobi_dinv_ext`) -- the hipk_dist_p*_solve loops."""
+def _native_plan(prob: DistProblem):
+    """(hipk_dist_plan, hipk_rccl, what must stay alive while they are used) of this rank, for the C-driven loops."""
     import os
     from . import _hipk
-    L, part, pl = _hipk.lib(), prob.part, prob.plan
+    part, pl = prob.part, prob.plan
     dev = prob.ops.device
-    n, n_ext = part.n_local, max(prob.n_ext, 1)
     peers = sum(1 for a, b in zip(pl.send_splits, pl.recv_splits) if a or b)
     mode = os.environ.get("HIPK_DIST_HALO", "p2p" if peers <= 4 else "allgather")
     coll = prob.coll_struct()
@@ -509,24 +506,41 @@ def _dist_cg_native(prob: DistProblem, x0_local, tol, atol, maxiter, check_every
         mode = "allgather"          # a provider without send/recv (P2PComm): the halo rides in the gathered slabs
     plan = _hipk.DistPlan()
     plan.rank, plan.world = part.rank, part.world
-    plan.n_local, plan.n_ext, plan.n_global = n, prob.n_ext, part.n_global
+    plan.n_local, plan.n_ext, plan.n_global = part.n_local, prob.n_ext, part.n_global
     plan.chunk_rows, plan.g_red, plan.per = part.ch, part.g, part.per
     plan.halo_mode = 1 if mode == "p2p" else 0
     plan.n_send, plan.n_ghost, plan.slab = pl.n_send, pl.n_ghost, pl.slab
     plan.send_idx_dev = pl.send_idx.data_ptr() if pl.n_send else None
     plan.ghost_src_dev = pl.ghost_src.data_ptr() if pl.n_ghost else None
-    send_off_d, dest_off_d = pl.send_off.to(dev).contiguous(), pl.dest_off.to(dev).contiguous()   # fused exchanges (kept alive below)
+    send_off_d, dest_off_d = pl.send_off.to(dev).contiguous(), pl.dest_off.to(dev).contiguous()   # fused exchanges
     plan.send_off_dev, plan.dest_off_dev = send_off_d.data_ptr(), dest_off_d.data_ptr()
     sc = (ctypes.c_int32 * part.world)(*[int(v) for v in pl.send_splits])
     rc = (ctypes.c_int32 * part.world)(*[int(v) for v in pl.recv_splits])
     plan.send_counts, plan.recv_counts = sc, rc
     sf = (ctypes.c_int64 * part.world)(*[int(v) for v in pl.send_first])
     plan.send_first = sf
+    return plan, coll, (send_off_d, dest_off_d, sc, rc, sf)
+
+
+def _dist_cg_native(prob: DistProblem, x0_local, tol, atol, maxiter, check_every, solver: str = "cg", restart: int = 0,
+                    solve_method: str = "batched", dinv: Optional[torch.Tensor] = None, cheb=None):
+    """One call into libhipk.so runs the whole loop of this rank (csrc/hipk_dist.hip): the host enqueues fixed batches
+    of iterations and reads the device stop word one batch late -- no Python between the kernels.  `dinv`: the Jacobi
+    preconditioner's reciprocal diagonal with its halo tail (n_ext doubles, `jacobi_dinv_ext`) -- the hipk_dist_p*_solve loops.
+    `cheb` = (degree, coefficient array) with `dinv`: the Chebyshev polynomial preconditioner (hipk_dist_chebcg_solve, cg only)."""
+    from . import _hipk
+    L, part = _hipk.lib(), prob.part
+    dev = prob.ops.device
+    n, n_ext = part.n_local, max(prob.n_ext, 1)
+    plan, coll, _keep = _native_plan(prob)
     x = prob.ops.zeros(n_ext)
     if x0_local is not None:
         x[:n] = x0_local
     pre = "p" if dinv is not None else ""
-    if pre:
+    if cheb is not None:
+        assert solver == "cg" and dinv is not None and len(cheb[1]) == 2 * int(cheb[0]) + 2
+        pre, solver = "", "chebcg"
+    if dinv is not None:
         assert dinv.dtype == torch.float64 and dinv.numel() == max(prob.n_ext, 1) and dinv.device == x.device and dinv.is_contiguous()
     if solver == "gmres" and int(restart) > 31:
         solver = "gmres_wide"       # restart 32 .. 255: H in the workspace, one all-gather per CGS pass (hipk_dist_gmres_wide_solve)
@@ -546,7 +560,7 @@ def _dist_cg_native(prob: DistProblem, x0_local, tol, atol, maxiter, check_every
         prm.gpu_tolerances = 1          # the reference's `device.type == 'cuda'` tolerance branch (TSL:737-740)
     st = _hipk.Stats()
     with torch.cuda.device(dev):
-        pre_args = (dinv.data_ptr(),) if pre else ()
+        pre_args = (int(cheb[0]), dinv.data_ptr(), cheb[1]) if cheb is not None else (dinv.data_ptr(),) if pre else ()
         rcode = solve_fn(prob.A["h"], ctypes.byref(plan), ctypes.byref(coll), *pre_args, prob.b.data_ptr(), x.data_ptr(),
                          work.data_ptr(), wb, ctypes.byref(prm), ctypes.byref(st),
                          torch.cuda.current_stream(dev).cuda_stream)
@@ -554,8 +568,9 @@ def _dist_cg_native(prob: DistProblem, x0_local, tol, atol, maxiter, check_every
     if getattr(prob, "p2p", None) is not None and prob.p2p.failed():
         raise RuntimeError("hipk_p2p: a rank never published its part of an exchange (wait bound hit); results discarded")
     return x[:n], int(st.info), DistStats(int(st.iterations), int(st.matvecs), int(st.info), st.b_norm, st.residual_norm,
-                                          st.x_norm, st.threshold, preconditioner="jacobi" if pre else "", solve_ms=float(st.solve_ms),
-                                          breakdown=int(st.breakdown))
+                                          st.x_norm, st.threshold,
+                                          preconditioner="chebyshev" if cheb is not None else "jacobi" if pre else "",
+                                          solve_ms=float(st.solve_ms), breakdown=int(st.breakdown))
 
 
 def _need_native(prob: DistProblem, what: str) -> None:
@@ -582,6 +597,31 @@ def jacobi_dinv_ext(prob: DistProblem, dinv: torch.Tensor) -> torch.Tensor:
         if part.world > 1:
             prob.halo_exchange(ext)
     return ext
+
+
+def dist_cheb_apply(prob: DistProblem, degree: int, dinv: torch.Tensor, coef, v_local: torch.Tensor) -> torch.Tensor:
+    """This rank's slice of z = p_m(D^-1 A) D^-1 v for the GLOBAL system (`hipk_dist_cheb_apply`), v_local the rank's slice of v:
+    degree halo exchanges on the current stream, no reduction.  `dinv` (`jacobi_dinv_ext`): n_ext doubles; `coef`: the ctypes
+    array of 2 * degree + 2 doubles of a `ChebyshevPreconditioner`.  Every rank calls it.  Concatenated over the ranks the result
+    equals the single-device apply bit for bit."""
+    _need_native(prob, "the row-partitioned Chebyshev apply on device vectors")
+    from . import _hipk
+    L, n, n_ext = _hipk.lib(), prob.part.n_local, max(prob.n_ext, 1)
+    dev = prob.ops.device
+    assert v_local.dtype == torch.float64 and v_local.numel() == n and v_local.device == dinv.device
+    assert dinv.dtype == torch.float64 and dinv.numel() == n_ext and dinv.is_contiguous() and len(coef) == 2 * int(degree) + 2
+    plan, coll, _keep = _native_plan(prob)
+    r, z = prob.ops.zeros(n_ext), prob.ops.zeros(n_ext)
+    r[:n] = v_local
+    wb = int(L.hipk_dist_cheb_work_bytes(ctypes.byref(plan)))
+    work = torch.empty(wb, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        rcode = L.hipk_dist_cheb_apply(prob.A["h"], ctypes.byref(plan), ctypes.byref(coll), int(degree), dinv.data_ptr(), coef,
+                                       r.data_ptr(), z.data_ptr(), work.data_ptr(), wb, torch.cuda.current_stream(dev).cuda_stream)
+    _hipk._check(rcode, "hipk_dist_cheb_apply")
+    if getattr(prob, "p2p", None) is not None and prob.p2p.failed():
+        raise RuntimeError("hipk_p2p: a rank never published its part of an exchange (wait bound hit); results discarded")
+    return z[:n].clone()
 
 
 def dist_bicgstab(prob: DistProblem, x0_local: Optional[torch.Tensor] = None, *, tol: float = 1e-5, atol: float = 0.0,
@@ -611,15 +651,17 @@ def dist_gmres(prob: DistProblem, x0_local: Optional[torch.Tensor] = None, *, to
 
 
 def dist_cg(prob: DistProblem, x0_local: Optional[torch.Tensor] = None, *, tol: float = 1e-5, atol: float = 0.0,
-            maxiter: Optional[int] = None, check_every: int = 32, dinv: Optional[torch.Tensor] = None):
+            maxiter: Optional[int] = None, check_every: int = 32, dinv: Optional[torch.Tensor] = None, cheb=None):
     """Row-partitioned CG; returns (x_local, info, DistStats). Same stopping rule, same `info` rule and,
     bit for bit, the same iterates as the single-device solve.  On GPUs with direct RCCL the whole loop runs in C
     (`_dist_cg_native`); the Python loop below is the backend-agnostic form (CPU test double, torch.distributed
     collectives, ranks without rows).  `dinv` (`jacobi_dinv_ext`): the Jacobi preconditioned loop (`hipk_dist_pcg_solve`), bit
-    for bit `cg(A, b, M=JacobiPreconditioner(A))`; it runs in C only."""
+    for bit `cg(A, b, M=JacobiPreconditioner(A))`; it runs in C only.  `cheb` = (degree, coefficient array of a
+    `ChebyshevPreconditioner`) with that `dinv`: the Chebyshev polynomial preconditioner of the global system
+    (`hipk_dist_chebcg_solve`), bit for bit `cg(A, b, M=ChebyshevPreconditioner(A, ...))`; C only as well."""
     if dinv is not None:
-        _need_native(prob, "dist_cg with a Jacobi preconditioner")
-        return _dist_cg_native(prob, x0_local, tol, atol, maxiter, min(check_every, 16), dinv=dinv)
+        _need_native(prob, "dist_cg with a Chebyshev preconditioner" if cheb is not None else "dist_cg with a Jacobi preconditioner")
+        return _dist_cg_native(prob, x0_local, tol, atol, maxiter, min(check_every, 16), dinv=dinv, cheb=cheb)
     if native_loop_ok(prob):
         return _dist_cg_native(prob, x0_local, tol, atol, maxiter, min(check_every, 16))
     ops, part, group = prob.ops, prob.part, prob.group
@@ -720,8 +762,18 @@ class RowBlockCSR:
     or from the replicated global matrix; both give the same bits, those of the single-device solve with
     `M=JacobiPreconditioner(A_global)`.  Its reciprocal diagonal with the halo entries is formed on the first solve with it and
     reused while the same preconditioner object is passed.  The Jacobi solves run on the C-driven loops only
-    (`hipk_dist_p*_solve`; RuntimeError without them).  Any other `M` (callables, `BlockJacobiPreconditioner`, matrices),
-    PyTrees, complex operands and autograd are not available on this operand (ValueError)."""
+    (`hipk_dist_p*_solve`; RuntimeError without them).
+
+    `cg` also takes a `ChebyshevPreconditioner` of the global system: `ChebyshevPreconditioner.for_row_block(A, degree=3)`, which
+    every rank builds from its block (Gershgorin bound and scale agreed over the ranks), or a `ChebyshevPreconditioner` of the
+    replicated global matrix.  The solve runs `hipk_dist_chebcg_solve` -- m + 2 collective launches per iteration for degree m,
+    halo exchanges and two all-gathers, bit for bit `cg(A_global, b, M=ChebyshevPreconditioner(A_global, ...))` -- on the
+    C-driven loop only (RuntimeError without it); `bicgstab` and `gmres` refuse it (ValueError).  dinv with its halo tail is
+    cached per preconditioner object as for Jacobi; after a solve the preconditioner's `applies` / `spmvs` have grown by
+    iterations + 2 applies.  The `for_row_block` object is also callable on the rank's slice of a vector (`chebyshev_apply`).
+
+    Any other `M` (callables, `BlockJacobiPreconditioner`, matrices), PyTrees, complex operands and autograd are not available
+    on this operand (ValueError)."""
     _hipk_row_block = True
 
     def __init__(self, crow_local: torch.Tensor, col_global: torch.Tensor, values: torch.Tensor, n_global: int, *,
@@ -745,7 +797,8 @@ class RowBlockCSR:
         self.dtype, self.device = values.dtype, values.device
         self.group = group
         self._ops, self._problem_cls, self._prob = ops, problem_cls, None
-        self._jacobi = None          # (preconditioner, its dinv tensor, dinv with the halo tail): the cache of `_jacobi_ext`
+        self._jacobi = None          # (preconditioner -- Jacobi or Chebyshev --, its dinv tensor, dinv with the halo tail): the
+        #                              cache of `_jacobi_ext`; the Chebyshev coefficient array is the preconditioner's own `_coef`
         self.last_stats: Optional[DistStats] = None
 
     # ---- which rows a rank owns
@@ -781,9 +834,22 @@ class RowBlockCSR:
         self._prob.b = b_local.contiguous()
         return self._prob
 
-    def check_preconditioner(self, M) -> None:
-        """ValueError unless M is a JacobiPreconditioner of this global system (the one `M` a row-partitioned solve takes)."""
-        from .module_a.preconditioners import JacobiPreconditioner
+    def check_preconditioner(self, M, method: Optional[str] = None) -> None:
+        """ValueError unless M is a preconditioner of this global system that the row-partitioned `method` takes: a
+        JacobiPreconditioner (all three solvers) or a ChebyshevPreconditioner (cg only), of this operand or of the replicated
+        global matrix."""
+        from .module_a.preconditioners import ChebyshevPreconditioner, JacobiPreconditioner
+        if isinstance(M, ChebyshevPreconditioner):
+            if method is not None and method != "cg":
+                raise ValueError(f"the row-partitioned ChebyshevPreconditioner runs under cg only (got {method})")
+            rows = getattr(M, "row_range", None)
+            if tuple(M.shape) != self.shape:
+                raise ValueError(f"ChebyshevPreconditioner of shape {tuple(M.shape)} for the {self.shape[0]} x {self.shape[1]} system")
+            if rows is not None and (tuple(rows) != (self.part.row0, self.part.row1) or M.dinv.numel() != self.part.n_local):
+                raise ValueError(f"ChebyshevPreconditioner of rows {tuple(rows)} for the row block [{self.part.row0}, {self.part.row1})")
+            if rows is None and M.dinv.numel() != self.shape[0]:
+                raise ValueError(f"ChebyshevPreconditioner with {M.dinv.numel()} diagonal entries for the {self.shape[0]}-row system")
+            return
         if not isinstance(M, JacobiPreconditioner):
             raise ValueError("preconditioners other than JacobiPreconditioner are not available on a RowBlockCSR (row-partitioned) "
                              f"operand (got {type(M).__name__})")
@@ -801,10 +867,35 @@ class RowBlockCSR:
             c = self._jacobi = (M, M.dinv, jacobi_dinv_ext(prob, M.dinv.detach()))
         return c[2]
 
+    def chebyshev_apply(self, M, v_local: torch.Tensor) -> torch.Tensor:
+        """This rank's slice of M v for a `ChebyshevPreconditioner.for_row_block` object of this operand (collective).  Device
+        vectors: `hipk_dist_cheb_apply`.  CPU vectors (an explicit `ops` backend): the class's torch steps, `halo_exchange` before
+        each product and the backend's SpMV in its residual form as the product."""
+        self.check_preconditioner(M)
+        prob = self._prob if self._prob is not None else self.problem(v_local.to(torch.float64))
+        if isinstance(prob.ops, HipOps):
+            _need_native(prob, "the row-partitioned Chebyshev apply on device vectors")     # before any collective
+            return dist_cheb_apply(prob, M.degree, self._jacobi_ext(prob, M), M._coef, v_local.contiguous())
+        n, ops = self.part.n_local, prob.ops
+        dinv = M.dinv.to(torch.float64)
+        c = lambda x: torch.tensor(x, dtype=torch.float64)       # noqa: E731
+        z_ext, res = ops.zeros(max(prob.n_ext, 1)), ops.zeros(max(n, 1))
+        d = c(M.c0) * (dinv * v_local)
+        z_ext[:n] = d
+        for k in range(M.degree):
+            if self.part.world > 1:
+                prob.halo_exchange(z_ext)
+            if n:
+                ops.spmv(prob.A, z_ext, res, MODE_RESID, bsub=v_local)
+            d = (c(M.c1[k]) * d) + (c(M.c2[k]) * (dinv * res[:n]))
+            z_ext[:n] = z_ext[:n] + d
+        z = z_ext[:n].clone()
+        return c(M.scale) * z if M.scale != 1.0 else z
+
     def solve(self, method: str, b_local, x0_local=None, *, tol=1e-5, atol=0.0, maxiter=None, restart=20, solve_method="batched",
               M=None):
         if M is not None:
-            self.check_preconditioner(M)
+            self.check_preconditioner(M, method)
         if not isinstance(b_local, torch.Tensor) or b_local.ndim != 1 or b_local.numel() != self.part.n_local:
             raise ValueError(f"RowBlockCSR: b must be this rank's slice of the right-hand side ({self.part.n_local} entries, rows "
                              f"[{self.part.row0}, {self.part.row1}))")
@@ -816,13 +907,19 @@ class RowBlockCSR:
             raise ValueError(f"Method '{method}' not available on a RowBlockCSR operand. Use: ['cg', 'bicgstab', 'gmres']")
         prob = self.problem(b_local.detach().to(torch.float64))
         x0 = None if x0_local is None else x0_local.detach().to(torch.float64)
-        dinv = None
+        dinv = cheb = None
         if M is not None:
+            from .module_a.preconditioners import ChebyshevPreconditioner
+            kind = "Chebyshev" if isinstance(M, ChebyshevPreconditioner) else "Jacobi"
             # before any collective of the preconditioner: the decision is the same on every rank (native_loop_ok is)
-            _need_native(prob, f"a Jacobi-preconditioned row-partitioned {method}")
+            _need_native(prob, f"a {kind}-preconditioned row-partitioned {method}")
             dinv = self._jacobi_ext(prob, M)
+            cheb = (M.degree, M._coef) if kind == "Chebyshev" else None
         if method == "cg":
-            x, info, st = dist_cg(prob, x0, tol=tol, atol=atol, maxiter=maxiter, dinv=dinv)
+            x, info, st = dist_cg(prob, x0, tol=tol, atol=atol, maxiter=maxiter, dinv=dinv, cheb=cheb)
+            if cheb is not None:      # the applies of this solve: one per iteration, z0 = M r0 and the final M (b - A x)
+                M.applies += st.iterations + 2
+                M.spmvs += (st.iterations + 2) * M.degree
         elif method == "bicgstab":
             x, info, st = dist_bicgstab(prob, x0, tol=tol, atol=atol, maxiter=maxiter, dinv=dinv)
         else:
@@ -834,7 +931,7 @@ class RowBlockCSR:
 
     def relative_residual(self) -> float:
         """||b - A x|| / ||b|| of the GLOBAL system for the last solve's x (its true-residual epilogue, TSL:1007-1014 / 766-773);
-        after a Jacobi-preconditioned solve ||M (b - A x)|| / ||b||, the quantity that epilogue tests (TSL:1007)."""
+        after a Jacobi- or Chebyshev-preconditioned solve ||M (b - A x)|| / ||b||, the quantity that epilogue tests (TSL:1007)."""
         st = self.last_stats
         return float("nan") if st is None else (st.residual_norm / st.b_norm if st.b_norm > 0 else float("inf"))
 

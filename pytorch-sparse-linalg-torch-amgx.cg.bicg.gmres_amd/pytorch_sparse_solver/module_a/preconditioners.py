@@ -5,7 +5,8 @@ works on every path and with the reference's own solvers; on the HIP fast path `
 preconditioned iteration device-resident (`hipk_pcg_solve`: the scaling is fused into the update and direction
 kernels, 16 n extra bytes per iteration instead of a separate pass) -- SURVEY 8f-3.  On a `RowBlockCSR` (one rank's rows of a
 global system) `JacobiPreconditioner(A)` holds the rank's slice of the reciprocal diagonal, and the row-partitioned
-cg / bicgstab / gmres run it in their C-driven loops (`hipk_dist_p*_solve`).
+cg / bicgstab / gmres run it in their C-driven loops (`hipk_dist_p*_solve`).  `ChebyshevPreconditioner.for_row_block(A_rb)` is the
+Chebyshev polynomial of the global system on such an operand, for the row-partitioned cg (`hipk_dist_chebcg_solve`).
 """
 import ctypes
 import math
@@ -234,7 +235,10 @@ class ChebyshevPreconditioner:
     stream without synchronisation: one launch per step where the matrix's SpMV kernel has the Chebyshev epilogue, else SpMV +
     a vector kernel (same bits).  The handle is `_hipk.handle_for(A)`, the one a solve of the same `A` holds; the apply takes no
     lock and uses none of the handle's reduction scratch.  `applies` / `spmvs` count calls and their SpMVs;
-    `get_last_stats().matvecs` keeps the reference's meaning, the solver's own applications of A."""
+    `get_last_stats().matvecs` keeps the reference's meaning, the solver's own applications of A.
+
+    On a `RowBlockCSR` the constructor raises; `ChebyshevPreconditioner.for_row_block(A_rb, ...)` builds the preconditioner of the
+    global system there (every rank calls it), for `cg(A_rb, b_local, M=P)`."""
 
     def __init__(self, A: torch.Tensor, degree: int = 3, lmax=None, lmin=None, ratio: float = 30.0, normalize: bool = True):
         if getattr(A, "_hipk_row_block", False) is True:
@@ -244,7 +248,7 @@ class ChebyshevPreconditioner:
             raise ValueError("ChebyshevPreconditioner needs a square matrix tensor")
         if not 1 <= int(degree) <= 32:
             raise ValueError("degree must be in [1, 32]")
-        self.degree = m = int(degree)
+        self.degree = int(degree)
         self.shape = tuple(A.shape)
         self._A = A.detach()
         d = _diagonal(self._A)
@@ -253,6 +257,13 @@ class ChebyshevPreconditioner:
         self.dinv = torch.reciprocal(d)
         if lmax is None:
             lmax = float((self._abs_row_sums().to(torch.float64) / d.to(torch.float64)).max())
+        self._set_coefficients(lmax, lmin, ratio, normalize, float(self.dinv.max()) if normalize else 0.0)
+        self._cpu = None      # (spec SpMV, dinv) per dtype, built on the first CPU apply
+        self._dev = None      # (handle, dinv) of the first device apply
+
+    def _set_coefficients(self, lmax, lmin, ratio, normalize, dinv_max) -> None:
+        """lmin, lmax, c0, c1, c2, scale and the counters, from the spectral bounds and max_i dinv_i (host doubles)."""
+        m = self.degree
         lmax = float(lmax)
         lmin = lmax / float(ratio) if lmin is None else float(lmin)
         if not 0.0 < lmin < lmax:
@@ -274,12 +285,16 @@ class ChebyshevPreconditioner:
                 dd = self.c1[k] * dd + self.c2[k]
                 zz = zz + dd
             bound = max(zz, (1 + 1 / math.cosh(m * math.acosh(sigma))) / lmin)
-            self.scale = 1 / (bound * float(self.dinv.max()))
+            self.scale = 1 / (bound * dinv_max)
         self._coef = (ctypes.c_double * (2 * m + 2))(self.c0, *self.c1, *self.c2, self.scale)
         self.applies = 0
         self.spmvs = 0
-        self._cpu = None      # (spec SpMV, dinv) per dtype, built on the first CPU apply
-        self._dev = None      # (handle, dinv) of the first device apply
+
+    @classmethod
+    def for_row_block(cls, A, degree: int = 3, lmax=None, lmin=None, ratio: float = 30.0, normalize: bool = True):
+        """The preconditioner of the GLOBAL system a `RowBlockCSR` is a row block of, for the row-partitioned `cg` -- see
+        `RowBlockChebyshevPreconditioner`.  Every rank of the operand's process group calls it."""
+        return RowBlockChebyshevPreconditioner(A, degree, lmax, lmin, ratio, normalize)
 
     def _abs_row_sums(self) -> torch.Tensor:
         A = self._A
@@ -328,6 +343,91 @@ class ChebyshevPreconditioner:
             if v.dtype not in (torch.float64, torch.float32):
                 raise ValueError(f"ChebyshevPreconditioner applies to float64 / float32 vectors, not {v.dtype}")
             z = self._apply_torch(v)
+        self.applies += 1
+        self.spmvs += self.degree
+        return z
+
+
+def _row_block_abs_row_sums(A) -> torch.Tensor:
+    """sum_j |a_ij| of a RowBlockCSR's rows, each row summed left to right in CSR order whatever the device: the bits
+    `ChebyshevPreconditioner._abs_row_sums` gives for the same rows of the global matrix on CPU tensors."""
+    crow, val = A.crow.to(torch.int64), A.val
+    n = A.part.n_local
+    s = torch.zeros(n, dtype=val.dtype, device=val.device)
+    if n == 0 or val.numel() == 0:
+        return s
+    lens = crow[1:] - crow[:-1]
+    K = int(lens.max())
+    if K > 64:        # long rows: the sequential CPU sum
+        rows = torch.repeat_interleave(torch.arange(n), lens.cpu())
+        return torch.zeros(n, dtype=val.dtype).index_add_(0, rows, val.abs().cpu()).to(val.device)
+    av = val.abs()
+    for k in range(K):
+        has = lens > k
+        s = torch.where(has, s + av[torch.where(has, crow[:-1] + k, 0)], s)
+    return s
+
+
+class RowBlockChebyshevPreconditioner(ChebyshevPreconditioner):
+    """`ChebyshevPreconditioner.for_row_block(A_rb, ...)`: the Chebyshev preconditioner of the GLOBAL system on a `RowBlockCSR`,
+    for `cg(A_rb, b_local, M=P)` -- bit for bit `cg(A, b, M=ChebyshevPreconditioner(A, ...))` on one device, for any rank count.
+
+    Every rank of the operand's process group constructs it (one MAX all-reduce: the Gershgorin `lmax` and max_i dinv_i are
+    maxima over the ranks' rows, and a zero or negative diagonal entry on ANY rank raises on every rank); without a process group
+    the world is 1 and nothing is exchanged.  `degree`, `lmin`, `lmax`, `c0`, `c1`, `c2`, `scale` are on every rank those of
+    `ChebyshevPreconditioner(A_global, ...)` with the same arguments; `shape` is the global shape, `row_range` the rank's rows,
+    `dinv` the reciprocal diagonal of those rows.
+
+    `P(v_local)` is collective too: every rank passes its slice of a global vector and gets its slice of M v (m halo exchanges,
+    no reduction).  Device vectors run `hipk_dist_cheb_apply`; CPU vectors (an operand built with an explicit `ops` backend) the
+    torch steps of the class around the backend's SpMV."""
+
+    def __init__(self, A, degree: int = 3, lmax=None, lmin=None, ratio: float = 30.0, normalize: bool = True):
+        if getattr(A, "_hipk_row_block", False) is not True:
+            raise ValueError("ChebyshevPreconditioner.for_row_block needs a RowBlockCSR")
+        if not 1 <= int(degree) <= 32:
+            raise ValueError("degree must be in [1, 32]")
+        self.degree = int(degree)
+        self.shape = tuple(A.shape)
+        self.row_range = (A.part.row0, A.part.row1)
+        self._A = A
+        d = _row_block_diagonal(A)
+        have = d.numel() > 0
+        bad = bool((d <= 0).any())
+        loc_lmax = loc_dinv = 0.0
+        if not bad and have:
+            if lmax is None:
+                loc_lmax = float((_row_block_abs_row_sums(A).to(torch.float64) / d.to(torch.float64)).max())
+            if normalize:
+                loc_dinv = float(torch.reciprocal(d).max())
+        bad, loc_lmax, loc_dinv = self._max_over_ranks(A, [1.0 if bad else 0.0, loc_lmax, loc_dinv])
+        if bad:
+            raise ValueError("ChebyshevPreconditioner: zero or negative entry on the diagonal (of some rank's rows of the "
+                             "RowBlockCSR)")
+        self.dinv = torch.reciprocal(d)
+        self._set_coefficients(loc_lmax if lmax is None else lmax, lmin, ratio, normalize, loc_dinv)
+        self._cpu = self._dev = None
+
+    @staticmethod
+    def _max_over_ranks(A, values):
+        import torch.distributed as dist
+        if A.part.world == 1 or not dist.is_initialized():
+            return values
+        dev = A.val.device if dist.get_backend(A.group) == "nccl" else torch.device("cpu")
+        t = torch.tensor(values, dtype=torch.float64, device=dev)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX, group=A.group)
+        return t.tolist()
+
+    def __call__(self, v):
+        A = self._A
+        n = A.part.n_local
+        if not isinstance(v, torch.Tensor) or v.shape != (n,):
+            raise ValueError(f"ChebyshevPreconditioner of rows {self.row_range} applied to a vector of shape "
+                             f"{tuple(getattr(v, 'shape', ()))} (this rank's slice has {n} entries)")
+        if v.dtype != torch.float64 or v.device != A.val.device:
+            raise ValueError(f"the row-partitioned ChebyshevPreconditioner applies to float64 vectors on {A.val.device}, not "
+                             f"{v.dtype} on {v.device}")
+        z = A.chebyshev_apply(self, v.detach())
         self.applies += 1
         self.spmvs += self.degree
         return z

@@ -506,10 +506,12 @@ def _is_row_block(A) -> bool:
 def _dist_solve(kind: str, A, b, x0, tol, atol, maxiter, M, restart=20, solve_method='batched'):
     """cg / bicgstab / gmres on a RowBlockCSR operand: the row-partitioned solvers (distributed.py, csrc/hipk_dist.hip) behind the
     reference's call surface.  Returns this rank's slice of x and the (rank-independent) info.  `M` may be a JacobiPreconditioner
-    (of the operand or of the global matrix): the Jacobi forms of the row-partitioned loops."""
+    (of the operand or of the global matrix): the Jacobi forms of the row-partitioned loops; or, under cg, a
+    ChebyshevPreconditioner (`ChebyshevPreconditioner.for_row_block(A)`, or of the global matrix): hipk_dist_chebcg_solve."""
+    from .preconditioners import ChebyshevPreconditioner
     if M is _identity:
         M = None
-    if M is not None and _jacobi_of(M) is None:
+    if M is not None and _jacobi_of(M) is None and not isinstance(M, ChebyshevPreconditioner):
         raise ValueError(f"{kind}: preconditioners other than JacobiPreconditioner are not available on a RowBlockCSR "
                          f"(row-partitioned) operand")
     if kind == 'gmres' and solve_method not in ('batched', 'incremental'):
