@@ -142,6 +142,17 @@ const char *hipk_last_spmv_kernel(void);
  * the solve back (its workgroups were not all resident), the chain shows it: "hipk_cg_mid_kernel<double,5,1,false> ->
  * launch sequence".  "" before the first solve. */
 const char *hipk_last_solve_path(void);
+/* The FORM that solve finished in: which variant of the path's kind, at the resolution of the dispatch.  A one-launch kernel
+ * reports the instantiation of its last launch, e.g. "hipk_cg_solve_lds_kernel<double,true,false>" (T, LOCAL, PRE; LOCAL false
+ * also after the kernel asked for agent-scope hand-offs), "hipk_gm_solve_lds_kernel<float,false>", "hipk_gm_cycle_small_kernel<double>"
+ * or the mid kernel's name as the path gives it.  A launch sequence reports which one, e.g. "cg two-launch: hipk_cg2_spmv_kernel<double,1280>
+ * + hipk_cg2_update_kernel", "cg three-launch, small", "bicgstab five-launch, Jacobi", "gmres restart > 31" (DESIGN.md 8b lists
+ * them) -- also when the loop ran no iteration.  hipk_{cg,bicgstab}_solve_multi and hipk_dist_* report their path string.
+ * hipk_solve_form_name(i), 0 <= i < hipk_solve_form_count(), enumerates every form of the single-device solvers (no GPU
+ * needed); NULL outside that range. */
+const char *hipk_last_solve_form(void);
+int hipk_solve_form_count(void);
+const char *hipk_solve_form_name(int i);
 /* mode 0: automatic (default); 1: never use the coded forms (A/B measurements, parity tests).
  * Environment: HIPK_SPMV_CODED=0 at creation time skips building the coded forms altogether,
  * HIPK_SPMV_OFFSET_CODED=0 only the offset-coded one. */

@@ -46,8 +46,8 @@
 #define ORC_MAX_PARTS 2048
 #define ORC_BASE_CHUNK 2048
 #define ORC_LONG_ROW 32
-#define ORC_MAXM 127 /* largest GMRES restart (the reference accepts any, TSL:641-644) */
-#define ORC_LD 128
+#define ORC_MAXM 255 /* largest GMRES restart (the reference accepts any, TSL:641-644) */
+#define ORC_LD 256
 #define ORC_EPS64 2.220446049250313e-16 /* torch.finfo(torch.float64).eps */
 #define ORC_EPS32 1.1920928955078125e-07 /* torch.finfo(torch.float32).eps */
 #ifdef ORC_F32

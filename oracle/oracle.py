@@ -270,7 +270,7 @@ def gmres(crow, col, val, b, x0=None, tol=1e-5, atol=0.0, restart=20, maxiter=No
                          -1 if maxiter is None else int(maxiter), method, 1 if gpu_tolerances else 0,
                          ctypes.byref(st))
     if rc != 0:
-        raise ValueError("oracle gmres supports 1 <= restart <= 127")
+        raise ValueError("oracle gmres supports 1 <= restart <= 255")
     return _result(x, st)
 
 
@@ -295,7 +295,7 @@ def gmres_jacobi(crow, col, val, dinv, b, x0=None, tol=1e-5, atol=0.0, restart=2
                                 int(restart), -1 if maxiter is None else int(maxiter), method,
                                 1 if gpu_tolerances else 0, ctypes.byref(st))
     if rc != 0:
-        raise ValueError("oracle gmres supports 1 <= restart <= 127")
+        raise ValueError("oracle gmres supports 1 <= restart <= 255")
     return _result(x, st)
 
 
@@ -360,7 +360,7 @@ def gmres32(crow, col, val, b, x0=None, tol=1e-5, atol=0.0, restart=20, maxiter=
                            -1 if maxiter is None else int(maxiter), method, 1 if gpu_tolerances else 0,
                            ctypes.byref(st))
     if rc != 0:
-        raise ValueError("oracle gmres supports 1 <= restart <= 127")
+        raise ValueError("oracle gmres supports 1 <= restart <= 255")
     return _result(x, st)
 
 
@@ -385,5 +385,5 @@ def gmres_jacobi32(crow, col, val, dinv, b, x0=None, tol=1e-5, atol=0.0, restart
                                   int(restart), -1 if maxiter is None else int(maxiter), method,
                                   1 if gpu_tolerances else 0, ctypes.byref(st))
     if rc != 0:
-        raise ValueError("oracle gmres supports 1 <= restart <= 127")
+        raise ValueError("oracle gmres supports 1 <= restart <= 255")
     return _result(x, st)

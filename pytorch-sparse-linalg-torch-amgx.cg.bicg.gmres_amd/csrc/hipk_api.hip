@@ -3,6 +3,7 @@
 
 #include "hipk_blas1.h"
 #include "hipk_common.h"
+#include "hipk_forms.h"
 #include "hipk_solve.h"
 #include "hipk_spmv.h"
 #include "hipk_coded.h"
@@ -30,7 +31,13 @@ void hipk_set_solve_path(const char *from, const char *last) {
         snprintf(g_solve_path, sizeof(g_solve_path), "%s -> %s", from, last);
     else
         snprintf(g_solve_path, sizeof(g_solve_path), "%s", last);
+    hipk_set_solve_form(g_solve_path);   // until the solver names its form (hipk_*_solve_multi, hipk_dist_*: the path)
 }
+static thread_local char g_solve_form[160] = "";
+extern "C" const char *hipk_last_solve_form(void) { return g_solve_form; }
+void hipk_set_solve_form(const char *form) { snprintf(g_solve_form, sizeof(g_solve_form), "%s", form); }
+extern "C" int hipk_solve_form_count(void) { return (int)(sizeof(hipk_solve_forms) / sizeof(hipk_solve_forms[0])); }
+extern "C" const char *hipk_solve_form_name(int i) { return i >= 0 && i < hipk_solve_form_count() ? hipk_solve_forms[i].name : nullptr; }
 #define HIPK_NOTE_KERNEL(...) snprintf(g_spmv_kernel, sizeof(g_spmv_kernel), __VA_ARGS__)
 #if __has_include("hipk_build_id.h")   // written by the Makefile (sha1 over the sources); absent in ad-hoc compiles of this file
 #include "hipk_build_id.h"

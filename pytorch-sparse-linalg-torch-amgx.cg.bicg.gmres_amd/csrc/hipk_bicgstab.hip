@@ -685,7 +685,7 @@ extern "C" size_t hipk_pbicgstab_work_bytes(int64_t n, int dtype) {
 // the one-launch instantiations the dispatch below selects (hipk_mid_pick), each with the name hipk_last_solve_path reports
 #define HIPK_MID_ROW(W, PRE)                                                                                               \
     {W, 1, PRE, hipk_bi_mid_kernel<T, W, PRE>,                                                                             \
-     sizeof(T) == 8 ? "hipk_bi_mid_kernel<double," #W "," #PRE ">" : "hipk_bi_mid_kernel<float," #W "," #PRE ">"}
+     HIPK_FORM_OF_T(T, "hipk_bi_mid_kernel<", #W "," #PRE ">")}
 template <typename T>
 static const hipk_mid_entry<hipk_bi_mid_args> hipk_bi_mid_table[] = {
     HIPK_MID_ROW(5, false), HIPK_MID_ROW(7, false), HIPK_MID_ROW(9, false), HIPK_MID_ROW(12, false),
@@ -880,6 +880,7 @@ static int hipk_bicgstab_solve_t(hipk_csr_s *A, const T *dinv, const T *b, T *x,
     hipk_bi_path_lds(path, A, prm, ext, maxiter, mid_loop, it, lds_loop_failed);
     const bool lds_spread = path.spread;
     bool lds_loop = path.lds_loop;
+    const char *lds_form = "";
     if (lds_loop) {
         bool local = path.local;   // a -2 (spread over several XCDs): agent-scope hand-offs
         hipk_bi_lds_args<T> ca;
@@ -929,8 +930,15 @@ static int hipk_bicgstab_solve_t(hipk_csr_s *A, const T *dinv, const T *b, T *x,
             if ((rc = hipk_launch_dot_parts(n, rhat, r, A->dtype, part_rhr, stream)) != HIPK_OK) return rc;
         }
         lds_loop = run == HIPK_OK;
+        // the instantiation of the last launch (hipk_last_solve_form)
+        lds_form = local ? (PRE ? HIPK_FORM_OF_T(T, "hipk_bi_solve_lds_kernel<", "true,true>") : HIPK_FORM_OF_T(T, "hipk_bi_solve_lds_kernel<", "true,false>"))
+                         : (PRE ? HIPK_FORM_OF_T(T, "hipk_bi_solve_lds_kernel<", "false,true>") : HIPK_FORM_OF_T(T, "hipk_bi_solve_lds_kernel<", "false,false>"));
     }
     hipk_set_solve_path(handed, mid_loop ? mid->name : lds_loop ? "hipk_bi_solve_lds_kernel" : "launch sequence");
+    hipk_set_solve_form(mid_loop ? mid->name
+                        : lds_loop ? lds_form
+                        : small ? (ext ? HIPK_FORM("bicgstab five-launch, small, callback M") : PRE ? HIPK_FORM("bicgstab five-launch, small, Jacobi") : HIPK_FORM("bicgstab five-launch, small"))
+                                : (ext ? HIPK_FORM("bicgstab five-launch, callback M") : PRE ? HIPK_FORM("bicgstab five-launch, Jacobi") : HIPK_FORM("bicgstab five-launch")));
     if (mid_loop) lds_loop = true;   // finished in the one-launch loop
     for (; !lds_loop && it < maxiter; ++it) {
         HIPK_CHECK_HIP(pace.gate(it, stream, &stop));

@@ -941,7 +941,7 @@ extern "C" size_t hipk_cg_work_bytes(int64_t n, int dtype) {
 // Two chunks per workgroup put four rows on a thread: at most 7 entries each in registers
 #define HIPK_MID_ROW(W, NCH, PRE)                                                                                          \
     {W, NCH, PRE, hipk_cg_mid_kernel<T, W, NCH, PRE>,                                                                      \
-     sizeof(T) == 8 ? "hipk_cg_mid_kernel<double," #W "," #NCH "," #PRE ">" : "hipk_cg_mid_kernel<float," #W "," #NCH "," #PRE ">"}
+     HIPK_FORM_OF_T(T, "hipk_cg_mid_kernel<", #W "," #NCH "," #PRE ">")}
 template <typename T>
 static const hipk_mid_entry<hipk_cg_mid_args> hipk_cg_mid_table[] = {
     HIPK_MID_ROW(5, 1, false), HIPK_MID_ROW(7, 1, false), HIPK_MID_ROW(9, 1, false), HIPK_MID_ROW(12, 1, false),
@@ -1101,7 +1101,7 @@ static int hipk_cg_mid_loop(hipk_csr_s *A, S *scal, const hipk_cg_path &path, T 
 template <typename T, bool PRE, typename S>
 static int hipk_cg_lds_loop(hipk_csr_s *A, S *scal, const hipk_cg_path &path, T *x, T *r, T *p, T *Ap, const T *dinv, const double *rz0_parts,
                             double *rz_sub, double *rr_sub, unsigned long long *flags, int64_t &it, int64_t maxiter, bool &failed,
-                            char (&handed)[128], const char *entry, hipStream_t stream) {
+                            char (&handed)[128], const char *entry, hipStream_t stream, const char **form) {
     const bool spread = path.spread;
     bool local = path.local;   // a -2 (spread over several XCDs): agent-scope hand-offs
     const int g = A->geom.g, lgrid = spread ? kGmSub * g : 8 * kGmSub * g;
@@ -1137,8 +1137,12 @@ static int hipk_cg_lds_loop(hipk_csr_s *A, S *scal, const hipk_cg_path &path, T 
         (loc ? hipk_cg_solve_lds_kernel<T, true, PRE> : hipk_cg_solve_lds_kernel<T, false, PRE>)<<<lgrid, HIPK_THREADS, 0, stream>>>(ca);
         return HIPK_OK;
     };
-    return hipk_resident_run(stream, scal, launch, hipk_cg_loop_state<S>, it, maxiter, &local, failed, handed, "hipk_cg_solve_lds_kernel",
-                             entry);
+    const int run = hipk_resident_run(stream, scal, launch, hipk_cg_loop_state<S>, it, maxiter, &local, failed, handed,
+                                      "hipk_cg_solve_lds_kernel", entry);
+    // the instantiation of the last launch (hipk_last_solve_form)
+    *form = local ? (PRE ? HIPK_FORM_OF_T(T, "hipk_cg_solve_lds_kernel<", "true,true>") : HIPK_FORM_OF_T(T, "hipk_cg_solve_lds_kernel<", "true,false>"))
+                  : (PRE ? HIPK_FORM_OF_T(T, "hipk_cg_solve_lds_kernel<", "false,true>") : HIPK_FORM_OF_T(T, "hipk_cg_solve_lds_kernel<", "false,false>"));
+    return run;
 }
 
 // The one-launch section of hipk_cg_solve (PRE = false) and hipk_pcg_solve (PRE = true): the mid loop, else the LDS loop, from
@@ -1161,6 +1165,7 @@ static int hipk_cg_one_launch(hipk_csr_s *A, S *scal, hipk_cg_path &path, const 
     };
     int rc;
     bool mid_done = false, lds_done = false;
+    const char *lds_form = "";
     if (path.mid) {
         const int run = hipk_cg_mid_loop<T, PRE>(A, scal, path, x, r, p, Ap, dinv, PRE ? part_z[0] : nullptr, it, maxiter, mid_failed, handed,
                                                  entry, stream);
@@ -1171,12 +1176,14 @@ static int hipk_cg_one_launch(hipk_csr_s *A, S *scal, hipk_cg_path &path, const 
     hipk_cg_path_lds(path, A, prm, maxiter, mid_done, lds_failed);
     if (path.lds_loop) {   // a hand-back (not co-resident; that launch modified nothing): the launch sequence takes over
         const int run = hipk_cg_lds_loop<T, PRE>(A, scal, path, x, r, p, Ap, dinv, PRE ? part_z[0] : nullptr, PRE ? part_z[1] : nullptr, rr_sub,
-                                                 flags, it, maxiter, lds_failed, handed, entry, stream);
+                                                 flags, it, maxiter, lds_failed, handed, entry, stream, &lds_form);
         if (run < 0) return run;
         if ((rc = after(run)) != HIPK_OK) return rc;
         lds_done = run == HIPK_OK;
     }
     hipk_set_solve_path(handed, mid_done ? path.mid_entry->name : lds_done ? "hipk_cg_solve_lds_kernel" : "launch sequence");
+    // (neither finished: the caller names its launch sequence)
+    if (mid_done || lds_done) hipk_set_solve_form(mid_done ? path.mid_entry->name : lds_form);
     *done = mid_done || lds_done;
     return HIPK_OK;
 }
@@ -1261,6 +1268,13 @@ static int hipk_cg_solve_t(hipk_csr_s *A, const T *b, T *x, char *work, const hi
     constexpr int kCap2 = sizeof(T) == 8 ? 1280 : 2048;
     hipk_cg_path_two(path, A, prm, lds_loop, it, kCap2, vec);
     const bool two_launch = path.two_launch;
+    if (!lds_loop)
+        hipk_set_solve_form(two_launch ? (sizeof(T) == 8 ? HIPK_FORM("cg two-launch: hipk_cg2_spmv_kernel<double,1280> + hipk_cg2_update_kernel")
+                                                         : HIPK_FORM("cg two-launch: hipk_cg2_spmv_kernel<float,2048> + hipk_cg2_update_kernel"))
+                            : small ? HIPK_FORM("cg three-launch, small")
+                            : streams && flat_dir ? HIPK_FORM("cg three-launch, streams + flat direction")
+                            : streams ? HIPK_FORM("cg three-launch, streams")
+                                      : HIPK_FORM("cg three-launch"));
     if (two_launch) {
         T *pbuf[2] = {p, (T *)((char *)Ap + vec)};   // p_0 = r_0 sits in pbuf[0] (start kernel); pass k reads pbuf[k & 1], writes the other
         hipk_cg2_args ca;
@@ -1831,6 +1845,7 @@ static int hipk_pcg_solve_t(hipk_csr_s *A, const T *dinv, const T *b, T *x, char
     if ((rc = hipk_cg_one_launch<T, true>(A, scal, path, prm, x, r, p, Ap, dinv, part_z, part_b, (unsigned long long *)(part_c + 1024), it, maxiter,
                                           mid_failed, lds_loop_failed, handed, "hipk_pcg_solve", stream, &lds_loop)) != HIPK_OK)
         return rc;
+    if (!lds_loop) hipk_set_solve_form(HIPK_FORM("pcg three-launch, Jacobi"));
     for (; !lds_loop && it < maxiter; ++it) {
         HIPK_CHECK_HIP(pace.gate(it, stream, &stop));
         if (stop <= it) break;

@@ -2226,7 +2226,7 @@ __global__ __launch_bounds__(HIPK_THREADS) void hipk_gm_scaled_sq_kernel(int64_t
 // the one-launch instantiations the dispatch below selects (hipk_mid_pick), each with the name hipk_last_solve_path reports
 #define HIPK_MID_ROW(W, PRE)                                                                                               \
     {W, 1, PRE, hipk_gm_mid_kernel<T, W, PRE>,                                                                             \
-     sizeof(T) == 8 ? "hipk_gm_mid_kernel<double," #W "," #PRE ">" : "hipk_gm_mid_kernel<float," #W "," #PRE ">"}
+     HIPK_FORM_OF_T(T, "hipk_gm_mid_kernel<", #W "," #PRE ">")}
 template <typename T>
 static const hipk_mid_entry<hipk_gm_mid_args> hipk_gm_mid_table[] = {
     HIPK_MID_ROW(5, false), HIPK_MID_ROW(7, false), HIPK_MID_ROW(9, false), HIPK_MID_ROW(12, false),
@@ -2439,6 +2439,21 @@ static int hipk_gmres_solve_t(hipk_csr_s *A, const T *dinv, const T *b, T *x, ch
     auto cycle_kernel = [&]() -> const char * {
         return mid_cycle ? mid->name : !cyc ? "launch sequence" : cyc_lds ? "hipk_gm_solve_lds_kernel" : "hipk_gm_cycle_small_kernel";
     };
+    // ... and its form (hipk_last_solve_form): the instantiation, or which launch sequence
+#define HIPK_GM_SEQ(name) (ext ? HIPK_FORM(name ", callback M") : HIPK_FORM(name))
+    const char *const seq_form = small ? (wide ? HIPK_GM_SEQ("gmres small + wide") : HIPK_GM_SEQ("gmres small + 256-thread"))
+                                 : m > HIPK_GM_MAXM ? (split_norm ? HIPK_GM_SEQ("gmres restart > 31 + split norm") : HIPK_GM_SEQ("gmres restart > 31"))
+                                 : stream_k ? (split_norm ? HIPK_GM_SEQ("gmres large, streaming + split norm") : HIPK_GM_SEQ("gmres large, streaming"))
+                                            : (split_norm ? HIPK_GM_SEQ("gmres large, first kernels + split norm") : HIPK_GM_SEQ("gmres large, first kernels"));
+#undef HIPK_GM_SEQ
+    auto cycle_form = [&]() -> const char * {
+        return mid_cycle ? mid->name
+               : !cyc    ? seq_form
+               : !cyc_lds ? (sizeof(T) == 8 ? HIPK_FORM("hipk_gm_cycle_small_kernel<double>") : HIPK_FORM("hipk_gm_cycle_small_kernel<float>"))
+               : cyc_local ? HIPK_FORM_OF_T(T, "hipk_gm_solve_lds_kernel<", "true>")
+                           : HIPK_FORM_OF_T(T, "hipk_gm_solve_lds_kernel<", "false>");
+    };
+    const char *last_form = seq_form;   // (none ran: the launch sequence's start and end)
     // spec: second-pass launches only at the steps where a second CGS pass is expected (step 0, then every step that ever asked
     // for one in this solve); a miss is caught on the device and the cycle re-enqueued from that step
     bool predict[HIPK_GM_MAXM_BIG + 1];
@@ -2625,6 +2640,7 @@ static int hipk_gmres_solve_t(hipk_csr_s *A, const T *dinv, const T *b, T *x, ch
             continue;
         }
         last_cycle = cycle_kernel();
+        last_form = cycle_form();
         if (cyc && cyc_lds) {  // hipk_gm_solve_lds_kernel ran whole cycles, loop test included
             cycles += hs->rep_cycles;
             matvecs += hs->rep_matvecs;
@@ -2685,6 +2701,7 @@ static int hipk_gmres_solve_t(hipk_csr_s *A, const T *dinv, const T *b, T *x, ch
     free(hs);
     if (rc != HIPK_OK) return rc;
     hipk_set_solve_path(handed, last_cycle);
+    hipk_set_solve_form(last_form);
     if ((cyc || cyc_lds) && hipk_sw_present("HIPK_GM_STAMPS")) {  // diagnostic build-in: where workgroup 0 of the cycle kernel spent its shader clocks
         unsigned long long st8[16];
         HIPK_CHECK_HIP(hipMemcpyAsync(st8, part_spare + 1600, sizeof(st8), hipMemcpyDeviceToHost, stream));

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "hipk_common.h"
+#include "hipk_forms.h"
 #include "hipk_switch.h"
 
 struct hipk_event_pair {

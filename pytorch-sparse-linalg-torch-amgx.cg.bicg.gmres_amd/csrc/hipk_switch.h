@@ -41,7 +41,7 @@ static constexpr hipk_sw_row hipk_switches[] = {
     {"HIPK_PACE_TIMEOUT_US", HIPK_SW_INT, "200000", "each solve", "t: microseconds the signal word may stand still before the stream-ordered fallback; negative: ignored", "test"},
     {"HIPK_PACE_WINDOW", HIPK_SW_INT, "8", "each solve", "k: iterations the host may run ahead of the GPU; outside 1 .. 4096: ignored", "user"},
     {"HIPK_TEST_LDS_NOT_RESIDENT", HIPK_SW_INT, "unset", "each one-launch loop; each hand-back", "k: the k-th launch of a one-launch loop reports its workgroups as not co-resident, k < 2 (0 included) reads as 1; set at all: a hand-back does not set the process-wide latch", "test"},
-    {"HIPK_NO_LDS_SPREAD", HIPK_SW_PRESENT, "off", "each solve", "9 .. 32 chunks: the launch sequences instead of the one-launch kernels spread over the chip (cg, bicgstab, gmres)", "tools A/B"},
+    {"HIPK_NO_LDS_SPREAD", HIPK_SW_PRESENT, "off", "each solve", "9 .. 32 chunks: the launch sequences instead of the one-launch kernels spread over the chip (cg, bicgstab, gmres)", "test, tools A/B"},
     // ---- CG (hipk_cg.hip)
     {"HIPK_CG_NO_SMALL", HIPK_SW_PRESENT, "off", "each CG solve", "general launch sequence also for <= 8 reduction chunks; also keeps both one-launch loops away", "test"},
     {"HIPK_CG_NO_LDS_LOOP", HIPK_SW_PRESENT, "off", "each CG solve", "launch sequences instead of either one-launch loop (mid and LDS)", "test, tools A/B"},
@@ -70,7 +70,7 @@ static constexpr hipk_sw_row hipk_switches[] = {
     {"HIPK_GMRES_MID", HIPK_SW_OFF_IF_0, "on", "each GMRES solve", "0: the launch sequence per Arnoldi step instead of hipk_gm_mid_kernel", "test, tools A/B"},
     {"HIPK_GMRES_MID_MIN", HIPK_SW_INT, "32", "each GMRES solve", "k: hipk_gm_mid_kernel from k + 1 chunks, floor 8 (A/B against the whole-solve kernel of 9 .. 32 chunks)", "tools A/B"},
     {"HIPK_GM_MD_WIDE", HIPK_SW_INT, "0", "each GMRES solve", "nonzero: multi-dot with up to 32 columns per workgroup; measured slower", "tools A/B"},
-    {"HIPK_GM_SPLIT_NORM", HIPK_SW_INT, "by chunk count", "each GMRES solve", "0 | nonzero: the one-kernel normalise step | scalars launch + flat scale kernel (large systems)", "tools A/B"},
+    {"HIPK_GM_SPLIT_NORM", HIPK_SW_INT, "by chunk count", "each GMRES solve", "0 | nonzero: the one-kernel normalise step | scalars launch + flat scale kernel (large systems)", "test, tools A/B"},
     {"HIPK_GM_NRES", HIPK_SW_INT, "5", "each GMRES solve", "k: basis columns read with the default cache policy, the rest non-temporal (no clamp)", "test, tools A/B"},
     {"HIPK_GM_SPEC", HIPK_SW_INT, "1", "each GMRES solve", "second CGS pass launched at every step (0), where predicted (1), or learned from scratch (2)", "test, tools A/B"},
     {"HIPK_GM_STAMPS", HIPK_SW_PRESENT, "off", "each launch and the end of a small-system GMRES solve", "stamps build only: print the per-phase shader clocks of the cycle kernels", "tools A/B"},

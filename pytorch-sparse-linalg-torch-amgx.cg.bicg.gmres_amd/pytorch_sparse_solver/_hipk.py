@@ -27,7 +27,7 @@ GMRES_BATCHED, GMRES_INCREMENTAL = 0, 1
 SYMBOLS = [
     "hipk_version", "hipk_build_id", "hipk_op_create", "hipk_placement_probe", "hipk_last_error", "hipk_device_count",
     "hipk_csr_create", "hipk_csr_destroy", "hipk_csr_rows", "hipk_csr_nnz", "hipk_csr_spmv_bytes",
-    "hipk_csr_spmv_path", "hipk_last_spmv_kernel", "hipk_last_solve_path", "hipk_csr_set_path", "hipk_csr_format_bytes",
+    "hipk_csr_spmv_path", "hipk_last_spmv_kernel", "hipk_last_solve_path", "hipk_last_solve_form", "hipk_solve_form_count", "hipk_solve_form_name", "hipk_csr_set_path", "hipk_csr_format_bytes",
     "hipk_csr_transpose_work_bytes", "hipk_csr_transpose",
     "hipk_chunk_size", "hipk_chunk_count", "hipk_scratch_bytes",
     "hipk_spmv", "hipk_spmv_dot", "hipk_dot", "hipk_axpy", "hipk_xpby", "hipk_block_jacobi_apply",
@@ -174,6 +174,10 @@ def lib():
     L.hipk_build_id.restype = ctypes.c_char_p
     L.hipk_last_spmv_kernel.restype = ctypes.c_char_p
     L.hipk_last_solve_path.restype = ctypes.c_char_p
+    L.hipk_last_solve_form.restype = ctypes.c_char_p
+    L.hipk_solve_form_count.restype = ctypes.c_int
+    L.hipk_solve_form_name.restype = ctypes.c_char_p
+    L.hipk_solve_form_name.argtypes = [ctypes.c_int]
     L.hipk_device_count.restype = i32
     L.hipk_csr_create.argtypes = [ctypes.POINTER(vp), i64, i64, i64, vp, vp, i32, vp, i32, vp]
     L.hipk_csr_destroy.argtypes = [vp]
@@ -278,6 +282,18 @@ def last_solve_path() -> str:
     """The loop that finished this thread's most recent solve (hipk_last_solve_path): a one-launch kernel instantiation,
     a whole-loop kernel or "launch sequence"; "a -> b" when a one-launch kernel handed the solve back."""
     return lib().hipk_last_solve_path().decode()
+
+
+def last_solve_form() -> str:
+    """The form that solve finished in (hipk_last_solve_form): the instantiation of a one-launch kernel's last launch, or which
+    launch sequence ("cg three-launch, small", "gmres restart > 31", ...)."""
+    return lib().hipk_last_solve_form().decode()
+
+
+def solve_forms() -> list:
+    """Every form a single-device solve can report (hipk_solve_form_name; no GPU needed)."""
+    L = lib()
+    return [L.hipk_solve_form_name(i).decode() for i in range(L.hipk_solve_form_count())]
 
 
 def _check(rc: int, what: str) -> None:

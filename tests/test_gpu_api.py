@@ -265,7 +265,8 @@ def test_restart_above_31_uses_reference_semantics(hipk):
 @pytest.mark.gpu
 def test_gmres_small_system_launch_folding_is_bit_identical(monkeypatch):
     """Systems of <= 8 reduction chunks fold the CGS2 decision and the h-vector reduction into their consumers
-    (7 instead of 10 launches per Arnoldi step): same bits as the general launch sequence."""
+    (7 instead of 10 launches per Arnoldi step): same bits as the general launch sequence.
+    (Variant against variant; tests/test_gpu_solver_forms.py pins each of these forms to the oracle and asserts which one ran.)"""
     import torch
     from pytorch_sparse_solver.module_a import get_last_stats, gmres
     from pytorch_sparse_solver.utils.matrix_utils import create_convdiff_2d_csr, create_ldc_pressure_csr
@@ -346,7 +347,8 @@ def test_handle_create_destroy_does_not_leak_device_memory():
 @pytest.mark.gpu
 def test_cg_small_system_path_without_combine_launch_is_bit_identical(monkeypatch):
     """Systems of <= 8 reduction chunks: the CG vector kernels fold the SpMV's tile sums themselves (3 instead of 4
-    launches per iteration) -- same bits as the general launch sequence, on the coded, tile and row-per-wavefront paths."""
+    launches per iteration) -- same bits as the general launch sequence, on the coded, tile and row-per-wavefront paths.
+    (Variant against variant; tests/test_gpu_solver_forms.py pins each of these forms to the oracle and asserts which one ran.)"""
     import torch
     from pytorch_sparse_solver.module_a import cg, get_last_stats
     from pytorch_sparse_solver.utils.matrix_utils import create_poisson_2d_csr, create_variable_diffusion_2d_csr
@@ -371,6 +373,8 @@ def test_cg_small_system_path_without_combine_launch_is_bit_identical(monkeypatc
 
 @pytest.mark.gpu
 def test_bicgstab_small_system_path_without_combine_launches_is_bit_identical(monkeypatch):
+    """The same for BiCGStab: both SpMVs of a small system skip their combine launch.
+    (Variant against variant; tests/test_gpu_solver_forms.py pins each of these forms to the oracle and asserts which one ran.)"""
     import torch
     from pytorch_sparse_solver.module_a import JacobiPreconditioner, bicgstab, get_last_stats
     from pytorch_sparse_solver.utils.matrix_utils import create_convdiff_2d_csr, create_ldc_pressure_csr
@@ -443,7 +447,8 @@ def test_host_signal_pacing_and_stream_polling_agree(monkeypatch):
 def test_gmres_wide_small_system_kernels_are_bit_identical(monkeypatch):
     """Small systems with 2048-row chunks run the GMRES multi-dot / update with one 256-thread group per chunk-loop
     step (1024 threads fp64, 512 fp32); HIPK_GMRES_NO_WIDE=1 selects the 256-thread kernels: same bits, ragged tails,
-    second CGS passes and fp32 storage included."""
+    second CGS passes and fp32 storage included.
+    (Variant against variant; tests/test_gpu_solver_forms.py pins each of these forms to the oracle and asserts which one ran.)"""
     import torch
     from pytorch_sparse_solver.module_a import gmres, get_last_stats
     from pytorch_sparse_solver.utils.matrix_utils import create_convdiff_2d_csr, create_ldc_pressure_csr
@@ -496,7 +501,8 @@ def test_gmres_one_launch_per_cycle_kernel_is_bit_identical(monkeypatch):
     HIPK_GMRES_NO_CYCLE=1 selects the multi-launch small-system path; HIPK_GM_LAUNCH_CYCLES bounds the cycles of one launch
     and HIPK_GM_CYCLE_AGENT=1 selects agent-scope hand-offs.  Same bits from all of them -- ragged tails, one to
     eight chunks, second CGS passes, breakdown / early exit, Jacobi scaling, fp32 storage, rows beyond the register-held
-    16 entries and restart lengths on either side of a multiple of 8 included."""
+    16 entries and restart lengths on either side of a multiple of 8 included.
+    (Variant against variant; tests/test_gpu_solver_forms.py pins each of these forms to the oracle and asserts which one ran.)"""
     import torch
     from pytorch_sparse_solver.module_a import JacobiPreconditioner, get_last_stats, gmres
     from pytorch_sparse_solver.utils.matrix_utils import (create_convdiff_2d_csr, create_ldc_pressure_csr,
@@ -548,7 +554,8 @@ def test_cg_whole_loop_in_one_launch_is_bit_identical(monkeypatch):
     """Small systems with short rows run the whole CG loop in ONE launch (hipk_cg_solve_lds_kernel: x, r, p in registers, eight
     workgroups per reduction chunk, two hand-offs per iteration, p advanced on the consumer side).  HIPK_CG_NO_LDS_LOOP=1 selects
     the three-launches-per-iteration loop: same bits, same counts -- ragged tails, one to eight chunks, x0, maxiter cut-offs that
-    fall inside and on the boundary of a launch's iteration budget, agent-scope hand-offs, fp32 storage."""
+    fall inside and on the boundary of a launch's iteration budget, agent-scope hand-offs, fp32 storage.
+    (Variant against variant; tests/test_gpu_solver_forms.py pins each of these forms to the oracle and asserts which one ran.)"""
     import torch
     from pytorch_sparse_solver.module_a import JacobiPreconditioner, cg, get_last_stats
     from pytorch_sparse_solver.utils.matrix_utils import (create_ldc_pressure_csr, create_poisson_2d_csr,
@@ -597,7 +604,8 @@ def test_bicgstab_whole_loop_in_one_launch_is_bit_identical(monkeypatch):
     """Small systems with short rows run the whole BiCGStab loop in ONE launch (hipk_bi_solve_lds_kernel: three hand-offs per
     iteration, p and s advanced on the consumer side); HIPK_BICGSTAB_NO_LDS_LOOP=1 selects the five-launches-per-iteration loop:
     same bits, same counts and the same breakdown codes -- ragged tails, one to eight chunks, x0, maxiter cut-offs inside and on
-    the boundary of a launch's iteration budget, the early exit, agent-scope hand-offs, fp32 storage."""
+    the boundary of a launch's iteration budget, the early exit, agent-scope hand-offs, fp32 storage.
+    (Variant against variant; tests/test_gpu_solver_forms.py pins each of these forms to the oracle and asserts which one ran.)"""
     import torch
     from pytorch_sparse_solver.module_a import JacobiPreconditioner, bicgstab, get_last_stats
     from pytorch_sparse_solver.utils.matrix_utils import (create_convdiff_2d_csr, create_ldc_pressure_csr, create_poisson_2d_csr,
@@ -649,7 +657,8 @@ def test_bicgstab_whole_loop_in_one_launch_is_bit_identical(monkeypatch):
 def test_one_launch_kernels_fall_back_when_their_workgroups_are_not_resident(monkeypatch):
     """The whole-solve kernels of small systems need all their workgroups resident at once; when the placement check fails
     (a shared device) nothing has been modified and the launch sequences take over.  HIPK_TEST_LDS_NOT_RESIDENT makes the
-    kernels report exactly that: same results as without them."""
+    kernels report exactly that: same results as without them.
+    (Variant against variant; tests/test_gpu_solver_forms.py pins each of these forms to the oracle and asserts which one ran.)"""
     import torch
     from pytorch_sparse_solver.module_a import bicgstab, cg, get_last_stats, gmres
     from pytorch_sparse_solver.utils.matrix_utils import create_convdiff_2d_csr, create_poisson_2d_csr
@@ -678,7 +687,8 @@ def test_one_launch_kernels_fall_back_in_the_middle_of_a_solve(monkeypatch):
     """a LATER launch of a one-launch loop may find its workgroups not co-resident (the first ran, e.g. the
     16384-iteration bound was reached or HIPK_*_LAUNCH_ITS is set).  The launch sequences then take over from iteration it > 0,
     where the one-launch kernels keep their reduction state in another layout (Jacobi-PCG: <r,z> only as a scalar; BiCGStab: 8 g
-    sub-partials).  Launches bounded to 7 iterations / 2 cycles, the SECOND launch fails: same bits as an undisturbed solve."""
+    sub-partials).  Launches bounded to 7 iterations / 2 cycles, the SECOND launch fails: same bits as an undisturbed solve.
+    (Variant against variant; tests/test_gpu_solver_forms.py pins each of these forms to the oracle and asserts which one ran.)"""
     import torch
     from pytorch_sparse_solver.module_a import JacobiPreconditioner, bicgstab, cg, get_last_stats, gmres
     from pytorch_sparse_solver.utils.matrix_utils import create_convdiff_2d_csr, create_poisson_2d_csr
@@ -812,7 +822,9 @@ def test_cg_two_launch_iteration_is_bit_identical(hipk, oracle, monkeypatch):
     """Launch-bound mid-size systems (33 .. 256 reduction chunks) run CG with TWO launches per iteration: the direction step is
     formed on the fly inside the SpMV (hipk_cg2_spmv_kernel / hipk_cg2_update_kernel).  Same bits as the three-launch sequence --
     x, iteration count, info, true and recurrence residuals -- for fp64 and fp32 storage, warm starts, maxiter cut-offs (even and
-    odd, 0 and 1), a stop at iteration 0; and, on one system, as the CPU oracle."""
+    odd, 0 and 1), a stop at iteration 0; and, on one system, as the CPU oracle.  HIPK_CG_MID=0 in both arms: these grids otherwise go
+    to hipk_cg_mid_kernel whatever HIPK_CG_TWO_LAUNCH says; hipk_last_solve_form names which iteration each arm ran
+    (tests/test_gpu_solver_forms.py pins the two-launch iteration to the oracle on both sides of each of its guards)."""
     from pytorch_sparse_solver.module_a import get_last_stats
     from pytorch_sparse_solver.utils.matrix_utils import create_poisson_2d_csr, create_variable_diffusion_2d_csr
     cases = [(create_poisson_2d_csr(300, 300, device=DEV), dict(tol=1e-8)),                       # 44 chunks
@@ -838,13 +850,18 @@ def test_cg_two_launch_iteration_is_bit_identical(hipk, oracle, monkeypatch):
             out = []
             for two in ("1", "0"):
                 monkeypatch.setenv("HIPK_CG_TWO_LAUNCH", two)
+                monkeypatch.setenv("HIPK_CG_MID", "0")
                 x = torch.zeros_like(b) if x0 is None else x0.clone()
                 st = hipk.solve("cg", h, b, x, atol=0.0, **{"maxiter": None, **kw})
+                cap = "double,1280" if dt == torch.float64 else "float,2048"
+                assert hipk.last_solve_form() == (f"cg two-launch: hipk_cg2_spmv_kernel<{cap}> + hipk_cg2_update_kernel" if two == "1"
+                                                  else "cg three-launch"), (idx, dt, two, hipk.last_solve_form())
                 out.append((x.clone(), st.iterations, st.matvecs, st.info, st.residual_norm, st.recurrence_rs))
             assert torch.equal(out[0][0], out[1][0]) and out[0][1:] == out[1][1:], (idx, dt, out[0][1:], out[1][1:])
             if idx == 8:
                 assert out[0][1] == 0
     monkeypatch.delenv("HIPK_CG_TWO_LAUNCH", raising=False)
+    monkeypatch.delenv("HIPK_CG_MID", raising=False)
     A, kw = cases[0]
     b = torch.ones(A.shape[0], dtype=torch.float64, device=DEV)
     x = torch.zeros_like(b)
