@@ -105,8 +105,14 @@ int hipk_device_count(void);
  * crow/col are device arrays of idx_bytes (4 or 8) wide integers as torch stores
  * them (int64); they are narrowed once to int32 (SURVEY 7.2 "index width").
  * `val` is BORROWED: it must stay alive and unchanged until hipk_csr_destroy.
- * Column indices must be sorted within each row (torch CSR invariant) only for
- * bitwise parity with the oracle, not for correctness. */
+ * A row is summed in STORED order: its products are rounded and added in the order
+ * of its entries in col/val (rows of more than 32 entries: 64 lane-strided partial
+ * sums of the stored sequence).  Column indices need not be sorted within a row, and
+ * a column may be stored more than once (the entries add, as in A x) or with the
+ * value 0: every SpMV kernel, solve form, the Chebyshev epilogue and the transpose
+ * accept such rows, and the results are bitwise those of the oracle on the same
+ * arrays (tests/test_gpu_entry_order.py).  The row-partitioned solves depend on
+ * it: a rank's boundary rows arrive with renumbered, unsorted ghost columns. */
 int hipk_csr_create(hipk_csr_t *out, int64_t n_rows, int64_t n_cols, int64_t nnz,
                     const void *crow_dev, const void *col_dev, int idx_bytes,
                     const void *val_dev, int dtype, hipk_stream_t stream);

@@ -3,7 +3,8 @@ of tests/_spmv_cases.py, and the run of one case -- switches, THEN the handle, h
 after the call, every output compared bit for bit with the oracle.
 
 As a program: python _spmv_inst_worker.py GROUP OUT.json CASE...  runs the cases of one fresh-process group (switches that
-hipk_launch_spmv reads once per process) in this process and writes {case: {"notes": [...], "failures": [...]}}."""
+hipk_launch_spmv reads once per process) in this process and writes {case: {"notes": [...], "failures": [...]}}.  GROUP
+"order:NAME" takes the cases from tests/_order_cases.py (tests/test_gpu_entry_order.py: unsorted and duplicate rows) instead."""
 import json
 import os
 import sys
@@ -39,13 +40,14 @@ class References:
     """x, w, b and the oracle's outputs for one matrix in one storage type: y = A x and b - A x, and per reduction chunk of `ch`
     rows the fused dots <w, y>, <x, A x> (w is x) and <y, y>."""
 
-    def __init__(self, oracle, name, dtype, ch):
+    def __init__(self, oracle, name, dtype, ch, arrays=None, vectors=None):
+        """arrays, vectors: (crow, col, val) and (x, w, b) of a matrix that is not one of tests/_spmv_cases.py: MATRICES."""
         self.name, self.dtype, self.ch = name, dtype, ch
         self.f = np.float64 if dtype == C.DOUBLE else np.float32
-        self.crow, self.col, val = C.matrix(name)
+        self.crow, self.col, val = C.matrix(name) if arrays is None else arrays
         self.val = val.astype(self.f)
         self.n = len(self.crow) - 1
-        self.x, self.w, self.b = C.vectors(name, dtype)
+        self.x, self.w, self.b = C.vectors(name, dtype) if vectors is None else vectors
         spmv = oracle.spmv if dtype == C.DOUBLE else oracle.spmv32
         oracle.set_threads(16)
         try:
@@ -111,6 +113,7 @@ class OnDevice:
         import torch
         to = lambda a: torch.from_numpy(a).to(DEV)   # noqa: E731
         self.crow, self.col, self.val = to(ref.crow), to(ref.col), to(ref.val)
+        self.crow32, self.col32 = None, None         # int32 copies, made when a case asks for them (idx_bytes 4)
         self.x, self.w, self.b = to(ref.x), to(ref.w), to(ref.b)
         self.x0, self.w0, self.b0 = self.x.clone(), self.w.clone(), self.b.clone()
 
@@ -133,16 +136,25 @@ def _launch(hipk, h, ref, dev, mode, wx):
     return note, y.cpu().numpy(), p0.cpu().numpy(), p1.cpu().numpy()
 
 
-def run_case(hipk, name, ref, dev, setenv):
-    """Run one case of the table.  setenv(name, value or None) changes the environment (the caller restores it).
+def run_case(hipk, name, ref, dev, setenv, case=None):
+    """Run one case of the table (`case`: a row of another table in the same layout; "idx32": crow / col as int32 tensors).
+    setenv(name, value or None) changes the environment (the caller restores it).
     Returns (notes, failures): [step, mode, w is x, note] per launch, and every mismatch found -- none stops the run."""
-    case = C.CASES[name]
-    assert (case["matrix"], case["dtype"]) == (ref.name, ref.dtype)
+    import torch
+    if case is None:
+        case = C.CASES[name]
+        assert (case["matrix"], case["dtype"]) == (ref.name, ref.dtype)
+    assert case["dtype"] == ref.dtype
     assert int(hipk.lib().hipk_chunk_size(ref.n)) == ref.ch
     notes, failures, outs = [], [], {}
     for k, v in case["env"].items():
         setenv(k, v)
-    h = hipk.CsrHandle(dev.crow, dev.col, dev.val, (ref.n, ref.n))     # after the switches: the handle caches its kernel choice
+    crow, col = dev.crow, dev.col
+    if case.get("idx32"):
+        if dev.crow32 is None:
+            dev.crow32, dev.col32 = dev.crow.to(torch.int32), dev.col.to(torch.int32)
+        crow, col = dev.crow32, dev.col32
+    h = hipk.CsrHandle(crow, col, dev.val, (ref.n, ref.n))     # after the switches: the handle caches its kernel choice
     try:
         if case["plain_only"]:
             h.set_path(plain_only=True)
@@ -207,17 +219,26 @@ def main():
         else:
             os.environ[k] = v
 
+    table = C
+    if group.startswith("order:"):
+        import _order_cases as table
+        group = group[len("order:"):]
     results, held = {}, {}
     for name in names:
-        case = C.CASES[name]
+        case = table.CASES[name]
         assert case["fresh"] == group, (name, case["fresh"], group)
-        key = (case["matrix"], case["dtype"])
+        key = (case["matrix"], case.get("transform"), case["dtype"])
         if key not in held:
             held.clear()
-            ref = References(O, key[0], key[1], int(hipk.lib().hipk_chunk_size(C.MATRICES[key[0]][0])))
+            if table is C:
+                ref = References(O, key[0], key[2], int(hipk.lib().hipk_chunk_size(C.MATRICES[key[0]][0])))
+            else:
+                arrays = table.arrays(*key)
+                ref = References(O, key[0], key[2], int(hipk.lib().hipk_chunk_size(len(arrays[0]) - 1)), arrays=arrays,
+                                 vectors=table.vectors(key[0], key[2]))
             held[key] = (ref, OnDevice(ref))
         print(name, flush=True)
-        notes, failures = run_case(hipk, name, *held[key], setenv)
+        notes, failures = run_case(hipk, name, *held[key], setenv, case=case)
         results[name] = {"notes": notes, "failures": failures}
         for k, v in touched.items():     # the next case sets its own switches, the group's among them
             if v is None:
