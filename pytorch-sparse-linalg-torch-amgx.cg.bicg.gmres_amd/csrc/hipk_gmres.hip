@@ -18,7 +18,6 @@
 //     triangular solve TSL:630) in the same arithmetic order as the oracle.
 // Traffic of step k (fp64): B_spmv + 8n(k+2) [multi-dot] + 8n(k+3) [update] + 16n [normalise].
 #include <math.h>
-#include <stdlib.h>
 
 #include "hipk_blas1.h"
 #include "hipk_solve.h"
@@ -2184,10 +2183,44 @@ static void hipk_lstsq_normal(const double *H, int ldh, int k, double beta0, dou
     }
 }
 
-static inline double hipk_tmin(double a, double b) {
-    if (isnan(a) || isnan(b)) return NAN;
-    return a < b ? a : b;
-}
+// ---------------------------------------------------------------- the workspace of a solve
+// At restart m with vectors of `vec` bytes: the header (hipk_gm_scal) | restart > 31: H, R, the Givens pairs, beta, h and r
+// (hipk_gm_view) | kGmSlots named partial arrays and the m + 1 of the multi-dot | the basis, m + 1 columns | one spare vector |
+// tail: what a caller puts behind them (the mid cycle's flagged words, the exchange buffers of the row-partitioned loop).  The
+// one-launch kernels address fixed places in it: part_spare + 512 (hand-off flags), part_spare + 1600 (stamps), and part_xx
+// holds ||M b||^2 until the end of the solve.
+static inline size_t hipk_gm_parts_offset(int m) { return kGmHeader + hipk_gm_big_doubles(m) * sizeof(double); }
+static inline size_t hipk_gm_basis_offset(int m) { return hipk_gm_parts_offset(m) + (size_t)(kGmSlots + m + 1) * HIPK_MAX_PARTS * sizeof(double); }
+static inline size_t hipk_gm_layout_bytes(int m, size_t vec) { return hipk_gm_basis_offset(m) + (size_t)(m + 2) * vec; }
+template <typename T>
+struct hipk_gm_layout {
+    hipk_gm_scal *scal;
+    size_t big_n;   // doubles of the block behind the header (0 up to restart 31, then big is null)
+    double *big;
+    double *part_ww, *part_qq, *part_res, *part_bb, *part_xx, *part_spare, *part_md;
+    T *V, *tmp;
+    int64_t ldv;
+    char *tail;
+    static hipk_gm_layout make(char *work, int m, size_t vec) {
+        hipk_gm_layout w;
+        w.scal = (hipk_gm_scal *)work;
+        w.big_n = hipk_gm_big_doubles(m);
+        w.big = w.big_n ? (double *)(work + kGmHeader) : nullptr;
+        double *parts = (double *)(work + hipk_gm_parts_offset(m));
+        w.part_ww = parts;
+        w.part_qq = parts + HIPK_MAX_PARTS;
+        w.part_res = parts + 2 * HIPK_MAX_PARTS;
+        w.part_bb = parts + 3 * HIPK_MAX_PARTS;
+        w.part_xx = parts + 4 * HIPK_MAX_PARTS;
+        w.part_spare = parts + 5 * HIPK_MAX_PARTS;   // (three slots)
+        w.part_md = parts + (size_t)kGmSlots * HIPK_MAX_PARTS;
+        w.V = (T *)(work + hipk_gm_basis_offset(m));
+        w.tmp = (T *)(work + hipk_gm_basis_offset(m) + (size_t)(m + 1) * vec);
+        w.ldv = (int64_t)(vec / sizeof(T));
+        w.tail = work + hipk_gm_layout_bytes(m, vec);
+        return w;
+    }
+};
 
 extern "C" size_t hipk_gmres_work_bytes(int64_t n, int restart, int dtype) {
     const size_t sv = (dtype == HIPK_F64) ? 8 : 4;
@@ -2196,8 +2229,102 @@ extern "C" size_t hipk_gmres_work_bytes(int64_t n, int restart, int dtype) {
     // mid-size systems (hipk_gm_mid.h): v_{k+1} as 16-byte flagged words (two more vectors) + the partial slots
     const hipk_geom gm = hipk_make_geom(n > 0 ? n : 1);
     const bool mid = gm.g > 8 && gm.g <= kGmMidMaxChunks && m <= HIPK_GM_MAXM;
-    return kGmHeader + hipk_gm_big_doubles(m) * sizeof(double) + (size_t)(kGmSlots + m + 1) * HIPK_MAX_PARTS * sizeof(double) +
-           (size_t)(m + 2) * vec + (mid ? hipk_align_up((size_t)(n > 0 ? n : 1) * 16, 256) + kGmMidSlotBytes : 0);   // v_{k+1} as 16-byte flagged words
+    return hipk_gm_layout_bytes(m, vec) + (mid ? hipk_align_up((size_t)(n > 0 ? n : 1) * 16, 256) + kGmMidSlotBytes : 0);
+}
+
+// TSL:735-753 on the GLOBAL size (python floats become fp32 tensors; python max() keeps a float a float): the absolute tolerance
+// the cycle loop tests the residual norm against ...
+static double hipk_gm_atol_eff(const hipk_params *prm, int64_t n_global, double b_norm) {
+    const double eps = HIPK_EPS64;  // the absolute floor keeps the fp64 eps also for fp32 storage (SURVEY A.5)
+    const double ng = (double)n_global;
+    const double cand = (prm->gpu_tolerances ? 1e-12 : 1e-14) * sqrt(ng);
+    const double adaptive = (cand > prm->tol) ? cand : (double)(float)prm->tol;
+    const double base_atol = (double)(float)(eps * (prm->gpu_tolerances ? 1000 : 100) * ng);
+    return hipk_tmax(adaptive * b_norm, hipk_tmax((double)(float)prm->atol, base_atol));
+}
+// ... and the tolerance of the incremental form's early exit, from ||M b|| (TSL:750; M = identity: ||b||)
+static inline double hipk_gm_ptol(double mb_norm, double atol_eff, double b_norm) { return mb_norm * hipk_tmin(1.0, atol_eff / b_norm); }
+// ||M b|| from the chunk partials of its square: folded into `slot` on the device, read back
+static int hipk_gm_mb_norm(const double *part, int g, double *slot, hipStream_t stream, double *mb_norm) {
+    HIPK_TRY(hipk_launch_finish1(part, g, slot, stream));
+    double mb2 = 0.0;
+    HIPK_CHECK_HIP(hipMemcpyAsync(&mb2, slot, sizeof(double), hipMemcpyDeviceToHost, stream));
+    HIPK_CHECK_HIP(hipStreamSynchronize(stream));
+    *mb_norm = hipk_norm_from_sq(mb2);
+    return HIPK_OK;
+}
+
+// The host's copy of a cycle's scalars and, beyond restart 31, of its small arrays
+struct hipk_gm_host {
+    std::vector<unsigned char> buf;
+    std::vector<double> big;
+    explicit hipk_gm_host(size_t big_n) : buf(sizeof(hipk_gm_scal)), big(big_n) {}
+    const hipk_gm_scal *operator->() const { return (const hipk_gm_scal *)buf.data(); }
+    // once everything enqueued so far has run
+    int read(const hipk_gm_scal *scal, const double *dev_big, hipStream_t stream) {
+        HIPK_CHECK_HIP(hipGetLastError());
+        HIPK_CHECK_HIP(hipMemcpyAsync(buf.data(), scal, sizeof(hipk_gm_scal), hipMemcpyDeviceToHost, stream));
+        if (!big.empty()) HIPK_CHECK_HIP(hipMemcpyAsync(big.data(), dev_big, big.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
+        HIPK_CHECK_HIP(hipStreamSynchronize(stream));
+        return HIPK_OK;
+    }
+    // y of the cycle's least squares over its k > 0 steps (beta0: the residual norm the cycle started from)
+    void solve_y(int m, int k, int incremental, double beta0, double *y) const {
+        // the cycle's small arrays: the struct's own (ld 32) or the workspace block's host copy (hipk_gm_cycle_init_kernel's layout)
+        const bool blk = !big.empty();
+        const int ldh = blk ? hipk_gm_big_ld(m) : HIPK_GM_LDH;
+        const double *Hh = blk ? big.data() : (*this)->H;
+        const double *Rh = blk ? Hh + (size_t)(m + 2) * ldh : (*this)->R;
+        const double *bvh = blk ? Rh + (size_t)ldh * ldh + 2 * ldh : (*this)->beta_vec;
+        if (!incremental) return hipk_lstsq_normal(Hh, ldh, k, beta0, y);
+        for (int i = k - 1; i >= 0; --i) {  // solve_triangular, TSL:630
+            double s = bvh[i];
+            for (int p = i + 1; p < k; ++p) s = fma(-Rh[i * ldh + p], y[p], s);
+            y[i] = s / Rh[i * ldh + i];
+        }
+    }
+};
+
+struct hipk_gm_tally {   // what a solve has done so far
+    int64_t cycles = 0, matvecs = 0;
+    int happy = 0;           // a cycle ended in a breakdown
+    double res_norm = 0.0;   // of the residual the next cycle starts from
+};
+
+// x += V[:, :k] y on `grid` chunks: hipk_gm_xupdate_kernel with y as a kernel argument of 32 doubles, beyond that of 256
+template <typename T>
+static void hipk_gm_xupdate(int grid, int64_t n, int ch, int k, const T *V, int64_t ldv, T *x, const hipk_gm_yN<HIPK_GM_MAXM_BIG + 1> &yb, hipStream_t stream) {
+    if (k <= HIPK_GM_LDH) {
+        hipk_gm_y yy;
+        memcpy(yy.y, yb.y, sizeof(yy.y));
+        hipk_gm_xupdate_kernel<T><<<grid, HIPK_THREADS, 0, stream>>>(n, ch, k, V, ldv, x, yy);
+    } else {
+        hipk_gm_xupdate_kernel<T, HIPK_GM_MAXM_BIG + 1><<<grid, HIPK_THREADS, 0, stream>>>(n, ch, k, V, ldv, x, yb);
+    }
+}
+
+// `gmres` epilogue (TSL:766-773), the counterpart of hipk_finish_isolve_stats: called with hipk_gm_final_kernel enqueued, it
+// closes the solve's event pair, reads the true residual and <x,x> back and fills the stats
+static int hipk_gm_finish_stats(hipk_stats *st, const hipk_gm_scal *scal, const hipk_event_pair &whole, hipStream_t stream, const hipk_gm_tally &t,
+                                double b_norm, double atol_eff) {
+    HIPK_CHECK_HIP(hipGetLastError());
+    double fin[4];
+    HIPK_CHECK_HIP(hipEventRecord(whole.b, stream));
+    HIPK_CHECK_HIP(hipMemcpyAsync(fin, scal, sizeof(fin), hipMemcpyDeviceToHost, stream));
+    HIPK_CHECK_HIP(hipStreamSynchronize(stream));
+    st->iterations = t.cycles;
+    st->matvecs = t.matvecs;
+    st->b_norm = b_norm;
+    st->residual_norm = hipk_norm_from_sq(fin[2]);
+    st->x_norm = hipk_norm_from_sq(fin[3]);
+    st->threshold = atol_eff * 10;  // TSL:769
+    st->info = (isnan(st->x_norm) || st->residual_norm > st->threshold) ? -1 : 0;
+    st->breakdown = t.happy;
+    st->recurrence_rs = t.res_norm;
+    float ms = 0.f;
+    HIPK_CHECK_HIP(hipEventElapsedTime(&ms, whole.a, whole.b));
+    st->solve_ms = ms;
+    return HIPK_OK;
 }
 
 // partials of || d .* v ||^2 (||M b|| of the preconditioned solver, TSL:750)
@@ -2235,7 +2362,7 @@ static const hipk_mid_entry<hipk_gm_mid_args> hipk_gm_mid_table[] = {
 
 // ---- which kernels the restart cycles of a gmres solve run in (m: restart; pre: Jacobi; ext: the caller's M through a callback):
 // the only place that knows GMRES's switches and size limits.  One step: every choice is made before the first cycle; a launch
-// that hands its cycle back only takes forms away (the driver's copies of cyc, cyc_lds, cyc_local, mid_cycle).
+// that hands its cycle back only takes forms away (hipk_gm_run's copies of cyc, cyc_lds, cyc_local, mid_cycle).
 struct hipk_gm_path {
     bool small = false;       // <= 8 chunks, restart <= 31: fewer launches per Arnoldi step
     bool wide = false;        // ... with hipk_gm_multidot_wide_kernel / hipk_gm_update_wide_kernel
@@ -2312,507 +2439,451 @@ static hipk_gm_path hipk_gm_path_choose(hipk_csr_s *A, const hipk_params *prm, i
     return path;
 }
 
+// ... and what a solve changes as it goes: its copies of the one-launch forms (a launch's verdict takes them away), the steps
+// at which a second CGS pass is launched, and what it will report
+struct hipk_gm_run {
+    bool cyc = false, cyc_lds = false, cyc_local = false, mid_cycle = false;
+    // spec: second-pass launches only at the steps where a second CGS pass is expected (step 0, then every step that ever asked
+    // for one in this solve); a miss is caught on the device and the cycle re-enqueued from that step
+    bool predict[HIPK_GM_MAXM_BIG + 1];
+    int launch_no = 0;   // one count for all one-launch kernels of the solve (HIPK_TEST_LDS_NOT_RESIDENT)
+    const char *mid_name = nullptr, *seq_form = nullptr;
+    const char *last_cycle = "launch sequence", *last_form = nullptr;   // what ran the last restart cycle (none ran: the launch sequence's start and end)
+    char handed[128] = "";   // the one-launch kernels that handed this solve back
+    void start(const hipk_gm_path &p, const char *seq) {
+        cyc = p.cyc, cyc_lds = p.cyc_lds, cyc_local = p.cyc_local, mid_cycle = p.mid_cycle;
+        mid_name = p.mid_entry ? p.mid_entry->name : nullptr;
+        seq_form = last_form = seq;
+        for (int j = 0; j <= HIPK_GM_MAXM_BIG; ++j) predict[j] = (j == 0) && p.predict_step0;
+    }
+    // the kernel the next cycle runs in (hipk_last_solve_path) ...
+    const char *kernel() const { return mid_cycle ? mid_name : !cyc ? "launch sequence" : cyc_lds ? "hipk_gm_solve_lds_kernel" : "hipk_gm_cycle_small_kernel"; }
+    // ... and its form (hipk_last_solve_form): the instantiation, or which launch sequence
+    template <typename T>
+    const char *form() const {
+        return mid_cycle ? mid_name
+               : !cyc    ? seq_form
+               : !cyc_lds ? (sizeof(T) == 8 ? HIPK_FORM("hipk_gm_cycle_small_kernel<double>") : HIPK_FORM("hipk_gm_cycle_small_kernel<float>"))
+               : cyc_local ? HIPK_FORM_OF_T(T, "hipk_gm_solve_lds_kernel<", "true>")
+                           : HIPK_FORM_OF_T(T, "hipk_gm_solve_lds_kernel<", "false>");
+    }
+    // What the redo word read back after a cycle's launches says, applied to the solve.  HIPK_REDO_RAN: go on with what is in memory.
+    // HIPK_REDO_AGENT: the workgroups of the LDS kernel were spread over several XCDs -- the same launch again with hand-offs at
+    // agent scope.  HIPK_REDO_HAND_BACK: the resident workgroups of a one-launch kernel did not all arrive (the device is shared and
+    // they were not co-resident); nothing of the cycle is kept -- column 0 is untouched -- the kernel joins `handed`, its process-wide
+    // latch is set and the solve goes on in the next form.  HIPK_REDO_ERROR: a hand-off of the mid cycle never completed.
+    hipk_redo_verdict take_verdict(int32_t redo, bool &lds_cycle_failed, bool &mid_failed) {
+        const hipk_redo_verdict verdict = hipk_redo_classify(redo, cyc_lds && cyc_local);
+        if (verdict == HIPK_REDO_RAN) return verdict;
+        if (mid_cycle) {
+            if (verdict == HIPK_REDO_ERROR) {
+                hipk_set_error("hipk_gmres_solve: a resident workgroup of the one-launch cycle stopped arriving");
+                return verdict;
+            }
+            hipk_hand_back(mid_failed, handed, kernel());
+            mid_cycle = false;
+            return HIPK_REDO_HAND_BACK;
+        }
+        if (hipk_sw_present("HIPK_GM_STAMPS")) fprintf(stderr, "hipk_gmres_solve: one-launch cycle abandoned (workgroups not co-resident)\n");
+        if (verdict == HIPK_REDO_AGENT) {
+            cyc_local = false;
+            return verdict;
+        }
+        if (cyc_lds)
+            hipk_hand_back(lds_cycle_failed, handed, kernel());
+        else
+            hipk_path_add(handed, kernel());
+        cyc = cyc_lds = false;
+        return HIPK_REDO_HAND_BACK;
+    }
+};
+
+#define HIPK_GM_SEQ(name) (ext ? HIPK_FORM(name ", callback M") : HIPK_FORM(name))
+static const char *hipk_gm_seq_form(const hipk_gm_path &p, int m, bool ext) {   // the form of the path's launch sequence
+    return p.small ? (p.wide ? HIPK_GM_SEQ("gmres small + wide") : HIPK_GM_SEQ("gmres small + 256-thread"))
+           : m > HIPK_GM_MAXM ? (p.split_norm ? HIPK_GM_SEQ("gmres restart > 31 + split norm") : HIPK_GM_SEQ("gmres restart > 31"))
+           : p.stream_k ? (p.split_norm ? HIPK_GM_SEQ("gmres large, streaming + split norm") : HIPK_GM_SEQ("gmres large, streaming"))
+                        : (p.split_norm ? HIPK_GM_SEQ("gmres large, first kernels + split norm") : HIPK_GM_SEQ("gmres large, first kernels"));
+}
+#undef HIPK_GM_SEQ
+
+static constexpr int HIPK_GM_LOOP_TEST = 1;   // hipk_gm_solve::cycle_steps: nothing for the host to finish, the loop test comes next
+
+// One single-device solve: its operands, workspace, constants and state, and the steps hipk_gmres_solve_t drives it through.
 // dinv != nullptr: left Jacobi preconditioning -- every A(.) is followed by M(.) = dinv .* (.) (TSL:351, 791, 766), applied
 // by the SpMV epilogue (HIPK_SPMV_SCALE) before its fused dots; ptol from ||M b|| (TSL:750).  Mirrored by orc_gmres_jacobi.
 // cb != nullptr (dinv == nullptr): M is the CALLER's device code, cb(user, in, out) enqueues out = M(in) on `stream`.  It runs
 // in place on the vector the SpMV just wrote; the squared norm the Jacobi form fuses into the SpMV epilogue is then a
 // chunked dot of the preconditioned vector (one more pass over it).
 template <typename T>
-static int hipk_gmres_solve_t(hipk_csr_s *A, const T *dinv, const T *b, T *x, char *work, const hipk_params *prm,
-                              hipk_stats *st, hipStream_t stream, hipk_precond_fn cb = nullptr, void *user = nullptr) {
-    const bool ext = cb != nullptr;
-    const int64_t n = A->n_rows;
-    const hipk_geom gm = A->geom;
-    const int m = prm->restart;
-    const size_t vec = hipk_align_up((size_t)n * sizeof(T), 256);
-    const int64_t ldv = (int64_t)(vec / sizeof(T));
-    hipk_gm_scal *scal = (hipk_gm_scal *)work;
-    // restart > 31: H, R, the Givens pairs, beta, h and r live in a block of the workspace behind the header (hipk_gm_view)
-    const size_t big_n = hipk_gm_big_doubles(m);
-    double *big = big_n ? (double *)(work + kGmHeader) : nullptr;
-    double *parts = (double *)(work + kGmHeader + big_n * sizeof(double));
-    double *part_ww = parts, *part_qq = parts + HIPK_MAX_PARTS, *part_res = parts + 2 * HIPK_MAX_PARTS;
-    double *part_bb = parts + 3 * HIPK_MAX_PARTS, *part_xx = parts + 4 * HIPK_MAX_PARTS;
-    double *part_spare = parts + 5 * HIPK_MAX_PARTS;
-    double *part_md = parts + (size_t)kGmSlots * HIPK_MAX_PARTS;
-    char *vbase = (char *)parts + (size_t)(kGmSlots + m + 1) * HIPK_MAX_PARTS * sizeof(double);
-    T *V = (T *)vbase;
-    T *tmp = (T *)(vbase + (size_t)(m + 1) * vec);
-    const int incremental = (prm->gmres_method == HIPK_GMRES_INCREMENTAL) ? 1 : 0;
-    // guards (`_safe_normalize`, breakdown threshold) use the eps of the working dtype, as torch.finfo(dtype) would
-    const double eps_t = (sizeof(T) == 8) ? HIPK_EPS64 : HIPK_EPS32;
-    const int64_t maxiter = (prm->maxiter < 0) ? 10 * n : prm->maxiter;  // TSL:719-721
-    hipk_set_solve_path(nullptr, "");
-    char handed[128] = "";   // the one-launch kernels that handed this solve back
-    const char *last_cycle = "launch sequence";   // what ran the last restart cycle (none ran: the launch sequence's start and end)
+struct hipk_gm_solve {
+    hipk_csr_s *A;
+    const T *dinv, *b;
+    T *x;
+    hipk_precond_fn cb;
+    void *user;
+    hipStream_t stream;
+    const bool ext;        // M through the callback
+    const int scale_bit;   // of the SpMV modes: M = diag(dinv) in the epilogue
+    const int64_t n, maxiter;
+    const hipk_geom gm;
+    const int m, nt, incremental;
+    const double eps_t;   // guards (`_safe_normalize`, breakdown threshold) use the eps of the working dtype, as torch.finfo(dtype) would
+    const hipk_gm_layout<T> ws;
+    hipk_spmv_args sa;   // what every SpMV of the solve has in common
+    double atol_eff = 0.0, ptol = 0.0;
+    hipk_gm_path path;   // chosen once ||M b|| is known (hipk_gm_path_choose)
+    hipk_gm_run run;
+    hipk_gm_tally t;
 
-    hipk_event_pair whole;
-    HIPK_CHECK_HIP(whole.create());
-    hipk_spmv_profiler prof(prm->profile != 0 ? HIPK_K_SPMV : 0);
-    HIPK_CHECK_HIP(hipEventRecord(whole.a, stream));
+    hipk_gm_solve(hipk_csr_s *A_, const T *dinv_, const T *b_, T *x_, char *work, const hipk_params *prm, hipStream_t s, hipk_precond_fn cb_, void *user_)
+        : A(A_), dinv(dinv_), b(b_), x(x_), cb(cb_), user(user_), stream(s), ext(cb_ != nullptr), scale_bit(dinv_ ? HIPK_SPMV_SCALE : 0),
+          n(A_->n_rows), maxiter(prm->maxiter < 0 ? 10 * A_->n_rows : prm->maxiter),  // TSL:719-721
+          gm(A_->geom), m(prm->restart), nt((int)((A_->n_rows + HIPK_TILE - 1) / HIPK_TILE)),
+          incremental(prm->gmres_method == HIPK_GMRES_INCREMENTAL ? 1 : 0), eps_t(sizeof(T) == 8 ? HIPK_EPS64 : HIPK_EPS32),
+          ws(hipk_gm_layout<T>::make(work, prm->restart, hipk_align_up((size_t)A_->n_rows * sizeof(T), 256))) {
+        memset(&sa, 0, sizeof(sa));
+        sa.crow = A->crow;
+        sa.col = A->col;
+        sa.val = A->val;
+        sa.n = n;
+        sa.ch = gm.ch;
+        sa.g = gm.g;
+        sa.dscale = dinv;
+    }
 
-    hipk_spmv_args sa;
-    memset(&sa, 0, sizeof(sa));
-    sa.crow = A->crow;
-    sa.col = A->col;
-    sa.val = A->val;
-    sa.n = n;
-    sa.ch = gm.ch;
-    sa.g = gm.g;
-    sa.dscale = dinv;
-    const int scale_bit = dinv ? HIPK_SPMV_SCALE : 0;
-    int rc;
-    int64_t matvecs = 0;
     // ext: v <- M(v) by the caller, part[c] = chunk partials of <v,v>
-    auto precondition = [&](T *v, double *part) -> int {
+    int precondition(T *v, double *part) const {
         if (cb(user, v, v) != 0) {
             hipk_set_error("hipk_pgmres_solve_cb: the preconditioner callback failed");
             return HIPK_ERR_ARG;
         }
         return hipk_launch_dot_parts(n, v, v, A->dtype, part, stream);
-    };
+    }
 
-    // residual = M(b - A x0) into column 0, unit residual + norm (TSL:791-792); <b,b>
-    hipk_spmv_args sr = sa;
-    sr.x = x;
-    sr.y = V;
-    sr.mode = HIPK_SPMV_RESID | HIPK_SPMV_DOT_YY | scale_bit;
-    sr.bsub = b;
-    sr.part0 = part_spare;
-    sr.part1 = part_res;
-    if ((rc = hipk_launch_dot_parts(n, b, b, A->dtype, part_bb, stream)) != HIPK_OK) return rc;
-    if ((rc = hipk_launch_spmv(A, sr, stream)) != HIPK_OK) return rc;
-    ++matvecs;
-    if (ext && (rc = precondition(V, part_res)) != HIPK_OK) return rc;
-    hipk_gm_resnorm_kernel<T><<<gm.g, HIPK_THREADS, 0, stream>>>(n, gm.ch, gm.g, scal, V, part_res, part_bb, eps_t);
-    HIPK_CHECK_HIP(hipGetLastError());
-    double head[2];
-    HIPK_CHECK_HIP(hipMemcpyAsync(head, scal, sizeof(head), hipMemcpyDeviceToHost, stream));
-    HIPK_CHECK_HIP(hipStreamSynchronize(stream));
-    double res_norm = head[0];
-    const double bs = head[1];
-    const double b_norm = hipk_norm_from_sq(bs);
-
-    // TSL:735-753 (python floats become fp32 tensors; python max() keeps a float a float)
-    const double eps = HIPK_EPS64;  // the absolute floor keeps the fp64 eps also for fp32 storage (SURVEY A.5)
-    const double sq = sqrt((double)n);
-    const double cand = (prm->gpu_tolerances ? 1e-12 : 1e-14) * sq;
-    const double adaptive = (cand > prm->tol) ? cand : (double)(float)prm->tol;
-    const double base_atol = (double)(float)(eps * (prm->gpu_tolerances ? 1000 : 100) * (double)n);
-    const double atol_eff = hipk_tmax(adaptive * b_norm, hipk_tmax((double)(float)prm->atol, base_atol));
-    double mb_norm = b_norm;  // ||M b|| (TSL:750)
-    if (dinv || ext) {
-        if (ext) {  // M b through the spare vector (the callback sees workspace vectors only)
-            HIPK_CHECK_HIP(hipMemcpyAsync(tmp, b, (size_t)n * sizeof(T), hipMemcpyDeviceToDevice, stream));
-            if ((rc = precondition(tmp, part_spare)) != HIPK_OK) return rc;
-        } else {
-            hipk_gm_scaled_sq_kernel<T><<<gm.g, HIPK_THREADS, 0, stream>>>(n, gm.ch, b, dinv, part_spare);
-        }
-        double *mb_dev = part_xx;  // the <x,x> slot is unused until the end of the solve
-        if ((rc = hipk_launch_finish1(part_spare, gm.g, mb_dev, stream)) != HIPK_OK) return rc;
-        double mb2 = 0.0;
-        HIPK_CHECK_HIP(hipMemcpyAsync(&mb2, mb_dev, sizeof(double), hipMemcpyDeviceToHost, stream));
+    // y = M(b - A x), the chunk partials of its squared norm in part_res (TSL:791, 766)
+    int residual(T *y) {
+        hipk_spmv_args sr = sa;
+        sr.x = x;
+        sr.y = y;
+        sr.mode = HIPK_SPMV_RESID | HIPK_SPMV_DOT_YY | scale_bit;
+        sr.bsub = b;
+        sr.part0 = ws.part_spare;
+        sr.part1 = ws.part_res;
+        HIPK_TRY(hipk_launch_spmv(A, sr, stream));
+        ++t.matvecs;
+        if (ext) HIPK_TRY(precondition(y, ws.part_res));
+        return HIPK_OK;
+    }
+    // ... into column 0 as the unit residual a cycle starts from; head = {its norm, <b,b>} read back (TSL:791-792)
+    int start_residual(double (&head)[2]) {
+        HIPK_TRY(residual(ws.V));
+        hipk_gm_resnorm_kernel<T><<<gm.g, HIPK_THREADS, 0, stream>>>(n, gm.ch, gm.g, ws.scal, ws.V, ws.part_res, ws.part_bb, eps_t);
+        HIPK_CHECK_HIP(hipGetLastError());
+        HIPK_CHECK_HIP(hipMemcpyAsync(head, ws.scal, sizeof(head), hipMemcpyDeviceToHost, stream));
         HIPK_CHECK_HIP(hipStreamSynchronize(stream));
-        mb_norm = hipk_norm_from_sq(mb2);
+        t.res_norm = head[0];
+        return HIPK_OK;
     }
-    const double ptol = mb_norm * hipk_tmin(1.0, atol_eff / b_norm);
 
-    hipk_gm_scal *hs = (hipk_gm_scal *)malloc(sizeof(hipk_gm_scal));
-    if (!hs) {
-        hipk_set_error("out of host memory");
-        return HIPK_ERR_ARG;
+    // ||M b|| (TSL:750); M = identity: ||b||
+    int precond_b_norm(double b_norm, double *mb_norm) const {
+        *mb_norm = b_norm;
+        if (!dinv && !ext) return HIPK_OK;
+        if (ext) {  // M b through the spare vector (the callback sees workspace vectors only)
+            HIPK_CHECK_HIP(hipMemcpyAsync(ws.tmp, b, (size_t)n * sizeof(T), hipMemcpyDeviceToDevice, stream));
+            HIPK_TRY(precondition(ws.tmp, ws.part_spare));
+        } else {
+            hipk_gm_scaled_sq_kernel<T><<<gm.g, HIPK_THREADS, 0, stream>>>(n, gm.ch, b, dinv, ws.part_spare);
+        }
+        return hipk_gm_mb_norm(ws.part_spare, gm.g, ws.part_xx, stream, mb_norm);  // the <x,x> slot is unused until the end of the solve
     }
-    std::vector<double> big_host(big_n);
-    int64_t cycles = 0;
-    // which kernels the cycles run in (hipk_gm_path above); the latches: a one-launch cycle once handed a solve back in this process
-    static bool lds_cycle_failed = false, mid_failed = false;
-    const hipk_gm_path path = hipk_gm_path_choose<T>(A, prm, m, dinv != nullptr, ext, lds_cycle_failed, mid_failed, stream);
-    const bool small = path.small, wide = path.wide, lds_spread = path.lds_spread, stream_k = path.stream_k, md_wide = path.md_wide;
-    const bool split_norm = path.split_norm, spec = path.spec;
-    const int gm_nres = path.nres;
-    // a verdict of a launch below takes a one-launch form away for the rest of the solve
-    bool cyc = path.cyc, cyc_lds = path.cyc_lds, cyc_local = path.cyc_local, mid_cycle = path.mid_cycle;
-    const hipk_mid_entry<hipk_gm_mid_args> *mid = path.mid_entry;
-    const hipk_mid_plan &mid_plan = path.mid_plan;
-    const size_t mid_lds = path.mid_lds;
-    // the kernel a cycle enqueued below runs in (hipk_last_solve_path)
-    auto cycle_kernel = [&]() -> const char * {
-        return mid_cycle ? mid->name : !cyc ? "launch sequence" : cyc_lds ? "hipk_gm_solve_lds_kernel" : "hipk_gm_cycle_small_kernel";
-    };
-    // ... and its form (hipk_last_solve_form): the instantiation, or which launch sequence
-#define HIPK_GM_SEQ(name) (ext ? HIPK_FORM(name ", callback M") : HIPK_FORM(name))
-    const char *const seq_form = small ? (wide ? HIPK_GM_SEQ("gmres small + wide") : HIPK_GM_SEQ("gmres small + 256-thread"))
-                                 : m > HIPK_GM_MAXM ? (split_norm ? HIPK_GM_SEQ("gmres restart > 31 + split norm") : HIPK_GM_SEQ("gmres restart > 31"))
-                                 : stream_k ? (split_norm ? HIPK_GM_SEQ("gmres large, streaming + split norm") : HIPK_GM_SEQ("gmres large, streaming"))
-                                            : (split_norm ? HIPK_GM_SEQ("gmres large, first kernels + split norm") : HIPK_GM_SEQ("gmres large, first kernels"));
-#undef HIPK_GM_SEQ
-    auto cycle_form = [&]() -> const char * {
-        return mid_cycle ? mid->name
-               : !cyc    ? seq_form
-               : !cyc_lds ? (sizeof(T) == 8 ? HIPK_FORM("hipk_gm_cycle_small_kernel<double>") : HIPK_FORM("hipk_gm_cycle_small_kernel<float>"))
-               : cyc_local ? HIPK_FORM_OF_T(T, "hipk_gm_solve_lds_kernel<", "true>")
-                           : HIPK_FORM_OF_T(T, "hipk_gm_solve_lds_kernel<", "false>");
-    };
-    const char *last_form = seq_form;   // (none ran: the launch sequence's start and end)
-    // spec: second-pass launches only at the steps where a second CGS pass is expected (step 0, then every step that ever asked
-    // for one in this solve); a miss is caught on the device and the cycle re-enqueued from that step
-    bool predict[HIPK_GM_MAXM_BIG + 1];
-    for (int j = 0; j <= HIPK_GM_MAXM_BIG; ++j) predict[j] = (j == 0) && path.predict_step0;
-    int happy = 0;
-    int lds_launch_no = 0;
-    int64_t prof_valid = 0;
-    rc = HIPK_OK;
-    const int nt = (int)((n + HIPK_TILE - 1) / HIPK_TILE);
-    while (cycles < maxiter && res_norm > atol_eff) {
-        hipk_gm_cycle_init_kernel<<<1, HIPK_THREADS, 0, stream>>>(scal, incremental, ptol, big, m);
-        int k_start = 0;
-      enqueue:
-        if (cyc) {
-            hipk_gm_cyc_args<T> ca;
-            ca.n = n;
-            ca.g = gm.g;
-            ca.m = m;
-            ca.scal = scal;
-            ca.V = V;
-            ca.ldv = ldv;
-            ca.crow = A->crow;
-            ca.col = A->col;
-            ca.val = (const T *)A->val;
-            ca.dscale = dinv;
-            ca.part_md = part_md;
-            ca.part_qq = part_qq;
-            ca.tile_ww = A->tile_part + 4 * (size_t)nt;
-            ca.q = tmp;
-            ca.incremental = incremental;
-            ca.ptol = ptol;
-            ca.beta0 = res_norm;
-            ca.b = b;
-            ca.x = x;
-            ca.atol_eff = atol_eff;
-            ca.cycles_left = maxiter - cycles;
-            ca.max_cycles = (int)hipk_sw_int("HIPK_GM_LAUNCH_CYCLES", 64);   // (read per launch)
-            ca.test_not_resident = (++lds_launch_no == hipk_test_fail_launch()) ? 1 : 0;   // (one count for all one-launch kernels)
-            ca.bar = &scal->bar;
-            ca.eps = eps_t;
-            ca.stamps = hipk_sw_present("HIPK_GM_STAMPS") ? (unsigned long long *)(part_spare + 1600) : nullptr;
-            if (ca.stamps && cycles == 0) (void)hipMemsetAsync(ca.stamps, 0, 128, stream);
-            ca.spread = lds_spread ? 1 : 0;
-            ca.flag_a = (unsigned long long *)(part_spare + 512);   // 2 x 512 words
-            ca.flag_b = ca.flag_a + kHoMaxWg;
-            if (cyc_lds) (void)hipMemsetAsync(ca.flag_a, 0, 2 * kHoMaxWg * sizeof(unsigned long long), stream);
-            const int lgrid = lds_spread ? kGmSub * gm.g : 8 * kGmSub * gm.g;
-            if (cyc_lds && cyc_local)
-                hipk_gm_solve_lds_kernel<T, true><<<lgrid, HIPK_THREADS, hipk_gm_solve_lds_bytes<T>(m), stream>>>(ca);
-            else if (cyc_lds)
-                hipk_gm_solve_lds_kernel<T, false><<<lgrid, HIPK_THREADS, hipk_gm_solve_lds_bytes<T>(m), stream>>>(ca);
-            else
-                hipk_gm_cycle_small_kernel<T><<<8 * gm.g, HIPK_BASE_CHUNK / hipk_vec<T>::VEC, 0, stream>>>(ca);
+
+    // One launch of hipk_gm_cycle_small_kernel (a restart cycle) or hipk_gm_solve_lds_kernel (cycles until the solve stops)
+    void launch_cycle() {
+        hipk_gm_cyc_args<T> ca;
+        ca.n = n;
+        ca.g = gm.g;
+        ca.m = m;
+        ca.scal = ws.scal;
+        ca.V = ws.V;
+        ca.ldv = ws.ldv;
+        ca.crow = A->crow;
+        ca.col = A->col;
+        ca.val = (const T *)A->val;
+        ca.dscale = dinv;
+        ca.part_md = ws.part_md;
+        ca.part_qq = ws.part_qq;
+        ca.tile_ww = A->tile_part + 4 * (size_t)nt;
+        ca.q = ws.tmp;
+        ca.incremental = incremental;
+        ca.ptol = ptol;
+        ca.beta0 = t.res_norm;
+        ca.b = b;
+        ca.x = x;
+        ca.atol_eff = atol_eff;
+        ca.cycles_left = maxiter - t.cycles;
+        ca.max_cycles = (int)hipk_sw_int("HIPK_GM_LAUNCH_CYCLES", 64);   // (read per launch)
+        ca.test_not_resident = (++run.launch_no == hipk_test_fail_launch()) ? 1 : 0;
+        ca.bar = &ws.scal->bar;
+        ca.eps = eps_t;
+        ca.stamps = hipk_sw_present("HIPK_GM_STAMPS") ? (unsigned long long *)(ws.part_spare + 1600) : nullptr;
+        if (ca.stamps && t.cycles == 0) (void)hipMemsetAsync(ca.stamps, 0, 128, stream);
+        ca.spread = path.lds_spread ? 1 : 0;
+        ca.flag_a = (unsigned long long *)(ws.part_spare + 512);   // 2 x 512 words
+        ca.flag_b = ca.flag_a + kHoMaxWg;
+        if (run.cyc_lds) (void)hipMemsetAsync(ca.flag_a, 0, 2 * kHoMaxWg * sizeof(unsigned long long), stream);
+        const int lgrid = path.lds_spread ? kGmSub * gm.g : 8 * kGmSub * gm.g;
+        if (run.cyc_lds && run.cyc_local)
+            hipk_gm_solve_lds_kernel<T, true><<<lgrid, HIPK_THREADS, hipk_gm_solve_lds_bytes<T>(m), stream>>>(ca);
+        else if (run.cyc_lds)
+            hipk_gm_solve_lds_kernel<T, false><<<lgrid, HIPK_THREADS, hipk_gm_solve_lds_bytes<T>(m), stream>>>(ca);
+        else
+            hipk_gm_cycle_small_kernel<T><<<8 * gm.g, HIPK_BASE_CHUNK / hipk_vec<T>::VEC, 0, stream>>>(ca);
+    }
+
+    // One launch of hipk_gm_mid_kernel: the Arnoldi steps of a cycle (hipk_gm_mid.h)
+    void launch_mid() {
+        hipk_gm_mid_args ca;
+        memset(&ca, 0, sizeof(ca));
+        ca.n = n;
+        ca.g = gm.g;
+        ca.win = path.mid_plan.max_slots * HIPK_TILE;
+        ca.plan = path.mid_plan;
+        ca.m = m;
+        ca.crow = A->crow;
+        ca.col = A->col;
+        ca.val = A->val;
+        ca.V = ws.V;
+        ca.ldv = ws.ldv;
+        ca.v_ll = (unsigned long long *)ws.tail;      // behind the basis and tmp (hipk_gmres_work_bytes)
+        ca.slots = (unsigned long long *)(ws.tail + hipk_align_up((size_t)n * 16, 256));
+        ca.dinv = dinv;
+        ca.scal = ws.scal;
+        ca.eps = eps_t;
+        ca.slot_stride = 16;
+        ca.xcd_aware = 1;
+        ca.test_not_resident = (++run.launch_no == hipk_test_fail_launch()) ? 1 : 0;
+        (void)hipMemsetAsync(ca.v_ll, 0, hipk_align_up((size_t)n * 16, 256), stream);
+        (void)hipMemsetAsync(ca.slots, 0, (size_t)kGmMidKinds * gm.g * ca.slot_stride * 16, stream);
+        path.mid_entry->kern<<<hipk_xcd_grid(gm.g), 1024, path.mid_lds, stream>>>(ca);
+    }
+
+    // The multi-dot h = V^H w of step k, pass `pass`, in the kernel the path takes ...
+    void launch_multidot(int k, int pass, T *w) const {
+        const dim3 mgrid(gm.g, k / 8 + 1);
+        if (path.wide)
+            hipk_gm_multidot_wide_kernel<T><<<mgrid, HIPK_BASE_CHUNK / hipk_vec<T>::VEC, 0, stream>>>(n, ws.scal, k, pass, ws.V, ws.ldv, w, ws.part_md, ws.part_qq,
+                                                                                                    gm.g, eps_t);
+        else if (path.small || !path.stream_k) {
+            const auto kern = path.small ? hipk_gm_multidot_kernel<T, true> : hipk_gm_multidot_kernel<T, false>;
+            kern<<<mgrid, HIPK_THREADS, 0, stream>>>(n, gm.ch, ws.scal, k, pass, ws.V, ws.ldv, w, ws.part_md, ws.part_qq, gm.g, eps_t);
+        } else {
+            // streaming: NC columns per workgroup, one workgroup per chunk and group of 8 columns (md_wide: of up to 32)
+            auto md = [&](auto kern, int group) {
+                kern<<<gm.g * (k / group + 1), HIPK_THREADS, 0, stream>>>(n, gm.ch, ws.scal, k, pass, ws.V, ws.ldv, w, ws.part_md, gm.g, path.nres);
+            };
+            if (k == 0) md(hipk_gm_multidot_stream_kernel<T, 1>, 8);
+            else if (k == 1) md(hipk_gm_multidot_stream_kernel<T, 2>, 8);
+            else if (k < 4) md(hipk_gm_multidot_stream_kernel<T, 4>, 8);
+            else if (k < 8 || !path.md_wide) md(hipk_gm_multidot_stream_kernel<T, 8>, 8);
+            else if (k < 16) md(hipk_gm_multidot_stream_kernel<T, 16>, 16);
+            else md(hipk_gm_multidot_stream_kernel<T, 32>, 32);
         }
-        {
-            if (mid_cycle) {
-                hipk_gm_mid_args ca;
-                memset(&ca, 0, sizeof(ca));
-                ca.n = n;
-                ca.g = gm.g;
-                ca.win = mid_plan.max_slots * HIPK_TILE;
-                ca.plan = mid_plan;
-                ca.m = m;
-                ca.crow = A->crow;
-                ca.col = A->col;
-                ca.val = A->val;
-                ca.V = V;
-                ca.ldv = ldv;
-                ca.v_ll = (unsigned long long *)(vbase + (size_t)(m + 2) * vec);      // behind the basis and tmp (hipk_gmres_work_bytes)
-                ca.slots = (unsigned long long *)(vbase + (size_t)(m + 2) * vec + hipk_align_up((size_t)n * 16, 256));
-                ca.dinv = dinv;
-                ca.scal = scal;
-                ca.eps = eps_t;
-                ca.slot_stride = 16;
-                ca.xcd_aware = 1;
-                ca.test_not_resident = (++lds_launch_no == hipk_test_fail_launch()) ? 1 : 0;
-                (void)hipMemsetAsync(ca.v_ll, 0, hipk_align_up((size_t)n * 16, 256), stream);
-                (void)hipMemsetAsync(ca.slots, 0, (size_t)kGmMidKinds * gm.g * ca.slot_stride * 16, stream);
-                mid->kern<<<hipk_xcd_grid(gm.g), 1024, mid_lds, stream>>>(ca);
-            }
+    }
+    // ... and the update q = w - V h with ||q||^2
+    void launch_update(int k, int pass, T *w) const {
+        if (path.wide)
+            hipk_gm_update_wide_kernel<T><<<gm.g, HIPK_BASE_CHUNK / hipk_vec<T>::VEC, 0, stream>>>(n, ws.scal, k, pass, ws.V, ws.ldv, w, ws.part_qq, ws.part_md, gm.g);
+        else if (path.small || !path.stream_k) {
+            const auto kern = path.small ? hipk_gm_update_kernel<T, true> : hipk_gm_update_kernel<T, false>;
+            kern<<<gm.g, HIPK_THREADS, 0, stream>>>(n, gm.ch, ws.scal, k, pass, ws.V, ws.ldv, w, ws.part_qq, ws.part_md, gm.g);
+        } else {
+            auto up = [&](auto kern) { kern<<<gm.g, HIPK_THREADS, 0, stream>>>(n, gm.ch, ws.scal, k, pass, ws.V, ws.ldv, w, ws.part_qq, path.nres); };
+            if (k < 8) up(hipk_gm_update_stream_kernel<T, 8>);
+            else if (k < 32) up(hipk_gm_update_stream_kernel<T, 32>);
+            else up(hipk_gm_update_stream_kernel<T, 256>);
         }
-        for (int k = (cyc || mid_cycle) ? m : k_start; k < m; ++k) {
-            T *w = V + (int64_t)(k + 1) * ldv;
+    }
+
+    // Enqueues Arnoldi steps k_start .. m - 1 of the launch sequence; no host synchronisation: a step after the cycle's stop is a no-op
+    int enqueue_steps(int k_start, hipk_spmv_profiler *prof) const {
+        const bool small = path.small;
+        for (int k = k_start; k < m; ++k) {
+            T *w = ws.V + (int64_t)(k + 1) * ws.ldv;
             hipk_spmv_args sw = sa;
-            sw.x = V + (int64_t)k * ldv;
+            sw.x = ws.V + (int64_t)k * ws.ldv;
             sw.y = w;
             sw.skip_combine = small ? 1 : 0;  // small systems: hipk_gm_normalize_kernel folds the tile sums itself
             sw.mode = ext ? 0 : (HIPK_SPMV_DOT_YY | scale_bit);  // w = M(A v_k), ||w||^2 of the scaled vector (TSL:351-352)
-            sw.part0 = part_spare;
-            sw.part1 = part_ww;
-            sw.stop_it = &scal->stop_step;
+            sw.part0 = ws.part_spare;
+            sw.part1 = ws.part_ww;
+            sw.stop_it = &ws.scal->stop_step;
             sw.it = k;
-            if ((rc = hipk_launch_spmv(A, sw, stream, &prof)) != HIPK_OK) break;
-            if (ext && (rc = precondition(w, part_ww)) != HIPK_OK) break;  // w = M(A v_k), ||w||^2 (TSL:351-352)
-            const int npass = (spec && !predict[k]) ? 1 : 2;
+            HIPK_TRY(hipk_launch_spmv(A, sw, stream, prof));
+            if (ext) HIPK_TRY(precondition(w, ws.part_ww));  // w = M(A v_k), ||w||^2 (TSL:351-352)
+            const int npass = (path.spec && !run.predict[k]) ? 1 : 2;
             for (int pass = 0; pass < npass; ++pass) {
-                const dim3 mgrid(gm.g, k / 8 + 1);
-                if (small) {  // 7 instead of 10 launches per Arnoldi step (decide and the two hreduce folded away)
-                    if (wide)
-                        hipk_gm_multidot_wide_kernel<T><<<mgrid, HIPK_BASE_CHUNK / hipk_vec<T>::VEC, 0, stream>>>(
-                            n, scal, k, pass, V, ldv, w, part_md, part_qq, gm.g, eps_t);
-                    else
-                        hipk_gm_multidot_kernel<T, true><<<mgrid, HIPK_THREADS, 0, stream>>>(n, gm.ch, scal, k, pass, V, ldv, w,
-                                                                                             part_md, part_qq, gm.g, eps_t);
-                    if (wide)
-                        hipk_gm_update_wide_kernel<T><<<gm.g, HIPK_BASE_CHUNK / hipk_vec<T>::VEC, 0, stream>>>(
-                            n, scal, k, pass, V, ldv, w, part_qq, part_md, gm.g);
-                    else
-                        hipk_gm_update_kernel<T, true><<<gm.g, HIPK_THREADS, 0, stream>>>(n, gm.ch, scal, k, pass, V, ldv, w,
-                                                                                          part_qq, part_md, gm.g);
-                } else {
-                    if (pass == 1) hipk_gm_decide_kernel<<<1, HIPK_THREADS, 0, stream>>>(scal, k, gm.g, part_qq, eps_t);
-                    if (stream_k) {
-#define HIPK_MD(NC, GW) hipk_gm_multidot_stream_kernel<T, NC><<<gm.g * (k / GW + 1), HIPK_THREADS, 0, stream>>>(n, gm.ch, scal, k, pass, V, ldv, w, part_md, gm.g, gm_nres)
-                        if (k == 0) HIPK_MD(1, 8);
-                        else if (k == 1) HIPK_MD(2, 8);
-                        else if (k < 4) HIPK_MD(4, 8);
-                        else if (k < 8 || !md_wide) HIPK_MD(8, 8);
-                        else if (k < 16) HIPK_MD(16, 16);
-                        else HIPK_MD(32, 32);
-#undef HIPK_MD
-                    }
-                    else
-                        hipk_gm_multidot_kernel<T, false><<<mgrid, HIPK_THREADS, 0, stream>>>(n, gm.ch, scal, k, pass, V, ldv, w,
-                                                                                              part_md, part_qq, gm.g, eps_t);
-                    hipk_gm_hreduce_kernel<<<k + 1, HIPK_THREADS, 0, stream>>>(scal, k, pass, gm.g, part_md);
-                    if (stream_k && k < 8)
-                        hipk_gm_update_stream_kernel<T, 8><<<gm.g, HIPK_THREADS, 0, stream>>>(n, gm.ch, scal, k, pass, V, ldv, w,
-                                                                                               part_qq, gm_nres);
-                    else if (stream_k) {
-#define HIPK_UP(KC) hipk_gm_update_stream_kernel<T, KC><<<gm.g, HIPK_THREADS, 0, stream>>>(n, gm.ch, scal, k, pass, V, ldv, w, part_qq, gm_nres)
-                        if (k < 32) HIPK_UP(32);
-                        else HIPK_UP(256);
-#undef HIPK_UP
-                    } else
-                        hipk_gm_update_kernel<T, false><<<gm.g, HIPK_THREADS, 0, stream>>>(n, gm.ch, scal, k, pass, V, ldv, w,
-                                                                                           part_qq, part_md, gm.g);
-                }
+                // small: 7 instead of 10 launches per Arnoldi step (decide and the two hreduce folded away)
+                if (!small && pass == 1) hipk_gm_decide_kernel<<<1, HIPK_THREADS, 0, stream>>>(ws.scal, k, gm.g, ws.part_qq, eps_t);
+                launch_multidot(k, pass, w);
+                if (!small) hipk_gm_hreduce_kernel<<<k + 1, HIPK_THREADS, 0, stream>>>(ws.scal, k, pass, gm.g, ws.part_md);
+                launch_update(k, pass, w);
             }
-            if (split_norm) {   // large systems: one workgroup for the scalars, a flat grid for the scaling (see hipk_gm_hcol_kernel)
-                hipk_gm_hcol_kernel<<<1, HIPK_THREADS, 0, stream>>>(gm.g, scal, k, part_qq, part_ww, eps_t, npass == 1 ? 1 : 0,
-                                                                   sizeof(T) == 4 ? 1 : 0);
-                hipk_gm_scale_kernel<T><<<(unsigned)((n + HIPK_BASE_CHUNK - 1) / HIPK_BASE_CHUNK), HIPK_THREADS, 0, stream>>>(n, scal, k, w);
+            if (path.split_norm) {   // large systems: one workgroup for the scalars, a flat grid for the scaling (see hipk_gm_hcol_kernel)
+                hipk_gm_hcol_kernel<<<1, HIPK_THREADS, 0, stream>>>(gm.g, ws.scal, k, ws.part_qq, ws.part_ww, eps_t, npass == 1 ? 1 : 0, sizeof(T) == 4 ? 1 : 0);
+                hipk_gm_scale_kernel<T><<<(unsigned)((n + HIPK_BASE_CHUNK - 1) / HIPK_BASE_CHUNK), HIPK_THREADS, 0, stream>>>(n, ws.scal, k, w);
             } else
                 hipk_gm_normalize_kernel<T><<<gm.g, HIPK_THREADS, 0, stream>>>(
-                    n, gm.ch, gm.g, scal, k, w, part_qq, (small && !ext) ? A->tile_part + 4 * (size_t)nt : part_ww, eps_t,
+                    n, gm.ch, gm.g, ws.scal, k, w, ws.part_qq, (small && !ext) ? A->tile_part + 4 * (size_t)nt : ws.part_ww, eps_t,
                     (small && !ext) ? nt : 0, npass == 1 ? 1 : 0);
         }
-        if (rc != HIPK_OK) break;
-        if (hipGetLastError() != hipSuccess || hipMemcpyAsync(hs, scal, sizeof(*hs), hipMemcpyDeviceToHost, stream) != hipSuccess ||
-            (big_n && hipMemcpyAsync(big_host.data(), big, big_n * sizeof(double), hipMemcpyDeviceToHost, stream) != hipSuccess) ||
-            hipStreamSynchronize(stream) != hipSuccess) {
-            hipk_set_error("hipk_gmres_solve: HIP failure inside a restart cycle");
-            rc = HIPK_ERR_HIP;
-            break;
-        }
-        const hipk_redo_verdict verdict = hipk_redo_classify(hs->redo, cyc_lds && cyc_local);
-        if (verdict != HIPK_REDO_RAN && mid_cycle) {
-            // the workgroups of the one-launch step loop did not all arrive (nothing of the cycle is kept) or one of its hand-offs
-            // never completed
-            if (verdict == HIPK_REDO_ERROR) {
-                hipk_set_error("hipk_gmres_solve: a resident workgroup of the one-launch cycle stopped arriving");
-                rc = HIPK_ERR_HIP;
-                break;
+        return HIPK_OK;
+    }
+
+    // The Arnoldi steps of one restart cycle, in the form `run` is in.  HIPK_OK: the steps are in memory (hs: their scalars) and the
+    // host ends the cycle.  HIPK_GM_LOOP_TEST: a one-launch kernel handed the solve back or is to be launched again, or
+    // hipk_gm_solve_lds_kernel ran whole cycles, loop test included.  The latches are the caller's: one pair per dtype.
+    int cycle_steps(hipk_gm_host &hs, hipk_spmv_profiler *prof, bool &lds_cycle_failed, bool &mid_failed) {
+        for (int k_start = 0;;) {
+            if (run.cyc) launch_cycle();
+            if (run.mid_cycle) launch_mid();
+            if (!run.cyc && !run.mid_cycle) HIPK_TRY(enqueue_steps(k_start, prof));
+            HIPK_TRY(hs.read(ws.scal, ws.big, stream));
+            const hipk_redo_verdict verdict = run.take_verdict(hs->redo, lds_cycle_failed, mid_failed);
+            if (verdict == HIPK_REDO_ERROR) return HIPK_ERR_HIP;
+            if (verdict != HIPK_REDO_RAN) return HIPK_GM_LOOP_TEST;
+            run.last_cycle = run.kernel();
+            run.last_form = run.form<T>();
+            if (run.cyc && run.cyc_lds) {
+                t.cycles += hs->rep_cycles;
+                t.matvecs += hs->rep_matvecs;
+                if (hs->rep_breakdown) t.happy = 1;
+                t.res_norm = hs->res_norm;
+                if (hs->rep_status != 2) return HIPK_GM_LOOP_TEST;
+                // 2: the Arnoldi steps of one more cycle are in memory, its normal equations were not positive definite:
+                // the host ends that cycle with the general solve
             }
-            hipk_hand_back(mid_failed, handed, mid->name);
-            mid_cycle = false;
-            continue;
-        }
-        if (verdict != HIPK_REDO_RAN) {
-            // the resident workgroups of a one-launch cycle did not all arrive (the device is shared and they were not
-            // co-resident): nothing of the cycle is kept -- column 0 is untouched -- and this solve goes on with one launch
-            // per kernel
-            if (hipk_sw_present("HIPK_GM_STAMPS")) fprintf(stderr, "hipk_gmres_solve: one-launch cycle abandoned (workgroups not co-resident)\n");
-            if (verdict == HIPK_REDO_AGENT) {
-                cyc_local = false;      // its workgroups were spread over several XCDs: hand-offs at agent scope from now on
-            } else {
-                if (cyc_lds)
-                    hipk_hand_back(lds_cycle_failed, handed, cycle_kernel());
-                else
-                    hipk_path_add(handed, cycle_kernel());
-                cyc = cyc_lds = false;
-            }
-            continue;
-        }
-        last_cycle = cycle_kernel();
-        last_form = cycle_form();
-        if (cyc && cyc_lds) {  // hipk_gm_solve_lds_kernel ran whole cycles, loop test included
-            cycles += hs->rep_cycles;
-            matvecs += hs->rep_matvecs;
-            if (hs->rep_breakdown) happy = 1;
-            res_norm = hs->res_norm;
-            if (hs->rep_status != 2) continue;
-            // 2: the Arnoldi steps of one more cycle are in memory, its normal equations were not positive definite:
-            // the general solve and the rest of that cycle below
-        }
-        if (hs->redo > 0) {  // speculation miss: second pass wanted at redo_step; enqueue the cycle again from there
+            if (hs->redo <= 0) return HIPK_OK;
+            // speculation miss: a second pass was wanted at redo_step; the cycle is enqueued again from there
             k_start = (int)hs->redo_step;
-            predict[k_start] = true;
-            hipk_gm_resume_kernel<<<1, 1, 0, stream>>>(scal);
-            goto enqueue;
+            run.predict[k_start] = true;
+            hipk_gm_resume_kernel<<<1, 1, 0, stream>>>(ws.scal);
         }
+    }
+};
+
+// diagnostic build-in (HIPK_GM_STAMPS): where workgroup 0 of the cycle kernel spent its shader clocks
+static int hipk_gm_print_stamps(const double *part_spare, bool lds, int64_t cycles, int m, hipStream_t stream) {
+    unsigned long long st8[16];
+    HIPK_CHECK_HIP(hipMemcpyAsync(st8, part_spare + 1600, sizeof(st8), hipMemcpyDeviceToHost, stream));
+    HIPK_CHECK_HIP(hipStreamSynchronize(stream));
+    if (lds)
+        fprintf(stderr, "hipk_gm_solve_lds_kernel stamps (shader clocks of workgroup 0, thread 0; %lld cycles of %d steps): A SpMV %llu | "
+                        "multi-dot (+ CGS2 decision of the step before a second pass) %llu | hand-off 1 %llu | B: loads + fold %llu | wait %llu | "
+                        "update %llu | wait %llu | <q,q> %llu | hand-off 2 %llu | C: folds %llu | wait %llu | normalise + H column %llu | "
+                        "wait %llu | end of cycle: least squares %llu | x update, residual, norm %llu\n",
+                (long long)cycles, m, st8[0], st8[1], st8[2], st8[8], st8[9], st8[10], st8[11], st8[3], st8[4], st8[12], st8[13],
+                st8[14], st8[5], st8[6], st8[7]);
+    else
+        fprintf(stderr, "hipk_gm_cycle_small_kernel stamps (shader clocks of workgroup 0, thread 0; %lld cycles of %d steps): A SpMV %llu | "
+                        "multi-dot %llu | barrier 1 %llu | B fold + update %llu | barrier 2 %llu | C decide + normalise %llu | barrier 3 %llu\n",
+                (long long)cycles, m, st8[0], st8[1], st8[2], st8[3], st8[4], st8[5], st8[6]);
+    return HIPK_OK;
+}
+
+// `gmres` (TSL:641-803) on one device: start residual and tolerances, the cycle loop, the true residual and the stats
+template <typename T>
+static int hipk_gmres_solve_t(hipk_csr_s *A, const T *dinv, const T *b, T *x, char *work, const hipk_params *prm,
+                              hipk_stats *st, hipStream_t stream, hipk_precond_fn cb = nullptr, void *user = nullptr) {
+    hipk_gm_solve<T> s(A, dinv, b, x, work, prm, stream, cb, user);
+    const hipk_gm_layout<T> &ws = s.ws;
+    const hipk_geom gm = s.gm;
+    const int64_t n = s.n;
+    const int m = s.m;
+    hipk_set_solve_path(nullptr, "");
+    hipk_event_pair whole;
+    HIPK_CHECK_HIP(whole.create());
+    hipk_spmv_profiler prof(prm->profile != 0 ? HIPK_K_SPMV : 0);
+    HIPK_CHECK_HIP(hipEventRecord(whole.a, stream));
+
+    double head[2], mb_norm;
+    HIPK_TRY(hipk_launch_dot_parts(n, b, b, A->dtype, ws.part_bb, stream));
+    HIPK_TRY(s.start_residual(head));
+    const double b_norm = hipk_norm_from_sq(head[1]);
+    s.atol_eff = hipk_gm_atol_eff(prm, n, b_norm);
+    HIPK_TRY(s.precond_b_norm(b_norm, &mb_norm));
+    s.ptol = hipk_gm_ptol(mb_norm, s.atol_eff, b_norm);
+
+    // which kernels the cycles run in (hipk_gm_path above); the latches: a one-launch cycle once handed a solve back in this process
+    static bool lds_cycle_failed = false, mid_failed = false;
+    s.path = hipk_gm_path_choose<T>(A, prm, m, dinv != nullptr, s.ext, lds_cycle_failed, mid_failed, stream);
+    s.run.start(s.path, hipk_gm_seq_form(s.path, m, s.ext));
+    hipk_gm_host hs(ws.big_n);
+    int64_t prof_valid = 0;
+    while (s.t.cycles < s.maxiter && s.t.res_norm > s.atol_eff) {
+        hipk_gm_cycle_init_kernel<<<1, HIPK_THREADS, 0, stream>>>(ws.scal, s.incremental, s.ptol, ws.big, m);
+        const int rc = s.cycle_steps(hs, &prof, lds_cycle_failed, mid_failed);
+        if (rc == HIPK_GM_LOOP_TEST) continue;
+        HIPK_TRY(rc);
         const int k = (int)hs->steps_done;
-        matvecs += k;
-        if (prof_valid == cycles * m) prof_valid += k;  // leading launches that did work
-        if (hs->breakdown) happy = 1;
+        s.t.matvecs += k;
+        if (prof_valid == s.t.cycles * m) prof_valid += k;  // leading launches that did work
+        if (hs->breakdown) s.t.happy = 1;
         hipk_gm_yN<HIPK_GM_MAXM_BIG + 1> yb;
         memset(&yb, 0, sizeof(yb));
         if (k > 0) {
-            // the cycle's small arrays: the struct's own (ld 32) or the workspace block's host copy (hipk_gm_cycle_init_kernel's layout)
-            const int ldh = big_n ? hipk_gm_big_ld(m) : HIPK_GM_LDH;
-            const double *Hh = big_n ? big_host.data() : hs->H;
-            const double *Rh = big_n ? Hh + (size_t)(m + 2) * ldh : hs->R;
-            const double *bvh = big_n ? Rh + (size_t)ldh * ldh + 2 * ldh : hs->beta_vec;
-            if (!incremental) {
-                hipk_lstsq_normal(Hh, ldh, k, res_norm, yb.y);
-            } else {
-                for (int i = k - 1; i >= 0; --i) {  // solve_triangular, TSL:630
-                    double s = bvh[i];
-                    for (int p = i + 1; p < k; ++p) s = fma(-Rh[i * ldh + p], yb.y[p], s);
-                    yb.y[i] = s / Rh[i * ldh + i];
-                }
-            }
-            if (k <= HIPK_GM_LDH) {
-                hipk_gm_y yy;
-                memcpy(yy.y, yb.y, sizeof(yy.y));
-                hipk_gm_xupdate_kernel<T><<<gm.g, HIPK_THREADS, 0, stream>>>(n, gm.ch, k, V, ldv, x, yy);
-            } else {
-                hipk_gm_xupdate_kernel<T, HIPK_GM_MAXM_BIG + 1><<<gm.g, HIPK_THREADS, 0, stream>>>(n, gm.ch, k, V, ldv, x, yb);
-            }
+            hs.solve_y(m, k, s.incremental, s.t.res_norm, yb.y);
+            hipk_gm_xupdate<T>(gm.g, n, gm.ch, k, ws.V, ws.ldv, x, yb, stream);
         }
-        if ((rc = hipk_launch_spmv(A, sr, stream)) != HIPK_OK) break;
-        ++matvecs;
-        if (ext && (rc = precondition(V, part_res)) != HIPK_OK) break;
-        hipk_gm_resnorm_kernel<T><<<gm.g, HIPK_THREADS, 0, stream>>>(n, gm.ch, gm.g, scal, V, part_res, part_bb, eps_t);
-        if (hipGetLastError() != hipSuccess || hipMemcpyAsync(head, scal, sizeof(head), hipMemcpyDeviceToHost, stream) != hipSuccess ||
-            hipStreamSynchronize(stream) != hipSuccess) {
-            hipk_set_error("hipk_gmres_solve: HIP failure at the end of a restart cycle");
-            rc = HIPK_ERR_HIP;
-            break;
-        }
-        res_norm = head[0];
-        ++cycles;
+        HIPK_TRY(s.start_residual(head));
+        ++s.t.cycles;
     }
-    free(hs);
-    if (rc != HIPK_OK) return rc;
-    hipk_set_solve_path(handed, last_cycle);
-    hipk_set_solve_form(last_form);
-    if ((cyc || cyc_lds) && hipk_sw_present("HIPK_GM_STAMPS")) {  // diagnostic build-in: where workgroup 0 of the cycle kernel spent its shader clocks
-        unsigned long long st8[16];
-        HIPK_CHECK_HIP(hipMemcpyAsync(st8, part_spare + 1600, sizeof(st8), hipMemcpyDeviceToHost, stream));
-        HIPK_CHECK_HIP(hipStreamSynchronize(stream));
-        if (cyc_lds)
-            fprintf(stderr, "hipk_gm_solve_lds_kernel stamps (shader clocks of workgroup 0, thread 0; %lld cycles of %d steps): A SpMV %llu | "
-                            "multi-dot (+ CGS2 decision of the step before a second pass) %llu | hand-off 1 %llu | B: loads + fold %llu | wait %llu | "
-                            "update %llu | wait %llu | <q,q> %llu | hand-off 2 %llu | C: folds %llu | wait %llu | normalise + H column %llu | "
-                            "wait %llu | end of cycle: least squares %llu | x update, residual, norm %llu\n",
-                    (long long)cycles, m, st8[0], st8[1], st8[2], st8[8], st8[9], st8[10], st8[11], st8[3], st8[4], st8[12], st8[13],
-                    st8[14], st8[5], st8[6], st8[7]);
-        else
-            fprintf(stderr, "hipk_gm_cycle_small_kernel stamps (shader clocks of workgroup 0, thread 0; %lld cycles of %d steps): A SpMV %llu | "
-                            "multi-dot %llu | barrier 1 %llu | B fold + update %llu | barrier 2 %llu | C decide + normalise %llu | barrier 3 %llu\n",
-                    (long long)cycles, m, st8[0], st8[1], st8[2], st8[3], st8[4], st8[5], st8[6]);
-    }
+    hipk_set_solve_path(s.run.handed, s.run.last_cycle);
+    hipk_set_solve_form(s.run.last_form);
+    if ((s.run.cyc || s.run.cyc_lds) && hipk_sw_present("HIPK_GM_STAMPS")) HIPK_TRY(hipk_gm_print_stamps(ws.part_spare, s.run.cyc_lds, s.t.cycles, m, stream));
 
     // TSL:766-773
-    hipk_spmv_args sf = sr;
-    sf.y = tmp;
-    if ((rc = hipk_launch_spmv(A, sf, stream)) != HIPK_OK) return rc;
-    ++matvecs;
-    if (ext && (rc = precondition(tmp, part_res)) != HIPK_OK) return rc;
-    if ((rc = hipk_launch_dot_parts(n, x, x, A->dtype, part_xx, stream)) != HIPK_OK) return rc;
-    hipk_gm_final_kernel<<<1, HIPK_THREADS, 0, stream>>>(scal, gm.g, part_res, part_xx);
-    HIPK_CHECK_HIP(hipGetLastError());
-    double fin[4];
-    HIPK_CHECK_HIP(hipEventRecord(whole.b, stream));
-    HIPK_CHECK_HIP(hipMemcpyAsync(fin, scal, sizeof(fin), hipMemcpyDeviceToHost, stream));
-    HIPK_CHECK_HIP(hipStreamSynchronize(stream));
-    st->iterations = cycles;
-    st->matvecs = matvecs;
-    st->b_norm = b_norm;
-    st->residual_norm = hipk_norm_from_sq(fin[2]);
-    st->x_norm = hipk_norm_from_sq(fin[3]);
-    st->threshold = atol_eff * 10;  // TSL:769
-    st->info = (isnan(st->x_norm) || st->residual_norm > st->threshold) ? -1 : 0;
-    st->breakdown = happy;
-    st->recurrence_rs = res_norm;
-    float ms = 0.f;
-    HIPK_CHECK_HIP(hipEventElapsedTime(&ms, whole.a, whole.b));
-    st->solve_ms = ms;
+    HIPK_TRY(s.residual(ws.tmp));
+    HIPK_TRY(hipk_launch_dot_parts(n, x, x, A->dtype, ws.part_xx, stream));
+    hipk_gm_final_kernel<<<1, HIPK_THREADS, 0, stream>>>(ws.scal, gm.g, ws.part_res, ws.part_xx);
+    HIPK_TRY(hipk_gm_finish_stats(st, ws.scal, whole, stream, s.t, b_norm, s.atol_eff));
     HIPK_CHECK_HIP(prof.collect(st, prof_valid));
     return HIPK_OK;
 }
 
-extern "C" int hipk_gmres_solve(hipk_csr_t A, const void *b, void *x, void *work, size_t work_bytes,
-                                const hipk_params *prm, hipk_stats *st, hipk_stream_t stream) {
-    HIPK_REQUIRE(A && b && x && work && prm && st, HIPK_ERR_ARG, "null argument");
+// the checks and the dispatch on the operand's dtype the three entries share (have_m: the entry's dinv or M is not null)
+static int hipk_gmres_entry(hipk_csr_t A, bool have_m, const void *dinv, hipk_precond_fn M, void *user, const void *b, void *x, void *work,
+                            size_t work_bytes, const hipk_params *prm, hipk_stats *st, hipk_stream_t stream) {
+    HIPK_REQUIRE(A && have_m && b && x && work && prm && st, HIPK_ERR_ARG, "null argument");
     HIPK_REQUIRE(A->n_rows == A->n_cols, HIPK_ERR_ARG, "linear operator must be a square matrix");
     HIPK_REQUIRE(A->n_rows > 0, HIPK_ERR_ARG, "empty system");
-    HIPK_REQUIRE(prm->restart >= 1 && prm->restart <= HIPK_GM_MAXM_BIG, HIPK_ERR_UNSUPPORTED,
-                 "restart must be in [1, 255] on the HIP path");
-    HIPK_REQUIRE(prm->gmres_method == HIPK_GMRES_BATCHED || prm->gmres_method == HIPK_GMRES_INCREMENTAL, HIPK_ERR_ARG,
-                 "Unsupported solve_method");
-    HIPK_REQUIRE(hipk_aligned16(b) && hipk_aligned16(x) && (((uintptr_t)work) & 255u) == 0, HIPK_ERR_ALIGN,
-                 "b/x must be 16-byte and work 256-byte aligned");
-    HIPK_REQUIRE(work_bytes >= hipk_gmres_work_bytes(A->n_rows, prm->restart, A->dtype), HIPK_ERR_WORKSPACE,
-                 "work too small");
+    HIPK_REQUIRE(prm->restart >= 1 && prm->restart <= HIPK_GM_MAXM_BIG, HIPK_ERR_UNSUPPORTED, "restart must be in [1, 255] on the HIP path");
+    HIPK_REQUIRE(prm->gmres_method == HIPK_GMRES_BATCHED || prm->gmres_method == HIPK_GMRES_INCREMENTAL, HIPK_ERR_ARG, "Unsupported solve_method");
+    HIPK_REQUIRE(hipk_aligned16(b) && hipk_aligned16(x) && hipk_aligned16(dinv) && (((uintptr_t)work) & 255u) == 0, HIPK_ERR_ALIGN,
+                 dinv ? "b/x/dinv must be 16-byte and work 256-byte aligned" : "b/x must be 16-byte and work 256-byte aligned");
+    HIPK_REQUIRE(work_bytes >= hipk_gmres_work_bytes(A->n_rows, prm->restart, A->dtype), HIPK_ERR_WORKSPACE, "work too small");
     HIPK_REQUIRE(b != x, HIPK_ERR_ARG, "b and x must not alias");
     memset(st, 0, sizeof(*st));
     if (A->dtype == HIPK_F64)
-        return hipk_gmres_solve_t<double>(A, nullptr, (const double *)b, (double *)x, (char *)work, prm, st,
-                                          (hipStream_t)stream);
-    return hipk_gmres_solve_t<float>(A, nullptr, (const float *)b, (float *)x, (char *)work, prm, st, (hipStream_t)stream);
+        return hipk_gmres_solve_t<double>(A, (const double *)dinv, (const double *)b, (double *)x, (char *)work, prm, st, (hipStream_t)stream, M, user);
+    return hipk_gmres_solve_t<float>(A, (const float *)dinv, (const float *)b, (float *)x, (char *)work, prm, st, (hipStream_t)stream, M, user);
+}
+
+extern "C" int hipk_gmres_solve(hipk_csr_t A, const void *b, void *x, void *work, size_t work_bytes,
+                                const hipk_params *prm, hipk_stats *st, hipk_stream_t stream) {
+    return hipk_gmres_entry(A, true, nullptr, nullptr, nullptr, b, x, work, work_bytes, prm, st, stream);
 }
 
 extern "C" int hipk_pgmres_solve(hipk_csr_t A, const void *dinv, const void *b, void *x, void *work, size_t work_bytes,
                                  const hipk_params *prm, hipk_stats *st, hipk_stream_t stream) {
-    HIPK_REQUIRE(A && dinv && b && x && work && prm && st, HIPK_ERR_ARG, "null argument");
-    HIPK_REQUIRE(A->n_rows == A->n_cols, HIPK_ERR_ARG, "linear operator must be a square matrix");
-    HIPK_REQUIRE(A->n_rows > 0, HIPK_ERR_ARG, "empty system");
-    HIPK_REQUIRE(prm->restart >= 1 && prm->restart <= HIPK_GM_MAXM_BIG, HIPK_ERR_UNSUPPORTED,
-                 "restart must be in [1, 255] on the HIP path");
-    HIPK_REQUIRE(prm->gmres_method == HIPK_GMRES_BATCHED || prm->gmres_method == HIPK_GMRES_INCREMENTAL, HIPK_ERR_ARG,
-                 "Unsupported solve_method");
-    HIPK_REQUIRE(hipk_aligned16(b) && hipk_aligned16(x) && hipk_aligned16(dinv) && (((uintptr_t)work) & 255u) == 0,
-                 HIPK_ERR_ALIGN, "b/x/dinv must be 16-byte and work 256-byte aligned");
-    HIPK_REQUIRE(work_bytes >= hipk_gmres_work_bytes(A->n_rows, prm->restart, A->dtype), HIPK_ERR_WORKSPACE,
-                 "work too small");
-    HIPK_REQUIRE(b != x, HIPK_ERR_ARG, "b and x must not alias");
-    memset(st, 0, sizeof(*st));
-    if (A->dtype == HIPK_F64)
-        return hipk_gmres_solve_t<double>(A, (const double *)dinv, (const double *)b, (double *)x, (char *)work, prm, st,
-                                          (hipStream_t)stream);
-    return hipk_gmres_solve_t<float>(A, (const float *)dinv, (const float *)b, (float *)x, (char *)work, prm, st,
-                                     (hipStream_t)stream);
+    return hipk_gmres_entry(A, dinv != nullptr, dinv, nullptr, nullptr, b, x, work, work_bytes, prm, st, stream);
 }
 
 extern "C" int hipk_pgmres_solve_cb(hipk_csr_t A, hipk_precond_fn M, void *user, const void *b, void *x, void *work,
                                     size_t work_bytes, const hipk_params *prm, hipk_stats *st, hipk_stream_t stream) {
-    HIPK_REQUIRE(A && M && b && x && work && prm && st, HIPK_ERR_ARG, "null argument");
-    HIPK_REQUIRE(A->n_rows == A->n_cols, HIPK_ERR_ARG, "linear operator must be a square matrix");
-    HIPK_REQUIRE(A->n_rows > 0, HIPK_ERR_ARG, "empty system");
-    HIPK_REQUIRE(prm->restart >= 1 && prm->restart <= HIPK_GM_MAXM_BIG, HIPK_ERR_UNSUPPORTED,
-                 "restart must be in [1, 255] on the HIP path");
-    HIPK_REQUIRE(prm->gmres_method == HIPK_GMRES_BATCHED || prm->gmres_method == HIPK_GMRES_INCREMENTAL, HIPK_ERR_ARG,
-                 "Unsupported solve_method");
-    HIPK_REQUIRE(hipk_aligned16(b) && hipk_aligned16(x) && (((uintptr_t)work) & 255u) == 0, HIPK_ERR_ALIGN,
-                 "b/x must be 16-byte and work 256-byte aligned");
-    HIPK_REQUIRE(work_bytes >= hipk_gmres_work_bytes(A->n_rows, prm->restart, A->dtype), HIPK_ERR_WORKSPACE,
-                 "work too small");
-    HIPK_REQUIRE(b != x, HIPK_ERR_ARG, "b and x must not alias");
-    memset(st, 0, sizeof(*st));
-    if (A->dtype == HIPK_F64)
-        return hipk_gmres_solve_t<double>(A, nullptr, (const double *)b, (double *)x, (char *)work, prm, st,
-                                          (hipStream_t)stream, M, user);
-    return hipk_gmres_solve_t<float>(A, nullptr, (const float *)b, (float *)x, (char *)work, prm, st, (hipStream_t)stream, M,
-                                     user);
+    return hipk_gmres_entry(A, M != nullptr, nullptr, M, user, b, x, work, work_bytes, prm, st, stream);
 }
-
 
 // =====================================================================================================================
 // Row-partitioned GMRES, the loop of one rank in C (new against the reference, which is single-device).  The algorithm is `gmres`
@@ -2843,8 +2914,7 @@ static size_t hipk_dgm_vec_bytes(const hipk_dist_plan *pl) {
 // workspace of either form at restart m (hipk_gm_big_doubles(m) is 0 up to 31)
 static size_t hipk_dgm_work_bytes(const hipk_dist_plan *plan, int m) {
     const size_t slab = (size_t)(plan->slab > 0 ? plan->slab : 1);
-    return kGmHeader + hipk_gm_big_doubles(m) * sizeof(double) + (size_t)(kGmSlots + m + 1) * HIPK_MAX_PARTS * sizeof(double) +
-           (size_t)(m + 2) * hipk_dgm_vec_bytes(plan) + hipk_align_up((size_t)(plan->n_send > 0 ? plan->n_send : 1) * 8, 256) +
+    return hipk_gm_layout_bytes(m, hipk_dgm_vec_bytes(plan)) + hipk_align_up((size_t)(plan->n_send > 0 ? plan->n_send : 1) * 8, 256) +
            hipk_align_up(slab * 8, 256) + hipk_align_up(slab * (size_t)plan->world * 8, 256);
 }
 extern "C" size_t hipk_dist_gmres_work_bytes(const hipk_dist_plan *plan, int restart) {
@@ -2877,26 +2947,17 @@ static int hipk_dist_gmres_t(bool pre, bool wide, hipk_csr_t A, const hipk_dist_
     const int gl = (int)((n + ch - 1) / ch);             // local chunks = grid of the vector kernels
     const int c0 = pl->rank * per;                       // this rank's position in the global partial arrays
     const int m = prm->restart;
-    const size_t vec = hipk_dgm_vec_bytes(pl);
-    const int64_t ldv = (int64_t)(vec / sizeof(T));
-    hipk_gm_scal *scal = (hipk_gm_scal *)work;
-    const size_t big_n = hipk_gm_big_doubles(m);          // wide: the cycle's small arrays (0 up to restart 31)
-    double *big = big_n ? (double *)(work + kGmHeader) : nullptr;
-    std::vector<double> big_host(big_n);
-    double *parts = (double *)(work + kGmHeader + big_n * sizeof(double));
-    double *part_ww = parts, *part_qq = parts + HIPK_MAX_PARTS, *part_res = parts + 2 * HIPK_MAX_PARTS;
-    double *part_bb = parts + 3 * HIPK_MAX_PARTS, *part_xx = parts + 4 * HIPK_MAX_PARTS;
-    double *part_spare = parts + 5 * HIPK_MAX_PARTS;
-    double *part_md = parts + (size_t)kGmSlots * HIPK_MAX_PARTS;
-    char *vbase = (char *)parts + (size_t)(kGmSlots + m + 1) * HIPK_MAX_PARTS * sizeof(double);
-    T *V = (T *)vbase;
-    T *tmp = (T *)(vbase + (size_t)(m + 1) * vec);
-    char *cbase = vbase + (size_t)(m + 2) * vec;
+    const hipk_gm_layout<T> lay = hipk_gm_layout<T>::make(work, m, hipk_dgm_vec_bytes(pl));
+    hipk_gm_scal *scal = lay.scal;
+    double *part_ww = lay.part_ww, *part_qq = lay.part_qq, *part_res = lay.part_res, *part_bb = lay.part_bb, *part_xx = lay.part_xx;
+    double *part_spare = lay.part_spare, *part_md = lay.part_md;
+    T *V = lay.V, *tmp = lay.tmp;
+    const int64_t ldv = lay.ldv;
+    char *cbase = lay.tail;   // the exchange buffers: send slab, this rank's block, everybody's
     double *slab_loc = (double *)(cbase + hipk_align_up((size_t)(pl->n_send > 0 ? pl->n_send : 1) * 8, 256));
     double *slab_all = (double *)((char *)slab_loc + hipk_align_up((size_t)(pl->slab > 0 ? pl->slab : 1) * 8, 256));
     const char *who = wide ? (pre ? "hipk_dist_pgmres_wide_solve" : "hipk_dist_gmres_wide_solve")
                            : (pre ? "hipk_dist_pgmres_solve" : "hipk_dist_gmres_solve");
-    const char *loop = wide ? who : "hipk_dist_gmres_solve";   // the name in the texts of a HIP failure
     const hipk_dist_xchg xc(pl, cc, stream, (double *)cbase, slab_loc, slab_all, who);
     T *x = (T *)x_ext;
     const T *b = (const T *)b_local;
@@ -2910,56 +2971,40 @@ static int hipk_dist_gmres_t(bool pre, bool wide, hipk_csr_t A, const hipk_dist_
     HIPK_CHECK_HIP(hipMemsetAsync(work, 0, need, stream));
     if (n_ext > n) HIPK_CHECK_HIP(hipMemsetAsync(x + n, 0, (size_t)(n_ext - n) * 8, stream));
 
-    // residual = b - A x0 into column 0, unit residual + norm (TSL:791-792); <b,b>
+    // residual = b - A x0 into column 0, unit residual + norm (TSL:791-792), read back with <b,b>
+    hipk_gm_tally t;
+    double head[2];
     auto residual = [&]() -> int {
         HIPK_TRY(xc.run(x));
         // with dinv: M (b - A x0), its squared norm (TSL:791)
         HIPK_TRY(hipk_dist_spmv(A, x, V, HIPK_SPMV_RESID | HIPK_SPMV_DOT_YY, nullptr, b, dinv, part_spare + c0, part_res + c0, nullptr, 0, stream));
         HIPK_TRY(xc.parts(part_res));
         hipk_gm_resnorm_kernel<T><<<gl, HIPK_THREADS, 0, stream>>>(n, ch, G, scal, V, part_res, part_bb, eps_t);
-        return hipGetLastError() == hipSuccess ? HIPK_OK : HIPK_ERR_HIP;
+        HIPK_CHECK_HIP(hipGetLastError());
+        ++t.matvecs;
+        HIPK_CHECK_HIP(hipMemcpyAsync(head, scal, sizeof(head), hipMemcpyDeviceToHost, stream));
+        HIPK_CHECK_HIP(hipStreamSynchronize(stream));
+        t.res_norm = head[0];
+        return HIPK_OK;
     };
     HIPK_TRY(hipk_dot_parts(n, ch, b, b, HIPK_F64, part_bb + c0, stream));
     HIPK_TRY(xc.parts(part_bb));
     HIPK_TRY(residual());
-    int64_t matvecs = 1;
-    double head[2];
-    HIPK_CHECK_HIP(hipMemcpyAsync(head, scal, sizeof(head), hipMemcpyDeviceToHost, stream));
-    HIPK_CHECK_HIP(hipStreamSynchronize(stream));
-    double res_norm = head[0];
-    const double bs = head[1];
-    const double b_norm = hipk_norm_from_sq(bs);
-    // TSL:735-753 on the GLOBAL size
-    const double eps = HIPK_EPS64;
-    const double ng = (double)pl->n_global;
-    const double cand = (prm->gpu_tolerances ? 1e-12 : 1e-14) * sqrt(ng);
-    const double adaptive = (cand > prm->tol) ? cand : (double)(float)prm->tol;
-    const double base_atol = (double)(float)(eps * (prm->gpu_tolerances ? 1000 : 100) * ng);
-    const double atol_eff = hipk_tmax(adaptive * b_norm, hipk_tmax((double)(float)prm->atol, base_atol));
+    const double b_norm = hipk_norm_from_sq(head[1]);
+    const double atol_eff = hipk_gm_atol_eff(prm, pl->n_global, b_norm);
     double mb_norm = b_norm;  // ||M b|| (TSL:750)
     if (dinv) {
         hipk_gm_scaled_sq_kernel<T><<<gl, HIPK_THREADS, 0, stream>>>(n, ch, b, dinv, part_spare + c0);
         HIPK_CHECK_HIP(hipGetLastError());
         HIPK_TRY(xc.parts(part_spare));
-        double *mb_dev = part_xx;  // the <x,x> slot is unused until the end of the solve
-        HIPK_TRY(hipk_reduce_parts(part_spare, G, mb_dev, stream));
-        double mb2 = 0.0;
-        HIPK_CHECK_HIP(hipMemcpyAsync(&mb2, mb_dev, sizeof(double), hipMemcpyDeviceToHost, stream));
-        HIPK_CHECK_HIP(hipStreamSynchronize(stream));
-        mb_norm = hipk_norm_from_sq(mb2);
+        HIPK_TRY(hipk_gm_mb_norm(part_spare, G, part_xx, stream, &mb_norm));  // the <x,x> slot is unused until the end of the solve
     }
-    const double ptol = mb_norm * hipk_tmin(1.0, atol_eff / b_norm);
+    const double ptol = hipk_gm_ptol(mb_norm, atol_eff, b_norm);
 
-    std::vector<unsigned char> hs_buf(sizeof(hipk_gm_scal));
-    hipk_gm_scal *hs = (hipk_gm_scal *)hs_buf.data();
+    hipk_gm_host hs(lay.big_n);   // wide: with the cycle's small arrays
     const int nres = 5;
-    int64_t cycles = 0;
-    int happy = 0;
-    while (cycles < maxiter && res_norm > atol_eff) {
-        if (wide)
-            hipk_gm_cycle_init_kernel<<<1, HIPK_THREADS, 0, stream>>>(scal, incremental, ptol, big, m);
-        else
-            hipk_gm_cycle_init_kernel<<<1, HIPK_THREADS, 0, stream>>>(scal, incremental, ptol);
+    while (t.cycles < maxiter && t.res_norm > atol_eff) {
+        hipk_gm_cycle_init_kernel<<<1, HIPK_THREADS, 0, stream>>>(scal, incremental, ptol, lay.big, m);   // (big == null: m is not read)
         for (int k = 0; k < m; ++k) {
             T *vk = V + (int64_t)k * ldv, *w = V + (int64_t)(k + 1) * ldv;
             HIPK_TRY(xc.run(vk));
@@ -2992,76 +3037,29 @@ static int hipk_dist_gmres_t(bool pre, bool wide, hipk_csr_t A, const hipk_dist_
             }
             hipk_gm_normalize_kernel<T><<<gl, HIPK_THREADS, 0, stream>>>(n, ch, G, scal, k, w, part_qq, part_ww, eps_t, 0, 0);
         }
-        if (hipGetLastError() != hipSuccess || hipMemcpyAsync(hs, scal, sizeof(*hs), hipMemcpyDeviceToHost, stream) != hipSuccess ||
-            (big_n && hipMemcpyAsync(big_host.data(), big, big_n * sizeof(double), hipMemcpyDeviceToHost, stream) != hipSuccess) ||
-            hipStreamSynchronize(stream) != hipSuccess) {
-            hipk_set_error("%s: HIP failure inside a restart cycle", loop);
-            return HIPK_ERR_HIP;
-        }
+        HIPK_TRY(hs.read(scal, lay.big, stream));
         const int k = (int)hs->steps_done;
-        matvecs += k;
-        if (hs->breakdown) happy = 1;
+        t.matvecs += k;
+        if (hs->breakdown) t.happy = 1;
         hipk_gm_yN<HIPK_GM_MAXM_BIG + 1> yb;
         memset(&yb, 0, sizeof(yb));
-        if (k > 0) {
-            // the cycle's small arrays: the struct's own (ld 32) or the workspace block's host copy (hipk_gm_cycle_init_kernel's layout)
-            const int ldh = big_n ? hipk_gm_big_ld(m) : HIPK_GM_LDH;
-            const double *Hh = big_n ? big_host.data() : hs->H;
-            const double *Rh = big_n ? Hh + (size_t)(m + 2) * ldh : hs->R;
-            const double *bvh = big_n ? Rh + (size_t)ldh * ldh + 2 * ldh : hs->beta_vec;
-            if (!incremental) {
-                hipk_lstsq_normal(Hh, ldh, k, res_norm, yb.y);
-            } else {
-                for (int i = k - 1; i >= 0; --i) {  // solve_triangular, TSL:630
-                    double sacc = bvh[i];
-                    for (int p = i + 1; p < k; ++p) sacc = fma(-Rh[i * ldh + p], yb.y[p], sacc);
-                    yb.y[i] = sacc / Rh[i * ldh + i];
-                }
-            }
-            if (k <= HIPK_GM_LDH) {
-                hipk_gm_y yy;
-                memcpy(yy.y, yb.y, sizeof(yy.y));
-                hipk_gm_xupdate_kernel<T><<<gl, HIPK_THREADS, 0, stream>>>(n, ch, k, V, ldv, x, yy);
-            } else {
-                hipk_gm_xupdate_kernel<T, HIPK_GM_MAXM_BIG + 1><<<gl, HIPK_THREADS, 0, stream>>>(n, ch, k, V, ldv, x, yb);
-            }
+        if (k > 0) {   // every rank's host from its own (identical) copy of H
+            hs.solve_y(m, k, incremental, t.res_norm, yb.y);
+            hipk_gm_xupdate<T>(gl, n, ch, k, V, ldv, x, yb, stream);
         }
         HIPK_TRY(residual());
-        ++matvecs;
-        if (hipMemcpyAsync(head, scal, sizeof(head), hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) {
-            hipk_set_error("%s: HIP failure at the end of a restart cycle", loop);
-            return HIPK_ERR_HIP;
-        }
-        res_norm = head[0];
-        ++cycles;
+        ++t.cycles;
     }
 
     // TSL:766-773
     HIPK_TRY(xc.run(x));
     HIPK_TRY(hipk_dist_spmv(A, x, tmp, HIPK_SPMV_RESID | HIPK_SPMV_DOT_YY, nullptr, b, dinv, part_spare + c0, part_res + c0, nullptr, 0, stream));
     HIPK_TRY(xc.parts(part_res));
-    ++matvecs;
+    ++t.matvecs;
     HIPK_TRY(hipk_dot_parts(n, ch, x, x, HIPK_F64, part_xx + c0, stream));
     HIPK_TRY(xc.parts(part_xx));
     hipk_gm_final_kernel<<<1, HIPK_THREADS, 0, stream>>>(scal, G, part_res, part_xx);
-    HIPK_CHECK_HIP(hipGetLastError());
-    double fin[4];
-    HIPK_CHECK_HIP(hipEventRecord(whole.b, stream));
-    HIPK_CHECK_HIP(hipMemcpyAsync(fin, scal, sizeof(fin), hipMemcpyDeviceToHost, stream));
-    HIPK_CHECK_HIP(hipStreamSynchronize(stream));
-    st->iterations = cycles;
-    st->matvecs = matvecs;
-    st->b_norm = b_norm;
-    st->residual_norm = hipk_norm_from_sq(fin[2]);
-    st->x_norm = hipk_norm_from_sq(fin[3]);
-    st->threshold = atol_eff * 10;  // TSL:769
-    st->info = (isnan(st->x_norm) || st->residual_norm > st->threshold) ? -1 : 0;
-    st->breakdown = happy;
-    st->recurrence_rs = res_norm;
-    float ms = 0.f;
-    HIPK_CHECK_HIP(hipEventElapsedTime(&ms, whole.a, whole.b));
-    st->solve_ms = ms;
-    return HIPK_OK;
+    return hipk_gm_finish_stats(st, scal, whole, stream, t, b_norm, atol_eff);
 }
 
 extern "C" int hipk_dist_gmres_solve(hipk_csr_t A, const hipk_dist_plan *pl, const hipk_rccl *cc, const void *b_local, void *x_ext,

@@ -268,6 +268,10 @@ static inline double hipk_tmax(double a, double b) {
     if (isnan(a) || isnan(b)) return NAN;
     return a > b ? a : b;
 }
+static inline double hipk_tmin(double a, double b) {
+    if (isnan(a) || isnan(b)) return NAN;
+    return a < b ? a : b;
+}
 // sqrt(torch.clamp(v, min=0)) as `_norm` does (TSL:154-162); NaN stays NaN.
 static inline double hipk_norm_from_sq(double v) { return sqrt(v < 0.0 ? 0.0 : v); }
 

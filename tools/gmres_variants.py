@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""GMRES(30) at N = 4M: A/B of the large-system kernel variants (env switches of hipk_gmres_solve_t) in one process.
+"""GMRES(30) at N = 4M: A/B of the large-system kernel variants (env switches of hipk_gm_path_choose) in one process.
 Prints ms per restart cycle and checks that every variant returns the same bits."""
 import os as _os; _os.environ.setdefault("HIPK_SPMV_NO_PLAN_CACHE", "1")  # this probe flips SpMV switches between launches
 import os, sys, time
