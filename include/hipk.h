@@ -322,7 +322,11 @@ int hipk_cheb_apply(hipk_csr_t A, int degree, const void *dinv, const double *co
  *   chunk_rows : chunk size of the GLOBAL row count (hipk_chunk_size(n_global))
  *   g_red      : number of partials of ALL ranks (hipk_chunk_count(n_global))
  * Kernels index partial OUTPUTS by local chunk and read partial INPUTS from the
- * gathered (global) arrays. */
+ * gathered (global) arrays.
+ * The vector operands of hipk_cg_* / hipk_cgm_* (r, p, x, Ap, z) must be 16-byte
+ * aligned, as those of hipk_dot_parts and hipk_spmv_ex: HIPK_ERR_ALIGN otherwise,
+ * checked before any launch (tests/test_gpu_step_api.py pins every entry point
+ * call by call against tests/_step_mirror.py). */
 int hipk_csr_create_ex(hipk_csr_t *out, int64_t n_rows, int64_t n_cols, int64_t nnz,
                        const void *crow_dev, const void *col_dev, int idx_bytes,
                        const void *val_dev, int dtype, int chunk_rows, hipk_stream_t stream);

@@ -95,6 +95,8 @@ def lib():
         L.orc32_dot.restype = ctypes.c_double
         L.orc32_dot_tiled.argtypes = [i64, fp, fp]
         L.orc32_dot_tiled.restype = ctypes.c_double
+        L.orc32_dot_parts_ch.argtypes = [i64, ctypes.c_int, fp, fp, dp]
+        L.orc32_dot_tiled_parts_ch.argtypes = [i64, ctypes.c_int, fp, fp, dp]
         L.orc32_spmv.argtypes = [i64, ip, ip, fp, fp, fp, fp]
         L.orc32_cg.argtypes = [i64, ip, ip, fp, fp, fp, ctypes.c_double, ctypes.c_double, i64, sp]
         L.orc32_bicgstab.argtypes = [i64, ip, ip, fp, fp, fp, ctypes.c_double, ctypes.c_double, i64, sp]
@@ -316,6 +318,26 @@ def dot32(a, b) -> float:
 def dot_tiled32(a, b) -> float:
     a, b = _f32(a), _f32(b)
     return float(lib().orc32_dot_tiled(a.size, _f(a), _f(b)))
+
+
+def dot_parts_ch32(a, b, ch: int) -> np.ndarray:
+    """dot_parts_ch on fp32 storage: a virtual thread owns 4 elements per step instead of 2, so these are not the bits of
+    dot_parts_ch on the widened values."""
+    a, b = _f32(a), _f32(b)
+    g = (a.size + ch - 1) // ch
+    parts = np.zeros(max(g, 0), dtype=np.float64)
+    if a.size:
+        lib().orc32_dot_parts_ch(a.size, int(ch), _f(a), _f(b), _d(parts))
+    return parts
+
+
+def dot_tiled_parts_ch32(a, b, ch: int) -> np.ndarray:
+    a, b = _f32(a), _f32(b)
+    g = (a.size + ch - 1) // ch
+    parts = np.zeros(max(g, 0), dtype=np.float64)
+    if a.size:
+        lib().orc32_dot_tiled_parts_ch(a.size, int(ch), _f(a), _f(b), _d(parts))
+    return parts
 
 
 def spmv32(crow, col, val, x, bsub=None) -> np.ndarray:

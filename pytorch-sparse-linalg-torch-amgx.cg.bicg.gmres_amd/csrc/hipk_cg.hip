@@ -1401,6 +1401,14 @@ static int hipk_step_check(int64_t n_local, int chunk_rows, int g_red, int dtype
     return HIPK_OK;
 }
 
+// The step kernels access their vector operands 16 bytes at a time (hipk_ld / hipk_st), as hipk_dot, hipk_axpy, hipk_dot_parts and
+// hipk_spmv_ex do, which refuse an operand that is not 16-byte aligned; so do the step entry points.  A null pointer passes: which
+// operands may be null is each entry point's own test.
+static int hipk_step_align(const void *a, const void *b, const void *c = nullptr) {
+    HIPK_REQUIRE(hipk_aligned16(a) && hipk_aligned16(b) && hipk_aligned16(c), HIPK_ERR_ALIGN, "vector operands must be 16-byte aligned");
+    return HIPK_OK;
+}
+
 extern "C" int hipk_cg_start(int64_t n_local, int chunk_rows, int g_red, void *scal_dev, const double *part_rr,
                              const double *part_bb, const void *r, void *p, int dtype, double tol, double atol,
                              int64_t maxiter, hipk_stream_t stream_) {
@@ -1408,6 +1416,7 @@ extern "C" int hipk_cg_start(int64_t n_local, int chunk_rows, int g_red, void *s
     int rc = hipk_step_check(n_local, chunk_rows, g_red, dtype);
     if (rc != HIPK_OK) return rc;
     HIPK_REQUIRE(scal_dev && part_rr && part_bb && r && p, HIPK_ERR_ARG, "null argument");
+    if ((rc = hipk_step_align(r, p)) != HIPK_OK) return rc;
     const float tolf = (float)tol, atolf = (float)atol;
     const double tol2 = (double)(tolf * tolf), atol_sq = (double)(atolf * atolf);
     const int grid = (int)((n_local + chunk_rows - 1) / chunk_rows);
@@ -1430,6 +1439,7 @@ extern "C" int hipk_cg_update(int64_t n_local, int chunk_rows, int g_red, const 
     int rc = hipk_step_check(n_local, chunk_rows, g_red, dtype);
     if (rc != HIPK_OK) return rc;
     HIPK_REQUIRE(scal_dev && part_pAp && Ap && r && part_rr_out, HIPK_ERR_ARG, "null argument");
+    if ((rc = hipk_step_align(Ap, r)) != HIPK_OK) return rc;
     const int grid = (int)((n_local + chunk_rows - 1) / chunk_rows);
     if (dtype == HIPK_F64)
         hipk_cg_update_kernel<double><<<grid, HIPK_THREADS, 0, stream>>>(n_local, chunk_rows, g_red,
@@ -1450,6 +1460,7 @@ extern "C" int hipk_cg_direction(int64_t n_local, int chunk_rows, int g_red, voi
     int rc = hipk_step_check(n_local, chunk_rows, g_red, dtype);
     if (rc != HIPK_OK) return rc;
     HIPK_REQUIRE(scal_dev && part_pAp && part_rr && r && p, HIPK_ERR_ARG, "null argument");   // x == NULL: p only (see hipk_cg_xupdate)
+    if ((rc = hipk_step_align(r, p, x)) != HIPK_OK) return rc;
     const int grid = (int)((n_local + chunk_rows - 1) / chunk_rows);
     if (dtype == HIPK_F64 && x)
         hipk_cg_direction_kernel<double><<<grid, HIPK_THREADS, 0, stream>>>(n_local, chunk_rows, g_red,
@@ -1477,6 +1488,7 @@ extern "C" int hipk_cg_xupdate(int64_t n_local, int chunk_rows, int g_red, const
     int rc = hipk_step_check(n_local, chunk_rows, g_red, dtype);
     if (rc != HIPK_OK) return rc;
     HIPK_REQUIRE(scal_dev && part_pAp && p && x, HIPK_ERR_ARG, "null argument");
+    if ((rc = hipk_step_align(p, x)) != HIPK_OK) return rc;
     const int grid = (int)((n_local + chunk_rows - 1) / chunk_rows);
     if (dtype == HIPK_F64)
         hipk_cg_xupdate_kernel<double><<<grid, HIPK_THREADS, 0, stream>>>(n_local, chunk_rows, g_red, (const hipk_cg_scal *)scal_dev, it,
@@ -1562,6 +1574,7 @@ extern "C" int hipk_cgm_start(int64_t n_local, int chunk_rows, int g_red, void *
     int rc = hipk_step_check(n_local, chunk_rows, g_red, dtype);
     if (rc != HIPK_OK) return rc;
     HIPK_REQUIRE(scal_dev && part_rz && part_rr && part_bb && z && p, HIPK_ERR_ARG, "null argument");
+    if ((rc = hipk_step_align(z, p)) != HIPK_OK) return rc;
     const float tolf = (float)tol, atolf = (float)atol;
     const double tol2 = (double)(tolf * tolf), atol_sq = (double)(atolf * atolf);
     const int grid = (int)((n_local + chunk_rows - 1) / chunk_rows);
@@ -1584,6 +1597,7 @@ extern "C" int hipk_cgm_direction(int64_t n_local, int chunk_rows, int g_red, vo
     int rc = hipk_step_check(n_local, chunk_rows, g_red, dtype);
     if (rc != HIPK_OK) return rc;
     HIPK_REQUIRE(scal_dev && part_pAp && part_rz && part_rr && z && p && x, HIPK_ERR_ARG, "null argument");
+    if ((rc = hipk_step_align(z, p, x)) != HIPK_OK) return rc;
     const int grid = (int)((n_local + chunk_rows - 1) / chunk_rows);
     if (dtype == HIPK_F64)
         hipk_cgm_direction_kernel<double><<<grid, HIPK_THREADS, 0, stream>>>(
