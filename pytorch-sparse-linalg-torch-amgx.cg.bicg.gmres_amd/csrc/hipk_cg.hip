@@ -8,7 +8,13 @@
 //   K3 direction  alpha again (same partials, same bits), beta = <r,r>/gamma; x += alpha p; p = r + beta p;
 //                 gamma <- <r,r>; stop test                (TSL:847, 851-853, 841) 40 n bytes
 // = B_spmv + 64 n bytes per iteration: the x update rides on the pass that already streams p, 8 n bytes
-// less than the 72 n of SURVEY 8d; the arithmetic per element is unchanged.  Every workgroup re-derives alpha/beta from the chunk
+// less than the 72 n of SURVEY 8d; the arithmetic per element is unchanged.
+// Cache-resident sizes beyond the one-launch loops (the headline among them) defer the x update: nothing reads x before the solve
+// ends, so K3 alternates between hipk_cg_pdir_kernel (p = r + beta p into a SECOND p buffer: 24 n bytes) and hipk_cg_xdir_kernel
+// (the same, and x = (x + alpha_{k-1} p_{k-1}) + alpha_k p_k for two iterations at once, in the reference's order and with its
+// roundings: 48 n bytes), with the alphas from the scalar block (K2 leaves them there) -- B_spmv + 60 n bytes per iteration on
+// average; hipk_cg_xflush_kernel after the loop adds the term an odd iteration count leaves owed.
+// Every workgroup re-derives alpha/beta from the chunk
 // partials of the previous kernel with the fixed tree, so no grid barrier, no atomics
 // and no host round trip are needed; the host follows the loop through a pinned word the direction kernel
 // stores to (hipk_pacer, hipk_solve.h) and the kernels of iterations >= stop_it return immediately, so the
@@ -42,8 +48,16 @@ struct hipk_cg_scal {
     double xx;         // <x,x>                               (TSL:1013)
     int64_t stop_it;   // iterations >= stop_it are no-ops
     int64_t *host_sig; // pinned host word the direction kernel reports to (hipk_pacer), or null
-    double dir_alpha;  // hipk_cg_scalars_kernel -> hipk_cg_direction_flat_kernel (streaming policy): gamma / <p,Ap>, <r,r> / gamma
-    double dir_beta;
+    union {
+        struct {
+            double dir_alpha;  // hipk_cg_scalars_kernel -> hipk_cg_direction_flat_kernel (streaming policy): gamma / <p,Ap>, <r,r> / gamma
+            double dir_beta;
+        };
+        // deferred x update (never together with the streaming policy, so the two share their words and the block keeps its
+        // size): alpha of iteration k, the value (T)(gamma / <p,Ap>) every consumer derives, in slot k & 1 -- stored by the
+        // update launch of iteration k, read by hipk_cg_xdir_kernel and hipk_cg_xflush_kernel
+        double alpha[2];
+    };
     hipk_lds_ctl ctl;  // hipk_cg_solve_lds_kernel (small systems: the whole loop in one launch)
 };
 static_assert(sizeof(hipk_cg_scal) <= 256, "the scalar block is 256 bytes");
@@ -87,11 +101,12 @@ __global__ __launch_bounds__(HIPK_THREADS) void hipk_cg_start_kernel(
 // SMALL (systems of <= 8 reduction chunks, launch-bound): <p,Ap> is folded here from the SpMV's per-wavefront tile
 // sums (hipk_fold_tiles8: part_pAp then points at them, `ntiles` tiles), the combine launch is skipped.
 // NT (systems whose CG working set -- x, r, p, Ap -- is far beyond the Infinity Cache): every vector is a stream.
+// alpha_out (the deferred x update follows: &scal->alpha[it & 1], words this kernel does not read): one thread leaves alpha there.
 template <typename T, bool SMALL = false, bool NT = false>
 __global__ __launch_bounds__(HIPK_THREADS) void hipk_cg_update_kernel(
     int64_t n, int ch, int g, const hipk_cg_scal *__restrict__ scal, int64_t it,
     const double *__restrict__ part_pAp, const T *__restrict__ Ap, T *__restrict__ r, double *__restrict__ part_rr,
-    int ntiles = 0) {
+    int ntiles = 0, double *__restrict__ alpha_out = nullptr) {
     const int c = blockIdx.x;
     hipk_pre<T, 2, NT> pre;
     pre.issue(n, ch, c, {Ap, (const T *)r});
@@ -101,6 +116,7 @@ __global__ __launch_bounds__(HIPK_THREADS) void hipk_cg_update_kernel(
                              : hipk_reduce_parts(part_pAp, g, sbuf);
     const double gamma = scal->gamma[it & 1];
     const T alpha = (T)(gamma / pAp);  // TSL:846
+    if (alpha_out != nullptr && c == 0 && threadIdx.x == 0) *alpha_out = (double)alpha;
     double acc = 0.0;
     pre.run([&](int64_t i, int nv, T(&v)[2][hipk_vec<T>::VEC]) {
         constexpr int VEC = hipk_vec<T>::VEC;
@@ -193,6 +209,200 @@ __global__ __launch_bounds__(HIPK_THREADS) void hipk_cg_direction_kernel(
         if (done) scal->stop_it = it + 1;
         hipk_signal(scal->host_sig, done ? (HIPK_SIG_STOP | (it + 1)) : (it + 1));
     }
+}
+
+// ---- K3 with the x update deferred (the three-launch sequence of cache-resident sizes; hipk_cg_solve_t drives them) ------------
+// Nothing reads x before the solve ends, so x is updated every SECOND iteration for two iterations at once, in the reference's
+// order and with its roundings: x = (x + alpha_{k-1} p_{k-1}) + alpha_k p_k, each product and each sum rounded on its own -- the
+// bits two successive `x += alpha p` give.  p ping-pongs between two buffers so that p_{k-1} is still there; the alphas come from
+// scal->alpha (hipk_cg_update_kernel's alpha_out), so no K3 folds part_pAp.
+// the bookkeeping of every K3: gamma of the next pass, the stop test, the host's signal word (TSL:853, 841)
+__device__ __forceinline__ void hipk_cg_dir_done(hipk_cg_scal *scal, int64_t it, int64_t maxiter, double rr) {
+    scal->gamma[(it + 1) & 1] = rr;  // TSL:853
+    // TSL:841 for the NEXT pass: stop when k+1 >= maxiter or rs <= atol2 (workgroups of THIS launch compare against `it`)
+    const bool done = (it + 1 >= maxiter || rr <= scal->atol2);
+    if (done) scal->stop_it = it + 1;
+    hipk_signal(scal->host_sig, done ? (HIPK_SIG_STOP | (it + 1)) : (it + 1));
+}
+
+// hipk_reduce_parts with this thread's partials requested EARLY, all at once: the fold's own loads are eight dependent round trips
+// when each waits for the one before (the compiler does not hoist a load out of its `i < g`), and a wait for any of them is a
+// wait for every vector access issued before it.  Clamped indices make the loads unconditional; the sum skips what the original
+// skips, so the bits are hipk_reduce_parts'.
+struct hipk_parts_pre {
+    static constexpr int NK = HIPK_MAX_PARTS / HIPK_THREADS;
+    double v[NK];
+    __device__ __forceinline__ void issue(const double *__restrict__ part, int g) {
+#pragma unroll
+        for (int k = 0; k < NK; ++k) {
+            const int i = threadIdx.x + k * HIPK_THREADS;
+            v[k] = part[i < g ? i : g - 1];
+        }
+    }
+    __device__ __forceinline__ double fold(int g, double *sbuf) const {
+        double acc = 0.0;
+#pragma unroll
+        for (int k = 0; k < NK; ++k)
+            if ((int)threadIdx.x + k * HIPK_THREADS < g) acc = acc + v[k];
+        return hipk_block_sum(acc, sbuf);
+    }
+};
+
+// One chunk of either K3.  XUP: also the x update.  FULL: the chunk has all of its first HIPK_BASE_CHUNK elements (every chunk but
+// a ragged last one): they go through registers, N0 steps per thread, without a validity count per step; the rest of a larger
+// chunk (n > 4 M rows), and a ragged chunk from its start, step by step as hipk_pre::run's tail.  The chunk is addressed through
+// uniform base pointers and 32-bit element offsets (rb, pb, qb, xb: r, p_k, the other p buffer, x at the chunk's first element):
+// with 64-bit indices and counts per thread the three operands of four steps (48 registers in fp64) did not leave room for 8
+// workgroups per CU.  FULL is a compile-time branch of the whole body so that each form counts its own loads in flight.
+//   p only:  r and p_k are requested, then the partials: the fold's first wait is for all of them, the rest of it is LDS only.
+//   with x:  x, p_{k-1}, p_k are requested first; the x part needs the two alphas only, so its stores leave before the fold, r
+//            is requested into the registers of p_{k-1}, the partials into those of x: the fold's first wait is for the x stores
+//            and r, the rest of it is LDS only.  qb holds p_{k-1} and receives p_{k+1}: every thread reads its elements first.
+template <typename T, bool XUP, bool FULL>
+__device__ __forceinline__ void hipk_cg_dir_chunk(int lim, int g, hipk_cg_scal *__restrict__ scal, int64_t it, int64_t maxiter,
+                                                  const double *__restrict__ part_rr, const T *__restrict__ rb, const T *__restrict__ pb,
+                                                  T *qb, T *xb, double *sbuf, bool lead, int64_t stop, double gamma, T alpha_prev, T alpha) {
+    constexpr int VEC = hipk_vec<T>::VEC;
+    constexpr int N0 = HIPK_BASE_CHUNK / (VEC * HIPK_THREADS);
+    constexpr unsigned STEP = VEC * HIPK_THREADS;
+    const unsigned o0 = VEC * threadIdx.x;
+    hipk_parts_pre parts;
+    T xv[N0][VEC], qv[N0][VEC], pv[N0][VEC];
+    T (&rv)[N0][VEC] = qv;   // with x: r arrives where p_{k-1} was
+    if constexpr (FULL) {
+#pragma unroll
+        for (int k = 0; k < N0; ++k) {
+            const unsigned o = o0 + k * STEP;
+            if constexpr (XUP) {
+                hipk_ld<T>((const T *)xb, o, VEC, xv[k]);
+                hipk_ld<T>((const T *)qb, o, VEC, qv[k]);
+            } else {
+                hipk_ld<T>(rb, o, VEC, rv[k]);
+            }
+            hipk_ld<T>(pb, o, VEC, pv[k]);
+        }
+    }
+    if (it >= stop) return;
+    if constexpr (XUP) {
+        if constexpr (FULL) {
+#pragma unroll
+            for (int k = 0; k < N0; ++k) {
+#pragma unroll
+                for (int e = 0; e < VEC; ++e) {
+                    const T m0 = alpha_prev * qv[k][e];
+                    const T x1 = xv[k][e] + m0;   // TSL:847 of iteration it - 1
+                    const T m1 = alpha * pv[k][e];
+                    xv[k][e] = x1 + m1;           // TSL:847 of iteration it
+                }
+                hipk_st<T>(xb, o0 + k * STEP, VEC, xv[k]);
+            }
+#pragma unroll
+            for (int k = 0; k < N0; ++k) hipk_ld<T>(rb, o0 + k * STEP, VEC, rv[k]);
+        }
+    }
+    // (the instruction scheduler otherwise starts the fold between the chunk's loads, and the last of them wait for the first)
+    __builtin_amdgcn_sched_barrier(0);
+    parts.issue(part_rr, g);
+    const double rr = parts.fold(g, sbuf);          // the tree of hipk_reduce_parts2: the direction kernel's bits
+    const T beta = (T)(rr / gamma);                 // TSL:851
+    if constexpr (FULL) {
+#pragma unroll
+        for (int k = 0; k < N0; ++k) {
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) {
+                const T m = beta * pv[k][e];
+                pv[k][e] = rv[k][e] + m;  // TSL:852
+            }
+            hipk_st<T>(qb, o0 + k * STEP, VEC, pv[k]);
+        }
+    }
+    for (unsigned o = o0 + (FULL ? N0 * STEP : 0u); (int)o < lim; o += STEP) {
+        const int nv = (lim - (int)o < VEC) ? lim - (int)o : VEC;
+        T xs[VEC], qs[VEC], ps[VEC], rs[VEC];
+        if constexpr (XUP) {
+            hipk_ld<T>((const T *)xb, o, nv, xs);
+            hipk_ld<T>((const T *)qb, o, nv, qs);
+        }
+        hipk_ld<T>(pb, o, nv, ps);
+        hipk_ld<T>(rb, o, nv, rs);
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) {
+            if constexpr (XUP) {
+                const T m0 = alpha_prev * qs[e];
+                const T x1 = xs[e] + m0;
+                const T m1 = alpha * ps[e];
+                xs[e] = x1 + m1;
+            }
+            const T m = beta * ps[e];
+            ps[e] = rs[e] + m;
+        }
+        if constexpr (XUP) hipk_st<T>(xb, o, nv, xs);
+        hipk_st<T>(qb, o, nv, ps);
+    }
+    if (lead) hipk_cg_dir_done(scal, it, maxiter, rr);
+}
+
+template <typename T, bool XUP>
+__device__ __forceinline__ void hipk_cg_dir_deferred(int64_t n, int ch, int g, hipk_cg_scal *__restrict__ scal, int64_t it, int64_t maxiter,
+                                                     const double *__restrict__ part_rr, const T *__restrict__ r, const T *__restrict__ p_cur,
+                                                     T *p_other, T *x) {
+    __shared__ double sbuf[HIPK_THREADS];
+    const int c = blockIdx.x;
+    const int64_t base = (int64_t)c * ch;
+    const int lim = (int)((base + ch < n) ? ch : n - base);   // elements of this chunk
+    const bool lead = c == 0 && threadIdx.x == 0;
+    // the scalars are requested here (scalar loads, before the two forms part) and looked at after the chunk's loads have been issued
+    const int64_t stop = scal->stop_it;
+    const double gamma = scal->gamma[it & 1];
+    // TSL:846 of iterations it - 1 and it, the bits the update kernels derived
+    const T alpha_prev = XUP ? (T)scal->alpha[(it - 1) & 1] : (T)0, alpha = XUP ? (T)scal->alpha[it & 1] : (T)0;
+    if (lim >= HIPK_BASE_CHUNK)
+        hipk_cg_dir_chunk<T, XUP, true>(lim, g, scal, it, maxiter, part_rr, r + base, p_cur + base, p_other + base, XUP ? x + base : x, sbuf, lead, stop, gamma, alpha_prev, alpha);
+    else
+        hipk_cg_dir_chunk<T, XUP, false>(lim, g, scal, it, maxiter, part_rr, r + base, p_cur + base, p_other + base, XUP ? x + base : x, sbuf, lead, stop, gamma, alpha_prev, alpha);
+}
+
+// iterations that only form p: p_next = r + beta p_cur into the OTHER buffer (3 passes instead of 5)
+template <typename T>
+__global__ __launch_bounds__(HIPK_THREADS) void hipk_cg_pdir_kernel(int64_t n, int ch, int g, hipk_cg_scal *__restrict__ scal, int64_t it,
+                                                                    int64_t maxiter, const double *__restrict__ part_rr,
+                                                                    const T *__restrict__ r, const T *__restrict__ p_cur,
+                                                                    T *__restrict__ p_next) {
+    hipk_cg_dir_deferred<T, false>(n, ch, g, scal, it, maxiter, part_rr, r, p_cur, p_next, (T *)nullptr);
+}
+
+// iterations that also update x (6 passes): x = (x + alpha_{k-1} p_{k-1}) + alpha_k p_k.  pq holds p_{k-1} and receives p_{k+1}:
+// one pointer, not restrict against itself
+template <typename T>
+__global__ __launch_bounds__(HIPK_THREADS) void hipk_cg_xdir_kernel(int64_t n, int ch, int g, hipk_cg_scal *__restrict__ scal, int64_t it,
+                                                                    int64_t maxiter, const double *__restrict__ part_rr,
+                                                                    const T *__restrict__ r, const T *__restrict__ p_cur, T *pq,
+                                                                    T *__restrict__ x) {
+    hipk_cg_dir_deferred<T, true>(n, ch, g, scal, it, maxiter, part_rr, r, p_cur, pq, x);
+}
+
+// after the loop: K iterations were completed (the device's stop word once it has fired, else the host's count), the deferred
+// sequence began at it0.  K - it0 odd: iteration K - 1 only formed p, x still lacks alpha_{K-1} p_{K-1} -- and p_{K-1} sits in the
+// buffer the sequence began with (K - 1 - it0 is even; the launches past the stop were no-ops).  Even, or K <= it0: nothing to do.
+template <typename T>
+__global__ __launch_bounds__(HIPK_THREADS) void hipk_cg_xflush_kernel(int64_t n, int ch, const hipk_cg_scal *__restrict__ scal, int64_t it_host,
+                                                                      int64_t it0, const T *__restrict__ p_first, T *__restrict__ x) {
+    const int64_t stop = scal->stop_it;
+    const int64_t K = stop < it_host ? stop : it_host;
+    if (K <= it0 || ((K - it0) & 1) == 0) return;
+    const T alpha = (T)scal->alpha[(K - 1) & 1];
+    hipk_chunk_loop<T>(n, ch, blockIdx.x, [&](int64_t i, int nv) {
+        constexpr int VEC = hipk_vec<T>::VEC;
+        T xv[VEC], pv[VEC];
+        hipk_ld<T>((const T *)x, i, nv, xv);
+        hipk_ld<T>(p_first, i, nv, pv);
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) {
+            const T m0 = alpha * pv[k];
+            xv[k] = xv[k] + m0;  // TSL:847
+        }
+        hipk_st<T>(x, i, nv, xv);
+    });
 }
 
 // ---- TWO launches per iteration for launch-bound mid-size systems (33 .. 150 reduction chunks: 65 k < n <= 307 k) ----------------
@@ -925,6 +1135,9 @@ __global__ __launch_bounds__(HIPK_THREADS) void hipk_cg_final_kernel(hipk_cg_sca
 // 518 k 21.2 / 20.2 (the general CSR tiles' 12 bytes per entry catch up with the saved launch): profiles/r03_cg_two_launch.txt
 static constexpr int kCg2MaxChunks = 150;
 
+// x, r, p, Ap beyond 1.5 x the 256 MiB Infinity Cache: the vector kernels treat every operand as a stream
+static inline bool hipk_cg_streams_by_size(size_t n, size_t sv) { return 4 * n * sv > (size_t)384 << 20; }
+
 extern "C" size_t hipk_cg_work_bytes(int64_t n, int dtype) {
     const size_t sv = (dtype == HIPK_F64) ? 8 : 4;
     const size_t vec = hipk_align_up((size_t)(n > 0 ? n : 1) * sv, 256);
@@ -934,7 +1147,10 @@ extern "C" size_t hipk_cg_work_bytes(int64_t n, int dtype) {
     const bool mid = gm.g > kMidMinChunks && gm.g <= kMidMaxChunks;   // + the chunk-partial slots of that loop, a line each
     // (r travels as 16-byte flagged words whatever the dtype: 16 n bytes from Ap on -- one more fp64 vector, three more fp32 ones)
     const size_t ll = hipk_align_up((size_t)(n > 0 ? n : 1) * 16, 256);
-    return 256 + hipk_scratch_bytes() + 3 * vec + (mid ? (ll - vec) + kMidSlotBytes : 0);
+    // beyond the mid loop, up to the size at which the streaming policy takes over (hipk_cg_path_begin): the second p of the
+    // deferred x update (hipk_cg_path_defer); the sizes of the streaming policy keep three vectors
+    const bool second_p = !mid && gm.g > kMidMaxChunks && !hipk_cg_streams_by_size((size_t)n, sv);
+    return 256 + hipk_scratch_bytes() + 3 * vec + (mid ? (ll - vec) + kMidSlotBytes : second_p ? vec : 0);
 }
 
 // the one-launch instantiations the dispatch sites below select (hipk_mid_pick), each with the name hipk_last_solve_path reports.
@@ -971,6 +1187,7 @@ struct hipk_cg_path {
     bool local = false;        // ... hand-offs through that XCD's L2 (a -2 of the kernel: agent scope from then on)
     int64_t max_its = 0;       // iterations one launch of either loop may run
     bool two_launch = false;   // plain CG: hipk_cg2_spmv_kernel + hipk_cg2_update_kernel per iteration
+    bool defer_x = false;      // plain CG, three launches: x updated every second iteration (hipk_cg_pdir_kernel / hipk_cg_xdir_kernel)
 };
 
 template <typename T, bool PRE>
@@ -981,7 +1198,7 @@ static hipk_cg_path hipk_cg_path_begin(hipk_csr_s *A, const hipk_params *prm, in
     if (!PRE) {   // the Jacobi launch sequence has one form: its kernels fold chunk partials and use the default cache policy
         path.small = g <= 8 && !hipk_sw_present("HIPK_CG_NO_SMALL");
         // x, r, p, Ap beyond 1.5 x the 256 MiB Infinity Cache (HIPK_CG_STREAMS=0/1 forces the choice: A/B measurements)
-        path.streams = hipk_sw_force("HIPK_CG_STREAMS", 4 * (size_t)n * sizeof(T) > (size_t)384 << 20);
+        path.streams = hipk_sw_force("HIPK_CG_STREAMS", hipk_cg_streams_by_size((size_t)n, sizeof(T)));
         // with it, and a vector alone beyond the 256 MiB Infinity Cache, the direction step as a scalars launch + a flat grid
         // (same vectors, same process, per CG iteration: N = 64 M 1079 -> 1011 us; N = 32 M 473 -> 471; N = 16 M, where p still finds
         // room in that cache, 237 -> 246: not taken there).  HIPK_CG_FLAT_DIRECTION=0|1 forces (tools/flat_probe.py, tests)
@@ -1038,6 +1255,15 @@ static void hipk_cg_path_two(hipk_cg_path &path, const hipk_csr_s *A, const hipk
     path.two_launch = !done && !path.small && g > 32 && g <= kCg2MaxChunks && A->geom.ch == HIPK_BASE_CHUNK && A->op_cb == nullptr &&
                       A->crow != nullptr && A->max_tile_nnz <= cap2 && A->max_row_len <= HIPK_LONG_ROW && prm->profile == 0 && it == 0 &&
                       hipk_sw_enabled("HIPK_CG_TWO_LAUNCH") && hipk_cg_work_bytes(A->n_rows, A->dtype) >= 256 + hipk_scratch_bytes() + 4 * vec;
+}
+
+// the three-launch sequence of plain CG with the x update deferred (hipk_cg_pdir_kernel, hipk_cg_xdir_kernel, hipk_cg_xflush_kernel):
+// the general form only (chunk partials, default cache policy), a matrix operand, no per-kernel profile (a profiled solve times
+// the kernels it names), room for a fourth vector in the workspace (a size of the streaming policy forced to HIPK_CG_STREAMS=0
+// finds none), from any iteration a one-launch loop handed back at.  HIPK_CG_DEFER_X=0: hipk_cg_direction_kernel every iteration
+static void hipk_cg_path_defer(hipk_cg_path &path, const hipk_csr_s *A, const hipk_params *prm, bool done, size_t vec) {
+    path.defer_x = !done && !path.two_launch && !path.small && !path.streams && A->op_cb == nullptr && prm->profile == 0 &&
+                   hipk_cg_work_bytes(A->n_rows, A->dtype) >= 256 + hipk_scratch_bytes() + 4 * vec && hipk_sw_enabled("HIPK_CG_DEFER_X");
 }
 
 // {redo, it_done, stop_it} of a host copy of hipk_cg_scal / hipk_pcg_scal (hipk_resident_run)
@@ -1268,6 +1494,8 @@ static int hipk_cg_solve_t(hipk_csr_s *A, const T *b, T *x, char *work, const hi
     constexpr int kCap2 = sizeof(T) == 8 ? 1280 : 2048;
     hipk_cg_path_two(path, A, prm, lds_loop, it, kCap2, vec);
     const bool two_launch = path.two_launch;
+    hipk_cg_path_defer(path, A, prm, lds_loop, vec);
+    const bool defer_x = path.defer_x;
     if (!lds_loop)
         hipk_set_solve_form(two_launch ? (sizeof(T) == 8 ? HIPK_FORM("cg two-launch: hipk_cg2_spmv_kernel<double,1280> + hipk_cg2_update_kernel")
                                                          : HIPK_FORM("cg two-launch: hipk_cg2_spmv_kernel<float,2048> + hipk_cg2_update_kernel"))
@@ -1306,7 +1534,28 @@ static int hipk_cg_solve_t(hipk_csr_s *A, const T *b, T *x, char *work, const hi
         }
         if (it > maxiter) it = maxiter;
     }
-    for (; !lds_loop && !two_launch && it < maxiter; ++it) {
+    if (defer_x) {
+        // p_j of iteration it0 + j lives in pbuf[j & 1]; even j only forms p_{j+1} in the other buffer, odd j also brings x up to date
+        T *pbuf[2] = {p, (T *)((char *)Ap + vec)};
+        const int64_t it0 = it;
+        for (; it < maxiter; ++it) {
+            HIPK_CHECK_HIP(pace.gate(it, stream, &stop));
+            if (stop <= it) break;
+            const int j = (int)((it - it0) & 1);
+            sa.it = it;
+            sa.x = sa.w = pbuf[j];
+            if ((rc = hipk_launch_spmv(A, sa, stream, &prof)) != HIPK_OK) return rc;
+            hipk_cg_update_kernel<T><<<gm.g, HIPK_THREADS, 0, stream>>>(n, gm.ch, gm.g, scal, it, part_a, Ap, r, part_b, 0, &scal->alpha[it & 1]);
+            if (j == 0)
+                hipk_cg_pdir_kernel<T><<<gm.g, HIPK_THREADS, 0, stream>>>(n, gm.ch, gm.g, scal, it, maxiter, part_b, r, pbuf[0], pbuf[1]);
+            else
+                hipk_cg_xdir_kernel<T><<<gm.g, HIPK_THREADS, 0, stream>>>(n, gm.ch, gm.g, scal, it, maxiter, part_b, r, pbuf[1], pbuf[0], x);
+            if ((it & 63) == 63) HIPK_CHECK_HIP(hipGetLastError());
+        }
+        // an odd number of iterations: the last one's x update is still owed (the device knows how many were completed)
+        hipk_cg_xflush_kernel<T><<<gm.g, HIPK_THREADS, 0, stream>>>(n, gm.ch, scal, it, it0, pbuf[0], x);
+    }
+    for (; !lds_loop && !two_launch && !defer_x && it < maxiter; ++it) {
         HIPK_CHECK_HIP(pace.gate(it, stream, &stop));
         if (stop <= it) break;
         {
@@ -1315,13 +1564,13 @@ static int hipk_cg_solve_t(hipk_csr_s *A, const T *b, T *x, char *work, const hi
             if ((rc = hipk_launch_spmv(A, sa, stream, &prof)) != HIPK_OK) return rc;
             if (small)
                 hipk_launch_timed(&prof, HIPK_K_UPDATE, hipk_cg_update_kernel<T, true>, gm.g, HIPK_THREADS, 0, stream, n, gm.ch, gm.g, scal, it,
-                                  A->tile_part, Ap, r, part_b, ntiles);
+                                  A->tile_part, Ap, r, part_b, ntiles, (double *)nullptr);
             else if (streams)
                 hipk_launch_timed(&prof, HIPK_K_UPDATE, hipk_cg_update_kernel<T, false, true>, gm.g, HIPK_THREADS, 0, stream, n, gm.ch, gm.g, scal, it,
-                                  part_a, Ap, r, part_b, 0);
+                                  part_a, Ap, r, part_b, 0, (double *)nullptr);
             else
                 hipk_launch_timed(&prof, HIPK_K_UPDATE, hipk_cg_update_kernel<T>, gm.g, HIPK_THREADS, 0, stream, n, gm.ch, gm.g, scal, it, part_a, Ap, r,
-                                  part_b, 0);
+                                  part_b, 0, (double *)nullptr);
             if (small)
                 hipk_launch_timed(&prof, HIPK_K_DIRECTION, hipk_cg_direction_kernel<T, true>, gm.g, HIPK_THREADS, 0, stream, n, gm.ch, gm.g, scal, it,
                                   maxiter, A->tile_part, part_b, r, p, x, ntiles);

@@ -39,7 +39,7 @@ static constexpr hipk_sw_row hipk_switches[] = {
     // ---- every solve loop (hipk_solve.h)
     {"HIPK_HOST_SIGNAL", HIPK_SW_OFF_IF_0, "on", "each solve", "0: follow the loop with stream-ordered reads of the device stop word instead of the pinned-host signal word", "test"},
     {"HIPK_PACE_TIMEOUT_US", HIPK_SW_INT, "200000", "each solve", "t: microseconds the signal word may stand still before the stream-ordered fallback; negative: ignored", "test"},
-    {"HIPK_PACE_WINDOW", HIPK_SW_INT, "8", "each solve", "k: iterations the host may run ahead of the GPU; outside 1 .. 4096: ignored", "user"},
+    {"HIPK_PACE_WINDOW", HIPK_SW_INT, "8", "each solve", "k: iterations the host may run ahead of the GPU; outside 1 .. 4096: ignored", "test, user"},
     {"HIPK_TEST_LDS_NOT_RESIDENT", HIPK_SW_INT, "unset", "each one-launch loop; each hand-back", "k: the k-th launch of a one-launch loop reports its workgroups as not co-resident, k < 2 (0 included) reads as 1; set at all: a hand-back does not set the process-wide latch", "test"},
     {"HIPK_NO_LDS_SPREAD", HIPK_SW_PRESENT, "off", "each solve", "9 .. 32 chunks: the launch sequences instead of the one-launch kernels spread over the chip (cg, bicgstab, gmres)", "test, tools A/B"},
     // ---- CG (hipk_cg.hip)
@@ -51,6 +51,7 @@ static constexpr hipk_sw_row hipk_switches[] = {
     {"HIPK_CG_LAUNCH_ITS", HIPK_SW_INT, "16384", "each one-launch loop", "k: iterations one launch of a one-launch CG loop may run, at least 1", "test"},
     {"HIPK_CG_LOOP_AGENT", HIPK_SW_PRESENT, "off", "each LDS loop", "agent-scope hand-offs in hipk_cg_solve_lds_kernel also on one XCD", "test"},
     {"HIPK_CG_TWO_LAUNCH", HIPK_SW_OFF_IF_0, "on", "each plain CG solve", "0: the three-launch iteration instead of hipk_cg2_spmv_kernel + hipk_cg2_update_kernel", "test, tools A/B"},
+    {"HIPK_CG_DEFER_X", HIPK_SW_OFF_IF_0, "on", "each plain CG solve", "0: every direction launch updates x (hipk_cg_direction_kernel)", "test, tools A/B"},
     {"HIPK_CG_STREAMS", HIPK_SW_FORCE01, "automatic", "each plain CG solve", "0 | 1: force the vector kernels' cache policy (unset: streams when x, r, p, Ap exceed 384 MiB)", "test"},
     {"HIPK_CG_FLAT_DIRECTION", HIPK_SW_FORCE01, "automatic", "each plain CG solve", "0 | 1: with the streaming policy, the direction step per chunk | as scalars launch + flat grid (unset: flat when a vector exceeds 256 MiB)", "test, tools A/B"},
     // ---- BiCGStab (hipk_bicgstab.hip)
