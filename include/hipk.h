@@ -201,6 +201,14 @@ int hipk_xpby(int64_t n, const void *x, double b, void *y, int dtype, hipk_strea
 
 /* ---- whole solves (device-resident loops) ------------------------------------
  * x: in = x0, out = solution.  b is not modified.  `work` >= *_work_bytes.
+ * The workspace contract (every entry point that takes `work`; tests/_arena.py):
+ *   - `work` need not be initialised: the result does not depend on what it
+ *     holds on entry, and what it holds after a call is unspecified;
+ *   - a call writes no byte outside [work, work + work_bytes) -- work_bytes the
+ *     figure of *_work_bytes, whatever larger size is passed --, x[0..n) and
+ *     the handle's own scratch; dinv and the matrix are read-only like b;
+ *   - one workspace may be reused, without clearing it, across solvers, sizes
+ *     and handles, by calls ordered on one stream.
  * The loop stops at exactly the iteration the reference stops at (device-side
  * stop word: launches past it are no-ops).  The host follows the loop through a
  * pinned word the deciding kernel stores to and keeps a few iterations queued

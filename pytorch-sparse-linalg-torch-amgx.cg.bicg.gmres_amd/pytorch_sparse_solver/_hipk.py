@@ -603,17 +603,22 @@ def block_jacobi_apply(binv: torch.Tensor, block_size: int, v: torch.Tensor) -> 
     return out
 
 
-def cheb_apply(h: CsrHandle, degree: int, dinv: torch.Tensor, coef, v: torch.Tensor) -> torch.Tensor:
+def cheb_apply(h: CsrHandle, degree: int, dinv: torch.Tensor, coef, v: torch.Tensor, work: Optional[torch.Tensor] = None,
+               out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """z = p_m(D^-1 A) D^-1 v on the device (hipk_cheb_apply), enqueued on the current stream.  `coef`: a ctypes array of
     2 * degree + 2 doubles (c0, c1[1..m], c2[1..m], scale).  Takes no lock and touches none of the handle's reduction scratch:
-    it is what a solve that HOLDS the handle calls as its preconditioner."""
+    it is what a solve that HOLDS the handle calls as its preconditioner.  `work`: None or the caller's two work vectors, a
+    contiguous uint8 tensor on the handle's device, 16-byte aligned, of at least 2 * ((n + 3) & ~3) elements' bytes; `out`: None
+    or where z goes (contiguous, 16-byte aligned, n elements)."""
     assert v.is_cuda and v.dtype == h.dtype and v.device == h.device and v.numel() == h.n and h.shape[0] == h.shape[1]
     assert dinv.is_contiguous() and dinv.dtype == v.dtype and dinv.device == v.device and dinv.numel() == h.n
     assert len(coef) == 2 * int(degree) + 2
     if not v.is_contiguous() or v.data_ptr() % 16:
         v = v.contiguous().clone()
-    out = torch.empty_like(v)
-    work = torch.empty(2 * ((h.n + 3) & ~3), dtype=v.dtype, device=v.device)   # ordered by the stream, as the launches are
+    if out is None:
+        out = torch.empty_like(v)
+    assert out.is_contiguous() and out.dtype == v.dtype and out.device == v.device and out.numel() == h.n and out.data_ptr() % 16 == 0
+    work = _workspace(work, v.device, 2 * ((h.n + 3) & ~3) * v.element_size(), 16)   # ordered by the stream, as the launches are
     with torch.cuda.device(v.device):
         _check(lib().hipk_cheb_apply(h.ptr, int(degree), dinv.data_ptr(), coef, v.data_ptr(), out.data_ptr(), work.data_ptr(),
                                      _stream(v.device)), "hipk_cheb_apply")
@@ -658,16 +663,33 @@ def _placed_cg_work(h, x: torch.Tensor, work_bytes: int):
     return best[0], best[1], best[2], best[3], len(held)
 
 
-def _solve(method: str, h: CsrHandle, b: torch.Tensor, x: torch.Tensor, prm: Params, work_bytes: int) -> SolveStats:
+def _workspace(work: Optional[torch.Tensor], device, nbytes: int, align: int = 256) -> torch.Tensor:
+    """The workspace of a call: a fresh allocation, or the caller's `work` after checking it (contiguous uint8 on `device`,
+    `align`-byte aligned, at least the library's `nbytes`).  The call is given `nbytes`, not work.numel()."""
+    if work is None:
+        return torch.empty(nbytes, dtype=torch.uint8, device=device)
+    if not isinstance(work, torch.Tensor) or work.dtype != torch.uint8 or not work.is_contiguous() or work.dim() != 1:
+        raise HipkError("work must be a contiguous one-dimensional uint8 tensor")
+    if work.device != torch.device(device):
+        raise HipkError(f"work is on {work.device}, the handle on {device}")
+    if work.data_ptr() % align:
+        raise HipkError(f"work must be {align}-byte aligned")
+    if work.numel() < nbytes:
+        raise HipkError(f"work holds {work.numel()} bytes, the call needs {nbytes}")
+    return work
+
+
+def _solve(method: str, h: CsrHandle, b: torch.Tensor, x: torch.Tensor, prm: Params, work_bytes: int,
+           work: Optional[torch.Tensor] = None) -> SolveStats:
     L = lib()
     placed = None
     with torch.cuda.device(h.device):
-        if method == "cg":
+        if method == "cg" and work is None:   # a caller's workspace stays where it is: no placement probe
             placed = _placed_cg_work(h, x, work_bytes)
     if placed is not None:
         _buf, work, x_run, probe_gbps, probe_tries = placed
     else:
-        work, x_run, probe_gbps, probe_tries = torch.empty(work_bytes, dtype=torch.uint8, device=h.device), x, 0.0, 0
+        work, x_run, probe_gbps, probe_tries = _workspace(work, h.device, work_bytes), x, 0.0, 0
     if hasattr(h, "regions"):   # OpHandle: the operator callback resolves raw pointers against these tensors
         h.regions.append(work)
     st = Stats()
@@ -687,8 +709,10 @@ def _solve(method: str, h: CsrHandle, b: torch.Tensor, x: torch.Tensor, prm: Par
 
 def solve(method: str, h: CsrHandle, b: torch.Tensor, x: torch.Tensor, *, tol: float, atol: float,
           maxiter: Optional[int], restart: int = 20, solve_method: str = "batched", check_every: int = 0,
-          profile: bool = False) -> SolveStats:
-    """Run hipk_{cg,bicgstab,gmres}_solve. `x` holds x0 on entry and the solution on return."""
+          profile: bool = False, work: Optional[torch.Tensor] = None) -> SolveStats:
+    """Run hipk_{cg,bicgstab,gmres}_solve. `x` holds x0 on entry and the solution on return.  `work`: None (allocated here) or
+    the caller's workspace, a contiguous uint8 tensor on the handle's device, 256-byte aligned, of at least the library's
+    *_work_bytes; the solve is given the library's figure, and the placement probe of large CG systems is skipped."""
     if h.shape[0] != h.shape[1]:
         raise ValueError(f"linear operator must be a square matrix, but has shape: {h.shape}")
     assert b.is_contiguous() and x.is_contiguous() and b.dtype == h.dtype and x.dtype == h.dtype
@@ -707,13 +731,14 @@ def solve(method: str, h: CsrHandle, b: torch.Tensor, x: torch.Tensor, *, tol: f
         wb = L.hipk_gmres_work_bytes(h.n, int(restart), code)
     else:
         wb = getattr(L, f"hipk_{method}_work_bytes")(h.n, code)
-    return _solve(method, h, b, x, prm, int(wb))
+    return _solve(method, h, b, x, prm, int(wb), work)
 
 
 def solve_pcg(h: CsrHandle, dinv: torch.Tensor, b: torch.Tensor, x: torch.Tensor, *, tol: float, atol: float,
-              maxiter: Optional[int], check_every: int = 0, method: str = "cg") -> SolveStats:
+              maxiter: Optional[int], check_every: int = 0, method: str = "cg",
+              work: Optional[torch.Tensor] = None) -> SolveStats:
     """hipk_pcg_solve / hipk_pbicgstab_solve (method "cg" / "bicgstab") with M = diag(dinv).
-    `x` holds x0 on entry and the solution on return."""
+    `x` holds x0 on entry and the solution on return.  `work`: as in `solve`."""
     if h.shape[0] != h.shape[1]:
         raise ValueError(f"linear operator must be a square matrix, but has shape: {h.shape}")
     for t in (dinv, b, x):
@@ -726,7 +751,7 @@ def solve_pcg(h: CsrHandle, dinv: torch.Tensor, b: torch.Tensor, x: torch.Tensor
     L = lib()
     name = {"cg": "pcg", "bicgstab": "pbicgstab"}[method]
     wb = int(getattr(L, f"hipk_{name}_work_bytes")(h.n, _dtype_code(h.dtype)))
-    work = torch.empty(wb, dtype=torch.uint8, device=h.device)
+    work = _workspace(work, h.device, wb)
     if hasattr(h, "regions"):   # OpHandle: the operator callback resolves raw pointers against these tensors
         h.regions.append(work)
     st = Stats()
@@ -759,9 +784,9 @@ def multi_work_bytes(n: int, k: int, dtype: torch.dtype, method: str, precond: b
 
 
 def solve_multi(method: str, h: CsrHandle, dinv: Optional[torch.Tensor], B: torch.Tensor, X: torch.Tensor, *, tol: float,
-                atol: float, maxiter: Optional[int], check_every: int = 0) -> MultiSolveStats:
+                atol: float, maxiter: Optional[int], check_every: int = 0, work: Optional[torch.Tensor] = None) -> MultiSolveStats:
     """hipk_{cg,bicgstab}_solve_multi: B, X row-major (n, k) of the handle's dtype; X holds X0 on entry and the solution on return.
-    dinv: None (M = identity) or the Jacobi vector."""
+    dinv: None (M = identity) or the Jacobi vector.  `work`: as in `solve`, of at least hipk_multi_work_bytes."""
     if h.shape[0] != h.shape[1]:
         raise ValueError(f"linear operator must be a square matrix, but has shape: {h.shape}")
     n, k = int(B.shape[0]), int(B.shape[1])
@@ -776,7 +801,7 @@ def solve_multi(method: str, h: CsrHandle, dinv: Optional[torch.Tensor], B: torc
     prm.gpu_tolerances = 1
     L = lib()
     wb = multi_work_bytes(n, k, h.dtype, method, dinv is not None)
-    work = torch.empty(wb, dtype=torch.uint8, device=h.device)
+    work = _workspace(work, h.device, wb)
     st = (Stats * k)()
     spmvs = ctypes.c_int64(0)
     with h._lock, torch.cuda.device(h.device):
@@ -793,8 +818,9 @@ def solve_multi(method: str, h: CsrHandle, dinv: Optional[torch.Tensor], B: torc
 
 
 def solve_pgmres(h: CsrHandle, dinv: torch.Tensor, b: torch.Tensor, x: torch.Tensor, *, tol: float, atol: float,
-                 maxiter: Optional[int], restart: int = 20, solve_method: str = "batched") -> SolveStats:
-    """hipk_pgmres_solve: GMRES with M = diag(dinv) applied after every A (left preconditioning)."""
+                 maxiter: Optional[int], restart: int = 20, solve_method: str = "batched",
+                 work: Optional[torch.Tensor] = None) -> SolveStats:
+    """hipk_pgmres_solve: GMRES with M = diag(dinv) applied after every A (left preconditioning).  `work`: as in `solve`."""
     if h.shape[0] != h.shape[1]:
         raise ValueError(f"linear operator must be a square matrix, but has shape: {h.shape}")
     for t in (dinv, b, x):
@@ -807,7 +833,7 @@ def solve_pgmres(h: CsrHandle, dinv: torch.Tensor, b: torch.Tensor, x: torch.Ten
     prm.gpu_tolerances = 1
     L = lib()
     wb = int(L.hipk_gmres_work_bytes(h.n, int(restart), _dtype_code(h.dtype)))
-    work = torch.empty(wb, dtype=torch.uint8, device=h.device)
+    work = _workspace(work, h.device, wb)
     if hasattr(h, "regions"):   # OpHandle: the operator callback resolves raw pointers against these tensors
         h.regions.append(work)
     st = Stats()
@@ -1042,21 +1068,24 @@ def solve_matrix_free(kind: str, A_fn, b: torch.Tensor, x: torch.Tensor, *, tol:
 
 
 def solve_bicgstab_callable(h: CsrHandle, M, b: torch.Tensor, x: torch.Tensor, *, tol: float, atol: float,
-                            maxiter: Optional[int], check_every: int = 0) -> SolveStats:
-    """hipk_pbicgstab_solve_cb: the device-resident BiCGStab loop with a CALLABLE preconditioner (TSL:859-964 with M)."""
-    return _solve_with_callback("bicgstab", h, M, b, x, tol=tol, atol=atol, maxiter=maxiter, check_every=check_every)
+                            maxiter: Optional[int], check_every: int = 0, work: Optional[torch.Tensor] = None) -> SolveStats:
+    """hipk_pbicgstab_solve_cb: the device-resident BiCGStab loop with a CALLABLE preconditioner (TSL:859-964 with M).
+    `work`: as in `solve`; M is called on views of it."""
+    return _solve_with_callback("bicgstab", h, M, b, x, tol=tol, atol=atol, maxiter=maxiter, check_every=check_every, work=work)
 
 
 def solve_gmres_callable(h: CsrHandle, M, b: torch.Tensor, x: torch.Tensor, *, tol: float, atol: float,
-                         maxiter: Optional[int], restart: int = 20, solve_method: str = "batched") -> SolveStats:
-    """hipk_pgmres_solve_cb: GMRES with a CALLABLE preconditioner applied after every A (TSL:641-803 with M)."""
+                         maxiter: Optional[int], restart: int = 20, solve_method: str = "batched",
+                         work: Optional[torch.Tensor] = None) -> SolveStats:
+    """hipk_pgmres_solve_cb: GMRES with a CALLABLE preconditioner applied after every A (TSL:641-803 with M).
+    `work`: as in `solve`; M is called on views of it."""
     return _solve_with_callback("gmres", h, M, b, x, tol=tol, atol=atol, maxiter=maxiter, restart=restart,
-                                solve_method=solve_method)
+                                solve_method=solve_method, work=work)
 
 
 def _solve_with_callback(kind: str, h: CsrHandle, M, b: torch.Tensor, x: torch.Tensor, *, tol: float, atol: float,
                          maxiter: Optional[int], check_every: int = 0, restart: int = 20,
-                         solve_method: str = "batched") -> SolveStats:
+                         solve_method: str = "batched", work: Optional[torch.Tensor] = None) -> SolveStats:
     """The C loop calls back here where the reference applies M -- BiCGStab: phat = M(p), shat = M(s), M(b - A x);
     GMRES: M(A v), M(b - A x), M b -- with pointers into the workspace; they are wrapped as views of the workspace
     tensor (no copy in), `M` runs on the current stream, its result is copied into the output slot.  No
@@ -1079,7 +1108,7 @@ def _solve_with_callback(kind: str, h: CsrHandle, M, b: torch.Tensor, x: torch.T
     else:
         wb = int(L.hipk_pbicgstab_work_bytes(h.n, _dtype_code(h.dtype)))
         fn = L.hipk_pbicgstab_solve_cb
-    work = torch.empty(wb, dtype=torch.uint8, device=h.device)
+    work = _workspace(work, h.device, wb)
     if hasattr(h, "regions"):   # OpHandle: the operator callback resolves raw pointers against these tensors
         h.regions.append(work)
     base, nbytes = work.data_ptr(), h.n * work.new_empty(0, dtype=h.dtype).element_size()

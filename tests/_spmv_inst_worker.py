@@ -1,11 +1,14 @@
 """Shared by tests/test_gpu_spmv_instantiations.py and run by it as a child process: the references of one (matrix, storage type)
 of tests/_spmv_cases.py, and the run of one case -- switches, THEN the handle, hipk_spmv_ex per mode, the kernel note read right
-after the call, every output compared bit for bit with the oracle.
+after the call, every output compared bit for bit with the oracle.  y lies in a guarded arena of exactly n elements
+(tests/_arena.py) and, for hipk_spmv_dot, the scratch in one of exactly hipk_scratch_bytes() filled with 0xFF: the guards are
+checked after every launch.
 
 As a program: python _spmv_inst_worker.py GROUP OUT.json CASE...  runs the cases of one fresh-process group (switches that
 hipk_launch_spmv reads once per process) in this process and writes {case: {"notes": [...], "failures": [...]}}.  GROUP
 "order:NAME" takes the cases from tests/_order_cases.py (tests/test_gpu_entry_order.py: unsorted and duplicate rows) instead."""
 import json
+import math
 import os
 import sys
 
@@ -116,6 +119,15 @@ class OnDevice:
         self.crow32, self.col32 = None, None         # int32 copies, made when a case asks for them (idx_bytes 4)
         self.x, self.w, self.b = to(ref.x), to(ref.w), to(ref.b)
         self.x0, self.w0, self.b0 = self.x.clone(), self.w.clone(), self.b.clone()
+        self.y_arena, self.scratch_arena = None, None   # made by the first launch, kept for the matrix
+
+    def arenas(self, scratch_bytes):
+        from _arena import Arena, guard_bytes_for
+        if self.y_arena is None:
+            n, item = self.x.numel(), self.x.element_size()
+            self.y_arena = Arena(DEV, n * item, 16, guard_bytes_for(n, item))
+            self.scratch_arena = Arena(DEV, scratch_bytes, 256, guard_bytes_for(n, item))
+        return self.y_arena, self.scratch_arena
 
     def unchanged(self):
         import torch
@@ -126,14 +138,31 @@ def _launch(hipk, h, ref, dev, mode, wx):
     import torch
     L = hipk.lib()
     n, G = ref.n, int(L.hipk_chunk_count(ref.n))
-    y = torch.full((n,), float("nan"), dtype=dev.x.dtype, device=DEV)
+    ya, _ = dev.arenas(int(L.hipk_scratch_bytes()))
+    y = ya.view(dev.x.dtype, n)
+    y.fill_(float("nan"))
     p0 = torch.full((G,), float("nan"), dtype=torch.float64, device=DEV)
     p1 = torch.full((G,), float("nan"), dtype=torch.float64, device=DEV)
     w = dev.x if wx else dev.w
     hipk._check(L.hipk_spmv_ex(h._h, dev.x.data_ptr(), y.data_ptr(), mode, w.data_ptr(), dev.b.data_ptr(), p0.data_ptr(), p1.data_ptr(),
                                None, 0, torch.cuda.current_stream().cuda_stream), "hipk_spmv_ex")
     note = hipk.CsrHandle.last_spmv_kernel()
-    return note, y.cpu().numpy(), p0.cpu().numpy(), p1.cpu().numpy()
+    return note, y.cpu().numpy(), p0.cpu().numpy(), p1.cpu().numpy(), ya.guards_intact() or ya.touched()
+
+
+def _launch_dot(hipk, h, ref, dev):
+    """hipk_spmv_dot (y = A x with <w, y>): y and the scratch in guarded arenas, the scratch filled with 0xFF."""
+    import torch
+    L = hipk.lib()
+    ya, sa = dev.arenas(int(L.hipk_scratch_bytes()))
+    y = ya.view(dev.x.dtype, ref.n)
+    y.fill_(float("nan"))
+    sa.fill(0xFF)
+    out = torch.full((1,), float("nan"), dtype=torch.float64, device=DEV)
+    hipk._check(L.hipk_spmv_dot(h._h, dev.x.data_ptr(), y.data_ptr(), dev.w.data_ptr(), out.data_ptr(), sa.data_ptr(),
+                                torch.cuda.current_stream().cuda_stream), "hipk_spmv_dot")
+    note = hipk.CsrHandle.last_spmv_kernel()
+    return note, y.cpu().numpy(), float(out.cpu()), [a.guards_intact() or a.touched() for a in (ya, sa)]
 
 
 def run_case(hipk, name, ref, dev, setenv, case=None):
@@ -178,17 +207,37 @@ def run_case(hipk, name, ref, dev, setenv, case=None):
                 setenv(k, v)
             for mode, wx in case["runs"]:
                 tag = f"{name} step {si} mode {mode}" + (" w=x" if wx else "")
-                got, y, p0, p1 = _launch(hipk, h, ref, dev, mode, wx)
+                got, y, p0, p1, intact = _launch(hipk, h, ref, dev, mode, wx)
+                if intact is not True:
+                    failures.append(f"{tag} [{got}]: a write outside y[0..n) (first, last offset, bytes: {intact})")
                 notes.append([si, mode, wx, got])
                 if got != want[mode]:
                     failures.append(f"{tag}: kernel {got}, expected {want[mode]}")
                 check(tag, got, mode, wx, y, p0, p1)
                 outs[(mode, wx)] = (y, p0, p1)
+            # hipk_spmv_dot with the step's switches: the bits of y, a finite <w, y> whatever the scratch held, no byte outside
+            tag = f"{name} step {si} hipk_spmv_dot"
+            got, y, dot, intact = _launch_dot(hipk, h, ref, dev)
+            d = differs(y, ref.y[False])
+            if d is not None:
+                failures.append(f"{tag} [{got}] y: {d}")
+            # <w, y> is the fp64 fold of the g chunk partials that mode 1 is pinned to bit for bit (ref.part0): g doubles summed in
+            # whatever order lie within g 2^-53 sum |part| of their exact sum, in both storage types
+            parts = ref.part0[(False, False)]
+            want_dot = math.fsum(parts)
+            bound = len(parts) * 2.0 ** -53 * math.fsum(np.abs(parts))
+            if not abs(dot - want_dot) <= bound:
+                failures.append(f"{tag} [{got}]: <w, y> = {dot!r}, {want_dot!r} expected within {bound:.3e}")
+            for what, ok in zip(("y[0..n)", "scratch[0..hipk_scratch_bytes)"), intact):
+                if ok is not True:
+                    failures.append(f"{tag} [{got}]: a write outside {what} (first, last offset, bytes: {ok})")
         if case["also_plain"]:
             h.set_path(plain_only=True)
             for mode, wx in case["runs"]:
                 tag = f"{name} plain CSR kernels mode {mode}" + (" w=x" if wx else "")
-                got, y, p0, p1 = _launch(hipk, h, ref, dev, mode, wx)
+                got, y, p0, p1, intact = _launch(hipk, h, ref, dev, mode, wx)
+                if intact is not True:
+                    failures.append(f"{tag} [{got}]: a write outside y[0..n) (first, last offset, bytes: {intact})")
                 if not got.startswith("hipk_spmv_kernel<"):
                     failures.append(f"{tag}: kernel {got}, expected hipk_spmv_kernel<...>")
                 cy, c0, c1 = outs[(mode, wx)]

@@ -94,6 +94,20 @@ def test_block_jacobi_kernel_bit_exact(hipk, oracle, n, bs, dt):
         ref = out
     z = hipk.block_jacobi_apply(torch.from_numpy(binv).to(dt).to(DEV).contiguous(), bs, torch.from_numpy(v).to(dt).to(DEV))
     assert np.array_equal(z.cpu().numpy(), ref)
+    # the same call with `out` in a guarded arena of exactly n elements, v and binv in arenas too (tests/_arena.py): the last block
+    # is ragged where n is no multiple of bs, and nothing past out[n - 1] (or before out[0]) may be written
+    from _arena import Arena, check_memory, guard_bytes_for
+    item = torch.empty(0, dtype=dt).element_size()
+    g = guard_bytes_for(n, item)
+    oa, va, ba = Arena(DEV, n * item, 16, g), Arena(DEV, n * item, 16, g), Arena(DEV, nb * bs * bs * item, 16, g)
+    vd, bd = va.put(torch.from_numpy(v).to(dt)), ba.put(torch.from_numpy(binv).to(dt))
+    oa.fill(0xFF)
+    va.snapshot()
+    ba.snapshot()
+    hipk._check(hipk.lib().hipk_block_jacobi_apply(n, bs, bd.data_ptr(), vd.data_ptr(), oa.data_ptr(), hipk._dtype_code(dt),
+                                                   hipk._stream(torch.device(DEV))), "hipk_block_jacobi_apply")
+    check_memory({"out": oa, "v": va, "binv": ba}, {"v": va, "binv": ba}, f"hipk_block_jacobi_apply n={n} bs={bs}")
+    assert oa.payload.cpu().numpy().tobytes() == ref.tobytes()
 
 
 @pytest.mark.gpu

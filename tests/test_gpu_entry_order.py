@@ -244,6 +244,29 @@ def _with_empty_rows(crow, col, val):
     return np.concatenate([[0], np.cumsum(lens)]).astype(np.int64), col[keep], val[keep]
 
 
+def _transpose_in_arenas(hipk, h, n_cols, nnz, ht):
+    """hipk_csr_transpose with `work` in a guarded arena of exactly hipk_csr_transpose_work_bytes and crow_t, col_t, val_t in arenas
+    of exactly n_cols + 1, nnz and nnz elements (tests/_arena.py), in the four workspace states: no byte outside them is written,
+    and the outputs are those of CsrHandle.transposed() whatever the workspace held."""
+    from _arena import Arena, guard_bytes_for, run_states
+    L = hipk.lib()
+    wb = int(L.hipk_csr_transpose_work_bytes(h.ptr))
+    item = ht.val.element_size()
+    g = guard_bytes_for(max(nnz, n_cols + 1), 8)
+    out = {"crow_t": Arena(DEV, 4 * (n_cols + 1), 16, g), "col_t": Arena(DEV, 4 * nnz, 16, g), "val_t": Arena(DEV, item * nnz, 16, g)}
+    work = Arena(DEV, wb, 256, g)
+
+    def run(i):
+        for a in out.values():
+            a.fill(0xA5)
+        hipk._check(L.hipk_csr_transpose(h.ptr, out["crow_t"].data_ptr(), out["col_t"].data_ptr(), out["val_t"].data_ptr(),
+                                         work.data_ptr(), wb, hipk._stream(h.device)), "hipk_csr_transpose")
+        return {k: a.payload.cpu().numpy().tobytes() for k, a in out.items()}
+    res = run_states(work, out, {}, run, label="hipk_csr_transpose")
+    for k, t in (("crow_t", ht.crow), ("col_t", ht.col), ("val_t", ht.val)):
+        assert res[0][k] == t.cpu().numpy().tobytes(), k
+
+
 @pytest.mark.parametrize("dtype", [OC.DOUBLE, OC.FLOAT])
 @pytest.mark.parametrize("empty", [False, True], ids=["square", "empty_rows"])
 @pytest.mark.parametrize("transform", ["shuf", "dup_shuf", "zero"])
@@ -269,6 +292,7 @@ def test_transpose_is_a_stable_sort_by_column(hipk, oracle, transform, empty, dt
         assert np.array_equal(ht.crow.cpu().numpy(), crow_t) and np.array_equal(ht.col.cpu().numpy(), col_t)
         got = ht.val.cpu().numpy()
         assert np.array_equal(got.view(np.int64 if f == np.float64 else np.int32), val_t.view(np.int64 if f == np.float64 else np.int32))
+        _transpose_in_arenas(hipk, h, n, len(col), ht)
         x = np.random.default_rng(n).standard_normal(n).astype(f)
         y = hipk.spmv(ht, torch.from_numpy(x).to(DEV)).cpu().numpy()
         _reported(notes=[hipk.CsrHandle.last_spmv_kernel()])

@@ -7,15 +7,20 @@ both sides of each dispatch boundary, and the edges inside the loops.  Each case
   * the returned stats against a long-double recomputation from the stored A, b and the returned x, so that the kernels and
     the oracle cannot share a bug unnoticed.
 
-Sizes that depend on the device (its compute-unit count n_cu) are resolved when a case runs; the paths do not depend on it."""
-import zlib
+Every solve runs through tests/_solve_runner.py: the workspace in a guarded arena of exactly *_work_bytes, x, b and dinv in arenas
+of exactly n elements, once per workspace state (0x00, 0xFF, 0x5A fill, no refill).  The path, the guards and the read-only
+operands are asserted after every run (the form too: form_of below); the 0x00 run feeds the assertions above, the others must
+equal it bit for bit.  No solve of this table takes 0.5 s on the GPU (the longest 0.008 s): every case runs all four states.
 
+Sizes that depend on the device (its compute-unit count n_cu) are resolved when a case runs; the paths do not depend on it."""
 import numpy as np
 import pytest
 import scipy.sparse as sp
 import torch
 
+from _arena import FILLS
 from _oracle_cases import _band, _check_stats_long_double, _ldc, _signed_band
+from _solve_runner import build_case, run_solve_case
 
 DEV = "cuda:0"
 CH = 2048            # rows per reduction chunk below 4 M rows (hipk_chunk_size)
@@ -335,6 +340,14 @@ ORACLE = {"cg": "cg", "pcg": "pcg_jacobi", "bicgstab": "bicgstab", "pbicgstab": 
 _built = {}
 
 
+def form_of(path):
+    """The expected hipk_last_solve_form of a row: a mid loop that finishes the solve names its instantiation as path AND form
+    (hipk_*_one_launch: hipk_set_solve_form(path.mid_entry->name)), so the form of such a row is its path literal.  The other rows
+    (the launch sequence, the LDS kernels, the hand-backs) finish in forms that tests/_form_cases.py pins by literal; here None:
+    the form of the first workspace state, in every state."""
+    return path if "_mid_kernel<" in path and " -> " not in path else None
+
+
 def _matrix(key, dt):
     """(scipy CSR with the stored values, device CSR tensor) for matrix `key` in storage dtype dt (cached per process)."""
     if (key, dt) not in _built:
@@ -355,32 +368,10 @@ def test_mid_loop_vs_oracle(hipk, oracle, monkeypatch, cid, key, dtn, kw, env, x
     dt = np.float64 if dtn == F64 else np.float32
     for k, v in env.items():
         monkeypatch.setenv(k, v)
-    M, A = _matrix(key, dt)
-    h = hipk.handle_for(A)
-    n = M.shape[0]
-    rng = np.random.default_rng(zlib.crc32(cid.encode()))
-    x0 = rng.standard_normal(n).astype(dt) if x0kind in ("rand", "exact") else None
-    if x0kind == "exact":       # b = A x0 (the library's own product): the loop stops at iteration 0
-        b = hipk.spmv(h, torch.from_numpy(x0).to(DEV)).cpu().numpy()
-    elif x0kind == "consistent":  # b = A x_true (the LDC matrix is singular)
-        b = (M.astype(np.float64) @ rng.standard_normal(n)).astype(dt)
-    else:
-        b = rng.standard_normal(n).astype(dt)
-    dinv = (1.0 / M.diagonal().astype(np.float64)).astype(dt) if solver in ("pcg", "pbicgstab", "pgmres") else None
-    bd = torch.from_numpy(b).to(DEV)
-    xd = torch.zeros_like(bd) if x0 is None else torch.from_numpy(x0).to(DEV)
+    M, h, b, x0, dinv = build_case(hipk, _matrix, cid, solver, key, dt, x0kind)
     gkw = {k: v for k, v in kw.items() if k in ("restart", "solve_method")}
     print("mid oracle case", cid, flush=True)   # (-s: which case a hang is in)
-    if solver in ("cg", "bicgstab", "gmres"):
-        st = hipk.solve(solver, h, bd, xd, tol=kw["tol"], atol=0.0, maxiter=kw["maxiter"], **gkw)
-    elif solver == "pgmres":
-        st = hipk.solve_pgmres(h, torch.from_numpy(dinv).to(DEV), bd, xd, tol=kw["tol"], atol=0.0, maxiter=kw["maxiter"], **gkw)
-    else:
-        st = hipk.solve_pcg(h, torch.from_numpy(dinv).to(DEV), bd, xd, tol=kw["tol"], atol=0.0, maxiter=kw["maxiter"],
-                            method={"pcg": "cg", "pbicgstab": "bicgstab"}[solver])
-    got_path = hipk.last_solve_path()
-    x = xd.cpu().numpy()
-    assert got_path == path, (cid, got_path)
+    st, x, _ = run_solve_case(hipk, cid, solver, h, b, x0, dinv, kw, path, form_of(path), FILLS)
 
     fn = getattr(oracle, ORACLE[solver] + ("32" if dt == np.float32 else ""))
     args = (M.indptr, M.indices, M.data) + ((dinv,) if dinv is not None else ()) + (b,)

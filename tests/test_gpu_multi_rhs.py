@@ -2,7 +2,11 @@
 of a block solve is bit for bit the single solve of that column on the device and the oracle's solve of it, with the same info,
 iterations and matvecs; the block loop ran (its path name), and the block-SpMV launch count is max_j matvecs_j per block of 16
 columns -- not the sum a column-by-column loop would give.  The public cg_multi / bicgstab_multi route device operands to the
-column loop (measured faster, multi_rhs._multi): pinned here too, with the same bits."""
+column loop (measured faster, multi_rhs._multi): pinned here too, with the same bits.
+
+The k sweeps and the tile / chunk edge sizes also run the block solve on guarded memory (tests/_arena.py): B and X (ldb = ldx = k)
+in arenas of exactly n * k elements, `work` in one of exactly hipk_multi_work_bytes, in the four workspace states; every run must
+leave the guards and B alone and reproduce, bit for bit, the X and the column stats pinned above."""
 import json
 import os
 
@@ -42,8 +46,42 @@ def _same(a, b):
     return a == b or (a != a and b != b)
 
 
-def check(oracle, kind, A, B, X0=None, M=None, use_oracle=True, **kw):
-    """Runs the block solve and, column by column, the single solve and the oracle; asserts the whole contract."""
+def _check_in_arenas(kind, A, B, X0, M, X, st, kw):
+    """hipk_{cg,bicgstab}_solve_multi with B, X and work in guarded memory, once per workspace state: equal to (X, st) every time."""
+    from pytorch_sparse_solver import _hipk
+    from _arena import Arena, guard_bytes_for, run_states
+    from _solve_runner import stat_bits
+    h = _hipk.handle_for(A)
+    n, k = B.shape
+    item = X.element_size()
+    g = guard_bytes_for(n, item)
+    ba, xa = Arena(DEV, n * k * item, 16, g), Arena(DEV, n * k * item, 16, g)
+    Bd = ba.put(B.to(X.dtype)).view(n, k)
+    X0d = torch.zeros_like(X) if X0 is None else X0.to(X.dtype).contiguous()
+    Xd = xa.view(X.dtype, n * k).view(n, k)
+    guarded, readonly = {"X": xa, "B": ba}, {"B": ba}
+    dinv = None
+    if M is not None:
+        da = Arena(DEV, n * item, 16, g)
+        dinv = da.put(M.dinv.to(X.dtype))
+        guarded["dinv"] = readonly["dinv"] = da
+    work = Arena(DEV, _hipk.multi_work_bytes(n, k, X.dtype, kind, dinv is not None), 256, g)
+
+    def run(i):
+        Xd.copy_(X0d)
+        s = _hipk.solve_multi(kind, h, dinv, Bd, Xd, tol=kw.get("tol", 1e-5), atol=kw.get("atol", 0.0), maxiter=kw.get("maxiter"),
+                              work=work.payload)
+        assert _hipk.last_solve_path() == f"hipk_{kind}_multi launch sequence"
+        return {"X": xa.payload.cpu().numpy().tobytes(), "stats": b"".join(stat_bits(c) for c in s.columns),
+                "block_spmvs": s.block_spmvs}
+    res = run_states(work, guarded, readonly, run, label=f"{kind}_multi n={n} k={k}")
+    assert res[0]["X"] == X.contiguous().cpu().numpy().tobytes(), "the block solve on guarded memory differs from the one on fresh tensors"
+    assert res[0]["stats"] == b"".join(stat_bits(c) for c in st.columns) and res[0]["block_spmvs"] == st.block_spmvs
+
+
+def check(oracle, kind, A, B, X0=None, M=None, use_oracle=True, arenas=False, **kw):
+    """Runs the block solve and, column by column, the single solve and the oracle; asserts the whole contract.
+    arenas: also on guarded memory in every workspace state (_check_in_arenas)."""
     from pytorch_sparse_solver import _hipk
     from pytorch_sparse_solver.module_a import bicgstab, bicgstab_multi, cg, cg_multi, get_last_stats
     from pytorch_sparse_solver.module_a.multi_rhs import _block_solve
@@ -56,6 +94,8 @@ def check(oracle, kind, A, B, X0=None, M=None, use_oracle=True, **kw):
     assert _hipk.last_solve_path() == f"hipk_{kind}_multi launch sequence"
     assert np.array_equal(_bits(Xp), _bits(X)) and torch.equal(infop, info)
     assert isinstance(st, _hipk.MultiSolveStats)
+    if arenas:
+        _check_in_arenas(kind, A, B, X0, M, X, st, kw)
     n, k = B.shape
     wdt = torch.float32 if A.dtype == torch.float32 else torch.float64
     assert X.shape == (n, k) and X.dtype == wdt and X.device == B.device
@@ -135,14 +175,14 @@ def _eigvec(nx, p, q):
 @pytest.mark.parametrize("k", [1, 2, 3, 8, 16, 17])
 def test_cg_multi_k_sweep(hipk, oracle, k):
     A = _poisson(40)
-    _, info, st = check(oracle, "cg", A, _rhs(1600, k, k), tol=1e-6)
+    _, info, st = check(oracle, "cg", A, _rhs(1600, k, k), arenas=True, tol=1e-6)
     assert (info == 0).all()
 
 
-@pytest.mark.parametrize("k", [1, 3, 17])
+@pytest.mark.parametrize("k", [1, 2, 3, 8, 16, 17])
 def test_bicgstab_multi_k_sweep(hipk, oracle, k):
     A = _convdiff(40)
-    check(oracle, "bicgstab", A, _rhs(1600, k, 100 + k), tol=1e-6)
+    check(oracle, "bicgstab", A, _rhs(1600, k, 100 + k), arenas=True, tol=1e-6)
 
 
 # ------------------------------------------------------------------ n at tile (256) and chunk (2048) edges
@@ -150,7 +190,7 @@ def test_bicgstab_multi_k_sweep(hipk, oracle, k):
 @pytest.mark.parametrize("kind", ["cg", "bicgstab"])
 def test_multi_tile_and_chunk_edges(hipk, oracle, kind, n):
     A = _random_spd(n, seed=n)
-    check(oracle, kind, A, _rhs(n, 3, n), tol=1e-7)
+    check(oracle, kind, A, _rhs(n, 3, n), arenas=True, tol=1e-7)
 
 
 @pytest.mark.parametrize("kind,nx,maxiter", [("cg", 200, None), ("bicgstab", 200, None), ("cg", 500, 300)])

@@ -9,19 +9,31 @@ their own table, tests/test_gpu_mid_oracle.py.)  Each case asserts
   * the returned stats against a long-double recomputation from the stored A, b and the returned x.
 
 The callback-M cases of GMRES compare as test_gpu_pcg.py's callable-M test does (counts equal, x to 1e-9): their ||M(.)||^2 is
-a chunked dot, the oracle's a tiled one."""
-import zlib
+a chunked dot, the oracle's a tiled one.
 
+Every solve runs through tests/_solve_runner.py: the workspace in a guarded arena of exactly *_work_bytes, x, b and dinv in arenas
+of exactly n elements, once per workspace state (0x00, 0xFF, 0x5A fill, no refill).  Path, form, guards and read-only operands are
+asserted after every run; the 0x00 run feeds the assertions above, the others must equal it bit for bit.  The cases of
+TWO_STATES keep the 0x00 and 0xFF runs only."""
 import numpy as np
 import pytest
 import torch
 
+from _arena import FILLS, FILLS_SHORT
 from _form_cases import CASES, F64, FIXED_B, MATRICES
 from _oracle_cases import _check_stats_long_double
+from _solve_runner import build_case, run_solve_case
 
 DEV = "cuda:0"
 ORACLE = {"cg": "cg", "pcg": "pcg_jacobi", "bicgstab": "bicgstab", "pbicgstab": "bicgstab_jacobi", "gmres": "gmres",
           "pgmres": "gmres_jacobi"}
+# cases whose GPU solve alone takes more than 0.5 s (0.64 and 0.60 s on one MI355X before this runner existed; the next one takes
+# 0.47 s): they keep the 0x00 and 0xFF workspace states (at most 10 % of the table)
+TWO_STATES = frozenset([
+    "pgmres-big-r255-c1r-split-f32",
+    "gmres-big-r255-c1r-f32",
+])
+assert TWO_STATES <= {c[0] for c in CASES} and 10 * len(TWO_STATES) <= len(CASES)
 _built = {}
 
 
@@ -44,46 +56,19 @@ def test_solver_form_vs_oracle(hipk, oracle, monkeypatch, cid, solver, key, dtn,
     dt = np.float64 if dtn == F64 else np.float32
     for k, v in env.items():     # before the handle exists
         monkeypatch.setenv(k, v)
-    M, A = _matrix(key, dt)
-    h = hipk.handle_for(A)
+    M, h, b, x0, dinv = build_case(hipk, _matrix, cid, solver, key, dt, x0kind, FIXED_B)
     n = M.shape[0]
-    rng = np.random.default_rng(zlib.crc32(cid.encode()))
-    x0 = rng.standard_normal(n).astype(dt) if x0kind in ("rand", "exact") else None
-    if x0kind == "exact":       # b = A x0 (the library's own product): the loop stops at iteration 0
-        b = hipk.spmv(h, torch.from_numpy(x0).to(DEV)).cpu().numpy()
-    elif x0kind == "fixture":
-        b = FIXED_B[key]().astype(dt)
-    else:
-        b = rng.standard_normal(n).astype(dt)
-    pre = solver in ("pcg", "pbicgstab", "pgmres")
+    pre = dinv is not None
     callback = bool(kw.get("callback"))
-    dinv = (1.0 / M.diagonal().astype(np.float64)).astype(dt) if pre else None
-    bd = torch.from_numpy(b).to(DEV)
-    xd = torch.zeros_like(bd) if x0 is None else torch.from_numpy(x0).to(DEV)
-    dd = torch.from_numpy(dinv).to(DEV) if pre else None
-    gkw = {k: v for k, v in kw.items() if k in ("restart", "solve_method")}
     print("solver form case", cid, flush=True)   # (-s: which case a hang is in)
-    if callback and solver == "pbicgstab":
-        st = hipk.solve_bicgstab_callable(h, lambda v: dd * v, bd, xd, tol=kw["tol"], atol=0.0, maxiter=kw["maxiter"])
-    elif callback:
-        st = hipk.solve_gmres_callable(h, lambda v: dd * v, bd, xd, tol=kw["tol"], atol=0.0, maxiter=kw["maxiter"], **gkw)
-    elif not pre:
-        st = hipk.solve(solver, h, bd, xd, tol=kw["tol"], atol=0.0, maxiter=kw["maxiter"], **gkw)
-    elif solver == "pgmres":
-        st = hipk.solve_pgmres(h, dd, bd, xd, tol=kw["tol"], atol=0.0, maxiter=kw["maxiter"], **gkw)
-    else:
-        st = hipk.solve_pcg(h, dd, bd, xd, tol=kw["tol"], atol=0.0, maxiter=kw["maxiter"], method={"pcg": "cg", "pbicgstab": "bicgstab"}[solver])
-    got_path, got_form = hipk.last_solve_path(), hipk.last_solve_form()
-    x = xd.cpu().numpy()
-    assert got_path == path, (cid, got_path, got_form)
-    assert got_form == form, (cid, got_form)
+    st, x, bd = run_solve_case(hipk, cid, solver, h, b, x0, dinv, kw, path, form, FILLS_SHORT if cid in TWO_STATES else FILLS)
     assert np.array_equal(bd.cpu().numpy(), b), cid
 
     fn = getattr(oracle, ORACLE[solver] + ("32" if dt == np.float32 else ""))
     args = (M.indptr, M.indices, M.data) + ((dinv,) if pre else ()) + (b,)
     okw = dict(x0=x0, tol=kw["tol"], atol=0.0, maxiter=kw["maxiter"])
     if solver in ("gmres", "pgmres"):
-        okw.update(gkw, gpu_tolerances=True)
+        okw.update({k: v for k, v in kw.items() if k in ("restart", "solve_method")}, gpu_tolerances=True)
     oracle.set_threads(16 if n >= 100_000 else 4 if n >= 10_000 else 1)   # (the bits do not depend on it; small systems lose time to threads)
     try:
         ref = fn(*args, **okw)
