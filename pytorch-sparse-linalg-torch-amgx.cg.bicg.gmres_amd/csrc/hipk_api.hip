@@ -905,15 +905,9 @@ int hipk_launch_spmv(const hipk_csr_s *h, const hipk_spmv_args &a_, hipStream_t 
 }
 
 static void hipk_fill_spmv_args(const hipk_csr_s *h, hipk_spmv_args &a, const void *x, void *y) {
-    memset(&a, 0, sizeof(a));
-    a.crow = h->crow;
-    a.col = h->col;
-    a.val = h->val;
+    a = hipk_spmv_base(h);
     a.x = x;
     a.y = y;
-    a.n = h->n_rows;
-    a.ch = h->geom.ch;
-    a.g = h->geom.g;
 }
 
 extern "C" int hipk_spmv(hipk_csr_t h, const void *x, void *y, hipk_stream_t stream) {

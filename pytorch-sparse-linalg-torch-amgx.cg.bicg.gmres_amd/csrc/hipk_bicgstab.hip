@@ -667,20 +667,62 @@ __global__ __launch_bounds__(HIPK_THREADS) void hipk_bi_final_kernel(hipk_bi_sca
 
 static constexpr int kBiSlots = 8;
 
-extern "C" size_t hipk_bicgstab_work_bytes(int64_t n, int dtype) {
-    const size_t sv = (dtype == HIPK_F64) ? 8 : 4;
-    const size_t vec = hipk_align_up((size_t)(n > 0 ? n : 1) * sv, 256);
-    // mid-size systems (hipk_bi_mid.h): q and r travel as 16-byte flagged words (q in s + t, r in two more vectors) + the partial slots
+// ---------------------------------------------------------------- the workspace of a solve
+// Byte offsets, from (n, dtype, pre) alone: hipk_bicgstab_work_bytes and hipk_pbicgstab_work_bytes return .total, the solve takes
+// its pointers from the rest.  scalars (hipk_bi_scal) | kBiSlots partial arrays | r, rhat, p, q, s, t | two more vector places
+// (pre: phat, shat) | mid-size systems: the flagged words and partial slots of hipk_bi_mid_kernel.
+// Three loop forms use it -- the mid loop, the LDS loop, the five-launch sequence -- one after the other: a one-launch loop has
+// returned (finished, or handed the solve back) before the next form's first launch is enqueued, and none runs twice.  A region
+// of one form may therefore lie in bytes that another form owns.
+struct hipk_bi_layout {
+    size_t scal;
+    // chunk partials of the five-launch sequence; part_spare: the dot slot an SpMV does not need
+    size_t part_rr, part_rhr, part_rq, part_ss, part_ts, part_tt, part_bb, part_spare;
+    size_t r, rhat, p, q, s, t;
+    size_t phat, shat;   // the SpMV inputs (TSL:908, 922); M = identity: p and s themselves
+    // The LDS loop (hipk_bi_solve_lds_kernel) in slots of the five-launch sequence, whose <t,s> and <t,t> partials are only
+    // written once that sequence runs:
+    size_t lds_flags;    // 3 x kHoMaxWg hand-off words, in the <t,t> slot
+    size_t lds_tsum2;    // the third tile-sum array, 4 words per tile, in the <t,s> slot
+    // The mid loop (hipk_bi_mid_kernel), behind the EIGHT vector places whether the solve is preconditioned or not (present iff mid):
+    bool mid;
+    size_t ll_bytes;     // n 16-byte flagged words, whatever the dtype
+    size_t q_ll, r_ll;   // q and r as flagged words
+    size_t slots;        // kBiMidSlotBytes of chunk-partial slots
+    size_t total;
+};
+static_assert(3 * kHoMaxWg <= HIPK_MAX_PARTS, "the LDS loop's hand-off flags fit the <t,t> slot");
+static_assert(4 * kHoMaxChunks * (HIPK_BASE_CHUNK / HIPK_TILE) <= HIPK_MAX_PARTS, "the LDS loop's third tile-sum array fits the <t,s> slot");
+
+static hipk_bi_layout hipk_bi_make_layout(int64_t n, int dtype, bool pre) {
+    const size_t rows = (size_t)(n > 0 ? n : 1), vec = hipk_align_up(rows * (dtype == HIPK_F64 ? 8 : 4), 256);
     const hipk_geom gm = hipk_make_geom(n > 0 ? n : 1);
-    const bool mid = gm.g > kMidMinChunks && gm.g <= kBiMidMaxChunks;
-    const size_t ll = hipk_align_up((size_t)(n > 0 ? n : 1) * 16, 256);   // q and r as 16-byte flagged words whatever the dtype
-    return 256 + (size_t)kBiSlots * HIPK_MAX_PARTS * sizeof(double) + 6 * vec + (mid ? 2 * vec + 2 * ll + kBiMidSlotBytes : 0);
+    hipk_bi_layout L;
+    hipk_carve take;
+    L.scal = take(256);
+    size_t *const parts[kBiSlots] = {&L.part_rr, &L.part_rhr, &L.part_rq, &L.part_ss, &L.part_ts, &L.part_tt, &L.part_bb, &L.part_spare};
+    for (size_t *slot : parts) *slot = take(HIPK_MAX_PARTS * sizeof(double));
+    L.lds_flags = L.part_tt;
+    L.lds_tsum2 = L.part_ts;
+    size_t *const vecs[6] = {&L.r, &L.rhat, &L.p, &L.q, &L.s, &L.t};
+    for (size_t *v : vecs) *v = take(vec);
+    L.mid = gm.g > kMidMinChunks && gm.g <= kBiMidMaxChunks;
+    // places seven and eight: phat and shat of a preconditioned solve; a plain solve of a mid-size system leaves them unused
+    const size_t v7 = (pre || L.mid) ? take(vec) : 0, v8 = (pre || L.mid) ? take(vec) : 0;
+    L.phat = pre ? v7 : L.p;
+    L.shat = pre ? v8 : L.s;
+    L.ll_bytes = hipk_align_up(rows * 16, 256);
+    L.q_ll = L.mid ? take(L.ll_bytes) : 0;
+    L.r_ll = L.mid ? take(L.ll_bytes) : 0;   // (directly behind q_ll: one memset clears both)
+    L.slots = L.mid ? take(kBiMidSlotBytes) : 0;
+    // hipk_pbicgstab_work_bytes has always been the plain size + two vectors: at the mid sizes, where the plain size already
+    // holds places seven and eight, two unused vectors end the workspace.  Callers size buffers by it; kept.
+    if (pre && L.mid) take(2 * vec);
+    L.total = take.o;
+    return L;
 }
-extern "C" size_t hipk_pbicgstab_work_bytes(int64_t n, int dtype) {
-    const size_t sv = (dtype == HIPK_F64) ? 8 : 4;
-    const size_t vec = hipk_align_up((size_t)(n > 0 ? n : 1) * sv, 256);
-    return hipk_bicgstab_work_bytes(n, dtype) + 2 * vec;  // + phat, shat
-}
+extern "C" size_t hipk_bicgstab_work_bytes(int64_t n, int dtype) { return hipk_bi_make_layout(n, dtype, false).total; }
+extern "C" size_t hipk_pbicgstab_work_bytes(int64_t n, int dtype) { return hipk_bi_make_layout(n, dtype, true).total; }   // + phat, shat
 
 // the one-launch instantiations the dispatch below selects (hipk_mid_pick), each with the name hipk_last_solve_path reports
 #define HIPK_MID_ROW(W, PRE)                                                                                               \
@@ -694,9 +736,6 @@ static const hipk_mid_entry<hipk_bi_mid_args> hipk_bi_mid_table[] = {
 // {redo, it_done, stop_it} of a host copy of the scalar block (hipk_resident_run)
 static hipk_loop_state hipk_bi_loop_state(const hipk_bi_scal &h) { return {h.redo, h.it_done, h.stop_it}; }
 
-// cb != null (PRE = false): the preconditioner is the CALLER's device code -- cb(user, in, out) enqueues out = M(in) on
-// `stream` -- applied where the Jacobi variant scales in-kernel: phat = M(p) before the first SpMV, shat = M(s) before the
-// second (TSL:908, 922), M(b - A x) for the final test (TSL:1007).  Same kernels, same order of operations.
 // ---- which paths a bicgstab solve takes (PRE: Jacobi; ext: the caller's M through a callback): the only place that knows
 // BiCGStab's switches and size limits.  Two steps, because a mid loop that handed the solve back changes what the LDS loop may do:
 //   hipk_bi_path_begin   before the iteration loop: small and the mid loop
@@ -750,101 +789,105 @@ static void hipk_bi_path_lds(hipk_bi_path &path, const hipk_csr_s *A, const hipk
     }
 }
 
+// what the five-launch sequence launches for its s and x updates, and the partials those fold (hipk_bi_steps::pick)
 template <typename T, bool PRE>
-static int hipk_bicgstab_solve_t(hipk_csr_s *A, const T *dinv, const T *b, T *x, char *work, const hipk_params *prm,
-                                 hipk_stats *st, hipStream_t stream, hipk_precond_fn cb = nullptr, void *user = nullptr) {
-    const bool ext = cb != nullptr;
-    const int64_t n = A->n_rows;
-    const hipk_geom gm = A->geom;
-    const size_t vec = hipk_align_up((size_t)n * sizeof(T), 256);
-    hipk_bi_scal *scal = (hipk_bi_scal *)work;
-    double *parts = (double *)(work + 256);
-    double *part_rr = parts, *part_rhr = parts + HIPK_MAX_PARTS, *part_rq = parts + 2 * HIPK_MAX_PARTS;
-    double *part_ss = parts + 3 * HIPK_MAX_PARTS, *part_ts = parts + 4 * HIPK_MAX_PARTS;
-    double *part_tt = parts + 5 * HIPK_MAX_PARTS, *part_bb = parts + 6 * HIPK_MAX_PARTS;
-    double *part_spare = parts + 7 * HIPK_MAX_PARTS;
-    char *vbase = work + 256 + (size_t)kBiSlots * HIPK_MAX_PARTS * sizeof(double);
-    T *r = (T *)vbase, *rhat = (T *)(vbase + vec), *p = (T *)(vbase + 2 * vec), *q = (T *)(vbase + 3 * vec);
-    T *s = (T *)(vbase + 4 * vec), *t = (T *)(vbase + 5 * vec);
-    T *phat = (PRE || ext) ? (T *)(vbase + 6 * vec) : p, *shat = (PRE || ext) ? (T *)(vbase + 7 * vec) : s;  // SpMV inputs (TSL:908, 922)
+struct hipk_bi_kernels {
+    decltype(&hipk_bi_supdate_kernel<T, PRE, false>) supdate;
+    decltype(&hipk_bi_xupdate_kernel<T, PRE, false>) xupdate;
+    const double *rq, *ts, *tt;   // <rhat,q>, <t,s>, <t,t>: chunk partials, or (small) the SpMVs' tile sums
+    int nt;                       // small: the tile count; else 0
+};
 
-    const int64_t maxiter = (prm->maxiter < 0) ? 10 * n : prm->maxiter;
-    const float tolf = (float)prm->tol, atolf = (float)prm->atol;
-    const double tol2 = (double)(tolf * tolf), atol_sq = (double)(atolf * atolf);
-    const int64_t check = prm->check_every > 0 ? prm->check_every : 32;
-    hipk_set_solve_path(nullptr, "");
+// One single-device solve: its operands, workspace and state, and the steps hipk_bicgstab_solve_t drives it through.
+// PRE: Jacobi, M = diag(dinv) applied in the kernels.  cb != null (PRE = false): the preconditioner is the CALLER's device code
+// -- cb(user, in, out) enqueues out = M(in) on `stream` -- applied where the Jacobi variant scales in-kernel: phat = M(p) before
+// the first SpMV, shat = M(s) before the second (TSL:908, 922), M(b - A x) for the final test (TSL:1007).  Same kernels, same
+// order of operations.
+template <typename T, bool PRE>
+struct hipk_bi_steps {
+    hipk_csr_s *A;
+    const T *dinv, *b;
+    T *x;
+    hipk_precond_fn cb;
+    void *user;
+    const hipk_params *prm;
+    hipStream_t stream;
+    const bool ext;   // M through the callback
+    const int64_t n, maxiter;
+    const hipk_geom gm;
+    const int nt;
+    const hipk_bi_layout lay;
+    char *const work;
+    hipk_bi_scal *const scal = hipk_at<hipk_bi_scal>(work, lay.scal);
+    double *const part_rr = hipk_at<double>(work, lay.part_rr), *const part_rhr = hipk_at<double>(work, lay.part_rhr);
+    double *const part_rq = hipk_at<double>(work, lay.part_rq), *const part_ss = hipk_at<double>(work, lay.part_ss);
+    double *const part_ts = hipk_at<double>(work, lay.part_ts), *const part_tt = hipk_at<double>(work, lay.part_tt);
+    double *const part_bb = hipk_at<double>(work, lay.part_bb), *const part_spare = hipk_at<double>(work, lay.part_spare);
+    T *const r = hipk_at<T>(work, lay.r), *const rhat = hipk_at<T>(work, lay.rhat), *const p = hipk_at<T>(work, lay.p), *const q = hipk_at<T>(work, lay.q);
+    T *const s = hipk_at<T>(work, lay.s), *const t = hipk_at<T>(work, lay.t), *const phat = hipk_at<T>(work, lay.phat), *const shat = hipk_at<T>(work, lay.shat);
+    hipk_event_pair whole;
+    hipk_spmv_profiler prof;
+    hipk_pacer pace;
+    hipk_bi_path path;
+    int64_t it = 0, stop = INT64_MAX;
+    bool done = false;       // a one-launch loop finished the solve
     char handed[128] = "";   // the one-launch loops that handed this solve back
 
-    hipk_event_pair whole;
-    HIPK_CHECK_HIP(whole.create());
-    hipk_spmv_profiler prof(prm->profile != 0 ? HIPK_K_SPMV : 0);
-    HIPK_CHECK_HIP(hipEventRecord(whole.a, stream));
+    hipk_bi_steps(hipk_csr_s *A_, const T *dinv_, const T *b_, T *x_, char *w, const hipk_params *prm_, hipStream_t s_, hipk_precond_fn cb_, void *user_)
+        : A(A_), dinv(dinv_), b(b_), x(x_), cb(cb_), user(user_), prm(prm_), stream(s_), ext(cb_ != nullptr), n(A_->n_rows),
+          maxiter(hipk_default_maxiter(prm_, A_->n_rows)), gm(A_->geom), nt((int)((A_->n_rows + HIPK_TILE - 1) / HIPK_TILE)),
+          lay(hipk_bi_make_layout(A_->n_rows, A_->dtype, PRE || cb_ != nullptr)), work(w), prof(prm_->profile != 0 ? HIPK_K_SPMV : 0),
+          pace(A_->host_poll, &scal->stop_it, prm_->check_every > 0 ? prm_->check_every : 32) {}
 
-    hipk_spmv_args sa;
-    memset(&sa, 0, sizeof(sa));
-    sa.crow = A->crow;
-    sa.col = A->col;
-    sa.val = A->val;
-    sa.n = n;
-    sa.ch = gm.ch;
-    sa.g = gm.g;
-    int rc;
+    // ext: out = M(in) by the caller
+    int precondition(const T *in, T *out) const {
+        if (cb(user, in, out) != 0) {
+            hipk_set_error("hipk_pbicgstab_solve_cb: the preconditioner callback failed");
+            return HIPK_ERR_ARG;
+        }
+        return HIPK_OK;
+    }
 
-    sa.x = x;
-    sa.y = r;
-    sa.mode = HIPK_SPMV_RESID | HIPK_SPMV_DOT_YY;
-    sa.bsub = b;
-    sa.part0 = part_spare;
-    sa.part1 = part_rr;
-    if ((rc = hipk_launch_spmv(A, sa, stream)) != HIPK_OK) return rc;
-    if ((rc = hipk_launch_dot_parts(n, b, b, A->dtype, part_bb, stream)) != HIPK_OK) return rc;
-    hipk_pacer pace(A->host_poll, &scal->stop_it, check);
-    HIPK_CHECK_HIP(pace.create());
-    hipk_bi_start_kernel<T><<<gm.g, HIPK_THREADS, 0, stream>>>(n, gm.ch, gm.g, scal, part_rr, part_bb, part_rhr, r,
-                                                                rhat, p, q, tol2, atol_sq, maxiter, pace.device_sig());
-    HIPK_CHECK_HIP(hipGetLastError());
+    // y = b - A x (scaled: M = diag(dinv) in the SpMV epilogue), the chunk partials of its squared norm in part_yy
+    int residual(T *y, double *part_yy, bool scaled) const {
+        hipk_spmv_args sa = hipk_spmv_base(A);
+        sa.x = x;
+        sa.y = y;
+        sa.mode = HIPK_SPMV_RESID | HIPK_SPMV_DOT_YY | (scaled ? HIPK_SPMV_SCALE : 0);
+        sa.dscale = scaled ? dinv : nullptr;
+        sa.bsub = b;
+        sa.part0 = part_spare;
+        sa.part1 = part_yy;
+        return hipk_launch_spmv(A, sa, stream);
+    }
 
-    hipk_spmv_args sq = sa, stt = sa;
-    sq.x = phat;
-    sq.y = q;
-    sq.mode = HIPK_SPMV_DOT_W;
-    sq.w = rhat;
-    sq.bsub = nullptr;
-    sq.part0 = part_rq;
-    sq.part1 = part_spare;
-    sq.stop_it = &scal->stop_it;
-    stt.x = shat;
-    stt.y = t;
-    stt.mode = HIPK_SPMV_DOT_W | HIPK_SPMV_DOT_YY;
-    stt.w = s;
-    stt.bsub = nullptr;
-    stt.part0 = part_ts;
-    stt.part1 = part_tt;
-    stt.stop_it = &scal->stop_it;
+    // r0 = b - A x0 with <r0,r0>; <b,b>; rhat = p = q = r0, the stop word and the tolerances (TSL:870-890)
+    int start() {
+        hipk_set_solve_path(nullptr, "");
+        HIPK_CHECK_HIP(whole.create());
+        HIPK_CHECK_HIP(hipEventRecord(whole.a, stream));
+        HIPK_TRY(residual(r, part_rr, false));
+        HIPK_TRY(hipk_launch_dot_parts(n, b, b, A->dtype, part_bb, stream));
+        HIPK_CHECK_HIP(pace.create());   // zeroes the pinned signal word: before the kernel that may write it is enqueued
+        const hipk_tol_sq tol(prm);
+        hipk_bi_start_kernel<T><<<gm.g, HIPK_THREADS, 0, stream>>>(n, gm.ch, gm.g, scal, part_rr, part_bb, part_rhr, r, rhat, p, q, tol.tol2,
+                                                                    tol.atol_sq, maxiter, pace.device_sig());
+        HIPK_CHECK_HIP(hipGetLastError());
+        return HIPK_OK;
+    }
 
-    // which paths this solve takes (hipk_bi_path above); the latches: a one-launch loop once handed a solve back in this process
-    static bool mid_failed = false, lds_loop_failed = false;
-    hipk_bi_path path = hipk_bi_path_begin<T, PRE>(A, prm, ext, maxiter, mid_failed, stream);
-    const bool small = path.small;
-    const int nt = (int)((n + HIPK_TILE - 1) / HIPK_TILE);
-    const double *tsum0 = A->tile_part, *tsum1 = A->tile_part + 4 * (size_t)nt;
-    sq.skip_combine = stt.skip_combine = small ? 1 : 0;
-
-    int64_t it = 0, stop = INT64_MAX;
-    // the whole loop in one launch, one workgroup per chunk (hipk_bi_mid.h)
-    const hipk_mid_entry<hipk_bi_mid_args> *mid = path.mid_entry;
-    bool mid_loop = path.mid;
-    if (mid_loop) {
-        const hipk_mid_plan &plan = path.mid_plan;
+    // the whole loop in one launch, one workgroup per chunk (hipk_bi_mid.h), from iteration `it` -- HIPK_OK, HIPK_HANDED_BACK or
+    // an error (hipk_resident_run); failed: the caller's latch
+    int mid_loop(bool &failed) {
+        const hipk_mid_entry<hipk_bi_mid_args> *mid = path.mid_entry;
         const size_t lds = path.mid_lds;
         hipk_bi_mid_args ca;
         ca.n = n;
         ca.g = gm.g;
-        ca.win = plan.max_slots * HIPK_TILE;
-        ca.plan = plan;
+        ca.win = path.mid_plan.max_slots * HIPK_TILE;
+        ca.plan = path.mid_plan;
         ca.crow = A->crow;
         ca.col = A->col;
-        const size_t ll_bytes = hipk_align_up((size_t)n * 16, 256);
         ca.val = A->val;
         ca.x = x;
         ca.r = r;
@@ -852,9 +895,9 @@ static int hipk_bicgstab_solve_t(hipk_csr_s *A, const T *dinv, const T *b, T *x,
         ca.q = q;
         ca.rhat = rhat;
         ca.dinv = dinv;
-        ca.q_ll = (unsigned long long *)(vbase + 8 * vec);      // behind the eight vectors (hipk_bicgstab_work_bytes)
-        ca.r_ll = (unsigned long long *)(vbase + 8 * vec + ll_bytes);
-        ca.slots = (unsigned long long *)(vbase + 8 * vec + 2 * ll_bytes);
+        ca.q_ll = hipk_at<unsigned long long>(work, lay.q_ll);
+        ca.r_ll = hipk_at<unsigned long long>(work, lay.r_ll);
+        ca.slots = hipk_at<unsigned long long>(work, lay.slots);
         ca.part_rr = part_rr;
         ca.part_rhr = part_rhr;
         ca.scal = scal;
@@ -865,23 +908,18 @@ static int hipk_bicgstab_solve_t(hipk_csr_s *A, const T *dinv, const T *b, T *x,
         auto launch = [&](int64_t it0, int test_not_resident, bool) -> int {
             ca.it0 = it0;
             ca.test_not_resident = test_not_resident;
-            HIPK_CHECK_HIP(hipMemsetAsync(ca.q_ll, 0, 2 * ll_bytes, stream));
+            HIPK_CHECK_HIP(hipMemsetAsync(ca.q_ll, 0, 2 * lay.ll_bytes, stream));   // q_ll and r_ll
             HIPK_CHECK_HIP(hipMemsetAsync(ca.slots, 0, kBiMidSlotBytes, stream));
             HIPK_CHECK_HIP(hipMemsetAsync(&scal->it_done, 0, sizeof(hipk_bi_scal) - offsetof(hipk_bi_scal, it_done), stream));
             mid->kern<<<hipk_xcd_grid(gm.g), 1024, lds, stream>>>(ca);
             return HIPK_OK;
         };
-        const int run = hipk_resident_run(stream, scal, launch, hipk_bi_loop_state, it, maxiter, nullptr, mid_failed, handed, mid->name,
-                                          "hipk_bicgstab_solve");
-        if (run < 0) return run;
-        mid_loop = run == HIPK_OK;
+        return hipk_resident_run(stream, scal, launch, hipk_bi_loop_state, it, maxiter, nullptr, failed, handed, mid->name, "hipk_bicgstab_solve");
     }
-    // the whole loop in one launch, eight workgroups per chunk (hipk_bi_solve_lds_kernel)
-    hipk_bi_path_lds(path, A, prm, ext, maxiter, mid_loop, it, lds_loop_failed);
-    const bool lds_spread = path.spread;
-    bool lds_loop = path.lds_loop;
-    const char *lds_form = "";
-    if (lds_loop) {
+
+    // the whole loop in one launch, eight workgroups per chunk (hipk_bi_solve_lds_kernel), from iteration `it` -- as mid_loop;
+    // *form: the instantiation of its last launch (hipk_last_solve_form)
+    int lds_loop(bool &failed, const char **form) {
         bool local = path.local;   // a -2 (spread over several XCDs): agent-scope hand-offs
         hipk_bi_lds_args<T> ca;
         ca.n = n;
@@ -899,15 +937,15 @@ static int hipk_bicgstab_solve_t(hipk_csr_s *A, const T *dinv, const T *b, T *x,
         ca.scal = scal;
         ca.tsum0 = A->tile_part;
         ca.tsum1 = A->tile_part + 4 * (size_t)nt;
-        ca.tsum2 = part_ts;   // (the launch sequence's chunk-partial slots of <t,s>, <t,t> are free here)
+        ca.tsum2 = hipk_at<double>(work, lay.lds_tsum2);
         ca.part_rr = part_rr;
         ca.part_rhr = part_rhr;
         ca.part_ss = part_ss;
-        ca.flag_a = (unsigned long long *)part_tt;   // 3 x 512 words
+        ca.flag_a = hipk_at<unsigned long long>(work, lay.lds_flags);
         ca.flag_b = ca.flag_a + kHoMaxWg;
         ca.flag_c = ca.flag_a + 2 * kHoMaxWg;
-        ca.spread = lds_spread ? 1 : 0;
-        const int lgrid = lds_spread ? kGmSub * gm.g : 8 * kGmSub * gm.g;
+        ca.spread = path.spread ? 1 : 0;
+        const int lgrid = path.spread ? kGmSub * gm.g : 8 * kGmSub * gm.g;
         ca.maxiter = maxiter;
         ca.max_its = path.max_its;
         auto launch = [&](int64_t it0, int test_not_resident, bool loc) -> int {
@@ -918,154 +956,162 @@ static int hipk_bicgstab_solve_t(hipk_csr_s *A, const T *dinv, const T *b, T *x,
             (loc ? hipk_bi_solve_lds_kernel<T, true, PRE> : hipk_bi_solve_lds_kernel<T, false, PRE>)<<<lgrid, HIPK_THREADS, 0, stream>>>(ca);
             return HIPK_OK;
         };
-        // a hand-back (not co-resident; this launch modified nothing): the launch sequence below takes over
-        const int run = hipk_resident_run(stream, scal, launch, hipk_bi_loop_state, it, maxiter, &local, lds_loop_failed, handed,
-                                          "hipk_bi_solve_lds_kernel", "hipk_bicgstab_solve");
-        if (run < 0) return run;
+        // a hand-back (not co-resident; this launch modified nothing): the launch sequence takes over
+        const int run = hipk_resident_run(stream, scal, launch, hipk_bi_loop_state, it, maxiter, &local, failed, handed, "hipk_bi_solve_lds_kernel",
+                                          "hipk_bicgstab_solve");
         if (run == HIPK_HANDED_BACK && it > 0) {
             // ... from iteration `it` of an EARLIER launch: the vectors and scalars are in memory, but part_rr / part_rhr hold
             // that launch's 8 g SUB-partials, not the g chunk partials the direction kernel folds.  Recompute them from r
             // and rhat (the spec's plain dot: the bits the x-update kernel of the launch sequence would have left)
-            if ((rc = hipk_launch_dot_parts(n, r, r, A->dtype, part_rr, stream)) != HIPK_OK) return rc;
-            if ((rc = hipk_launch_dot_parts(n, rhat, r, A->dtype, part_rhr, stream)) != HIPK_OK) return rc;
+            HIPK_TRY(hipk_launch_dot_parts(n, r, r, A->dtype, part_rr, stream));
+            HIPK_TRY(hipk_launch_dot_parts(n, rhat, r, A->dtype, part_rhr, stream));
         }
-        lds_loop = run == HIPK_OK;
-        // the instantiation of the last launch (hipk_last_solve_form)
-        lds_form = local ? (PRE ? HIPK_FORM_OF_T(T, "hipk_bi_solve_lds_kernel<", "true,true>") : HIPK_FORM_OF_T(T, "hipk_bi_solve_lds_kernel<", "true,false>"))
-                         : (PRE ? HIPK_FORM_OF_T(T, "hipk_bi_solve_lds_kernel<", "false,true>") : HIPK_FORM_OF_T(T, "hipk_bi_solve_lds_kernel<", "false,false>"));
+        *form = local ? (PRE ? HIPK_FORM_OF_T(T, "hipk_bi_solve_lds_kernel<", "true,true>") : HIPK_FORM_OF_T(T, "hipk_bi_solve_lds_kernel<", "true,false>"))
+                      : (PRE ? HIPK_FORM_OF_T(T, "hipk_bi_solve_lds_kernel<", "false,true>") : HIPK_FORM_OF_T(T, "hipk_bi_solve_lds_kernel<", "false,false>"));
+        return run;
     }
-    hipk_set_solve_path(handed, mid_loop ? mid->name : lds_loop ? "hipk_bi_solve_lds_kernel" : "launch sequence");
-    hipk_set_solve_form(mid_loop ? mid->name
-                        : lds_loop ? lds_form
-                        : small ? (ext ? HIPK_FORM("bicgstab five-launch, small, callback M") : PRE ? HIPK_FORM("bicgstab five-launch, small, Jacobi") : HIPK_FORM("bicgstab five-launch, small"))
-                                : (ext ? HIPK_FORM("bicgstab five-launch, callback M") : PRE ? HIPK_FORM("bicgstab five-launch, Jacobi") : HIPK_FORM("bicgstab five-launch")));
-    if (mid_loop) lds_loop = true;   // finished in the one-launch loop
-    for (; !lds_loop && it < maxiter; ++it) {
-        HIPK_CHECK_HIP(pace.gate(it, stream, &stop));
-        if (stop <= it) break;
-        {
-            hipk_bi_direction_kernel<T, PRE><<<gm.g, HIPK_THREADS, 0, stream>>>(n, gm.ch, gm.g, scal, it, part_rr,
-                                                                                 part_rhr, r, q, p, dinv, phat);
-            if (ext && cb(user, p, phat) != 0) {
-                hipk_set_error("hipk_pbicgstab_solve_cb: the preconditioner callback failed");
-                return HIPK_ERR_ARG;
-            }
+
+    const char *five_launch_form() const {
+        return path.small ? (ext ? HIPK_FORM("bicgstab five-launch, small, callback M") : PRE ? HIPK_FORM("bicgstab five-launch, small, Jacobi") : HIPK_FORM("bicgstab five-launch, small"))
+                          : (ext ? HIPK_FORM("bicgstab five-launch, callback M") : PRE ? HIPK_FORM("bicgstab five-launch, Jacobi") : HIPK_FORM("bicgstab five-launch"));
+    }
+
+    // The one-launch section: the mid loop, else the LDS loop, from iteration `it`; `done` when one of them finished the solve, else
+    // the five-launch sequence goes on from `it`.  Records the path and the form the solve reports.  The latches: a one-launch loop
+    // once handed a solve back in this process
+    int one_launch(bool &mid_failed, bool &lds_failed) {
+        path = hipk_bi_path_begin<T, PRE>(A, prm, ext, maxiter, mid_failed, stream);
+        bool mid_done = false, lds_done = false;
+        const char *lds_form = "";
+        if (path.mid) {
+            const int run = mid_loop(mid_failed);
+            if (run < 0) return run;
+            mid_done = run == HIPK_OK;
+        }
+        hipk_bi_path_lds(path, A, prm, ext, maxiter, mid_done, it, lds_failed);
+        if (path.lds_loop) {
+            const int run = lds_loop(lds_failed, &lds_form);
+            if (run < 0) return run;
+            lds_done = run == HIPK_OK;
+        }
+        done = mid_done || lds_done;
+        hipk_set_solve_path(handed, mid_done ? path.mid_entry->name : lds_done ? "hipk_bi_solve_lds_kernel" : "launch sequence");
+        hipk_set_solve_form(mid_done ? path.mid_entry->name : lds_done ? lds_form : five_launch_form());
+        return HIPK_OK;
+    }
+
+    // small (<= 8 chunks): the SpMVs skip their combine launch and the consumers fold the tile sums.  x advances with phat / shat
+    // (TSL:942): the PRE form of the x update also when they come from the callback
+    hipk_bi_kernels<T, PRE> pick() const {
+        const bool xpre = PRE || ext;
+        const double *tsum0 = A->tile_part, *tsum1 = A->tile_part + 4 * (size_t)nt;
+        if (path.small)
+            return {hipk_bi_supdate_kernel<T, PRE, true>, xpre ? hipk_bi_xupdate_kernel<T, true, true> : hipk_bi_xupdate_kernel<T, false, true>, tsum0,
+                    tsum0, tsum1, nt};
+        return {hipk_bi_supdate_kernel<T, PRE, false>, xpre ? hipk_bi_xupdate_kernel<T, true, false> : hipk_bi_xupdate_kernel<T, false, false>, part_rq,
+                part_ts, part_tt, 0};
+    }
+
+    // direction, SpMV q = A phat, s update, SpMV t = A shat, x update per iteration: the host enqueues iterations a few ahead of the
+    // GPU and stops when the x update reports the stop (hipk_pacer); launches past the stop are no-ops on the device
+    int five_launch_sequence() {
+        const hipk_bi_kernels<T, PRE> k = pick();
+        hipk_spmv_args sq = hipk_spmv_base(A), stt = sq;
+        sq.x = phat;
+        sq.y = q;
+        sq.mode = HIPK_SPMV_DOT_W;
+        sq.w = rhat;
+        sq.part0 = part_rq;
+        sq.part1 = part_spare;
+        stt.x = shat;
+        stt.y = t;
+        stt.mode = HIPK_SPMV_DOT_W | HIPK_SPMV_DOT_YY;
+        stt.w = s;
+        stt.part0 = part_ts;
+        stt.part1 = part_tt;
+        sq.stop_it = stt.stop_it = &scal->stop_it;
+        sq.skip_combine = stt.skip_combine = path.small ? 1 : 0;
+        for (; it < maxiter; ++it) {
+            HIPK_CHECK_HIP(pace.gate(it, stream, &stop));
+            if (stop <= it) break;
+            hipk_bi_direction_kernel<T, PRE><<<gm.g, HIPK_THREADS, 0, stream>>>(n, gm.ch, gm.g, scal, it, part_rr, part_rhr, r, q, p, dinv, phat);
+            if (ext) HIPK_TRY(precondition(p, phat));
             sq.it = it;
-            if ((rc = hipk_launch_spmv(A, sq, stream, &prof)) != HIPK_OK) return rc;
-            if (small)
-                hipk_bi_supdate_kernel<T, PRE, true><<<gm.g, HIPK_THREADS, 0, stream>>>(n, gm.ch, gm.g, scal, it, part_rhr, tsum0, r,
-                                                                                        q, s, part_ss, dinv, shat, nt);
-            else
-                hipk_bi_supdate_kernel<T, PRE, false><<<gm.g, HIPK_THREADS, 0, stream>>>(n, gm.ch, gm.g, scal, it, part_rhr, part_rq,
-                                                                                         r, q, s, part_ss, dinv, shat, 0);
-            if (ext && cb(user, s, shat) != 0) {
-                hipk_set_error("hipk_pbicgstab_solve_cb: the preconditioner callback failed");
-                return HIPK_ERR_ARG;
-            }
+            HIPK_TRY(hipk_launch_spmv(A, sq, stream, &prof));
+            k.supdate<<<gm.g, HIPK_THREADS, 0, stream>>>(n, gm.ch, gm.g, scal, it, part_rhr, k.rq, r, q, s, part_ss, dinv, shat, k.nt);
+            if (ext) HIPK_TRY(precondition(s, shat));
             stt.it = it;
-            if ((rc = hipk_launch_spmv(A, stt, stream)) != HIPK_OK) return rc;
-            // x advances with phat / shat (TSL:942): the PRE form of the kernel also when they come from the callback
-            if (small && (PRE || ext))
-                hipk_bi_xupdate_kernel<T, true, true><<<gm.g, HIPK_THREADS, 0, stream>>>(
-                    n, gm.ch, gm.g, scal, it, maxiter, part_ss, tsum0, tsum1, phat, s, t, rhat, x, r, part_rr, part_rhr, shat, nt);
-            else if (small)
-                hipk_bi_xupdate_kernel<T, false, true><<<gm.g, HIPK_THREADS, 0, stream>>>(
-                    n, gm.ch, gm.g, scal, it, maxiter, part_ss, tsum0, tsum1, phat, s, t, rhat, x, r, part_rr, part_rhr, shat, nt);
-            else if (PRE || ext)
-                hipk_bi_xupdate_kernel<T, true, false><<<gm.g, HIPK_THREADS, 0, stream>>>(
-                    n, gm.ch, gm.g, scal, it, maxiter, part_ss, part_ts, part_tt, phat, s, t, rhat, x, r, part_rr, part_rhr, shat, 0);
-            else
-                hipk_bi_xupdate_kernel<T, false, false><<<gm.g, HIPK_THREADS, 0, stream>>>(
-                    n, gm.ch, gm.g, scal, it, maxiter, part_ss, part_ts, part_tt, phat, s, t, rhat, x, r, part_rr, part_rhr, shat, 0);
+            HIPK_TRY(hipk_launch_spmv(A, stt, stream));
+            k.xupdate<<<gm.g, HIPK_THREADS, 0, stream>>>(n, gm.ch, gm.g, scal, it, maxiter, part_ss, k.ts, k.tt, phat, s, t, rhat, x, r, part_rr, part_rhr,
+                                                         shat, k.nt);
+            if ((it & 31) == 31) HIPK_CHECK_HIP(hipGetLastError());
         }
-        if ((it & 31) == 31) HIPK_CHECK_HIP(hipGetLastError());
+        return HIPK_OK;
     }
-    HIPK_CHECK_HIP(hipGetLastError());
 
-    // TSL:1007-1014 (PRE: ||M (b - A x)||, the row scaling runs in the SpMV epilogue)
-    sa.x = x;
-    sa.y = t;
-    sa.mode = HIPK_SPMV_RESID | HIPK_SPMV_DOT_YY | (PRE ? HIPK_SPMV_SCALE : 0);
-    sa.dscale = dinv;
-    sa.bsub = b;
-    sa.part0 = part_spare;
-    sa.part1 = part_ss;
-    sa.stop_it = nullptr;
-    if ((rc = hipk_launch_spmv(A, sa, stream)) != HIPK_OK) return rc;
-    if (ext) {  // ||M (b - A x)||^2 of the caller's M
-        if (cb(user, t, phat) != 0) {
-            hipk_set_error("hipk_pbicgstab_solve_cb: the preconditioner callback failed");
-            return HIPK_ERR_ARG;
+    // TSL:1007-1014: the true residual (PRE: ||M (b - A x)||, the row scaling runs in the SpMV epilogue) and ||x|| decide info
+    int finish(hipk_stats *st) {
+        HIPK_CHECK_HIP(hipGetLastError());
+        HIPK_TRY(residual(t, part_ss, PRE));
+        if (ext) {  // ||M (b - A x)||^2 of the caller's M
+            HIPK_TRY(precondition(t, phat));
+            HIPK_TRY(hipk_launch_dot_parts(n, phat, phat, A->dtype, part_ss, stream));
         }
-        if ((rc = hipk_launch_dot_parts(n, phat, phat, A->dtype, part_ss, stream)) != HIPK_OK) return rc;
-    }
-    if ((rc = hipk_launch_dot_parts(n, x, x, A->dtype, part_bb, stream)) != HIPK_OK) return rc;
-    hipk_bi_final_kernel<<<1, HIPK_THREADS, 0, stream>>>(scal, gm.g, part_ss, part_bb);
-    HIPK_CHECK_HIP(hipGetLastError());
-    hipk_bi_scal hs;
-    HIPK_CHECK_HIP(hipEventRecord(whole.b, stream));
-    HIPK_CHECK_HIP(hipMemcpyAsync(&hs, scal, sizeof(hs), hipMemcpyDeviceToHost, stream));
-    HIPK_CHECK_HIP(hipStreamSynchronize(stream));
+        HIPK_TRY(hipk_launch_dot_parts(n, x, x, A->dtype, part_bb, stream));
+        hipk_bi_final_kernel<<<1, HIPK_THREADS, 0, stream>>>(scal, gm.g, part_ss, part_bb);
+        HIPK_CHECK_HIP(hipGetLastError());
+        hipk_bi_scal hs;
+        HIPK_CHECK_HIP(hipEventRecord(whole.b, stream));
+        HIPK_CHECK_HIP(hipMemcpyAsync(&hs, scal, sizeof(hs), hipMemcpyDeviceToHost, stream));
+        HIPK_CHECK_HIP(hipStreamSynchronize(stream));
 
-    hipk_finish_isolve_stats(st, prm, hs.bs, hs.res2, hs.xx, hs.iters, 1 + 2 * hs.iters + hs.extra_mv + 1);
-    st->recurrence_rs = hs.rs_last;
-    st->breakdown = hs.code;
-    float ms = 0.f;
-    HIPK_CHECK_HIP(hipEventElapsedTime(&ms, whole.a, whole.b));
-    st->solve_ms = ms;
-    HIPK_CHECK_HIP(prof.collect(st, hs.iters));
-    return HIPK_OK;
+        hipk_finish_isolve_stats(st, prm, hs.bs, hs.res2, hs.xx, hs.iters, 1 + 2 * hs.iters + hs.extra_mv + 1);
+        st->recurrence_rs = hs.rs_last;
+        st->breakdown = hs.code;
+        float ms = 0.f;
+        HIPK_CHECK_HIP(hipEventElapsedTime(&ms, whole.a, whole.b));
+        st->solve_ms = ms;
+        HIPK_CHECK_HIP(prof.collect(st, hs.iters));
+        return HIPK_OK;
+    }
+};
+
+template <typename T, bool PRE>
+static int hipk_bicgstab_solve_t(hipk_csr_s *A, const T *dinv, const T *b, T *x, char *work, const hipk_params *prm, hipk_stats *st,
+                                 hipStream_t stream, hipk_precond_fn cb, void *user) {
+    static bool mid_failed = false, lds_loop_failed = false;   // per dtype and PRE; the callback entry shares those of the plain one
+    hipk_bi_steps<T, PRE> s(A, dinv, b, x, work, prm, stream, cb, user);
+    HIPK_TRY(s.start());
+    HIPK_TRY(s.one_launch(mid_failed, lds_loop_failed));
+    if (!s.done) HIPK_TRY(s.five_launch_sequence());
+    return s.finish(st);
+}
+
+// the checks and the dispatch on the operand's dtype the three entries share (have_m: the entry's dinv or M is not null)
+static int hipk_bicgstab_entry(hipk_csr_t A, bool have_m, const void *dinv, hipk_precond_fn M, void *user, const void *b, void *x, void *work,
+                               size_t work_bytes, const hipk_params *prm, hipk_stats *st, hipk_stream_t stream) {
+    HIPK_TRY(hipk_solve_check(A, have_m, dinv, b, x, work, work_bytes, (dinv || M) ? hipk_pbicgstab_work_bytes : hipk_bicgstab_work_bytes, prm, st));
+    hipStream_t s = (hipStream_t)stream;
+    if (dinv)
+        return A->dtype == HIPK_F64 ? hipk_bicgstab_solve_t<double, true>(A, (const double *)dinv, (const double *)b, (double *)x, (char *)work, prm, st, s, nullptr, nullptr)
+                                    : hipk_bicgstab_solve_t<float, true>(A, (const float *)dinv, (const float *)b, (float *)x, (char *)work, prm, st, s, nullptr, nullptr);
+    return A->dtype == HIPK_F64 ? hipk_bicgstab_solve_t<double, false>(A, nullptr, (const double *)b, (double *)x, (char *)work, prm, st, s, M, user)
+                                : hipk_bicgstab_solve_t<float, false>(A, nullptr, (const float *)b, (float *)x, (char *)work, prm, st, s, M, user);
 }
 
 extern "C" int hipk_bicgstab_solve(hipk_csr_t A, const void *b, void *x, void *work, size_t work_bytes,
                                    const hipk_params *prm, hipk_stats *st, hipk_stream_t stream) {
-    HIPK_REQUIRE(A && b && x && work && prm && st, HIPK_ERR_ARG, "null argument");
-    HIPK_REQUIRE(A->n_rows == A->n_cols, HIPK_ERR_ARG, "linear operator must be a square matrix");
-    HIPK_REQUIRE(A->n_rows > 0, HIPK_ERR_ARG, "empty system");
-    HIPK_REQUIRE(hipk_aligned16(b) && hipk_aligned16(x) && (((uintptr_t)work) & 255u) == 0, HIPK_ERR_ALIGN,
-                 "b/x must be 16-byte and work 256-byte aligned");
-    HIPK_REQUIRE(work_bytes >= hipk_bicgstab_work_bytes(A->n_rows, A->dtype), HIPK_ERR_WORKSPACE, "work too small");
-    HIPK_REQUIRE(b != x, HIPK_ERR_ARG, "b and x must not alias");
-    memset(st, 0, sizeof(*st));
-    if (A->dtype == HIPK_F64)
-        return hipk_bicgstab_solve_t<double, false>(A, nullptr, (const double *)b, (double *)x, (char *)work, prm, st,
-                                                    (hipStream_t)stream);
-    return hipk_bicgstab_solve_t<float, false>(A, nullptr, (const float *)b, (float *)x, (char *)work, prm, st,
-                                               (hipStream_t)stream);
+    return hipk_bicgstab_entry(A, true, nullptr, nullptr, nullptr, b, x, work, work_bytes, prm, st, stream);
 }
 
 extern "C" int hipk_pbicgstab_solve(hipk_csr_t A, const void *dinv, const void *b, void *x, void *work, size_t work_bytes,
                                     const hipk_params *prm, hipk_stats *st, hipk_stream_t stream) {
-    HIPK_REQUIRE(A && dinv && b && x && work && prm && st, HIPK_ERR_ARG, "null argument");
-    HIPK_REQUIRE(A->n_rows == A->n_cols, HIPK_ERR_ARG, "linear operator must be a square matrix");
-    HIPK_REQUIRE(A->n_rows > 0, HIPK_ERR_ARG, "empty system");
-    HIPK_REQUIRE(hipk_aligned16(b) && hipk_aligned16(x) && hipk_aligned16(dinv) && (((uintptr_t)work) & 255u) == 0,
-                 HIPK_ERR_ALIGN, "b/x/dinv must be 16-byte and work 256-byte aligned");
-    HIPK_REQUIRE(work_bytes >= hipk_pbicgstab_work_bytes(A->n_rows, A->dtype), HIPK_ERR_WORKSPACE, "work too small");
-    HIPK_REQUIRE(b != x, HIPK_ERR_ARG, "b and x must not alias");
-    memset(st, 0, sizeof(*st));
-    if (A->dtype == HIPK_F64)
-        return hipk_bicgstab_solve_t<double, true>(A, (const double *)dinv, (const double *)b, (double *)x, (char *)work, prm,
-                                                   st, (hipStream_t)stream);
-    return hipk_bicgstab_solve_t<float, true>(A, (const float *)dinv, (const float *)b, (float *)x, (char *)work, prm, st,
-                                              (hipStream_t)stream);
+    return hipk_bicgstab_entry(A, dinv != nullptr, dinv, nullptr, nullptr, b, x, work, work_bytes, prm, st, stream);
 }
 
 extern "C" int hipk_pbicgstab_solve_cb(hipk_csr_t A, hipk_precond_fn M, void *user, const void *b, void *x, void *work,
                                        size_t work_bytes, const hipk_params *prm, hipk_stats *st, hipk_stream_t stream) {
-    HIPK_REQUIRE(A && M && b && x && work && prm && st, HIPK_ERR_ARG, "null argument");
-    HIPK_REQUIRE(A->n_rows == A->n_cols, HIPK_ERR_ARG, "linear operator must be a square matrix");
-    HIPK_REQUIRE(A->n_rows > 0, HIPK_ERR_ARG, "empty system");
-    HIPK_REQUIRE(hipk_aligned16(b) && hipk_aligned16(x) && (((uintptr_t)work) & 255u) == 0, HIPK_ERR_ALIGN,
-                 "b/x must be 16-byte and work 256-byte aligned");
-    HIPK_REQUIRE(work_bytes >= hipk_pbicgstab_work_bytes(A->n_rows, A->dtype), HIPK_ERR_WORKSPACE, "work too small");
-    HIPK_REQUIRE(b != x, HIPK_ERR_ARG, "b and x must not alias");
-    memset(st, 0, sizeof(*st));
-    if (A->dtype == HIPK_F64)
-        return hipk_bicgstab_solve_t<double, false>(A, nullptr, (const double *)b, (double *)x, (char *)work, prm, st,
-                                                    (hipStream_t)stream, M, user);
-    return hipk_bicgstab_solve_t<float, false>(A, nullptr, (const float *)b, (float *)x, (char *)work, prm, st,
-                                               (hipStream_t)stream, M, user);
+    return hipk_bicgstab_entry(A, M != nullptr, nullptr, M, user, b, x, work, work_bytes, prm, st, stream);
 }
 
 
@@ -1149,9 +1195,8 @@ static int hipk_dist_bicgstab_t(hipk_csr_t A, const hipk_dist_plan *pl, const hi
     const int64_t n = pl->n_local, n_ext = pl->n_ext;
     const int ch = pl->chunk_rows, G = pl->g_red, per = pl->per, W = pl->world;
     const int grid = (int)((n + ch - 1) / ch);
-    const int64_t maxiter = (prm->maxiter < 0) ? 10 * pl->n_global : prm->maxiter;   // TSL:982-984
-    const float tolf = (float)prm->tol, atolf = (float)prm->atol;
-    const double tol2 = (double)(tolf * tolf), atol_sq = (double)(atolf * atolf);
+    const int64_t maxiter = hipk_default_maxiter(prm, pl->n_global);
+    const hipk_tol_sq tol(prm);
     const int64_t *stop_dev = &scal->stop_it;
     // grouped(): each exchange of the loop is one group at world > 1, whatever it carries
     const hipk_dist_xchg xc(pl, cc, stream, (double *)(wk + L.send_buf), (double *)(wk + L.slab_loc), (double *)(wk + L.slab_all),
@@ -1171,7 +1216,7 @@ static int hipk_dist_bicgstab_t(hipk_csr_t A, const hipk_dist_plan *pl, const hi
     HIPK_TRY(hipk_dot_parts(n, ch, b, b, HIPK_F64, part_a, stream));
     HIPK_TRY(xc.parts(part_a, g_bb));
     HIPK_CHECK_HIP(hipMemcpyAsync(g_rhr, g_rr, (size_t)W * per * 8, hipMemcpyDeviceToDevice, stream));
-    hipk_bi_start_kernel<T><<<grid, HIPK_THREADS, 0, stream>>>(n, ch, G, scal, g_rr, g_bb, spare, r, rhat, p, q, tol2, atol_sq, maxiter,
+    hipk_bi_start_kernel<T><<<grid, HIPK_THREADS, 0, stream>>>(n, ch, G, scal, g_rr, g_bb, spare, r, rhat, p, q, tol.tol2, tol.atol_sq, maxiter,
                                                                 nullptr);
     HIPK_CHECK_HIP(hipGetLastError());
 

@@ -1138,21 +1138,6 @@ static constexpr int kCg2MaxChunks = 150;
 // x, r, p, Ap beyond 1.5 x the 256 MiB Infinity Cache: the vector kernels treat every operand as a stream
 static inline bool hipk_cg_streams_by_size(size_t n, size_t sv) { return 4 * n * sv > (size_t)384 << 20; }
 
-extern "C" size_t hipk_cg_work_bytes(int64_t n, int dtype) {
-    const size_t sv = (dtype == HIPK_F64) ? 8 : 4;
-    const size_t vec = hipk_align_up((size_t)(n > 0 ? n : 1) * sv, 256);
-    // r, p, Ap; mid-size systems (two launches per iteration) a second p: the direction step is formed while the old p is gathered
-    const hipk_geom gm = hipk_make_geom(n > 0 ? n : 1);
-    // (the one-launch mid-size loop, hipk_cg_mid.h, keeps r as 16-byte flagged words in Ap + that fourth vector)
-    const bool mid = gm.g > kMidMinChunks && gm.g <= kMidMaxChunks;   // + the chunk-partial slots of that loop, a line each
-    // (r travels as 16-byte flagged words whatever the dtype: 16 n bytes from Ap on -- one more fp64 vector, three more fp32 ones)
-    const size_t ll = hipk_align_up((size_t)(n > 0 ? n : 1) * 16, 256);
-    // beyond the mid loop, up to the size at which the streaming policy takes over (hipk_cg_path_begin): the second p of the
-    // deferred x update (hipk_cg_path_defer); the sizes of the streaming policy keep three vectors
-    const bool second_p = !mid && gm.g > kMidMaxChunks && !hipk_cg_streams_by_size((size_t)n, sv);
-    return 256 + hipk_scratch_bytes() + 3 * vec + (mid ? (ll - vec) + kMidSlotBytes : second_p ? vec : 0);
-}
-
 // the one-launch instantiations the dispatch sites below select (hipk_mid_pick), each with the name hipk_last_solve_path reports.
 // Two chunks per workgroup put four rows on a thread: at most 7 entries each in registers
 #define HIPK_MID_ROW(W, NCH, PRE)                                                                                          \
@@ -1166,6 +1151,81 @@ static const hipk_mid_entry<hipk_cg_mid_args> hipk_cg_mid_table[] = {
 #undef HIPK_MID_ROW
 static constexpr int kPcgMidMaxChunks = 256;                                 // one chunk per workgroup, one workgroup per CU
 static constexpr size_t kPcgMidSlotBytes = 3 * (size_t)kMidMaxChunks * 256;   // <p,Ap>, <r,r>, <r,z> slot arrays
+
+// ---------------------------------------------------------------- the workspace of a cg or Jacobi pcg solve
+// Byte offsets, from (n, dtype, pre) alone: hipk_cg_work_bytes and hipk_pcg_work_bytes return .total, the solve takes its pointers
+// from the rest.  scalars (hipk_cg_scal / hipk_pcg_scal) | partial slots (cg: the four of hipk_scratch_bytes, pcg: six) | r, p, Ap |
+// what the size allows behind Ap.  The loop forms of a solve -- the mid loop, the LDS loop, one launch sequence -- run one after
+// the other: a one-launch loop has returned (finished, or handed the solve back) before the next form's first launch is
+// enqueued, and none runs twice.  A region of one form may therefore lie in bytes that another form owns.
+struct hipk_cg_layout {
+    size_t scal;
+    size_t part_a, part_b, part_c;   // <p,Ap> | <r,r> | spare dot slot of the SpMV
+    size_t part_z[2];                // pcg: <r,z> ping-pong (read by all workgroups of the update kernel while the early ones already
+                                     // write the next one)
+    size_t part_d;                   // <b,b> / <x,x>: pcg a slot of its own, cg part_a
+    size_t r, p, Ap;
+    // The LDS loop (hipk_cg_solve_lds_kernel) in slots of the launch sequences, which only write them once they run (pcg:
+    // part_z[1] is first written by the update kernel of iteration 0; hipk_cg_steps<T, true>::one_launch rebuilds the slot the
+    // sequence reads after a hand-back):
+    size_t lds_flags;    // 2 x kHoMaxWg hand-off words, the upper half of the spare slot
+    size_t lds_rr_sub;   // sub-partials of <r,r>, in its chunk-partial slot (part_b, which holds those of <r0,r0> at iteration 0)
+    size_t lds_rz_sub;   // pcg: sub-partials of <r,z>, in part_z[1]
+    // The mid loop (hipk_cg_mid_kernel), present iff mid.  It keeps r as 16-byte flagged words whatever the dtype -- one more
+    // fp64 vector, three more fp32 ones -- from Ap on: at these sizes the place of Ap is ll_bytes long and Ap is its head.
+    bool mid;
+    size_t ll_bytes;
+    size_t r_ll;                   // = Ap
+    size_t pap_ll, rr_ll, rz_ll;   // the chunk-partial slots of <p,Ap>, <r,r> and (pcg) <r,z>, kMidSlotArray bytes each
+    // A second direction vector behind Ap: the two-launch form gathers the old p while it forms the new one, the deferred-x form
+    // keeps p_j by parity.  At the mid sizes it lies in the mid loop's bytes (the tail of r_ll and, where 2 vec = ll_bytes + 256,
+    // the first line of pap_ll); beyond them, up to the size at which the streaming policy takes over, it is a vector of its own.
+    // No room (fourth_vector false) up to kMidMinChunks chunks, at the streaming sizes, and in a pcg solve, which has neither form.
+    bool fourth_vector;
+    size_t p2;
+    size_t total;
+};
+static constexpr size_t kMidSlotArray = (size_t)kMidMaxChunks * 256;   // a slot array of the mid loop at the widest slot stride
+static_assert(kMidSlotBytes == 2 * kMidSlotArray && kPcgMidSlotBytes == 3 * kMidSlotArray, "pap_ll, rr_ll and (pcg) rz_ll");
+static_assert(HIPK_MAX_PARTS / 2 + 2 * kHoMaxWg <= HIPK_MAX_PARTS, "the LDS loop's hand-off flags fit the upper half of the spare slot");
+static_assert(kHoMaxWg <= HIPK_MAX_PARTS, "the LDS loop's sub-partials fit a chunk-partial slot");
+static_assert(kMidSlotBytes >= 256, "p2 ends inside the mid loop's bytes: 2 vec <= ll_bytes + 256");
+static_assert(HIPK_SCRATCH_SLOTS == 4, "cg: part_a, part_b, part_c and one unused slot");
+
+static hipk_cg_layout hipk_cg_make_layout(int64_t n, int dtype, bool pre) {
+    const size_t sv = (dtype == HIPK_F64) ? 8 : 4, rows = (size_t)(n > 0 ? n : 1), vec = hipk_align_up(rows * sv, 256);
+    const size_t slot = HIPK_MAX_PARTS * sizeof(double);
+    const hipk_geom gm = hipk_make_geom(n > 0 ? n : 1);
+    hipk_cg_layout L;
+    hipk_carve take;
+    L.scal = take(256);
+    L.part_a = take(slot);
+    L.part_b = take(slot);
+    L.part_c = take(slot);
+    L.part_z[0] = take(slot);   // (cg: the fourth slot of hipk_scratch_bytes, unused)
+    L.part_z[1] = pre ? take(slot) : 0;
+    L.part_d = pre ? take(slot) : L.part_a;
+    L.lds_flags = L.part_c + slot / 2;
+    L.lds_rr_sub = L.part_b;
+    L.lds_rz_sub = L.part_z[1];
+    L.r = take(vec);
+    L.p = take(vec);
+    L.mid = gm.g > kMidMinChunks && gm.g <= (pre ? kPcgMidMaxChunks : kMidMaxChunks);
+    L.ll_bytes = hipk_align_up(rows * 16, 256);
+    L.Ap = L.r_ll = take(L.mid ? L.ll_bytes : vec);
+    L.pap_ll = L.mid ? take(pre ? kPcgMidSlotBytes : kMidSlotBytes) : 0;
+    L.rr_ll = L.pap_ll + kMidSlotArray;
+    L.rz_ll = L.rr_ll + kMidSlotArray;
+    // beyond the mid loop, up to the size at which the streaming policy takes over (hipk_cg_path_begin): a vector of its own
+    const bool second_p = !pre && !L.mid && gm.g > kMidMaxChunks && !hipk_cg_streams_by_size(rows, sv);
+    L.p2 = L.Ap + vec;
+    if (second_p) take(vec);
+    L.fourth_vector = !pre && (L.mid || second_p);
+    L.total = take.o;
+    return L;
+}
+extern "C" size_t hipk_cg_work_bytes(int64_t n, int dtype) { return hipk_cg_make_layout(n, dtype, false).total; }
+extern "C" size_t hipk_pcg_work_bytes(int64_t n, int dtype) { return hipk_cg_make_layout(n, dtype, true).total; }
 
 // ---- which paths a cg (PRE = false) or Jacobi pcg (PRE = true) solve takes: the only place that knows CG's switches and size
 // limits.  Three steps, because a loop that handed the solve back changes what the next path may do:
@@ -1250,392 +1310,26 @@ static void hipk_cg_path_lds(hipk_cg_path &path, const hipk_csr_s *A, const hipk
 
 // launch-bound mid-size systems of plain CG, 33 .. kCg2MaxChunks chunks: TWO launches per iteration, from iteration 0 only (p_0 = r_0
 // sits where its first pass reads it) and with room for a fourth vector in the workspace.  cap2: the kernel's tile capacity
-static void hipk_cg_path_two(hipk_cg_path &path, const hipk_csr_s *A, const hipk_params *prm, bool done, int64_t it, int cap2, size_t vec) {
+static void hipk_cg_path_two(hipk_cg_path &path, const hipk_csr_s *A, const hipk_params *prm, bool done, int64_t it, int cap2, const hipk_cg_layout &lay) {
     const int g = A->geom.g;
     path.two_launch = !done && !path.small && g > 32 && g <= kCg2MaxChunks && A->geom.ch == HIPK_BASE_CHUNK && A->op_cb == nullptr &&
                       A->crow != nullptr && A->max_tile_nnz <= cap2 && A->max_row_len <= HIPK_LONG_ROW && prm->profile == 0 && it == 0 &&
-                      hipk_sw_enabled("HIPK_CG_TWO_LAUNCH") && hipk_cg_work_bytes(A->n_rows, A->dtype) >= 256 + hipk_scratch_bytes() + 4 * vec;
+                      hipk_sw_enabled("HIPK_CG_TWO_LAUNCH") && lay.fourth_vector;
 }
 
 // the three-launch sequence of plain CG with the x update deferred (hipk_cg_pdir_kernel, hipk_cg_xdir_kernel, hipk_cg_xflush_kernel):
 // the general form only (chunk partials, default cache policy), a matrix operand, no per-kernel profile (a profiled solve times
 // the kernels it names), room for a fourth vector in the workspace (a size of the streaming policy forced to HIPK_CG_STREAMS=0
 // finds none), from any iteration a one-launch loop handed back at.  HIPK_CG_DEFER_X=0: hipk_cg_direction_kernel every iteration
-static void hipk_cg_path_defer(hipk_cg_path &path, const hipk_csr_s *A, const hipk_params *prm, bool done, size_t vec) {
+static void hipk_cg_path_defer(hipk_cg_path &path, const hipk_csr_s *A, const hipk_params *prm, bool done, const hipk_cg_layout &lay) {
     path.defer_x = !done && !path.two_launch && !path.small && !path.streams && A->op_cb == nullptr && prm->profile == 0 &&
-                   hipk_cg_work_bytes(A->n_rows, A->dtype) >= 256 + hipk_scratch_bytes() + 4 * vec && hipk_sw_enabled("HIPK_CG_DEFER_X");
+                   lay.fourth_vector && hipk_sw_enabled("HIPK_CG_DEFER_X");
 }
 
 // {redo, it_done, stop_it} of a host copy of hipk_cg_scal / hipk_pcg_scal (hipk_resident_run)
 template <typename S>
 static hipk_loop_state hipk_cg_loop_state(const S &h) {
     return {h.ctl.redo, h.ctl.it_done, h.stop_it};
-}
-
-// launch-bound mid-size systems: the whole CG loop (PRE: Jacobi PCG, M = diag(dinv)) in one launch, path.mid_entry's kernel on workgroups
-// of path.nch chunks, from iteration `it` -- HIPK_OK, HIPK_HANDED_BACK or an error (hipk_resident_run);
-// r travels as flagged words in Ap + the vector behind it, the chunk-partial slots follow (hipk_cg_work_bytes, hipk_pcg_work_bytes)
-template <typename T, bool PRE, typename S>
-static int hipk_cg_mid_loop(hipk_csr_s *A, S *scal, const hipk_cg_path &path, T *x, T *r, T *p, T *Ap, const T *dinv, const double *rz0_parts,
-                            int64_t &it, int64_t maxiter, bool &failed, char (&handed)[128], const char *entry, hipStream_t stream) {
-    const hipk_mid_entry<hipk_cg_mid_args> *mid = path.mid_entry;
-    const hipk_mid_plan &plan = path.mid_plan;
-    const size_t lds = path.mid_lds;
-    const int g = A->geom.g, grid = (g + mid->nch - 1) / mid->nch;
-    const size_t ll_bytes = hipk_align_up((size_t)A->n_rows * 16, 256);   // r as 16-byte flagged words
-    hipk_cg_mid_args ca;
-    memset(&ca, 0, sizeof(ca));
-    ca.n = A->n_rows;
-    ca.g = g;
-    ca.win = plan.max_slots * HIPK_TILE;
-    ca.plan = plan;
-    ca.crow = A->crow;
-    ca.col = A->col;
-    ca.val = A->val;
-    ca.x = x;
-    ca.r = r;
-    ca.p = p;
-    ca.r_ll = (unsigned long long *)Ap;                          // Ap + the fourth vector: 2 x vec >= 16 n bytes
-    ca.pap_ll = (unsigned long long *)((char *)Ap + ll_bytes);    // behind the flagged words of r
-    ca.rr_ll = ca.pap_ll + (size_t)kMidMaxChunks * 256 / 8;
-    if (PRE) ca.rz_ll = ca.rr_ll + (size_t)kMidMaxChunks * 256 / 8;
-    ca.dinv = dinv;
-    ca.rz0_parts = rz0_parts;
-    ca.slot_stride = path.slot_stride;
-    ca.xcd_aware = path.xcd_aware;
-    ca.ctl = &scal->ctl;
-    ca.gamma = scal->gamma;
-    ca.atol2 = &scal->atol2;
-    ca.stop_it = &scal->stop_it;
-    ca.maxiter = maxiter;
-    ca.max_its = path.max_its;
-    auto launch = [&](int64_t it0, int test_not_resident, bool) -> int {
-        ca.it0 = it0;
-        ca.test_not_resident = test_not_resident;
-        HIPK_CHECK_HIP(hipMemsetAsync(ca.r_ll, 0, ll_bytes, stream));
-        HIPK_CHECK_HIP(hipMemsetAsync(ca.pap_ll, 0, PRE ? kPcgMidSlotBytes : kMidSlotBytes, stream));
-        HIPK_CHECK_HIP(hipMemsetAsync(&scal->ctl, 0, sizeof(hipk_lds_ctl), stream));
-        mid->kern<<<hipk_xcd_grid(grid), 1024, lds, stream>>>(ca);   // hipk_xcd_chunk: padded to a multiple of 8
-        return HIPK_OK;
-    };
-    return hipk_resident_run(stream, scal, launch, hipk_cg_loop_state<S>, it, maxiter, nullptr, failed, handed, mid->name, entry);
-}
-
-// launch-bound systems with short rows: the whole CG loop (PRE: Jacobi PCG, M = diag(dinv)) in one launch, hipk_cg_solve_lds_kernel,
-// from iteration `it` -- HIPK_OK, HIPK_HANDED_BACK or an error (hipk_resident_run).  scal: hipk_cg_scal / hipk_pcg_scal; rr_sub,
-// rz_sub: the kernel's sub-partial scratch; flags: 2 x kHoMaxWg hand-off words; failed: the caller's latch
-template <typename T, bool PRE, typename S>
-static int hipk_cg_lds_loop(hipk_csr_s *A, S *scal, const hipk_cg_path &path, T *x, T *r, T *p, T *Ap, const T *dinv, const double *rz0_parts,
-                            double *rz_sub, double *rr_sub, unsigned long long *flags, int64_t &it, int64_t maxiter, bool &failed,
-                            char (&handed)[128], const char *entry, hipStream_t stream, const char **form) {
-    const bool spread = path.spread;
-    bool local = path.local;   // a -2 (spread over several XCDs): agent-scope hand-offs
-    const int g = A->geom.g, lgrid = spread ? kGmSub * g : 8 * kGmSub * g;
-    hipk_cg_lds_args<T> ca;
-    ca.n = A->n_rows;
-    ca.g = g;
-    ca.crow = A->crow;
-    ca.col = A->col;
-    ca.val = (const T *)A->val;
-    ca.x = x;
-    ca.r = r;
-    ca.p = p;
-    ca.Ap = Ap;
-    ca.ctl = &scal->ctl;
-    ca.gamma = scal->gamma;
-    ca.atol2 = &scal->atol2;
-    ca.stop_it = &scal->stop_it;
-    ca.dinv = dinv;
-    ca.rz0_parts = rz0_parts;
-    ca.rz_sub = rz_sub;
-    ca.tile_pp = A->tile_part;
-    ca.rr_sub = rr_sub;
-    ca.flag_a = flags;
-    ca.flag_b = ca.flag_a + kHoMaxWg;
-    ca.spread = spread ? 1 : 0;
-    ca.maxiter = maxiter;
-    ca.max_its = path.max_its;
-    auto launch = [&](int64_t it0, int test_not_resident, bool loc) -> int {
-        ca.it0 = it0;
-        ca.test_not_resident = test_not_resident;
-        HIPK_CHECK_HIP(hipMemsetAsync(ca.flag_a, 0, 2 * kHoMaxWg * sizeof(unsigned long long), stream));
-        HIPK_CHECK_HIP(hipMemsetAsync(&scal->ctl, 0, sizeof(hipk_lds_ctl), stream));
-        (loc ? hipk_cg_solve_lds_kernel<T, true, PRE> : hipk_cg_solve_lds_kernel<T, false, PRE>)<<<lgrid, HIPK_THREADS, 0, stream>>>(ca);
-        return HIPK_OK;
-    };
-    const int run = hipk_resident_run(stream, scal, launch, hipk_cg_loop_state<S>, it, maxiter, &local, failed, handed,
-                                      "hipk_cg_solve_lds_kernel", entry);
-    // the instantiation of the last launch (hipk_last_solve_form)
-    *form = local ? (PRE ? HIPK_FORM_OF_T(T, "hipk_cg_solve_lds_kernel<", "true,true>") : HIPK_FORM_OF_T(T, "hipk_cg_solve_lds_kernel<", "true,false>"))
-                  : (PRE ? HIPK_FORM_OF_T(T, "hipk_cg_solve_lds_kernel<", "false,true>") : HIPK_FORM_OF_T(T, "hipk_cg_solve_lds_kernel<", "false,false>"));
-    return run;
-}
-
-// The one-launch section of hipk_cg_solve (PRE = false) and hipk_pcg_solve (PRE = true): the mid loop, else the LDS loop, from
-// iteration `it`; *done when one of them finished the solve, else the caller's launch sequence goes on from `it`.  Records
-// the path hipk_last_solve_path reports.  part_z (PRE): the launch sequence's ping-pong chunk partials of <r,z>; part_z[0] holds
-// those of iteration 0, part_z[1] is the LDS loop's sub-partial scratch.  rr_sub, flags: as hipk_cg_lds_loop's
-template <typename T, bool PRE, typename S>
-static int hipk_cg_one_launch(hipk_csr_s *A, S *scal, hipk_cg_path &path, const hipk_params *prm, T *x, T *r, T *p, T *Ap, const T *dinv,
-                              double *const *part_z, double *rr_sub, unsigned long long *flags, int64_t &it, int64_t maxiter,
-                              bool &mid_failed, bool &lds_failed, char (&handed)[128], const char *entry, hipStream_t stream, bool *done) {
-    // a hand-back at it > 0 (from an EARLIER launch of the loop): x, r, p are in memory, but <r,z> only as scal->gamma[it & 1], while
-    // the Jacobi launch sequence folds it from the chunk partials part_z[it & 1].  Rebuild that slot as {gamma, 0, 0, ...}: the
-    // fold of it is gamma, bit for bit.  (Plain CG's launch sequence reads gamma itself.)
-    auto after = [&](int run) -> int {
-        if (PRE && run == HIPK_HANDED_BACK && it > 0) {
-            HIPK_CHECK_HIP(hipMemsetAsync(part_z[it & 1], 0, (size_t)A->geom.g * sizeof(double), stream));
-            HIPK_CHECK_HIP(hipMemcpyAsync(part_z[it & 1], &scal->gamma[it & 1], sizeof(double), hipMemcpyDeviceToDevice, stream));
-        }
-        return HIPK_OK;
-    };
-    int rc;
-    bool mid_done = false, lds_done = false;
-    const char *lds_form = "";
-    if (path.mid) {
-        const int run = hipk_cg_mid_loop<T, PRE>(A, scal, path, x, r, p, Ap, dinv, PRE ? part_z[0] : nullptr, it, maxiter, mid_failed, handed,
-                                                 entry, stream);
-        if (run < 0) return run;
-        if ((rc = after(run)) != HIPK_OK) return rc;
-        mid_done = run == HIPK_OK;
-    }
-    hipk_cg_path_lds(path, A, prm, maxiter, mid_done, lds_failed);
-    if (path.lds_loop) {   // a hand-back (not co-resident; that launch modified nothing): the launch sequence takes over
-        const int run = hipk_cg_lds_loop<T, PRE>(A, scal, path, x, r, p, Ap, dinv, PRE ? part_z[0] : nullptr, PRE ? part_z[1] : nullptr, rr_sub,
-                                                 flags, it, maxiter, lds_failed, handed, entry, stream, &lds_form);
-        if (run < 0) return run;
-        if ((rc = after(run)) != HIPK_OK) return rc;
-        lds_done = run == HIPK_OK;
-    }
-    hipk_set_solve_path(handed, mid_done ? path.mid_entry->name : lds_done ? "hipk_cg_solve_lds_kernel" : "launch sequence");
-    // (neither finished: the caller names its launch sequence)
-    if (mid_done || lds_done) hipk_set_solve_form(mid_done ? path.mid_entry->name : lds_form);
-    *done = mid_done || lds_done;
-    return HIPK_OK;
-}
-
-template <typename T>
-static int hipk_cg_solve_t(hipk_csr_s *A, const T *b, T *x, char *work, const hipk_params *prm, hipk_stats *st,
-                           hipStream_t stream) {
-    const int64_t n = A->n_rows;
-    const hipk_geom gm = A->geom;
-    const size_t vec = hipk_align_up((size_t)(n > 0 ? n : 1) * sizeof(T), 256);
-    hipk_cg_scal *scal = (hipk_cg_scal *)work;
-    double *parts = (double *)(work + 256);
-    double *part_a = parts;                       // <p,Ap> / <b,b> / <x,x>
-    double *part_b = parts + HIPK_MAX_PARTS;      // <r,r>
-    double *part_c = parts + 2 * HIPK_MAX_PARTS;  // spare dot slot of the spmv kernel
-    T *r = (T *)(work + 256 + hipk_scratch_bytes());
-    T *p = (T *)((char *)r + vec);
-    T *Ap = (T *)((char *)p + vec);
-
-    const int64_t maxiter = (prm->maxiter < 0) ? 10 * n : prm->maxiter;  // TSL:982-984
-    hipk_set_solve_path(nullptr, "");
-    char handed[128] = "";   // the one-launch loops that handed this solve back
-    // torch.square(torch.tensor(tol)): python floats become fp32 tensors (TSL:816-817)
-    const float tolf = (float)prm->tol, atolf = (float)prm->atol;
-    const double tol2 = (double)(tolf * tolf), atol_sq = (double)(atolf * atolf);
-    int64_t check = prm->check_every > 0 ? prm->check_every : 64;
-
-    hipk_event_pair whole;
-    HIPK_CHECK_HIP(whole.create());
-    hipk_spmv_profiler prof(prm->profile);   // only launches of the selected kind carry events (hipk_solve.h: chain mode perturbs)
-    HIPK_CHECK_HIP(hipEventRecord(whole.a, stream));
-
-    hipk_spmv_args sa;
-    memset(&sa, 0, sizeof(sa));
-    sa.crow = A->crow;
-    sa.col = A->col;
-    sa.val = A->val;
-    sa.n = n;
-    sa.ch = gm.ch;
-    sa.g = gm.g;
-    int rc;
-    int64_t matvecs = 0;
-
-    // r0 = b - A x0 with <r0,r0> partials (TSL:820, 826); <b,b> partials (TSL:815)
-    sa.x = x;
-    sa.y = r;
-    sa.mode = HIPK_SPMV_RESID | HIPK_SPMV_DOT_YY;
-    sa.bsub = b;
-    sa.part0 = part_c;
-    sa.part1 = part_b;
-    if ((rc = hipk_launch_spmv(A, sa, stream)) != HIPK_OK) return rc;
-    ++matvecs;
-    if ((rc = hipk_launch_dot_parts(n, b, b, A->dtype, part_a, stream)) != HIPK_OK) return rc;
-    hipk_pacer pace(A->host_poll, &scal->stop_it, check);
-    HIPK_CHECK_HIP(pace.create());
-    hipk_cg_start_kernel<T><<<gm.g, HIPK_THREADS, 0, stream>>>(n, gm.ch, gm.g, scal, part_b, part_a, r, p, tol2,
-                                                                atol_sq, maxiter, pace.device_sig());
-    HIPK_CHECK_HIP(hipGetLastError());
-
-    // ---- iteration loop: the host enqueues iterations a few ahead of the GPU and stops when the direction kernel
-    // reports the stop (hipk_pacer, hipk_solve.h); launches past the stop are no-ops on the device.
-    sa.x = p;
-    sa.y = Ap;
-    sa.mode = HIPK_SPMV_DOT_W;
-    sa.w = p;
-    sa.bsub = nullptr;
-    sa.part0 = part_a;
-    sa.part1 = part_c;
-    sa.stop_it = &scal->stop_it;
-    // which paths this solve takes (hipk_cg_path above); the latches: a one-launch loop once handed a solve back in this process
-    static bool mid_failed = false, lds_loop_failed = false;
-    hipk_cg_path path = hipk_cg_path_begin<T, false>(A, prm, maxiter, mid_failed, stream);
-    const bool small = path.small, streams = path.streams, flat_dir = path.flat_dir;
-    const int ntiles = (int)((n + HIPK_TILE - 1) / HIPK_TILE);
-    sa.skip_combine = small ? 1 : 0;
-
-    int64_t it = 0, stop = INT64_MAX;
-    bool lds_loop = false;   // finished in a one-launch loop: none of the launch sequences below runs
-    if ((rc = hipk_cg_one_launch<T, false>(A, scal, path, prm, x, r, p, Ap, (const T *)nullptr, nullptr, part_b, (unsigned long long *)(part_c + 1024),
-                                           it, maxiter, mid_failed, lds_loop_failed, handed, "hipk_cg_solve", stream, &lds_loop)) != HIPK_OK)
-        return rc;
-    constexpr int kCap2 = sizeof(T) == 8 ? 1280 : 2048;
-    hipk_cg_path_two(path, A, prm, lds_loop, it, kCap2, vec);
-    const bool two_launch = path.two_launch;
-    hipk_cg_path_defer(path, A, prm, lds_loop, vec);
-    const bool defer_x = path.defer_x;
-    if (!lds_loop)
-        hipk_set_solve_form(two_launch ? (sizeof(T) == 8 ? HIPK_FORM("cg two-launch: hipk_cg2_spmv_kernel<double,1280> + hipk_cg2_update_kernel")
-                                                         : HIPK_FORM("cg two-launch: hipk_cg2_spmv_kernel<float,2048> + hipk_cg2_update_kernel"))
-                            : small ? HIPK_FORM("cg three-launch, small")
-                            : streams && flat_dir ? HIPK_FORM("cg three-launch, streams + flat direction")
-                            : streams ? HIPK_FORM("cg three-launch, streams")
-                                      : HIPK_FORM("cg three-launch"));
-    if (two_launch) {
-        T *pbuf[2] = {p, (T *)((char *)Ap + vec)};   // p_0 = r_0 sits in pbuf[0] (start kernel); pass k reads pbuf[k & 1], writes the other
-        hipk_cg2_args ca;
-        ca.crow = A->crow;
-        ca.col = A->col;
-        ca.val = A->val;
-        ca.n = n;
-        ca.ch = gm.ch;
-        ca.g = gm.g;
-        ca.scal = scal;
-        ca.maxiter = maxiter;
-        ca.part_rr = part_b;
-        ca.r = r;
-        ca.Ap = Ap;
-        ca.tpart = A->tile_part;
-        const int grid1 = ((ntiles + 7) >> 3) << 3;
-        // pass `maxiter` is bookkeeping only (its K1 folds the last <r,r>, sets the stop word and gamma: TSL:841 "k >= maxiter")
-        for (; it <= maxiter; ++it) {
-            HIPK_CHECK_HIP(pace.gate(it, stream, &stop));
-            if (stop <= it) break;
-            ca.it = it;
-            ca.p_old = pbuf[it & 1];
-            ca.p_new = pbuf[(it + 1) & 1];
-            hipk_cg2_spmv_kernel<T, kCap2><<<grid1, HIPK_THREADS, 0, stream>>>(ca);
-            if (it < maxiter)
-                hipk_cg2_update_kernel<T><<<gm.g, HIPK_THREADS, 0, stream>>>(n, gm.ch, gm.g, scal, it, A->tile_part, ntiles, Ap,
-                                                                            (const T *)pbuf[(it + 1) & 1], r, x, part_b);
-            if ((it & 63) == 63) HIPK_CHECK_HIP(hipGetLastError());
-        }
-        if (it > maxiter) it = maxiter;
-    }
-    if (defer_x) {
-        // p_j of iteration it0 + j lives in pbuf[j & 1]; even j only forms p_{j+1} in the other buffer, odd j also brings x up to date
-        T *pbuf[2] = {p, (T *)((char *)Ap + vec)};
-        const int64_t it0 = it;
-        for (; it < maxiter; ++it) {
-            HIPK_CHECK_HIP(pace.gate(it, stream, &stop));
-            if (stop <= it) break;
-            const int j = (int)((it - it0) & 1);
-            sa.it = it;
-            sa.x = sa.w = pbuf[j];
-            if ((rc = hipk_launch_spmv(A, sa, stream, &prof)) != HIPK_OK) return rc;
-            hipk_cg_update_kernel<T><<<gm.g, HIPK_THREADS, 0, stream>>>(n, gm.ch, gm.g, scal, it, part_a, Ap, r, part_b, 0, &scal->alpha[it & 1]);
-            if (j == 0)
-                hipk_cg_pdir_kernel<T><<<gm.g, HIPK_THREADS, 0, stream>>>(n, gm.ch, gm.g, scal, it, maxiter, part_b, r, pbuf[0], pbuf[1]);
-            else
-                hipk_cg_xdir_kernel<T><<<gm.g, HIPK_THREADS, 0, stream>>>(n, gm.ch, gm.g, scal, it, maxiter, part_b, r, pbuf[1], pbuf[0], x);
-            if ((it & 63) == 63) HIPK_CHECK_HIP(hipGetLastError());
-        }
-        // an odd number of iterations: the last one's x update is still owed (the device knows how many were completed)
-        hipk_cg_xflush_kernel<T><<<gm.g, HIPK_THREADS, 0, stream>>>(n, gm.ch, scal, it, it0, pbuf[0], x);
-    }
-    for (; !lds_loop && !two_launch && !defer_x && it < maxiter; ++it) {
-        HIPK_CHECK_HIP(pace.gate(it, stream, &stop));
-        if (stop <= it) break;
-        {
-            sa.it = it;
-            // params.profile selects the kernel whose durations are reported (1 SpMV, 2 update, 3 direction, 4 scalars)
-            if ((rc = hipk_launch_spmv(A, sa, stream, &prof)) != HIPK_OK) return rc;
-            if (small)
-                hipk_launch_timed(&prof, HIPK_K_UPDATE, hipk_cg_update_kernel<T, true>, gm.g, HIPK_THREADS, 0, stream, n, gm.ch, gm.g, scal, it,
-                                  A->tile_part, Ap, r, part_b, ntiles, (double *)nullptr);
-            else if (streams)
-                hipk_launch_timed(&prof, HIPK_K_UPDATE, hipk_cg_update_kernel<T, false, true>, gm.g, HIPK_THREADS, 0, stream, n, gm.ch, gm.g, scal, it,
-                                  part_a, Ap, r, part_b, 0, (double *)nullptr);
-            else
-                hipk_launch_timed(&prof, HIPK_K_UPDATE, hipk_cg_update_kernel<T>, gm.g, HIPK_THREADS, 0, stream, n, gm.ch, gm.g, scal, it, part_a, Ap, r,
-                                  part_b, 0, (double *)nullptr);
-            if (small)
-                hipk_launch_timed(&prof, HIPK_K_DIRECTION, hipk_cg_direction_kernel<T, true>, gm.g, HIPK_THREADS, 0, stream, n, gm.ch, gm.g, scal, it,
-                                  maxiter, A->tile_part, part_b, r, p, x, ntiles);
-            else if (streams && flat_dir) {
-                // profile 3 times the flat kernel (the step's 40 n bytes), profile 4 the scalars launch before it
-                hipk_launch_timed(&prof, HIPK_K_SCALARS, hipk_cg_scalars_kernel, 1, HIPK_THREADS, 0, stream, gm.g, scal, it,
-                                  maxiter, part_a, part_b);
-                hipk_launch_timed(&prof, HIPK_K_DIRECTION, hipk_cg_direction_flat_kernel<T>, (unsigned)((n + HIPK_BASE_CHUNK - 1) / HIPK_BASE_CHUNK),
-                                  HIPK_THREADS, 0, stream, n, scal, it, r, p, x);
-            } else if (streams)
-                hipk_launch_timed(&prof, HIPK_K_DIRECTION, hipk_cg_direction_kernel<T, false, true>, gm.g, HIPK_THREADS, 0, stream, n, gm.ch, gm.g, scal, it,
-                                  maxiter, part_a, part_b, r, p, x, 0);
-            else
-                hipk_launch_timed(&prof, HIPK_K_DIRECTION, hipk_cg_direction_kernel<T>, gm.g, HIPK_THREADS, 0, stream, n, gm.ch, gm.g, scal, it, maxiter,
-                                  part_a, part_b, r, p, x, 0);
-        }
-        if ((it & 63) == 63) HIPK_CHECK_HIP(hipGetLastError());
-    }
-    HIPK_CHECK_HIP(hipGetLastError());
-
-    // ---- TSL:1007-1014: true residual, ||x||
-    sa.x = x;
-    sa.y = Ap;
-    sa.mode = HIPK_SPMV_RESID | HIPK_SPMV_DOT_YY;
-    sa.w = nullptr;
-    sa.bsub = b;
-    sa.part0 = part_c;
-    sa.part1 = part_b;
-    sa.stop_it = nullptr;
-    sa.skip_combine = 0;
-    if ((rc = hipk_launch_spmv(A, sa, stream)) != HIPK_OK) return rc;
-    ++matvecs;
-    if ((rc = hipk_launch_dot_parts(n, x, x, A->dtype, part_a, stream)) != HIPK_OK) return rc;
-    hipk_cg_final_kernel<<<1, HIPK_THREADS, 0, stream>>>(scal, gm.g, part_b, part_a);
-    HIPK_CHECK_HIP(hipGetLastError());
-    hipk_cg_scal hs;
-    HIPK_CHECK_HIP(hipEventRecord(whole.b, stream));
-    HIPK_CHECK_HIP(hipMemcpyAsync(&hs, scal, sizeof(hs), hipMemcpyDeviceToHost, stream));
-    HIPK_CHECK_HIP(hipStreamSynchronize(stream));
-
-    const int64_t iterations = (hs.stop_it < it) ? hs.stop_it : it;  // the device's stop word is authoritative
-    matvecs += iterations;
-    hipk_finish_isolve_stats(st, prm, hs.bs, hs.res2, hs.xx, iterations, matvecs);
-    st->recurrence_rs = hs.gamma[iterations & 1];
-    st->breakdown = 0;
-    float ms = 0.f;
-    HIPK_CHECK_HIP(hipEventElapsedTime(&ms, whole.a, whole.b));
-    st->solve_ms = ms;
-    HIPK_CHECK_HIP(prof.collect(st, iterations));
-    return HIPK_OK;
-}
-
-extern "C" int hipk_cg_solve(hipk_csr_t A, const void *b, void *x, void *work, size_t work_bytes,
-                             const hipk_params *prm, hipk_stats *st, hipk_stream_t stream) {
-    HIPK_REQUIRE(A && b && x && work && prm && st, HIPK_ERR_ARG, "null argument");
-    HIPK_REQUIRE(A->n_rows == A->n_cols, HIPK_ERR_ARG, "linear operator must be a square matrix");
-    HIPK_REQUIRE(A->n_rows > 0, HIPK_ERR_ARG, "empty system");
-    HIPK_REQUIRE(hipk_aligned16(b) && hipk_aligned16(x) && (((uintptr_t)work) & 255u) == 0, HIPK_ERR_ALIGN,
-                 "b/x must be 16-byte and work 256-byte aligned");
-    HIPK_REQUIRE(work_bytes >= hipk_cg_work_bytes(A->n_rows, A->dtype), HIPK_ERR_WORKSPACE, "work too small");
-    HIPK_REQUIRE(b != x, HIPK_ERR_ARG, "b and x must not alias");
-    memset(st, 0, sizeof(*st));
-    if (A->dtype == HIPK_F64)
-        return hipk_cg_solve_t<double>(A, (const double *)b, (double *)x, (char *)work, prm, st, (hipStream_t)stream);
-    return hipk_cg_solve_t<float>(A, (const float *)b, (float *)x, (char *)work, prm, st, (hipStream_t)stream);
 }
 
 // ------------------------------------------------------------------ step API (include/hipk.h)
@@ -2028,149 +1722,411 @@ __global__ __launch_bounds__(HIPK_THREADS) void hipk_pcg_final_kernel(hipk_pcg_s
     }
 }
 
-extern "C" size_t hipk_pcg_work_bytes(int64_t n, int dtype) {
-    const size_t sv = (dtype == HIPK_F64) ? 8 : 4;
-    const size_t vec = hipk_align_up((size_t)(n > 0 ? n : 1) * sv, 256);
-    // mid-size systems (the one-launch loop, hipk_cg_mid.h<.., PRE>): r as 16-byte flagged words in Ap + a fourth vector, three slot arrays
-    const hipk_geom gm = hipk_make_geom(n > 0 ? n : 1);
-    const bool mid = gm.g > kMidMinChunks && gm.g <= kPcgMidMaxChunks;
-    const size_t ll = hipk_align_up((size_t)(n > 0 ? n : 1) * 16, 256);   // r as 16-byte flagged words, from Ap on
-    return 256 + 6 * HIPK_MAX_PARTS * sizeof(double) + 3 * vec + (mid ? (ll - vec) + kPcgMidSlotBytes : 0);  // scalars | six partial slots | r, p, Ap
+// what the three-launch sequence of plain CG launches for its update and direction steps (hipk_cg_steps::pick)
+template <typename T>
+struct hipk_cg_kernels {
+    decltype(&hipk_cg_update_kernel<T>) update;
+    decltype(&hipk_cg_direction_kernel<T>) direction;   // null: the flat form, hipk_cg_scalars_kernel + hipk_cg_direction_flat_kernel
+    const double *pap;   // what they fold <p,Ap> from: the chunk partials, or (small) the SpMV's tile sums
+    int ntiles;          // small: the tile count; else 0
+    const char *form;
+};
+
+// One single-device solve of hipk_cg_solve (PRE = false) or hipk_pcg_solve (PRE = true, M = diag(dinv)): its operands, workspace
+// and state, and the steps hipk_cg_solve_t and hipk_pcg_solve_t drive it through.
+template <typename T, bool PRE>
+struct hipk_cg_steps {
+    typedef typename std::conditional<PRE, hipk_pcg_scal, hipk_cg_scal>::type S;
+    static constexpr int kCap2 = sizeof(T) == 8 ? 1280 : 2048;   // the tile capacity of hipk_cg2_spmv_kernel
+    hipk_csr_s *A;
+    const T *dinv, *b;
+    T *x;
+    const hipk_params *prm;
+    hipStream_t stream;
+    const int64_t n, maxiter;
+    const hipk_geom gm;
+    const int ntiles;
+    const hipk_cg_layout lay;
+    char *const work;
+    S *const scal = hipk_at<S>(work, lay.scal);
+    double *const part_a = hipk_at<double>(work, lay.part_a), *const part_b = hipk_at<double>(work, lay.part_b);
+    double *const part_c = hipk_at<double>(work, lay.part_c), *const part_d = hipk_at<double>(work, lay.part_d);
+    double *const part_z[2] = {hipk_at<double>(work, lay.part_z[0]), hipk_at<double>(work, lay.part_z[1])};
+    T *const r = hipk_at<T>(work, lay.r), *const p = hipk_at<T>(work, lay.p), *const Ap = hipk_at<T>(work, lay.Ap);
+    hipk_spmv_args sa = hipk_spmv_base(A);   // the SpMV of an iteration, Ap = A p with <p,Ap>
+    hipk_event_pair whole;
+    hipk_spmv_profiler prof;
+    hipk_pacer pace;
+    hipk_cg_path path;
+    int64_t it = 0, stop = INT64_MAX;
+    bool done = false;       // a one-launch loop finished the solve
+    char handed[128] = "";   // the one-launch loops that handed this solve back
+
+    // profile: the KIND of kernel whose durations are reported (hipk_spmv_profiler; only launches of it carry events), 0: none
+    hipk_cg_steps(hipk_csr_s *A_, const T *dinv_, const T *b_, T *x_, char *w, const hipk_params *prm_, hipStream_t s_, int profile)
+        : A(A_), dinv(dinv_), b(b_), x(x_), prm(prm_), stream(s_), n(A_->n_rows), maxiter(hipk_default_maxiter(prm_, A_->n_rows)), gm(A_->geom),
+          ntiles((int)((A_->n_rows + HIPK_TILE - 1) / HIPK_TILE)), lay(hipk_cg_make_layout(A_->n_rows, A_->dtype, PRE)), work(w), prof(profile),
+          pace(A_->host_poll, &scal->stop_it, prm_->check_every > 0 ? prm_->check_every : 64) {}
+
+    // y = b - A x; the chunk partials of its squared norm in part_yy, or (null) none
+    int residual(T *y, double *part_yy) const {
+        hipk_spmv_args sr = sa;   // the handle's arrays and geometry; everything an iteration's SpMV sets is set again
+        sr.x = x;
+        sr.y = y;
+        sr.mode = HIPK_SPMV_RESID | (part_yy ? HIPK_SPMV_DOT_YY : 0);
+        sr.w = nullptr;
+        sr.bsub = b;
+        sr.part0 = part_c;
+        sr.part1 = part_yy ? part_yy : part_c;
+        sr.stop_it = nullptr;
+        sr.skip_combine = 0;
+        return hipk_launch_spmv(A, sr, stream);
+    }
+
+    // r0 = b - A x0 with <r0,r0> partials (TSL:820, 826); <b,b> partials (TSL:815); p0 (PRE: z0 = M r0, p0 = z0, the partials of
+    // gamma0 = <r0,z0> in part_z[0]), the stop word and the tolerances
+    int start() {
+        hipk_set_solve_path(nullptr, "");
+        HIPK_CHECK_HIP(whole.create());
+        HIPK_CHECK_HIP(hipEventRecord(whole.a, stream));
+        HIPK_TRY(residual(r, part_b));
+        HIPK_TRY(hipk_launch_dot_parts(n, b, b, A->dtype, part_d, stream));
+        HIPK_CHECK_HIP(pace.create());   // zeroes the pinned signal word: before the kernel that may write it is enqueued
+        const hipk_tol_sq tol(prm);
+        if constexpr (PRE)
+            hipk_pcg_start_kernel<T><<<gm.g, HIPK_THREADS, 0, stream>>>(n, gm.ch, gm.g, scal, part_b, part_d, r, dinv, p, part_z[0], tol.tol2,
+                                                                         tol.atol_sq, maxiter, pace.device_sig());
+        else
+            hipk_cg_start_kernel<T><<<gm.g, HIPK_THREADS, 0, stream>>>(n, gm.ch, gm.g, scal, part_b, part_d, r, p, tol.tol2, tol.atol_sq, maxiter,
+                                                                        pace.device_sig());
+        HIPK_CHECK_HIP(hipGetLastError());
+        sa.x = p;
+        sa.y = Ap;
+        sa.mode = HIPK_SPMV_DOT_W;
+        sa.w = p;
+        sa.part0 = part_a;
+        sa.part1 = part_c;
+        sa.stop_it = &scal->stop_it;
+        return HIPK_OK;
+    }
+
+    // launch-bound mid-size systems: the whole loop in one launch, path.mid_entry's kernel on workgroups of path.nch chunks, from
+    // iteration `it` -- HIPK_OK, HIPK_HANDED_BACK or an error (hipk_resident_run); failed: the caller's latch
+    int mid_loop(bool &failed, const char *entry) {
+        const hipk_mid_entry<hipk_cg_mid_args> *mid = path.mid_entry;
+        const size_t lds = path.mid_lds;
+        const int grid = (gm.g + mid->nch - 1) / mid->nch;
+        hipk_cg_mid_args ca;
+        memset(&ca, 0, sizeof(ca));
+        ca.n = n;
+        ca.g = gm.g;
+        ca.win = path.mid_plan.max_slots * HIPK_TILE;
+        ca.plan = path.mid_plan;
+        ca.crow = A->crow;
+        ca.col = A->col;
+        ca.val = A->val;
+        ca.x = x;
+        ca.r = r;
+        ca.p = p;
+        ca.r_ll = hipk_at<unsigned long long>(work, lay.r_ll);
+        ca.pap_ll = hipk_at<unsigned long long>(work, lay.pap_ll);
+        ca.rr_ll = hipk_at<unsigned long long>(work, lay.rr_ll);
+        if (PRE) ca.rz_ll = hipk_at<unsigned long long>(work, lay.rz_ll);
+        ca.dinv = dinv;
+        ca.rz0_parts = PRE ? part_z[0] : nullptr;
+        ca.slot_stride = path.slot_stride;
+        ca.xcd_aware = path.xcd_aware;
+        ca.ctl = &scal->ctl;
+        ca.gamma = scal->gamma;
+        ca.atol2 = &scal->atol2;
+        ca.stop_it = &scal->stop_it;
+        ca.maxiter = maxiter;
+        ca.max_its = path.max_its;
+        auto launch = [&](int64_t it0, int test_not_resident, bool) -> int {
+            ca.it0 = it0;
+            ca.test_not_resident = test_not_resident;
+            HIPK_CHECK_HIP(hipMemsetAsync(ca.r_ll, 0, lay.ll_bytes, stream));
+            HIPK_CHECK_HIP(hipMemsetAsync(ca.pap_ll, 0, PRE ? kPcgMidSlotBytes : kMidSlotBytes, stream));
+            HIPK_CHECK_HIP(hipMemsetAsync(&scal->ctl, 0, sizeof(hipk_lds_ctl), stream));
+            mid->kern<<<hipk_xcd_grid(grid), 1024, lds, stream>>>(ca);   // hipk_xcd_chunk: padded to a multiple of 8
+            return HIPK_OK;
+        };
+        return hipk_resident_run(stream, scal, launch, hipk_cg_loop_state<S>, it, maxiter, nullptr, failed, handed, mid->name, entry);
+    }
+
+    // launch-bound systems with short rows: the whole loop in one launch, hipk_cg_solve_lds_kernel, from iteration `it` -- as
+    // mid_loop; *form: the instantiation of its last launch (hipk_last_solve_form)
+    int lds_loop(bool &failed, const char *entry, const char **form) {
+        bool local = path.local;   // a -2 (spread over several XCDs): agent-scope hand-offs
+        const int lgrid = path.spread ? kGmSub * gm.g : 8 * kGmSub * gm.g;
+        hipk_cg_lds_args<T> ca;
+        ca.n = n;
+        ca.g = gm.g;
+        ca.crow = A->crow;
+        ca.col = A->col;
+        ca.val = (const T *)A->val;
+        ca.x = x;
+        ca.r = r;
+        ca.p = p;
+        ca.Ap = Ap;
+        ca.ctl = &scal->ctl;
+        ca.gamma = scal->gamma;
+        ca.atol2 = &scal->atol2;
+        ca.stop_it = &scal->stop_it;
+        ca.dinv = dinv;
+        ca.rz0_parts = PRE ? part_z[0] : nullptr;
+        ca.rz_sub = PRE ? hipk_at<double>(work, lay.lds_rz_sub) : nullptr;
+        ca.tile_pp = A->tile_part;
+        ca.rr_sub = hipk_at<double>(work, lay.lds_rr_sub);
+        ca.flag_a = hipk_at<unsigned long long>(work, lay.lds_flags);
+        ca.flag_b = ca.flag_a + kHoMaxWg;
+        ca.spread = path.spread ? 1 : 0;
+        ca.maxiter = maxiter;
+        ca.max_its = path.max_its;
+        auto launch = [&](int64_t it0, int test_not_resident, bool loc) -> int {
+            ca.it0 = it0;
+            ca.test_not_resident = test_not_resident;
+            HIPK_CHECK_HIP(hipMemsetAsync(ca.flag_a, 0, 2 * kHoMaxWg * sizeof(unsigned long long), stream));
+            HIPK_CHECK_HIP(hipMemsetAsync(&scal->ctl, 0, sizeof(hipk_lds_ctl), stream));
+            (loc ? hipk_cg_solve_lds_kernel<T, true, PRE> : hipk_cg_solve_lds_kernel<T, false, PRE>)<<<lgrid, HIPK_THREADS, 0, stream>>>(ca);
+            return HIPK_OK;
+        };
+        const int run = hipk_resident_run(stream, scal, launch, hipk_cg_loop_state<S>, it, maxiter, &local, failed, handed,
+                                          "hipk_cg_solve_lds_kernel", entry);
+        *form = local ? (PRE ? HIPK_FORM_OF_T(T, "hipk_cg_solve_lds_kernel<", "true,true>") : HIPK_FORM_OF_T(T, "hipk_cg_solve_lds_kernel<", "true,false>"))
+                      : (PRE ? HIPK_FORM_OF_T(T, "hipk_cg_solve_lds_kernel<", "false,true>") : HIPK_FORM_OF_T(T, "hipk_cg_solve_lds_kernel<", "false,false>"));
+        return run;
+    }
+
+    // The one-launch section: the mid loop, else the LDS loop, from iteration `it`; `done` when one of them finished the solve,
+    // else the caller's launch sequence goes on from `it` (and names its form).  Records the path hipk_last_solve_path reports.
+    // The latches: a one-launch loop once handed a solve back in this process
+    int one_launch(bool &mid_failed, bool &lds_failed, const char *entry) {
+        path = hipk_cg_path_begin<T, PRE>(A, prm, maxiter, mid_failed, stream);
+        sa.skip_combine = path.small ? 1 : 0;
+        // a hand-back at it > 0 (from an EARLIER launch of the loop): x, r, p are in memory, but <r,z> only as scal->gamma[it & 1], while
+        // the Jacobi launch sequence folds it from the chunk partials part_z[it & 1].  Rebuild that slot as {gamma, 0, 0, ...}: the
+        // fold of it is gamma, bit for bit.  (Plain CG's launch sequence reads gamma itself.)
+        auto after = [&](int run) -> int {
+            if (PRE && run == HIPK_HANDED_BACK && it > 0) {
+                HIPK_CHECK_HIP(hipMemsetAsync(part_z[it & 1], 0, (size_t)gm.g * sizeof(double), stream));
+                HIPK_CHECK_HIP(hipMemcpyAsync(part_z[it & 1], &scal->gamma[it & 1], sizeof(double), hipMemcpyDeviceToDevice, stream));
+            }
+            return HIPK_OK;
+        };
+        bool mid_done = false, lds_done = false;
+        const char *lds_form = "";
+        if (path.mid) {
+            const int run = mid_loop(mid_failed, entry);
+            if (run < 0) return run;
+            HIPK_TRY(after(run));
+            mid_done = run == HIPK_OK;
+        }
+        hipk_cg_path_lds(path, A, prm, maxiter, mid_done, lds_failed);
+        if (path.lds_loop) {   // a hand-back (not co-resident; that launch modified nothing): the launch sequence takes over
+            const int run = lds_loop(lds_failed, entry, &lds_form);
+            if (run < 0) return run;
+            HIPK_TRY(after(run));
+            lds_done = run == HIPK_OK;
+        }
+        done = mid_done || lds_done;
+        hipk_set_solve_path(handed, mid_done ? path.mid_entry->name : lds_done ? "hipk_cg_solve_lds_kernel" : "launch sequence");
+        if (done) hipk_set_solve_form(mid_done ? path.mid_entry->name : lds_form);
+        return HIPK_OK;
+    }
+
+    // ---- the launch sequences: the host enqueues iterations a few ahead of the GPU and stops when the direction kernel reports
+    // the stop (hipk_pacer, hipk_solve.h); launches past the stop are no-ops on the device.
+
+    // plain CG, 33 .. kCg2MaxChunks chunks: hipk_cg2_spmv_kernel + hipk_cg2_update_kernel per iteration
+    int two_launch_sequence() {
+        T *pbuf[2] = {p, hipk_at<T>(work, lay.p2)};   // p_0 = r_0 sits in pbuf[0] (start kernel); pass k reads pbuf[k & 1], writes the other
+        hipk_cg2_args ca;
+        ca.crow = A->crow;
+        ca.col = A->col;
+        ca.val = A->val;
+        ca.n = n;
+        ca.ch = gm.ch;
+        ca.g = gm.g;
+        ca.scal = scal;
+        ca.maxiter = maxiter;
+        ca.part_rr = part_b;
+        ca.r = r;
+        ca.Ap = Ap;
+        ca.tpart = A->tile_part;
+        const int grid1 = ((ntiles + 7) >> 3) << 3;
+        // pass `maxiter` is bookkeeping only (its K1 folds the last <r,r>, sets the stop word and gamma: TSL:841 "k >= maxiter")
+        for (; it <= maxiter; ++it) {
+            HIPK_CHECK_HIP(pace.gate(it, stream, &stop));
+            if (stop <= it) break;
+            ca.it = it;
+            ca.p_old = pbuf[it & 1];
+            ca.p_new = pbuf[(it + 1) & 1];
+            hipk_cg2_spmv_kernel<T, kCap2><<<grid1, HIPK_THREADS, 0, stream>>>(ca);
+            if (it < maxiter)
+                hipk_cg2_update_kernel<T><<<gm.g, HIPK_THREADS, 0, stream>>>(n, gm.ch, gm.g, scal, it, A->tile_part, ntiles, Ap,
+                                                                            (const T *)pbuf[(it + 1) & 1], r, x, part_b);
+            if ((it & 63) == 63) HIPK_CHECK_HIP(hipGetLastError());
+        }
+        if (it > maxiter) it = maxiter;
+        return HIPK_OK;
+    }
+
+    // plain CG, three launches with the x update deferred: SpMV, hipk_cg_update_kernel, hipk_cg_pdir_kernel / hipk_cg_xdir_kernel
+    int deferred_x_sequence() {
+        // p_j of iteration it0 + j lives in pbuf[j & 1]; even j only forms p_{j+1} in the other buffer, odd j also brings x up to date
+        T *pbuf[2] = {p, hipk_at<T>(work, lay.p2)};
+        const int64_t it0 = it;
+        for (; it < maxiter; ++it) {
+            HIPK_CHECK_HIP(pace.gate(it, stream, &stop));
+            if (stop <= it) break;
+            const int j = (int)((it - it0) & 1);
+            sa.it = it;
+            sa.x = sa.w = pbuf[j];
+            HIPK_TRY(hipk_launch_spmv(A, sa, stream, &prof));
+            hipk_cg_update_kernel<T><<<gm.g, HIPK_THREADS, 0, stream>>>(n, gm.ch, gm.g, scal, it, part_a, Ap, r, part_b, 0, &scal->alpha[it & 1]);
+            if (j == 0)
+                hipk_cg_pdir_kernel<T><<<gm.g, HIPK_THREADS, 0, stream>>>(n, gm.ch, gm.g, scal, it, maxiter, part_b, r, pbuf[0], pbuf[1]);
+            else
+                hipk_cg_xdir_kernel<T><<<gm.g, HIPK_THREADS, 0, stream>>>(n, gm.ch, gm.g, scal, it, maxiter, part_b, r, pbuf[1], pbuf[0], x);
+            if ((it & 63) == 63) HIPK_CHECK_HIP(hipGetLastError());
+        }
+        // an odd number of iterations: the last one's x update is still owed (the device knows how many were completed)
+        hipk_cg_xflush_kernel<T><<<gm.g, HIPK_THREADS, 0, stream>>>(n, gm.ch, scal, it, it0, pbuf[0], x);
+        return HIPK_OK;
+    }
+
+    // the kernels of the plain three-launch sequence (hipk_cg_path: small / streams / flat_dir) and the form they make
+    hipk_cg_kernels<T> pick() const {
+        if (path.small)
+            return {hipk_cg_update_kernel<T, true>, hipk_cg_direction_kernel<T, true>, A->tile_part, ntiles, HIPK_FORM("cg three-launch, small")};
+        if (path.streams && path.flat_dir)
+            return {hipk_cg_update_kernel<T, false, true>, nullptr, part_a, 0, HIPK_FORM("cg three-launch, streams + flat direction")};
+        if (path.streams)
+            return {hipk_cg_update_kernel<T, false, true>, hipk_cg_direction_kernel<T, false, true>, part_a, 0, HIPK_FORM("cg three-launch, streams")};
+        return {hipk_cg_update_kernel<T>, hipk_cg_direction_kernel<T>, part_a, 0, HIPK_FORM("cg three-launch")};
+    }
+
+    // plain CG: SpMV, update, direction.  params.profile selects the kernel whose durations are reported (1 SpMV, 2 update,
+    // 3 direction -- of the flat form its flat kernel, the step's 40 n bytes --, 4 the scalars launch before that)
+    int three_launch_sequence(const hipk_cg_kernels<T> &k) {
+        for (; it < maxiter; ++it) {
+            HIPK_CHECK_HIP(pace.gate(it, stream, &stop));
+            if (stop <= it) break;
+            sa.it = it;
+            HIPK_TRY(hipk_launch_spmv(A, sa, stream, &prof));
+            hipk_launch_timed(&prof, HIPK_K_UPDATE, k.update, gm.g, HIPK_THREADS, 0, stream, n, gm.ch, gm.g, scal, it, k.pap, Ap, r, part_b, k.ntiles,
+                              (double *)nullptr);
+            if (k.direction) {
+                hipk_launch_timed(&prof, HIPK_K_DIRECTION, k.direction, gm.g, HIPK_THREADS, 0, stream, n, gm.ch, gm.g, scal, it, maxiter, k.pap, part_b, r,
+                                  p, x, k.ntiles);
+            } else {
+                hipk_launch_timed(&prof, HIPK_K_SCALARS, hipk_cg_scalars_kernel, 1, HIPK_THREADS, 0, stream, gm.g, scal, it, maxiter, part_a, part_b);
+                hipk_launch_timed(&prof, HIPK_K_DIRECTION, hipk_cg_direction_flat_kernel<T>, (unsigned)((n + HIPK_BASE_CHUNK - 1) / HIPK_BASE_CHUNK),
+                                  HIPK_THREADS, 0, stream, n, scal, it, r, p, x);
+            }
+            if ((it & 63) == 63) HIPK_CHECK_HIP(hipGetLastError());
+        }
+        return HIPK_OK;
+    }
+
+    // Jacobi PCG: SpMV, hipk_pcg_update_kernel, hipk_pcg_direction_kernel
+    int jacobi_sequence() {
+        for (; it < maxiter; ++it) {
+            HIPK_CHECK_HIP(pace.gate(it, stream, &stop));
+            if (stop <= it) break;
+            sa.it = it;
+            HIPK_TRY(hipk_launch_spmv(A, sa, stream));
+            hipk_pcg_update_kernel<T><<<gm.g, HIPK_THREADS, 0, stream>>>(n, gm.ch, gm.g, scal, it, part_a, part_z[it & 1], Ap, dinv, r, part_b,
+                                                                          part_z[(it + 1) & 1]);
+            hipk_pcg_direction_kernel<T><<<gm.g, HIPK_THREADS, 0, stream>>>(n, gm.ch, gm.g, scal, it, maxiter, part_a, part_z[it & 1],
+                                                                             part_z[(it + 1) & 1], part_b, r, dinv, p, x);
+            if ((it & 63) == 63) HIPK_CHECK_HIP(hipGetLastError());
+        }
+        return HIPK_OK;
+    }
+
+    // TSL:1007-1014: the true residual (PRE: ||M (b - A x)||) and ||x|| decide info
+    int finish(hipk_stats *st) {
+        HIPK_CHECK_HIP(hipGetLastError());
+        if constexpr (PRE) {
+            HIPK_TRY(residual(Ap, nullptr));
+            hipk_pcg_resnorm_kernel<T><<<gm.g, HIPK_THREADS, 0, stream>>>(n, gm.ch, Ap, dinv, part_b);
+        } else {
+            HIPK_TRY(residual(Ap, part_b));
+        }
+        HIPK_TRY(hipk_launch_dot_parts(n, x, x, A->dtype, part_d, stream));
+        if constexpr (PRE)
+            hipk_pcg_final_kernel<<<1, HIPK_THREADS, 0, stream>>>(scal, gm.g, part_b, part_d);
+        else
+            hipk_cg_final_kernel<<<1, HIPK_THREADS, 0, stream>>>(scal, gm.g, part_b, part_d);
+        HIPK_CHECK_HIP(hipGetLastError());
+        S hs;
+        HIPK_CHECK_HIP(hipEventRecord(whole.b, stream));
+        HIPK_CHECK_HIP(hipMemcpyAsync(&hs, scal, sizeof(hs), hipMemcpyDeviceToHost, stream));
+        HIPK_CHECK_HIP(hipStreamSynchronize(stream));
+
+        const int64_t iterations = (hs.stop_it < it) ? hs.stop_it : it;  // the device's stop word is authoritative
+        hipk_finish_isolve_stats(st, prm, hs.bs, hs.res2, hs.xx, iterations, iterations + 2);   // + r0 and the true residual
+        if constexpr (PRE)
+            st->recurrence_rs = (done && iterations > 0) ? hs.ctl.rs_last : hs.rs_last;
+        else
+            st->recurrence_rs = hs.gamma[iterations & 1];
+        st->breakdown = 0;
+        float ms = 0.f;
+        HIPK_CHECK_HIP(hipEventElapsedTime(&ms, whole.a, whole.b));
+        st->solve_ms = ms;
+        HIPK_CHECK_HIP(prof.collect(st, iterations));
+        return HIPK_OK;
+    }
+};
+
+template <typename T>
+static int hipk_cg_solve_t(hipk_csr_s *A, const T *b, T *x, char *work, const hipk_params *prm, hipk_stats *st, hipStream_t stream) {
+    static bool mid_failed = false, lds_loop_failed = false;   // per dtype; hipk_pcg_solve_t has its own
+    hipk_cg_steps<T, false> s(A, nullptr, b, x, work, prm, stream, prm->profile);
+    HIPK_TRY(s.start());
+    HIPK_TRY(s.one_launch(mid_failed, lds_loop_failed, "hipk_cg_solve"));
+    // what is left when neither loop finished: two launches per iteration, else three with the x update deferred, else three
+    hipk_cg_path_two(s.path, A, prm, s.done, s.it, s.kCap2, s.lay);
+    hipk_cg_path_defer(s.path, A, prm, s.done, s.lay);
+    if (!s.done) {
+        const hipk_cg_kernels<T> k = s.pick();   // (the deferred-x form reports the three-launch form it replaces the direction step of)
+        hipk_set_solve_form(!s.path.two_launch ? k.form
+                            : sizeof(T) == 8   ? HIPK_FORM("cg two-launch: hipk_cg2_spmv_kernel<double,1280> + hipk_cg2_update_kernel")
+                                               : HIPK_FORM("cg two-launch: hipk_cg2_spmv_kernel<float,2048> + hipk_cg2_update_kernel"));
+        HIPK_TRY(s.path.two_launch ? s.two_launch_sequence() : s.path.defer_x ? s.deferred_x_sequence() : s.three_launch_sequence(k));
+    }
+    return s.finish(st);
 }
 
 template <typename T>
-static int hipk_pcg_solve_t(hipk_csr_s *A, const T *dinv, const T *b, T *x, char *work, const hipk_params *prm,
-                            hipk_stats *st, hipStream_t stream) {
-    const int64_t n = A->n_rows;
-    const hipk_geom gm = A->geom;
-    const size_t vec = hipk_align_up((size_t)(n > 0 ? n : 1) * sizeof(T), 256);
-    hipk_pcg_scal *scal = (hipk_pcg_scal *)work;
-    double *parts = (double *)(work + 256);
-    double *part_a = parts, *part_b = parts + HIPK_MAX_PARTS, *part_c = parts + 2 * HIPK_MAX_PARTS;
-    double *part_z[2] = {parts + 3 * HIPK_MAX_PARTS, parts + 4 * HIPK_MAX_PARTS};
-    double *part_d = parts + 5 * HIPK_MAX_PARTS;
-    T *r = (T *)(work + 256 + 6 * HIPK_MAX_PARTS * sizeof(double));
-    T *p = (T *)((char *)r + vec);
-    T *Ap = (T *)((char *)p + vec);
-
-    const int64_t maxiter = (prm->maxiter < 0) ? 10 * n : prm->maxiter;
-    const float tolf = (float)prm->tol, atolf = (float)prm->atol;
-    const double tol2 = (double)(tolf * tolf), atol_sq = (double)(atolf * atolf);
-    const int64_t check = prm->check_every > 0 ? prm->check_every : 64;
-    hipk_set_solve_path(nullptr, "");
-    char handed[128] = "";   // the one-launch loops that handed this solve back
-
-    hipk_event_pair whole;
-    HIPK_CHECK_HIP(whole.create());
-    HIPK_CHECK_HIP(hipEventRecord(whole.a, stream));
-
-    hipk_spmv_args sa;
-    memset(&sa, 0, sizeof(sa));
-    sa.crow = A->crow;
-    sa.col = A->col;
-    sa.val = A->val;
-    sa.n = n;
-    sa.ch = gm.ch;
-    sa.g = gm.g;
-    int rc;
-    int64_t matvecs = 0;
-
-    // r0 = b - A x0 with <r0,r0> partials; <b,b>; z0, p0, gamma0 partials
-    sa.x = x;
-    sa.y = r;
-    sa.mode = HIPK_SPMV_RESID | HIPK_SPMV_DOT_YY;
-    sa.bsub = b;
-    sa.part0 = part_c;
-    sa.part1 = part_b;
-    if ((rc = hipk_launch_spmv(A, sa, stream)) != HIPK_OK) return rc;
-    ++matvecs;
-    if ((rc = hipk_launch_dot_parts(n, b, b, A->dtype, part_d, stream)) != HIPK_OK) return rc;
-    hipk_pacer pace(A->host_poll, &scal->stop_it, check);
-    HIPK_CHECK_HIP(pace.create());
-    hipk_pcg_start_kernel<T><<<gm.g, HIPK_THREADS, 0, stream>>>(n, gm.ch, gm.g, scal, part_b, part_d, r, dinv, p, part_z[0],
-                                                                 tol2, atol_sq, maxiter, pace.device_sig());
-    HIPK_CHECK_HIP(hipGetLastError());
-
-    sa.x = p;
-    sa.y = Ap;
-    sa.mode = HIPK_SPMV_DOT_W;
-    sa.w = p;
-    sa.bsub = nullptr;
-    sa.part0 = part_a;
-    sa.part1 = part_c;
-    sa.stop_it = &scal->stop_it;
-
-    int64_t it = 0, stop = INT64_MAX;
-    // which paths this solve takes (hipk_cg_path above); the latches: a one-launch loop once handed a solve back in this process
-    static bool mid_failed = false, lds_loop_failed = false;
-    hipk_cg_path path = hipk_cg_path_begin<T, true>(A, prm, maxiter, mid_failed, stream);
-    bool lds_loop = false;   // finished in a one-launch loop
-    if ((rc = hipk_cg_one_launch<T, true>(A, scal, path, prm, x, r, p, Ap, dinv, part_z, part_b, (unsigned long long *)(part_c + 1024), it, maxiter,
-                                          mid_failed, lds_loop_failed, handed, "hipk_pcg_solve", stream, &lds_loop)) != HIPK_OK)
-        return rc;
-    if (!lds_loop) hipk_set_solve_form(HIPK_FORM("pcg three-launch, Jacobi"));
-    for (; !lds_loop && it < maxiter; ++it) {
-        HIPK_CHECK_HIP(pace.gate(it, stream, &stop));
-        if (stop <= it) break;
-        {
-            sa.it = it;
-            if ((rc = hipk_launch_spmv(A, sa, stream)) != HIPK_OK) return rc;
-            hipk_pcg_update_kernel<T><<<gm.g, HIPK_THREADS, 0, stream>>>(n, gm.ch, gm.g, scal, it, part_a, part_z[it & 1], Ap,
-                                                                          dinv, r, part_b, part_z[(it + 1) & 1]);
-            hipk_pcg_direction_kernel<T><<<gm.g, HIPK_THREADS, 0, stream>>>(n, gm.ch, gm.g, scal, it, maxiter, part_a,
-                                                                             part_z[it & 1], part_z[(it + 1) & 1], part_b, r,
-                                                                             dinv, p, x);
-        }
-        if ((it & 63) == 63) HIPK_CHECK_HIP(hipGetLastError());
+static int hipk_pcg_solve_t(hipk_csr_s *A, const T *dinv, const T *b, T *x, char *work, const hipk_params *prm, hipk_stats *st, hipStream_t stream) {
+    static bool mid_failed = false, lds_loop_failed = false;   // per dtype
+    hipk_cg_steps<T, true> s(A, dinv, b, x, work, prm, stream, 0);   // (no per-kernel profile of the Jacobi kernels)
+    HIPK_TRY(s.start());
+    HIPK_TRY(s.one_launch(mid_failed, lds_loop_failed, "hipk_pcg_solve"));
+    if (!s.done) {
+        hipk_set_solve_form(HIPK_FORM("pcg three-launch, Jacobi"));
+        HIPK_TRY(s.jacobi_sequence());
     }
-    HIPK_CHECK_HIP(hipGetLastError());
+    return s.finish(st);
+}
 
-    // TSL:1007-1014 with M: ||M (b - A x)||, ||x||
-    sa.x = x;
-    sa.y = Ap;
-    sa.mode = HIPK_SPMV_RESID;
-    sa.w = nullptr;
-    sa.bsub = b;
-    sa.part0 = part_c;
-    sa.part1 = part_c;
-    sa.stop_it = nullptr;
-    if ((rc = hipk_launch_spmv(A, sa, stream)) != HIPK_OK) return rc;
-    ++matvecs;
-    hipk_pcg_resnorm_kernel<T><<<gm.g, HIPK_THREADS, 0, stream>>>(n, gm.ch, Ap, dinv, part_b);
-    if ((rc = hipk_launch_dot_parts(n, x, x, A->dtype, part_d, stream)) != HIPK_OK) return rc;
-    hipk_pcg_final_kernel<<<1, HIPK_THREADS, 0, stream>>>(scal, gm.g, part_b, part_d);
-    HIPK_CHECK_HIP(hipGetLastError());
-    hipk_pcg_scal hs;
-    HIPK_CHECK_HIP(hipEventRecord(whole.b, stream));
-    HIPK_CHECK_HIP(hipMemcpyAsync(&hs, scal, sizeof(hs), hipMemcpyDeviceToHost, stream));
-    HIPK_CHECK_HIP(hipStreamSynchronize(stream));
-
-    const int64_t iterations = (hs.stop_it < it) ? hs.stop_it : it;
-    matvecs += iterations;
-    hipk_finish_isolve_stats(st, prm, hs.bs, hs.res2, hs.xx, iterations, matvecs);
-    st->recurrence_rs = (lds_loop && iterations > 0) ? hs.ctl.rs_last : hs.rs_last;
-    st->breakdown = 0;
-    float ms = 0.f;
-    HIPK_CHECK_HIP(hipEventElapsedTime(&ms, whole.a, whole.b));
-    st->solve_ms = ms;
-    return HIPK_OK;
+extern "C" int hipk_cg_solve(hipk_csr_t A, const void *b, void *x, void *work, size_t work_bytes,
+                             const hipk_params *prm, hipk_stats *st, hipk_stream_t stream) {
+    HIPK_TRY(hipk_solve_check(A, true, nullptr, b, x, work, work_bytes, hipk_cg_work_bytes, prm, st));
+    if (A->dtype == HIPK_F64)
+        return hipk_cg_solve_t<double>(A, (const double *)b, (double *)x, (char *)work, prm, st, (hipStream_t)stream);
+    return hipk_cg_solve_t<float>(A, (const float *)b, (float *)x, (char *)work, prm, st, (hipStream_t)stream);
 }
 
 extern "C" int hipk_pcg_solve(hipk_csr_t A, const void *dinv, const void *b, void *x, void *work, size_t work_bytes,
                               const hipk_params *prm, hipk_stats *st, hipk_stream_t stream) {
-    HIPK_REQUIRE(A && dinv && b && x && work && prm && st, HIPK_ERR_ARG, "null argument");
-    HIPK_REQUIRE(A->n_rows == A->n_cols, HIPK_ERR_ARG, "linear operator must be a square matrix");
-    HIPK_REQUIRE(A->n_rows > 0, HIPK_ERR_ARG, "empty system");
-    HIPK_REQUIRE(hipk_aligned16(b) && hipk_aligned16(x) && hipk_aligned16(dinv) && (((uintptr_t)work) & 255u) == 0,
-                 HIPK_ERR_ALIGN, "b/x/dinv must be 16-byte and work 256-byte aligned");
-    HIPK_REQUIRE(work_bytes >= hipk_pcg_work_bytes(A->n_rows, A->dtype), HIPK_ERR_WORKSPACE, "work too small");
-    HIPK_REQUIRE(b != x, HIPK_ERR_ARG, "b and x must not alias");
-    memset(st, 0, sizeof(*st));
+    HIPK_TRY(hipk_solve_check(A, dinv != nullptr, dinv, b, x, work, work_bytes, hipk_pcg_work_bytes, prm, st));
     if (A->dtype == HIPK_F64)
-        return hipk_pcg_solve_t<double>(A, (const double *)dinv, (const double *)b, (double *)x, (char *)work, prm, st,
-                                        (hipStream_t)stream);
-    return hipk_pcg_solve_t<float>(A, (const float *)dinv, (const float *)b, (float *)x, (char *)work, prm, st,
-                                   (hipStream_t)stream);
+        return hipk_pcg_solve_t<double>(A, (const double *)dinv, (const double *)b, (double *)x, (char *)work, prm, st, (hipStream_t)stream);
+    return hipk_pcg_solve_t<float>(A, (const float *)dinv, (const float *)b, (float *)x, (char *)work, prm, st, (hipStream_t)stream);
 }
 
 // =====================================================================================================================
@@ -2239,9 +2195,8 @@ extern "C" int hipk_dist_pcg_solve(hipk_csr_t A, const hipk_dist_plan *pl, const
     const int64_t n = pl->n_local, n_ext = pl->n_ext;
     const int ch = pl->chunk_rows, G = pl->g_red;
     const int grid = (int)((n + ch - 1) / ch), grid_ext = (int)((n_ext + ch - 1) / ch);
-    const int64_t maxiter = (prm->maxiter < 0) ? 10 * pl->n_global : prm->maxiter;   // TSL:982-984
-    const float tolf = (float)prm->tol, atolf = (float)prm->atol;
-    const double tol2 = (double)(tolf * tolf), atol_sq = (double)(atolf * atolf);
+    const int64_t maxiter = hipk_default_maxiter(prm, pl->n_global);
+    const hipk_tol_sq tol(prm);
     const int64_t *stop_dev = &scal->stop_it;
     const hipk_dist_xchg xc(pl, cc, stream, (double *)(wk + L.send_buf), (double *)(wk + L.slab_loc), (double *)(wk + L.slab_all),
                             "hipk_dist_pcg_solve");
@@ -2258,7 +2213,7 @@ extern "C" int hipk_dist_pcg_solve(hipk_csr_t A, const hipk_dist_plan *pl, const
     HIPK_TRY(xc.parts(part_loc, g_rr));
     HIPK_TRY(hipk_dot_parts(n, ch, b, b, HIPK_F64, part_loc, stream));
     HIPK_TRY(xc.parts(part_loc, g_bb));
-    hipk_pcg_start_kernel<T><<<grid, HIPK_THREADS, 0, stream>>>(n, ch, G, scal, g_rr, g_bb, r, dinv, p, part_rz, tol2, atol_sq,
+    hipk_pcg_start_kernel<T><<<grid, HIPK_THREADS, 0, stream>>>(n, ch, G, scal, g_rr, g_bb, r, dinv, p, part_rz, tol.tol2, tol.atol_sq,
                                                                  maxiter, nullptr);
     HIPK_CHECK_HIP(hipGetLastError());
     HIPK_TRY(xc.run(p, part_rz, g_rz[0]));

@@ -18,8 +18,8 @@
 // device; their collectives still pair up).  The RCCL entry points come in as function pointers resolved from the
 // librccl that created the communicator (no link-time dependency; tests plug host-staged stand-ins in).
 //
-// The exchanges, the batch loop and the workspace carver are shared with the other five row-partitioned loops (csrc/
-// hipk_dist_xchg.h); their argument checks, hipk_dist_check, are defined here.
+// The exchanges and the batch loop are shared with the other five row-partitioned loops (csrc/hipk_dist_xchg.h), the workspace
+// carver with every solve (csrc/hipk_solve.h); their argument checks, hipk_dist_check, are defined here.
 #include <stdlib.h>
 
 #include "hipk_dist_xchg.h"
@@ -95,7 +95,7 @@ extern "C" int hipk_dist_cg_solve(hipk_csr_t A, const hipk_dist_plan *pl, const 
     const int64_t n = pl->n_local, n_ext = pl->n_ext;
     const int ch = pl->chunk_rows, G = pl->g_red, per = pl->per, W = pl->world;
     const int64_t *stop_dev = (const int64_t *)((char *)scal + 48);   // hipk_cg_scal::stop_it
-    const int64_t maxiter = (prm->maxiter < 0) ? 10 * pl->n_global : prm->maxiter;   // TSL:982-984
+    const int64_t maxiter = hipk_default_maxiter(prm, pl->n_global);
     const hipk_dist_xchg xc(pl, cc, stream, (double *)(wk + L.send_buf), (double *)(wk + L.slab_loc), (double *)(wk + L.slab_all),
                             "hipk_dist_cg_solve");
 

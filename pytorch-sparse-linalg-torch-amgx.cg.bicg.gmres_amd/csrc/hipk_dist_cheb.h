@@ -97,14 +97,7 @@ struct hipk_dcheb {
     // where z_0 goes: z_k lives in z_out when m - k is even (one launch per step), always (two)
     double *z_start() const { return (fused && (m & 1)) ? z_alt : z_out; }
     hipk_spmv_args args(const double *r) const {
-        hipk_spmv_args a;
-        memset(&a, 0, sizeof(a));
-        a.crow = A->crow;
-        a.col = A->col;
-        a.val = A->val;
-        a.n = A->n_rows;
-        a.ch = A->geom.ch;
-        a.g = A->geom.g;
+        hipk_spmv_args a = hipk_spmv_base(A);
         a.bsub = r;
         a.dscale = dinv;
         a.cheb_d = d;
@@ -270,7 +263,7 @@ extern "C" int hipk_dist_chebcg_solve(hipk_csr_t A, const hipk_dist_plan *pl, co
     const int64_t n = pl->n_local, n_ext = pl->n_ext;
     const int ch = pl->chunk_rows, G = pl->g_red;
     const int grid = (int)((n + ch - 1) / ch);
-    const int64_t maxiter = (prm->maxiter < 0) ? 10 * pl->n_global : prm->maxiter;   // TSL:982-984
+    const int64_t maxiter = hipk_default_maxiter(prm, pl->n_global);
     const int64_t *stop_dev = &scal->stop_it;
     const hipk_dist_xchg xc(pl, cc, stream, (double *)(wk + L.send_buf), (double *)(wk + L.slab_loc), (double *)(wk + L.slab_all),
                             "hipk_dist_chebcg_solve");

@@ -1,6 +1,6 @@
 // hipk_dist_xchg.h -- host side shared by the six row-partitioned loops (hipk_dist_{,p}cg_solve, hipk_dist_{,p}bicgstab_solve,
 // hipk_dist_{,p}gmres_solve): every collective call of one rank through the hipk_rccl entry points, the argument checks, the
-// workspace carver, the batch driver and the SpMV with a row scaling.
+// batch driver and the SpMV with a row scaling.
 //
 // The conventions are those of hipk_dist_cg_solve (csrc/hipk_dist.hip): partials are all-gathered in rank (= global chunk)
 // order, the halo of a vector lands in its tail v[n_local .. n_ext) (neighbour send/recv pairs, or an all-gather of padded
@@ -10,16 +10,6 @@
 #include "hipk_common.h"
 #include "hipk_solve.h"
 #include "hipk_spmv.h"
-
-// workspace carver: consecutive 256-byte aligned pieces; .o is the size so far
-struct hipk_carve {
-    size_t o = 0;
-    size_t operator()(size_t bytes) {
-        const size_t at = o;
-        o += hipk_align_up(bytes, 256);
-        return at;
-    }
-};
 
 struct hipk_dist_xchg {
     const hipk_dist_plan *pl;
@@ -129,16 +119,9 @@ static int hipk_dist_batches(const hipk_params *prm, int64_t *host_poll, const i
 static inline int hipk_dist_spmv(const hipk_csr_s *h, const void *x, void *y, int mode, const void *w, const void *bsub,
                                  const void *dscale, double *part0, double *part1, const int64_t *stop_dev, int64_t it,
                                  hipStream_t stream) {
-    hipk_spmv_args a;
-    memset(&a, 0, sizeof(a));
-    a.crow = h->crow;
-    a.col = h->col;
-    a.val = h->val;
+    hipk_spmv_args a = hipk_spmv_base(h);
     a.x = x;
     a.y = y;
-    a.n = h->n_rows;
-    a.ch = h->geom.ch;
-    a.g = h->geom.g;
     a.mode = mode | (dscale ? HIPK_SPMV_SCALE : 0);
     a.w = w;
     a.bsub = bsub;

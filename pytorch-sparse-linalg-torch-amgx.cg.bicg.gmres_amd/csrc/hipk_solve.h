@@ -263,6 +263,44 @@ struct hipk_pacer {
 
 static inline size_t hipk_align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// workspace carver: consecutive 256-byte aligned pieces; .o is the size so far
+struct hipk_carve {
+    size_t o = 0;
+    size_t operator()(size_t bytes) {
+        const size_t at = o;
+        o += hipk_align_up(bytes, 256);
+        return at;
+    }
+};
+// the piece of a workspace that a layout put at byte `off`
+template <typename U>
+static inline U *hipk_at(char *work, size_t off) { return (U *)(work + off); }
+
+// `_isolve`'s default iteration limit on the GLOBAL size (TSL:982-984)
+static inline int64_t hipk_default_maxiter(const hipk_params *prm, int64_t n_global) { return prm->maxiter < 0 ? 10 * n_global : prm->maxiter; }
+// torch.square(torch.tensor(tol)): python floats become fp32 tensors, squared in fp32 (TSL:816-817)
+struct hipk_tol_sq {
+    double tol2, atol_sq;
+    hipk_tol_sq(double tol, double atol) : tol2((double)((float)tol * (float)tol)), atol_sq((double)((float)atol * (float)atol)) {}
+    explicit hipk_tol_sq(const hipk_params *prm) : hipk_tol_sq(prm->tol, prm->atol) {}
+};
+
+// The argument checks of the single-device entries hipk_cg_solve, hipk_pcg_solve, hipk_bicgstab_solve, hipk_pbicgstab_solve and
+// hipk_pbicgstab_solve_cb; clears *st.  have_m: the entry's dinv or M is not null (an entry without one: true); dinv: checked for
+// alignment where the entry has one, else null; need: the entry's *_work_bytes
+static inline int hipk_solve_check(const hipk_csr_s *A, bool have_m, const void *dinv, const void *b, const void *x, const void *work,
+                                   size_t work_bytes, size_t (*need)(int64_t, int), const hipk_params *prm, hipk_stats *st) {
+    HIPK_REQUIRE(A && have_m && b && x && work && prm && st, HIPK_ERR_ARG, "null argument");
+    HIPK_REQUIRE(A->n_rows == A->n_cols, HIPK_ERR_ARG, "linear operator must be a square matrix");
+    HIPK_REQUIRE(A->n_rows > 0, HIPK_ERR_ARG, "empty system");
+    HIPK_REQUIRE(hipk_aligned16(b) && hipk_aligned16(x) && hipk_aligned16(dinv) && (((uintptr_t)work) & 255u) == 0, HIPK_ERR_ALIGN,
+                 dinv ? "b/x/dinv must be 16-byte and work 256-byte aligned" : "b/x must be 16-byte and work 256-byte aligned");
+    HIPK_REQUIRE(work_bytes >= need(A->n_rows, A->dtype), HIPK_ERR_WORKSPACE, "work too small");
+    HIPK_REQUIRE(b != x, HIPK_ERR_ARG, "b and x must not alias");
+    memset(st, 0, sizeof(*st));
+    return HIPK_OK;
+}
+
 // torch.maximum semantics (NaN wins).
 static inline double hipk_tmax(double a, double b) {
     if (isnan(a) || isnan(b)) return NAN;

@@ -77,6 +77,18 @@ struct hipk_spmv_args {
     void *cheb_d;           // HIPK_SPMV_CHEB: the direction vector d, updated in place (each row by its own lane)
     double cheb_c1, cheb_c2, cheb_scale;  //   this step's coefficients; scale = 1 except in the last step
 };
+// what every SpMV on the handle's matrix has in common: its arrays and the reduction geometry of its rows; all else zero
+static inline hipk_spmv_args hipk_spmv_base(const hipk_csr_s *h) {
+    hipk_spmv_args a;
+    memset(&a, 0, sizeof(a));
+    a.crow = h->crow;
+    a.col = h->col;
+    a.val = h->val;
+    a.n = h->n_rows;
+    a.ch = h->geom.ch;
+    a.g = h->geom.g;
+    return a;
+}
 
 #ifdef __HIPCC__
 #define HIPK_TILE 256
