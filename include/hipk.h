@@ -265,6 +265,29 @@ int hipk_cg_solve_multi(hipk_csr_t A, const void *dinv, int k, const void *B, in
 int hipk_bicgstab_solve_multi(hipk_csr_t A, const void *dinv, int k, const void *B, int64_t ldb, void *X, int64_t ldx, void *work,
                               size_t work_bytes, const hipk_params *prm, hipk_stats *st, int64_t *block_spmvs,
                               hipk_stream_t stream);
+/* ---- many small systems: S independent systems with ONE sparsity pattern, one workgroup per system (csrc/hipk_batch.hip) ----
+ * System s has the shared pattern crow_dev[n + 1] / col_dev[nnz] (int32, device), the values vals + s * ldv, the right-hand side
+ * B + s * ldb and x0 / the solution in X + s * ldx (device arrays of `dtype`; ldv >= nnz, ldb, ldx >= n); dinv is NULL (M = identity)
+ * or the Jacobi vectors dinv + s * ldd.  Row s of the result and st[s] (st: `batch` entries) are bit for bit hipk_cg_solve /
+ * hipk_pcg_solve (hipk_bicgstab_solve / hipk_pbicgstab_solve) of system s: the same params (tol through fp32, maxiter < 0 = 10 n),
+ * the same stats, every system stopping -- or breaking down -- at its own iteration.  One launch of hipk_cg_batch_kernel<T, PRE> /
+ * hipk_bi_batch_kernel<T, PRE> runs every system's whole solve including the true residual and `info`; a launch runs at most
+ * HIPK_BATCH_LAUNCH_ITS iterations per system and the next one resumes the unfinished systems (same bits for any budget).
+ * Envelope: n <= 4096 and at most 32 stored entries per row, else HIPK_ERR_UNSUPPORTED.  Row starts must be 16-byte aligned
+ * (vals, B, X, dinv aligned and ld * sizeof(T) a multiple of 16), else HIPK_ERR_ALIGN; elements of a row beyond nnz or n are
+ * never read or written.  A call that returns an error has written nothing, `work` included (the row bound is checked on the
+ * host from a copy of crow_dev).  `work`: hipk_batch_work_bytes, 256-byte aligned, the workspace contract above.  No handle is needed
+ * and no handle scratch is used.  hipk_last_solve_path() and hipk_last_solve_form() report the kernel, e.g.
+ * "hipk_cg_batch_kernel<double,false>"; hipk_last_batch_launches() the launches the calling thread's last batch solve took. */
+size_t hipk_batch_work_bytes(int64_t n, int64_t nnz, int batch, int dtype, int solver /* 0 cg, 1 bicgstab */, int precond);
+int hipk_cg_solve_batch(int64_t n, int64_t nnz, const int32_t *crow_dev, const int32_t *col_dev, const void *vals, int64_t ldv,
+                        const void *dinv /* NULL: M = identity */, int64_t ldd, int batch, const void *B, int64_t ldb, void *X,
+                        int64_t ldx, int dtype, void *work, size_t work_bytes, const hipk_params *prm, hipk_stats *st /* batch entries */,
+                        hipk_stream_t stream);
+int hipk_bicgstab_solve_batch(int64_t n, int64_t nnz, const int32_t *crow_dev, const int32_t *col_dev, const void *vals, int64_t ldv,
+                              const void *dinv, int64_t ldd, int batch, const void *B, int64_t ldb, void *X, int64_t ldx, int dtype,
+                              void *work, size_t work_bytes, const hipk_params *prm, hipk_stats *st, hipk_stream_t stream);
+int hipk_last_batch_launches(void);
 /* Placement probe for systems whose vectors live in HBM (N >> 8 M rows): the memory shape of the CG direction step (reads r, p, x;
  * writes p, x) on the three vectors, storing back the bits it loaded (safe on live data); *us_out = the fastest of `reps` (<= 16)
  * timed passes in microseconds.  40 n bytes (fp64) per pass.  On MI355X such a step runs at one of two discrete speeds depending on

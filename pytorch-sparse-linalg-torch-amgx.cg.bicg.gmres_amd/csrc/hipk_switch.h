@@ -75,6 +75,8 @@ static constexpr hipk_sw_row hipk_switches[] = {
     {"HIPK_GM_NRES", HIPK_SW_INT, "5", "each GMRES solve", "k: basis columns read with the default cache policy, the rest non-temporal (no clamp)", "test, tools A/B"},
     {"HIPK_GM_SPEC", HIPK_SW_INT, "1", "each GMRES solve", "second CGS pass launched at every step (0), where predicted (1), or learned from scratch (2)", "test, tools A/B"},
     {"HIPK_GM_STAMPS", HIPK_SW_PRESENT, "off", "each launch and the end of a small-system GMRES solve", "stamps build only: print the per-phase shader clocks of the cycle kernels", "tools A/B"},
+    // ---- many small systems (hipk_batch.hip)
+    {"HIPK_BATCH_LAUNCH_ITS", HIPK_SW_INT, "16384", "each batch solve", "k: iterations per system one launch of a batch kernel may run, at least 1", "test"},
     // ---- row-partitioned CG (hipk_dist.hip)
     {"HIPK_DIST_OVERLAP", HIPK_SW_INT, "0", "each hipk_dist_cg_solve", "nonzero: x += alpha p on a side stream beside the second collective; measured slower", "test"},
     {"HIPK_DIST_FUSED", HIPK_SW_OFF_IF_0, "on", "each hipk_dist_cg_solve", "0: the collective entry points also on a communicator with a fused area", "user"},

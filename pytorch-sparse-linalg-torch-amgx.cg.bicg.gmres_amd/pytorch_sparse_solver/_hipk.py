@@ -56,6 +56,8 @@ SYMBOLS = [
     "hipk_p2p_group_start", "hipk_p2p_group_end", "hipk_p2p_all_gather",
     # many right-hand sides per matrix read
     "hipk_multi_work_bytes", "hipk_cg_solve_multi", "hipk_bicgstab_solve_multi",
+    # many small systems with one sparsity pattern, one workgroup per system
+    "hipk_batch_work_bytes", "hipk_cg_solve_batch", "hipk_bicgstab_solve_batch", "hipk_last_batch_launches",
 ]
 
 
@@ -274,6 +276,11 @@ def lib():
     for name in ("cg", "bicgstab"):
         getattr(L, f"hipk_{name}_solve_multi").argtypes = [vp, vp, i32, vp, i64, vp, i64, vp, ctypes.c_size_t, ctypes.POINTER(Params),
                                                           ctypes.POINTER(Stats), ctypes.POINTER(i64), vp]
+    L.hipk_batch_work_bytes.argtypes = [i64, i64, i32, i32, i32, i32]
+    L.hipk_batch_work_bytes.restype = ctypes.c_size_t
+    for name in ("cg", "bicgstab"):
+        getattr(L, f"hipk_{name}_solve_batch").argtypes = [i64, i64, vp, vp, vp, i64, vp, i64, i32, vp, i64, vp, i64, i32, vp,
+                                                          ctypes.c_size_t, ctypes.POINTER(Params), ctypes.POINTER(Stats), vp]
     _lib = L
     return L
 
@@ -815,6 +822,69 @@ def solve_multi(method: str, h: CsrHandle, dinv: Optional[torch.Tensor], B: torc
                        recurrence_rs=c.recurrence_rs, solve_ms=c.solve_ms, spmv_ms_avg=0.0, spmv_profiled=0) for c in st]
     ms = sum(st[j].solve_ms for j in range(0, k, MULTI_MAX_BLOCK))
     return MultiSolveStats(method=f"{method}_multi", columns=cols, block_spmvs=int(spmvs.value), solve_ms=ms)
+
+
+@dataclass
+class BatchSolveStats:
+    """Side channel of cg_batch / bicgstab_batch: per-system lists (one entry per system), the path that ran
+    (`hipk_last_solve_path` of the batch kernel, or "loop"), the kernel launches the solve took (0 on the loop route) and its time."""
+    method: str
+    iterations: list
+    matvecs: list
+    info: list
+    breakdown: list
+    b_norm: list
+    residual_norm: list
+    x_norm: list
+    threshold: list
+    recurrence_rs: list
+    path: str
+    launches: int
+    solve_ms: float
+
+
+BATCH_MAX_N = 4096      # the envelope of hipk_{cg,bicgstab}_solve_batch: rows per system ...
+BATCH_MAX_ROW = 32      # ... and stored entries per row
+
+
+def batch_work_bytes(n: int, nnz: int, batch: int, dtype: torch.dtype, method: str, precond: bool) -> int:
+    """hipk_batch_work_bytes (pure host code: callable without a GPU)."""
+    return int(lib().hipk_batch_work_bytes(int(n), int(nnz), int(batch), _dtype_code(dtype), 0 if method == "cg" else 1,
+                                           1 if precond else 0))
+
+
+def solve_batch(method: str, n: int, nnz: int, crow: torch.Tensor, col: torch.Tensor, vals: torch.Tensor, dinv: Optional[torch.Tensor],
+                B: torch.Tensor, X: torch.Tensor, *, tol: float, atol: float, maxiter: Optional[int],
+                work: Optional[torch.Tensor] = None) -> BatchSolveStats:
+    """hipk_{cg,bicgstab}_solve_batch: crow (n + 1,), col (nnz,) int32; vals (S, ldv), B (S, ldb), X (S, ldx), dinv None or
+    (S, ldd), row-major with unit inner stride, of one dtype on one device; X holds X0 on entry and the solutions on return."""
+    S = int(B.shape[0])
+    dev = B.device
+    for t in (vals, B, X) + (() if dinv is None else (dinv,)):
+        assert t.dim() == 2 and t.shape[0] == S and t.stride(1) == 1 and t.dtype == B.dtype and t.device == dev
+    assert crow.dtype == torch.int32 and col.dtype == torch.int32 and crow.is_contiguous() and col.is_contiguous()
+    assert crow.numel() == n + 1 and col.numel() == nnz and crow.device == dev and col.device == dev
+    prm = Params()
+    prm.tol, prm.atol = float(tol), float(atol)
+    prm.maxiter = -1 if maxiter is None else int(maxiter)
+    prm.gpu_tolerances = 1
+    L = lib()
+    wb = batch_work_bytes(n, nnz, S, B.dtype, method, dinv is not None)
+    work = _workspace(work, dev, wb)
+    st = (Stats * S)()
+    ld = lambda t: int(t.stride(0))
+    with torch.cuda.device(dev):
+        rc = getattr(L, f"hipk_{method}_solve_batch")(n, nnz, crow.data_ptr(), col.data_ptr(), vals.data_ptr(), ld(vals),
+                                                      None if dinv is None else dinv.data_ptr(), 0 if dinv is None else ld(dinv), S,
+                                                      B.data_ptr(), ld(B), X.data_ptr(), ld(X), _dtype_code(B.dtype), work.data_ptr(),
+                                                      wb, ctypes.byref(prm), st, _stream(dev))
+    _check(rc, f"hipk_{method}_solve_batch")
+    name = method if dinv is None else {"cg": "pcg_jacobi", "bicgstab": "pbicgstab_jacobi"}[method]
+    col_of = lambda f: [getattr(c, f) for c in st]
+    return BatchSolveStats(method=f"{name}_batch", iterations=col_of("iterations"), matvecs=col_of("matvecs"), info=col_of("info"),
+                           breakdown=col_of("breakdown"), b_norm=col_of("b_norm"), residual_norm=col_of("residual_norm"),
+                           x_norm=col_of("x_norm"), threshold=col_of("threshold"), recurrence_rs=col_of("recurrence_rs"),
+                           path=last_solve_path(), launches=int(L.hipk_last_batch_launches()), solve_ms=float(st[0].solve_ms))
 
 
 def solve_pgmres(h: CsrHandle, dinv: torch.Tensor, b: torch.Tensor, x: torch.Tensor, *, tol: float, atol: float,

@@ -1,0 +1,237 @@
+"""cg_batch / bicgstab_batch: S independent small systems that share ONE sparsity pattern.
+
+`X[s]`, `info[s]` and the per-system statistics are what `cg(A_s, B[s], X0[s], ...)` (or `bicgstab`) returns for the CSR tensor A_s
+of system s, bit for bit.  Two routes compute them:
+
+  'kernel'  the batch kernels of libhipk.so (csrc/hipk_batch.hip): one 256-thread workgroup owns one system for its whole solve,
+            a launch covers all S systems.  Device operands, n <= 4096, at most 32 stored entries per row.
+  'loop'    one public single solve per system: every input the single solvers accept, CPU tensors included.
+  'auto'    the kernel for device operands inside its envelope when S >= BATCH_MIN_SYSTEMS, else the loop.
+"""
+from __future__ import annotations
+
+import time
+from typing import Optional, Sequence, Tuple
+
+import torch
+
+from .preconditioners import JacobiPreconditioner
+from .torch_sparse_linalg import _set_stats, bicgstab, cg, get_last_stats
+
+# The smallest S at which 'auto' takes the batch kernels: the measured crossover (tools/batch_probe.py, profiles/batch_probe.txt;
+# DESIGN.md 7c).  One system alone is slower in the kernel than in the single solve's one-launch loop from n = 1024 on (0.26-0.8x:
+# one workgroup against 8 to 32) and still at S = 4 for n = 4096 (0.50x); at S = 8 the kernel is level at worst (cg, n = 4096:
+# 0.98x) and 2-8.4x ahead elsewhere, from S = 64 on 16-900x.
+BATCH_MIN_SYSTEMS = 8
+
+
+def _aligned_rows(t: torch.Tensor) -> bool:
+    """Rows of a 2-D tensor start 16-byte aligned and are contiguous inside."""
+    es = t.element_size()
+    return t.stride(1) == 1 and t.data_ptr() % 16 == 0 and (t.stride(0) * es) % 16 == 0 and t.stride(0) >= t.shape[1]
+
+
+def _pad_rows(t: torch.Tensor) -> torch.Tensor:
+    """`t` itself when its rows are aligned already, else a copy with the leading dimension rounded up to 16 bytes."""
+    if _aligned_rows(t):
+        return t
+    per = 16 // t.element_size()
+    ld = (t.shape[1] + per - 1) // per * per
+    buf = torch.zeros((t.shape[0], ld), dtype=t.dtype, device=t.device)
+    buf[:, :t.shape[1]] = t
+    return buf[:, :t.shape[1]]
+
+
+class BatchedCSR:
+    """S square CSR matrices with one pattern: crow (n + 1,), col (nnz,) shared, values (S, nnz) (fp64 or fp32), on one device.
+    Rows may be unsorted, hold a column twice or a stored zero, as everywhere in this library."""
+
+    def __init__(self, crow: torch.Tensor, col: torch.Tensor, values: torch.Tensor):
+        for name, t in (("crow", crow), ("col", col), ("values", values)):
+            if not isinstance(t, torch.Tensor):
+                raise ValueError(f"BatchedCSR: {name} must be a tensor")
+        if crow.dim() != 1 or crow.numel() < 2 or col.dim() != 1 or values.dim() != 2:
+            raise ValueError("BatchedCSR: crow must have shape (n + 1,), col (nnz,) and values (S, nnz)")
+        if crow.dtype.is_floating_point or col.dtype.is_floating_point:
+            raise ValueError("BatchedCSR: crow and col must be integer tensors")
+        if values.dtype not in (torch.float64, torch.float32):
+            raise ValueError(f"BatchedCSR: values must be float64 or float32, got {values.dtype}")
+        if values.shape[0] < 1 or values.shape[1] != col.numel():
+            raise ValueError(f"BatchedCSR: values must have shape (S, nnz) with S >= 1 and nnz = {col.numel()}, got {tuple(values.shape)}")
+        if not (crow.device == col.device == values.device):
+            raise ValueError("BatchedCSR: crow, col and values must be on one device")
+        if values.requires_grad:
+            raise ValueError("BatchedCSR: the batch solves are not differentiable")
+        if int(crow[0]) != 0 or int(crow[-1]) != col.numel() or bool((crow[1:] < crow[:-1]).any()):
+            raise ValueError("BatchedCSR: crow is not a row pointer array of nnz entries")
+        n = crow.numel() - 1
+        if col.numel() and (int(col.min()) < 0 or int(col.max()) >= n):
+            raise ValueError("BatchedCSR: a column index is outside [0, n)")
+        self.crow, self.col, self.values = crow, col, values
+        self.n, self.nnz, self.batch = n, int(col.numel()), int(values.shape[0])
+        self.shape = (self.batch, n, n)
+        self.max_row_len = int((crow[1:] - crow[:-1]).max()) if n else 0
+        # indices narrowed once (the kernels and the Jacobi diagonal read these)
+        self.crow32 = crow.to(torch.int32).contiguous()
+        self.col32 = col.to(torch.int32).contiguous()
+        self._kernel_values = None
+
+    @property
+    def device(self):
+        return self.values.device
+
+    @property
+    def dtype(self):
+        return self.values.dtype
+
+    @classmethod
+    def from_csr_list(cls, mats: Sequence[torch.Tensor]) -> "BatchedCSR":
+        mats = list(mats)
+        if not mats:
+            raise ValueError("BatchedCSR.from_csr_list: empty list")
+        for A in mats:
+            if not (isinstance(A, torch.Tensor) and A.layout == torch.sparse_csr and A.dim() == 2 and A.shape[0] == A.shape[1]):
+                raise ValueError("BatchedCSR.from_csr_list: every matrix must be a square torch CSR tensor")
+        crow, col = mats[0].crow_indices(), mats[0].col_indices()
+        for s, A in enumerate(mats[1:], 1):
+            if A.shape != mats[0].shape or A.dtype != mats[0].dtype or A.device != mats[0].device:
+                raise ValueError(f"BatchedCSR.from_csr_list: matrix {s} differs from matrix 0 in shape, dtype or device")
+            if not (torch.equal(A.crow_indices(), crow) and torch.equal(A.col_indices(), col)):
+                raise ValueError(f"BatchedCSR.from_csr_list: matrix {s} does not share the sparsity pattern (crow / col) of matrix 0")
+        return cls(crow, col, torch.stack([A.values() for A in mats]))
+
+    def system(self, s: int) -> torch.Tensor:
+        """The CSR tensor A_s (its values a copy when row s of `values` does not start 16-byte aligned, as the single solves need)."""
+        v = self.values[s]
+        return torch.sparse_csr_tensor(self.crow, self.col, v.clone() if v.data_ptr() % 16 else v, size=(self.n, self.n))
+
+    def kernel_values(self) -> torch.Tensor:
+        """`values` with 16-byte aligned rows: `values` itself, or a padded copy that is made again whenever `values` was written to
+        (keyed on its address and version counter, as the handle cache of the single solves is)."""
+        key = (self.values.data_ptr(), self.values._version)
+        if self._kernel_values is None or self._kernel_values[0] != key:
+            self._kernel_values = (key, _pad_rows(self.values))
+        return self._kernel_values[1]
+
+    def in_envelope(self) -> bool:
+        from .. import _hipk
+        return 1 <= self.n <= _hipk.BATCH_MAX_N and self.max_row_len <= _hipk.BATCH_MAX_ROW
+
+
+class BatchedJacobiPreconditioner:
+    """M_s(v) = v / diag(A_s) for every system of a BatchedCSR: `dinv` (S, n), row s bitwise `JacobiPreconditioner(A_s).dinv`."""
+
+    def __init__(self, A: BatchedCSR):
+        if not isinstance(A, BatchedCSR):
+            raise ValueError("BatchedJacobiPreconditioner needs a BatchedCSR")
+        n = A.n
+        rows = torch.repeat_interleave(torch.arange(n, device=A.device), A.crow[1:] - A.crow[:-1])
+        on = A.col == rows
+        d = torch.zeros((A.batch, n), dtype=A.dtype, device=A.device)
+        d.index_add_(1, rows[on], A.values[:, on])          # duplicate diagonal entries add, as in A @ e_i
+        if bool((d == 0).any()):
+            raise ValueError("BatchedJacobiPreconditioner: zero on the diagonal")
+        self.dinv = torch.reciprocal(d)
+        self.shape = A.shape
+
+    def system(self, s: int) -> JacobiPreconditioner:
+        J = JacobiPreconditioner.__new__(JacobiPreconditioner)
+        d = self.dinv[s]
+        J.dinv = d.clone() if d.data_ptr() % 16 else d
+        J.shape = (self.shape[1], self.shape[2])
+        return J
+
+
+def _check(name, A, B, X0, M, route):
+    if not isinstance(A, BatchedCSR):
+        raise ValueError(f"{name}: A must be a BatchedCSR")
+    if route not in ("auto", "kernel", "loop"):
+        raise ValueError(f"{name}: route must be 'auto', 'kernel' or 'loop', got {route!r}")
+    for what, t in (("B", B), ("X0", X0)):
+        if t is None and what == "X0":
+            continue
+        if not isinstance(t, torch.Tensor) or t.dim() != 2 or tuple(t.shape) != (A.batch, A.n):
+            raise ValueError(f"{name}: {what} must have shape (S, n) = ({A.batch}, {A.n}), got {tuple(getattr(t, 'shape', ()))}")
+        if torch.is_complex(t) or not t.dtype.is_floating_point:
+            raise ValueError(f"{name}: {what} must be a real floating-point tensor, got {t.dtype}")
+        if t.device != A.device:
+            raise ValueError(f"{name}: {what} is on {t.device}, the matrices on {A.device}")
+        if t.dtype != A.dtype:
+            raise ValueError(f"{name}: {what} is {t.dtype}, the matrices are {A.dtype}")
+        if t.requires_grad:
+            raise ValueError(f"{name} is not differentiable: call {name.split('_')[0]}_differentiable on each system instead")
+    if M is not None:
+        if not isinstance(M, BatchedJacobiPreconditioner):
+            raise ValueError(f"{name}: M must be None or a BatchedJacobiPreconditioner, got {type(M).__name__}")
+        if tuple(M.shape) != tuple(A.shape) or M.dinv.device != A.device:
+            raise ValueError(f"{name}: the preconditioner (shape {tuple(M.shape)}, {M.dinv.device}) does not match A "
+                             f"(shape {tuple(A.shape)}, {A.device})")
+
+
+def _kernel_solve(kind, A: BatchedCSR, B, X0, tol, atol, maxiter, M):
+    from .. import _hipk
+    dt = A.dtype                                  # fp64, or fp32 storage when the matrices are fp32 (as the single solves)
+    BB = _pad_rows(B.detach().to(dt))
+    if X0 is None:
+        X = _pad_rows(torch.zeros((A.batch, A.n), dtype=dt, device=A.device))
+    else:
+        X = X0.detach().to(dt).clone()
+        if not _aligned_rows(X):
+            X = _pad_rows(X)
+    dinv = None if M is None else _pad_rows(M.dinv.detach().to(dt))
+    st = _hipk.solve_batch(kind, A.n, A.nnz, A.crow32, A.col32, A.kernel_values(), dinv, BB, X, tol=tol, atol=atol, maxiter=maxiter)
+    return X.contiguous(), st
+
+
+def _loop_solve(kind, A: BatchedCSR, B, X0, tol, atol, maxiter, M):
+    from .. import _hipk
+    solver = cg if kind == "cg" else bicgstab
+    xs, infos, stats = [], [], []
+    t0 = time.perf_counter()
+    for s in range(A.batch):
+        x, info = solver(A.system(s), B[s].clone(), None if X0 is None else X0[s].clone(), tol=tol, atol=atol, maxiter=maxiter,
+                          M=None if M is None else M.system(s))
+        xs.append(x)
+        infos.append(int(info))
+        stats.append(get_last_stats())
+    ms = (time.perf_counter() - t0) * 1e3
+    f = lambda name, default: [getattr(c, name, default) if c is not None else default for c in stats]
+    name = kind if M is None else {"cg": "pcg_jacobi", "bicgstab": "pbicgstab_jacobi"}[kind]
+    st = _hipk.BatchSolveStats(method=f"{name}_batch", iterations=f("iterations", 0), matvecs=f("matvecs", 0), info=infos,
+                               breakdown=f("breakdown", 0), b_norm=f("b_norm", 0.0), residual_norm=f("residual_norm", 0.0),
+                               x_norm=f("x_norm", 0.0), threshold=f("threshold", 0.0), recurrence_rs=f("recurrence_rs", 0.0),
+                               path="loop", launches=0, solve_ms=ms)
+    return torch.stack(xs), st
+
+
+def _batch(kind: str, A, B, X0, tol, atol, maxiter, M, route):
+    name = f"{kind}_batch"
+    _check(name, A, B, X0, M, route)
+    on_device = A.values.is_cuda
+    if route == "kernel":
+        if not on_device:
+            raise ValueError(f"{name}: route='kernel' needs device tensors (A is on {A.device}); use route='loop'")
+        if not A.in_envelope():
+            raise ValueError(f"{name}: route='kernel' takes systems of at most 4096 rows with at most 32 stored entries per row "
+                             f"(n = {A.n}, longest row {A.max_row_len}); use route='loop'")
+    use_kernel = route == "kernel" or (route == "auto" and on_device and A.in_envelope() and A.batch >= BATCH_MIN_SYSTEMS)
+    X, st = (_kernel_solve if use_kernel else _loop_solve)(kind, A, B, X0, tol, atol, maxiter, M)
+    _set_stats(st)
+    return X, torch.tensor([int(i) for i in st.info], dtype=torch.int64)
+
+
+def cg_batch(A: BatchedCSR, B: torch.Tensor, X0: Optional[torch.Tensor] = None, *, tol: float = 1e-5, atol: float = 0.0,
+             maxiter: Optional[int] = None, M: Optional[BatchedJacobiPreconditioner] = None,
+             route: str = "auto") -> Tuple[torch.Tensor, torch.Tensor]:
+    """Conjugate gradients for the S systems A_s X[s] = B[s], B of shape (S, n).
+
+    Returns `(X, info)`: X of shape (S, n), info a 1-D int64 CPU tensor of length S with `info[s]` = the info of
+    `cg(A_s, B[s], X0[s], ...)`.  `get_last_stats()` is then a `BatchSolveStats`.  Not differentiable."""
+    return _batch("cg", A, B, X0, tol, atol, maxiter, M, route)
+
+
+def bicgstab_batch(A: BatchedCSR, B: torch.Tensor, X0: Optional[torch.Tensor] = None, *, tol: float = 1e-5, atol: float = 0.0,
+                   maxiter: Optional[int] = None, M: Optional[BatchedJacobiPreconditioner] = None,
+                   route: str = "auto") -> Tuple[torch.Tensor, torch.Tensor]:
+    """BiCGStab for the S systems A_s X[s] = B[s] (see `cg_batch`); breakdowns (-10, -11) are decided per system."""
+    return _batch("bicgstab", A, B, X0, tol, atol, maxiter, M, route)
