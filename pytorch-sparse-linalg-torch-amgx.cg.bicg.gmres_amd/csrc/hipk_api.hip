@@ -599,8 +599,15 @@ extern "C" int64_t hipk_csr_format_bytes(hipk_csr_t h) {
 // ------------------------------------------------------------------ SpMV launch
 // CAP (LDS product slots per tile): 1280 = 256 rows x 5 nnz, the 5-point stencil's tile, and it keeps the
 // workgroup at 11 KB LDS => 8 workgroups per CU.  Denser tiles take the kernel's general path.
-int hipk_launch_spmv(const hipk_csr_s *h, const hipk_spmv_args &a_, hipStream_t stream, hipk_spmv_profiler *prof) {
+// resolve (hipk_spmv_resolves_wide_chunk): nothing is launched; HIPK_SPMV_IS_WIDE_CHUNK and *resolve = the kernel's arguments when
+// the launch would be the chunk walk of hipk_spmv_sell_wide_kernel, else HIPK_SPMV_NOT_WIDE_CHUNK.  The kernel note is the launch's.
+#define HIPK_SPMV_IS_WIDE_CHUNK 1001
+#define HIPK_SPMV_NOT_WIDE_CHUNK 1002
+static int hipk_launch_spmv_(const hipk_csr_s *h, const hipk_spmv_args &a_, hipStream_t stream, hipk_spmv_profiler *prof, hipk_spmv_args *resolve) {
     hipk_spmv_args a = a_;
+    if (resolve && (h->op_cb != nullptr || h->n_rows <= 0 || h->nnz / h->n_rows >= 48 || h->n_huge > 0 || h->n_codes <= 0 || h->path_override == 1 ||
+                    h->coded_layout < 2))
+        return HIPK_SPMV_NOT_WIDE_CHUNK;   // (the paths below that launch something before the sliced-ELL dispatch, or never reach it)
     const int ntiles = (int)((a.n + 255) / 256);
     const int grid = ((ntiles + 7) >> 3) << 3;
     a.tpart0 = h->tile_part;
@@ -841,6 +848,11 @@ int hipk_launch_spmv(const hipk_csr_s *h, const hipk_spmv_args &a_, hipStream_t 
             }
             if (want_cheb && !cheb) return HIPK_SPMV_NO_CHEB;   // the one-row-per-lane coded kernels have no Chebyshev epilogue
             if (want_cheb && a.y == nullptr) return HIPK_OK;    // hipk_cheb_apply asking whether the epilogue exists: no launch
+            if (resolve) {
+                if (!chunked || strided || strncmp(g_spmv_kernel, "hipk_spmv_sell_wide_kernel<", 27) != 0) return HIPK_SPMV_NOT_WIDE_CHUNK;
+                *resolve = a;
+                return HIPK_SPMV_IS_WIDE_CHUNK;
+            }
             hipk_launch_timed(prof, HIPK_K_SPMV, kern, lgrid, HIPK_THREADS, 0, stream, a);
             if ((!chunked || strided) && !a.skip_combine && (a.mode & (HIPK_SPMV_DOT_W | HIPK_SPMV_DOT_YY))) {
                 hipk_launch_timed(prof, HIPK_K_AUX, hipk_tile_combine_kernel, (a.g + 3) / 4, HIPK_THREADS, 0, stream, (a.mode & HIPK_SPMV_DOT_W) ? a.tpart0 : nullptr, (a.mode & HIPK_SPMV_DOT_YY) ? a.tpart1 : nullptr,
@@ -903,6 +915,14 @@ int hipk_launch_spmv(const hipk_csr_s *h, const hipk_spmv_args &a_, hipStream_t 
     HIPK_CHECK_HIP(hipGetLastError());
     return HIPK_OK;
 }
+
+int hipk_launch_spmv(const hipk_csr_s *h, const hipk_spmv_args &a, hipStream_t stream, hipk_spmv_profiler *prof) {
+    return hipk_launch_spmv_(h, a, stream, prof, nullptr);
+}
+bool hipk_spmv_resolves_wide_chunk(const hipk_csr_s *h, const hipk_spmv_args &a, hipk_spmv_args *filled) {
+    return hipk_launch_spmv_(h, a, nullptr, nullptr, filled) == HIPK_SPMV_IS_WIDE_CHUNK;
+}
+void hipk_note_spmv_kernel(const char *name) { HIPK_NOTE_KERNEL("%s", name); }
 
 static void hipk_fill_spmv_args(const hipk_csr_s *h, hipk_spmv_args &a, const void *x, void *y) {
     a = hipk_spmv_base(h);

@@ -14,6 +14,8 @@
 // (the same, and x = (x + alpha_{k-1} p_{k-1}) + alpha_k p_k for two iterations at once, in the reference's order and with its
 // roundings: 48 n bytes), with the alphas from the scalar block (K2 leaves them there) -- B_spmv + 60 n bytes per iteration on
 // average; hipk_cg_xflush_kernel after the loop adds the term an odd iteration count leaves owed.
+// On fp64 constant-coefficient stencils of those sizes K1 and K2 are ONE launch, hipk_cg_fuse_update_kernel (hipk_cg_fuse.h): Ap stays in
+// LDS, <p,Ap> crosses the workgroups inside the launch -- B_spmv - 8 n + 16 n bytes instead of B_spmv + 24 n.
 // Every workgroup re-derives alpha/beta from the chunk
 // partials of the previous kernel with the fixed tree, so no grid barrier, no atomics
 // and no host round trip are needed; the host follows the loop through a pinned word the direction kernel
@@ -62,6 +64,7 @@ struct hipk_cg_scal {
 };
 static_assert(sizeof(hipk_cg_scal) <= 256, "the scalar block is 256 bytes");
 #include "hipk_cg_mid.h"   // one-launch loop for mid-size systems (uses hipk_lds_ctl)
+#include "hipk_cg_fuse.h"  // the stencil SpMV and the update step in one launch (uses hipk_cg_scal)
 
 // gamma0 = <r0,r0>, bs = <b,b>, atol2; p = r0.
 template <typename T>
@@ -1183,8 +1186,17 @@ struct hipk_cg_layout {
     // No room (fourth_vector false) up to kMidMinChunks chunks, at the streaming sizes, and in a pcg solve, which has neither form.
     bool fourth_vector;
     size_t p2;
+    // The fused SpMV + update launch (hipk_cg_fuse.h) keeps Ap on chip, so the head of Ap is its own: the chunks' flagged <p,Ap>
+    // words, then the collector's replicas -- one region, cleared by one memset when the sequence begins.  (Not in the partial
+    // slots: hipk_cg_direction_kernel folds the plain <p,Ap> partials from part_a, which the fused launch therefore still writes.)
+    // A sequence of the separate kernels that takes over after a give-up writes Ap again; the fused form is not tried again then.
+    size_t fuse_words, fuse_ctl;
     size_t total;
 };
+static constexpr size_t kFuseBytes = kFuseWordsBytes + kFuseCtlBytes;
+static_assert(kFuseWordsBytes % 256 == 0 && kFuseCtlBytes == 8 * 16 * kFuseReplicaSlots, "the replicas follow the words, 128 bytes apart");
+static_assert(kFuseBytes <= (size_t)kMidMaxChunks * HIPK_BASE_CHUNK * sizeof(double),
+              "the fused form runs beyond the mid loop's chunk count, fp64: Ap is longer than its region");
 static constexpr size_t kMidSlotArray = (size_t)kMidMaxChunks * 256;   // a slot array of the mid loop at the widest slot stride
 static_assert(kMidSlotBytes == 2 * kMidSlotArray && kPcgMidSlotBytes == 3 * kMidSlotArray, "pap_ll, rr_ll and (pcg) rz_ll");
 static_assert(HIPK_MAX_PARTS / 2 + 2 * kHoMaxWg <= HIPK_MAX_PARTS, "the LDS loop's hand-off flags fit the upper half of the spare slot");
@@ -1221,6 +1233,8 @@ static hipk_cg_layout hipk_cg_make_layout(int64_t n, int dtype, bool pre) {
     L.p2 = L.Ap + vec;
     if (second_p) take(vec);
     L.fourth_vector = !pre && (L.mid || second_p);
+    L.fuse_words = L.Ap;
+    L.fuse_ctl = L.Ap + kFuseWordsBytes;
     L.total = take.o;
     return L;
 }
@@ -1248,6 +1262,9 @@ struct hipk_cg_path {
     int64_t max_its = 0;       // iterations one launch of either loop may run
     bool two_launch = false;   // plain CG: hipk_cg2_spmv_kernel + hipk_cg2_update_kernel per iteration
     bool defer_x = false;      // plain CG, three launches: x updated every second iteration (hipk_cg_pdir_kernel / hipk_cg_xdir_kernel)
+    bool fuse_update = false;  // plain CG, fp64 stencils: SpMV and update step in one launch (hipk_cg_fuse_update_kernel), two launches in all
+    void (*fuse_kern)(hipk_spmv_args, hipk_cg_fuse_args) = nullptr;
+    hipk_spmv_args fuse_sa;    // ... its SpMV arguments, as hipk_launch_spmv fills them for the kernel it replaces
 };
 
 template <typename T, bool PRE>
@@ -1324,6 +1341,33 @@ static void hipk_cg_path_two(hipk_cg_path &path, const hipk_csr_s *A, const hipk
 static void hipk_cg_path_defer(hipk_cg_path &path, const hipk_csr_s *A, const hipk_params *prm, bool done, const hipk_cg_layout &lay) {
     path.defer_x = !done && !path.two_launch && !path.small && !path.streams && A->op_cb == nullptr && prm->profile == 0 &&
                    lay.fourth_vector && hipk_sw_enabled("HIPK_CG_DEFER_X");
+}
+
+// hipk_cg_fuse_update_kernel in place of the SpMV and hipk_cg_update_kernel, in the deferred-x sequence and in the plain three-launch
+// sequence (their direction kernels unchanged): the general form only, fp64, a matrix operand, no per-kernel profile; the handle's
+// CG-loop SpMV (sa: y = A p with <p, y>) resolves to the chunk walk of the two-rows-per-lane kernel on chunks of HIPK_BASE_CHUNK
+// rows -- today constant-coefficient stencils of 512 < g <= 2048 chunks --; all g workgroups can be resident at once (the
+// occupancy API's answer for the fused kernel x compute units; the kernel holds <= 80 SGPRs and <= 64 VGPRs by construction --
+// tests/test_gpu_cg_fuse_update.py reads the compiler's report -- because that API answers 8 where the chip admits 7 above 80
+// SGPRs: DESIGN section 9); the launch's sequence number fits 31 bits; the collector never gave up on this handle;
+// HIPK_CG_FUSE_UPDATE=0|1 forces (read per solve).
+// No gate by chunk count inside that envelope: every run beat every run of the separate kernels at 591, 958 and 1954 chunks (+2 %,
+// +6 %, +11.7 %: profiles/cg_fuse_update_ab.md).
+template <typename T>
+static void hipk_cg_path_fuse(hipk_cg_path &path, hipk_csr_s *A, const hipk_params *prm, bool done, int64_t it, int64_t maxiter,
+                              const hipk_spmv_args &sa) {
+    path.fuse_update = false;
+    if (sizeof(T) != 8 || done || path.two_launch || path.small || path.streams || A->op_cb != nullptr || prm->profile != 0 ||
+        A->geom.ch != HIPK_BASE_CHUNK || A->geom.g <= kMidMaxChunks || A->cg_fuse_failed || maxiter - it >= ((int64_t)1 << 31) ||
+        !hipk_sw_force("HIPK_CG_FUSE_UPDATE", true))
+        return;
+    if (!hipk_spmv_resolves_wide_chunk(A, sa, &path.fuse_sa)) return;
+    path.fuse_kern = A->sell_w == 5 ? hipk_cg_fuse_update_kernel<5> : A->sell_w == 8 ? hipk_cg_fuse_update_kernel<8> : hipk_cg_fuse_update_kernel<4>;
+    int occ = 0;
+    const bool resident = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, path.fuse_kern, HIPK_THREADS, 0) == hipSuccess &&
+                          (int64_t)occ * A->n_cu >= A->geom.g;
+    (void)hipGetLastError();
+    path.fuse_update = resident;
 }
 
 // {redo, it_done, stop_it} of a host copy of hipk_cg_scal / hipk_pcg_scal (hipk_resident_run)
@@ -1761,6 +1805,8 @@ struct hipk_cg_steps {
     int64_t it = 0, stop = INT64_MAX;
     bool done = false;       // a one-launch loop finished the solve
     char handed[128] = "";   // the one-launch loops that handed this solve back
+    int p_first = 0;         // deferred x: which of {p, p2} holds p_it when the sequence begins (1 after a fused sequence gave up
+                             // an odd number of iterations into it)
 
     // profile: the KIND of kernel whose durations are reported (hipk_spmv_profiler; only launches of it carry events), 0: none
     hipk_cg_steps(hipk_csr_s *A_, const T *dinv_, const T *b_, T *x_, char *w, const hipk_params *prm_, hipStream_t s_, int profile)
@@ -1975,16 +2021,21 @@ struct hipk_cg_steps {
     // plain CG, three launches with the x update deferred: SpMV, hipk_cg_update_kernel, hipk_cg_pdir_kernel / hipk_cg_xdir_kernel
     int deferred_x_sequence() {
         // p_j of iteration it0 + j lives in pbuf[j & 1]; even j only forms p_{j+1} in the other buffer, odd j also brings x up to date
-        T *pbuf[2] = {p, hipk_at<T>(work, lay.p2)};
+        T *pbuf[2] = {p_first ? hipk_at<T>(work, lay.p2) : p, p_first ? p : hipk_at<T>(work, lay.p2)};
         const int64_t it0 = it;
+        if (path.fuse_update) HIPK_TRY(fuse_begin());
         for (; it < maxiter; ++it) {
             HIPK_CHECK_HIP(pace.gate(it, stream, &stop));
             if (stop <= it) break;
             const int j = (int)((it - it0) & 1);
-            sa.it = it;
-            sa.x = sa.w = pbuf[j];
-            HIPK_TRY(hipk_launch_spmv(A, sa, stream, &prof));
-            hipk_cg_update_kernel<T><<<gm.g, HIPK_THREADS, 0, stream>>>(n, gm.ch, gm.g, scal, it, part_a, Ap, r, part_b, 0, &scal->alpha[it & 1]);
+            if (path.fuse_update) {
+                fuse_launch(it0, pbuf[j]);
+            } else {
+                sa.it = it;
+                sa.x = sa.w = pbuf[j];
+                HIPK_TRY(hipk_launch_spmv(A, sa, stream, &prof));
+                hipk_cg_update_kernel<T><<<gm.g, HIPK_THREADS, 0, stream>>>(n, gm.ch, gm.g, scal, it, part_a, Ap, r, part_b, 0, &scal->alpha[it & 1]);
+            }
             if (j == 0)
                 hipk_cg_pdir_kernel<T><<<gm.g, HIPK_THREADS, 0, stream>>>(n, gm.ch, gm.g, scal, it, maxiter, part_b, r, pbuf[0], pbuf[1]);
             else
@@ -1993,8 +2044,66 @@ struct hipk_cg_steps {
         }
         // an odd number of iterations: the last one's x update is still owed (the device knows how many were completed)
         hipk_cg_xflush_kernel<T><<<gm.g, HIPK_THREADS, 0, stream>>>(n, gm.ch, scal, it, it0, pbuf[0], x);
+        return path.fuse_update ? fuse_end(it0, true) : HIPK_OK;
+    }
+
+    // ---- hipk_cg_fuse_update_kernel in place of the SpMV and the update launch (hipk_cg_path_fuse)
+    // the sequence begins: the flagged words and the collector's replicas (one region, the head of Ap) and the give-up word
+    int fuse_begin() {
+        HIPK_CHECK_HIP(hipMemsetAsync(hipk_at<char>(work, lay.fuse_words), 0, kFuseBytes, stream));
+        HIPK_CHECK_HIP(hipMemsetAsync(&scal->ctl, 0, sizeof(hipk_lds_ctl), stream));
+        // tests: HIPK_TEST_CG_FUSE_GIVE_UP=k makes the collector of iteration k behave as if its poll had run out
+        fuse_give_up_at = hipk_sw_present("HIPK_TEST_CG_FUSE_GIVE_UP") ? hipk_sw_int("HIPK_TEST_CG_FUSE_GIVE_UP", -1) : -1;
+        fuse_note();
         return HIPK_OK;
     }
+    // the kernel note of the loop's products (hipk_last_spmv_kernel); again after the solve's last residual, which has its own
+    void fuse_note() const {
+        char name[64];
+        snprintf(name, sizeof(name), "hipk_cg_fuse_update_kernel<%d>", A->sell_w);
+        hipk_note_spmv_kernel(name);
+    }
+    // iteration `it` of a sequence that began at it0: Ap = A pk on chip, alpha, r -= alpha Ap, the partials of <r,r>
+    void fuse_launch(int64_t it0, const T *pk) {
+        hipk_spmv_args fa = path.fuse_sa;
+        fa.it = it;
+        fa.x = fa.w = pk;
+        hipk_cg_fuse_args ff;
+        ff.scal = (hipk_cg_scal *)scal;
+        ff.r = (double *)r;
+        ff.part_rr = part_b;
+        ff.part_pap = part_a;
+        ff.words = hipk_at<char>(work, lay.fuse_words);
+        ff.ctl = hipk_at<char>(work, lay.fuse_ctl);
+        ff.seq = (unsigned)(it - it0) + 1u;
+        ff.give_up = it == fuse_give_up_at ? 1 : 0;
+        path.fuse_kern<<<hipk_xcd_grid(gm.g), HIPK_THREADS, 0, stream>>>(fa, ff);
+    }
+    // the sequence has ended: HIPK_OK, or HIPK_HANDED_BACK when the collector gave up at some iteration -- the state is that
+    // iteration's, the latch is set on the handle, the stop word and the pacer are rearmed, and the caller goes on from `it` with
+    // the separate kernels.  deferred: the flush has brought x up to date; p of that iteration is where its parity put it
+    int fuse_end(int64_t it0, bool deferred) {
+        S hs;
+        HIPK_CHECK_HIP(hipGetLastError());
+        HIPK_CHECK_HIP(hipMemcpyAsync(&hs, scal, sizeof(hs), hipMemcpyDeviceToHost, stream));
+        HIPK_CHECK_HIP(hipStreamSynchronize(stream));
+        if (hs.ctl.redo == -3) {
+            hipk_set_error("hipk_cg_solve: the collector of the fused SpMV + update launch stopped arriving");
+            return HIPK_ERR_HIP;
+        }
+        if (hs.ctl.redo != -1) return HIPK_OK;
+        A->cg_fuse_failed = 1;
+        path.fuse_update = false;
+        if (deferred) p_first ^= (int)((hs.stop_it - it0) & 1);
+        it = hs.stop_it;
+        stop = INT64_MAX;
+        HIPK_CHECK_HIP(hipMemcpyAsync(&scal->stop_it, &stop, sizeof(int64_t), hipMemcpyHostToDevice, stream));
+        HIPK_CHECK_HIP(hipMemsetAsync(&scal->ctl, 0, sizeof(hipk_lds_ctl), stream));
+        HIPK_CHECK_HIP(hipStreamSynchronize(stream));
+        HIPK_CHECK_HIP(pace.resume(it));
+        return HIPK_HANDED_BACK;
+    }
+    int64_t fuse_give_up_at = -1;
 
     // the kernels of the plain three-launch sequence (hipk_cg_path: small / streams / flat_dir) and the form they make
     hipk_cg_kernels<T> pick() const {
@@ -2010,13 +2119,19 @@ struct hipk_cg_steps {
     // plain CG: SpMV, update, direction.  params.profile selects the kernel whose durations are reported (1 SpMV, 2 update,
     // 3 direction -- of the flat form its flat kernel, the step's 40 n bytes --, 4 the scalars launch before that)
     int three_launch_sequence(const hipk_cg_kernels<T> &k) {
+        const int64_t it0 = it;
+        if (path.fuse_update) HIPK_TRY(fuse_begin());
         for (; it < maxiter; ++it) {
             HIPK_CHECK_HIP(pace.gate(it, stream, &stop));
             if (stop <= it) break;
-            sa.it = it;
-            HIPK_TRY(hipk_launch_spmv(A, sa, stream, &prof));
-            hipk_launch_timed(&prof, HIPK_K_UPDATE, k.update, gm.g, HIPK_THREADS, 0, stream, n, gm.ch, gm.g, scal, it, k.pap, Ap, r, part_b, k.ntiles,
-                              (double *)nullptr);
+            if (path.fuse_update) {
+                fuse_launch(it0, p);
+            } else {
+                sa.it = it;
+                HIPK_TRY(hipk_launch_spmv(A, sa, stream, &prof));
+                hipk_launch_timed(&prof, HIPK_K_UPDATE, k.update, gm.g, HIPK_THREADS, 0, stream, n, gm.ch, gm.g, scal, it, k.pap, Ap, r, part_b, k.ntiles,
+                                  (double *)nullptr);
+            }
             if (k.direction) {
                 hipk_launch_timed(&prof, HIPK_K_DIRECTION, k.direction, gm.g, HIPK_THREADS, 0, stream, n, gm.ch, gm.g, scal, it, maxiter, k.pap, part_b, r,
                                   p, x, k.ntiles);
@@ -2027,7 +2142,7 @@ struct hipk_cg_steps {
             }
             if ((it & 63) == 63) HIPK_CHECK_HIP(hipGetLastError());
         }
-        return HIPK_OK;
+        return path.fuse_update ? fuse_end(it0, false) : HIPK_OK;
     }
 
     // Jacobi PCG: SpMV, hipk_pcg_update_kernel, hipk_pcg_direction_kernel
@@ -2090,14 +2205,20 @@ static int hipk_cg_solve_t(hipk_csr_s *A, const T *b, T *x, char *work, const hi
     // what is left when neither loop finished: two launches per iteration, else three with the x update deferred, else three
     hipk_cg_path_two(s.path, A, prm, s.done, s.it, s.kCap2, s.lay);
     hipk_cg_path_defer(s.path, A, prm, s.done, s.lay);
+    hipk_cg_path_fuse<T>(s.path, A, prm, s.done, s.it, s.maxiter, s.sa);
     if (!s.done) {
         const hipk_cg_kernels<T> k = s.pick();   // (the deferred-x form reports the three-launch form it replaces the direction step of)
         hipk_set_solve_form(!s.path.two_launch ? k.form
                             : sizeof(T) == 8   ? HIPK_FORM("cg two-launch: hipk_cg2_spmv_kernel<double,1280> + hipk_cg2_update_kernel")
                                                : HIPK_FORM("cg two-launch: hipk_cg2_spmv_kernel<float,2048> + hipk_cg2_update_kernel"));
-        HIPK_TRY(s.path.two_launch ? s.two_launch_sequence() : s.path.defer_x ? s.deferred_x_sequence() : s.three_launch_sequence(k));
+        // (a fused sequence whose collector gave up has handed the solve back at s.it: the same sequence again, separate kernels)
+        int run = s.path.two_launch ? s.two_launch_sequence() : s.path.defer_x ? s.deferred_x_sequence() : s.three_launch_sequence(k);
+        if (run == HIPK_HANDED_BACK) run = s.path.defer_x ? s.deferred_x_sequence() : s.three_launch_sequence(k);
+        HIPK_TRY(run);
     }
-    return s.finish(st);
+    const int rc = s.finish(st);
+    if (!s.done && s.path.fuse_update) s.fuse_note();   // the loop's products, not the true residual's, are what a fused solve reports
+    return rc;
 }
 
 template <typename T>

@@ -351,7 +351,7 @@ static inline int hipk_sell_units(int w) {  // host: units of 256 B of a tile wh
     return 4 * d + bp;
 }
 
-__global__ __launch_bounds__(HIPK_THREADS) void hipk_tile_width_kernel(const int *__restrict__ crow, int64_t n_rows,
+static __global__ __launch_bounds__(HIPK_THREADS) void hipk_tile_width_kernel(const int *__restrict__ crow, int64_t n_rows,
                                                                        int *__restrict__ tile_w) {
     __shared__ int wmax[HIPK_THREADS / 64];
     const int64_t r = (int64_t)blockIdx.x * HIPK_TILE + threadIdx.x;
@@ -374,7 +374,7 @@ __global__ __launch_bounds__(HIPK_THREADS) void hipk_tile_width_kernel(const int
 // the tiles that contain a grid-line end).  ucode[tile] = those bytes (two groups of four, padding 0xFF) when the
 // tile has at most two groups and all rows agree, else 0 (no valid tile packs to 0: codes of a row are distinct).
 // The SpMV then takes a uniform tile's codes from one scalar load and never reads its planes.
-__global__ __launch_bounds__(HIPK_THREADS) void hipk_tile_uniform_kernel(const unsigned char *__restrict__ code,
+static __global__ __launch_bounds__(HIPK_THREADS) void hipk_tile_uniform_kernel(const unsigned char *__restrict__ code,
                                                                          const int *__restrict__ tile_off, int ntiles,
                                                                          unsigned long long *__restrict__ ucode,
                                                                          int *__restrict__ count) {
@@ -429,7 +429,7 @@ __global__ __launch_bounds__(HIPK_THREADS) void hipk_tile_uniform_kernel(const u
 // products, same order of additions as the one-row-per-lane path: same bits).  Conditions: full tile, <= 7 entries per row,
 // every load of the pattern in range for every row pair (so not the tiles at the first / last grid line of the matrix).
 #define HIPK_SELL_MASKED 254u
-__global__ __launch_bounds__(HIPK_THREADS) void hipk_tile_masked_kernel(const unsigned char *__restrict__ code,
+static __global__ __launch_bounds__(HIPK_THREADS) void hipk_tile_masked_kernel(const unsigned char *__restrict__ code,
                                                                         const int *__restrict__ tile_off, int ntiles, int64_t n_rows,
                                                                         const int *__restrict__ dict_off,
                                                                         const unsigned long long *__restrict__ ucode,
@@ -1024,7 +1024,7 @@ __device__ __forceinline__ double hipk_half_tree2(double2 d) {  // sums of rows 
 // (s_memrealtime: comparable across compute units) at its phase boundaries; tools/spmv_stamps_probe.py prints where the time goes.
 #ifdef HIPK_GM_STAMPS
 #define HIPK_WIDE_NSTAMP 8
-__device__ unsigned long long hipk_wide_stamps[2048 * 4 * HIPK_WIDE_NSTAMP];
+static __device__ unsigned long long hipk_wide_stamps[2048 * 4 * HIPK_WIDE_NSTAMP];
 #define HIPK_WSTAMP(k)                                                                                                   \
     do {                                                                                                                 \
         if (lane == 0 && blockIdx.x < 2048)                                                                              \
@@ -1036,9 +1036,32 @@ __device__ unsigned long long hipk_wide_stamps[2048 * 4 * HIPK_WIDE_NSTAMP];
 // HIPK_SGPR80 (hipk_common.h): the 8-wide instantiations and the run-time-mode ones sat at 82-106 scalar registers (seven or six
 // workgroups per CU admitted); the stamps twin of the 5-wide one at 92 -- its first run showed workgroups 1792 .. 1953 starting 8 us
 // late, an artefact of the twin (the product kernel has 68).
-template <int UNITS, int MODE = -1, int WALK = 0>
-__global__ __launch_bounds__(HIPK_THREADS) HIPK_SGPR80 void hipk_spmv_sell_wide_kernel(hipk_spmv_args a) {
+// The kernel's body is hipk_sell_wide_walk, shared with the CG loop's fused SpMV + update kernel (hipk_cg_fuse.h).  FUSE: the
+// rows' results do not go to y but stay in LDS (`stage`, indexed by the row's place in the chunk: 2048 doubles), the tile sums are
+// sized by the 8 tiles of such a chunk, and the walk ends BEFORE the chunk fold: *out tells the caller where the chunk's pieces
+// are (true), or nothing is to be done (false: a padding workgroup, or the stop word has fired -- nothing was stored).
+#define HIPK_FUSE_TPC (HIPK_BASE_CHUNK / 256)
+struct hipk_wide_chunk {
+    int chunk, cnt;    // the workgroup's reduction chunk and its tiles
+    double *wsum0;     // LDS: per-wavefront sums of <w, y>, 4 per tile (hipk_wave_fold folds them)
+    double *stage;     // LDS: y of the chunk's rows
+    double *free256;   // LDS: 256 doubles the walk no longer needs (the dictionary's values), e.g. for hipk_block_sum
+};
+template <bool FUSE>
+struct hipk_wide_stage {
+    static __device__ __forceinline__ double *get() { return nullptr; }
+};
+template <>
+struct hipk_wide_stage<true> {
+    static __device__ __forceinline__ double *get() {
+        __shared__ __attribute__((aligned(16))) double stage[HIPK_BASE_CHUNK];
+        return stage;
+    }
+};
+template <int UNITS, int MODE, int WALK, bool FUSE = false>
+__device__ __forceinline__ bool hipk_sell_wide_walk(const hipk_spmv_args &a, hipk_wide_chunk *out = nullptr) {
     typedef double T;
+    static_assert(!FUSE || (WALK == 0 && MODE == HIPK_SPMV_DOT_W), "the fused form: chunk walk, <w, y> compiled in");
     constexpr bool STRIDED = WALK != 0;  // tile sums to the per-tile buffer, no in-kernel fold
     // MODE = HIPK_SPMV_CHEB_MODE: one Chebyshev step (hipk_cheb_apply) -- a compiled-in mode only, the run-time-mode instantiation
     // knows nothing of it (a run-time test here would cost every other instantiation registers)
@@ -1049,19 +1072,20 @@ __global__ __launch_bounds__(HIPK_THREADS) HIPK_SGPR80 void hipk_spmv_sell_wide_
     const int ntiles = (int)((a.n + HIPK_TILE - 1) / HIPK_TILE);
     const int tpc = a.ch / HIPK_TILE;
     const int chunk = STRIDED ? 0 : hipk_xcd_chunk(blockIdx.x, a.g);
-    if (chunk < 0) return;
+    if (chunk < 0) return false;
     // local tile i of this workgroup is tile t_first + i, i < cnt
     int t_first = chunk * tpc;
     int cnt = ((t_first + tpc < ntiles) ? t_first + tpc : ntiles) - t_first;
     if (WALK == 1) {
         const int ngroups = (ntiles + HIPK_SELL_GROUP - 1) / HIPK_SELL_GROUP;
         const int grp = hipk_xcd_chunk(blockIdx.x, ngroups);
-        if (grp < 0) return;
+        if (grp < 0) return false;
         t_first = grp * HIPK_SELL_GROUP;
         cnt = (t_first + HIPK_SELL_GROUP < ntiles ? t_first + HIPK_SELL_GROUP : ntiles) - t_first;
     }
-    __shared__ double wsum0[STRIDED ? 1 : HIPK_SELL_MAX_TPC * 4];
-    __shared__ double wsum1[STRIDED ? 1 : HIPK_SELL_MAX_TPC * 4];
+    __shared__ double wsum0[STRIDED ? 1 : FUSE ? HIPK_FUSE_TPC * 4 : HIPK_SELL_MAX_TPC * 4];
+    __shared__ double wsum1[(STRIDED || FUSE) ? 1 : HIPK_SELL_MAX_TPC * 4];
+    double *const stage = hipk_wide_stage<FUSE>::get();
     __shared__ T dval[HIPK_CODED_MAX];
     __shared__ int doff[HIPK_CODED_MAX];
     const int t = threadIdx.x, lane = t & 63;
@@ -1085,7 +1109,7 @@ __global__ __launch_bounds__(HIPK_THREADS) HIPK_SGPR80 void hipk_spmv_sell_wide_
         dv = g_dval[t];
         dofs = g_doff[t];
     }
-    if (a.stop_it != nullptr && a.it >= *a.stop_it) return;
+    if (a.stop_it != nullptr && a.it >= *a.stop_it) return false;
     dval[t] = dv;  // slots >= n_codes, in particular HIPK_SELL_PAD: offset 0, value 0
     doff[t] = dofs;
     HIPK_WSTAMP(1);
@@ -1157,7 +1181,8 @@ __global__ __launch_bounds__(HIPK_THREADS) HIPK_SGPR80 void hipk_spmv_sell_wide_
                 ((T *)a.cheb_d)[row] = dn;
                 out = a.cheb_scale * (cz + dn);
             }
-            y[row] = out;
+            if constexpr (FUSE) stage[i * HIPK_TILE + t] = out;
+            else y[row] = out;
             if (mode & HIPK_SPMV_DOT_W) d0 = (double)ow * (double)out;
             if (mode & HIPK_SPMV_DOT_YY) d1 = (double)out * (double)out;
         }
@@ -1271,7 +1296,8 @@ __global__ __launch_bounds__(HIPK_THREADS) HIPK_SGPR80 void hipk_spmv_sell_wide_
             out.x = a.cheb_scale * (cz.x + dn.x);
             out.y = a.cheb_scale * (cz.y + dn.y);
         }
-        *(double2 *)((char *)y + vo) = out;
+        if constexpr (FUSE) *(double2 *)(stage + i * HIPK_TILE + wh * 128 + 2 * lane) = out;
+        else *(double2 *)((char *)y + vo) = out;
         const int slot = i * 4 + 2 * wh + (lane >> 5);
         if (mode & HIPK_SPMV_DOT_W) {
             double2 d = {ow.x * out.x, ow.y * out.y};
@@ -1307,6 +1333,10 @@ __global__ __launch_bounds__(HIPK_THREADS) HIPK_SGPR80 void hipk_spmv_sell_wide_
 #endif
     }
     HIPK_WSTAMP(5);
+    if constexpr (FUSE) {
+        *out = {chunk, cnt, wsum0, stage, (double *)dval};
+        return true;
+    }
     if (!STRIDED && (mode & (HIPK_SPMV_DOT_W | HIPK_SPMV_DOT_YY))) {
         __syncthreads();
         HIPK_WSTAMP(6);
@@ -1322,5 +1352,10 @@ __global__ __launch_bounds__(HIPK_THREADS) HIPK_SGPR80 void hipk_spmv_sell_wide_
         }
     }
     HIPK_WSTAMP(7);
+    return true;
+}
+template <int UNITS, int MODE = -1, int WALK = 0>
+__global__ __launch_bounds__(HIPK_THREADS) HIPK_SGPR80 void hipk_spmv_sell_wide_kernel(hipk_spmv_args a) {
+    (void)hipk_sell_wide_walk<UNITS, MODE, WALK>(a);
 }
 #endif

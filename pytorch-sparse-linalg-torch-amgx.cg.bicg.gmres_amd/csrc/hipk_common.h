@@ -147,6 +147,7 @@ struct hipk_csr_s {
     // matrix-free operator (hipk_op_create): every product is op_cb(op_user, x, y) + an epilogue kernel; no CSR arrays
     int (*op_cb)(void *user, const void *x_dev, void *y_dev);
     void *op_user;
+    int cg_fuse_failed;     // hipk_cg_solve: the collector of the fused SpMV + update launch once gave up on this handle (hipk_cg_fuse.h)
     mutable hipk_spmv_plan plans[12];
     mutable int n_plans;
 };

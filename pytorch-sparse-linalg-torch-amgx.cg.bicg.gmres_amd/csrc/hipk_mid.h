@@ -218,14 +218,14 @@ static inline bool hipk_mid_eligible(hipk_csr_s *A, const hipk_mid_entry<Args> *
 
 // thread t's share of the G flagged chunk partials in the spec's order (hipk_reduce_parts: t, t + 256; the tree follows);
 // *fail set when a partial never arrived
+// acc: the sum so far, for a fold polled in several calls (the words from `off` on continue the same ascending sum)
 template <int NK = kMidMaxChunks / 256, bool STG = false>
-__device__ __forceinline__ double hipk_mid_poll(hipk_ll_rsrc rs, int g, unsigned seq, int *fail, int ss, unsigned off = 0) {
+__device__ __forceinline__ double hipk_mid_poll(hipk_ll_rsrc rs, int g, unsigned seq, int *fail, int ss, unsigned off = 0, double acc = 0.0) {
     const int t = threadIdx.x;
     hipk_v4u w[NK];
 #pragma unroll
     for (int k = 0; k < NK; ++k)
         if (t + k * 256 < g) w[k] = hipk_ll_load(rs, (t + k * 256) * ss, off);
-    double acc = 0.0;
 #pragma unroll
     for (int k = 0; k < NK; ++k)
         if (t + k * 256 < g) {

@@ -221,6 +221,15 @@ struct hipk_pacer {
         return poll.create();
     }
     int64_t *device_sig() const { return sig; }
+    // a loop that stopped at `it` without being finished goes on from there: the caller has synchronised the stream and rearmed
+    // the device stop word; reads of the old stop word still in flight are dropped, the signal word says `it` iterations again
+    hipError_t resume(int64_t it) {
+        int64_t dropped = INT64_MAX;
+        const hipError_t e = poll.drain(&dropped);
+        if (sig) __atomic_store_n(sig, it, __ATOMIC_RELEASE);
+        next_post = it;
+        return e;
+    }
     // Call before enqueueing iteration `it`; *stop <= it afterwards means: do not enqueue it.
     hipError_t gate(int64_t it, hipStream_t s, int64_t *stop) {
         if (live) {

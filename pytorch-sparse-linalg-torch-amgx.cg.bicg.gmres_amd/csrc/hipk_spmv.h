@@ -478,6 +478,11 @@ static __global__ __launch_bounds__(HIPK_THREADS) void hipk_tile_combine_kernel(
 struct hipk_spmv_profiler;
 int hipk_launch_spmv(const hipk_csr_s *h, const hipk_spmv_args &a, hipStream_t stream,
                      hipk_spmv_profiler *prof = nullptr);
+// whether a launch of `a` on h would be the chunk walk of hipk_spmv_sell_wide_kernel (a workgroup per reduction chunk, WALK = 0),
+// without launching anything; *filled: the arguments as that kernel gets them; the kernel note is that launch's
+bool hipk_spmv_resolves_wide_chunk(const hipk_csr_s *h, const hipk_spmv_args &a, hipk_spmv_args *filled);
+// the kernel note (hipk_last_spmv_kernel) of a product that a solver's own kernel forms
+void hipk_note_spmv_kernel(const char *name);
 // hipk_cheb_apply's vector kernels on a row block of n rows in chunks of ch (fp64; hipk_api.hip), for the row-partitioned apply:
 // step 0 (d = c0 * (dinv * r), z = d) and the vector half of a two-launch step (d = (c1 d) + (c2 res), z = scale (z + d));
 // hipk_note_cheb_step appends " + hipk_cheb_step_kernel<double>" to the kernel note, as hipk_cheb_apply does for that form
