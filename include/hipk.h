@@ -265,7 +265,7 @@ int hipk_cg_solve_multi(hipk_csr_t A, const void *dinv, int k, const void *B, in
 int hipk_bicgstab_solve_multi(hipk_csr_t A, const void *dinv, int k, const void *B, int64_t ldb, void *X, int64_t ldx, void *work,
                               size_t work_bytes, const hipk_params *prm, hipk_stats *st, int64_t *block_spmvs,
                               hipk_stream_t stream);
-/* ---- many small systems: S independent systems with ONE sparsity pattern, one workgroup per system (csrc/hipk_batch.hip) ----
+/* ---- many small systems: S independent systems with ONE sparsity pattern, one workgroup per system (csrc/hipk_batch.hip, hipk_batch_gm.hip) ----
  * System s has the shared pattern crow_dev[n + 1] / col_dev[nnz] (int32, device), the values vals + s * ldv, the right-hand side
  * B + s * ldb and x0 / the solution in X + s * ldx (device arrays of `dtype`; ldv >= nnz, ldb, ldx >= n); dinv is NULL (M = identity)
  * or the Jacobi vectors dinv + s * ldd.  Row s of the result and st[s] (st: `batch` entries) are bit for bit hipk_cg_solve /
@@ -288,6 +288,21 @@ int hipk_bicgstab_solve_batch(int64_t n, int64_t nnz, const int32_t *crow_dev, c
                               const void *dinv, int64_t ldd, int batch, const void *B, int64_t ldb, void *X, int64_t ldx, int dtype,
                               void *work, size_t work_bytes, const hipk_params *prm, hipk_stats *st, hipk_stream_t stream);
 int hipk_last_batch_launches(void);
+/* Restarted GMRES for the same batches (csrc/hipk_batch_gm.hip): row s of the result and st[s] are bit for bit hipk_gmres_solve /
+ * hipk_pgmres_solve of system s with the same params -- prm->restart (1 .. 31, else HIPK_ERR_UNSUPPORTED), prm->gmres_method and
+ * prm->gpu_tolerances are read; iterations = restart cycles, breakdown = 1 on happy breakdown -- every system stopping at its own
+ * cycle and, with HIPK_GMRES_INCREMENTAL, at its own Arnoldi step inside a cycle.  One launch of hipk_gm_batch_kernel<T, PRE> runs
+ * every system's whole solve; the basis (restart + 1 vectors per system) lives in `work`.  A non-positive pivot of the normal
+ * equations' Cholesky factorisation is followed by the partial-pivot elimination on the device.  A launch ends a system's work at
+ * the first cycle boundary at or after HIPK_BATCH_LAUNCH_ITS Arnoldi steps and the next one resumes it (same bits for any budget).
+ * Arguments, envelope, alignment, error codes and the workspace contract as hipk_cg_solve_batch; `work`:
+ * hipk_gmres_batch_work_bytes (pure host code; 0 for a restart outside 1 .. 31).  hipk_last_solve_path() reports e.g.
+ * "hipk_gm_batch_kernel<double,false>". */
+size_t hipk_gmres_batch_work_bytes(int64_t n, int64_t nnz, int batch, int dtype, int restart, int precond);
+int hipk_gmres_solve_batch(int64_t n, int64_t nnz, const int32_t *crow_dev, const int32_t *col_dev, const void *vals, int64_t ldv,
+                           const void *dinv /* NULL: M = identity */, int64_t ldd, int batch, const void *B, int64_t ldb, void *X,
+                           int64_t ldx, int dtype, void *work, size_t work_bytes, const hipk_params *prm, hipk_stats *st /* batch entries */,
+                           hipk_stream_t stream);
 /* Placement probe for systems whose vectors live in HBM (N >> 8 M rows): the memory shape of the CG direction step (reads r, p, x;
  * writes p, x) on the three vectors, storing back the bits it loaded (safe on live data); *us_out = the fastest of `reps` (<= 16)
  * timed passes in microseconds.  40 n bytes (fp64) per pass.  On MI355X such a step runs at one of two discrete speeds depending on

@@ -312,4 +312,24 @@ __device__ __forceinline__ void hipk_reduce_parts2(const double *__restrict__ p0
     r0 = a;
     r1 = b;
 }
+
+// the Givens rotation of GMRES' incremental form
+__device__ __forceinline__ void hipk_givens(double a, double b, double &cs, double &sn) {  // TSL:508-518
+    if (fabs(b) == 0.0) {
+        cs = 1.0;
+        sn = 0.0;
+        return;
+    }
+    if (fabs(a) < fabs(b)) {
+        const double t = -(a / b);
+        const double r = 1.0 / sqrt(1.0 + fabs(t) * fabs(t));
+        cs = r * t;
+        sn = r;
+    } else {
+        const double t = -(b / a);
+        const double r = 1.0 / sqrt(1.0 + fabs(t) * fabs(t));
+        cs = r;
+        sn = r * t;
+    }
+}
 #endif  // __HIPCC__

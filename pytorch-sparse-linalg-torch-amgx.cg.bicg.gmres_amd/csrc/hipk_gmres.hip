@@ -653,25 +653,6 @@ __global__ __launch_bounds__(HIPK_THREADS, (KC <= 8 ? 8 : 1)) void hipk_gm_updat
     }
 }
 
-__device__ __forceinline__ void hipk_givens(double a, double b, double &cs, double &sn) {  // TSL:508-518
-    if (fabs(b) == 0.0) {
-        cs = 1.0;
-        sn = 0.0;
-        return;
-    }
-    if (fabs(a) < fabs(b)) {
-        const double t = -(a / b);
-        const double r = 1.0 / sqrt(1.0 + fabs(t) * fabs(t));
-        cs = r * t;
-        sn = r;
-    } else {
-        const double t = -(b / a);
-        const double r = 1.0 / sqrt(1.0 + fabs(t) * fabs(t));
-        cs = r;
-        sn = r * t;
-    }
-}
-
 // v_{k+1} = q/||q|| (zero when ||q|| <= eps ||A v_k||), column k of H, breakdown,
 // and for 'incremental' the Givens update + early-exit test  (TSL:358-387, 595-623)
 template <typename T>

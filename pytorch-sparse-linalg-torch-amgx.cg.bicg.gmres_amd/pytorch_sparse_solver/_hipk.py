@@ -58,6 +58,7 @@ SYMBOLS = [
     "hipk_multi_work_bytes", "hipk_cg_solve_multi", "hipk_bicgstab_solve_multi",
     # many small systems with one sparsity pattern, one workgroup per system
     "hipk_batch_work_bytes", "hipk_cg_solve_batch", "hipk_bicgstab_solve_batch", "hipk_last_batch_launches",
+    "hipk_gmres_batch_work_bytes", "hipk_gmres_solve_batch",
 ]
 
 
@@ -278,7 +279,9 @@ def lib():
                                                           ctypes.POINTER(Stats), ctypes.POINTER(i64), vp]
     L.hipk_batch_work_bytes.argtypes = [i64, i64, i32, i32, i32, i32]
     L.hipk_batch_work_bytes.restype = ctypes.c_size_t
-    for name in ("cg", "bicgstab"):
+    L.hipk_gmres_batch_work_bytes.argtypes = [i64, i64, i32, i32, i32, i32]
+    L.hipk_gmres_batch_work_bytes.restype = ctypes.c_size_t
+    for name in ("cg", "bicgstab", "gmres"):
         getattr(L, f"hipk_{name}_solve_batch").argtypes = [i64, i64, vp, vp, vp, i64, vp, i64, i32, vp, i64, vp, i64, i32, vp,
                                                           ctypes.c_size_t, ctypes.POINTER(Params), ctypes.POINTER(Stats), vp]
     _lib = L
@@ -826,7 +829,7 @@ def solve_multi(method: str, h: CsrHandle, dinv: Optional[torch.Tensor], B: torc
 
 @dataclass
 class BatchSolveStats:
-    """Side channel of cg_batch / bicgstab_batch: per-system lists (one entry per system), the path that ran
+    """Side channel of cg_batch / bicgstab_batch / gmres_batch: per-system lists (one entry per system), the path that ran
     (`hipk_last_solve_path` of the batch kernel, or "loop"), the kernel launches the solve took (0 on the loop route) and its time."""
     method: str
     iterations: list
@@ -843,8 +846,9 @@ class BatchSolveStats:
     solve_ms: float
 
 
-BATCH_MAX_N = 4096      # the envelope of hipk_{cg,bicgstab}_solve_batch: rows per system ...
+BATCH_MAX_N = 4096      # the envelope of hipk_{cg,bicgstab,gmres}_solve_batch: rows per system ...
 BATCH_MAX_ROW = 32      # ... and stored entries per row
+GMRES_BATCH_MAX_RESTART = 31   # ... and, for hipk_gmres_solve_batch, the restart (HIPK_GM_MAXM)
 
 
 def batch_work_bytes(n: int, nnz: int, batch: int, dtype: torch.dtype, method: str, precond: bool) -> int:
@@ -853,10 +857,15 @@ def batch_work_bytes(n: int, nnz: int, batch: int, dtype: torch.dtype, method: s
                                            1 if precond else 0))
 
 
+def gmres_batch_work_bytes(n: int, nnz: int, batch: int, dtype: torch.dtype, restart: int, precond: bool) -> int:
+    """hipk_gmres_batch_work_bytes (pure host code: callable without a GPU); 0 for a restart outside 1 .. 31."""
+    return int(lib().hipk_gmres_batch_work_bytes(int(n), int(nnz), int(batch), _dtype_code(dtype), int(restart), 1 if precond else 0))
+
+
 def solve_batch(method: str, n: int, nnz: int, crow: torch.Tensor, col: torch.Tensor, vals: torch.Tensor, dinv: Optional[torch.Tensor],
                 B: torch.Tensor, X: torch.Tensor, *, tol: float, atol: float, maxiter: Optional[int],
-                work: Optional[torch.Tensor] = None) -> BatchSolveStats:
-    """hipk_{cg,bicgstab}_solve_batch: crow (n + 1,), col (nnz,) int32; vals (S, ldv), B (S, ldb), X (S, ldx), dinv None or
+                work: Optional[torch.Tensor] = None, restart: int = 20, solve_method: str = "batched") -> BatchSolveStats:
+    """hipk_{cg,bicgstab,gmres}_solve_batch (restart and solve_method: gmres only): crow (n + 1,), col (nnz,) int32; vals (S, ldv), B (S, ldb), X (S, ldx), dinv None or
     (S, ldd), row-major with unit inner stride, of one dtype on one device; X holds X0 on entry and the solutions on return."""
     S = int(B.shape[0])
     dev = B.device
@@ -869,7 +878,12 @@ def solve_batch(method: str, n: int, nnz: int, crow: torch.Tensor, col: torch.Te
     prm.maxiter = -1 if maxiter is None else int(maxiter)
     prm.gpu_tolerances = 1
     L = lib()
-    wb = batch_work_bytes(n, nnz, S, B.dtype, method, dinv is not None)
+    if method == "gmres":
+        prm.restart = int(restart)
+        prm.gmres_method = {"batched": GMRES_BATCHED, "incremental": GMRES_INCREMENTAL}[solve_method]
+        wb = gmres_batch_work_bytes(n, nnz, S, B.dtype, restart, dinv is not None)
+    else:
+        wb = batch_work_bytes(n, nnz, S, B.dtype, method, dinv is not None)
     work = _workspace(work, dev, wb)
     st = (Stats * S)()
     ld = lambda t: int(t.stride(0))
@@ -879,7 +893,7 @@ def solve_batch(method: str, n: int, nnz: int, crow: torch.Tensor, col: torch.Te
                                                       B.data_ptr(), ld(B), X.data_ptr(), ld(X), _dtype_code(B.dtype), work.data_ptr(),
                                                       wb, ctypes.byref(prm), st, _stream(dev))
     _check(rc, f"hipk_{method}_solve_batch")
-    name = method if dinv is None else {"cg": "pcg_jacobi", "bicgstab": "pbicgstab_jacobi"}[method]
+    name = method if dinv is None else {"cg": "pcg_jacobi", "bicgstab": "pbicgstab_jacobi", "gmres": "pgmres_jacobi"}[method]
     col_of = lambda f: [getattr(c, f) for c in st]
     return BatchSolveStats(method=f"{name}_batch", iterations=col_of("iterations"), matvecs=col_of("matvecs"), info=col_of("info"),
                            breakdown=col_of("breakdown"), b_norm=col_of("b_norm"), residual_norm=col_of("residual_norm"),

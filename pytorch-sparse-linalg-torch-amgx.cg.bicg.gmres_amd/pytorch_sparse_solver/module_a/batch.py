@@ -1,12 +1,14 @@
-"""cg_batch / bicgstab_batch: S independent small systems that share ONE sparsity pattern.
+"""cg_batch / bicgstab_batch / gmres_batch: S independent small systems that share ONE sparsity pattern.
 
-`X[s]`, `info[s]` and the per-system statistics are what `cg(A_s, B[s], X0[s], ...)` (or `bicgstab`) returns for the CSR tensor A_s
-of system s, bit for bit.  Two routes compute them:
+`X[s]`, `info[s]` and the per-system statistics are what `cg(A_s, B[s], X0[s], ...)` (or `bicgstab`, `gmres`) returns for the CSR
+tensor A_s of system s, bit for bit.  Two routes compute them:
 
-  'kernel'  the batch kernels of libhipk.so (csrc/hipk_batch.hip): one 256-thread workgroup owns one system for its whole solve,
-            a launch covers all S systems.  Device operands, n <= 4096, at most 32 stored entries per row.
+  'kernel'  the batch kernels of libhipk.so (csrc/hipk_batch.hip, hipk_batch_gm.hip): one 256-thread workgroup owns one system for
+            its whole solve, a launch covers all S systems.  Device operands, n <= 4096, at most 32 stored entries per row;
+            gmres_batch: restart <= 31.
   'loop'    one public single solve per system: every input the single solvers accept, CPU tensors included.
-  'auto'    the kernel for device operands inside its envelope when S >= BATCH_MIN_SYSTEMS, else the loop.
+  'auto'    the kernel for device operands inside its envelope when S >= BATCH_MIN_SYSTEMS (gmres_batch: GMRES_BATCH_MIN_SYSTEMS),
+            else the loop.
 """
 from __future__ import annotations
 
@@ -16,7 +18,7 @@ from typing import Optional, Sequence, Tuple
 import torch
 
 from .preconditioners import JacobiPreconditioner
-from .torch_sparse_linalg import _set_stats, bicgstab, cg, get_last_stats
+from .torch_sparse_linalg import _set_stats, bicgstab, cg, get_last_stats, gmres
 
 # The smallest S at which 'auto' takes the batch kernels: the measured crossover (tools/batch_probe.py, profiles/batch_probe.txt;
 # DESIGN.md 7c).  One system alone is slower in the kernel than in the single solve's one-launch loop from n = 1024 on (0.26-0.8x:
@@ -168,7 +170,7 @@ def _check(name, A, B, X0, M, route):
                              f"(shape {tuple(A.shape)}, {A.device})")
 
 
-def _kernel_solve(kind, A: BatchedCSR, B, X0, tol, atol, maxiter, M):
+def _kernel_solve(kind, A: BatchedCSR, B, X0, tol, atol, maxiter, M, **gm):
     from .. import _hipk
     dt = A.dtype                                  # fp64, or fp32 storage when the matrices are fp32 (as the single solves)
     BB = _pad_rows(B.detach().to(dt))
@@ -179,24 +181,25 @@ def _kernel_solve(kind, A: BatchedCSR, B, X0, tol, atol, maxiter, M):
         if not _aligned_rows(X):
             X = _pad_rows(X)
     dinv = None if M is None else _pad_rows(M.dinv.detach().to(dt))
-    st = _hipk.solve_batch(kind, A.n, A.nnz, A.crow32, A.col32, A.kernel_values(), dinv, BB, X, tol=tol, atol=atol, maxiter=maxiter)
+    st = _hipk.solve_batch(kind, A.n, A.nnz, A.crow32, A.col32, A.kernel_values(), dinv, BB, X, tol=tol, atol=atol, maxiter=maxiter,
+                            **gm)
     return X.contiguous(), st
 
 
-def _loop_solve(kind, A: BatchedCSR, B, X0, tol, atol, maxiter, M):
+def _loop_solve(kind, A: BatchedCSR, B, X0, tol, atol, maxiter, M, **gm):
     from .. import _hipk
-    solver = cg if kind == "cg" else bicgstab
+    solver = {"cg": cg, "bicgstab": bicgstab, "gmres": gmres}[kind]
     xs, infos, stats = [], [], []
     t0 = time.perf_counter()
     for s in range(A.batch):
         x, info = solver(A.system(s), B[s].clone(), None if X0 is None else X0[s].clone(), tol=tol, atol=atol, maxiter=maxiter,
-                          M=None if M is None else M.system(s))
+                          M=None if M is None else M.system(s), **gm)
         xs.append(x)
         infos.append(int(info))
         stats.append(get_last_stats())
     ms = (time.perf_counter() - t0) * 1e3
     f = lambda name, default: [getattr(c, name, default) if c is not None else default for c in stats]
-    name = kind if M is None else {"cg": "pcg_jacobi", "bicgstab": "pbicgstab_jacobi"}[kind]
+    name = kind if M is None else {"cg": "pcg_jacobi", "bicgstab": "pbicgstab_jacobi", "gmres": "pgmres_jacobi"}[kind]
     st = _hipk.BatchSolveStats(method=f"{name}_batch", iterations=f("iterations", 0), matvecs=f("matvecs", 0), info=infos,
                                breakdown=f("breakdown", 0), b_norm=f("b_norm", 0.0), residual_norm=f("residual_norm", 0.0),
                                x_norm=f("x_norm", 0.0), threshold=f("threshold", 0.0), recurrence_rs=f("recurrence_rs", 0.0),
@@ -235,3 +238,39 @@ def bicgstab_batch(A: BatchedCSR, B: torch.Tensor, X0: Optional[torch.Tensor] = 
                    route: str = "auto") -> Tuple[torch.Tensor, torch.Tensor]:
     """BiCGStab for the S systems A_s X[s] = B[s] (see `cg_batch`); breakdowns (-10, -11) are decided per system."""
     return _batch("bicgstab", A, B, X0, tol, atol, maxiter, M, route)
+
+
+# The smallest S at which 'auto' takes hipk_gm_batch_kernel.  PROVISIONAL: the crossover measured for cg_batch / bicgstab_batch
+# (BATCH_MIN_SYSTEMS); no run of tools/gmres_batch_probe.py is recorded yet (DESIGN.md 7c), the value is to be set from its first one.
+GMRES_BATCH_MIN_SYSTEMS = 8
+
+
+def gmres_batch(A: BatchedCSR, B: torch.Tensor, X0: Optional[torch.Tensor] = None, *, tol: float = 1e-5, atol: float = 0.0,
+                restart: int = 20, maxiter: Optional[int] = None, M: Optional[BatchedJacobiPreconditioner] = None,
+                solve_method: str = "batched", route: str = "auto") -> Tuple[torch.Tensor, torch.Tensor]:
+    """Restarted GMRES for the S systems A_s X[s] = B[s] (see `cg_batch`): `maxiter` counts restart cycles, every system stops at its
+    own cycle and, with solve_method='incremental', at its own Arnoldi step inside a cycle; happy breakdown is decided per system.
+    The kernel route takes restart <= 31."""
+    from .. import _hipk
+    name = "gmres_batch"
+    _check(name, A, B, X0, M, route)
+    if int(restart) < 1:
+        raise ValueError(f"{name}: restart must be at least 1, got {restart}")
+    if solve_method not in ("batched", "incremental"):
+        raise ValueError(f"Unsupported solve_method: {solve_method}")
+    on_device = A.values.is_cuda
+    inside = A.in_envelope() and int(restart) <= _hipk.GMRES_BATCH_MAX_RESTART
+    if route == "kernel":
+        if not on_device:
+            raise ValueError(f"{name}: route='kernel' needs device tensors (A is on {A.device}); use route='loop'")
+        if not A.in_envelope():
+            raise ValueError(f"{name}: route='kernel' takes systems of at most 4096 rows with at most 32 stored entries per row "
+                             f"(n = {A.n}, longest row {A.max_row_len}); use route='loop'")
+        if not inside:
+            raise ValueError(f"{name}: route='kernel' takes a restart of at most {_hipk.GMRES_BATCH_MAX_RESTART} (restart = {restart}); "
+                             f"use route='loop'")
+    use_kernel = route == "kernel" or (route == "auto" and on_device and inside and A.batch >= GMRES_BATCH_MIN_SYSTEMS)
+    X, st = (_kernel_solve if use_kernel else _loop_solve)("gmres", A, B, X0, tol, atol, maxiter, M, restart=int(restart),
+                                                           solve_method=solve_method)
+    _set_stats(st)
+    return X, torch.tensor([int(i) for i in st.info], dtype=torch.int64)
