@@ -157,6 +157,10 @@ const char *hipk_last_solve_path(void);
  * hipk_solve_form_name(i), 0 <= i < hipk_solve_form_count(), enumerates every form of the single-device solvers (no GPU
  * needed); NULL outside that range. */
 const char *hipk_last_solve_form(void);
+/* The iterations of the calling thread's last hipk_cg_solve whose direction step (beta, p = r + beta p, the stop test) ran as the
+ * tail of the fused SpMV + update launch (hipk_cg_fuse_update_kernel) instead of a launch of its own; 0 when none did.  The note,
+ * path and form of such a solve are those of the fused sequence it is a variant of. */
+int hipk_last_cg_fused_directions(void);
 int hipk_solve_form_count(void);
 const char *hipk_solve_form_name(int i);
 /* mode 0: automatic (default); 1: never use the coded forms (A/B measurements, parity tests).

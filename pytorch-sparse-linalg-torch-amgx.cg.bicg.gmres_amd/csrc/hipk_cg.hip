@@ -16,6 +16,9 @@
 // average; hipk_cg_xflush_kernel after the loop adds the term an odd iteration count leaves owed.
 // On fp64 constant-coefficient stencils of those sizes K1 and K2 are ONE launch, hipk_cg_fuse_update_kernel (hipk_cg_fuse.h): Ap stays in
 // LDS, <p,Ap> crosses the workgroups inside the launch -- B_spmv - 8 n + 16 n bytes instead of B_spmv + 24 n.
+// With the x update deferred that launch also does K3 (its direction tail: <r,r> crosses the workgroups the same way, r_{k+1} is
+// still in registers): ONE launch per iteration, 16 n bytes for a p-only step and 40 n for one with x instead of 24 n and 48 n --
+// B_spmv + 36 n bytes per iteration on average.
 // Every workgroup re-derives alpha/beta from the chunk
 // partials of the previous kernel with the fixed tree, so no grid barrier, no atomics
 // and no host round trip are needed; the host follows the loop through a pinned word the direction kernel
@@ -64,6 +67,15 @@ struct hipk_cg_scal {
 };
 static_assert(sizeof(hipk_cg_scal) <= 256, "the scalar block is 256 bytes");
 #include "hipk_cg_mid.h"   // one-launch loop for mid-size systems (uses hipk_lds_ctl)
+// the bookkeeping of every deferred-x K3 and of the fused launch's direction tail (hipk_cg_fuse.h, hence up here): gamma of the
+// next pass, the stop test, the host's signal word (TSL:853, 841)
+__device__ __forceinline__ void hipk_cg_dir_done(hipk_cg_scal *scal, int64_t it, int64_t maxiter, double rr) {
+    scal->gamma[(it + 1) & 1] = rr;  // TSL:853
+    // TSL:841 for the NEXT pass: stop when k+1 >= maxiter or rs <= atol2 (workgroups of THIS launch compare against `it`)
+    const bool done = (it + 1 >= maxiter || rr <= scal->atol2);
+    if (done) scal->stop_it = it + 1;
+    hipk_signal(scal->host_sig, done ? (HIPK_SIG_STOP | (it + 1)) : (it + 1));
+}
 #include "hipk_cg_fuse.h"  // the stencil SpMV and the update step in one launch (uses hipk_cg_scal)
 
 // gamma0 = <r0,r0>, bs = <b,b>, atol2; p = r0.
@@ -219,14 +231,6 @@ __global__ __launch_bounds__(HIPK_THREADS) void hipk_cg_direction_kernel(
 // order and with its roundings: x = (x + alpha_{k-1} p_{k-1}) + alpha_k p_k, each product and each sum rounded on its own -- the
 // bits two successive `x += alpha p` give.  p ping-pongs between two buffers so that p_{k-1} is still there; the alphas come from
 // scal->alpha (hipk_cg_update_kernel's alpha_out), so no K3 folds part_pAp.
-// the bookkeeping of every K3: gamma of the next pass, the stop test, the host's signal word (TSL:853, 841)
-__device__ __forceinline__ void hipk_cg_dir_done(hipk_cg_scal *scal, int64_t it, int64_t maxiter, double rr) {
-    scal->gamma[(it + 1) & 1] = rr;  // TSL:853
-    // TSL:841 for the NEXT pass: stop when k+1 >= maxiter or rs <= atol2 (workgroups of THIS launch compare against `it`)
-    const bool done = (it + 1 >= maxiter || rr <= scal->atol2);
-    if (done) scal->stop_it = it + 1;
-    hipk_signal(scal->host_sig, done ? (HIPK_SIG_STOP | (it + 1)) : (it + 1));
-}
 
 // hipk_reduce_parts with this thread's partials requested EARLY, all at once: the fold's own loads are eight dependent round trips
 // when each waits for the one before (the compiler does not hoist a load out of its `i < g`), and a wait for any of them is a
@@ -389,7 +393,10 @@ __global__ __launch_bounds__(HIPK_THREADS) void hipk_cg_xdir_kernel(int64_t n, i
 // buffer the sequence began with (K - 1 - it0 is even; the launches past the stop were no-ops).  Even, or K <= it0: nothing to do.
 template <typename T>
 __global__ __launch_bounds__(HIPK_THREADS) void hipk_cg_xflush_kernel(int64_t n, int ch, const hipk_cg_scal *__restrict__ scal, int64_t it_host,
-                                                                      int64_t it0, const T *__restrict__ p_first, T *__restrict__ x) {
+                                                                      int64_t it0, const T *__restrict__ p_first, T *__restrict__ x,
+                                                                      int dir_tail = 0) {
+    // (the direction tail of the fused launch gave up: iteration stop_it is half done, hipk_cg_steps::fuse_end settles x)
+    if (dir_tail && scal->ctl.redo == kFuseDirGaveUp) return;
     const int64_t stop = scal->stop_it;
     const int64_t K = stop < it_host ? stop : it_host;
     if (K <= it0 || ((K - it0) & 1) == 0) return;
@@ -1187,14 +1194,17 @@ struct hipk_cg_layout {
     bool fourth_vector;
     size_t p2;
     // The fused SpMV + update launch (hipk_cg_fuse.h) keeps Ap on chip, so the head of Ap is its own: the chunks' flagged <p,Ap>
-    // words, then the collector's replicas -- one region, cleared by one memset when the sequence begins.  (Not in the partial
+    // words, then the collector's replicas, then the same again for the <r,r> of the direction tail (the kernel finds the second
+    // pair behind the first) -- one region, cleared by one memset when the sequence begins.  (Not in the partial
     // slots: hipk_cg_direction_kernel folds the plain <p,Ap> partials from part_a, which the fused launch therefore still writes.)
     // A sequence of the separate kernels that takes over after a give-up writes Ap again; the fused form is not tried again then.
     size_t fuse_words, fuse_ctl;
     size_t total;
 };
-static constexpr size_t kFuseBytes = kFuseWordsBytes + kFuseCtlBytes;
+static constexpr size_t kFuseBytes = 2 * (kFuseWordsBytes + kFuseCtlBytes);   // <p,Ap>'s words and replicas, then <r,r>'s (the direction tail)
 static_assert(kFuseWordsBytes % 256 == 0 && kFuseCtlBytes == 8 * 16 * kFuseReplicaSlots, "the replicas follow the words, 128 bytes apart");
+static_assert(kFuseBytes == 2 * (kFuseWordsBytes + kFuseCtlBytes) && (kFuseWordsBytes + kFuseCtlBytes) % 256 == 0,
+              "the direction tail's words and replicas follow the first pair, laid out the same");
 static_assert(kFuseBytes <= (size_t)kMidMaxChunks * HIPK_BASE_CHUNK * sizeof(double),
               "the fused form runs beyond the mid loop's chunk count, fp64: Ap is longer than its region");
 static constexpr size_t kMidSlotArray = (size_t)kMidMaxChunks * 256;   // a slot array of the mid loop at the widest slot stride
@@ -1263,6 +1273,7 @@ struct hipk_cg_path {
     bool two_launch = false;   // plain CG: hipk_cg2_spmv_kernel + hipk_cg2_update_kernel per iteration
     bool defer_x = false;      // plain CG, three launches: x updated every second iteration (hipk_cg_pdir_kernel / hipk_cg_xdir_kernel)
     bool fuse_update = false;  // plain CG, fp64 stencils: SpMV and update step in one launch (hipk_cg_fuse_update_kernel), two launches in all
+    bool fuse_dir = false;     // ... and, with the x update deferred, the direction step as that launch's tail: one launch in all
     void (*fuse_kern)(hipk_spmv_args, hipk_cg_fuse_args) = nullptr;
     hipk_spmv_args fuse_sa;    // ... its SpMV arguments, as hipk_launch_spmv fills them for the kernel it replaces
 };
@@ -1351,12 +1362,14 @@ static void hipk_cg_path_defer(hipk_cg_path &path, const hipk_csr_s *A, const hi
 // tests/test_gpu_cg_fuse_update.py reads the compiler's report -- because that API answers 8 where the chip admits 7 above 80
 // SGPRs: DESIGN section 9); the launch's sequence number fits 31 bits; the collector never gave up on this handle;
 // HIPK_CG_FUSE_UPDATE=0|1 forces (read per solve).
+// fuse_dir: with the x update deferred (path.defer_x) the direction step runs as that launch's tail, same envelope;
+// HIPK_CG_FUSE_DIRECTION=0|1 forces (read per solve).
 // No gate by chunk count inside that envelope: every run beat every run of the separate kernels at 591, 958 and 1954 chunks (+2 %,
 // +6 %, +11.7 %: profiles/cg_fuse_update_ab.md).
 template <typename T>
 static void hipk_cg_path_fuse(hipk_cg_path &path, hipk_csr_s *A, const hipk_params *prm, bool done, int64_t it, int64_t maxiter,
                               const hipk_spmv_args &sa) {
-    path.fuse_update = false;
+    path.fuse_update = path.fuse_dir = false;
     if (sizeof(T) != 8 || done || path.two_launch || path.small || path.streams || A->op_cb != nullptr || prm->profile != 0 ||
         A->geom.ch != HIPK_BASE_CHUNK || A->geom.g <= kMidMaxChunks || A->cg_fuse_failed || maxiter - it >= ((int64_t)1 << 31) ||
         !hipk_sw_force("HIPK_CG_FUSE_UPDATE", true))
@@ -1368,6 +1381,7 @@ static void hipk_cg_path_fuse(hipk_cg_path &path, hipk_csr_s *A, const hipk_para
                           (int64_t)occ * A->n_cu >= A->geom.g;
     (void)hipGetLastError();
     path.fuse_update = resident;
+    path.fuse_dir = resident && path.defer_x && hipk_sw_force("HIPK_CG_FUSE_DIRECTION", true);
 }
 
 // {redo, it_done, stop_it} of a host copy of hipk_cg_scal / hipk_pcg_scal (hipk_resident_run)
@@ -1766,6 +1780,11 @@ __global__ __launch_bounds__(HIPK_THREADS) void hipk_pcg_final_kernel(hipk_pcg_s
     }
 }
 
+// hipk_last_cg_fused_directions (include/hipk.h): the iterations of this thread's last CG solve whose direction step ran as the
+// tail of hipk_cg_fuse_update_kernel
+static thread_local int64_t hipk_cg_fused_directions = 0;
+extern "C" int hipk_last_cg_fused_directions(void) { return (int)(hipk_cg_fused_directions > INT32_MAX ? INT32_MAX : hipk_cg_fused_directions); }
+
 // what the three-launch sequence of plain CG launches for its update and direction steps (hipk_cg_steps::pick)
 template <typename T>
 struct hipk_cg_kernels {
@@ -2028,6 +2047,11 @@ struct hipk_cg_steps {
             HIPK_CHECK_HIP(pace.gate(it, stream, &stop));
             if (stop <= it) break;
             const int j = (int)((it - it0) & 1);
+            if (path.fuse_dir) {   // one launch: the direction step is its tail (odd j: with the x part)
+                fuse_launch(it0, pbuf[j], pbuf[j ^ 1], j ? x : nullptr);
+                if ((it & 63) == 63) HIPK_CHECK_HIP(hipGetLastError());
+                continue;
+            }
             if (path.fuse_update) {
                 fuse_launch(it0, pbuf[j]);
             } else {
@@ -2043,8 +2067,8 @@ struct hipk_cg_steps {
             if ((it & 63) == 63) HIPK_CHECK_HIP(hipGetLastError());
         }
         // an odd number of iterations: the last one's x update is still owed (the device knows how many were completed)
-        hipk_cg_xflush_kernel<T><<<gm.g, HIPK_THREADS, 0, stream>>>(n, gm.ch, scal, it, it0, pbuf[0], x);
-        return path.fuse_update ? fuse_end(it0, true) : HIPK_OK;
+        hipk_cg_xflush_kernel<T><<<gm.g, HIPK_THREADS, 0, stream>>>(n, gm.ch, scal, it, it0, pbuf[0], x, path.fuse_dir ? 1 : 0);
+        return path.fuse_update ? fuse_end(it0, true, pbuf) : HIPK_OK;
     }
 
     // ---- hipk_cg_fuse_update_kernel in place of the SpMV and the update launch (hipk_cg_path_fuse)
@@ -2054,6 +2078,8 @@ struct hipk_cg_steps {
         HIPK_CHECK_HIP(hipMemsetAsync(&scal->ctl, 0, sizeof(hipk_lds_ctl), stream));
         // tests: HIPK_TEST_CG_FUSE_GIVE_UP=k makes the collector of iteration k behave as if its poll had run out
         fuse_give_up_at = hipk_sw_present("HIPK_TEST_CG_FUSE_GIVE_UP") ? hipk_sw_int("HIPK_TEST_CG_FUSE_GIVE_UP", -1) : -1;
+        // ... HIPK_TEST_CG_FUSE_DIR_GIVE_UP=k the collector of its second hand-off (the direction tail)
+        fuse_dir_give_up_at = hipk_sw_present("HIPK_TEST_CG_FUSE_DIR_GIVE_UP") ? hipk_sw_int("HIPK_TEST_CG_FUSE_DIR_GIVE_UP", -1) : -1;
         fuse_note();
         return HIPK_OK;
     }
@@ -2064,7 +2090,8 @@ struct hipk_cg_steps {
         hipk_note_spmv_kernel(name);
     }
     // iteration `it` of a sequence that began at it0: Ap = A pk on chip, alpha, r -= alpha Ap, the partials of <r,r>
-    void fuse_launch(int64_t it0, const T *pk) {
+    // p_next (the direction tail): p_{it+1} = r + beta pk into it, the next pass's gamma, the stop test; xq: also the x part
+    void fuse_launch(int64_t it0, const T *pk, T *p_next = nullptr, T *xq = nullptr) {
         hipk_spmv_args fa = path.fuse_sa;
         fa.it = it;
         fa.x = fa.w = pk;
@@ -2077,33 +2104,52 @@ struct hipk_cg_steps {
         ff.ctl = hipk_at<char>(work, lay.fuse_ctl);
         ff.seq = (unsigned)(it - it0) + 1u;
         ff.give_up = it == fuse_give_up_at ? 1 : 0;
+        ff.p_next = (double *)p_next;
+        ff.x = (double *)xq;
+        ff.maxiter = maxiter;
+        ff.dir_give_up = p_next != nullptr && it == fuse_dir_give_up_at ? 1 : 0;
         path.fuse_kern<<<hipk_xcd_grid(gm.g), HIPK_THREADS, 0, stream>>>(fa, ff);
     }
     // the sequence has ended: HIPK_OK, or HIPK_HANDED_BACK when the collector gave up at some iteration -- the state is that
     // iteration's, the latch is set on the handle, the stop word and the pacer are rearmed, and the caller goes on from `it` with
     // the separate kernels.  deferred: the flush has brought x up to date; p of that iteration is where its parity put it
-    int fuse_end(int64_t it0, bool deferred) {
+    // The collector of the direction tail gave up (ctl.redo = kFuseDirGaveUp) at iteration K = stop_it, j = K - it0 into the sequence:
+    // r, part_rr and alpha_K are K's, p_{K+1} is not stored, the flush has done nothing.  hipk_cg_pdir_kernel finishes K from
+    // pbuf[j & 1] into the other buffer (and does its bookkeeping), and the caller goes on at K + 1 with p_{K+1} there.  x: odd j,
+    // the tail's x part has brought it up to date through K; even j, it lacks alpha_K p_K only, which the flush kernel adds as
+    // the one owed term of a sequence of one iteration begun at K -- so the sequence that goes on owes nothing.
+    int fuse_end(int64_t it0, bool deferred, T *const *pbuf = nullptr) {
         S hs;
         HIPK_CHECK_HIP(hipGetLastError());
         HIPK_CHECK_HIP(hipMemcpyAsync(&hs, scal, sizeof(hs), hipMemcpyDeviceToHost, stream));
         HIPK_CHECK_HIP(hipStreamSynchronize(stream));
+        const int64_t ran = (hs.stop_it < it ? hs.stop_it : it) - it0;   // iterations this sequence completed
+        if (path.fuse_dir) hipk_cg_fused_directions += ran > 0 ? ran : 0;
         if (hs.ctl.redo == -3) {
             hipk_set_error("hipk_cg_solve: the collector of the fused SpMV + update launch stopped arriving");
             return HIPK_ERR_HIP;
         }
-        if (hs.ctl.redo != -1) return HIPK_OK;
+        const bool dir_gave_up = path.fuse_dir && hs.ctl.redo == kFuseDirGaveUp;
+        if (hs.ctl.redo != -1 && !dir_gave_up) return HIPK_OK;
         A->cg_fuse_failed = 1;
-        path.fuse_update = false;
-        if (deferred) p_first ^= (int)((hs.stop_it - it0) & 1);
+        path.fuse_update = path.fuse_dir = false;
         it = hs.stop_it;
         stop = INT64_MAX;
         HIPK_CHECK_HIP(hipMemcpyAsync(&scal->stop_it, &stop, sizeof(int64_t), hipMemcpyHostToDevice, stream));
         HIPK_CHECK_HIP(hipMemsetAsync(&scal->ctl, 0, sizeof(hipk_lds_ctl), stream));
         HIPK_CHECK_HIP(hipStreamSynchronize(stream));
         HIPK_CHECK_HIP(pace.resume(it));
+        if (dir_gave_up) {
+            const int j = (int)((it - it0) & 1);
+            hipk_cg_pdir_kernel<T><<<gm.g, HIPK_THREADS, 0, stream>>>(n, gm.ch, gm.g, scal, it, maxiter, part_b, r, pbuf[j], pbuf[j ^ 1]);
+            if (j == 0) hipk_cg_xflush_kernel<T><<<gm.g, HIPK_THREADS, 0, stream>>>(n, gm.ch, scal, it + 1, it, pbuf[0], x);
+            HIPK_CHECK_HIP(hipGetLastError());
+            ++it;
+        }
+        if (deferred) p_first ^= (int)((it - it0) & 1);
         return HIPK_HANDED_BACK;
     }
-    int64_t fuse_give_up_at = -1;
+    int64_t fuse_give_up_at = -1, fuse_dir_give_up_at = -1;
 
     // the kernels of the plain three-launch sequence (hipk_cg_path: small / streams / flat_dir) and the form they make
     hipk_cg_kernels<T> pick() const {
@@ -2200,6 +2246,7 @@ template <typename T>
 static int hipk_cg_solve_t(hipk_csr_s *A, const T *b, T *x, char *work, const hipk_params *prm, hipk_stats *st, hipStream_t stream) {
     static bool mid_failed = false, lds_loop_failed = false;   // per dtype; hipk_pcg_solve_t has its own
     hipk_cg_steps<T, false> s(A, nullptr, b, x, work, prm, stream, prm->profile);
+    hipk_cg_fused_directions = 0;
     HIPK_TRY(s.start());
     HIPK_TRY(s.one_launch(mid_failed, lds_loop_failed, "hipk_cg_solve"));
     // what is left when neither loop finished: two launches per iteration, else three with the x update deferred, else three

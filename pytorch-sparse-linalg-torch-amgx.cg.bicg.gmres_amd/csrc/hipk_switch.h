@@ -53,6 +53,8 @@ static constexpr hipk_sw_row hipk_switches[] = {
     {"HIPK_CG_TWO_LAUNCH", HIPK_SW_OFF_IF_0, "on", "each plain CG solve", "0: the three-launch iteration instead of hipk_cg2_spmv_kernel + hipk_cg2_update_kernel", "test, tools A/B"},
     {"HIPK_CG_DEFER_X", HIPK_SW_OFF_IF_0, "on", "each plain CG solve", "0: every direction launch updates x (hipk_cg_direction_kernel)", "test, tools A/B"},
     {"HIPK_CG_FUSE_UPDATE", HIPK_SW_FORCE01, "automatic", "each plain CG solve", "0 | 1: the SpMV and the update step as two launches | as hipk_cg_fuse_update_kernel where the form applies (unset: fused where it applies)", "test, tools A/B"},
+    {"HIPK_CG_FUSE_DIRECTION", HIPK_SW_FORCE01, "automatic", "each plain CG solve", "0 | 1: the direction step of the fused deferred-x sequence as hipk_cg_pdir_kernel / hipk_cg_xdir_kernel launches | as the tail of hipk_cg_fuse_update_kernel where the form applies (unset: the tail where it applies)", "test, tools A/B"},
+    {"HIPK_TEST_CG_FUSE_DIR_GIVE_UP", HIPK_SW_INT, "unset", "each fused CG sequence", "k: the collector of the direction tail's hand-off at iteration k behaves as if its poll had run out (the solve goes on with the separate kernels)", "test"},
     {"HIPK_TEST_CG_FUSE_GIVE_UP", HIPK_SW_INT, "unset", "each fused CG sequence", "k: the collector of hipk_cg_fuse_update_kernel at iteration k behaves as if its poll had run out (the solve goes on with the separate kernels)", "test"},
     {"HIPK_CG_STREAMS", HIPK_SW_FORCE01, "automatic", "each plain CG solve", "0 | 1: force the vector kernels' cache policy (unset: streams when x, r, p, Ap exceed 384 MiB)", "test"},
     {"HIPK_CG_FLAT_DIRECTION", HIPK_SW_FORCE01, "automatic", "each plain CG solve", "0 | 1: with the streaming policy, the direction step per chunk | as scalars launch + flat grid (unset: flat when a vector exceeds 256 MiB)", "test, tools A/B"},
