@@ -1,8 +1,8 @@
 """The case table of cg_batch / bicgstab_batch (tests/test_batch_cases.py checks it on the CPU oracle, tests/test_gpu_batch.py runs
 every case through the batch kernels).
 
-A case: id, solver ('cg' | 'bicgstab'), dtype ('f64' | 'f32'), pre (Jacobi), the pattern (a grid of the project's generators, or a
-dense n x n pattern), S, the x0 kind ('none' | 'random' | 'exact': the exact solution of system 1, so that system alone runs 0
+A case: id, solver ('cg' | 'bicgstab'), dtype ('f64' | 'f32'), pre (Jacobi), the pattern (a grid of the project's generators, a
+dense n x n pattern, or `pattern` + `transform` of tests/_batch_patterns.py: general rows of 1 to 32 entries in stored order), S, the x0 kind ('none' | 'random' | 'exact': the exact solution of system 1, so that system alone runs 0
 iterations), keyword arguments, environment and the path string the kernel route must report.  S > 4 cycles the four matrices with
 fresh seeded right-hand sides.  `kernel` False: the case lies outside the kernel's envelope ('auto' loops, 'kernel' raises)."""
 import json
@@ -27,6 +27,8 @@ class Case:
     pre: bool
     grid: tuple = None        # (nx, ny), or None for a dense pattern
     dense: str = None         # 'spd1' | 'spd2' | 'spd3' | 'bd-10' | 'bd-11'
+    pattern: tuple = None     # ('rag31', n) | ('rag32', n) | ('dense32',) | ('empty', n) of tests/_batch_patterns.py
+    transform: str = None     # a key of tests/_order_cases.TRANSFORMS, applied to `pattern`
     S: int = 4
     x0: str = "none"
     kwargs: dict = field(default_factory=dict)
@@ -49,6 +51,29 @@ class Case:
 def _c(solver, dtype, pre, grid, S=4, x0="none", tag="", **kw):
     name = f"{solver}{'-jac' if pre else ''}-{dtype}-{grid[0]}x{grid[1]}-S{S}-x0{x0}{tag}"
     return Case(id=name, solver=solver, dtype=dtype, pre=pre, grid=grid, S=S, x0=x0, **kw)
+
+
+def _p(solver, dtype, pre, pattern, transform, S=4, x0="none", tag="", **kw):
+    name = f"{solver}{'-jac' if pre else ''}-{dtype}-{'n'.join(str(v) for v in pattern)}-{transform or 'sorted'}-S{S}-x0{x0}{tag}"
+    return Case(id=name, solver=solver, dtype=dtype, pre=pre, pattern=pattern, transform=transform, S=S, x0=x0, **kw)
+
+
+def _pattern_cases(solver, tol32=None):
+    """The pattern axis for one solver: rows of 1 .. 32 entries, unsorted, repeated, a stored zero, an empty row (n = 300: two tiles,
+    the second of 44 rows; n = 2049: nine tiles, a second reduction chunk of one row; dense 32: every row at the bound)."""
+    kw32 = {} if tol32 is None else {"kwargs": {"tol": tol32}}
+    return [
+        _p(solver, "f64", False, ("rag31", 300), "dup_shuf"),
+        _p(solver, "f64", True, ("rag31", 300), "dup_diag", x0="random"),
+        _p(solver, "f32", False, ("rag31", 2049), "shuf", S=5, **kw32),
+        _p(solver, "f32", True, ("rag31", 2049), "dup_diag", **kw32),
+        _p(solver, "f64", False, ("rag31", 2049), "zero", x0="exact"),
+        _p(solver, "f64", True, ("rag31", 2049), "rev"),                    # nnz odd: the padded copy of `values`
+        _p(solver, "f64", False, ("rag32", 300), "shuf"),                   # rows of 1 and of 32 entries in one wavefront
+        _p(solver, "f64", False, ("dense32",), "rev", S=2),
+        _p(solver, "f64", False, ("empty", 300), None, tag="-maxiter4", kwargs={"maxiter": 4}),
+        _p(solver, "f64", False, ("dense32",), "dup", S=2, kernel=False),   # 33 entries per row: 'auto' loops, 'kernel' raises
+    ]
 
 
 CASES = [
@@ -90,12 +115,20 @@ CASES = [
     # ---- outside the envelope: 'auto' takes the loop, 'kernel' raises
     _c("cg", "f64", False, (17, 241), S=2, kernel=False, kwargs={"maxiter": 20}),
 ]
+# fp32 BiCGStab on rag31(2049) stagnates above TOL['f32'] on the oracle (relative residuals 1.4e-5 .. 2.8e-5, breakdown -11, info -1);
+# at 1e-4 every system of both fp32 cases ends with info 0 and no breakdown (tests/test_batch_cases.py asserts it)
+PATTERN_TOL32 = {"cg": None, "bicgstab": 1e-4}
+CASES += _pattern_cases("cg", PATTERN_TOL32["cg"]) + _pattern_cases("bicgstab", PATTERN_TOL32["bicgstab"])
+PATTERN_CASES = [c for c in CASES if c.pattern]
 BY_ID = {c.id: c for c in CASES}
 # the cases that also run with HIPK_BATCH_LAUNCH_ITS = 7 and = 1 (every instantiation's save / resume path; > 1 launch each)
 BUDGET_IDS = ["cg-f64-7x5-S4-x0none", "cg-jac-f64-16x16-S4-x0none", "cg-f32-41x25-S4-x0random", "cg-jac-f32-41x25-S4-x0none",
               "cg-f64-45x45-S4-x0random", "bicgstab-f64-7x5-S4-x0none", "bicgstab-jac-f64-7x5-S5-x0random",
               "bicgstab-f32-41x25-S4-x0random", "bicgstab-jac-f32-16x16-S4-x0none", "bicgstab-jac-f64-41x25-S4-x0none",
-              "bicgstab-f64-16x16-S5-x0none-b0", "cg-f32-48x48-S5-x0none", "bicgstab-jac-f32-64x32-S4-x0random"]
+              "bicgstab-f64-16x16-S5-x0none-b0", "cg-f32-48x48-S5-x0none", "bicgstab-jac-f32-64x32-S4-x0random",
+              # the pattern axis: a Jacobi case with 32-entry rows and a diagonal stored twice, and n = 2049 (the second chunk)
+              "cg-jac-f64-rag31n300-dup_diag-S4-x0random", "cg-f32-rag31n2049-shuf-S5-x0none",
+              "bicgstab-jac-f64-rag31n300-dup_diag-S4-x0random", "bicgstab-f32-rag31n2049-shuf-S5-x0none"]
 
 
 def _np_dtype(case):
@@ -119,7 +152,12 @@ def build(case):
     """-> dict crow, col (int32), vals (S, nnz), B (S, n), X0 ((S, n) or None), all numpy in the case's dtype."""
     dt = _np_dtype(case)
     rng = np.random.default_rng([zlib.crc32(case.id.encode()), 7])
-    if case.dense:
+    if case.pattern:
+        from _batch_patterns import build_pattern
+        crow, col, vals = build_pattern(case.pattern, case.transform, case.solver, case.S, rng)
+        n = crow.size - 1
+        B = rng.standard_normal((case.S, n))
+    elif case.dense:
         if case.dense.startswith("bd"):
             d = json.load(open(os.path.join(GOLDEN, "bicgstab_breakdown.json")))[case.dense[2:]]
             M0 = np.array(d["A"], dtype=np.float64)

@@ -2,7 +2,8 @@
 case through hipk_gm_batch_kernel).
 
 A case: id, dtype ('f64' | 'f32'), pre (Jacobi), restart, method ('batched' | 'incremental'), the pattern (a convection-diffusion
-grid, or a dense n x n pattern), S, the x0 kind ('none' | 'random' | 'exact': the exact solution of system 1, which then runs 0
+grid, a dense n x n pattern, or `pattern` + `transform` of tests/_batch_patterns.py: general rows of 1 to 32 entries in stored
+order), S, the x0 kind ('none' | 'random' | 'exact': the exact solution of system 1, which then runs 0
 cycles and 2 operator applications), keyword arguments and the path string the kernel route must report.  S > 4 cycles the four
 matrices with fresh seeded right-hand sides.  `special`: system 0 of the 7 x 5 pattern has only a constant diagonal ('diag': happy
 breakdown at step 1) or only zeros ('zero': a zero column in H; 'batched' meets a zero Cholesky pivot) with b = ones, next to a partner
@@ -26,6 +27,8 @@ class Case:
     method: str
     grid: tuple = None        # (nx, ny), or None for a dense pattern
     dense: int = None         # n of a dense pattern
+    pattern: tuple = None     # ('rag31', n) | ('rag32', n) | ('dense32',) | ('empty', n) of tests/_batch_patterns.py
+    transform: str = None     # a key of tests/_order_cases.TRANSFORMS, applied to `pattern`
     S: int = 4
     x0: str = "none"
     kwargs: dict = field(default_factory=dict)
@@ -53,6 +56,12 @@ def _c(dtype, pre, grid, restart, method, S=4, x0="none", tag="", **kw):
 def _d(dtype, pre, n, restart, method):
     return Case(id=f"gmres{'-jac' if pre else ''}-{dtype}-dense{n}-r{restart}-{method[0]}", dtype=dtype, pre=pre, restart=restart,
                 method=method, dense=n, S=2)
+
+
+def _p(dtype, pre, pattern, transform, restart, method, S=4, x0="none", tag="", **kw):
+    name = (f"gmres{'-jac' if pre else ''}-{dtype}-{'n'.join(str(v) for v in pattern)}-{transform or 'sorted'}-r{restart}-{method[0]}"
+            f"-S{S}-x0{x0}{tag}")
+    return Case(id=name, dtype=dtype, pre=pre, restart=restart, method=method, pattern=pattern, transform=transform, S=S, x0=x0, **kw)
 
 
 B, I = "batched", "incremental"
@@ -87,20 +96,37 @@ CASES = [
     # ---- outside the envelope: 'auto' takes the loop, 'kernel' raises
     _c("f64", False, (16, 16), 32, B, S=2, kernel=False),
     _c("f64", False, (17, 241), 5, B, S=2, kernel=False, kwargs={"maxiter": 4}),
+    # ---- the pattern axis: rows of 1 .. 32 entries, unsorted, repeated, a stored zero, an empty row (n = 300: two tiles, the second
+    # of 44 rows; n = 2049: nine tiles, a second reduction chunk of one row; dense 32: every row at the bound)
+    _p("f64", False, ("rag31", 300), "dup_shuf", 10, I), _p("f64", True, ("rag31", 300), "dup_diag", 10, B, x0="random"),
+    _p("f32", False, ("rag31", 2049), "shuf", 10, I, S=5), _p("f32", True, ("rag31", 2049), "dup_diag", 10, B),
+    _p("f64", False, ("rag31", 2049), "zero", 10, I, x0="exact"),
+    _p("f64", True, ("rag31", 2049), "rev", 10, B),                             # nnz odd: the padded copy of `values`
+    _p("f64", False, ("rag32", 300), "shuf", 10, B),                            # rows of 1 and of 32 entries in one wavefront
+    _p("f64", False, ("dense32",), "rev", 8, I, S=2),
+    _p("f64", False, ("empty", 300), None, 5, B, tag="-maxiter2", kwargs={"maxiter": 2}),
+    _p("f64", False, ("dense32",), "dup", 5, B, S=2, kernel=False),             # 33 entries per row: 'auto' loops, 'kernel' raises
 ]
+PATTERN_CASES = [c for c in CASES if c.pattern]
 BY_ID = {c.id: c for c in CASES}
 # the cases that also run with HIPK_BATCH_LAUNCH_ITS = 7 and = 1 (every instantiation, both methods; > 1 launch each)
 BUDGET_IDS = ["gmres-f64-7x5-r5-b-S4-x0none", "gmres-f64-7x5-r1-i-S4-x0none", "gmres-jac-f64-7x5-r2-b-S5-x0random",
               "gmres-f32-7x5-r5-i-S2-x0none", "gmres-jac-f64-16x16-r20-i-S4-x0none", "gmres-jac-f32-257x1-r8-b-S4-x0random",
               "gmres-f32-41x25-r9-b-S4-x0random", "gmres-jac-f32-41x25-r30-i-S4-x0none", "gmres-f64-683x3-r7-b-S4-x0none",
-              "gmres-f64-64x64-r20-b-S4-x0none", "gmres-jac-f64-16x16-r8-b-S5-x0none-b0"]
+              "gmres-f64-64x64-r20-b-S4-x0none", "gmres-jac-f64-16x16-r8-b-S5-x0none-b0",
+              # the pattern axis: a Jacobi case with 32-entry rows and a diagonal stored twice, and n = 2049 (the second chunk)
+              "gmres-jac-f64-rag31n300-dup_diag-r10-b-S4-x0random", "gmres-f32-rag31n2049-shuf-r10-i-S5-x0none"]
 
 
 def build(case):
     """-> dict crow, col (int32), vals (S, nnz), B (S, n), X0 ((S, n) or None), all numpy in the case's dtype."""
     dt = _np_dtype(case)
     rng = np.random.default_rng([zlib.crc32(case.id.encode()), 11])
-    if case.dense:
+    if case.pattern:
+        from _batch_patterns import build_pattern
+        crow, col, vals = build_pattern(case.pattern, case.transform, "gmres", case.S, rng)
+        n = crow.size - 1
+    elif case.dense:
         n = case.dense
         mats = [(3.0 + s) * np.eye(n) + 0.5 * np.ones((n, n)) + 0.25 * np.triu(np.ones((n, n)), 1) for s in range(case.S)]
         crow, col = _dense_pattern(n)

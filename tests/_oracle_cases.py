@@ -51,6 +51,15 @@ def _ldc(nx):
     return M
 
 
+def _row_sums(a, indptr):
+    """Per row the sum of its entries of `a`, 0 for a row without stored entries (np.add.reduceat alone gives a[indptr[i]] there)."""
+    out = np.zeros(len(indptr) - 1, dtype=a.dtype)
+    ne = np.flatnonzero(np.diff(indptr) > 0)
+    if ne.size:
+        out[ne] = np.add.reduceat(a, indptr[:-1][ne])
+    return out
+
+
 def _check_stats_long_double(solver, dt, M, dinv, b, x, st, kw):
     """The returned stats against long-double arithmetic on the stored A, b, (dinv) and the returned x.
 
@@ -67,8 +76,8 @@ def _check_stats_long_double(solver, dt, M, dinv, b, x, st, kw):
     ld = np.longdouble
     xl, bl, vl = x.astype(ld), b.astype(ld), M.data.astype(ld)
     dl = np.ones(n, dtype=ld) if dinv is None else dinv.astype(ld)
-    Ax = np.add.reduceat(vl * xl[M.indices], M.indptr[:-1])
-    aAx = np.add.reduceat(np.abs(vl) * np.abs(xl[M.indices]), M.indptr[:-1])
+    Ax = _row_sums(vl * xl[M.indices], M.indptr)
+    aAx = _row_sums(np.abs(vl) * np.abs(xl[M.indices]), M.indptr)
     b_norm = np.sqrt(np.sum(bl * bl))
     assert abs(st.b_norm - b_norm) <= gn * b_norm, (st.b_norm, b_norm)
     tolf = float(np.float32(kw["tol"]))

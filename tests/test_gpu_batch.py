@@ -1,19 +1,23 @@
 """cg_batch / bicgstab_batch on the GPU: every case of tests/_batch_cases.py through the batch kernels (csrc/hipk_batch.hip), bitwise
 against the CPU oracle per system; the three routes and the launch budgets agree; the C entry points keep the memory contract."""
 import ctypes
+from types import SimpleNamespace
 
 import numpy as np
 import pytest
+import scipy.sparse as sp
 import torch
 
 import _batch_cases as BC
 from _arena import Arena, check_memory, guard_bytes_for, run_states
+from _oracle_cases import _check_stats_long_double
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 KERNEL_CASES = [c for c in BC.CASES if c.kernel]
 # the loop route runs S single solves per case (the 300- and 1030-system batches included: about a second each)
 LOOP_CASES = KERNEL_CASES
+PATTERN_KERNEL_CASES = [c for c in BC.PATTERN_CASES if c.kernel]
 
 
 def _bits(a):
@@ -86,6 +90,49 @@ def test_batched_jacobi_matches_the_single_preconditioner(hipk):
             assert torch.equal(M.dinv[s], JacobiPreconditioner(A.system(s)).dinv)
 
 
+def check_jacobi_vectors_on_repeated_diagonals(data):
+    """dinv[s] of the batch preconditioner is bitwise the single one's where a diagonal is stored twice, in both dtypes."""
+    from pytorch_sparse_solver.module_a import BatchedCSR, BatchedJacobiPreconditioner, JacobiPreconditioner
+    rows = np.repeat(np.arange(data["n"]), np.diff(data["crow"]))
+    assert np.bincount(rows[data["col"] == rows]).max() == 2
+    for dt in (np.float64, np.float32):
+        A = BatchedCSR(torch.from_numpy(data["crow"]).to(DEV), torch.from_numpy(data["col"]).to(DEV),
+                       torch.from_numpy(data["vals"].astype(dt)).to(DEV))
+        M = BatchedJacobiPreconditioner(A)
+        assert M.dinv.dtype == A.dtype and bool(torch.isfinite(M.dinv).all())
+        for s in range(A.batch):
+            assert torch.equal(M.dinv[s], JacobiPreconditioner(A.system(s)).dinv), (dt, s)
+
+
+@pytest.mark.parametrize("cid", ["cg-jac-f64-rag31n300-dup_diag-S4-x0random", "cg-f64-rag31n300-dup_shuf-S4-x0none",
+                                 "bicgstab-jac-f32-rag31n2049-dup_diag-S4-x0none", "bicgstab-f64-rag31n300-dup_shuf-S4-x0none"])
+def test_batched_jacobi_adds_a_diagonal_stored_twice_like_the_single_preconditioner(hipk, oracle, cid):
+    check_jacobi_vectors_on_repeated_diagonals(BC.reference(BC.BY_ID[cid], oracle)[0])
+
+
+def check_stats_in_long_double(case, data, X, st, M, solver):
+    """x and the stats of every system against long-double arithmetic on the stored arrays (independent of the oracle, which shares
+    the kernels' summation order); the bound is derived in _oracle_cases._check_stats_long_double."""
+    n = data["n"]
+    Xh = X.cpu().numpy()
+    dinv = M.dinv.cpu().numpy() if case.pre else None
+    for s in range(case.S):
+        A = sp.csr_matrix((data["vals"][s], data["col"], data["crow"]), shape=(n, n))
+        one = SimpleNamespace(**{k: getattr(st, k)[s] for k in ("b_norm", "residual_norm", "x_norm", "threshold", "info")})
+        _check_stats_long_double(solver, data["vals"].dtype.type, A, dinv[s] if case.pre else None, data["B"][s], Xh[s], one,
+                                 case.solve_kwargs)
+
+
+@pytest.mark.parametrize("case", PATTERN_KERNEL_CASES, ids=lambda c: c.id)
+def test_pattern_cases_hold_in_long_double(hipk, oracle, case):
+    assert "atol" not in case.kwargs
+    data, _ = BC.reference(case, oracle)
+    ops = _operands(case, data)
+    X, info, st = _solve(case, ops, "kernel")
+    assert st.path == case.path
+    check_stats_in_long_double(case, data, X, st, ops[3], ("p" if case.pre else "") + case.solver)
+
+
 # ------------------------------------------------------------------ routes
 @pytest.mark.parametrize("case", LOOP_CASES, ids=lambda c: c.id)
 def test_loop_and_auto_routes_agree_with_the_kernel(hipk, oracle, case):
@@ -130,9 +177,21 @@ def test_auto_switches_exactly_at_batch_min_systems(hipk, oracle, monkeypatch):
 
 def test_outside_the_envelope_auto_loops_and_kernel_raises(hipk, oracle):
     case = next(c for c in BC.CASES if not c.kernel)
+    _check_outside(case, oracle, "at most 4096 rows")
+
+
+@pytest.mark.parametrize("cid", ["cg-f64-dense32-dup-S2-x0none", "bicgstab-f64-dense32-dup-S2-x0none"])
+def test_a_row_of_33_entries_auto_loops_and_kernel_raises(hipk, oracle, cid):
+    assert {c.id for c in BC.CASES if not c.kernel} == {"cg-f64-17x241-S2-x0none", "cg-f64-dense32-dup-S2-x0none",
+                                                        "bicgstab-f64-dense32-dup-S2-x0none"}
+    _check_outside(BC.BY_ID[cid], oracle, r"at most 32 stored entries per row \(n = 32, longest row 33\)")
+
+
+def _check_outside(case, oracle, bound):
+    assert not case.kernel
     data, ref = BC.reference(case, oracle)
     ops = _operands(case, data)
-    with pytest.raises(ValueError, match="at most 4096 rows"):
+    with pytest.raises(ValueError, match=bound):
         _solve(case, ops, "kernel")
     X, info, st = _solve(case, ops, "auto")
     assert st.path == "loop"
@@ -255,7 +314,9 @@ class _Abi:
 
 
 ABI_IDS = ["cg-f64-17x15-S5-x0exact", "cg-jac-f32-41x25-S4-x0none", "bicgstab-f64-45x45-S4-x0none", "bicgstab-jac-f64-7x5-S5-x0random",
-           "bicgstab-f64-bd-10"]
+           "bicgstab-f64-bd-10",
+           # rows of 2 to 32 entries, unsorted, a column stored twice; ldv > nnz
+           "cg-f64-rag31n300-dup_shuf-S4-x0none", "bicgstab-f64-rag31n300-dup_shuf-S4-x0none"]
 
 
 @pytest.mark.parametrize("cid", ABI_IDS)
@@ -264,7 +325,7 @@ def test_abi_workspace_states_guards_and_pads(hipk, oracle, cid):
     data, ref = BC.reference(case, oracle)
     dinv = BC.jacobi_dinv(data) if case.pre else None
     abi = _Abi(hipk, case, data, dinv)
-    assert abi.wb % 256 == 0
+    assert abi.wb % 256 == 0 and abi.ldv > abi.nnz
     work = Arena(DEV, abi.wb, 256, guard_bytes_for(abi.n, 8))
     x_pads0 = _bits(abi.x_start[:, abi.n:])
 
@@ -345,6 +406,29 @@ def test_abi_error_codes_write_nothing(hipk, oracle):
     assert rc == -4 and "32 stored entries" in hipk.lib().hipk_last_error().decode(), rc
     check_memory(dict(abi33.guarded(), work=work33), dict(abi33.readonly(), work=work33), "33-entry row")
     assert _bits(abi33.x_rows()) == _bits(abi33.x_start)
+
+
+def check_abi_accepts_dense32(hipk, case, data, ref, abi):
+    """The inclusive partner of the 33-entry rejection: every row exactly 32 stored entries, rc 0 and the oracle's bits."""
+    assert np.diff(data["crow"]).min() == np.diff(data["crow"]).max() == BC.MAX_ROW
+    work = Arena(DEV, abi.wb, 256, guard_bytes_for(abi.n, 8)).fill(0x3C)
+    for a in abi.readonly().values():
+        a.snapshot()
+    rc, st = abi.call(work.data_ptr(), abi.wb)
+    assert rc == 0, hipk.lib().hipk_last_error().decode()
+    assert hipk.last_solve_path() == case.path
+    check_memory(dict(abi.guarded(), work=work), abi.readonly(), case.id)
+    X = abi.x_rows()
+    for s, r in enumerate(ref):
+        assert (st[s].iterations, st[s].matvecs, st[s].info) == (r.iterations, r.matvecs, r.info), (case.id, s)
+        assert _bits(X[s, :abi.n]) == _bits(r.x.astype(X.dtype)), (case.id, s)
+
+
+@pytest.mark.parametrize("cid", ["cg-f64-dense32-rev-S2-x0none", "bicgstab-f64-dense32-rev-S2-x0none"])
+def test_abi_accepts_rows_of_exactly_32_entries(hipk, oracle, cid):
+    case = BC.BY_ID[cid]
+    data, ref = BC.reference(case, oracle)
+    check_abi_accepts_dense32(hipk, case, data, ref, _Abi(hipk, case, data, None))
 
 
 # ------------------------------------------------------------------ a batch solve leaves nothing behind that a single solve reads

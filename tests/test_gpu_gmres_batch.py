@@ -10,11 +10,12 @@ import torch
 import _batch_cases as BC
 import _gmres_batch_cases as GC
 from _arena import Arena, check_memory, guard_bytes_for, run_states
-from test_gpu_batch import _Abi
+from test_gpu_batch import _Abi, check_abi_accepts_dense32, check_jacobi_vectors_on_repeated_diagonals, check_stats_in_long_double
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 KERNEL_CASES = [c for c in GC.CASES if c.kernel]
+PATTERN_KERNEL_CASES = [c for c in GC.PATTERN_CASES if c.kernel]
 NORMS = ("residual_norm", "x_norm", "b_norm", "threshold")
 
 
@@ -91,6 +92,21 @@ def test_batched_jacobi_is_the_single_preconditioner_on_convection_diffusion(hip
             assert torch.equal(M.dinv[s], JacobiPreconditioner(A.system(s)).dinv)
 
 
+@pytest.mark.parametrize("cid", ["gmres-jac-f64-rag31n300-dup_diag-r10-b-S4-x0random", "gmres-f64-rag31n300-dup_shuf-r10-i-S4-x0none"])
+def test_batched_jacobi_adds_a_diagonal_stored_twice_like_the_single_preconditioner(hipk, oracle, cid):
+    check_jacobi_vectors_on_repeated_diagonals(GC.reference(GC.BY_ID[cid], oracle)[0])
+
+
+@pytest.mark.parametrize("case", PATTERN_KERNEL_CASES, ids=lambda c: c.id)
+def test_pattern_cases_hold_in_long_double(hipk, oracle, case):
+    assert "atol" not in case.kwargs
+    data, _ = GC.reference(case, oracle)
+    ops = _operands(case, data)
+    X, info, st = _solve(case, ops, "kernel")
+    assert st.path == case.path
+    check_stats_in_long_double(case, data, X, st, ops[3], "pgmres" if case.pre else "gmres")
+
+
 # ------------------------------------------------------------------ routes
 @pytest.mark.parametrize("case", KERNEL_CASES, ids=lambda c: c.id)
 def test_loop_and_auto_routes_agree_with_the_kernel(hipk, oracle, case):
@@ -125,8 +141,8 @@ def test_auto_switches_exactly_at_gmres_batch_min_systems(hipk, oracle, monkeypa
 
 def test_outside_the_envelope_auto_loops_and_kernel_raises(hipk, oracle):
     outside = [c for c in GC.CASES if not c.kernel]
-    assert len(outside) == 2
-    for case, bound in zip(outside, ("at most 31", "at most 4096 rows")):
+    assert len(outside) == 3
+    for case, bound in zip(outside, ("at most 31", "at most 4096 rows", r"at most 32 stored entries per row \(n = 32, longest row 33\)")):
         data, ref = GC.reference(case, oracle)
         ops = _operands(case, data)
         with pytest.raises(ValueError, match=bound):
@@ -202,7 +218,9 @@ class _GmAbi(_Abi):
 
 
 ABI_IDS = ["gmres-f64-17x15-r7-i-S5-x0exact", "gmres-jac-f32-41x25-r30-i-S4-x0none", "gmres-f64-45x45-r31-b-S4-x0random",
-           "gmres-jac-f64-7x5-r2-b-S5-x0random", "gmres-f64-7x5-r5-b-S2-x0none-zero"]
+           "gmres-jac-f64-7x5-r2-b-S5-x0random", "gmres-f64-7x5-r5-b-S2-x0none-zero",
+           # rows of 2 to 32 entries, unsorted, a column stored twice; ldv > nnz
+           "gmres-f64-rag31n300-dup_shuf-r10-i-S4-x0none"]
 
 
 @pytest.mark.parametrize("cid", ABI_IDS)
@@ -211,7 +229,7 @@ def test_abi_workspace_states_guards_and_pads(hipk, oracle, cid):
     data, ref = GC.reference(case, oracle)
     dinv = GC.jacobi_dinv(data) if case.pre else None
     abi = _GmAbi(hipk, case, data, dinv)
-    assert abi.wb % 256 == 0 and abi.wb > 0
+    assert abi.wb % 256 == 0 and abi.wb > 0 and abi.ldv > abi.nnz
     work = Arena(DEV, abi.wb, 256, guard_bytes_for(abi.n, 8))
     x_pads0 = _bits(abi.x_start[:, abi.n:])
 
@@ -258,6 +276,12 @@ def test_abi_one_workspace_shared_with_cg_and_bicgstab_and_a_side_stream(hipk, o
             X = abi.x_rows()
             for s, r in enumerate(ref):
                 assert _bits(X[s, :abi.n]) == _bits(r.x.astype(X.dtype)) and st[s].iterations == r.iterations, (c.id, rnd, s)
+
+
+def test_abi_accepts_rows_of_exactly_32_entries(hipk, oracle):
+    case = GC.BY_ID["gmres-f64-dense32-rev-r8-i-S2-x0none"]
+    data, ref = GC.reference(case, oracle)
+    check_abi_accepts_dense32(hipk, case, data, ref, _GmAbi(hipk, case, data, None))
 
 
 def test_abi_error_codes_write_nothing(hipk, oracle):
