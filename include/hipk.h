@@ -307,6 +307,26 @@ int hipk_gmres_solve_batch(int64_t n, int64_t nnz, const int32_t *crow_dev, cons
                            const void *dinv /* NULL: M = identity */, int64_t ldd, int batch, const void *B, int64_t ldb, void *X,
                            int64_t ldx, int dtype, void *work, size_t work_bytes, const hipk_params *prm, hipk_stats *st /* batch entries */,
                            hipk_stream_t stream);
+/* Block-Jacobi forms of hipk_cg_solve_batch / hipk_bicgstab_solve_batch (csrc/hipk_batch_bj.hip): M_s = blockdiag(binv_s), binv_s =
+ * binv + s * ldbinv the ceil(n / block_size) inverted diagonal blocks of system s, block_size x block_size each, row-major per
+ * block (the layout of hipk_block_jacobi_apply; a ragged last block completed with identity); ldbinv, in elements, is at least
+ * ceil(n / block_size) * block_size^2.  Row s of the result and st[s] are bit for bit the single solve of system s with that M as
+ * its callable: hipk_cgm_start / hipk_cgm_direction between the fused kernels (orc_pcg_blockjacobi) resp. hipk_pbicgstab_solve_cb
+ * (final test: the plain dot of z = M (b - A x) with itself).  One launch of hipk_cg_bjbatch_kernel<T> / hipk_bi_bjbatch_kernel<T>
+ * runs every system's whole solve; HIPK_BATCH_LAUNCH_ITS bounds a launch as above.  Envelope: that of hipk_cg_solve_batch and
+ * 1 <= block_size <= 32, else HIPK_ERR_UNSUPPORTED; a null binv, one not aligned to its element size or a short ldbinv is
+ * HIPK_ERR_ARG (rows of a block need no 16-byte alignment: binv is read element by element); the other operands, error codes, the
+ * write-nothing-on-error rule and the workspace contract as hipk_cg_solve_batch, `work`: hipk_bj_batch_work_bytes.
+ * hipk_last_solve_path() reports e.g. "hipk_cg_bjbatch_kernel<double>". */
+size_t hipk_bj_batch_work_bytes(int64_t n, int64_t nnz, int batch, int dtype, int solver /* 0 cg, 1 bicgstab */, int block_size);
+int hipk_cg_solve_batch_bj(int64_t n, int64_t nnz, const int32_t *crow_dev, const int32_t *col_dev, const void *vals, int64_t ldv,
+                           const void *binv, int64_t ldbinv /* elements between systems */, int block_size, int batch, const void *B,
+                           int64_t ldb, void *X, int64_t ldx, int dtype, void *work, size_t work_bytes, const hipk_params *prm,
+                           hipk_stats *st /* batch entries */, hipk_stream_t stream);
+int hipk_bicgstab_solve_batch_bj(int64_t n, int64_t nnz, const int32_t *crow_dev, const int32_t *col_dev, const void *vals, int64_t ldv,
+                                 const void *binv, int64_t ldbinv, int block_size, int batch, const void *B, int64_t ldb, void *X,
+                                 int64_t ldx, int dtype, void *work, size_t work_bytes, const hipk_params *prm, hipk_stats *st,
+                                 hipk_stream_t stream);
 /* Placement probe for systems whose vectors live in HBM (N >> 8 M rows): the memory shape of the CG direction step (reads r, p, x;
  * writes p, x) on the three vectors, storing back the bits it loaded (safe on live data); *us_out = the fastest of `reps` (<= 16)
  * timed passes in microseconds.  40 n bytes (fp64) per pass.  On MI355X such a step runs at one of two discrete speeds depending on

@@ -246,6 +246,42 @@ __device__ __forceinline__ void hipk_batch_save(const hipk_batch_args &a, hipk_b
     atomicAdd(a.unfinished, 1);
 }
 
+// ---- block-Jacobi (hipk_batch_bj.hip): the launch's argument block, and one row of the apply
+struct hipk_bjbatch_args {
+    hipk_batch_args a;
+    const void *binv;   // system s: binv + s * ldbinv, ceil(n / bs) blocks of bs x bs, row-major per block
+    int64_t ldbinv;
+    int bs;
+};
+
+// z_i of z = blockdiag(binv) v, the expression of hipk_block_jacobi_kernel (orc_block_jacobi_apply): the fma chain over the block's
+// columns in ascending order.  `in` must be complete (LDS, behind a barrier): a block's columns belong to other threads.  Rows of a
+// block are not 16-byte aligned in general (bs = 3), so binv is read element by element.
+template <typename T>
+__device__ __forceinline__ T hipk_bbj_row(const T *__restrict__ binv, const T *in, int i, int n, int bs) {
+    const int b0 = (i / bs) * bs;
+    const T *__restrict__ row = binv + (size_t)i * bs;   // block b, local row i - b0: (b * bs + (i - b0)) * bs = i * bs
+    const int cols = (n - b0 < bs) ? n - b0 : bs;
+    T acc = (T)0;
+    // eight columns at a time: their loads are issued together, so a lane takes the 64 bytes (fp64) of its row while the cache
+    // line is there (lanes are bs elements apart: one load per column left every line to be fetched again for the next column).
+    // The chain itself is unchanged: a column that does not exist adds no link (fma(0, 0, -0.0) would turn the sign).
+    for (int j0 = 0; j0 < cols; j0 += 8) {
+        T a[8], v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const bool ok = j0 + u < cols;
+            a[u] = ok ? row[j0 + u] : (T)0;
+            v[u] = ok ? in[b0 + j0 + u] : (T)0;
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            if (j0 + u < cols) acc = fma(a[u], v[u], acc);
+        }
+    }
+    return acc;
+}
+
 // ---------------------------------------------------------------------------------------------------------------- host
 // what hipk_last_batch_launches() reports for the calling thread (hipk_batch.hip)
 void hipk_batch_note_launches(int launches);

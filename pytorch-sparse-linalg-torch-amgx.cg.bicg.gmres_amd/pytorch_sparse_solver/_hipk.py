@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import collections
 import ctypes
+import math
 import os
 import threading
 from dataclasses import dataclass
@@ -59,6 +60,8 @@ SYMBOLS = [
     # many small systems with one sparsity pattern, one workgroup per system
     "hipk_batch_work_bytes", "hipk_cg_solve_batch", "hipk_bicgstab_solve_batch", "hipk_last_batch_launches",
     "hipk_gmres_batch_work_bytes", "hipk_gmres_solve_batch",
+    # ... with the block-Jacobi preconditioner
+    "hipk_bj_batch_work_bytes", "hipk_cg_solve_batch_bj", "hipk_bicgstab_solve_batch_bj",
 ]
 
 
@@ -286,6 +289,11 @@ def lib():
     for name in ("cg", "bicgstab", "gmres"):
         getattr(L, f"hipk_{name}_solve_batch").argtypes = [i64, i64, vp, vp, vp, i64, vp, i64, i32, vp, i64, vp, i64, i32, vp,
                                                           ctypes.c_size_t, ctypes.POINTER(Params), ctypes.POINTER(Stats), vp]
+    L.hipk_bj_batch_work_bytes.argtypes = [i64, i64, i32, i32, i32, i32]
+    L.hipk_bj_batch_work_bytes.restype = ctypes.c_size_t
+    for name in ("cg", "bicgstab"):
+        getattr(L, f"hipk_{name}_solve_batch_bj").argtypes = [i64, i64, vp, vp, vp, i64, vp, i64, i32, i32, vp, i64, vp, i64, i32, vp,
+                                                             ctypes.c_size_t, ctypes.POINTER(Params), ctypes.POINTER(Stats), vp]
     _lib = L
     return L
 
@@ -909,6 +917,46 @@ def solve_batch(method: str, n: int, nnz: int, crow: torch.Tensor, col: torch.Te
                            path=last_solve_path(), launches=int(L.hipk_last_batch_launches()), solve_ms=float(st[0].solve_ms))
 
 
+def bj_batch_work_bytes(n: int, nnz: int, batch: int, dtype: torch.dtype, method: str, block_size: int) -> int:
+    """hipk_bj_batch_work_bytes (pure host code: callable without a GPU)."""
+    return int(lib().hipk_bj_batch_work_bytes(int(n), int(nnz), int(batch), _dtype_code(dtype), 0 if method == "cg" else 1,
+                                              int(block_size)))
+
+
+def solve_batch_bj(method: str, n: int, nnz: int, crow: torch.Tensor, col: torch.Tensor, vals: torch.Tensor, binv: torch.Tensor,
+                   block_size: int, B: torch.Tensor, X: torch.Tensor, *, tol: float, atol: float, maxiter: Optional[int],
+                   work: Optional[torch.Tensor] = None) -> BatchSolveStats:
+    """hipk_{cg,bicgstab}_solve_batch_bj: the operands of `solve_batch`, and binv (S, ceil(n / bs), bs, bs) contiguous."""
+    S = int(B.shape[0])
+    dev = B.device
+    bs = int(block_size)
+    for t in (vals, B, X):
+        assert t.dim() == 2 and t.shape[0] == S and t.stride(1) == 1 and t.dtype == B.dtype and t.device == dev
+    assert tuple(binv.shape) == (S, (n + bs - 1) // bs, bs, bs) and binv.is_contiguous() and binv.dtype == B.dtype and binv.device == dev
+    assert crow.dtype == torch.int32 and col.dtype == torch.int32 and crow.is_contiguous() and col.is_contiguous()
+    assert crow.numel() == n + 1 and col.numel() == nnz and crow.device == dev and col.device == dev
+    prm = Params()
+    prm.tol, prm.atol = float(tol), float(atol)
+    prm.maxiter = -1 if maxiter is None else int(maxiter)
+    prm.gpu_tolerances = 1
+    L = lib()
+    wb = bj_batch_work_bytes(n, nnz, S, B.dtype, method, bs)
+    work = _workspace(work, dev, wb)
+    st = (Stats * S)()
+    ld = lambda t: int(t.stride(0))
+    with torch.cuda.device(dev):
+        rc = getattr(L, f"hipk_{method}_solve_batch_bj")(n, nnz, crow.data_ptr(), col.data_ptr(), vals.data_ptr(), ld(vals),
+                                                         binv.data_ptr(), ld(binv), bs, S, B.data_ptr(), ld(B), X.data_ptr(), ld(X),
+                                                         _dtype_code(B.dtype), work.data_ptr(), wb, ctypes.byref(prm), st, _stream(dev))
+    _check(rc, f"hipk_{method}_solve_batch_bj")
+    name = {"cg": "pcg_blockjacobi", "bicgstab": "pbicgstab_blockjacobi"}[method]
+    col_of = lambda f: [getattr(c, f) for c in st]
+    return BatchSolveStats(method=f"{name}_batch", iterations=col_of("iterations"), matvecs=col_of("matvecs"), info=col_of("info"),
+                           breakdown=col_of("breakdown"), b_norm=col_of("b_norm"), residual_norm=col_of("residual_norm"),
+                           x_norm=col_of("x_norm"), threshold=col_of("threshold"), recurrence_rs=col_of("recurrence_rs"),
+                           path=last_solve_path(), launches=int(L.hipk_last_batch_launches()), solve_ms=float(st[0].solve_ms))
+
+
 def solve_pgmres(h: CsrHandle, dinv: torch.Tensor, b: torch.Tensor, x: torch.Tensor, *, tol: float, atol: float,
                  maxiter: Optional[int], restart: int = 20, solve_method: str = "batched",
                  work: Optional[torch.Tensor] = None) -> SolveStats:
@@ -1053,8 +1101,10 @@ def solve_cg_stepwise(h: Optional[CsrHandle], A_fn, M, b: torch.Tensor, x: torch
             _check(L.hipk_reduce_parts(prt.data_ptr(), G, out[k:k + 1].data_ptr(), s), "hipk_reduce_parts")
         e1.record()
         res2, xx, bs, rs = (float(v) for v in out.cpu())
-    b_norm, res_norm = max(bs, 0.0) ** 0.5, max(res2, 0.0) ** 0.5
-    x_norm = max(xx, 0.0) ** 0.5 if xx == xx else float("nan")
+    # math.sqrt, not ** 0.5: pow(v, 0.5) is off by one ulp from the correctly rounded root for about one value in a thousand, and
+    # the C loops, the batch kernels and the oracle all take sqrt
+    b_norm, res_norm = math.sqrt(max(bs, 0.0)), math.sqrt(max(res2, 0.0))
+    x_norm = math.sqrt(max(xx, 0.0)) if xx == xx else float("nan")
     thr = max(float(torch.tensor(tol, dtype=torch.float32)) * b_norm, float(torch.tensor(atol, dtype=torch.float32)))
     info = -1 if (x_norm != x_norm or res_norm > thr) else 0
     method = ("cg_callable_M" if M is not None else "cg") if h is not None else \

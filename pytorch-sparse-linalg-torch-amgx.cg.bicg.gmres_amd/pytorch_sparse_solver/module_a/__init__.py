@@ -5,7 +5,8 @@ on hand-written gfx950 kernels (libhipk.so), everything else on the generic torc
 `get_last_stats()` (iteration counts the reference never returns), `JacobiPreconditioner` (a callable for the
 reference's `M` hook that the fast path runs device-resident), `ChebyshevPreconditioner` (a polynomial in D^-1 A whose steps
 run in the SpMV kernels' epilogue), `cg_multi` / `bicgstab_multi` (k right-hand sides per matrix read) and `cg_batch` /
-`bicgstab_batch` / `gmres_batch` (many small systems with one sparsity pattern, one workgroup per system) are the additions.
+`bicgstab_batch` / `gmres_batch` (many small systems with one sparsity pattern, one workgroup per system; point- or block-Jacobi
+preconditioned) are the additions.
 """
 from .torch_sparse_linalg import (
     cg, bicgstab, gmres,
@@ -13,13 +14,13 @@ from .torch_sparse_linalg import (
     LinearSolveFunction, ImplicitAdjointFunction, get_last_stats,
 )
 from .multi_rhs import cg_multi, bicgstab_multi
-from .batch import BatchedCSR, BatchedJacobiPreconditioner, cg_batch, bicgstab_batch, gmres_batch
+from .batch import BatchedCSR, BatchedJacobiPreconditioner, BatchedBlockJacobiPreconditioner, cg_batch, bicgstab_batch, gmres_batch
 from .torch_tree_util import tree_leaves, tree_map, tree_flatten, tree_unflatten, Partial
 from .preconditioners import BlockJacobiPreconditioner, ChebyshevPreconditioner, JacobiPreconditioner
 
 __all__ = [
     'cg', 'bicgstab', 'gmres', 'cg_multi', 'bicgstab_multi',
-    'BatchedCSR', 'BatchedJacobiPreconditioner', 'cg_batch', 'bicgstab_batch', 'gmres_batch',
+    'BatchedCSR', 'BatchedJacobiPreconditioner', 'BatchedBlockJacobiPreconditioner', 'cg_batch', 'bicgstab_batch', 'gmres_batch',
     'cg_differentiable', 'bicgstab_differentiable', 'gmres_differentiable',
     'LinearSolveFunction',
     'tree_leaves', 'tree_map', 'tree_flatten', 'tree_unflatten', 'Partial',

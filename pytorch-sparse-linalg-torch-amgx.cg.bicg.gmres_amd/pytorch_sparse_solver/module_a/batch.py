@@ -7,17 +7,20 @@ tensor A_s of system s, bit for bit.  Two routes compute them:
             its whole solve, a launch covers all S systems.  Device operands, n <= 4096, at most 32 stored entries per row;
             gmres_batch: restart <= 31.
   'loop'    one public single solve per system: every input the single solvers accept, CPU tensors included.
-  'auto'    the kernel for device operands inside its envelope when S >= BATCH_MIN_SYSTEMS (gmres_batch: GMRES_BATCH_MIN_SYSTEMS),
-            else the loop.
+  'auto'    the kernel for device operands inside its envelope when S >= BATCH_MIN_SYSTEMS (gmres_batch: GMRES_BATCH_MIN_SYSTEMS;
+            with a BatchedBlockJacobiPreconditioner: BJ_BATCH_MIN_SYSTEMS), else the loop.
+
+`M` is None, a `BatchedJacobiPreconditioner` or a `BatchedBlockJacobiPreconditioner` (csrc/hipk_batch_bj.hip; gmres_batch runs the
+latter on the loop only).
 """
 from __future__ import annotations
 
 import time
-from typing import Optional, Sequence, Tuple
+from typing import Optional, Sequence, Tuple, Union
 
 import torch
 
-from .preconditioners import JacobiPreconditioner
+from .preconditioners import BlockJacobiPreconditioner, JacobiPreconditioner
 from .torch_sparse_linalg import _set_stats, bicgstab, cg, get_last_stats, gmres
 
 # The smallest S at which 'auto' takes the batch kernels: the measured crossover (tools/batch_probe.py, profiles/batch_probe.txt;
@@ -25,6 +28,14 @@ from .torch_sparse_linalg import _set_stats, bicgstab, cg, get_last_stats, gmres
 # one workgroup against 8 to 32) and still at S = 4 for n = 4096 (0.50x); at S = 8 the kernel is level at worst (cg, n = 4096:
 # 0.98x) and 2-8.4x ahead elsewhere, from S = 64 on 16-900x.
 BATCH_MIN_SYSTEMS = 8
+
+
+# The smallest S at which 'auto' takes hipk_cg_bjbatch_kernel / hipk_bi_bjbatch_kernel for a BatchedBlockJacobiPreconditioner: the
+# measured crossover (tools/bj_batch_probe.py, profiles/bj_batch_probe.txt).  The loop here is the single solves'
+# callback form (11-32 k system-iterations per second whatever n), far slower than the one-launch loops BATCH_MIN_SYSTEMS was set
+# against.  At S = 2 the kernel is still behind for n = 4096 (bs = 32: cg 0.80x, bicgstab 0.61x); at S = 4 it is ahead in all twelve
+# probed cases (1.18x at worst: bicgstab, n = 4096, bs = 32), at S = 8 2.3-56x.
+BJ_BATCH_MIN_SYSTEMS = 4
 
 
 def _aligned_rows(t: torch.Tensor) -> bool:
@@ -144,6 +155,62 @@ class BatchedJacobiPreconditioner:
         return J
 
 
+class BatchedBlockJacobiPreconditioner:
+    """M_s(v) = blockdiag(A_s)^-1 v for every system of a BatchedCSR, with `block_size` x `block_size` diagonal blocks
+    (1 <= block_size <= 32): `binv` (S, ceil(n / block_size), block_size, block_size), contiguous, in the dtype and on the device of
+    `A.values`.  The blocks of all systems are taken in one pass over the shared pattern (entries stored twice add, a ragged last
+    block is completed with identity) and inverted by one `torch.linalg.inv`.  `binv=` given: those blocks are M as they are (an
+    approximate inverse; identity blocks make M the identity)."""
+
+    def __init__(self, A: BatchedCSR, block_size: int = 4, binv: Optional[torch.Tensor] = None):
+        if not isinstance(A, BatchedCSR):
+            raise ValueError("BatchedBlockJacobiPreconditioner needs a BatchedCSR")
+        if not 1 <= int(block_size) <= 32:
+            raise ValueError("block_size must be in [1, 32]")
+        bs = self.block_size = int(block_size)
+        n = A.n
+        nb = (n + bs - 1) // bs
+        self.shape = A.shape
+        if binv is not None:
+            want = (A.batch, nb, bs, bs)
+            if not isinstance(binv, torch.Tensor) or tuple(binv.shape) != want:
+                raise ValueError(f"BatchedBlockJacobiPreconditioner: binv must have shape (S, ceil(n / bs), bs, bs) = {want}, got "
+                                 f"{tuple(getattr(binv, 'shape', ()))}")
+            if binv.dtype != A.dtype or binv.device != A.device:
+                raise ValueError(f"BatchedBlockJacobiPreconditioner: binv is {binv.dtype} on {binv.device}, the matrices are "
+                                 f"{A.dtype} on {A.device}")
+            if not binv.is_contiguous():
+                raise ValueError("BatchedBlockJacobiPreconditioner: binv must be contiguous")
+            self.binv = binv.detach()
+            return
+        rows = torch.repeat_interleave(torch.arange(n, device=A.device), A.crow[1:] - A.crow[:-1])
+        cols = A.col.to(torch.int64)
+        on = torch.div(rows, bs, rounding_mode="floor") == torch.div(cols, bs, rounding_mode="floor")
+        blocks = torch.zeros((A.batch, nb * bs * bs), dtype=A.dtype, device=A.device)
+        blocks.index_add_(1, rows[on] * bs + cols[on] % bs, A.values[:, on])   # block b, local row i: (b bs + i) bs = row bs
+        blocks = blocks.view(A.batch, nb, bs, bs)
+        pad = nb * bs - n
+        if pad:
+            idx = torch.arange(bs - pad, bs, device=A.device)
+            blocks[:, nb - 1, idx, idx] = 1.0
+        try:
+            self.binv = torch.linalg.inv(blocks.view(A.batch * nb, bs, bs)).view(A.batch, nb, bs, bs).contiguous()
+        except RuntimeError as e:
+            raise ValueError(f"BatchedBlockJacobiPreconditioner: a diagonal block is singular ({e})") from None
+
+    def system(self, s: int) -> BlockJacobiPreconditioner:
+        """The single solves' preconditioner of system s; its `binv` IS `self.binv[s]` (not inverted again: a batched inverse need
+        not give the same bits for another batch size)."""
+        P = BlockJacobiPreconditioner.__new__(BlockJacobiPreconditioner)
+        P.block_size = self.block_size
+        P.shape = (self.shape[1], self.shape[2])
+        P.binv = self.binv[s]
+        return P
+
+
+BatchedPreconditioner = Union[BatchedJacobiPreconditioner, BatchedBlockJacobiPreconditioner]
+
+
 def _check(name, A, B, X0, M, route):
     if not isinstance(A, BatchedCSR):
         raise ValueError(f"{name}: A must be a BatchedCSR")
@@ -163,10 +230,12 @@ def _check(name, A, B, X0, M, route):
         if t.requires_grad:
             raise ValueError(f"{name} is not differentiable: call {name.split('_')[0]}_differentiable on each system instead")
     if M is not None:
-        if not isinstance(M, BatchedJacobiPreconditioner):
-            raise ValueError(f"{name}: M must be None or a BatchedJacobiPreconditioner, got {type(M).__name__}")
-        if tuple(M.shape) != tuple(A.shape) or M.dinv.device != A.device:
-            raise ValueError(f"{name}: the preconditioner (shape {tuple(M.shape)}, {M.dinv.device}) does not match A "
+        if not isinstance(M, (BatchedJacobiPreconditioner, BatchedBlockJacobiPreconditioner)):
+            raise ValueError(f"{name}: M must be None or a BatchedJacobiPreconditioner or a BatchedBlockJacobiPreconditioner, "
+                             f"got {type(M).__name__}")
+        where = (M.binv if isinstance(M, BatchedBlockJacobiPreconditioner) else M.dinv).device
+        if tuple(M.shape) != tuple(A.shape) or where != A.device:
+            raise ValueError(f"{name}: the preconditioner (shape {tuple(M.shape)}, {where}) does not match A "
                              f"(shape {tuple(A.shape)}, {A.device})")
 
 
@@ -180,6 +249,10 @@ def _kernel_solve(kind, A: BatchedCSR, B, X0, tol, atol, maxiter, M, **gm):
         X = X0.detach().to(dt).clone()
         if not _aligned_rows(X):
             X = _pad_rows(X)
+    if isinstance(M, BatchedBlockJacobiPreconditioner):
+        st = _hipk.solve_batch_bj(kind, A.n, A.nnz, A.crow32, A.col32, A.kernel_values(), M.binv.to(dt).contiguous(), M.block_size, BB, X,
+                                  tol=tol, atol=atol, maxiter=maxiter)
+        return X.contiguous(), st
     dinv = None if M is None else _pad_rows(M.dinv.detach().to(dt))
     st = _hipk.solve_batch(kind, A.n, A.nnz, A.crow32, A.col32, A.kernel_values(), dinv, BB, X, tol=tol, atol=atol, maxiter=maxiter,
                             **gm)
@@ -199,7 +272,8 @@ def _loop_solve(kind, A: BatchedCSR, B, X0, tol, atol, maxiter, M, **gm):
         stats.append(get_last_stats())
     ms = (time.perf_counter() - t0) * 1e3
     f = lambda name, default: [getattr(c, name, default) if c is not None else default for c in stats]
-    name = kind if M is None else {"cg": "pcg_jacobi", "bicgstab": "pbicgstab_jacobi", "gmres": "pgmres_jacobi"}[kind]
+    tag = "blockjacobi" if isinstance(M, BatchedBlockJacobiPreconditioner) else "jacobi"
+    name = kind if M is None else {"cg": f"pcg_{tag}", "bicgstab": f"pbicgstab_{tag}", "gmres": f"pgmres_{tag}"}[kind]
     st = _hipk.BatchSolveStats(method=f"{name}_batch", iterations=f("iterations", 0), matvecs=f("matvecs", 0), info=infos,
                                breakdown=f("breakdown", 0), b_norm=f("b_norm", 0.0), residual_norm=f("residual_norm", 0.0),
                                x_norm=f("x_norm", 0.0), threshold=f("threshold", 0.0), recurrence_rs=f("recurrence_rs", 0.0),
@@ -217,14 +291,15 @@ def _batch(kind: str, A, B, X0, tol, atol, maxiter, M, route):
         if not A.in_envelope():
             raise ValueError(f"{name}: route='kernel' takes systems of at most 4096 rows with at most 32 stored entries per row "
                              f"(n = {A.n}, longest row {A.max_row_len}); use route='loop'")
-    use_kernel = route == "kernel" or (route == "auto" and on_device and A.in_envelope() and A.batch >= BATCH_MIN_SYSTEMS)
+    least = BJ_BATCH_MIN_SYSTEMS if isinstance(M, BatchedBlockJacobiPreconditioner) else BATCH_MIN_SYSTEMS
+    use_kernel = route == "kernel" or (route == "auto" and on_device and A.in_envelope() and A.batch >= least)
     X, st = (_kernel_solve if use_kernel else _loop_solve)(kind, A, B, X0, tol, atol, maxiter, M)
     _set_stats(st)
     return X, torch.tensor([int(i) for i in st.info], dtype=torch.int64)
 
 
 def cg_batch(A: BatchedCSR, B: torch.Tensor, X0: Optional[torch.Tensor] = None, *, tol: float = 1e-5, atol: float = 0.0,
-             maxiter: Optional[int] = None, M: Optional[BatchedJacobiPreconditioner] = None,
+             maxiter: Optional[int] = None, M: Optional[BatchedPreconditioner] = None,
              route: str = "auto") -> Tuple[torch.Tensor, torch.Tensor]:
     """Conjugate gradients for the S systems A_s X[s] = B[s], B of shape (S, n).
 
@@ -234,7 +309,7 @@ def cg_batch(A: BatchedCSR, B: torch.Tensor, X0: Optional[torch.Tensor] = None, 
 
 
 def bicgstab_batch(A: BatchedCSR, B: torch.Tensor, X0: Optional[torch.Tensor] = None, *, tol: float = 1e-5, atol: float = 0.0,
-                   maxiter: Optional[int] = None, M: Optional[BatchedJacobiPreconditioner] = None,
+                   maxiter: Optional[int] = None, M: Optional[BatchedPreconditioner] = None,
                    route: str = "auto") -> Tuple[torch.Tensor, torch.Tensor]:
     """BiCGStab for the S systems A_s X[s] = B[s] (see `cg_batch`); breakdowns (-10, -11) are decided per system."""
     return _batch("bicgstab", A, B, X0, tol, atol, maxiter, M, route)
@@ -246,7 +321,7 @@ GMRES_BATCH_MIN_SYSTEMS = 8
 
 
 def gmres_batch(A: BatchedCSR, B: torch.Tensor, X0: Optional[torch.Tensor] = None, *, tol: float = 1e-5, atol: float = 0.0,
-                restart: int = 20, maxiter: Optional[int] = None, M: Optional[BatchedJacobiPreconditioner] = None,
+                restart: int = 20, maxiter: Optional[int] = None, M: Optional[BatchedPreconditioner] = None,
                 solve_method: str = "batched", route: str = "auto") -> Tuple[torch.Tensor, torch.Tensor]:
     """Restarted GMRES for the S systems A_s X[s] = B[s] (see `cg_batch`): `maxiter` counts restart cycles, every system stops at its
     own cycle and, with solve_method='incremental', at its own Arnoldi step inside a cycle; happy breakdown is decided per system.
@@ -259,8 +334,12 @@ def gmres_batch(A: BatchedCSR, B: torch.Tensor, X0: Optional[torch.Tensor] = Non
     if solve_method not in ("batched", "incremental"):
         raise ValueError(f"Unsupported solve_method: {solve_method}")
     on_device = A.values.is_cuda
-    inside = A.in_envelope() and int(restart) <= _hipk.GMRES_BATCH_MAX_RESTART
+    block = isinstance(M, BatchedBlockJacobiPreconditioner)
+    inside = A.in_envelope() and int(restart) <= _hipk.GMRES_BATCH_MAX_RESTART and not block
     if route == "kernel":
+        if block:
+            raise ValueError(f"{name}: the GMRES batch kernel has no block-Jacobi form (M is a BatchedBlockJacobiPreconditioner); "
+                             f"use route='loop' or route='auto', which run one gmres per system")
         if not on_device:
             raise ValueError(f"{name}: route='kernel' needs device tensors (A is on {A.device}); use route='loop'")
         if not A.in_envelope():
