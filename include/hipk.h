@@ -382,6 +382,48 @@ int hipk_block_jacobi_apply(int64_t n, int block_size, const void *binv_dev, con
 int hipk_cheb_apply(hipk_csr_t A, int degree, const void *dinv, const double *coef_host, const void *r, void *z, void *work,
                     hipk_stream_t stream);
 
+/* ---- aggregation multigrid on a grid: the transfer steps (csrc/hipk_mg.hip) ----------------------------
+ * The device steps of `AggregationMultigridPreconditioner` that are not an SpMV or a Chebyshev apply.  A level is a box of
+ * n0 x n1 x n2 points (each >= 1; a two-dimensional grid passes n0 = 1), row index (i0 n1 + i1) n2 + i2; the next level has
+ * ceil(n_d / 2) points per dimension and the aggregate of fine point (i0, i1, i2) is coarse point (i0 / 2, i1 / 2, i2 / 2).
+ * Indices are computed from the dimensions, there are no index arrays.  Every call is one streaming launch enqueued on `stream`
+ * and never synchronises; vectors are of `dtype`, 16-byte aligned (else HIPK_ERR_ALIGN) and distinct; elements at and beyond
+ * the vector's length are never read or written.  Every operation is a separate rounding, no fma; `omega` / `scale` are rounded
+ * to `dtype` once.
+ *   hipk_mg_restrict    : rc[I] = the sum of t (n0 n1 n2 elements) over the members of aggregate I in ascending fine index, left
+ *                         to right, the first member starting the sum; rc has prod(ceil(n_d / 2)) elements.
+ *   hipk_mg_prolong_add : z[i] = z[i] + (omega * e[agg(i)]), z of n0 n1 n2 elements, e of the coarse level's.
+ *   hipk_mg_correct     : z[i] = scale * (z[i] + d[i]), i < n (the last step of a level; scale = 1 except on the finest).
+ *   hipk_mg_diag        : z[i] = scale * (dinv[i] * r[i]), i < n (the level with one unknown). */
+int hipk_mg_restrict(int64_t n0, int64_t n1, int64_t n2, const void *t, void *rc, int dtype, hipk_stream_t stream);
+int hipk_mg_prolong_add(int64_t n0, int64_t n1, int64_t n2, double omega, const void *e, void *z, int dtype, hipk_stream_t stream);
+int hipk_mg_correct(int64_t n, double scale, const void *d, void *z, int dtype, hipk_stream_t stream);
+int hipk_mg_diag(int64_t n, double scale, const void *dinv, const void *r, void *z, int dtype, hipk_stream_t stream);
+/* The tail of the V-cycle in ONE launch of one 256-thread workgroup (hipk_mg_tail_kernel<T>): for the run of levels
+ * levels[0 .. nlev), each the ceil(d / 2) coarsening of the one before and the last with one unknown,
+ *     z = scale * V(0, r),   V(j, r) = steps 1 - 6 of the class's docstring with S_j the Chebyshev recurrence of hipk_cheb_apply
+ *                            (degree steps, coefficients c0, c1[k], c2[k] of the level, scale 1), V(nlev - 1, r) = dinv r,
+ * bit for bit what hipk_cheb_apply, hipk_spmv_ex (mode 4), hipk_mg_restrict, hipk_mg_prolong_add, hipk_mg_correct and
+ * hipk_mg_diag give on the same levels, launch by launch.  A level is described by int32 CSR arrays, values and the reciprocal
+ * diagonal of `dtype` (device pointers, read only), its dimensions, n = n0 n1 n2 and `max_row`, the largest number of stored
+ * entries in a row (it decides nothing but the envelope: the kernel sums a row in stored order).  The descriptors are passed
+ * twice: `levels_host` for the checks and the workspace layout, `levels_dev` the same bytes in device memory (built once by the
+ * caller, 16-byte aligned) for the kernel.  Envelope: n <= 4096 and max_row <= 32 on every level, else HIPK_ERR_UNSUPPORTED;
+ * 1 <= nlev <= 16, 1 <= degree <= 32, consistent dimensions, else HIPK_ERR_ARG; r, z 16-byte and `work` 256-byte aligned, else
+ * HIPK_ERR_ALIGN; `work` >= hipk_mg_tail_work_bytes (pure host code; 0 for bad arguments), else HIPK_ERR_WORKSPACE.  A call that
+ * returns an error has launched nothing and written nothing.  The workspace contract above holds: every element of `work` the
+ * kernel reads it has written before.  r: levels[0].n elements, read only; z likewise, written.  Never synchronises. */
+typedef struct {
+    const int32_t *crow, *col; /* device: n + 1 row pointers, the columns                          */
+    const void *val, *dinv;    /* device, `dtype`: the values, the n reciprocal diagonal entries   */
+    int32_t n0, n1, n2, n;     /* the level's box (a two-dimensional grid has n0 = 1), n = n0 n1 n2 */
+    int32_t max_row, reserved;
+    double c0, c1[32], c2[32]; /* the smoother's coefficients, c1[k - 1], c2[k - 1] for step k       */
+} hipk_mg_level;
+size_t hipk_mg_tail_work_bytes(const hipk_mg_level *levels_host, int nlev, int dtype);
+int hipk_mg_tail_apply(const hipk_mg_level *levels_host, const void *levels_dev, int nlev, int degree, double omega, double scale,
+                       const void *r, void *z, int dtype, void *work, size_t work_bytes, hipk_stream_t stream);
+
 /* ---- step API: externally driven loops (row-partitioned multi-GPU CG) ------------
  * The reference is single-device; the row-partitioned solver (north_star) drives the
  * SAME fused kernels from the host side of each rank and exchanges (a) the x-vector

@@ -62,6 +62,10 @@ SYMBOLS = [
     "hipk_gmres_batch_work_bytes", "hipk_gmres_solve_batch",
     # ... with the block-Jacobi preconditioner
     "hipk_bj_batch_work_bytes", "hipk_cg_solve_batch_bj", "hipk_bicgstab_solve_batch_bj",
+    # aggregation multigrid on a grid: the transfer steps
+    "hipk_mg_restrict", "hipk_mg_prolong_add", "hipk_mg_correct", "hipk_mg_diag",
+    # ... and the V-cycle's small levels in one launch
+    "hipk_mg_tail_work_bytes", "hipk_mg_tail_apply",
 ]
 
 
@@ -147,6 +151,14 @@ class DistPlan(ctypes.Structure):
 
 
 # hipk_precond_fn / hipk_op_fn (include/hipk.h): int f(void *user, const void *in_dev, void *out_dev)
+class MgLevel(ctypes.Structure):
+    """hipk_mg_level: one level of hipk_mg_tail_apply."""
+    _fields_ = [("crow", ctypes.c_void_p), ("col", ctypes.c_void_p), ("val", ctypes.c_void_p), ("dinv", ctypes.c_void_p),
+                ("n0", ctypes.c_int32), ("n1", ctypes.c_int32), ("n2", ctypes.c_int32), ("n", ctypes.c_int32),
+                ("max_row", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("c0", ctypes.c_double), ("c1", ctypes.c_double * 32), ("c2", ctypes.c_double * 32)]
+
+
 PRECOND_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p)
 OP_FN = PRECOND_FN
 
@@ -294,6 +306,13 @@ def lib():
     for name in ("cg", "bicgstab"):
         getattr(L, f"hipk_{name}_solve_batch_bj").argtypes = [i64, i64, vp, vp, vp, i64, vp, i64, i32, i32, vp, i64, vp, i64, i32, vp,
                                                              ctypes.c_size_t, ctypes.POINTER(Params), ctypes.POINTER(Stats), vp]
+    L.hipk_mg_restrict.argtypes = [i64, i64, i64, vp, vp, i32, vp]
+    L.hipk_mg_prolong_add.argtypes = [i64, i64, i64, dbl, vp, vp, i32, vp]
+    L.hipk_mg_correct.argtypes = [i64, dbl, vp, vp, i32, vp]
+    L.hipk_mg_diag.argtypes = [i64, dbl, vp, vp, vp, i32, vp]
+    L.hipk_mg_tail_work_bytes.argtypes = [ctypes.POINTER(MgLevel), i32, i32]
+    L.hipk_mg_tail_work_bytes.restype = ctypes.c_size_t
+    L.hipk_mg_tail_apply.argtypes = [ctypes.POINTER(MgLevel), vp, i32, i32, dbl, dbl, vp, vp, i32, vp, ctypes.c_size_t, vp]
     _lib = L
     return L
 
@@ -649,6 +668,111 @@ def cheb_apply(h: CsrHandle, degree: int, dinv: torch.Tensor, coef, v: torch.Ten
         _check(lib().hipk_cheb_apply(h.ptr, int(degree), dinv.data_ptr(), coef, v.data_ptr(), out.data_ptr(), work.data_ptr(),
                                      _stream(v.device)), "hipk_cheb_apply")
     return out
+
+
+def spmv_residual(h: CsrHandle, x: torch.Tensor, b: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    """out = b - A x, the SpMV's residual form (hipk_spmv_ex, mode 4), on the current stream.  No fused dot, so it takes no lock
+    and touches none of the handle's reduction scratch: a preconditioner may call it inside a solve that holds the handle."""
+    for v in (x, b, out):
+        assert v.is_contiguous() and v.dtype == h.dtype and v.device == h.device and v.numel() == h.n
+    with torch.cuda.device(h.device):
+        _check(lib().hipk_spmv_ex(h.ptr, x.data_ptr(), out.data_ptr(), 4, None, b.data_ptr(), None, None, None, 0,
+                                  _stream(h.device)), "hipk_spmv_ex")
+    return out
+
+
+def _grid3(dims):
+    """(n0, n1, n2) of a 2- or 3-dimensional grid, slowest dimension first (a two-dimensional one has n0 = 1)."""
+    d = tuple(int(v) for v in dims)
+    return (1,) * (3 - len(d)) + d
+
+
+def mg_restrict(dims, t: torch.Tensor, rc: torch.Tensor) -> torch.Tensor:
+    """rc[I] = the sum of t over aggregate I in ascending fine index (hipk_mg_restrict); `dims` is the FINE grid."""
+    n0, n1, n2 = _grid3(dims)
+    assert t.is_cuda and t.is_contiguous() and rc.is_contiguous() and rc.dtype == t.dtype and rc.device == t.device
+    assert t.numel() == n0 * n1 * n2 and rc.numel() == ((n0 + 1) // 2) * ((n1 + 1) // 2) * ((n2 + 1) // 2)
+    with torch.cuda.device(t.device):
+        _check(lib().hipk_mg_restrict(n0, n1, n2, t.data_ptr(), rc.data_ptr(), _dtype_code(t.dtype), _stream(t.device)),
+               "hipk_mg_restrict")
+    return rc
+
+
+def mg_prolong_add(dims, omega: float, e: torch.Tensor, z: torch.Tensor) -> torch.Tensor:
+    """z[i] += omega * e[agg(i)] in place (hipk_mg_prolong_add); `dims` is the FINE grid, z's."""
+    n0, n1, n2 = _grid3(dims)
+    assert z.is_cuda and z.is_contiguous() and e.is_contiguous() and e.dtype == z.dtype and e.device == z.device
+    assert z.numel() == n0 * n1 * n2 and e.numel() == ((n0 + 1) // 2) * ((n1 + 1) // 2) * ((n2 + 1) // 2)
+    with torch.cuda.device(z.device):
+        _check(lib().hipk_mg_prolong_add(n0, n1, n2, float(omega), e.data_ptr(), z.data_ptr(), _dtype_code(z.dtype),
+                                         _stream(z.device)), "hipk_mg_prolong_add")
+    return z
+
+
+def mg_correct(scale: float, d: torch.Tensor, z: torch.Tensor) -> torch.Tensor:
+    """z = scale * (z + d) in place (hipk_mg_correct)."""
+    assert z.is_cuda and z.is_contiguous() and d.is_contiguous() and d.dtype == z.dtype and d.device == z.device and d.numel() == z.numel()
+    with torch.cuda.device(z.device):
+        _check(lib().hipk_mg_correct(z.numel(), float(scale), d.data_ptr(), z.data_ptr(), _dtype_code(z.dtype), _stream(z.device)),
+               "hipk_mg_correct")
+    return z
+
+
+def mg_diag(scale: float, dinv: torch.Tensor, r: torch.Tensor, z: torch.Tensor) -> torch.Tensor:
+    """z = scale * (dinv * r) (hipk_mg_diag)."""
+    assert z.is_cuda and all(v.is_contiguous() and v.dtype == z.dtype and v.device == z.device and v.numel() == z.numel() for v in (dinv, r, z))
+    with torch.cuda.device(z.device):
+        _check(lib().hipk_mg_diag(z.numel(), float(scale), dinv.data_ptr(), r.data_ptr(), z.data_ptr(), _dtype_code(z.dtype),
+                                  _stream(z.device)), "hipk_mg_diag")
+    return z
+
+
+MG_TAIL_MAX_N = 4096      # the envelope of hipk_mg_tail_apply: unknowns per level ...
+MG_TAIL_MAX_ROW = 32      # ... and stored entries per row (the batch kernels')
+
+
+class MgTail:
+    """The descriptors of hipk_mg_tail_apply for a run of levels, on the host and as one device blob, and the tensors they point
+    into.  `levels`: per level a dict with int32 `crow` / `col`, `val`, `dinv` (contiguous device tensors of one dtype), `dims`
+    (2 or 3 entries), `max_row` and the smoother's `c0`, `c1`, `c2` (None on the last level, which has one unknown)."""
+
+    def __init__(self, levels, degree: int):
+        self.nlev, self.degree = len(levels), int(degree)
+        self.dtype, self.device = levels[0]["val"].dtype, levels[0]["val"].device
+        self.host = (MgLevel * self.nlev)()
+        self._keep = []
+        for d, lev in zip(self.host, levels):
+            for name in ("crow", "col", "val", "dinv"):
+                t = lev[name]
+                assert t.is_cuda and t.is_contiguous() and t.device == self.device
+                assert t.dtype == (torch.int32 if name in ("crow", "col") else self.dtype)
+                self._keep.append(t)
+                setattr(d, name, t.data_ptr())
+            d.n0, d.n1, d.n2 = _grid3(lev["dims"])
+            d.n = d.n0 * d.n1 * d.n2
+            assert lev["crow"].numel() == d.n + 1 and lev["dinv"].numel() == d.n and lev["col"].numel() == lev["val"].numel()
+            d.max_row = int(lev["max_row"])
+            if lev.get("c0") is not None:
+                d.c0 = float(lev["c0"])
+                for k in range(self.degree):
+                    d.c1[k], d.c2[k] = float(lev["c1"][k]), float(lev["c2"][k])
+        raw = torch.frombuffer(bytearray(bytes(self.host)), dtype=torch.uint8)
+        self.blob = raw.to(self.device)
+        self.work_bytes = int(lib().hipk_mg_tail_work_bytes(self.host, self.nlev, _dtype_code(self.dtype)))
+
+
+def mg_tail_apply(tail: MgTail, omega: float, scale: float, r: torch.Tensor, z: torch.Tensor,
+                  work: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """z = scale * V(0, r) over the tail's levels in one launch (hipk_mg_tail_apply), on the current stream."""
+    n = int(tail.host[0].n)
+    for v in (r, z):
+        assert v.is_cuda and v.is_contiguous() and v.dtype == tail.dtype and v.device == tail.device and v.numel() == n
+    work = _workspace(work, tail.device, tail.work_bytes)
+    with torch.cuda.device(tail.device):
+        _check(lib().hipk_mg_tail_apply(tail.host, tail.blob.data_ptr(), tail.nlev, tail.degree, float(omega), float(scale),
+                                        r.data_ptr(), z.data_ptr(), _dtype_code(tail.dtype), work.data_ptr(), tail.work_bytes,
+                                        _stream(tail.device)), "hipk_mg_tail_apply")
+    return z
 
 
 # -------------------------------------------------------------------- whole solves

@@ -4,7 +4,8 @@ Same exports as the reference's `module_a/__init__.py:47-63`; CUDA/ROCm tensor i
 on hand-written gfx950 kernels (libhipk.so), everything else on the generic torch path.
 `get_last_stats()` (iteration counts the reference never returns), `JacobiPreconditioner` (a callable for the
 reference's `M` hook that the fast path runs device-resident), `ChebyshevPreconditioner` (a polynomial in D^-1 A whose steps
-run in the SpMV kernels' epilogue), `cg_multi` / `bicgstab_multi` (k right-hand sides per matrix read) and `cg_batch` /
+run in the SpMV kernels' epilogue), `AggregationMultigridPreconditioner` (a V-cycle of aggregation multigrid for a matrix on a
+structured grid), `cg_multi` / `bicgstab_multi` (k right-hand sides per matrix read) and `cg_batch` /
 `bicgstab_batch` / `gmres_batch` (many small systems with one sparsity pattern, one workgroup per system; point- or block-Jacobi
 preconditioned) are the additions.
 """
@@ -17,6 +18,7 @@ from .multi_rhs import cg_multi, bicgstab_multi
 from .batch import BatchedCSR, BatchedJacobiPreconditioner, BatchedBlockJacobiPreconditioner, cg_batch, bicgstab_batch, gmres_batch
 from .torch_tree_util import tree_leaves, tree_map, tree_flatten, tree_unflatten, Partial
 from .preconditioners import BlockJacobiPreconditioner, ChebyshevPreconditioner, JacobiPreconditioner
+from .multigrid import AggregationMultigridPreconditioner
 
 __all__ = [
     'cg', 'bicgstab', 'gmres', 'cg_multi', 'bicgstab_multi',
@@ -25,6 +27,7 @@ __all__ = [
     'LinearSolveFunction',
     'tree_leaves', 'tree_map', 'tree_flatten', 'tree_unflatten', 'Partial',
     'get_last_stats', 'JacobiPreconditioner', 'BlockJacobiPreconditioner', 'ChebyshevPreconditioner',
+    'AggregationMultigridPreconditioner',
 ]
 
 __version__ = '1.0.0'

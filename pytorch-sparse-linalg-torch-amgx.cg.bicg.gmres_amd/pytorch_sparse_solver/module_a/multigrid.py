@@ -1,0 +1,343 @@
+"""Aggregation multigrid on a structured grid, as a preconditioner for the `M` argument of cg / bicgstab / gmres.
+
+`AggregationMultigridPreconditioner(A, grid)` is one V-cycle of plain (unsmoothed) aggregation: 2 x 2 (x 2) boxes of grid points
+are the aggregates, the coarse matrices are the Galerkin products with the piecewise-constant prolongation, the smoother of every
+level is the Chebyshev polynomial of `ChebyshevPreconditioner`, and the coarse correction is over-weighted by `omega`.  Its
+iteration count grows only slowly with the grid, where the polynomial and Jacobi preconditioners follow sqrt(cond(A)).
+
+Like `ChebyshevPreconditioner` the apply consists of SpMVs and element-wise steps only -- no dot product, no atomics -- so it is
+deterministic, independent of launch shapes and bitwise equal to a CPU mirror of the steps (tests/_mg_mirror.py).
+"""
+import math
+
+import torch
+
+from .preconditioners import ChebyshevPreconditioner, _diagonal
+
+__all__ = ["AggregationMultigridPreconditioner", "MG_TAIL_MAX_ROWS"]
+
+# The default of `tail_rows`: levels of at most this many unknowns run inside the one-launch tail kernel (0: none do).
+# Measured (tools/mg_probe.py, profiles/mg_probe.txt, MI355X, fp64, 5-point Poisson 2000 x 2000, degree 1, device time per apply):
+# tail_rows 0: 877.3 us (100 launches), 256: 563.1 us (64), 1024: 532.0 us (55), 4096: 620.3 us (46).  One workgroup walks the
+# levels of up to 1024 rows faster than their launches do, but not the 3969-row one: 1024 had the least time, as it had in the two
+# earlier runs of the probe (656.1 and 774.8 us, before the transfer kernels took the chunk form).  Variable diffusion 2000 x 2000
+# and 7-point 128^3 agree; at 1000 x 1000 4096 is ahead (364.4 against 398.9 us), at 4000 x 4000 256 and 1024 tie.
+MG_TAIL_MAX_ROWS = 1024
+
+
+def _grid3(dims):
+    d = tuple(int(v) for v in dims)
+    return (1,) * (3 - len(d)) + d
+
+
+def _coarse_dims(dims):
+    return tuple((int(v) + 1) // 2 for v in dims)
+
+
+def _aggregate_of(idx: torch.Tensor, dims) -> torch.Tensor:
+    """Coarse row of the fine rows `idx` (int64) of a grid `dims`: (i0 // 2, i1 // 2, i2 // 2) of (i0, i1, i2)."""
+    n0, n1, n2 = _grid3(dims)
+    m0, m1, m2 = _grid3(_coarse_dims(dims))
+    i2 = idx % n2
+    q = torch.div(idx, n2, rounding_mode="floor")
+    i1 = q % n1
+    i0 = torch.div(q, n1, rounding_mode="floor")
+    h = lambda v: torch.div(v, 2, rounding_mode="floor")
+    return (h(i0) * m1 + h(i1)) * m2 + h(i2)
+
+
+def _rows_of(crow: torch.Tensor) -> torch.Tensor:
+    n = crow.numel() - 1
+    return torch.repeat_interleave(torch.arange(n, device=crow.device), crow[1:] - crow[:-1])
+
+
+def _galerkin(crow: torch.Tensor, col: torch.Tensor, val: torch.Tensor, dims):
+    """CSR arrays of P^T A P for the piecewise-constant P of the grid's aggregates.  Entry (I, J) is the sum of the stored entries of
+    A with agg(row) = I and agg(col) = J in the order they are stored in A (s = first; s = s + next, in the storage dtype); rows
+    sorted by column, stored zeros kept.  Torch ops without repeated scatter targets: the same bits on CPU and device, run to run."""
+    crow, col = crow.to(torch.int64), col.to(torch.int64)
+    nc = math.prod(_coarse_dims(dims))
+    key = _aggregate_of(_rows_of(crow), dims) * nc + _aggregate_of(col, dims)
+    skey, order = torch.sort(key, stable=True)              # stable: a segment keeps A's storage order
+    v = val[order]
+    ukey, counts = torch.unique_consecutive(skey, return_counts=True)
+    start = torch.cumsum(counts, 0) - counts
+    s = v[start]
+    for k in range(1, int(counts.max()) if counts.numel() else 0):   # one pass per rank within a segment
+        has = counts > k
+        s = torch.where(has, s + v[torch.where(has, start + k, start)], s)
+    I = torch.div(ukey, nc, rounding_mode="floor")
+    crow_c = torch.zeros(nc + 1, dtype=torch.int64, device=val.device)
+    crow_c[1:] = torch.cumsum(torch.bincount(I, minlength=nc), 0)
+    return crow_c, ukey % nc, s
+
+
+def _abs_row_sums(crow: torch.Tensor, val: torch.Tensor) -> torch.Tensor:
+    """sum_j |a_ij| with each row summed left to right in stored order, whatever the device (the bits of the sequential CPU sum
+    `ChebyshevPreconditioner` takes its Gershgorin bound from)."""
+    crow = crow.to(torch.int64)
+    n = crow.numel() - 1
+    lens = crow[1:] - crow[:-1]
+    K = int(lens.max()) if n and val.numel() else 0
+    if K > 64:        # long rows (a dense matrix as CSR): the sequential CPU sum
+        rows = _rows_of(crow.cpu())
+        return torch.zeros(n, dtype=val.dtype).index_add_(0, rows, val.abs().cpu()).to(val.device)
+    s = torch.zeros(n, dtype=val.dtype, device=val.device)
+    av = val.abs()
+    for k in range(K):
+        has = lens > k
+        s = torch.where(has, s + av[torch.where(has, crow[:-1] + k, 0)], s)
+    return s
+
+
+class _Level:
+    """One level: `csr` (the matrix, a CSR tensor), `dims`, `n`, `dinv` (the reciprocal diagonal) and, except on the level with
+    one unknown, the smoother's coefficients `c0`, `c1`, `c2` (`ChebyshevPreconditioner`'s, `smoother` is that object)."""
+
+    def __init__(self, csr, dims):
+        self.csr, self.dims, self.n = csr, tuple(dims), int(csr.shape[0])
+        crow = csr.crow_indices()
+        self.max_row = int((crow[1:] - crow[:-1]).max())
+        self.smoother = None
+        self.dinv = None
+        self.c0 = self.c1 = self.c2 = None
+
+
+class AggregationMultigridPreconditioner:
+    """M(r) = one V-cycle of aggregation multigrid for a matrix `A` whose unknowns are the points of a structured grid.
+
+    `grid = (n0, n1)` or `(n0, n1, n2)`, slowest dimension first: row (i0 n1 + i1) n2 + i2, prod(grid) == n
+    (`create_poisson_2d_csr(nx, ny)` is `grid=(nx, ny)`; the transposed grid still converges but costs several times the
+    iterations).  `A` is fp64 or fp32 in any layout, on CPU or device; unsorted rows, a column stored twice and stored zeros are
+    accepted.  The supported use is an SPD `A` with `cg`: M is then a fixed SPD operator.  With `bicgstab` / `gmres` it is left
+    preconditioning, deterministic, and promises nothing about convergence.
+
+    Levels.  dims_{l+1} = ceil(dims_l / 2) per dimension, down to the level L with one unknown; the aggregate of fine point
+    (i0, i1, i2) is coarse point (i0 // 2, i1 // 2, i2 // 2).  A_{l+1} = P^T A_l P with the piecewise-constant P: entry (I, J) is
+    the sum of the stored entries of A_l with agg(row) = I, agg(col) = J in A_l's storage order, s = first, s = s + next in the
+    storage dtype; rows sorted by column, stored zeros kept -- the same bits on CPU and device.
+
+    Smoother.  S_l is the recurrence of `ChebyshevPreconditioner(A_l, degree=degree, ratio=ratio, normalize=False)` (lmax the
+    Gershgorin bound, rows summed in stored order); level L is z = dinv_L r, dinv_L = 1 / a.
+
+    The apply V(l, r), every step a separate rounding, no fma, `omega` rounded to the storage dtype once:
+        1. z = S_l(r)
+        2. t = r - A_l z                          (the SpMV's residual form and its one summation order)
+        3. rc[I] = the sum of t over the members of aggregate I in ascending fine index, left to right from the first member
+        4. e = V(l + 1, rc)
+        5. z = z + (omega * e[agg(i)])
+        6. t = r - A_l z;  d = S_l(t);  z = z + d
+    and M(r) = scale * V(0, r) when scale != 1.
+
+    `normalize`.  The reference decides `info` from ||M (b - A x)|| <= tol ||b|| (TSL:1007-1014) and this M approximates A^-1, norm
+    about 1 / lambda_min(A): unscaled, a converged solve mostly returns info = -1.  `normalize=True` estimates the norm of the
+    unscaled cycle by eight steps of the power iteration from v = ones / sqrt(n) (w = M_1 v, lambda = ||w||, v = w / lambda; the
+    constant vector is close to the top eigenvector) and sets scale = 1 / lambda, a host double.  Scaling M changes neither the
+    iterates nor the counts.
+
+    Device vectors run hand-written kernels on the current stream without synchronisation: `hipk_cheb_apply` for S_l, the SpMV's
+    residual form, `hipk_mg_restrict`, `hipk_mg_prolong_add`, `hipk_mg_correct` (step 6's sum and the scale) and `hipk_mg_diag`
+    (level L).  `tail_rows`: the levels from the first one with at most that many unknowns on (capped at 4096; 0: none; None: the
+    module constant `MG_TAIL_MAX_ROWS`) run in ONE launch of one workgroup instead, `hipk_mg_tail_apply`, bit for bit the same
+    result; when one of them has a row of more than 32 stored entries the kernel's envelope is left and they all stay launches.
+    `tail_from` is the first level the tail kernel runs, or None.  Level 0 uses `_hipk.handle_for(A)`, the handle a solve of `A` holds; the object owns a `CsrHandle` per coarse level
+    (the handle cache holds eight entries, a deep hierarchy would flush it) and all work vectors.  CPU vectors run torch ops in
+    exactly the order above, with `_SpecSpmv` for the row sums.
+
+    Attributes: `levels` (per level `csr`, `dims`, `n`, `dinv`, `c0`, `c1`, `c2`), `scale`, `applies`, `tail_rows`, `tail_from`,
+    `launches_per_apply` (the launches of one device apply, a Chebyshev step counted as the one launch it is where the SpMV has
+    the Chebyshev epilogue: 2 degree + 7 per level above the tail -- above L without one --, then one)."""
+
+    def __init__(self, A: torch.Tensor, grid, degree: int = 1, ratio: float = 4.0, omega: float = 1.8, normalize: bool = True,
+                 tail_rows=None):
+        if getattr(A, "_hipk_row_block", False) is True:
+            raise ValueError("AggregationMultigridPreconditioner is not available on a RowBlockCSR")
+        if not (isinstance(A, torch.Tensor) and A.ndim == 2 and A.shape[0] == A.shape[1]):
+            raise ValueError("AggregationMultigridPreconditioner needs a square matrix tensor")
+        if A.dtype not in (torch.float64, torch.float32):
+            raise ValueError(f"AggregationMultigridPreconditioner needs a float64 or float32 matrix, not {A.dtype}")
+        try:
+            dims = tuple(int(v) for v in grid)
+        except TypeError:
+            raise ValueError("grid must be (n0, n1) or (n0, n1, n2)") from None
+        if len(dims) not in (2, 3):
+            raise ValueError(f"grid must have 2 or 3 dimensions, got {len(dims)}")
+        if min(dims) < 1 or math.prod(dims) != A.shape[0]:
+            raise ValueError(f"grid {dims} does not have the matrix's {A.shape[0]} points")
+        if not 1 <= int(degree) <= 32:
+            raise ValueError("degree must be in [1, 32]")
+        if not float(omega) > 0.0:
+            raise ValueError("omega must be positive")
+        self.degree, self.ratio, self.omega = int(degree), float(ratio), float(omega)
+        self.shape = tuple(A.shape)
+        self.dtype, self.device = A.dtype, A.device
+        self._A = A.detach()
+        csr = self._A if A.layout == torch.sparse_csr else \
+            (self._A.coalesce() if A.layout == torch.sparse_coo else self._A).to_sparse_csr()
+        self.levels = []
+        while True:
+            lev = _Level(csr, dims)
+            self._set_up_smoother(lev, len(self.levels))
+            self.levels.append(lev)
+            if lev.n == 1:
+                break
+            crow, col, val = _galerkin(csr.crow_indices(), csr.col_indices(), csr.values(), dims)
+            dims = _coarse_dims(dims)
+            n = math.prod(dims)
+            csr = torch.sparse_csr_tensor(crow, col, val, size=(n, n))
+        L = len(self.levels) - 1
+        # the tail: the levels from the first one of at most `tail_rows` unknowns on, when they all fit the kernel's envelope
+        tail_rows = MG_TAIL_MAX_ROWS if tail_rows is None else int(tail_rows)
+        if tail_rows < 0:
+            raise ValueError("tail_rows must be 0 (no tail kernel) or positive")
+        self.tail_rows = min(tail_rows, 4096)
+        first = next((l for l, lev in enumerate(self.levels) if lev.n <= self.tail_rows), None)
+        self.tail_from = first if first is not None and all(lev.max_row <= 32 for lev in self.levels[first:]) else None
+        self.launches_per_apply = (L if self.tail_from is None else self.tail_from) * (2 * self.degree + 7) + 1
+        self._cpu = None      # per level: (spec SpMV, the aggregate of every row, step 3's gather indices)
+        self._dev = None      # per level: handle and work vectors of the device apply
+        self.scale = 1.0
+        self.applies = 0
+        if normalize:
+            v = torch.full((self.shape[0],), 1.0 / math.sqrt(self.shape[0]), dtype=self.dtype, device=self.device)
+            lam = 1.0
+            for _ in range(8):
+                w = self(v)
+                lam = float(torch.linalg.vector_norm(w.to(torch.float64)))
+                if not (lam > 0.0 and math.isfinite(lam)):
+                    raise ValueError("AggregationMultigridPreconditioner: the norm estimate of the V-cycle broke down "
+                                     f"(||M v|| = {lam}); is the matrix symmetric positive definite?")
+                v = w / lam
+            self.scale = 1.0 / lam
+            self.applies = 0
+
+    def _set_up_smoother(self, lev: _Level, l: int) -> None:
+        csr = lev.csr
+        try:
+            if lev.n == 1:
+                a = csr.values().sum() if csr.values().numel() else torch.zeros((), dtype=csr.dtype)
+                if not float(a) > 0.0:
+                    raise ValueError("zero or negative entry on the diagonal")
+                lev.dinv = torch.reciprocal(a).reshape(1)
+                return
+            sm = ChebyshevPreconditioner(csr, degree=self.degree, lmax=self._gershgorin(csr), ratio=self.ratio, normalize=False)
+        except ValueError as e:
+            raise ValueError(f"AggregationMultigridPreconditioner, level {l} ({'x'.join(map(str, lev.dims))}): {e}") from None
+        lev.smoother, lev.dinv, lev.c0, lev.c1, lev.c2 = sm, sm.dinv, sm.c0, sm.c1, sm.c2
+
+    @staticmethod
+    def _gershgorin(csr) -> float:
+        d = _diagonal(csr)
+        if bool((d <= 0).any()):
+            raise ValueError("zero or negative entry on the diagonal")
+        return float((_abs_row_sums(csr.crow_indices(), csr.values()).to(torch.float64) / d.to(torch.float64)).max())
+
+    # ------------------------------------------------------------------ CPU: torch ops in the documented order
+    def _cpu_state(self):
+        if self._cpu is None:
+            st = []
+            for lev in self.levels[:-1]:
+                n0, n1, n2 = _grid3(lev.dims)
+                m0, m1, m2 = _grid3(_coarse_dims(lev.dims))
+                I = torch.arange(m0 * m1 * m2)
+                I2, q = I % m2, torch.div(I, m2, rounding_mode="floor")
+                I1, I0 = q % m1, torch.div(q, m1, rounding_mode="floor")
+                members = []          # ascending fine index: d2 fastest
+                for d0 in (0, 1):
+                    for d1 in (0, 1):
+                        for d2 in (0, 1):
+                            i0, i1, i2 = 2 * I0 + d0, 2 * I1 + d1, 2 * I2 + d2
+                            has = (i0 < n0) & (i1 < n1) & (i2 < n2)
+                            members.append((has, torch.where(has, (i0 * n1 + i1) * n2 + i2, 0)))
+                st.append((_aggregate_of(torch.arange(lev.n), lev.dims), members))
+            self._cpu = st
+        return self._cpu
+
+    def _v_torch(self, l: int, r: torch.Tensor) -> torch.Tensor:
+        lev = self.levels[l]
+        if lev.n == 1:
+            return lev.dinv.cpu() * r
+        agg, members = self._cpu_state()[l]
+        S = lev.smoother._apply_torch
+        z = S(r)
+        spmv = lev.smoother._cpu[0]         # the smoother's `_SpecSpmv` of A_l, built by its first apply
+        t = r - spmv(z)
+        rc = t[members[0][1]]
+        for has, idx in members[1:]:
+            rc = torch.where(has, rc + t[idx], rc)
+        e = self._v_torch(l + 1, rc)
+        z = z + (torch.tensor(self.omega, dtype=r.dtype) * e[agg])
+        t = r - spmv(z)
+        return z + S(t)
+
+    # ------------------------------------------------------------------ device: one launch per step
+    def _dev_state(self):
+        if self._dev is None:
+            from .. import _hipk
+            dev, dt = self.device, self.dtype
+            st = []
+            tf = len(self.levels) if self.tail_from is None else self.tail_from
+            for l, lev in enumerate(self.levels):
+                s = {"dinv": lev.dinv.to(device=dev, dtype=dt).contiguous()}
+                vec = lambda: torch.empty(lev.n, dtype=dt, device=dev)
+                if l and l <= tf:
+                    s["r"], s["z"] = vec(), vec()
+                if l >= tf:          # a level of the tail kernel: int32 CSR arrays for its descriptor
+                    c = lev.csr
+                    s.update(crow=c.crow_indices().to(torch.int32).contiguous(), col=c.col_indices().to(torch.int32).contiguous(),
+                             val=c.values().contiguous(), dims=lev.dims, max_row=lev.max_row, c0=lev.c0, c1=lev.c1, c2=lev.c2)
+                elif lev.n > 1:
+                    c = lev.csr
+                    s["h"] = _hipk.handle_for(self._A) if l == 0 else \
+                        _hipk.CsrHandle(c.crow_indices(), c.col_indices(), c.values(), c.shape)
+                    s["t"], s["d"] = vec(), vec()
+                    s["work"] = torch.empty(2 * ((lev.n + 3) & ~3) * c.values().element_size(), dtype=torch.uint8, device=dev)
+                st.append(s)
+            if tf < len(self.levels):
+                self._tail = _hipk.MgTail(st[tf:], self.degree)
+                self._tail_work = torch.empty(self._tail.work_bytes, dtype=torch.uint8, device=dev)
+            self._dev = st
+        return self._dev
+
+    def _apply_device(self, v: torch.Tensor) -> torch.Tensor:
+        from .. import _hipk
+        st, levels = self._dev_state(), self.levels
+        L = len(levels) - 1 if self.tail_from is None else self.tail_from      # the last level the launches reach
+        if not v.is_contiguous() or v.data_ptr() % 16:
+            v = v.contiguous().clone()
+        out = torch.empty_like(v)
+        r = lambda l: v if l == 0 else st[l]["r"]
+        z = lambda l: out if l == 0 else st[l]["z"]
+        smooth = lambda l, src, dst: _hipk.cheb_apply(st[l]["h"], self.degree, st[l]["dinv"], levels[l].smoother._coef, src,
+                                                      work=st[l]["work"], out=dst)
+        for l in range(L):
+            smooth(l, r(l), z(l))
+            _hipk.spmv_residual(st[l]["h"], z(l), r(l), st[l]["t"])
+            _hipk.mg_restrict(levels[l].dims, st[l]["t"], r(l + 1))
+        if self.tail_from is None:
+            _hipk.mg_diag(self.scale if L == 0 else 1.0, st[L]["dinv"], r(L), z(L))
+        else:
+            _hipk.mg_tail_apply(self._tail, self.omega, self.scale if L == 0 else 1.0, r(L), z(L), work=self._tail_work)
+        for l in range(L - 1, -1, -1):
+            _hipk.mg_prolong_add(levels[l].dims, self.omega, z(l + 1), z(l))
+            _hipk.spmv_residual(st[l]["h"], z(l), r(l), st[l]["t"])
+            smooth(l, st[l]["t"], st[l]["d"])
+            _hipk.mg_correct(self.scale if l == 0 else 1.0, st[l]["d"], z(l))
+        return out
+
+    def __call__(self, v):
+        n = self.shape[0]
+        if not isinstance(v, torch.Tensor) or v.shape != (n,):
+            raise ValueError(f"AggregationMultigridPreconditioner for {n} unknowns applied to a vector of shape "
+                             f"{tuple(getattr(v, 'shape', ()))}")
+        if v.dtype != self.dtype or v.device != self.device:
+            raise ValueError(f"AggregationMultigridPreconditioner of a {self.dtype} matrix on {self.device} applied to a {v.dtype} "
+                             f"vector on {v.device}")
+        if v.is_cuda:
+            z = self._apply_device(v.detach())
+        else:
+            z = self._v_torch(0, v.detach())
+            if self.scale != 1.0:
+                z = torch.tensor(self.scale, dtype=v.dtype) * z
+        self.applies += 1
+        return z

@@ -1,0 +1,149 @@
+"""AggregationMultigridPreconditioner against plain cg and the Chebyshev preconditioner on one MI355X, fp64, one process.
+
+For every system -- 5-point Poisson 1000^2, 2000^2 and 4000^2, `create_variable_diffusion_2d_csr(2000, 2000)`, 7-point Poisson 128^3;
+b = ones, cg(tol=1e-6) -- the four configurations
+    plain | ChebyshevPreconditioner(degree=3) | multigrid degree 1 | multigrid degree 2
+are solved `--reps` times in alternation (plain, cheb, mg1, mg2, plain, ...): wall clock around the whole public call, device
+synchronised before and after; iterations, info and the true relative residual are recorded, times as min..max.  Plain cg does not
+touch the code of this preconditioner: it is the library's path as it was.  The preconditioners are built once per system (the
+set-up time is printed, it is not part of a solve).
+
+Then the device time of one multigrid apply (HIP events around `--applies` applies, degree 1) at tail_rows 0 / 256 / 1024 / 4096:
+what the one-launch tail kernel is worth against the launch sequence on the same levels.  MG_TAIL_MAX_ROWS is set from the
+2000^2 row.
+
+  python tools/mg_probe.py                                  # everything; one JSON line per system
+  python tools/mg_probe.py --systems poisson2000 --reps 1 --configs mg1 --applies 0      # one solve (for rocprofv3 --kernel-trace)
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "pytorch-sparse-linalg-torch-amgx.cg.bicg.gmres_amd"))
+
+import torch  # noqa: E402
+
+DEV = "cuda:0"
+TAILS = (0, 256, 1024, 4096)
+
+
+def poisson_3d_csr(n0, n1, n2, device):
+    """7-point Dirichlet Laplacian on an n0 x n1 x n2 box, row (i0 n1 + i1) n2 + i2: diagonal 6, neighbours -1, sorted rows."""
+    idx = torch.arange(n0 * n1 * n2, device=device).reshape(n0, n1, n2)
+    rows, cols = [idx.reshape(-1)], [idx.reshape(-1)]
+    for d in range(3):
+        lo, hi = idx.narrow(d, 0, idx.shape[d] - 1).reshape(-1), idx.narrow(d, 1, idx.shape[d] - 1).reshape(-1)
+        rows += [lo, hi]
+        cols += [hi, lo]
+    r, c = torch.cat(rows), torch.cat(cols)
+    v = torch.where(r == c, 6.0, -1.0).to(torch.float64)
+    n = n0 * n1 * n2
+    return torch.sparse_coo_tensor(torch.stack([r, c]), v, (n, n)).coalesce().to_sparse_csr()
+
+
+def systems():
+    from pytorch_sparse_solver.utils.matrix_utils import create_poisson_2d_csr, create_variable_diffusion_2d_csr
+    return {
+        "poisson1000": (lambda: create_poisson_2d_csr(1000, 1000, device=DEV), (1000, 1000)),
+        "poisson2000": (lambda: create_poisson_2d_csr(2000, 2000, device=DEV), (2000, 2000)),
+        "poisson4000": (lambda: create_poisson_2d_csr(4000, 4000, device=DEV), (4000, 4000)),
+        "vardiff2000": (lambda: create_variable_diffusion_2d_csr(2000, 2000, device=DEV), (2000, 2000)),
+        "poisson3d128": (lambda: poisson_3d_csr(128, 128, 128, DEV), (128, 128, 128)),
+    }
+
+
+def _timed(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    out = fn()
+    torch.cuda.synchronize()
+    return out, time.perf_counter() - t0
+
+
+def run_system(name, make, grid, reps, configs, applies):
+    from pytorch_sparse_solver.module_a import AggregationMultigridPreconditioner, ChebyshevPreconditioner, cg, get_last_stats
+    A = make()
+    n = A.shape[0]
+    b = torch.ones(n, dtype=torch.float64, device=DEV)
+    bn = float(torch.linalg.vector_norm(b))
+    row = {"system": name, "n": n, "grid": list(grid), "nnz": int(A.values().numel())}
+    Ms, setup = {"plain": None}, {}
+    for cfg in configs:
+        if cfg == "cheb3":
+            Ms[cfg], setup[cfg] = _timed(lambda: ChebyshevPreconditioner(A, degree=3))
+        elif cfg.startswith("mg"):
+            Ms[cfg], setup[cfg] = _timed(lambda: AggregationMultigridPreconditioner(A, grid, degree=int(cfg[2:])))
+    row["setup_ms"] = {k: round(1e3 * v, 1) for k, v in setup.items()}
+    mg = next((Ms[c] for c in configs if c.startswith("mg")), None)
+    if mg is not None:
+        row["levels"] = [lev.n for lev in mg.levels]
+        row["tail_from"], row["launches_per_apply"] = mg.tail_from, mg.launches_per_apply
+    for cfg in configs:                                   # warm-up: code objects, allocator, the handle of A
+        cg(A, b, tol=1e-6, M=Ms[cfg], maxiter=5)
+    times = {cfg: [] for cfg in configs}
+    for _ in range(reps):
+        for cfg in configs:
+            (x, info), t = _timed(lambda: cg(A, b, tol=1e-6, M=Ms[cfg]))
+            st = get_last_stats()
+            times[cfg].append(t)
+            row[cfg] = {"iterations": st.iterations, "info": int(info), "method": st.method,
+                        "relres": float(torch.linalg.vector_norm(b - A @ x)) / bn}
+    for cfg in configs:
+        row[cfg]["ms_min_max"] = [round(1e3 * min(times[cfg]), 2), round(1e3 * max(times[cfg]), 2)]
+        row[cfg]["ms_per_iteration"] = round(1e3 * min(times[cfg]) / max(row[cfg]["iterations"], 1), 4)
+        if cfg != "plain" and "plain" in configs:
+            row[cfg]["time_over_plain"] = round(min(times[cfg]) / min(times["plain"]), 3)
+    if applies > 0:
+        v = torch.randn(n, dtype=torch.float64, device=DEV)
+        row["apply_us_by_tail_rows"] = {}
+        ref = None
+        for tail in TAILS:
+            M = AggregationMultigridPreconditioner(A, grid, degree=1, tail_rows=tail)
+            for _ in range(3):
+                z = M(v)
+            ref = z if ref is None else ref
+            assert torch.equal(z, ref), "the tail kernel changed the result"
+            best = float("inf")
+            for _ in range(3):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                e0.record()
+                for _ in range(applies):
+                    M(v)
+                e1.record()
+                torch.cuda.synchronize()
+                best = min(best, 1e3 * e0.elapsed_time(e1) / applies)
+            row["apply_us_by_tail_rows"][str(tail)] = {"us": round(best, 1), "tail_from": M.tail_from, "launches": M.launches_per_apply}
+            del M
+    return row
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--systems", nargs="*", default=None)
+    ap.add_argument("--configs", nargs="*", default=["plain", "cheb3", "mg1", "mg2"])
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--applies", type=int, default=20)
+    a = ap.parse_args()
+    from pytorch_sparse_solver import _hipk
+    from pytorch_sparse_solver.module_a import multigrid
+    print(json.dumps({"hipk_build_id": _hipk.lib().hipk_build_id().decode(), "device": torch.cuda.get_device_name(0), "reps": a.reps,
+                      "applies": a.applies, "tol": 1e-6, "dtype": "float64", "MG_TAIL_MAX_ROWS": multigrid.MG_TAIL_MAX_ROWS}), flush=True)
+    table = systems()
+    for name in a.systems or list(table):
+        make, grid = table[name]
+        try:
+            row = run_system(name, make, grid, a.reps, a.configs, a.applies)
+        except torch.cuda.OutOfMemoryError as e:
+            row = {"system": name, "skipped": f"does not fit: {str(e).splitlines()[0]}"}
+        print(json.dumps(row), flush=True)
+        _hipk.clear_cache()
+        torch.cuda.empty_cache()
+
+
+if __name__ == "__main__":
+    main()
