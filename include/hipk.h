@@ -161,6 +161,9 @@ const char *hipk_last_solve_form(void);
  * tail of the fused SpMV + update launch (hipk_cg_fuse_update_kernel) instead of a launch of its own; 0 when none did.  The note,
  * path and form of such a solve are those of the fused sequence it is a variant of. */
 int hipk_last_cg_fused_directions(void);
+/* ... and those of them whose launch kept p of its uniform tiles in registers between the SpMV walk and the direction tail
+ * instead of loading it again (0 with HIPK_CG_FUSE_KEEP_P=0). */
+int hipk_last_cg_fused_kept_p(void);
 int hipk_solve_form_count(void);
 const char *hipk_solve_form_name(int i);
 /* mode 0: automatic (default); 1: never use the coded forms (A/B measurements, parity tests).

@@ -1274,6 +1274,7 @@ struct hipk_cg_path {
     bool defer_x = false;      // plain CG, three launches: x updated every second iteration (hipk_cg_pdir_kernel / hipk_cg_xdir_kernel)
     bool fuse_update = false;  // plain CG, fp64 stencils: SpMV and update step in one launch (hipk_cg_fuse_update_kernel), two launches in all
     bool fuse_dir = false;     // ... and, with the x update deferred, the direction step as that launch's tail: one launch in all
+    bool fuse_keep_p = false;  // ... whose p_k of uniform tiles stays in the walk's registers instead of being loaded again
     void (*fuse_kern)(hipk_spmv_args, hipk_cg_fuse_args) = nullptr;
     hipk_spmv_args fuse_sa;    // ... its SpMV arguments, as hipk_launch_spmv fills them for the kernel it replaces
 };
@@ -1364,12 +1365,14 @@ static void hipk_cg_path_defer(hipk_cg_path &path, const hipk_csr_s *A, const hi
 // HIPK_CG_FUSE_UPDATE=0|1 forces (read per solve).
 // fuse_dir: with the x update deferred (path.defer_x) the direction step runs as that launch's tail, same envelope;
 // HIPK_CG_FUSE_DIRECTION=0|1 forces (read per solve).
+// fuse_keep_p: the tail takes p_k of the uniform tiles from the walk's registers (hipk_cg_fuse.h, step 7); HIPK_CG_FUSE_KEEP_P=0
+// makes it load all of p_k again (read per solve; same bits).
 // No gate by chunk count inside that envelope: every run beat every run of the separate kernels at 591, 958 and 1954 chunks (+2 %,
 // +6 %, +11.7 %: profiles/cg_fuse_update_ab.md).
 template <typename T>
 static void hipk_cg_path_fuse(hipk_cg_path &path, hipk_csr_s *A, const hipk_params *prm, bool done, int64_t it, int64_t maxiter,
                               const hipk_spmv_args &sa) {
-    path.fuse_update = path.fuse_dir = false;
+    path.fuse_update = path.fuse_dir = path.fuse_keep_p = false;
     if (sizeof(T) != 8 || done || path.two_launch || path.small || path.streams || A->op_cb != nullptr || prm->profile != 0 ||
         A->geom.ch != HIPK_BASE_CHUNK || A->geom.g <= kMidMaxChunks || A->cg_fuse_failed || maxiter - it >= ((int64_t)1 << 31) ||
         !hipk_sw_force("HIPK_CG_FUSE_UPDATE", true))
@@ -1382,6 +1385,7 @@ static void hipk_cg_path_fuse(hipk_cg_path &path, hipk_csr_s *A, const hipk_para
     (void)hipGetLastError();
     path.fuse_update = resident;
     path.fuse_dir = resident && path.defer_x && hipk_sw_force("HIPK_CG_FUSE_DIRECTION", true);
+    path.fuse_keep_p = path.fuse_dir && hipk_sw_enabled("HIPK_CG_FUSE_KEEP_P");
 }
 
 // {redo, it_done, stop_it} of a host copy of hipk_cg_scal / hipk_pcg_scal (hipk_resident_run)
@@ -1784,6 +1788,9 @@ __global__ __launch_bounds__(HIPK_THREADS) void hipk_pcg_final_kernel(hipk_pcg_s
 // tail of hipk_cg_fuse_update_kernel
 static thread_local int64_t hipk_cg_fused_directions = 0;
 extern "C" int hipk_last_cg_fused_directions(void) { return (int)(hipk_cg_fused_directions > INT32_MAX ? INT32_MAX : hipk_cg_fused_directions); }
+// hipk_last_cg_fused_kept_p: ... and those of them whose launch had keep_p set
+static thread_local int64_t hipk_cg_fused_kept_p = 0;
+extern "C" int hipk_last_cg_fused_kept_p(void) { return (int)(hipk_cg_fused_kept_p > INT32_MAX ? INT32_MAX : hipk_cg_fused_kept_p); }
 
 // what the three-launch sequence of plain CG launches for its update and direction steps (hipk_cg_steps::pick)
 template <typename T>
@@ -2107,6 +2114,7 @@ struct hipk_cg_steps {
         ff.p_next = (double *)p_next;
         ff.x = (double *)xq;
         ff.maxiter = maxiter;
+        ff.keep_p = p_next != nullptr && path.fuse_keep_p ? 1 : 0;
         ff.dir_give_up = p_next != nullptr && it == fuse_dir_give_up_at ? 1 : 0;
         path.fuse_kern<<<hipk_xcd_grid(gm.g), HIPK_THREADS, 0, stream>>>(fa, ff);
     }
@@ -2125,6 +2133,7 @@ struct hipk_cg_steps {
         HIPK_CHECK_HIP(hipStreamSynchronize(stream));
         const int64_t ran = (hs.stop_it < it ? hs.stop_it : it) - it0;   // iterations this sequence completed
         if (path.fuse_dir) hipk_cg_fused_directions += ran > 0 ? ran : 0;
+        if (path.fuse_keep_p) hipk_cg_fused_kept_p += ran > 0 ? ran : 0;
         if (hs.ctl.redo == -3) {
             hipk_set_error("hipk_cg_solve: the collector of the fused SpMV + update launch stopped arriving");
             return HIPK_ERR_HIP;
@@ -2132,7 +2141,7 @@ struct hipk_cg_steps {
         const bool dir_gave_up = path.fuse_dir && hs.ctl.redo == kFuseDirGaveUp;
         if (hs.ctl.redo != -1 && !dir_gave_up) return HIPK_OK;
         A->cg_fuse_failed = 1;
-        path.fuse_update = path.fuse_dir = false;
+        path.fuse_update = path.fuse_dir = path.fuse_keep_p = false;
         it = hs.stop_it;
         stop = INT64_MAX;
         HIPK_CHECK_HIP(hipMemcpyAsync(&scal->stop_it, &stop, sizeof(int64_t), hipMemcpyHostToDevice, stream));
@@ -2246,7 +2255,7 @@ template <typename T>
 static int hipk_cg_solve_t(hipk_csr_s *A, const T *b, T *x, char *work, const hipk_params *prm, hipk_stats *st, hipStream_t stream) {
     static bool mid_failed = false, lds_loop_failed = false;   // per dtype; hipk_pcg_solve_t has its own
     hipk_cg_steps<T, false> s(A, nullptr, b, x, work, prm, stream, prm->profile);
-    hipk_cg_fused_directions = 0;
+    hipk_cg_fused_directions = hipk_cg_fused_kept_p = 0;
     HIPK_TRY(s.start());
     HIPK_TRY(s.one_launch(mid_failed, lds_loop_failed, "hipk_cg_solve"));
     // what is left when neither loop finished: two launches per iteration, else three with the x update deferred, else three

@@ -18,8 +18,10 @@
 // Only <r,r> stands between the r update and p = r + beta p, and r_{k+1} is in this thread's registers already:
 //   6. every workgroup publishes its <r,r> partial (the value it stores to part_rr[c]) as a flagged word of a SECOND words region
 //      (g x 16 bytes and eight replicas of its own, behind the first region's replicas at the head of Ap);
-//   7. requests its elements of p_k (the walk's operand) in hipk_cg_dir_chunk's layout, before the wait; on an x iteration (every
-//      second one: x set) the x part comes here too, x = (x + alpha_{k-1} p_{k-1}) + alpha_k p_k with hipk_cg_dir_chunk's
+//   7. takes its elements of p_k (the walk's operand) in hipk_cg_dir_chunk's layout: with keep_p the steps whose tile was uniform
+//      are in this thread's registers since the walk (hipk_sell_wide_walk's `keep`: the diagonal entry's load) and only the steps
+//      of tiles with a grid-line end are requested, before the wait; without it, and in workgroup 0, all of them are.  On an x
+//      iteration (every second one: x set) the x part comes here too, x = (x + alpha_{k-1} p_{k-1}) + alpha_k p_k with hipk_cg_dir_chunk's
 //      operations and roundings, p_{k-1} read from the buffer that will receive p_{k+1}, one step's x and p_{k-1} at a time (the
 //      four operands of four steps do not fit 64 registers); its stores leave before the wait;
 //   8. workgroup 0 polls the g words (two per thread in flight, four times: hipk_parts_pre::fold's order, then hipk_block_sum --
@@ -27,8 +29,8 @@
 //      does hipk_cg_dir_done (the next pass's gamma, the stop test, the host's signal word) and only then its own step 7;
 //      everybody else polls replica b & 7 as at the first hand-off;
 //   9. beta = (T)(<r,r> / gamma), p_{k+1} = r_{k+1} + beta p_k into the other p buffer.
-// Per iteration the tail moves 16 n bytes (p in, p out) where hipk_cg_pdir_kernel moves 24 n, and 40 n where hipk_cg_xdir_kernel
-// moves 48 n: r is not read again, and there is no second launch.  When the collector of the second hand-off gives up
+// Per iteration the tail moves 16 n bytes (p in, p out; 8 n plus the non-uniform tiles' rows with keep_p) where hipk_cg_pdir_kernel
+// moves 24 n, and 40 n where hipk_cg_xdir_kernel moves 48 n: r is not read again, and there is no second launch.  When the collector of the second hand-off gives up
 // (HIPK_TEST_CG_FUSE_DIR_GIVE_UP) it hands out the give-up mark, sets stop_it = it and ctl.redo = kFuseDirGaveUp: no workgroup
 // stores p_{k+1} and hipk_cg_dir_done is not run -- the state is iteration `it` after its update (x included on an x iteration),
 // and hipk_cg_steps::fuse_end finishes the iteration with hipk_cg_pdir_kernel.
@@ -65,6 +67,7 @@ struct hipk_cg_fuse_args {
     double *p_next;     // receives p_{k+1} = r_{k+1} + beta p_k; p_k is the walk's operand (a.x).  On an x iteration it holds p_{k-1}
     double *x;          // not null: an x iteration, x = (x + alpha_{k-1} p_{k-1}) + alpha_k p_k before the second wait
     int64_t maxiter;    // hipk_cg_dir_done's
+    int keep_p;         // the tail takes p_k of uniform tiles from the walk's registers (HIPK_CG_FUSE_KEEP_P=0: loads all of it)
     int dir_give_up;    // HIPK_TEST_CG_FUSE_DIR_GIVE_UP: the collector of the SECOND hand-off behaves as if its poll had run out
 };
 
@@ -74,10 +77,12 @@ __global__ __launch_bounds__(HIPK_THREADS) HIPK_SGPR80 void hipk_cg_fuse_update_
     constexpr int VEC = hipk_vec<T>::VEC, N0 = HIPK_BASE_CHUNK / (VEC * HIPK_THREADS);
     constexpr unsigned STEP = VEC * HIPK_THREADS;
     static_assert(HIPK_MAX_PARTS / HIPK_THREADS == 8, "the collector's poll: eight words per thread");
+    static_assert(N0 == HIPK_FUSE_TPC / 2 && VEC == 2, "step k of the tail is the walk's tile 2 k + (wave >> 1), two rows per lane");
     __shared__ double s_pap;
     __shared__ int s_fail;
     hipk_wide_chunk wc;
-    if (!hipk_sell_wide_walk<UNITS, HIPK_SPMV_DOT_W, 0, true>(a, &wc)) return;   // padding workgroup, or the stop word has fired
+    T pv[N0][VEC];   // p_k of this thread's elements: the walk leaves the steps of uniform tiles here (wc.kept), step 7 loads the others
+    if (!hipk_sell_wide_walk<UNITS, HIPK_SPMV_DOT_W, 0, true>(a, &wc, pv)) return;   // padding workgroup, or the stop word has fired
     const int t = threadIdx.x, lane = t & 63;
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
     const int c = wc.chunk;
@@ -112,6 +117,9 @@ __global__ __launch_bounds__(HIPK_THREADS) HIPK_SGPR80 void hipk_cg_fuse_update_
     }
     // 4. the collector folds; everybody else waits for one of its replicas
     if (blockIdx.x == 0) {
+        // (the collector loads all of its p in step 7: the walk's values die here, or they would sit beside the polled words)
+#pragma unroll
+        for (int k = 0; k < N0; ++k) pv[k][0] = pv[k][1] = (T)0;
         double acc = 0.0;
         if (f.give_up) {
             if (t == 0) s_fail = 1;
@@ -191,13 +199,13 @@ __global__ __launch_bounds__(HIPK_THREADS) HIPK_SGPR80 void hipk_cg_fuse_update_
     // (The collector does this behind its hand-out: on an x iteration the step ends with stores, and the fold's barriers wait for them.)
     const T *const pb = (const T *)a.x + base;
     T *const qb = f.p_next + base;
-    T pv[N0][VEC];
+    const unsigned kept = (f.keep_p && blockIdx.x != 0) ? wc.kept : 0u;   // (a kept step is a whole tile: nv = VEC)
     auto request_p = [&]() {
 #pragma unroll
         for (int k = 0; k < N0; ++k) {
             const int o = (int)(o0 + k * STEP);
             const int nv = (lim - o < VEC) ? lim - o : VEC;
-            if (nv > 0) hipk_ld<T>(pb, o, nv, pv[k]);
+            if (nv > 0 && !((kept >> k) & 1u)) hipk_ld<T>(pb, o, nv, pv[k]);
         }
         if (f.x != nullptr) {
             T *const xb = f.x + base;
@@ -224,6 +232,8 @@ __global__ __launch_bounds__(HIPK_THREADS) HIPK_SGPR80 void hipk_cg_fuse_update_
     };
     // 8. the collector folds <r,r> (hipk_parts_pre::fold's bits) and does the bookkeeping of a direction kernel
     if (blockIdx.x == 0) {
+#pragma unroll
+        for (int k = 0; k < N0; ++k) pv[k][0] = pv[k][1] = (T)0;   // (as at the first hand-off: nothing of p lives across the poll)
         // (the polled words beside r_{k+1} do not fit the 64 vector registers: r_{k+1} waits in the staged Ap's place, which step
         // 5 has read -- every thread its own elements, so no barrier)
 #pragma unroll

@@ -1040,12 +1040,19 @@ static __device__ unsigned long long hipk_wide_stamps[2048 * 4 * HIPK_WIDE_NSTAM
 // rows' results do not go to y but stay in LDS (`stage`, indexed by the row's place in the chunk: 2048 doubles), the tile sums are
 // sized by the 8 tiles of such a chunk, and the walk ends BEFORE the chunk fold: *out tells the caller where the chunk's pieces
 // are (true), or nothing is to be done (false: a padding workgroup, or the stop word has fired -- nothing was stored).
+// FUSE also hands back the operand w of the uniform tiles this thread formed (`keep`, `kept`): thread T of wavefront pair wp takes
+// rows 256 i + 2 (T - 128 wp) and the next one of local uniform tile i = 2 k + wp -- chunk offset 512 k + 2 T, exactly the elements
+// thread T owns in step k of the vector kernels' layout.  With w == x (the CG loop: <p, A p>) the caller need not load its
+// elements of p again.  Only the first HIPK_FUSE_KEEP(UNITS) steps are kept: the 8-wide tile holds sixteen gathered doubles per
+// lane, and every kept step lives across them (63 vector registers with one step kept, 65 / 68 / 72 with two / three / four).
 #define HIPK_FUSE_TPC (HIPK_BASE_CHUNK / 256)
+#define HIPK_FUSE_KEEP(UNITS) ((UNITS) == 8 ? 1 : HIPK_FUSE_TPC / 2)
 struct hipk_wide_chunk {
     int chunk, cnt;    // the workgroup's reduction chunk and its tiles
     double *wsum0;     // LDS: per-wavefront sums of <w, y>, 4 per tile (hipk_wave_fold folds them)
     double *stage;     // LDS: y of the chunk's rows
     double *free256;   // LDS: 256 doubles the walk no longer needs (the dictionary's values), e.g. for hipk_block_sum
+    unsigned kept;     // wave-uniform, bit k: keep[k] holds w of this thread's two rows of local tile 2 k + (wave >> 1)
 };
 template <bool FUSE>
 struct hipk_wide_stage {
@@ -1059,7 +1066,8 @@ struct hipk_wide_stage<true> {
     }
 };
 template <int UNITS, int MODE, int WALK, bool FUSE = false>
-__device__ __forceinline__ bool hipk_sell_wide_walk(const hipk_spmv_args &a, hipk_wide_chunk *out = nullptr) {
+__device__ __forceinline__ bool hipk_sell_wide_walk(const hipk_spmv_args &a, hipk_wide_chunk *out = nullptr,
+                                                    double (*keep)[2] = nullptr) {
     typedef double T;
     static_assert(!FUSE || (WALK == 0 && MODE == HIPK_SPMV_DOT_W), "the fused form: chunk walk, <w, y> compiled in");
     constexpr bool STRIDED = WALK != 0;  // tile sums to the per-tile buffer, no in-kernel fold
@@ -1215,7 +1223,7 @@ __device__ __forceinline__ bool hipk_sell_wide_walk(const hipk_spmv_args &a, hip
         sbo[k] = 0;
         sv[k] = (T)0;
     }
-    auto uniform_tile = [&](int tl, int i, unsigned long long uc_in) {
+    auto uniform_tile = [&](int tl, int i, unsigned long long uc_in) -> double2 {   // returns w of the lane's two rows
         // a MASKED tile: the rows have subsets of the pattern; the marker byte reads as padding below
         const bool masked = (unsigned)(uc_in >> 56) == HIPK_SELL_MASKED;
         const unsigned long long uc = masked ? (uc_in | 0xFF00000000000000ull) : uc_in;
@@ -1315,6 +1323,7 @@ __device__ __forceinline__ bool hipk_sell_wide_walk(const hipk_spmv_args &a, hip
                 else wsum1[slot] = r;
             }
         }
+        return ow;
     };
 
     // ---- the tiles whose rows differ first, whole workgroup
@@ -1323,6 +1332,35 @@ __device__ __forceinline__ bool hipk_sell_wide_walk(const hipk_spmv_args &a, hip
         per_lane_tile(t_first + i, i);
     }
     HIPK_WSTAMP(3);
+    if constexpr (FUSE) {
+        // the same walk, step k = i >> 1 counted: w of the first steps stays in keep[k] (k is scalar: the stores sit behind
+        // uniform branches, keep[] is indexed statically and stays in registers)
+        constexpr int KEEP = HIPK_FUSE_KEEP(UNITS);
+        unsigned kept = 0u;
+        for (int k = 0; 2 * k + wp < cnt; ++k) {
+            const int i = 2 * k + wp;
+            const unsigned long long uc = tile_ucode_of(i);
+            if (uc == 0ull) continue;
+            const double2 ow = uniform_tile(t_first + i, i, uc);
+            if (k < KEEP) kept |= 1u << k;
+            if (k == 0) {
+                keep[0][0] = ow.x;
+                keep[0][1] = ow.y;
+            } else if (KEEP > 1 && k == 1) {
+                keep[1][0] = ow.x;
+                keep[1][1] = ow.y;
+            } else if (KEEP > 2 && k == 2) {
+                keep[2][0] = ow.x;
+                keep[2][1] = ow.y;
+            } else if (KEEP > 3 && k == 3) {
+                keep[3][0] = ow.x;
+                keep[3][1] = ow.y;
+            }
+        }
+        HIPK_WSTAMP(5);
+        *out = {chunk, cnt, wsum0, stage, (double *)dval, kept};
+        return true;
+    }
     // ---- the uniform tiles of this wavefront pair's parity
     for (int i = wp; i < cnt; i += 2) {
         const unsigned long long uc = tile_ucode_of(i);
@@ -1333,10 +1371,6 @@ __device__ __forceinline__ bool hipk_sell_wide_walk(const hipk_spmv_args &a, hip
 #endif
     }
     HIPK_WSTAMP(5);
-    if constexpr (FUSE) {
-        *out = {chunk, cnt, wsum0, stage, (double *)dval};
-        return true;
-    }
     if (!STRIDED && (mode & (HIPK_SPMV_DOT_W | HIPK_SPMV_DOT_YY))) {
         __syncthreads();
         HIPK_WSTAMP(6);

@@ -28,7 +28,7 @@ GMRES_BATCHED, GMRES_INCREMENTAL = 0, 1
 SYMBOLS = [
     "hipk_version", "hipk_build_id", "hipk_op_create", "hipk_placement_probe", "hipk_last_error", "hipk_device_count",
     "hipk_csr_create", "hipk_csr_destroy", "hipk_csr_rows", "hipk_csr_nnz", "hipk_csr_spmv_bytes",
-    "hipk_csr_spmv_path", "hipk_last_spmv_kernel", "hipk_last_solve_path", "hipk_last_solve_form", "hipk_last_cg_fused_directions", "hipk_solve_form_count", "hipk_solve_form_name", "hipk_csr_set_path", "hipk_csr_format_bytes",
+    "hipk_csr_spmv_path", "hipk_last_spmv_kernel", "hipk_last_solve_path", "hipk_last_solve_form", "hipk_last_cg_fused_directions", "hipk_last_cg_fused_kept_p", "hipk_solve_form_count", "hipk_solve_form_name", "hipk_csr_set_path", "hipk_csr_format_bytes",
     "hipk_csr_transpose_work_bytes", "hipk_csr_transpose",
     "hipk_chunk_size", "hipk_chunk_count", "hipk_scratch_bytes",
     "hipk_spmv", "hipk_spmv_dot", "hipk_dot", "hipk_axpy", "hipk_xpby", "hipk_block_jacobi_apply",
@@ -195,6 +195,8 @@ def lib():
     L.hipk_last_solve_form.restype = ctypes.c_char_p
     if hasattr(L, "hipk_last_cg_fused_directions"):   # (HIPK_LIB_PATH may name an older build: A/B runs against the parent commit)
         L.hipk_last_cg_fused_directions.restype = ctypes.c_int
+    if hasattr(L, "hipk_last_cg_fused_kept_p"):
+        L.hipk_last_cg_fused_kept_p.restype = ctypes.c_int
     L.hipk_solve_form_count.restype = ctypes.c_int
     L.hipk_solve_form_name.restype = ctypes.c_char_p
     L.hipk_solve_form_name.argtypes = [ctypes.c_int]
@@ -333,6 +335,12 @@ def last_cg_fused_directions() -> int:
     """The iterations of this thread's last CG solve whose direction step ran inside the fused SpMV + update launch
     (hipk_last_cg_fused_directions); 0 when none did."""
     return int(lib().hipk_last_cg_fused_directions())
+
+
+def last_cg_fused_kept_p() -> int:
+    """The iterations of this thread's last CG solve whose fused launch kept p of its uniform tiles in registers for the
+    direction tail (hipk_last_cg_fused_kept_p); 0 when none did."""
+    return int(lib().hipk_last_cg_fused_kept_p())
 
 
 def solve_forms() -> list:
