@@ -427,6 +427,43 @@ size_t hipk_mg_tail_work_bytes(const hipk_mg_level *levels_host, int nlev, int d
 int hipk_mg_tail_apply(const hipk_mg_level *levels_host, const void *levels_dev, int nlev, int degree, double omega, double scale,
                        const void *r, void *z, int dtype, void *work, size_t work_bytes, hipk_stream_t stream);
 
+/* ---- aggregation multigrid on a matrix graph: the transfer steps by index arrays (csrc/hipk_mg_graph.hip) ----
+ * The same steps for `AggregationMultigridPreconditioner.from_graph`, whose aggregates are not boxes.  A fine level of n rows and
+ * a coarse one of nc (1 <= nc <= n < 2^31) are linked by int32 device arrays, read only:
+ *   agg  : n entries, the aggregate of every fine row, in [0, nc);
+ *   aptr : nc + 1 entries, aptr[0] = 0, aptr[nc] = n, strictly ascending (an aggregate has at least one member, any number);
+ *   amem : n entries, amem[aptr[I] .. aptr[I + 1]) the members of aggregate I in ascending fine index.
+ * The CONTENTS of the index arrays are the caller's responsibility: they are not checked.  Every call is one streaming launch
+ * enqueued on `stream` and never synchronises; the kernel walks the vector it writes in the library's chunk form, 16-byte
+ * groups; vectors are of `dtype`, vectors and index arrays 16-byte aligned (else HIPK_ERR_ALIGN) and distinct; elements at and
+ * beyond a vector's length are never read or written.  One rounding per operation, no fma, no atomics; `omega` is rounded to
+ * `dtype` once.  n or nc out of range, a null pointer or t == rc / e == z: HIPK_ERR_ARG; another dtype: HIPK_ERR_UNSUPPORTED.
+ *   hipk_mg_restrict_agg    : rc[I] = t[amem[aptr[I]]], then rc[I] = rc[I] + t[amem[k]] for k = aptr[I] + 1 .. aptr[I + 1] - 1.
+ *   hipk_mg_prolong_add_agg : z[i] = z[i] + (omega * e[agg[i]]), i < n. */
+int hipk_mg_restrict_agg(int64_t n, int64_t nc, const int32_t *aptr, const int32_t *amem, const void *t, void *rc, int dtype,
+                         hipk_stream_t stream);
+int hipk_mg_prolong_add_agg(int64_t n, int64_t nc, const int32_t *agg, double omega, const void *e, void *z, int dtype,
+                            hipk_stream_t stream);
+/* hipk_mg_tail_apply for index-array levels (hipk_mg_gtail_kernel<T>, one launch of one 256-thread workgroup): levels[0 .. nlev),
+ * level j + 1 the aggregation of level j by its agg / aptr / amem (as above, with n = levels[j].n and nc = levels[j + 1].n),
+ *     z = scale * V(0, r),   V(j, r) = steps 1 - 6 with the transfers above,   V(nlev - 1, r) = dinv r  (any n >= 1 there),
+ * bit for bit what hipk_cheb_apply, hipk_spmv_ex (mode 4), hipk_mg_restrict_agg, hipk_mg_prolong_add_agg, hipk_mg_correct and
+ * hipk_mg_diag give on the same levels, launch by launch.  The last level's agg / aptr / amem and coefficients are not read.
+ * Envelope: n <= 4096 and max_row <= 32 on every level and nlev <= 32, else HIPK_ERR_UNSUPPORTED; nlev >= 1, 1 <= degree <= 32,
+ * 1 <= levels[j + 1].n <= levels[j].n, no null pointer, else HIPK_ERR_ARG.  Alignment, workspace (hipk_mg_gtail_work_bytes: pure
+ * host code, 0 for bad arguments), the error contract -- an erroring call launches and writes nothing -- and the workspace
+ * contract -- every byte of `work` the kernel reads it has written before -- are hipk_mg_tail_apply's. */
+typedef struct {
+    const int32_t *crow, *col;         /* device: n + 1 row pointers, the columns                         */
+    const void *val, *dinv;            /* device, `dtype`: the values, the n reciprocal diagonal entries  */
+    const int32_t *agg, *aptr, *amem;  /* device: the link to the next level (not read on the last level) */
+    int32_t n, max_row;
+    double c0, c1[32], c2[32];         /* the smoother's coefficients, c1[k - 1], c2[k - 1] for step k      */
+} hipk_mg_glevel;
+size_t hipk_mg_gtail_work_bytes(const hipk_mg_glevel *levels_host, int nlev, int dtype);
+int hipk_mg_gtail_apply(const hipk_mg_glevel *levels_host, const void *levels_dev, int nlev, int degree, double omega, double scale,
+                        const void *r, void *z, int dtype, void *work, size_t work_bytes, hipk_stream_t stream);
+
 /* ---- step API: externally driven loops (row-partitioned multi-GPU CG) ------------
  * The reference is single-device; the row-partitioned solver (north_star) drives the
  * SAME fused kernels from the host side of each rank and exchanges (a) the x-vector

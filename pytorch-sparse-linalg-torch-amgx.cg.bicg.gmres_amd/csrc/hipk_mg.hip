@@ -15,10 +15,9 @@
 // One rounding per operation, no fma (the file is built with -ffp-contract=off).
 #include "hipk_blas1.h"
 #include "hipk_common.h"
+#include "hipk_mg_tail.h"
 
-// the tail kernel's envelope, that of the batch kernels (HIPK_BATCH_MAX_N / HIPK_BATCH_MAX_ROW in hipk_batch.h)
-#define HIPK_MG_TAIL_MAX_N 4096
-#define HIPK_MG_TAIL_MAX_ROW 32
+// the tail kernel's envelope: HIPK_MG_TAIL_MAX_N / HIPK_MG_TAIL_MAX_ROW of hipk_mg_tail.h, and
 #define HIPK_MG_TAIL_MAX_LEVELS 16
 
 struct hipk_mg_dims {
@@ -200,87 +199,9 @@ extern "C" int hipk_mg_diag(int64_t n, double scale, const void *dinv, const voi
 
 // ------------------------------------------------------------------------------------------------------------- the tail kernel
 // One launch, ONE 256-thread workgroup: V(l, .) for the run of small levels j = 0 .. nlev - 1 of the descriptor array (level
-// nlev - 1 has one unknown), down and back up -- what the launch sequence spends 2 degree + 7 launches per level on.  The rules of
-// the batch kernels (hipk_batch.h) hold: no other workgroup exists; every barrier stands outside the loops over rows and is
-// reached by all threads; a gather (the SpMV's x, the restriction's t, the prolongation's e) reads a vector that is complete in
-// LDS behind a barrier; a row is summed in stored order, s = 0, s = s + a_ij x_j, which for rows of at most 32 entries is the
-// summation order of every SpMV kernel -- so the result is bit for bit the launch sequence's.
-//   LDS : xs[4096] of T, the gather vector (32 KiB fp64, 16 KiB fp32, static).
-//   slab: per level five vectors of (n + 3) & ~3 elements -- r | z | t | d | w -- in `work`, levels back to back; level 0 reads the
-//         caller's r and writes the caller's z instead of its first two.  r and z of a level wait there for the coarse correction;
-//         t is the residual, d the post-smoother's output, w the Chebyshev recurrence's own vector.
-// Thread t owns rows t, t + 256, ...: every element-wise step touches own rows only, and every slab element a thread reads
-// outside a staging copy is one it wrote itself.  Every slab element is written before it is read: `work` need not be initialised.
-template <typename T>
-struct hipk_mg_vecs {
-    T *r, *z, *t, *d, *w;
-};
-
-template <typename T>
-__device__ __forceinline__ hipk_mg_vecs<T> hipk_mg_level_vecs(const hipk_mg_level *lv, int j, const T *rin, T *zout, T *slab) {
-    int64_t off = 0;
-    for (int i = 0; i < j; ++i) off += 5 * (int64_t)((lv[i].n + 3) & ~3);
-    const int nvp = (lv[j].n + 3) & ~3;
-    T *b = slab + off;
-    hipk_mg_vecs<T> v;
-    v.r = j ? b : const_cast<T *>(rin);   // level 0's r is the caller's: read only
-    v.z = j ? b + nvp : zout;
-    v.t = b + 2 * nvp;
-    v.d = b + 3 * nvp;
-    v.w = b + 4 * nvp;
-    return v;
-}
-
-template <typename T>
-__device__ __forceinline__ T hipk_mg_rowsum(const hipk_mg_level &L, const T *xs, int row) {
-    const T *__restrict__ val = (const T *)L.val;
-    const int lo = L.crow[row], hi = L.crow[row + 1];
-    T s = (T)0;
-    for (int j = lo; j < hi; ++j) {
-        const T p = val[j] * xs[L.col[j]];
-        s = s + p;
-    }
-    return s;
-}
-
-// xs = v (own rows), complete behind the barrier
-template <typename T>
-__device__ __forceinline__ void hipk_mg_stage(int n, const T *v, T *xs) {
-    for (int row = threadIdx.x; row < n; row += HIPK_THREADS) xs[row] = v[row];
-    __syncthreads();
-}
-
-// out = b - A x
-template <typename T>
-__device__ __forceinline__ void hipk_mg_residual(const hipk_mg_level &L, const T *x, const T *b, T *out, T *xs) {
-    hipk_mg_stage(L.n, x, xs);
-    for (int row = threadIdx.x; row < L.n; row += HIPK_THREADS) out[row] = b[row] - hipk_mg_rowsum(L, xs, row);
-    __syncthreads();
-}
-
-// z = S(r): the Chebyshev recurrence of hipk_cheb_apply with scale 1; w is its vector d
-template <typename T>
-__device__ __forceinline__ void hipk_mg_smooth(const hipk_mg_level &L, int m, const T *r, T *z, T *w, T *xs) {
-    const T *__restrict__ dinv = (const T *)L.dinv;
-    const T c0 = (T)L.c0;
-    for (int row = threadIdx.x; row < L.n; row += HIPK_THREADS) {
-        const T d = c0 * (dinv[row] * r[row]);
-        w[row] = d;
-        z[row] = d;
-    }
-    for (int k = 0; k < m; ++k) {
-        const T c1 = (T)L.c1[k], c2 = (T)L.c2[k];
-        hipk_mg_stage(L.n, z, xs);
-        for (int row = threadIdx.x; row < L.n; row += HIPK_THREADS) {
-            const T res = dinv[row] * (r[row] - hipk_mg_rowsum(L, xs, row));
-            const T d = (c1 * w[row]) + (c2 * res);
-            w[row] = d;
-            z[row] = z[row] + d;
-        }
-        __syncthreads();
-    }
-}
-
+// nlev - 1 has one unknown), down and back up -- what the launch sequence spends 2 degree + 7 launches per level on.  The steps
+// (staging, residual, Chebyshev recurrence), the slab layout and the rules they keep are hipk_mg_tail.h's, shared with the tail
+// kernel of the index-array levels (hipk_mg_graph.hip); the result is bit for bit the launch sequence's.
 template <typename T>
 __global__ __launch_bounds__(HIPK_THREADS) void hipk_mg_tail_kernel(const hipk_mg_level *__restrict__ lv, int nlev, int m, T omega, T scale,
                                                                     const T *rin, T *zout, T *slab) {
@@ -364,9 +285,7 @@ static int hipk_mg_tail_check(const hipk_mg_level *lv, int nlev, int degree, int
 
 extern "C" size_t hipk_mg_tail_work_bytes(const hipk_mg_level *levels_host, int nlev, int dtype) {
     if (!levels_host || nlev < 1 || nlev > HIPK_MG_TAIL_MAX_LEVELS) return 0;
-    size_t el = 0;
-    for (int j = 0; j < nlev; ++j) el += 5 * (size_t)(((int64_t)levels_host[j].n + 3) & ~(int64_t)3);
-    return (el * (dtype == HIPK_F64 ? 8 : 4) + 255) & ~(size_t)255;
+    return hipk_mg_slab_bytes(levels_host, nlev, dtype);
 }
 
 extern "C" int hipk_mg_tail_apply(const hipk_mg_level *levels_host, const void *levels_dev, int nlev, int degree, double omega,

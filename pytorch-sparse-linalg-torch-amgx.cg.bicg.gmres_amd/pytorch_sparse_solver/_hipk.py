@@ -66,6 +66,8 @@ SYMBOLS = [
     "hipk_mg_restrict", "hipk_mg_prolong_add", "hipk_mg_correct", "hipk_mg_diag",
     # ... and the V-cycle's small levels in one launch
     "hipk_mg_tail_work_bytes", "hipk_mg_tail_apply",
+    # aggregation multigrid on a matrix graph: the transfers by index arrays, and their tail kernel
+    "hipk_mg_restrict_agg", "hipk_mg_prolong_add_agg", "hipk_mg_gtail_work_bytes", "hipk_mg_gtail_apply",
 ]
 
 
@@ -156,6 +158,14 @@ class MgLevel(ctypes.Structure):
     _fields_ = [("crow", ctypes.c_void_p), ("col", ctypes.c_void_p), ("val", ctypes.c_void_p), ("dinv", ctypes.c_void_p),
                 ("n0", ctypes.c_int32), ("n1", ctypes.c_int32), ("n2", ctypes.c_int32), ("n", ctypes.c_int32),
                 ("max_row", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("c0", ctypes.c_double), ("c1", ctypes.c_double * 32), ("c2", ctypes.c_double * 32)]
+
+
+class MgGLevel(ctypes.Structure):
+    """hipk_mg_glevel: one level of hipk_mg_gtail_apply."""
+    _fields_ = [("crow", ctypes.c_void_p), ("col", ctypes.c_void_p), ("val", ctypes.c_void_p), ("dinv", ctypes.c_void_p),
+                ("agg", ctypes.c_void_p), ("aptr", ctypes.c_void_p), ("amem", ctypes.c_void_p),
+                ("n", ctypes.c_int32), ("max_row", ctypes.c_int32),
                 ("c0", ctypes.c_double), ("c1", ctypes.c_double * 32), ("c2", ctypes.c_double * 32)]
 
 
@@ -315,6 +325,11 @@ def lib():
     L.hipk_mg_tail_work_bytes.argtypes = [ctypes.POINTER(MgLevel), i32, i32]
     L.hipk_mg_tail_work_bytes.restype = ctypes.c_size_t
     L.hipk_mg_tail_apply.argtypes = [ctypes.POINTER(MgLevel), vp, i32, i32, dbl, dbl, vp, vp, i32, vp, ctypes.c_size_t, vp]
+    L.hipk_mg_restrict_agg.argtypes = [i64, i64, vp, vp, vp, vp, i32, vp]
+    L.hipk_mg_prolong_add_agg.argtypes = [i64, i64, vp, dbl, vp, vp, i32, vp]
+    L.hipk_mg_gtail_work_bytes.argtypes = [ctypes.POINTER(MgGLevel), i32, i32]
+    L.hipk_mg_gtail_work_bytes.restype = ctypes.c_size_t
+    L.hipk_mg_gtail_apply.argtypes = [ctypes.POINTER(MgGLevel), vp, i32, i32, dbl, dbl, vp, vp, i32, vp, ctypes.c_size_t, vp]
     _lib = L
     return L
 
@@ -780,6 +795,86 @@ def mg_tail_apply(tail: MgTail, omega: float, scale: float, r: torch.Tensor, z: 
         _check(lib().hipk_mg_tail_apply(tail.host, tail.blob.data_ptr(), tail.nlev, tail.degree, float(omega), float(scale),
                                         r.data_ptr(), z.data_ptr(), _dtype_code(tail.dtype), work.data_ptr(), tail.work_bytes,
                                         _stream(tail.device)), "hipk_mg_tail_apply")
+    return z
+
+
+def _check_index(name: str, a: torch.Tensor, numel: int, like: torch.Tensor) -> None:
+    """An int32 index array of the multigrid transfers: dtype, length, device and alignment (its contents are the caller's)."""
+    assert a.is_cuda and a.is_contiguous() and a.dtype == torch.int32 and a.device == like.device, f"{name}: a contiguous int32 device tensor"
+    assert a.numel() == numel, f"{name}: {a.numel()} entries, {numel} expected"
+    assert a.data_ptr() % 16 == 0, f"{name} must be 16-byte aligned"
+
+
+def mg_restrict_agg(aptr: torch.Tensor, amem: torch.Tensor, t: torch.Tensor, rc: torch.Tensor) -> torch.Tensor:
+    """rc[I] = the sum of t over amem[aptr[I] : aptr[I + 1]], left to right from the first member (hipk_mg_restrict_agg)."""
+    assert t.is_cuda and t.is_contiguous() and rc.is_contiguous() and rc.dtype == t.dtype and rc.device == t.device
+    assert t.data_ptr() % 16 == 0 and rc.data_ptr() % 16 == 0
+    _check_index("aptr", aptr, rc.numel() + 1, t)
+    _check_index("amem", amem, t.numel(), t)
+    with torch.cuda.device(t.device):
+        _check(lib().hipk_mg_restrict_agg(t.numel(), rc.numel(), aptr.data_ptr(), amem.data_ptr(), t.data_ptr(), rc.data_ptr(),
+                                          _dtype_code(t.dtype), _stream(t.device)), "hipk_mg_restrict_agg")
+    return rc
+
+
+def mg_prolong_add_agg(agg: torch.Tensor, omega: float, e: torch.Tensor, z: torch.Tensor) -> torch.Tensor:
+    """z[i] += omega * e[agg[i]] in place (hipk_mg_prolong_add_agg)."""
+    assert z.is_cuda and z.is_contiguous() and e.is_contiguous() and e.dtype == z.dtype and e.device == z.device
+    assert z.data_ptr() % 16 == 0 and e.data_ptr() % 16 == 0
+    _check_index("agg", agg, z.numel(), z)
+    with torch.cuda.device(z.device):
+        _check(lib().hipk_mg_prolong_add_agg(z.numel(), e.numel(), agg.data_ptr(), float(omega), e.data_ptr(), z.data_ptr(),
+                                             _dtype_code(z.dtype), _stream(z.device)), "hipk_mg_prolong_add_agg")
+    return z
+
+
+MG_GTAIL_MAX_LEVELS = 32  # the envelope of hipk_mg_gtail_apply beyond MG_TAIL_MAX_N / MG_TAIL_MAX_ROW: levels
+
+
+class MgGTail:
+    """`MgTail` for hipk_mg_gtail_apply: per level a dict with int32 `crow` / `col`, `val`, `dinv`, `max_row`, the smoother's `c0`,
+    `c1`, `c2` and the int32 index arrays `agg`, `aptr`, `amem` to the next level (all four absent or None on the last level)."""
+
+    def __init__(self, levels, degree: int):
+        self.nlev, self.degree = len(levels), int(degree)
+        self.dtype, self.device = levels[0]["val"].dtype, levels[0]["val"].device
+        self.host = (MgGLevel * self.nlev)()
+        self._keep = []
+        for j, (d, lev) in enumerate(zip(self.host, levels)):
+            d.n = int(lev["dinv"].numel())
+            for name in ("crow", "col", "val", "dinv"):
+                t = lev[name]
+                assert t.is_cuda and t.is_contiguous() and t.device == self.device
+                assert t.dtype == (torch.int32 if name in ("crow", "col") else self.dtype)
+                self._keep.append(t)
+                setattr(d, name, t.data_ptr())
+            assert lev["crow"].numel() == d.n + 1 and lev["col"].numel() == lev["val"].numel()
+            d.max_row = int(lev["max_row"])
+            if j + 1 < self.nlev:
+                nc = int(levels[j + 1]["dinv"].numel())
+                for name, numel in (("agg", d.n), ("aptr", nc + 1), ("amem", d.n)):
+                    _check_index(name, lev[name], numel, lev["val"])
+                    self._keep.append(lev[name])
+                    setattr(d, name, lev[name].data_ptr())
+                d.c0 = float(lev["c0"])
+                for k in range(self.degree):
+                    d.c1[k], d.c2[k] = float(lev["c1"][k]), float(lev["c2"][k])
+        raw = torch.frombuffer(bytearray(bytes(self.host)), dtype=torch.uint8)
+        self.blob = raw.to(self.device)
+        self.work_bytes = int(lib().hipk_mg_gtail_work_bytes(self.host, self.nlev, _dtype_code(self.dtype)))
+
+
+def mg_gtail_apply(tail: MgGTail, omega: float, scale: float, r: torch.Tensor, z: torch.Tensor,
+                   work: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """z = scale * V(0, r) over the tail's index-array levels in one launch (hipk_mg_gtail_apply), on the current stream."""
+    n = int(tail.host[0].n)
+    for v in (r, z):
+        assert v.is_cuda and v.is_contiguous() and v.dtype == tail.dtype and v.device == tail.device and v.numel() == n
+    work = _workspace(work, tail.device, tail.work_bytes)
+    with torch.cuda.device(tail.device):
+        _check(lib().hipk_mg_gtail_apply(tail.host, tail.blob.data_ptr(), tail.nlev, tail.degree, float(omega), float(scale),
+                                         r.data_ptr(), z.data_ptr(), _dtype_code(tail.dtype), work.data_ptr(), tail.work_bytes,
+                                         _stream(tail.device)), "hipk_mg_gtail_apply")
     return z
 
 

@@ -5,7 +5,7 @@ on hand-written gfx950 kernels (libhipk.so), everything else on the generic torc
 `get_last_stats()` (iteration counts the reference never returns), `JacobiPreconditioner` (a callable for the
 reference's `M` hook that the fast path runs device-resident), `ChebyshevPreconditioner` (a polynomial in D^-1 A whose steps
 run in the SpMV kernels' epilogue), `AggregationMultigridPreconditioner` (a V-cycle of aggregation multigrid for a matrix on a
-structured grid), `cg_multi` / `bicgstab_multi` (k right-hand sides per matrix read) and `cg_batch` /
+structured grid or, `from_graph`, for any matrix, with `pairwise_aggregates` from the matrix graph), `cg_multi` / `bicgstab_multi` (k right-hand sides per matrix read) and `cg_batch` /
 `bicgstab_batch` / `gmres_batch` (many small systems with one sparsity pattern, one workgroup per system; point- or block-Jacobi
 preconditioned) are the additions.
 """
@@ -18,7 +18,7 @@ from .multi_rhs import cg_multi, bicgstab_multi
 from .batch import BatchedCSR, BatchedJacobiPreconditioner, BatchedBlockJacobiPreconditioner, cg_batch, bicgstab_batch, gmres_batch
 from .torch_tree_util import tree_leaves, tree_map, tree_flatten, tree_unflatten, Partial
 from .preconditioners import BlockJacobiPreconditioner, ChebyshevPreconditioner, JacobiPreconditioner
-from .multigrid import AggregationMultigridPreconditioner
+from .multigrid import AggregationMultigridPreconditioner, pairwise_aggregates
 
 __all__ = [
     'cg', 'bicgstab', 'gmres', 'cg_multi', 'bicgstab_multi',
@@ -27,7 +27,7 @@ __all__ = [
     'LinearSolveFunction',
     'tree_leaves', 'tree_map', 'tree_flatten', 'tree_unflatten', 'Partial',
     'get_last_stats', 'JacobiPreconditioner', 'BlockJacobiPreconditioner', 'ChebyshevPreconditioner',
-    'AggregationMultigridPreconditioner',
+    'AggregationMultigridPreconditioner', 'pairwise_aggregates',
 ]
 
 __version__ = '1.0.0'

@@ -5,6 +5,9 @@ are the aggregates, the coarse matrices are the Galerkin products with the piece
 level is the Chebyshev polynomial of `ChebyshevPreconditioner`, and the coarse correction is over-weighted by `omega`.  Its
 iteration count grows only slowly with the grid, where the polynomial and Jacobi preconditioners follow sqrt(cond(A)).
 
+`AggregationMultigridPreconditioner.from_graph(A)` is the same object for a matrix without a known grid: the aggregates are
+`pairwise_aggregates` of the matrix graph (pairwise matching on strong couplings), everything else is unchanged.
+
 Like `ChebyshevPreconditioner` the apply consists of SpMVs and element-wise steps only -- no dot product, no atomics -- so it is
 deterministic, independent of launch shapes and bitwise equal to a CPU mirror of the steps (tests/_mg_mirror.py).
 """
@@ -14,7 +17,7 @@ import torch
 
 from .preconditioners import ChebyshevPreconditioner, _diagonal
 
-__all__ = ["AggregationMultigridPreconditioner", "MG_TAIL_MAX_ROWS"]
+__all__ = ["AggregationMultigridPreconditioner", "MG_TAIL_MAX_ROWS", "MG_GRAPH_MAX_LEVELS", "pairwise_aggregates"]
 
 # The default of `tail_rows`: levels of at most this many unknowns run inside the one-launch tail kernel (0: none do).
 # Measured (tools/mg_probe.py, profiles/mg_probe.txt, MI355X, fp64, 5-point Poisson 2000 x 2000, degree 1, device time per apply):
@@ -22,7 +25,14 @@ __all__ = ["AggregationMultigridPreconditioner", "MG_TAIL_MAX_ROWS"]
 # levels of up to 1024 rows faster than their launches do, but not the 3969-row one: 1024 had the least time, as it had in the two
 # earlier runs of the probe (656.1 and 774.8 us, before the transfer kernels took the chunk form).  Variable diffusion 2000 x 2000
 # and 7-point 128^3 agree; at 1000 x 1000 4096 is ahead (364.4 against 398.9 us), at 4000 x 4000 256 and 1024 tie.
+# Graph hierarchies (`from_graph`) take the same default: their sweep at 2000 x 2000 decides nothing (profiles/mg_graph_probe.txt: a
+# small level has a row of 38 entries, so no tail runs at any value, 2852 - 2889 us); at 1000 x 1000 256 / 1024 / 4096 gave 807.0 /
+# 802.2 / 860.3 us, on an anisotropic 2000 x 2000 operator 960.1 / 995.7 / 1063.2 us.
 MG_TAIL_MAX_ROWS = 1024
+
+# `from_graph`: a hierarchy of more levels than this is refused as a stalled coarsening (pairwise matching shrinks a level by a
+# factor of about 3.2 with two passes: 48 levels are far beyond any matrix that fits a device)
+MG_GRAPH_MAX_LEVELS = 48
 
 
 def _grid3(dims):
@@ -57,7 +67,18 @@ def _galerkin(crow: torch.Tensor, col: torch.Tensor, val: torch.Tensor, dims):
     sorted by column, stored zeros kept.  Torch ops without repeated scatter targets: the same bits on CPU and device, run to run."""
     crow, col = crow.to(torch.int64), col.to(torch.int64)
     nc = math.prod(_coarse_dims(dims))
-    key = _aggregate_of(_rows_of(crow), dims) * nc + _aggregate_of(col, dims)
+    return _galerkin_keys(_aggregate_of(_rows_of(crow), dims) * nc + _aggregate_of(col, dims), val, nc)
+
+
+def _galerkin_agg(crow: torch.Tensor, col: torch.Tensor, val: torch.Tensor, agg: torch.Tensor, nc: int):
+    """`_galerkin` for aggregates given as an index array: `agg` (int64, one entry per row) maps a row to its aggregate in
+    [0, nc).  The same rule and the same bits: entry (I, J) is s = first, s = s + next over A's storage order."""
+    crow, col = crow.to(torch.int64), col.to(torch.int64)
+    return _galerkin_keys(agg[_rows_of(crow)] * nc + agg[col], val, int(nc))
+
+
+def _galerkin_keys(key: torch.Tensor, val: torch.Tensor, nc: int):
+    """The sum of `_galerkin` over the stored entries keyed I * nc + J."""
     skey, order = torch.sort(key, stable=True)              # stable: a segment keeps A's storage order
     v = val[order]
     ukey, counts = torch.unique_consecutive(skey, return_counts=True)
@@ -90,12 +111,112 @@ def _abs_row_sums(crow: torch.Tensor, val: torch.Tensor) -> torch.Tensor:
     return s
 
 
+def _edge_hash(u: torch.Tensor, v: torch.Tensor) -> torch.Tensor:
+    """h(u, v) of `pairwise_aggregates`: non-negative int64 throughout, no product overflows for u, v < 2^31."""
+    k = (u * 73856093 + v * 19349663) & 0x7FFFFFFF
+    k = ((k ^ (k >> 15)) * 0x2C1B3C6D) & 0x7FFFFFFF
+    k = ((k ^ (k >> 12)) * 0x297A2D39) & 0x7FFFFFFF
+    return k ^ (k >> 15)
+
+
+def _matching_pass(crow: torch.Tensor, col: torch.Tensor, val: torch.Tensor, theta: float):
+    """One pass of `pairwise_aggregates` on the coalesced matrix (crow, col, val) -- unique (row, col), rows sorted --: (the aggregate
+    of every vertex, the number of aggregates, the handshake rounds)."""
+    n = crow.numel() - 1
+    dev = val.device
+    ids = torch.arange(n, device=dev)
+    rows = _rows_of(crow)
+    off = rows != col
+    u, v = torch.minimum(rows[off], col[off]), torch.maximum(rows[off], col[off])
+    key, order = torch.sort(u * n + v, stable=True)           # an undirected edge is stored once or twice
+    a = val[off].abs().to(torch.float64)[order]
+    key, counts = torch.unique_consecutive(key, return_counts=True)
+    start = torch.cumsum(counts, 0) - counts
+    w = a[start]
+    two = counts > 1
+    w = torch.where(two, torch.maximum(w, a[torch.where(two, start + 1, start)]), w)
+    u, v = torch.div(key, n, rounding_mode="floor"), key % n
+    m = torch.zeros(n, dtype=torch.float64, device=dev)       # the largest incident weight: a maximum, independent of order
+    m.scatter_reduce_(0, u, w, "amax").scatter_reduce_(0, v, w, "amax")
+    strong = (w > 0) & (w >= theta * torch.minimum(m[u], m[v]))
+    u, v, key = u[strong], v[strong], key[strong]
+    by_hash = torch.sort(_edge_hash(u, v), stable=True)[1]    # `key` ascends: ties of the hash go to the smaller u n + v
+    rank = torch.empty_like(by_hash)
+    rank[by_hash] = torch.arange(by_hash.numel(), device=dev)
+    partner = ids.clone()
+    free = torch.ones(n, dtype=torch.bool, device=dev)
+    rounds = 0
+    while True:
+        live = free[u] & free[v]
+        if not bool(live.any()):
+            break
+        u, v, rank = u[live], v[live], rank[live]
+        best = torch.full((n,), torch.iinfo(torch.int64).max, dtype=torch.int64, device=dev)
+        best.scatter_reduce_(0, u, rank, "amin").scatter_reduce_(0, v, rank, "amin")
+        hit = (best[u] == rank) & (best[v] == rank)           # the smallest live rank at both ends: no two hits share a vertex
+        mu, mv = u[hit], v[hit]
+        partner[mu], partner[mv] = mv, mu
+        free[mu] = False
+        free[mv] = False
+        rounds += 1
+    first = torch.minimum(ids, partner)                       # the smallest member names the aggregate
+    number = torch.cumsum((first == ids).to(torch.int64), 0) - 1
+    return number[first], int(number[-1]) + 1, rounds
+
+
+def pairwise_aggregates(A_csr: torch.Tensor, passes: int = 2, theta: float = 0.25):
+    """(agg, nc): aggregates of the matrix graph of the CSR tensor `A_csr` by `passes` (1 .. 4) passes of pairwise matching on
+    strong couplings.  `agg` (int64, n entries) maps a row to its aggregate in [0, nc); aggregates have 1 .. 2^passes members and
+    are numbered in ascending order of their smallest member.  Torch ops whose results do not depend on the order of execution:
+    the same `agg` on CPU and device.
+
+    A pass, on a matrix with n vertices:
+      coalesce   entries stored with the same (row, col) are summed in stored order (`_galerkin_agg` with identity aggregates);
+      edges      e = (u, v), u < v, of weight w_e = max(|a_uv|, |a_vu|) in fp64, a direction that is not stored counting as 0;
+                 m_u = the largest weight at u;
+      strong     w_e > 0 and w_e >= theta * min(m_u, m_v) (the product one fp64 rounding);
+      rank       strong edges by the hash h(u, v) (`_edge_hash`), the smaller first, ties to the smaller u n + v.  The weight
+                 does not enter: a rank monotone in a smooth coefficient makes the handshake take O(n) rounds, a random one O(log n);
+      matching   the greedy matching in rank order, by handshake rounds: an edge is live while both ends are free, every free
+                 vertex takes the smallest rank among its live edges, an edge that is the smallest at both ends is matched;
+      result     a matched pair or an unmatched vertex.
+    Pass p + 1 runs on the Galerkin matrix of A with the composite aggregates of passes 1 .. p (one `_galerkin_agg` sum from A,
+    used for the weights only) and pairs those aggregates; it is skipped once a pass has formed no pair.  nc == n exactly when the
+    coalesced matrix has no non-zero off-diagonal entry."""
+    if not (isinstance(A_csr, torch.Tensor) and A_csr.layout == torch.sparse_csr and A_csr.ndim == 2 and A_csr.shape[0] == A_csr.shape[1]):
+        raise ValueError("pairwise_aggregates needs a square CSR tensor")
+    if isinstance(passes, bool) or int(passes) != passes or not 1 <= int(passes) <= 4:
+        raise ValueError(f"passes must be 1, 2, 3 or 4, got {passes}")
+    theta = float(theta)
+    if not 0.0 <= theta <= 1.0:
+        raise ValueError(f"theta must be in [0, 1], got {theta}")
+    return _pairwise_aggregates(A_csr, int(passes), theta)[:2]
+
+
+def _pairwise_aggregates(A_csr, passes: int, theta: float):
+    """(agg, nc, the handshake rounds of every pass run)."""
+    crow, col, val = A_csr.crow_indices().to(torch.int64), A_csr.col_indices().to(torch.int64), A_csr.values()
+    n = int(A_csr.shape[0])
+    if n >= 2 ** 31:
+        raise ValueError("pairwise_aggregates takes fewer than 2^31 rows")
+    agg, nc, rounds = torch.arange(n, device=val.device), n, []
+    for _ in range(passes):
+        step, nc_next, r = _matching_pass(*_galerkin_agg(crow, col, val, agg, nc), theta)
+        rounds.append(r)
+        if nc_next == nc:
+            break
+        agg, nc = step[agg], nc_next
+    return agg, nc, rounds
+
+
 class _Level:
-    """One level: `csr` (the matrix, a CSR tensor), `dims`, `n`, `dinv` (the reciprocal diagonal) and, except on the level with
-    one unknown, the smoother's coefficients `c0`, `c1`, `c2` (`ChebyshevPreconditioner`'s, `smoother` is that object)."""
+    """One level: `csr` (the matrix, a CSR tensor), `dims`, `n`, `dinv` (the reciprocal diagonal) and, except on the last level,
+    the smoother's coefficients `c0`, `c1`, `c2` (`ChebyshevPreconditioner`'s, `smoother` is that object).  `agg`: on a level of a
+    graph hierarchy that has a next one, the int64 map from its rows to the next level's; None otherwise."""
 
     def __init__(self, csr, dims):
         self.csr, self.dims, self.n = csr, tuple(dims), int(csr.shape[0])
+        self.agg = None
         crow = csr.crow_indices()
         self.max_row = int((crow[1:] - crow[:-1]).max())
         self.smoother = None
@@ -144,18 +265,16 @@ class AggregationMultigridPreconditioner:
     (the handle cache holds eight entries, a deep hierarchy would flush it) and all work vectors.  CPU vectors run torch ops in
     exactly the order above, with `_SpecSpmv` for the row sums.
 
-    Attributes: `levels` (per level `csr`, `dims`, `n`, `dinv`, `c0`, `c1`, `c2`), `scale`, `applies`, `tail_rows`, `tail_from`,
+    `from_graph(A, ...)` builds the same object without a grid, from aggregates of the matrix graph (see there).
+
+    Attributes: `levels` (per level `csr`, `dims`, `n`, `dinv`, `c0`, `c1`, `c2`, `agg`), `graph` (True for `from_graph`),
+    `handshake_rounds` (graph: per level the rounds of each matching pass), `scale`, `applies`, `tail_rows`, `tail_from`,
     `launches_per_apply` (the launches of one device apply, a Chebyshev step counted as the one launch it is where the SpMV has
     the Chebyshev epilogue: 2 degree + 7 per level above the tail -- above L without one --, then one)."""
 
     def __init__(self, A: torch.Tensor, grid, degree: int = 1, ratio: float = 4.0, omega: float = 1.8, normalize: bool = True,
                  tail_rows=None):
-        if getattr(A, "_hipk_row_block", False) is True:
-            raise ValueError("AggregationMultigridPreconditioner is not available on a RowBlockCSR")
-        if not (isinstance(A, torch.Tensor) and A.ndim == 2 and A.shape[0] == A.shape[1]):
-            raise ValueError("AggregationMultigridPreconditioner needs a square matrix tensor")
-        if A.dtype not in (torch.float64, torch.float32):
-            raise ValueError(f"AggregationMultigridPreconditioner needs a float64 or float32 matrix, not {A.dtype}")
+        self._check_matrix(A)
         try:
             dims = tuple(int(v) for v in grid)
         except TypeError:
@@ -164,6 +283,42 @@ class AggregationMultigridPreconditioner:
             raise ValueError(f"grid must have 2 or 3 dimensions, got {len(dims)}")
         if min(dims) < 1 or math.prod(dims) != A.shape[0]:
             raise ValueError(f"grid {dims} does not have the matrix's {A.shape[0]} points")
+        self._set_up(A, dims, degree, ratio, omega, normalize, tail_rows, None)
+
+    @classmethod
+    def from_graph(cls, A: torch.Tensor, degree: int = 1, ratio: float = 4.0, omega: float = 1.8, normalize: bool = True,
+                   tail_rows=None, passes: int = 2, theta: float = 0.25):
+        """The same preconditioner for ANY square `A`: the aggregates come from the matrix graph, not from a grid.
+
+        Level l's aggregates are `pairwise_aggregates(A_l, passes, theta)` (pairwise matching on strong couplings, aggregates of
+        1 .. 2^passes rows; `passes` 1 .. 4, `theta` in [0, 1]), A_{l+1} is the one-step Galerkin sum from A_l with them under the
+        rule above, and steps 3 and 5 read index arrays: the members of an aggregate in ascending fine index, and agg(i).
+        Coarsening ends at the first level whose graph has no pair left, which is the level without a non-zero off-diagonal entry
+        -- one unknown for a connected graph, one per component otherwise --; that level is z = dinv r.  More than
+        `MG_GRAPH_MAX_LEVELS` (48) levels is a ValueError: the coarsening has stalled (a star graph loses one pair per pass).
+        Smoother, V-cycle, `normalize`, `tail_rows`, `applies` and `launches_per_apply` are the grid object's; every level has
+        `dims == (n,)` and, except the last, `agg` (int64, the map to the next level).  The device transfers are
+        `hipk_mg_restrict_agg` / `hipk_mg_prolong_add_agg`, the tail `hipk_mg_gtail_apply` (at most 32 levels, else launches)."""
+        self = cls.__new__(cls)
+        cls._check_matrix(A)
+        if isinstance(passes, bool) or int(passes) != passes or not 1 <= int(passes) <= 4:
+            raise ValueError(f"passes must be 1, 2, 3 or 4, got {passes}")
+        if not 0.0 <= float(theta) <= 1.0:
+            raise ValueError(f"theta must be in [0, 1], got {theta}")
+        self._set_up(A, (int(A.shape[0]),), degree, ratio, omega, normalize, tail_rows, (int(passes), float(theta)))
+        return self
+
+    @staticmethod
+    def _check_matrix(A) -> None:
+        if getattr(A, "_hipk_row_block", False) is True:
+            raise ValueError("AggregationMultigridPreconditioner is not available on a RowBlockCSR")
+        if not (isinstance(A, torch.Tensor) and A.ndim == 2 and A.shape[0] == A.shape[1]):
+            raise ValueError("AggregationMultigridPreconditioner needs a square matrix tensor")
+        if A.dtype not in (torch.float64, torch.float32):
+            raise ValueError(f"AggregationMultigridPreconditioner needs a float64 or float32 matrix, not {A.dtype}")
+
+    def _set_up(self, A, dims, degree, ratio, omega, normalize, tail_rows, graph) -> None:
+        """Everything after the argument checks of the two constructors.  `graph`: None on a grid, else (passes, theta)."""
         if not 1 <= int(degree) <= 32:
             raise ValueError("degree must be in [1, 32]")
         if not float(omega) > 0.0:
@@ -175,15 +330,32 @@ class AggregationMultigridPreconditioner:
         csr = self._A if A.layout == torch.sparse_csr else \
             (self._A.coalesce() if A.layout == torch.sparse_coo else self._A).to_sparse_csr()
         self.levels = []
+        self.graph = graph is not None
+        self.handshake_rounds = [] if self.graph else None      # per level with a next one: the rounds of each matching pass
         while True:
             lev = _Level(csr, dims)
-            self._set_up_smoother(lev, len(self.levels))
+            if self.graph:
+                agg, n, rounds = _pairwise_aggregates(csr, *graph)
+                last = n == lev.n
+            else:
+                last = lev.n == 1
+            self._set_up_smoother(lev, len(self.levels), last)
             self.levels.append(lev)
-            if lev.n == 1:
+            if last:
                 break
-            crow, col, val = _galerkin(csr.crow_indices(), csr.col_indices(), csr.values(), dims)
-            dims = _coarse_dims(dims)
-            n = math.prod(dims)
+            if self.graph:
+                if len(self.levels) == MG_GRAPH_MAX_LEVELS:
+                    raise ValueError(f"AggregationMultigridPreconditioner.from_graph: the coarsening has stalled, level "
+                                     f"{len(self.levels) - 1} still has {lev.n} unknowns and more than {MG_GRAPH_MAX_LEVELS} "
+                                     f"levels would be needed (sizes {[v.n for v in self.levels[:4]]} ...)")
+                lev.agg = agg
+                self.handshake_rounds.append(rounds)
+                crow, col, val = _galerkin_agg(csr.crow_indices(), csr.col_indices(), csr.values(), agg, n)
+                dims = (n,)
+            else:
+                crow, col, val = _galerkin(csr.crow_indices(), csr.col_indices(), csr.values(), dims)
+                dims = _coarse_dims(dims)
+                n = math.prod(dims)
             csr = torch.sparse_csr_tensor(crow, col, val, size=(n, n))
         L = len(self.levels) - 1
         # the tail: the levels from the first one of at most `tail_rows` unknowns on, when they all fit the kernel's envelope
@@ -192,7 +364,9 @@ class AggregationMultigridPreconditioner:
             raise ValueError("tail_rows must be 0 (no tail kernel) or positive")
         self.tail_rows = min(tail_rows, 4096)
         first = next((l for l, lev in enumerate(self.levels) if lev.n <= self.tail_rows), None)
-        self.tail_from = first if first is not None and all(lev.max_row <= 32 for lev in self.levels[first:]) else None
+        fits = first is not None and all(lev.max_row <= 32 for lev in self.levels[first:]) and \
+            (not self.graph or len(self.levels) - first <= 32)
+        self.tail_from = first if fits else None
         self.launches_per_apply = (L if self.tail_from is None else self.tail_from) * (2 * self.degree + 7) + 1
         self._cpu = None      # per level: (spec SpMV, the aggregate of every row, step 3's gather indices)
         self._dev = None      # per level: handle and work vectors of the device apply
@@ -211,10 +385,16 @@ class AggregationMultigridPreconditioner:
             self.scale = 1.0 / lam
             self.applies = 0
 
-    def _set_up_smoother(self, lev: _Level, l: int) -> None:
+    def _set_up_smoother(self, lev: _Level, l: int, last: bool) -> None:
         csr = lev.csr
         try:
-            if lev.n == 1:
+            if last and self.graph:          # no non-zero off-diagonal entry is left: any number of unknowns
+                d = _diagonal(csr)
+                if bool((d <= 0).any()):
+                    raise ValueError("zero or negative entry on the diagonal")
+                lev.dinv = torch.reciprocal(d)
+                return
+            if last:
                 a = csr.values().sum() if csr.values().numel() else torch.zeros((), dtype=csr.dtype)
                 if not float(a) > 0.0:
                     raise ValueError("zero or negative entry on the diagonal")
@@ -237,6 +417,14 @@ class AggregationMultigridPreconditioner:
         if self._cpu is None:
             st = []
             for lev in self.levels[:-1]:
+                if lev.agg is not None:          # index arrays: member k of every aggregate that has one, ascending fine index
+                    agg = lev.agg.cpu()
+                    amem = torch.sort(agg, stable=True)[1]
+                    counts = torch.bincount(agg)
+                    start = torch.cumsum(counts, 0) - counts
+                    members = [(counts > k, amem[torch.where(counts > k, start + k, start)]) for k in range(int(counts.max()))]
+                    st.append((agg, members))
+                    continue
                 n0, n1, n2 = _grid3(lev.dims)
                 m0, m1, m2 = _grid3(_coarse_dims(lev.dims))
                 I = torch.arange(m0 * m1 * m2)
@@ -255,7 +443,7 @@ class AggregationMultigridPreconditioner:
 
     def _v_torch(self, l: int, r: torch.Tensor) -> torch.Tensor:
         lev = self.levels[l]
-        if lev.n == 1:
+        if l == len(self.levels) - 1:
             return lev.dinv.cpu() * r
         agg, members = self._cpu_state()[l]
         S = lev.smoother._apply_torch
@@ -282,11 +470,17 @@ class AggregationMultigridPreconditioner:
                 vec = lambda: torch.empty(lev.n, dtype=dt, device=dev)
                 if l and l <= tf:
                     s["r"], s["z"] = vec(), vec()
+                if lev.agg is not None:          # the transfers' index arrays: agg, and the members aggregate by aggregate
+                    agg = lev.agg.to(dev)
+                    counts = torch.bincount(agg, minlength=self.levels[l + 1].n)
+                    s["agg"] = agg.to(torch.int32).contiguous()
+                    s["amem"] = torch.sort(agg, stable=True)[1].to(torch.int32).contiguous()
+                    s["aptr"] = torch.cat([counts.new_zeros(1), torch.cumsum(counts, 0)]).to(torch.int32).contiguous()
                 if l >= tf:          # a level of the tail kernel: int32 CSR arrays for its descriptor
                     c = lev.csr
                     s.update(crow=c.crow_indices().to(torch.int32).contiguous(), col=c.col_indices().to(torch.int32).contiguous(),
                              val=c.values().contiguous(), dims=lev.dims, max_row=lev.max_row, c0=lev.c0, c1=lev.c1, c2=lev.c2)
-                elif lev.n > 1:
+                elif l < len(self.levels) - 1:
                     c = lev.csr
                     s["h"] = _hipk.handle_for(self._A) if l == 0 else \
                         _hipk.CsrHandle(c.crow_indices(), c.col_indices(), c.values(), c.shape)
@@ -294,7 +488,7 @@ class AggregationMultigridPreconditioner:
                     s["work"] = torch.empty(2 * ((lev.n + 3) & ~3) * c.values().element_size(), dtype=torch.uint8, device=dev)
                 st.append(s)
             if tf < len(self.levels):
-                self._tail = _hipk.MgTail(st[tf:], self.degree)
+                self._tail = (_hipk.MgGTail if self.graph else _hipk.MgTail)(st[tf:], self.degree)
                 self._tail_work = torch.empty(self._tail.work_bytes, dtype=torch.uint8, device=dev)
             self._dev = st
         return self._dev
@@ -313,13 +507,20 @@ class AggregationMultigridPreconditioner:
         for l in range(L):
             smooth(l, r(l), z(l))
             _hipk.spmv_residual(st[l]["h"], z(l), r(l), st[l]["t"])
-            _hipk.mg_restrict(levels[l].dims, st[l]["t"], r(l + 1))
+            if self.graph:
+                _hipk.mg_restrict_agg(st[l]["aptr"], st[l]["amem"], st[l]["t"], r(l + 1))
+            else:
+                _hipk.mg_restrict(levels[l].dims, st[l]["t"], r(l + 1))
         if self.tail_from is None:
             _hipk.mg_diag(self.scale if L == 0 else 1.0, st[L]["dinv"], r(L), z(L))
         else:
-            _hipk.mg_tail_apply(self._tail, self.omega, self.scale if L == 0 else 1.0, r(L), z(L), work=self._tail_work)
+            tail_apply = _hipk.mg_gtail_apply if self.graph else _hipk.mg_tail_apply
+            tail_apply(self._tail, self.omega, self.scale if L == 0 else 1.0, r(L), z(L), work=self._tail_work)
         for l in range(L - 1, -1, -1):
-            _hipk.mg_prolong_add(levels[l].dims, self.omega, z(l + 1), z(l))
+            if self.graph:
+                _hipk.mg_prolong_add_agg(st[l]["agg"], self.omega, z(l + 1), z(l))
+            else:
+                _hipk.mg_prolong_add(levels[l].dims, self.omega, z(l + 1), z(l))
             _hipk.spmv_residual(st[l]["h"], z(l), r(l), st[l]["t"])
             smooth(l, st[l]["t"], st[l]["d"])
             _hipk.mg_correct(self.scale if l == 0 else 1.0, st[l]["d"], z(l))

@@ -14,6 +14,13 @@ what the one-launch tail kernel is worth against the launch sequence on the same
 
   python tools/mg_probe.py                                  # everything; one JSON line per system
   python tools/mg_probe.py --systems poisson2000 --reps 1 --configs mg1 --applies 0      # one solve (for rocprofv3 --kernel-trace)
+
+`--graph`: `AggregationMultigridPreconditioner.from_graph` (aggregates from the matrix graph, degrees 1 and 2: gmg1, gmg2) beside the
+grid class (mg1) and plain cg on the same systems and on an anisotropic 5-point operator (y-coupling x 0.01, 2000^2); the level sizes,
+the handshake rounds, the longest row of any level and the set-up time of the graph hierarchy are recorded, and the tail_rows sweep
+times the GRAPH hierarchy's apply.  profiles/mg_graph_probe.txt is its output.
+
+  python tools/mg_probe.py --graph --reps 2
 """
 import argparse
 import json
@@ -56,6 +63,25 @@ def systems():
     }
 
 
+def anisotropic_2d_csr(nx, ny, eps, device):
+    """5-point Dirichlet operator on an nx x ny grid, row i ny + j: coupling -1 along i, -eps along j, diagonal 2 + 2 eps."""
+    idx = torch.arange(nx * ny, device=device).reshape(nx, ny)
+    rows, cols, vals = [idx.reshape(-1)], [idx.reshape(-1)], [torch.full((nx * ny,), 2.0 + 2.0 * eps, dtype=torch.float64, device=device)]
+    for d, w in ((0, -1.0), (1, -eps)):
+        lo, hi = idx.narrow(d, 0, idx.shape[d] - 1).reshape(-1), idx.narrow(d, 1, idx.shape[d] - 1).reshape(-1)
+        rows += [lo, hi]
+        cols += [hi, lo]
+        vals += [torch.full((2 * lo.numel(),), w, dtype=torch.float64, device=device)]
+    n = nx * ny
+    return torch.sparse_coo_tensor(torch.stack([torch.cat(rows), torch.cat(cols)]), torch.cat(vals), (n, n)).coalesce().to_sparse_csr()
+
+
+def graph_systems():
+    table = systems()
+    table["aniso2000"] = (lambda: anisotropic_2d_csr(2000, 2000, 0.01, DEV), (2000, 2000))
+    return table
+
+
 def _timed(fn):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -64,7 +90,7 @@ def _timed(fn):
     return out, time.perf_counter() - t0
 
 
-def run_system(name, make, grid, reps, configs, applies):
+def run_system(name, make, grid, reps, configs, applies, graph=False):
     from pytorch_sparse_solver.module_a import AggregationMultigridPreconditioner, ChebyshevPreconditioner, cg, get_last_stats
     A = make()
     n = A.shape[0]
@@ -77,11 +103,25 @@ def run_system(name, make, grid, reps, configs, applies):
             Ms[cfg], setup[cfg] = _timed(lambda: ChebyshevPreconditioner(A, degree=3))
         elif cfg.startswith("mg"):
             Ms[cfg], setup[cfg] = _timed(lambda: AggregationMultigridPreconditioner(A, grid, degree=int(cfg[2:])))
+        elif cfg.startswith("gmg"):
+            try:
+                Ms[cfg], setup[cfg] = _timed(lambda: AggregationMultigridPreconditioner.from_graph(A, degree=int(cfg[3:])))
+            except ValueError as e:                       # the 48-level stall: recorded, the other configurations go on
+                row[cfg] = {"refused": str(e)}
+    configs = [c for c in configs if c == "plain" or c in Ms]
+    if graph and not any(c.startswith("gmg") for c in configs):
+        applies = 0                                       # no graph hierarchy to time
     row["setup_ms"] = {k: round(1e3 * v, 1) for k, v in setup.items()}
     mg = next((Ms[c] for c in configs if c.startswith("mg")), None)
     if mg is not None:
         row["levels"] = [lev.n for lev in mg.levels]
         row["tail_from"], row["launches_per_apply"] = mg.tail_from, mg.launches_per_apply
+    gmg = next((Ms[c] for c in configs if c.startswith("gmg")), None)
+    if gmg is not None:
+        row["graph_levels"] = [lev.n for lev in gmg.levels]
+        row["graph_tail_from"], row["graph_launches_per_apply"] = gmg.tail_from, gmg.launches_per_apply
+        row["graph_handshake_rounds_max"] = max(max(r) for r in gmg.handshake_rounds)
+        row["graph_longest_row"] = max(lev.max_row for lev in gmg.levels)
     for cfg in configs:                                   # warm-up: code objects, allocator, the handle of A
         cg(A, b, tol=1e-6, M=Ms[cfg], maxiter=5)
     times = {cfg: [] for cfg in configs}
@@ -102,7 +142,8 @@ def run_system(name, make, grid, reps, configs, applies):
         row["apply_us_by_tail_rows"] = {}
         ref = None
         for tail in TAILS:
-            M = AggregationMultigridPreconditioner(A, grid, degree=1, tail_rows=tail)
+            M = AggregationMultigridPreconditioner.from_graph(A, degree=1, tail_rows=tail) if graph else \
+                AggregationMultigridPreconditioner(A, grid, degree=1, tail_rows=tail)
             for _ in range(3):
                 z = M(v)
             ref = z if ref is None else ref
@@ -125,19 +166,22 @@ def run_system(name, make, grid, reps, configs, applies):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--systems", nargs="*", default=None)
-    ap.add_argument("--configs", nargs="*", default=["plain", "cheb3", "mg1", "mg2"])
+    ap.add_argument("--configs", nargs="*", default=None, help="default: plain cheb3 mg1 mg2; with --graph: plain mg1 gmg1 gmg2")
+    ap.add_argument("--graph", action="store_true", help="from_graph beside the grid class; the tail_rows sweep on the graph hierarchy")
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--applies", type=int, default=20)
     a = ap.parse_args()
+    a.configs = a.configs or (["plain", "mg1", "gmg1", "gmg2"] if a.graph else ["plain", "cheb3", "mg1", "mg2"])
     from pytorch_sparse_solver import _hipk
     from pytorch_sparse_solver.module_a import multigrid
     print(json.dumps({"hipk_build_id": _hipk.lib().hipk_build_id().decode(), "device": torch.cuda.get_device_name(0), "reps": a.reps,
-                      "applies": a.applies, "tol": 1e-6, "dtype": "float64", "MG_TAIL_MAX_ROWS": multigrid.MG_TAIL_MAX_ROWS}), flush=True)
-    table = systems()
+                      "applies": a.applies, "tol": 1e-6, "dtype": "float64", "MG_TAIL_MAX_ROWS": multigrid.MG_TAIL_MAX_ROWS,
+                      "mode": "graph" if a.graph else "grid", "configs": a.configs}), flush=True)
+    table = graph_systems() if a.graph else systems()
     for name in a.systems or list(table):
         make, grid = table[name]
         try:
-            row = run_system(name, make, grid, a.reps, a.configs, a.applies)
+            row = run_system(name, make, grid, a.reps, a.configs, a.applies, graph=a.graph)
         except torch.cuda.OutOfMemoryError as e:
             row = {"system": name, "skipped": f"does not fit: {str(e).splitlines()[0]}"}
         print(json.dumps(row), flush=True)
