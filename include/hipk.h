@@ -464,6 +464,34 @@ size_t hipk_mg_gtail_work_bytes(const hipk_mg_glevel *levels_host, int nlev, int
 int hipk_mg_gtail_apply(const hipk_mg_glevel *levels_host, const void *levels_dev, int nlev, int degree, double omega, double scale,
                         const void *r, void *z, int dtype, void *work, size_t work_bytes, hipk_stream_t stream);
 
+/* ---- aggregation multigrid: a dense coarsest level (csrc/hipk_mg_dense.hip) ----------------------------
+ * `from_graph(coarse_rows=K)` ends the hierarchy at a level of n <= K unknowns that is solved with the stored inverse of its
+ * matrix instead of being coarsened further.  cinv: n x n of `dtype` on the device, read only, column by column -- element
+ * (i, j) at cinv[j ld + i], ld >= n a multiple of 4 (else HIPK_ERR_ARG / HIPK_ERR_ALIGN), 16-byte aligned; rows n .. ld - 1
+ * of a column are padding and never read.  z = cinv r under this rounding spec, in segments of 64 columns:
+ *     p_q = 0;  p_q = p_q + (cinv[i, j] * r[j])   for j = 64 q .. min(64 q + 64, n) - 1 ascending
+ *     s   = 0;  s   = s + p_q                     for q ascending
+ *     z[i] = scale * s
+ * one rounding per operation, no fma, everything in `dtype`, `scale` rounded to it once.  The p_q are computed in parallel and
+ * meet in LDS behind a barrier, where the thread of row i adds them in ascending q: no atomics, no hand-off between workgroups,
+ * the same bits whatever the launch shape.
+ *   hipk_mg_dense_apply : one launch of ceil(n / 16) (fp64; 32 rows per workgroup in fp32) workgroups of 256 threads, each on 128
+ *                         bytes of every column; r is staged in LDS.  1 <= n <= 2048 (n < 1: HIPK_ERR_ARG, n > 2048:
+ *                         HIPK_ERR_UNSUPPORTED); r, z of n elements, 16-byte aligned, distinct; elements at and beyond n are
+ *                         never read or written.  Enqueued on `stream`, never synchronises.
+ *   hipk_mg_gtail_dense_apply : hipk_mg_gtail_apply whose LAST level is dense: levels[0 .. nlev - 1) are its sparse levels under its
+ *                         envelope (n <= 4096, max_row <= 32, nlev <= 32) and V(nlev - 1, r) = cinv r by the spec above, with
+ *                         all 256 threads on rows x segments (scale applies there only when nlev == 1).  Of levels[nlev - 1]
+ *                         only n is read, 1 <= n <= 512 (above: HIPK_ERR_UNSUPPORTED) and n <= levels[nlev - 2].n.  One launch
+ *                         of one workgroup, bit for bit the launch sequence that ends in hipk_mg_dense_apply.  Workspace
+ *                         (hipk_mg_gtail_dense_work_bytes: pure host code, 0 for bad arguments), alignment and the error
+ *                         contract -- an erroring call launches and writes nothing -- are hipk_mg_gtail_apply's. */
+int hipk_mg_dense_apply(int64_t n, int64_t ld, const void *cinv, double scale, const void *r, void *z, int dtype, hipk_stream_t stream);
+size_t hipk_mg_gtail_dense_work_bytes(const hipk_mg_glevel *levels_host, int nlev, int dtype);
+int hipk_mg_gtail_dense_apply(const hipk_mg_glevel *levels_host, const void *levels_dev, int nlev, int degree, double omega, double scale,
+                              const void *cinv, int64_t ld, const void *r, void *z, int dtype, void *work, size_t work_bytes,
+                              hipk_stream_t stream);
+
 /* ---- step API: externally driven loops (row-partitioned multi-GPU CG) ------------
  * The reference is single-device; the row-partitioned solver (north_star) drives the
  * SAME fused kernels from the host side of each rank and exchanges (a) the x-vector

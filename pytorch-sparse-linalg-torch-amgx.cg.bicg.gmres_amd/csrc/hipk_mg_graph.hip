@@ -12,9 +12,7 @@
 // -ffp-contract=off), no atomics, no hand-off between workgroups.
 #include "hipk_blas1.h"
 #include "hipk_common.h"
-#include "hipk_mg_tail.h"
-
-#define HIPK_MG_GTAIL_MAX_LEVELS 32
+#include "hipk_mg_gwalk.h"
 
 // rc[I] = t[first member], then + t[member] over the others in ascending fine index.  A thread owns VEC consecutive aggregates:
 // their member lists are one contiguous run of amem.
@@ -110,31 +108,15 @@ extern "C" int hipk_mg_prolong_add_agg(int64_t n, int64_t nc, const int32_t *agg
 
 // ------------------------------------------------------------------------------------------------------------- the tail kernel
 // hipk_mg_tail_kernel (hipk_mg.hip) for index-array levels: one launch, ONE 256-thread workgroup walks levels j = 0 .. nlev - 1 down
-// and back up with the steps, the slab and the rules of hipk_mg_tail.h.  The restriction gathers the staged t through amem, the
-// prolongation the staged e through agg, both complete in LDS behind a barrier; thread t owns aggregates t, t + 256, ... of the
-// coarse level as it owns its rows, so rc[I] is written by the thread that reads it next.  The last level is z = dinv r on any
-// number of rows.  Bit for bit the launch sequence's result.
+// and back up with the steps, the slab and the rules of hipk_mg_tail.h; the two walks are hipk_mg_gwalk.h's, which
+// hipk_mg_gtail_dense_kernel (hipk_mg_dense.hip) shares.  The last level is z = dinv r on any number of rows.  Bit for bit the
+// launch sequence's result.
 template <typename T>
 __global__ __launch_bounds__(HIPK_THREADS) void hipk_mg_gtail_kernel(const hipk_mg_glevel *__restrict__ lv, int nlev, int m, T omega, T scale,
                                                                      const T *rin, T *zout, T *slab) {
     __shared__ T xs[HIPK_MG_TAIL_MAX_N];
     const int t = threadIdx.x;
-    for (int j = 0; j + 1 < nlev; ++j) {   // down: steps 1 - 3
-        const hipk_mg_glevel &L = lv[j];
-        const hipk_mg_vecs<T> v = hipk_mg_level_vecs<T>(lv, j, rin, zout, slab);
-        T *rc = hipk_mg_level_vecs<T>(lv, j + 1, rin, zout, slab).r;
-        hipk_mg_smooth<T>(L, m, v.r, v.z, v.w, xs);
-        hipk_mg_residual<T>(L, v.z, v.r, v.t, xs);
-        hipk_mg_stage(L.n, v.t, xs);
-        const int nc = lv[j + 1].n;
-        for (int I = t; I < nc; I += HIPK_THREADS) {
-            const int lo = L.aptr[I], hi = L.aptr[I + 1];
-            T s = xs[L.amem[lo]];
-            for (int k = lo + 1; k < hi; ++k) s = s + xs[L.amem[k]];
-            rc[I] = s;
-        }
-        __syncthreads();
-    }
+    hipk_mg_gwalk_down<T>(lv, nlev, m, rin, zout, slab, xs);
     {   // the last level: no off-diagonal entry is left
         const hipk_mg_glevel &L = lv[nlev - 1];
         const hipk_mg_vecs<T> v = hipk_mg_level_vecs<T>(lv, nlev - 1, rin, zout, slab);
@@ -144,20 +126,7 @@ __global__ __launch_bounds__(HIPK_THREADS) void hipk_mg_gtail_kernel(const hipk_
             v.z[row] = (nlev == 1) ? scale * zz : zz;
         }
     }
-    for (int j = nlev - 2; j >= 0; --j) {   // up: steps 5 - 6
-        const hipk_mg_glevel &L = lv[j];
-        const hipk_mg_vecs<T> v = hipk_mg_level_vecs<T>(lv, j, rin, zout, slab);
-        const T *e = hipk_mg_level_vecs<T>(lv, j + 1, rin, zout, slab).z;
-        hipk_mg_stage(lv[j + 1].n, e, xs);
-        for (int row = t; row < L.n; row += HIPK_THREADS) v.z[row] = v.z[row] + (omega * xs[L.agg[row]]);
-        __syncthreads();
-        hipk_mg_residual<T>(L, v.z, v.r, v.t, xs);
-        hipk_mg_smooth<T>(L, m, v.t, v.d, v.w, xs);
-        for (int row = t; row < L.n; row += HIPK_THREADS) {
-            const T zz = v.z[row] + v.d[row];
-            v.z[row] = (j == 0) ? scale * zz : zz;
-        }
-    }
+    hipk_mg_gwalk_up<T>(lv, nlev, m, omega, scale, rin, zout, slab, xs);
 }
 
 static int hipk_mg_gtail_check(const hipk_mg_glevel *lv, int nlev, int degree, int dtype) {
@@ -165,17 +134,7 @@ static int hipk_mg_gtail_check(const hipk_mg_glevel *lv, int nlev, int degree, i
     HIPK_REQUIRE(nlev <= HIPK_MG_GTAIL_MAX_LEVELS, HIPK_ERR_UNSUPPORTED, "hipk_mg_gtail_apply takes at most 32 levels");
     HIPK_REQUIRE(degree >= 1 && degree <= 32, HIPK_ERR_ARG, "degree must be in [1, 32]");
     HIPK_REQUIRE(dtype == HIPK_F64 || dtype == HIPK_F32, HIPK_ERR_UNSUPPORTED, "dtype must be HIPK_F32 or HIPK_F64");
-    for (int j = 0; j < nlev; ++j) {
-        const hipk_mg_glevel &L = lv[j];
-        HIPK_REQUIRE(L.n >= 1, HIPK_ERR_ARG, "a level has no unknowns");
-        HIPK_REQUIRE(L.n <= HIPK_MG_TAIL_MAX_N && L.max_row <= HIPK_MG_TAIL_MAX_ROW, HIPK_ERR_UNSUPPORTED,
-                     "hipk_mg_gtail_apply takes levels of at most 4096 unknowns and 32 stored entries per row");
-        HIPK_REQUIRE(L.crow && L.col && L.val && L.dinv, HIPK_ERR_ARG, "null pointer in a level");
-        if (j + 1 < nlev) {
-            HIPK_REQUIRE(L.agg && L.aptr && L.amem, HIPK_ERR_ARG, "null index array in a level that has a next one");
-            HIPK_REQUIRE(lv[j + 1].n <= L.n, HIPK_ERR_ARG, "a level has more unknowns than the level above");
-        }
-    }
+    HIPK_TRY(hipk_mg_gtail_check_levels(lv, nlev, nlev, "hipk_mg_gtail_apply takes levels of at most 4096 unknowns and 32 stored entries per row"));
     return HIPK_OK;
 }
 

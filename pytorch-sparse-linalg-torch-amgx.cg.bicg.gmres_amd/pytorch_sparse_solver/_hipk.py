@@ -68,6 +68,8 @@ SYMBOLS = [
     "hipk_mg_tail_work_bytes", "hipk_mg_tail_apply",
     # aggregation multigrid on a matrix graph: the transfers by index arrays, and their tail kernel
     "hipk_mg_restrict_agg", "hipk_mg_prolong_add_agg", "hipk_mg_gtail_work_bytes", "hipk_mg_gtail_apply",
+    # ... with a dense coarsest level: z = cinv r as a launch, and as the tail's last level
+    "hipk_mg_dense_apply", "hipk_mg_gtail_dense_work_bytes", "hipk_mg_gtail_dense_apply",
 ]
 
 
@@ -330,6 +332,10 @@ def lib():
     L.hipk_mg_gtail_work_bytes.argtypes = [ctypes.POINTER(MgGLevel), i32, i32]
     L.hipk_mg_gtail_work_bytes.restype = ctypes.c_size_t
     L.hipk_mg_gtail_apply.argtypes = [ctypes.POINTER(MgGLevel), vp, i32, i32, dbl, dbl, vp, vp, i32, vp, ctypes.c_size_t, vp]
+    L.hipk_mg_dense_apply.argtypes = [i64, i64, vp, dbl, vp, vp, i32, vp]
+    L.hipk_mg_gtail_dense_work_bytes.argtypes = [ctypes.POINTER(MgGLevel), i32, i32]
+    L.hipk_mg_gtail_dense_work_bytes.restype = ctypes.c_size_t
+    L.hipk_mg_gtail_dense_apply.argtypes = [ctypes.POINTER(MgGLevel), vp, i32, i32, dbl, dbl, vp, i64, vp, vp, i32, vp, ctypes.c_size_t, vp]
     _lib = L
     return L
 
@@ -833,15 +839,26 @@ MG_GTAIL_MAX_LEVELS = 32  # the envelope of hipk_mg_gtail_apply beyond MG_TAIL_M
 
 class MgGTail:
     """`MgTail` for hipk_mg_gtail_apply: per level a dict with int32 `crow` / `col`, `val`, `dinv`, `max_row`, the smoother's `c0`,
-    `c1`, `c2` and the int32 index arrays `agg`, `aptr`, `amem` to the next level (all four absent or None on the last level)."""
+    `c1`, `c2` and the int32 index arrays `agg`, `aptr`, `amem` to the next level (all four absent or None on the last level).
 
-    def __init__(self, levels, degree: int):
+    `cinv` (with `ld`): the descriptors of hipk_mg_gtail_dense_apply instead.  The last entry of `levels` is then the dense level,
+    a dict of which only `n` is read, and `cinv` its stored inverse (`mg_dense_apply`'s layout)."""
+
+    def __init__(self, levels, degree: int, cinv: Optional[torch.Tensor] = None, ld: int = 0):
         self.nlev, self.degree = len(levels), int(degree)
-        self.dtype, self.device = levels[0]["val"].dtype, levels[0]["val"].device
+        self.cinv, self.ld = cinv, int(ld)
+        sizes = [int(lev["dinv"].numel()) for lev in levels[:-1 if cinv is not None else None]] + ([int(levels[-1]["n"])] if cinv is not None else [])
+        if cinv is not None:
+            self.dtype, self.device = cinv.dtype, cinv.device
+            _check_cinv(cinv, sizes[-1], self.ld)
+        else:
+            self.dtype, self.device = levels[0]["val"].dtype, levels[0]["val"].device
         self.host = (MgGLevel * self.nlev)()
         self._keep = []
         for j, (d, lev) in enumerate(zip(self.host, levels)):
-            d.n = int(lev["dinv"].numel())
+            d.n = sizes[j]
+            if cinv is not None and j == self.nlev - 1:
+                break
             for name in ("crow", "col", "val", "dinv"):
                 t = lev[name]
                 assert t.is_cuda and t.is_contiguous() and t.device == self.device
@@ -851,7 +868,7 @@ class MgGTail:
             assert lev["crow"].numel() == d.n + 1 and lev["col"].numel() == lev["val"].numel()
             d.max_row = int(lev["max_row"])
             if j + 1 < self.nlev:
-                nc = int(levels[j + 1]["dinv"].numel())
+                nc = sizes[j + 1]
                 for name, numel in (("agg", d.n), ("aptr", nc + 1), ("amem", d.n)):
                     _check_index(name, lev[name], numel, lev["val"])
                     self._keep.append(lev[name])
@@ -861,12 +878,14 @@ class MgGTail:
                     d.c1[k], d.c2[k] = float(lev["c1"][k]), float(lev["c2"][k])
         raw = torch.frombuffer(bytearray(bytes(self.host)), dtype=torch.uint8)
         self.blob = raw.to(self.device)
-        self.work_bytes = int(lib().hipk_mg_gtail_work_bytes(self.host, self.nlev, _dtype_code(self.dtype)))
+        work_bytes = lib().hipk_mg_gtail_work_bytes if cinv is None else lib().hipk_mg_gtail_dense_work_bytes
+        self.work_bytes = int(work_bytes(self.host, self.nlev, _dtype_code(self.dtype)))
 
 
 def mg_gtail_apply(tail: MgGTail, omega: float, scale: float, r: torch.Tensor, z: torch.Tensor,
                    work: Optional[torch.Tensor] = None) -> torch.Tensor:
     """z = scale * V(0, r) over the tail's index-array levels in one launch (hipk_mg_gtail_apply), on the current stream."""
+    assert tail.cinv is None, "the tail was built with a dense level: mg_gtail_dense_apply"
     n = int(tail.host[0].n)
     for v in (r, z):
         assert v.is_cuda and v.is_contiguous() and v.dtype == tail.dtype and v.device == tail.device and v.numel() == n
@@ -875,6 +894,43 @@ def mg_gtail_apply(tail: MgGTail, omega: float, scale: float, r: torch.Tensor, z
         _check(lib().hipk_mg_gtail_apply(tail.host, tail.blob.data_ptr(), tail.nlev, tail.degree, float(omega), float(scale),
                                          r.data_ptr(), z.data_ptr(), _dtype_code(tail.dtype), work.data_ptr(), tail.work_bytes,
                                          _stream(tail.device)), "hipk_mg_gtail_apply")
+    return z
+
+
+MG_DENSE_MAX_N = 2048     # the envelope of hipk_mg_dense_apply: unknowns of the dense level ...
+MG_DENSE_TAIL_N = 512     # ... and of hipk_mg_gtail_dense_apply's last level
+
+
+def _check_cinv(cinv: torch.Tensor, n: int, ld: int) -> None:
+    """The stored inverse of a dense level: n columns of ld elements, element (i, j) at j * ld + i."""
+    assert cinv.is_cuda and cinv.is_contiguous() and cinv.data_ptr() % 16 == 0, "cinv: a contiguous 16-byte aligned device tensor"
+    assert ld >= n and ld % 4 == 0 and cinv.numel() == n * ld, f"cinv: {cinv.numel()} elements for n = {n}, ld = {ld}"
+
+
+def mg_dense_apply(cinv: torch.Tensor, ld: int, scale: float, r: torch.Tensor, z: torch.Tensor) -> torch.Tensor:
+    """z = scale * (cinv r) for the column-by-column inverse of a dense level, summed in segments of 64 columns (hipk_mg_dense_apply)."""
+    n = z.numel()
+    for v in (r, z):
+        assert v.is_cuda and v.is_contiguous() and v.dtype == cinv.dtype and v.device == cinv.device and v.numel() == n
+    _check_cinv(cinv, n, int(ld))
+    with torch.cuda.device(z.device):
+        _check(lib().hipk_mg_dense_apply(n, int(ld), cinv.data_ptr(), float(scale), r.data_ptr(), z.data_ptr(), _dtype_code(z.dtype),
+                                         _stream(z.device)), "hipk_mg_dense_apply")
+    return z
+
+
+def mg_gtail_dense_apply(tail: MgGTail, omega: float, scale: float, r: torch.Tensor, z: torch.Tensor,
+                         work: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """z = scale * V(0, r) over the tail's index-array levels and its dense last level in one launch (hipk_mg_gtail_dense_apply)."""
+    assert tail.cinv is not None, "the tail was built without a dense level"
+    n = int(tail.host[0].n)
+    for v in (r, z):
+        assert v.is_cuda and v.is_contiguous() and v.dtype == tail.dtype and v.device == tail.device and v.numel() == n
+    work = _workspace(work, tail.device, tail.work_bytes)
+    with torch.cuda.device(tail.device):
+        _check(lib().hipk_mg_gtail_dense_apply(tail.host, tail.blob.data_ptr(), tail.nlev, tail.degree, float(omega), float(scale),
+                                               tail.cinv.data_ptr(), tail.ld, r.data_ptr(), z.data_ptr(), _dtype_code(tail.dtype),
+                                               work.data_ptr(), tail.work_bytes, _stream(tail.device)), "hipk_mg_gtail_dense_apply")
     return z
 
 

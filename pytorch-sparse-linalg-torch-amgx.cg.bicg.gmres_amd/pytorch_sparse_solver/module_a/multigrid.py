@@ -12,12 +12,14 @@ Like `ChebyshevPreconditioner` the apply consists of SpMVs and element-wise step
 deterministic, independent of launch shapes and bitwise equal to a CPU mirror of the steps (tests/_mg_mirror.py).
 """
 import math
+import numbers
 
 import torch
 
 from .preconditioners import ChebyshevPreconditioner, _diagonal
 
-__all__ = ["AggregationMultigridPreconditioner", "MG_TAIL_MAX_ROWS", "MG_GRAPH_MAX_LEVELS", "pairwise_aggregates"]
+__all__ = ["AggregationMultigridPreconditioner", "MG_TAIL_MAX_ROWS", "MG_GRAPH_MAX_LEVELS", "MG_DENSE_MAX_ROWS", "MG_DENSE_TAIL_ROWS",
+           "pairwise_aggregates"]
 
 # The default of `tail_rows`: levels of at most this many unknowns run inside the one-launch tail kernel (0: none do).
 # Measured (tools/mg_probe.py, profiles/mg_probe.txt, MI355X, fp64, 5-point Poisson 2000 x 2000, degree 1, device time per apply):
@@ -33,6 +35,12 @@ MG_TAIL_MAX_ROWS = 1024
 # `from_graph`: a hierarchy of more levels than this is refused as a stalled coarsening (pairwise matching shrinks a level by a
 # factor of about 3.2 with two passes: 48 levels are far beyond any matrix that fits a device)
 MG_GRAPH_MAX_LEVELS = 48
+
+# `from_graph(coarse_rows=K)`: the largest dense coarsest level (`hipk_mg_dense_apply`'s envelope; its fp64 inverse is 32 MB), and
+# the largest one the one-launch tail takes as its last level (`hipk_mg_gtail_dense_apply`'s: one workgroup streams the inverse)
+MG_DENSE_MAX_ROWS = 2048
+MG_DENSE_TAIL_ROWS = 512
+DENSE_SEGMENT = 64        # the columns of one partial sum of the dense step
 
 
 def _grid3(dims):
@@ -212,7 +220,10 @@ def _pairwise_aggregates(A_csr, passes: int, theta: float):
 class _Level:
     """One level: `csr` (the matrix, a CSR tensor), `dims`, `n`, `dinv` (the reciprocal diagonal) and, except on the last level,
     the smoother's coefficients `c0`, `c1`, `c2` (`ChebyshevPreconditioner`'s, `smoother` is that object).  `agg`: on a level of a
-    graph hierarchy that has a next one, the int64 map from its rows to the next level's; None otherwise."""
+    graph hierarchy that has a next one, the int64 map from its rows to the next level's; None otherwise.  A dense last level
+    (`from_graph(coarse_rows=K)`) has no `dinv` and no smoother but `cinv`, the inverse of its matrix in the storage dtype as a
+    contiguous (n, ld) tensor, `ld = (n + 3) & ~3`: `cinv[j, i]` is element (i, j) of the inverse -- column j of the inverse is row
+    j of the tensor, so element (i, j) sits at `j * ld + i` of the memory -- and `cinv[:, n:]` is zero padding."""
 
     def __init__(self, csr, dims):
         self.csr, self.dims, self.n = csr, tuple(dims), int(csr.shape[0])
@@ -222,6 +233,7 @@ class _Level:
         self.smoother = None
         self.dinv = None
         self.c0 = self.c1 = self.c2 = None
+        self.cinv = self.ld = None
 
 
 class AggregationMultigridPreconditioner:
@@ -267,7 +279,8 @@ class AggregationMultigridPreconditioner:
 
     `from_graph(A, ...)` builds the same object without a grid, from aggregates of the matrix graph (see there).
 
-    Attributes: `levels` (per level `csr`, `dims`, `n`, `dinv`, `c0`, `c1`, `c2`, `agg`), `graph` (True for `from_graph`),
+    Attributes: `levels` (per level `csr`, `dims`, `n`, `dinv`, `c0`, `c1`, `c2`, `agg`, `cinv`), `graph` (True for `from_graph`),
+    `coarse_rows` and `dense` (`from_graph(coarse_rows=K)`: K, and whether the last level is solved with `levels[-1].cinv`),
     `handshake_rounds` (graph: per level the rounds of each matching pass), `scale`, `applies`, `tail_rows`, `tail_from`,
     `launches_per_apply` (the launches of one device apply, a Chebyshev step counted as the one launch it is where the SpMV has
     the Chebyshev epilogue: 2 degree + 7 per level above the tail -- above L without one --, then one)."""
@@ -283,11 +296,11 @@ class AggregationMultigridPreconditioner:
             raise ValueError(f"grid must have 2 or 3 dimensions, got {len(dims)}")
         if min(dims) < 1 or math.prod(dims) != A.shape[0]:
             raise ValueError(f"grid {dims} does not have the matrix's {A.shape[0]} points")
-        self._set_up(A, dims, degree, ratio, omega, normalize, tail_rows, None)
+        self._set_up(A, dims, degree, ratio, omega, normalize, tail_rows, None, None)
 
     @classmethod
     def from_graph(cls, A: torch.Tensor, degree: int = 1, ratio: float = 4.0, omega: float = 1.8, normalize: bool = True,
-                   tail_rows=None, passes: int = 2, theta: float = 0.25):
+                   tail_rows=None, passes: int = 2, theta: float = 0.25, coarse_rows=None):
         """The same preconditioner for ANY square `A`: the aggregates come from the matrix graph, not from a grid.
 
         Level l's aggregates are `pairwise_aggregates(A_l, passes, theta)` (pairwise matching on strong couplings, aggregates of
@@ -298,14 +311,33 @@ class AggregationMultigridPreconditioner:
         `MG_GRAPH_MAX_LEVELS` (48) levels is a ValueError: the coarsening has stalled (a star graph loses one pair per pass).
         Smoother, V-cycle, `normalize`, `tail_rows`, `applies` and `launches_per_apply` are the grid object's; every level has
         `dims == (n,)` and, except the last, `agg` (int64, the map to the next level).  The device transfers are
-        `hipk_mg_restrict_agg` / `hipk_mg_prolong_add_agg`, the tail `hipk_mg_gtail_apply` (at most 32 levels, else launches)."""
+        `hipk_mg_restrict_agg` / `hipk_mg_prolong_add_agg`, the tail `hipk_mg_gtail_apply` (at most 32 levels, else launches).
+
+        `coarse_rows=K` (an integer in [1, `MG_DENSE_MAX_ROWS`] = 2048; None: the hierarchy above, unchanged) ends the coarsening
+        at the first level, level 0 included, of at most K unknowns -- or where the rule above ends it, whichever comes first --
+        and solves that level with the inverse of its matrix.  The matching shrinks a level by 3.2 only down to a few thousand
+        unknowns and by two unknowns per level below that; the cut removes those levels.  The levels above the cut are the
+        default hierarchy's, bit for bit.  The dense level (`dense` is True, `levels[-1].cinv`): its coalesced matrix (entries
+        stored with the same (row, col) summed in stored order) is written out densely, converted to fp64 on the CPU, inverted
+        there with `torch.linalg.inv` and rounded once to the storage dtype -- the same bits from a CPU and a device matrix; a
+        singular matrix or a non-finite inverse is a ValueError.  V(L, r) = cinv r in segments of 64 columns:
+            p_q = 0;  p_q = p_q + (cinv[i, j] * r[j])   for j = 64 q .. min(64 q + 64, n) - 1 ascending
+            s   = 0;  s   = s + p_q                     for q ascending;   z[i] = s
+        one rounding per operation, no fma, in the storage dtype.  On the device it is the last level of the tail
+        (`hipk_mg_gtail_dense_apply`) when `tail_rows` selects a tail, every sparse level below it fits the tail's envelope and
+        the dense level has at most `MG_DENSE_TAIL_ROWS` (512) unknowns; otherwise the levels run as launches and end in one
+        `hipk_mg_dense_apply`.  `launches_per_apply` keeps its formula."""
         self = cls.__new__(cls)
         cls._check_matrix(A)
+        if coarse_rows is not None:
+            if isinstance(coarse_rows, bool) or not isinstance(coarse_rows, numbers.Integral) or not 1 <= coarse_rows <= MG_DENSE_MAX_ROWS:
+                raise ValueError(f"coarse_rows must be None or an integer in [1, {MG_DENSE_MAX_ROWS}], got {coarse_rows!r}")
+            coarse_rows = int(coarse_rows)
         if isinstance(passes, bool) or int(passes) != passes or not 1 <= int(passes) <= 4:
             raise ValueError(f"passes must be 1, 2, 3 or 4, got {passes}")
         if not 0.0 <= float(theta) <= 1.0:
             raise ValueError(f"theta must be in [0, 1], got {theta}")
-        self._set_up(A, (int(A.shape[0]),), degree, ratio, omega, normalize, tail_rows, (int(passes), float(theta)))
+        self._set_up(A, (int(A.shape[0]),), degree, ratio, omega, normalize, tail_rows, (int(passes), float(theta)), coarse_rows)
         return self
 
     @staticmethod
@@ -317,8 +349,9 @@ class AggregationMultigridPreconditioner:
         if A.dtype not in (torch.float64, torch.float32):
             raise ValueError(f"AggregationMultigridPreconditioner needs a float64 or float32 matrix, not {A.dtype}")
 
-    def _set_up(self, A, dims, degree, ratio, omega, normalize, tail_rows, graph) -> None:
-        """Everything after the argument checks of the two constructors.  `graph`: None on a grid, else (passes, theta)."""
+    def _set_up(self, A, dims, degree, ratio, omega, normalize, tail_rows, graph, coarse_rows) -> None:
+        """Everything after the argument checks of the two constructors.  `graph`: None on a grid, else (passes, theta);
+        `coarse_rows`: None, or on a graph the largest dense last level."""
         if not 1 <= int(degree) <= 32:
             raise ValueError("degree must be in [1, 32]")
         if not float(omega) > 0.0:
@@ -332,8 +365,14 @@ class AggregationMultigridPreconditioner:
         self.levels = []
         self.graph = graph is not None
         self.handshake_rounds = [] if self.graph else None      # per level with a next one: the rounds of each matching pass
+        self.coarse_rows, self.dense = coarse_rows, False
         while True:
             lev = _Level(csr, dims)
+            if coarse_rows is not None and lev.n <= coarse_rows:      # the cut: this level is solved, not coarsened
+                self._set_up_dense(lev, len(self.levels))
+                self.levels.append(lev)
+                self.dense = True
+                break
             if self.graph:
                 agg, n, rounds = _pairwise_aggregates(csr, *graph)
                 last = n == lev.n
@@ -364,8 +403,8 @@ class AggregationMultigridPreconditioner:
             raise ValueError("tail_rows must be 0 (no tail kernel) or positive")
         self.tail_rows = min(tail_rows, 4096)
         first = next((l for l, lev in enumerate(self.levels) if lev.n <= self.tail_rows), None)
-        fits = first is not None and all(lev.max_row <= 32 for lev in self.levels[first:]) and \
-            (not self.graph or len(self.levels) - first <= 32)
+        fits = first is not None and all(lev.max_row <= 32 for lev in self.levels[first:len(self.levels) - self.dense]) and \
+            (not self.graph or len(self.levels) - first <= 32) and (not self.dense or self.levels[-1].n <= MG_DENSE_TAIL_ROWS)
         self.tail_from = first if fits else None
         self.launches_per_apply = (L if self.tail_from is None else self.tail_from) * (2 * self.degree + 7) + 1
         self._cpu = None      # per level: (spec SpMV, the aggregate of every row, step 3's gather indices)
@@ -404,6 +443,25 @@ class AggregationMultigridPreconditioner:
         except ValueError as e:
             raise ValueError(f"AggregationMultigridPreconditioner, level {l} ({'x'.join(map(str, lev.dims))}): {e}") from None
         lev.smoother, lev.dinv, lev.c0, lev.c1, lev.c2 = sm, sm.dinv, sm.c0, sm.c1, sm.c2
+
+    def _set_up_dense(self, lev: _Level, l: int) -> None:
+        """`lev.cinv` of a dense last level: the inverse of its coalesced matrix, taken in fp64 on the CPU and rounded once."""
+        csr, n = lev.csr, lev.n
+        crow, col, val = _galerkin_agg(csr.crow_indices(), csr.col_indices(), csr.values(), torch.arange(n, device=csr.device), n)
+        dense = torch.zeros((n, n), dtype=val.dtype, device=val.device)
+        dense[_rows_of(crow), col] = val                          # coalesced: every (row, col) once
+        where = f"AggregationMultigridPreconditioner.from_graph, dense level {l} ({n})"
+        try:
+            inv = torch.linalg.inv(dense.to(device="cpu", dtype=torch.float64))
+        except RuntimeError as e:
+            raise ValueError(f"{where}: the matrix is singular ({e})") from None
+        inv = inv.to(val.dtype)
+        if not bool(torch.isfinite(inv).all()):
+            raise ValueError(f"{where}: the inverse is not finite; is the matrix singular?")
+        lev.ld = (n + 3) & ~3
+        cinv = torch.zeros((n, lev.ld), dtype=val.dtype)
+        cinv[:, :n] = inv.T                                       # row j of the tensor is column j of the inverse
+        lev.cinv = cinv.to(self.device)
 
     @staticmethod
     def _gershgorin(csr) -> float:
@@ -444,7 +502,7 @@ class AggregationMultigridPreconditioner:
     def _v_torch(self, l: int, r: torch.Tensor) -> torch.Tensor:
         lev = self.levels[l]
         if l == len(self.levels) - 1:
-            return lev.dinv.cpu() * r
+            return self._dense_torch(lev, r) if self.dense else lev.dinv.cpu() * r
         agg, members = self._cpu_state()[l]
         S = lev.smoother._apply_torch
         z = S(r)
@@ -458,6 +516,23 @@ class AggregationMultigridPreconditioner:
         t = r - spmv(z)
         return z + S(t)
 
+    @staticmethod
+    def _dense_torch(lev: _Level, r: torch.Tensor) -> torch.Tensor:
+        """z = cinv r by the dense step's rounding spec: pass k adds column 64 q + k to the partial of every segment q that has
+        one (a product, then a sum, each one torch op and one rounding), then the partials are added in ascending q."""
+        n = lev.n
+        C = lev.cinv.cpu()[:, :n]                                 # C[j] is column j of the inverse
+        first = torch.arange(0, n, DENSE_SEGMENT)
+        P = torch.zeros((first.numel(), n), dtype=r.dtype)
+        for k in range(min(DENSE_SEGMENT, n)):
+            q = torch.nonzero(first + k < n).flatten()
+            j = first[q] + k
+            P[q] = P[q] + (C[j] * r[j, None])
+        s = torch.zeros(n, dtype=r.dtype)
+        for q in range(first.numel()):
+            s = s + P[q]
+        return s
+
     # ------------------------------------------------------------------ device: one launch per step
     def _dev_state(self):
         if self._dev is None:
@@ -466,8 +541,14 @@ class AggregationMultigridPreconditioner:
             st = []
             tf = len(self.levels) if self.tail_from is None else self.tail_from
             for l, lev in enumerate(self.levels):
-                s = {"dinv": lev.dinv.to(device=dev, dtype=dt).contiguous()}
                 vec = lambda: torch.empty(lev.n, dtype=dt, device=dev)
+                if lev.cinv is not None:         # the dense last level: nothing but its inverse
+                    s = {"n": lev.n, "cinv": lev.cinv.to(device=dev, dtype=dt).contiguous().reshape(-1), "ld": lev.ld}
+                    if l and l <= tf:
+                        s["r"], s["z"] = vec(), vec()
+                    st.append(s)
+                    continue
+                s = {"dinv": lev.dinv.to(device=dev, dtype=dt).contiguous()}
                 if l and l <= tf:
                     s["r"], s["z"] = vec(), vec()
                 if lev.agg is not None:          # the transfers' index arrays: agg, and the members aggregate by aggregate
@@ -488,7 +569,10 @@ class AggregationMultigridPreconditioner:
                     s["work"] = torch.empty(2 * ((lev.n + 3) & ~3) * c.values().element_size(), dtype=torch.uint8, device=dev)
                 st.append(s)
             if tf < len(self.levels):
-                self._tail = (_hipk.MgGTail if self.graph else _hipk.MgTail)(st[tf:], self.degree)
+                if self.dense:
+                    self._tail = _hipk.MgGTail(st[tf:], self.degree, cinv=st[-1]["cinv"], ld=st[-1]["ld"])
+                else:
+                    self._tail = (_hipk.MgGTail if self.graph else _hipk.MgTail)(st[tf:], self.degree)
                 self._tail_work = torch.empty(self._tail.work_bytes, dtype=torch.uint8, device=dev)
             self._dev = st
         return self._dev
@@ -511,10 +595,12 @@ class AggregationMultigridPreconditioner:
                 _hipk.mg_restrict_agg(st[l]["aptr"], st[l]["amem"], st[l]["t"], r(l + 1))
             else:
                 _hipk.mg_restrict(levels[l].dims, st[l]["t"], r(l + 1))
-        if self.tail_from is None:
+        if self.tail_from is None and self.dense:
+            _hipk.mg_dense_apply(st[L]["cinv"], st[L]["ld"], self.scale if L == 0 else 1.0, r(L), z(L))
+        elif self.tail_from is None:
             _hipk.mg_diag(self.scale if L == 0 else 1.0, st[L]["dinv"], r(L), z(L))
         else:
-            tail_apply = _hipk.mg_gtail_apply if self.graph else _hipk.mg_tail_apply
+            tail_apply = _hipk.mg_gtail_dense_apply if self.dense else _hipk.mg_gtail_apply if self.graph else _hipk.mg_tail_apply
             tail_apply(self._tail, self.omega, self.scale if L == 0 else 1.0, r(L), z(L), work=self._tail_work)
         for l in range(L - 1, -1, -1):
             if self.graph:

@@ -21,6 +21,14 @@ the handshake rounds, the longest row of any level and the set-up time of the gr
 times the GRAPH hierarchy's apply.  profiles/mg_graph_probe.txt is its output.
 
   python tools/mg_probe.py --graph --reps 2
+
+`--graph` also runs `from_graph(degree=1, coarse_rows=K)` for K = 256 / 512 / 1024 / 2048 (gmg1c256 ... gmg1c2048: the hierarchy cut
+at a dense coarsest level) next to gmg1 in the same alternation, and records per configuration the levels, the launches of an apply
+and `tail_from`, and the device time of the dense step alone in both forms: the launch `hipk_mg_dense_apply` and, up to 512 rows,
+the one-workgroup tail `hipk_mg_gtail_dense_apply` on that level alone.  A last line times both forms on random matrices of
+256 / 512 / 1024 / 2048 rows.  profiles/mg_dense_probe.txt is the output of
+
+  python tools/mg_probe.py --graph --reps 2 --applies 0 --configs plain mg1 gmg1 gmg1c256 gmg1c512 gmg1c1024 gmg1c2048
 """
 import argparse
 import json
@@ -36,6 +44,38 @@ import torch  # noqa: E402
 
 DEV = "cuda:0"
 TAILS = (0, 256, 1024, 4096)
+CUTS = (256, 512, 1024, 2048)
+
+
+def _event_us(fn, calls=50):
+    """Device time of one call of fn (HIP events around `calls` calls, the best of three)."""
+    for _ in range(3):
+        fn()
+    best = float("inf")
+    for _ in range(3):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        for _ in range(calls):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        best = min(best, 1e3 * e0.elapsed_time(e1) / calls)
+    return round(best, 1)
+
+
+def dense_step_us(cinv, n, ld):
+    """{"launch": us, "tail": us or None}: z = cinv r alone as hipk_mg_dense_apply and as hipk_mg_gtail_dense_apply with one level."""
+    from pytorch_sparse_solver import _hipk
+    r, z = torch.randn(n, dtype=cinv.dtype, device=DEV), torch.empty(n, dtype=cinv.dtype, device=DEV)
+    out = {"n": n, "launch": _event_us(lambda: _hipk.mg_dense_apply(cinv, ld, 1.0, r, z)), "tail": None}
+    ref = z.clone()
+    if n <= _hipk.MG_DENSE_TAIL_N:
+        tail = _hipk.MgGTail([{"n": n}], 1, cinv=cinv, ld=ld)
+        work = torch.empty(tail.work_bytes, dtype=torch.uint8, device=DEV)
+        out["tail"] = _event_us(lambda: _hipk.mg_gtail_dense_apply(tail, 1.8, 1.0, r, z, work=work))
+        assert torch.equal(z, ref), "the two forms of the dense step differ"
+    return out
 
 
 def poisson_3d_csr(n0, n1, n2, device):
@@ -104,8 +144,10 @@ def run_system(name, make, grid, reps, configs, applies, graph=False):
         elif cfg.startswith("mg"):
             Ms[cfg], setup[cfg] = _timed(lambda: AggregationMultigridPreconditioner(A, grid, degree=int(cfg[2:])))
         elif cfg.startswith("gmg"):
+            degree, _, cut = cfg[3:].partition("c")
             try:
-                Ms[cfg], setup[cfg] = _timed(lambda: AggregationMultigridPreconditioner.from_graph(A, degree=int(cfg[3:])))
+                Ms[cfg], setup[cfg] = _timed(lambda: AggregationMultigridPreconditioner.from_graph(A, degree=int(degree),
+                                                                                                     coarse_rows=int(cut) if cut else None))
             except ValueError as e:                       # the 48-level stall: recorded, the other configurations go on
                 row[cfg] = {"refused": str(e)}
     configs = [c for c in configs if c == "plain" or c in Ms]
@@ -122,6 +164,15 @@ def run_system(name, make, grid, reps, configs, applies, graph=False):
         row["graph_tail_from"], row["graph_launches_per_apply"] = gmg.tail_from, gmg.launches_per_apply
         row["graph_handshake_rounds_max"] = max(max(r) for r in gmg.handshake_rounds)
         row["graph_longest_row"] = max(lev.max_row for lev in gmg.levels)
+    row["hierarchy"] = {}
+    for cfg in configs:
+        M = Ms[cfg]
+        if cfg.startswith("gmg"):
+            row["hierarchy"][cfg] = {"levels": len(M.levels), "last": M.levels[-1].n, "launches": M.launches_per_apply, "tail_from": M.tail_from,
+                                     "longest_row_above_the_last": max([lev.max_row for lev in M.levels[:-1]] or [0])}
+            if M.dense:
+                M(b)                                       # builds the device state
+                row["hierarchy"][cfg]["dense_step_us"] = dense_step_us(M._dev_state()[-1]["cinv"], M.levels[-1].n, M.levels[-1].ld)
     for cfg in configs:                                   # warm-up: code objects, allocator, the handle of A
         cg(A, b, tol=1e-6, M=Ms[cfg], maxiter=5)
     times = {cfg: [] for cfg in configs}
@@ -166,12 +217,12 @@ def run_system(name, make, grid, reps, configs, applies, graph=False):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--systems", nargs="*", default=None)
-    ap.add_argument("--configs", nargs="*", default=None, help="default: plain cheb3 mg1 mg2; with --graph: plain mg1 gmg1 gmg2")
+    ap.add_argument("--configs", nargs="*", default=None, help="default: plain cheb3 mg1 mg2; with --graph: plain mg1 gmg1 gmg2 gmg1c256 gmg1c512 gmg1c1024 gmg1c2048")
     ap.add_argument("--graph", action="store_true", help="from_graph beside the grid class; the tail_rows sweep on the graph hierarchy")
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--applies", type=int, default=20)
     a = ap.parse_args()
-    a.configs = a.configs or (["plain", "mg1", "gmg1", "gmg2"] if a.graph else ["plain", "cheb3", "mg1", "mg2"])
+    a.configs = a.configs or (["plain", "mg1", "gmg1", "gmg2"] + [f"gmg1c{k}" for k in CUTS] if a.graph else ["plain", "cheb3", "mg1", "mg2"])
     from pytorch_sparse_solver import _hipk
     from pytorch_sparse_solver.module_a import multigrid
     print(json.dumps({"hipk_build_id": _hipk.lib().hipk_build_id().decode(), "device": torch.cuda.get_device_name(0), "reps": a.reps,
@@ -187,6 +238,12 @@ def main():
         print(json.dumps(row), flush=True)
         _hipk.clear_cache()
         torch.cuda.empty_cache()
+    if a.graph and a.systems is None:                     # the dense step alone on random matrices, both forms
+        steps = []
+        for n in CUTS:
+            ld = (n + 3) & ~3
+            steps.append(dense_step_us(torch.randn(n * ld, dtype=torch.float64, device=DEV), n, ld))
+        print(json.dumps({"dense_step_us_random_fp64": steps}), flush=True)
 
 
 if __name__ == "__main__":
