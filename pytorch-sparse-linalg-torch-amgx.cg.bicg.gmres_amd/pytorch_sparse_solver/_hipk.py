@@ -388,6 +388,16 @@ def _dtype_code(dt: torch.dtype) -> int:
     raise HipkError(f"unsupported dtype {dt}")
 
 
+def aligned(t: torch.Tensor, align: int = 16) -> torch.Tensor:
+    """The operand whose `data_ptr()` goes to libhipk.so: `t` itself (the same object, no copy) when it is contiguous and starts
+    `align`-byte aligned, else a fresh contiguous copy of its values.  Never writes to `t`.  The C entry points refuse vectors
+    that are not 16-byte aligned (HIPK_ERR_ALIGN: the kernels use 16-byte accesses), and `.contiguous()` keeps a contiguous view
+    where it starts -- `buf[1:n + 1]`, a slab `state[n:2 * n]` with odd n -- so every wrapper routes its operands through here."""
+    if t.is_contiguous() and t.data_ptr() % align == 0:
+        return t
+    return t.clone(memory_format=torch.contiguous_format)
+
+
 class _SolveLock:
     """threading.Lock that refuses re-entry from the thread that holds it: a preconditioner callable that solves
     with the SAME matrix object would otherwise dead-lock (and would share the handle's scratch with the outer solve)."""
@@ -417,9 +427,9 @@ class CsrHandle:
     def __init__(self, crow: torch.Tensor, col: torch.Tensor, val: torch.Tensor, shape):
         if not val.is_cuda:
             raise HipkError("CsrHandle needs CUDA/ROCm tensors")
-        self.crow = crow.contiguous()
-        self.col = col.contiguous()
-        self.val = val.contiguous()
+        self.crow = aligned(crow)
+        self.col = aligned(col)
+        self.val = aligned(val)     # hipk_csr_create refuses values that are not 16-byte aligned: a view's values are copied
         self.shape = (int(shape[0]), int(shape[1]))
         self.device = val.device
         self.dtype = val.dtype
@@ -687,8 +697,7 @@ def cheb_apply(h: CsrHandle, degree: int, dinv: torch.Tensor, coef, v: torch.Ten
     assert v.is_cuda and v.dtype == h.dtype and v.device == h.device and v.numel() == h.n and h.shape[0] == h.shape[1]
     assert dinv.is_contiguous() and dinv.dtype == v.dtype and dinv.device == v.device and dinv.numel() == h.n
     assert len(coef) == 2 * int(degree) + 2
-    if not v.is_contiguous() or v.data_ptr() % 16:
-        v = v.contiguous().clone()
+    v = aligned(v)
     if out is None:
         out = torch.empty_like(v)
     assert out.is_contiguous() and out.dtype == v.dtype and out.device == v.device and out.numel() == h.n and out.data_ptr() % 16 == 0
@@ -1305,7 +1314,7 @@ def solve_cg_stepwise(h: Optional[CsrHandle], A_fn, M, b: torch.Tensor, x: torch
         z = fn(v)
         if not isinstance(z, torch.Tensor) or z.shape != v.shape:
             raise ValueError(f"the {what} must map a vector to a vector of the same shape")
-        return z.to(device=dev, dtype=b.dtype).contiguous()
+        return aligned(z.to(device=dev, dtype=b.dtype))
 
     import contextlib
     with (h._lock if h is not None else contextlib.nullcontext()), torch.cuda.device(dev):

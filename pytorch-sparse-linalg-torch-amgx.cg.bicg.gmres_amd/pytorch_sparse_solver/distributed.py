@@ -160,7 +160,7 @@ class HipOps:
 
     def make_matrix(self, crow, col_local, val, n_local, n_cols_ext, ch):
         h = ctypes.c_void_p()
-        crow, col_local, val = crow.contiguous(), col_local.to(crow.dtype).contiguous(), val.contiguous()
+        crow, col_local, val = self.k.aligned(crow), self.k.aligned(col_local.to(crow.dtype)), self.k.aligned(val)
         with torch.cuda.device(self.device):
             rc = self.L.hipk_csr_create_ex(ctypes.byref(h), n_local, n_cols_ext, val.numel(), crow.data_ptr(),
                                            col_local.data_ptr(), crow.element_size(), val.data_ptr(),
@@ -371,7 +371,8 @@ class DistProblem:
         self.n_local = part.n_local
         self.n_ext = part.n_local + self.plan.n_ghost
         self.nnz_local = int(val.numel())
-        self.b = b_local.contiguous()
+        from . import _hipk
+        self.b = _hipk.aligned(b_local)      # hipk_dist_*_solve refuses a b that is not 16-byte aligned: a view is copied
         self.A = ops.make_matrix(crow, self.plan.col_local, val, part.n_local, max(self.n_ext, 1), part.ch) \
             if part.n_local > 0 else None
         # algorithmic bytes of this rank's SpMV (SURVEY 8d formula on the local block)
@@ -512,7 +513,7 @@ def _native_plan(prob: DistProblem):
     plan.n_send, plan.n_ghost, plan.slab = pl.n_send, pl.n_ghost, pl.slab
     plan.send_idx_dev = pl.send_idx.data_ptr() if pl.n_send else None
     plan.ghost_src_dev = pl.ghost_src.data_ptr() if pl.n_ghost else None
-    send_off_d, dest_off_d = pl.send_off.to(dev).contiguous(), pl.dest_off.to(dev).contiguous()   # fused exchanges
+    send_off_d, dest_off_d = _hipk.aligned(pl.send_off.to(dev)), _hipk.aligned(pl.dest_off.to(dev))   # fused exchanges
     plan.send_off_dev, plan.dest_off_dev = send_off_d.data_ptr(), dest_off_d.data_ptr()
     sc = (ctypes.c_int32 * part.world)(*[int(v) for v in pl.send_splits])
     rc = (ctypes.c_int32 * part.world)(*[int(v) for v in pl.recv_splits])
@@ -831,7 +832,8 @@ class RowBlockCSR:
                 ops = HipOps(self.val.device)
             cls = self._problem_cls or DistProblem
             self._prob = cls(self.crow, self.col, self.val, b_local, self.part, ops, self.group)
-        self._prob.b = b_local.contiguous()
+        from . import _hipk
+        self._prob.b = _hipk.aligned(b_local)
         return self._prob
 
     def check_preconditioner(self, M, method: Optional[str] = None) -> None:
@@ -875,7 +877,7 @@ class RowBlockCSR:
         prob = self._prob if self._prob is not None else self.problem(v_local.to(torch.float64))
         if isinstance(prob.ops, HipOps):
             _need_native(prob, "the row-partitioned Chebyshev apply on device vectors")     # before any collective
-            return dist_cheb_apply(prob, M.degree, self._jacobi_ext(prob, M), M._coef, v_local.contiguous())
+            return dist_cheb_apply(prob, M.degree, self._jacobi_ext(prob, M), M._coef, prob.ops.k.aligned(v_local))
         n, ops = self.part.n_local, prob.ops
         dinv = M.dinv.to(torch.float64)
         c = lambda x: torch.tensor(x, dtype=torch.float64)       # noqa: E731

@@ -85,8 +85,9 @@ class BatchedCSR:
         self.shape = (self.batch, n, n)
         self.max_row_len = int((crow[1:] - crow[:-1]).max()) if n else 0
         # indices narrowed once (the kernels and the Jacobi diagonal read these)
-        self.crow32 = crow.to(torch.int32).contiguous()
-        self.col32 = col.to(torch.int32).contiguous()
+        from .. import _hipk
+        self.crow32 = _hipk.aligned(crow.to(torch.int32))
+        self.col32 = _hipk.aligned(col.to(torch.int32))
         self._kernel_values = None
 
     @property
@@ -115,8 +116,8 @@ class BatchedCSR:
 
     def system(self, s: int) -> torch.Tensor:
         """The CSR tensor A_s (its values a copy when row s of `values` does not start 16-byte aligned, as the single solves need)."""
-        v = self.values[s]
-        return torch.sparse_csr_tensor(self.crow, self.col, v.clone() if v.data_ptr() % 16 else v, size=(self.n, self.n))
+        from .. import _hipk
+        return torch.sparse_csr_tensor(self.crow, self.col, _hipk.aligned(self.values[s]), size=(self.n, self.n))
 
     def kernel_values(self) -> torch.Tensor:
         """`values` with 16-byte aligned rows: `values` itself, or a padded copy that is made again whenever `values` was written to
@@ -149,8 +150,8 @@ class BatchedJacobiPreconditioner:
 
     def system(self, s: int) -> JacobiPreconditioner:
         J = JacobiPreconditioner.__new__(JacobiPreconditioner)
-        d = self.dinv[s]
-        J.dinv = d.clone() if d.data_ptr() % 16 else d
+        from .. import _hipk
+        J.dinv = _hipk.aligned(self.dinv[s])
         J.shape = (self.shape[1], self.shape[2])
         return J
 
@@ -250,7 +251,7 @@ def _kernel_solve(kind, A: BatchedCSR, B, X0, tol, atol, maxiter, M, **gm):
         if not _aligned_rows(X):
             X = _pad_rows(X)
     if isinstance(M, BatchedBlockJacobiPreconditioner):
-        st = _hipk.solve_batch_bj(kind, A.n, A.nnz, A.crow32, A.col32, A.kernel_values(), M.binv.to(dt).contiguous(), M.block_size, BB, X,
+        st = _hipk.solve_batch_bj(kind, A.n, A.nnz, A.crow32, A.col32, A.kernel_values(), _hipk.aligned(M.binv.to(dt)), M.block_size, BB, X,
                                   tol=tol, atol=atol, maxiter=maxiter)
         return X.contiguous(), st
     dinv = None if M is None else _pad_rows(M.dinv.detach().to(dt))

@@ -50,14 +50,14 @@ def _block_solve(kind: str, A, B, X0, tol, atol, maxiter, M):
     _check_device_operands(A, B, X0)
     h = _hipk.handle_for(A)  # raises HipkError when libhipk.so is missing: no fallback
     work_dtype = torch.float64 if h.dtype == torch.float64 else torch.float32   # as _fast_solve
-    BB = B.detach().to(work_dtype).contiguous()
-    X = torch.zeros_like(BB) if X0 is None else X0.detach().to(work_dtype).clone().contiguous()
+    BB = _hipk.aligned(B.detach().to(work_dtype))
+    X = torch.zeros_like(BB) if X0 is None else _hipk.aligned(X0.detach().to(work_dtype).clone())
     dinv = None
     jac = _jacobi_of(M)
     if jac is not None:
         if jac.shape != tuple(A.shape):
             raise ValueError(f'preconditioner shape {jac.shape} does not match the operator {tuple(A.shape)}')
-        dinv = jac.dinv.detach().to(device=BB.device, dtype=work_dtype).contiguous()
+        dinv = _hipk.aligned(jac.dinv.detach().to(device=BB.device, dtype=work_dtype))
     st = _hipk.solve_multi(kind, h, dinv, BB, X, tol=tol, atol=atol, maxiter=maxiter)
     _set_stats(st)
     return X, torch.tensor([c.info for c in st.columns], dtype=torch.int64)

@@ -543,24 +543,24 @@ class AggregationMultigridPreconditioner:
             for l, lev in enumerate(self.levels):
                 vec = lambda: torch.empty(lev.n, dtype=dt, device=dev)
                 if lev.cinv is not None:         # the dense last level: nothing but its inverse
-                    s = {"n": lev.n, "cinv": lev.cinv.to(device=dev, dtype=dt).contiguous().reshape(-1), "ld": lev.ld}
+                    s = {"n": lev.n, "cinv": _hipk.aligned(lev.cinv.to(device=dev, dtype=dt)).reshape(-1), "ld": lev.ld}
                     if l and l <= tf:
                         s["r"], s["z"] = vec(), vec()
                     st.append(s)
                     continue
-                s = {"dinv": lev.dinv.to(device=dev, dtype=dt).contiguous()}
+                s = {"dinv": _hipk.aligned(lev.dinv.to(device=dev, dtype=dt))}
                 if l and l <= tf:
                     s["r"], s["z"] = vec(), vec()
                 if lev.agg is not None:          # the transfers' index arrays: agg, and the members aggregate by aggregate
                     agg = lev.agg.to(dev)
                     counts = torch.bincount(agg, minlength=self.levels[l + 1].n)
-                    s["agg"] = agg.to(torch.int32).contiguous()
-                    s["amem"] = torch.sort(agg, stable=True)[1].to(torch.int32).contiguous()
-                    s["aptr"] = torch.cat([counts.new_zeros(1), torch.cumsum(counts, 0)]).to(torch.int32).contiguous()
+                    s["agg"] = _hipk.aligned(agg.to(torch.int32))
+                    s["amem"] = _hipk.aligned(torch.sort(agg, stable=True)[1].to(torch.int32))
+                    s["aptr"] = _hipk.aligned(torch.cat([counts.new_zeros(1), torch.cumsum(counts, 0)]).to(torch.int32))
                 if l >= tf:          # a level of the tail kernel: int32 CSR arrays for its descriptor
                     c = lev.csr
-                    s.update(crow=c.crow_indices().to(torch.int32).contiguous(), col=c.col_indices().to(torch.int32).contiguous(),
-                             val=c.values().contiguous(), dims=lev.dims, max_row=lev.max_row, c0=lev.c0, c1=lev.c1, c2=lev.c2)
+                    s.update(crow=_hipk.aligned(c.crow_indices().to(torch.int32)), col=_hipk.aligned(c.col_indices().to(torch.int32)),
+                             val=_hipk.aligned(c.values()), dims=lev.dims, max_row=lev.max_row, c0=lev.c0, c1=lev.c1, c2=lev.c2)
                 elif l < len(self.levels) - 1:
                     c = lev.csr
                     s["h"] = _hipk.handle_for(self._A) if l == 0 else \
@@ -581,8 +581,7 @@ class AggregationMultigridPreconditioner:
         from .. import _hipk
         st, levels = self._dev_state(), self.levels
         L = len(levels) - 1 if self.tail_from is None else self.tail_from      # the last level the launches reach
-        if not v.is_contiguous() or v.data_ptr() % 16:
-            v = v.contiguous().clone()
+        v = _hipk.aligned(v)
         out = torch.empty_like(v)
         r = lambda l: v if l == 0 else st[l]["r"]
         z = lambda l: out if l == 0 else st[l]["z"]

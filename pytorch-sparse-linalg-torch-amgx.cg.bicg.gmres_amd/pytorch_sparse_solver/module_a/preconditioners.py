@@ -137,7 +137,7 @@ class BlockJacobiPreconditioner:
             from .. import _hipk
             if binv is not self.binv:
                 self.binv = binv          # keep the converted copy: the solver calls with one dtype
-            return _hipk.block_jacobi_apply(binv, bs, v.contiguous())
+            return _hipk.block_jacobi_apply(binv, bs, _hipk.aligned(v))
         nb = binv.shape[0]
         vp = torch.zeros(nb * bs, dtype=v.dtype, device=v.device)
         vp[:n] = v
@@ -333,7 +333,7 @@ class ChebyshevPreconditioner:
                 if not self._A.is_cuda:
                     raise ValueError("ChebyshevPreconditioner of a CPU matrix applied to a device vector")
                 h = _hipk.handle_for(self._A)
-                self._dev = (h, self.dinv.to(device=h.device, dtype=h.dtype).contiguous())
+                self._dev = (h, _hipk.aligned(self.dinv.to(device=h.device, dtype=h.dtype)))
             h, dinv = self._dev
             if v.dtype != h.dtype or v.device != h.device:
                 raise ValueError(f"ChebyshevPreconditioner of a {h.dtype} matrix on {h.device} applied to a {v.dtype} vector on "

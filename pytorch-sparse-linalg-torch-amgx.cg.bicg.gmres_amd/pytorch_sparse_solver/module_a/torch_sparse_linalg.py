@@ -149,12 +149,12 @@ def _fast_solve(method: str, A, b, x0, tol, atol, maxiter, restart=20, solve_met
     # fp64 is forced exactly like the reference (TSL:979-980). fp32 storage is an
     # extension, taken only when A itself is fp32 (the reference raises there).
     work_dtype = torch.float64 if h.dtype == torch.float64 else torch.float32
-    bb = b.detach().to(work_dtype).contiguous()
-    x = torch.zeros_like(bb) if x0 is None else x0.detach().to(work_dtype).clone().contiguous()
+    bb = _hipk.aligned(b.detach().to(work_dtype))
+    x = torch.zeros_like(bb) if x0 is None else _hipk.aligned(x0.detach().to(work_dtype).clone())
     if jacobi is not None:  # cg / gmres with M = diag(dinv): hipk_pcg_solve / hipk_pgmres_solve
         if jacobi.shape != tuple(A.shape):
             raise ValueError(f'preconditioner shape {jacobi.shape} does not match the operator {tuple(A.shape)}')
-        dinv = jacobi.dinv.detach().to(device=bb.device, dtype=work_dtype).contiguous()
+        dinv = _hipk.aligned(jacobi.dinv.detach().to(device=bb.device, dtype=work_dtype))
         if method == 'gmres':
             st = _hipk.solve_pgmres(h, dinv, bb, x, tol=tol, atol=atol, maxiter=maxiter, restart=restart,
                                     solve_method=solve_method)
@@ -182,8 +182,8 @@ def _fast_solve_matrix_free(A, b, x0, tol, atol, maxiter, M):
 
     if x0 is not None and x0.shape != b.shape:
         raise ValueError(f'arrays in x0 and b must have matching shapes: {x0.shape} vs {b.shape}')
-    bb = b.detach().to(torch.float64).contiguous()
-    x = torch.zeros_like(bb) if x0 is None else x0.detach().to(torch.float64).clone().contiguous()
+    bb = _hipk.aligned(b.detach().to(torch.float64))
+    x = torch.zeros_like(bb) if x0 is None else _hipk.aligned(x0.detach().to(torch.float64).clone())
     M_fn = None if (M is None or M is _identity) else _normalize_matvec(M)
     st = _hipk.solve_cg_stepwise(None, _normalize_matvec(A), M_fn, bb, x, tol=tol, atol=atol, maxiter=maxiter)
     _set_stats(st)
@@ -200,15 +200,15 @@ def _fast_solve_matrix_free_c(kind, A, b, x0, tol, atol, maxiter, M, restart=20,
         raise ValueError(f'arrays in x0 and b must have matching shapes: {x0.shape} vs {b.shape}')
     if kind == 'gmres' and solve_method not in ('batched', 'incremental'):
         raise ValueError(f"Unsupported solve_method: {solve_method}")
-    bb = b.detach().to(torch.float64).contiguous()
-    x = torch.zeros_like(bb) if x0 is None else x0.detach().to(torch.float64).clone().contiguous()
+    bb = _hipk.aligned(b.detach().to(torch.float64))
+    x = torch.zeros_like(bb) if x0 is None else _hipk.aligned(x0.detach().to(torch.float64).clone())
     A_fn = _normalize_matvec(A)
     jac = _jacobi_of(M)
     if jac is not None:
         if jac.shape != (bb.numel(), bb.numel()):
             raise ValueError(f'preconditioner shape {jac.shape} does not match the operator {(bb.numel(), bb.numel())}')
         st = _hipk.solve_matrix_free(kind, A_fn, bb, x, tol=tol, atol=atol, maxiter=maxiter, restart=restart,
-                                     solve_method=solve_method, dinv=jac.dinv.detach().to(device=bb.device, dtype=torch.float64).contiguous())
+                                     solve_method=solve_method, dinv=_hipk.aligned(jac.dinv.detach().to(device=bb.device, dtype=torch.float64)))
     else:
         M_fn = None if (M is None or M is _identity) else _normalize_matvec(M)
         st = _hipk.solve_matrix_free(kind, A_fn, bb, x, tol=tol, atol=atol, maxiter=maxiter, restart=restart,
@@ -231,8 +231,8 @@ def _fast_solve_callable(kind, A, b, x0, tol, atol, maxiter, M, restart=20, solv
         raise RuntimeError(f'size mismatch, got input ({A.shape[0]}x{A.shape[1]}), vec ({b.numel()})')
     h = _hipk.handle_for(A)
     work_dtype = torch.float64 if h.dtype == torch.float64 else torch.float32
-    bb = b.detach().to(work_dtype).contiguous()
-    x = torch.zeros_like(bb) if x0 is None else x0.detach().to(work_dtype).clone().contiguous()
+    bb = _hipk.aligned(b.detach().to(work_dtype))
+    x = torch.zeros_like(bb) if x0 is None else _hipk.aligned(x0.detach().to(work_dtype).clone())
     if kind == 'gmres':
         st = _hipk.solve_gmres_callable(h, _normalize_matvec(M), bb, x, tol=tol, atol=atol, maxiter=maxiter,
                                         restart=restart, solve_method=solve_method)

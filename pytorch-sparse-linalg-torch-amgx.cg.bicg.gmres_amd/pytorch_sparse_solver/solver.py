@@ -131,7 +131,7 @@ class SparseSolver:
         elif A.is_cuda and A.layout in (torch.sparse_csr, torch.strided, torch.sparse_coo) and x.ndim == 1 \
                 and not torch.is_complex(A) and A.dtype == x.dtype and A.dtype in (torch.float64, torch.float32):
             from . import _hipk
-            Ax = _hipk.spmv(_hipk.handle_for(A), x.detach().contiguous())
+            Ax = _hipk.spmv(_hipk.handle_for(A), _hipk.aligned(x.detach()))
         elif A.is_sparse:
             Ax = torch.sparse.mm(A, x.unsqueeze(-1)).squeeze(-1)
         else:

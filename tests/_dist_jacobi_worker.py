@@ -158,6 +158,12 @@ def hip_task(a, rank, world):
     cls = FusedMailbox if a.get("comm") == "fused" else StagedCounting
     Arb = pss.RowBlockCSR.from_global_csr(A.to(dev), ops=HipOps(dev), problem_cls=cls)
     b_loc = b[r0:r1].to(dev)
+    b_owner = None
+    if a.get("b_layout") == "off1":    # optional: this rank's b as a contiguous view one element off a 16-byte boundary, in guards
+        b_owner = torch.full((b_loc.numel() + 129,), -3.5e203, dtype=torch.float64, device=dev)
+        b_owner[65:65 + b_loc.numel()] = b_loc
+        b_snap = b_owner.clone()
+        b_loc = b_owner[65:65 + r1 - r0]
     P = JacobiPreconditioner(Arb) if a["pmode"] == "local" else JacobiPreconditioner(A.to(dev))
     method = "gmres" if solver.startswith("gmres") else solver
     kw = {"tol": tol}
@@ -206,7 +212,9 @@ def hip_task(a, rank, world):
     Ad, bd = A.to(dev), b.to(dev)
     xs, info_s = getattr(module_a, method)(Ad, bd, M=JacobiPreconditioner(Ad), **kw)
     ss = module_a.get_last_stats()
-    return {"bitwise_equal": bool(np.array_equal(x, ref.x)), "single_equal": bool(np.array_equal(x, xs.cpu().numpy())),
+    layout = {} if b_owner is None else {"b_mod16": b_loc.data_ptr() % 16, "b_owner_unchanged": bool(torch.equal(b_owner, b_snap))}
+    return {**layout,
+            "bitwise_equal": bool(np.array_equal(x, ref.x)), "single_equal": bool(np.array_equal(x, xs.cpu().numpy())),
             "single_vs_oracle": bool(np.array_equal(ref.x, xs.cpu().numpy())),
             "info": [p[2] for p in pieces], "ref_info": ref.info, "single_info": int(info_s),
             "iterations": [p[3] for p in pieces], "ref_iterations": ref.iterations, "single_iterations": ss.iterations,
