@@ -17,9 +17,6 @@
 #include "hipk_common.h"
 #include "hipk_mg_tail.h"
 
-// the tail kernel's envelope: HIPK_MG_TAIL_MAX_N / HIPK_MG_TAIL_MAX_ROW of hipk_mg_tail.h, and
-#define HIPK_MG_TAIL_MAX_LEVELS 16
-
 struct hipk_mg_dims {
     int64_t n0, n1, n2;   // the fine level
     int64_t m0, m1, m2;   // the coarse level
@@ -199,69 +196,17 @@ extern "C" int hipk_mg_diag(int64_t n, double scale, const void *dinv, const voi
 
 // ------------------------------------------------------------------------------------------------------------- the tail kernel
 // One launch, ONE 256-thread workgroup: V(l, .) for the run of small levels j = 0 .. nlev - 1 of the descriptor array (level
-// nlev - 1 has one unknown), down and back up -- what the launch sequence spends 2 degree + 7 launches per level on.  The steps
-// (staging, residual, Chebyshev recurrence), the slab layout and the rules they keep are hipk_mg_tail.h's, shared with the tail
-// kernel of the index-array levels (hipk_mg_graph.hip); the result is bit for bit the launch sequence's.
+// nlev - 1 has one unknown), down and back up -- what the launch sequence spends 2 degree + 7 launches per level on.  The steps,
+// the walks, the slab layout and the rules they keep are hipk_mg_tail.h's, shared with the tail kernels of the index-array levels
+// (hipk_mg_graph.hip, hipk_mg_dense.hip); the box arithmetic of the two transfers is its hipk_mg_box_xf.  The result is bit for
+// bit the launch sequence's.
 template <typename T>
 __global__ __launch_bounds__(HIPK_THREADS) void hipk_mg_tail_kernel(const hipk_mg_level *__restrict__ lv, int nlev, int m, T omega, T scale,
                                                                     const T *rin, T *zout, T *slab) {
     __shared__ T xs[HIPK_MG_TAIL_MAX_N];
-    const int t = threadIdx.x;
-    for (int j = 0; j + 1 < nlev; ++j) {   // down: steps 1 - 3
-        const hipk_mg_level &L = lv[j];
-        const hipk_mg_vecs<T> v = hipk_mg_level_vecs<T>(lv, j, rin, zout, slab);
-        T *rc = hipk_mg_level_vecs<T>(lv, j + 1, rin, zout, slab).r;
-        hipk_mg_smooth<T>(L, m, v.r, v.z, v.w, xs);
-        hipk_mg_residual<T>(L, v.z, v.r, v.t, xs);
-        hipk_mg_stage(L.n, v.t, xs);
-        const int n0 = L.n0, n1 = L.n1, n2 = L.n2, m1 = (n1 + 1) >> 1, m2 = (n2 + 1) >> 1;
-        const int nc = lv[j + 1].n;
-        for (int I = t; I < nc; I += HIPK_THREADS) {
-            const int I2 = I % m2, q = I / m2, I1 = q % m1, I0 = q / m1;
-            const bool has2 = 2 * I2 + 1 < n2;
-            T s = (T)0;
-#pragma unroll
-            for (int d0 = 0; d0 < 2; ++d0) {
-#pragma unroll
-                for (int d1 = 0; d1 < 2; ++d1) {
-                    const int i0 = 2 * I0 + d0, i1 = 2 * I1 + d1;
-                    if (i0 < n0 && i1 < n1) {
-                        const int f = (i0 * n1 + i1) * n2 + 2 * I2;
-                        s = (d0 == 0 && d1 == 0) ? xs[f] : s + xs[f];
-                        if (has2) s = s + xs[f + 1];
-                    }
-                }
-            }
-            rc[I] = s;
-        }
-        __syncthreads();
-    }
-    {   // the level with one unknown
-        const hipk_mg_level &L = lv[nlev - 1];
-        const hipk_mg_vecs<T> v = hipk_mg_level_vecs<T>(lv, nlev - 1, rin, zout, slab);
-        if (t == 0) {
-            const T zz = ((const T *)L.dinv)[0] * v.r[0];
-            v.z[0] = (nlev == 1) ? scale * zz : zz;
-        }
-    }
-    for (int j = nlev - 2; j >= 0; --j) {   // up: steps 5 - 6
-        const hipk_mg_level &L = lv[j];
-        const hipk_mg_vecs<T> v = hipk_mg_level_vecs<T>(lv, j, rin, zout, slab);
-        const T *e = hipk_mg_level_vecs<T>(lv, j + 1, rin, zout, slab).z;
-        hipk_mg_stage(lv[j + 1].n, e, xs);
-        const int n1 = L.n1, n2 = L.n2, m1 = (n1 + 1) >> 1, m2 = (n2 + 1) >> 1;
-        for (int row = t; row < L.n; row += HIPK_THREADS) {
-            const int i2 = row % n2, q = row / n2, i1 = q % n1, i0 = q / n1;
-            v.z[row] = v.z[row] + (omega * xs[((i0 >> 1) * m1 + (i1 >> 1)) * m2 + (i2 >> 1)]);
-        }
-        __syncthreads();
-        hipk_mg_residual<T>(L, v.z, v.r, v.t, xs);
-        hipk_mg_smooth<T>(L, m, v.t, v.d, v.w, xs);
-        for (int row = t; row < L.n; row += HIPK_THREADS) {
-            const T zz = v.z[row] + v.d[row];
-            v.z[row] = (j == 0) ? scale * zz : zz;
-        }
-    }
+    hipk_mg_walk_down<T, hipk_mg_level, hipk_mg_box_xf>(lv, nlev, m, rin, zout, slab, xs);
+    hipk_mg_last_diag<T>(lv, nlev, scale, rin, zout, slab);   // the level with one unknown
+    hipk_mg_walk_up<T, hipk_mg_level, hipk_mg_box_xf>(lv, nlev, m, omega, scale, rin, zout, slab, xs);
 }
 
 static int hipk_mg_tail_check(const hipk_mg_level *lv, int nlev, int degree, int dtype) {
@@ -284,25 +229,15 @@ static int hipk_mg_tail_check(const hipk_mg_level *lv, int nlev, int degree, int
 }
 
 extern "C" size_t hipk_mg_tail_work_bytes(const hipk_mg_level *levels_host, int nlev, int dtype) {
-    if (!levels_host || nlev < 1 || nlev > HIPK_MG_TAIL_MAX_LEVELS) return 0;
-    return hipk_mg_slab_bytes(levels_host, nlev, dtype);
+    return hipk_mg_work_bytes(levels_host, nlev, HIPK_MG_TAIL_MAX_LEVELS, dtype);
 }
 
 extern "C" int hipk_mg_tail_apply(const hipk_mg_level *levels_host, const void *levels_dev, int nlev, int degree, double omega,
                                   double scale, const void *r, void *z, int dtype, void *work, size_t work_bytes, hipk_stream_t stream) {
     HIPK_TRY(hipk_mg_tail_check(levels_host, nlev, degree, dtype));
-    HIPK_REQUIRE(levels_dev && r && z && work, HIPK_ERR_ARG, "null argument");
-    HIPK_REQUIRE(hipk_aligned16(r) && hipk_aligned16(z) && hipk_aligned16(levels_dev) && (((uintptr_t)work) & 255u) == 0, HIPK_ERR_ALIGN,
-                 "r, z and the level blob must be 16-byte aligned, work 256-byte aligned");
-    HIPK_REQUIRE(r != z, HIPK_ERR_ARG, "r and z must be distinct");
-    HIPK_REQUIRE(work_bytes >= hipk_mg_tail_work_bytes(levels_host, nlev, dtype), HIPK_ERR_WORKSPACE, "work buffer too small");
-    const hipk_mg_level *lv = (const hipk_mg_level *)levels_dev;
-    if (dtype == HIPK_F64)
-        hipk_mg_tail_kernel<double><<<1, HIPK_THREADS, 0, (hipStream_t)stream>>>(lv, nlev, degree, omega, scale, (const double *)r, (double *)z,
-                                                                                 (double *)work);
-    else
-        hipk_mg_tail_kernel<float><<<1, HIPK_THREADS, 0, (hipStream_t)stream>>>(lv, nlev, degree, (float)omega, (float)scale, (const float *)r,
-                                                                                (float *)z, (float *)work);
-    HIPK_CHECK_HIP(hipGetLastError());
-    return HIPK_OK;
+    return hipk_mg_tail_launch(levels_host, levels_dev, nlev, HIPK_MG_TAIL_MAX_LEVELS, r, z, dtype, work, work_bytes, [&](auto tag) {
+        typedef decltype(tag) T;
+        hipk_mg_tail_kernel<T><<<1, HIPK_THREADS, 0, (hipStream_t)stream>>>((const hipk_mg_level *)levels_dev, nlev, degree, (T)omega, (T)scale,
+                                                                            (const T *)r, (T *)z, (T *)work);
+    });
 }

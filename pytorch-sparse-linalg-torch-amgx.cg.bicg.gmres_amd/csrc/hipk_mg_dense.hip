@@ -13,7 +13,7 @@
 // staged in LDS, the p_q meet in LDS behind a barrier and the thread that owns row i adds them in ascending q.  No atomics, no
 // hand-off between workgroups; nothing at or beyond n is read or written in r and z.
 #include "hipk_common.h"
-#include "hipk_mg_gwalk.h"
+#include "hipk_mg_tail.h"
 
 #define HIPK_MG_DENSE_MAX_N 2048
 #define HIPK_MG_DENSE_TAIL_N 512
@@ -82,7 +82,7 @@ __global__ __launch_bounds__(HIPK_THREADS) void hipk_mg_gtail_dense_kernel(const
     __shared__ T xs[HIPK_MG_TAIL_MAX_N];
     __shared__ T rs[HIPK_MG_DENSE_TAIL_N];
     static_assert(HIPK_MG_DENSE_TAIL_N * (HIPK_MG_DENSE_TAIL_N / HIPK_MG_DENSE_SEG) <= HIPK_MG_TAIL_MAX_N, "the partials must fit xs");
-    hipk_mg_gwalk_down<T>(lv, nlev, m, rin, zout, slab, xs);
+    hipk_mg_walk_down<T, hipk_mg_glevel, hipk_mg_index_xf>(lv, nlev, m, rin, zout, slab, xs);
     {
         const int n = lv[nlev - 1].n;
         const hipk_mg_vecs<T> v = hipk_mg_level_vecs<T>(lv, nlev - 1, rin, zout, slab);
@@ -90,7 +90,7 @@ __global__ __launch_bounds__(HIPK_THREADS) void hipk_mg_gtail_dense_kernel(const
         hipk_mg_dense_rows<T>(n, ld, cinv, 0, n, nlev == 1, scale, rs, xs, v.z);
         __syncthreads();
     }
-    hipk_mg_gwalk_up<T>(lv, nlev, m, omega, scale, rin, zout, slab, xs);
+    hipk_mg_walk_up<T, hipk_mg_glevel, hipk_mg_index_xf>(lv, nlev, m, omega, scale, rin, zout, slab, xs);
 }
 
 static int hipk_mg_dense_check(int64_t n, int64_t max_n, int64_t ld, const void *cinv, int dtype, const char *envelope) {
@@ -121,39 +121,20 @@ extern "C" int hipk_mg_dense_apply(int64_t n, int64_t ld, const void *cinv, doub
     return HIPK_OK;
 }
 
-static int hipk_mg_gtail_dense_check(const hipk_mg_glevel *lv, int nlev, int degree, int dtype) {
-    HIPK_REQUIRE(lv && nlev >= 1, HIPK_ERR_ARG, "at least one level");
-    HIPK_REQUIRE(nlev <= HIPK_MG_GTAIL_MAX_LEVELS, HIPK_ERR_UNSUPPORTED, "hipk_mg_gtail_dense_apply takes at most 32 levels");
-    HIPK_REQUIRE(degree >= 1 && degree <= 32, HIPK_ERR_ARG, "degree must be in [1, 32]");
-    HIPK_REQUIRE(dtype == HIPK_F64 || dtype == HIPK_F32, HIPK_ERR_UNSUPPORTED, "dtype must be HIPK_F32 or HIPK_F64");
-    HIPK_TRY(hipk_mg_gtail_check_levels(lv, nlev - 1, nlev,
-                                        "hipk_mg_gtail_dense_apply takes sparse levels of at most 4096 unknowns and 32 stored entries per row"));
-    return HIPK_OK;
-}
-
 extern "C" size_t hipk_mg_gtail_dense_work_bytes(const hipk_mg_glevel *levels_host, int nlev, int dtype) {
-    if (!levels_host || nlev < 1 || nlev > HIPK_MG_GTAIL_MAX_LEVELS) return 0;
-    return hipk_mg_slab_bytes(levels_host, nlev, dtype);
+    return hipk_mg_work_bytes(levels_host, nlev, HIPK_MG_GTAIL_MAX_LEVELS, dtype);
 }
 
 extern "C" int hipk_mg_gtail_dense_apply(const hipk_mg_glevel *levels_host, const void *levels_dev, int nlev, int degree, double omega, double scale,
                                          const void *cinv, int64_t ld, const void *r, void *z, int dtype, void *work, size_t work_bytes,
                                          hipk_stream_t stream) {
-    HIPK_TRY(hipk_mg_gtail_dense_check(levels_host, nlev, degree, dtype));
+    HIPK_TRY(hipk_mg_gtail_check(levels_host, nlev - 1, nlev, degree, dtype, "hipk_mg_gtail_dense_apply takes at most 32 levels",
+                                 "hipk_mg_gtail_dense_apply takes sparse levels of at most 4096 unknowns and 32 stored entries per row"));
     HIPK_TRY(hipk_mg_dense_check(levels_host[nlev - 1].n, HIPK_MG_DENSE_TAIL_N, ld, cinv, dtype,
                                  "hipk_mg_gtail_dense_apply takes a dense level of at most 512 unknowns"));
-    HIPK_REQUIRE(levels_dev && r && z && work, HIPK_ERR_ARG, "null argument");
-    HIPK_REQUIRE(hipk_aligned16(r) && hipk_aligned16(z) && hipk_aligned16(levels_dev) && (((uintptr_t)work) & 255u) == 0, HIPK_ERR_ALIGN,
-                 "r, z and the level blob must be 16-byte aligned, work 256-byte aligned");
-    HIPK_REQUIRE(r != z, HIPK_ERR_ARG, "r and z must be distinct");
-    HIPK_REQUIRE(work_bytes >= hipk_mg_gtail_dense_work_bytes(levels_host, nlev, dtype), HIPK_ERR_WORKSPACE, "work buffer too small");
-    const hipk_mg_glevel *lv = (const hipk_mg_glevel *)levels_dev;
-    if (dtype == HIPK_F64)
-        hipk_mg_gtail_dense_kernel<double><<<1, HIPK_THREADS, 0, (hipStream_t)stream>>>(lv, nlev, degree, omega, scale, (const double *)cinv, (int)ld,
-                                                                                        (const double *)r, (double *)z, (double *)work);
-    else
-        hipk_mg_gtail_dense_kernel<float><<<1, HIPK_THREADS, 0, (hipStream_t)stream>>>(lv, nlev, degree, (float)omega, (float)scale, (const float *)cinv,
-                                                                                       (int)ld, (const float *)r, (float *)z, (float *)work);
-    HIPK_CHECK_HIP(hipGetLastError());
-    return HIPK_OK;
+    return hipk_mg_tail_launch(levels_host, levels_dev, nlev, HIPK_MG_GTAIL_MAX_LEVELS, r, z, dtype, work, work_bytes, [&](auto tag) {
+        typedef decltype(tag) T;
+        hipk_mg_gtail_dense_kernel<T><<<1, HIPK_THREADS, 0, (hipStream_t)stream>>>((const hipk_mg_glevel *)levels_dev, nlev, degree, (T)omega, (T)scale,
+                                                                                   (const T *)cinv, (int)ld, (const T *)r, (T *)z, (T *)work);
+    });
 }

@@ -12,7 +12,7 @@
 // -ffp-contract=off), no atomics, no hand-off between workgroups.
 #include "hipk_blas1.h"
 #include "hipk_common.h"
-#include "hipk_mg_gwalk.h"
+#include "hipk_mg_tail.h"
 
 // rc[I] = t[first member], then + t[member] over the others in ascending fine index.  A thread owns VEC consecutive aggregates:
 // their member lists are one contiguous run of amem.
@@ -108,56 +108,28 @@ extern "C" int hipk_mg_prolong_add_agg(int64_t n, int64_t nc, const int32_t *agg
 
 // ------------------------------------------------------------------------------------------------------------- the tail kernel
 // hipk_mg_tail_kernel (hipk_mg.hip) for index-array levels: one launch, ONE 256-thread workgroup walks levels j = 0 .. nlev - 1 down
-// and back up with the steps, the slab and the rules of hipk_mg_tail.h; the two walks are hipk_mg_gwalk.h's, which
-// hipk_mg_gtail_dense_kernel (hipk_mg_dense.hip) shares.  The last level is z = dinv r on any number of rows.  Bit for bit the
-// launch sequence's result.
+// and back up with the steps, the walks, the slab and the rules of hipk_mg_tail.h; the two transfers are its hipk_mg_index_xf.
+// The last level is z = dinv r on any number of rows.  Bit for bit the launch sequence's result.
 template <typename T>
 __global__ __launch_bounds__(HIPK_THREADS) void hipk_mg_gtail_kernel(const hipk_mg_glevel *__restrict__ lv, int nlev, int m, T omega, T scale,
                                                                      const T *rin, T *zout, T *slab) {
     __shared__ T xs[HIPK_MG_TAIL_MAX_N];
-    const int t = threadIdx.x;
-    hipk_mg_gwalk_down<T>(lv, nlev, m, rin, zout, slab, xs);
-    {   // the last level: no off-diagonal entry is left
-        const hipk_mg_glevel &L = lv[nlev - 1];
-        const hipk_mg_vecs<T> v = hipk_mg_level_vecs<T>(lv, nlev - 1, rin, zout, slab);
-        const T *__restrict__ dinv = (const T *)L.dinv;
-        for (int row = t; row < L.n; row += HIPK_THREADS) {
-            const T zz = dinv[row] * v.r[row];
-            v.z[row] = (nlev == 1) ? scale * zz : zz;
-        }
-    }
-    hipk_mg_gwalk_up<T>(lv, nlev, m, omega, scale, rin, zout, slab, xs);
-}
-
-static int hipk_mg_gtail_check(const hipk_mg_glevel *lv, int nlev, int degree, int dtype) {
-    HIPK_REQUIRE(lv && nlev >= 1, HIPK_ERR_ARG, "at least one level");
-    HIPK_REQUIRE(nlev <= HIPK_MG_GTAIL_MAX_LEVELS, HIPK_ERR_UNSUPPORTED, "hipk_mg_gtail_apply takes at most 32 levels");
-    HIPK_REQUIRE(degree >= 1 && degree <= 32, HIPK_ERR_ARG, "degree must be in [1, 32]");
-    HIPK_REQUIRE(dtype == HIPK_F64 || dtype == HIPK_F32, HIPK_ERR_UNSUPPORTED, "dtype must be HIPK_F32 or HIPK_F64");
-    HIPK_TRY(hipk_mg_gtail_check_levels(lv, nlev, nlev, "hipk_mg_gtail_apply takes levels of at most 4096 unknowns and 32 stored entries per row"));
-    return HIPK_OK;
+    hipk_mg_walk_down<T, hipk_mg_glevel, hipk_mg_index_xf>(lv, nlev, m, rin, zout, slab, xs);
+    hipk_mg_last_diag<T>(lv, nlev, scale, rin, zout, slab);
+    hipk_mg_walk_up<T, hipk_mg_glevel, hipk_mg_index_xf>(lv, nlev, m, omega, scale, rin, zout, slab, xs);
 }
 
 extern "C" size_t hipk_mg_gtail_work_bytes(const hipk_mg_glevel *levels_host, int nlev, int dtype) {
-    if (!levels_host || nlev < 1 || nlev > HIPK_MG_GTAIL_MAX_LEVELS) return 0;
-    return hipk_mg_slab_bytes(levels_host, nlev, dtype);
+    return hipk_mg_work_bytes(levels_host, nlev, HIPK_MG_GTAIL_MAX_LEVELS, dtype);
 }
 
 extern "C" int hipk_mg_gtail_apply(const hipk_mg_glevel *levels_host, const void *levels_dev, int nlev, int degree, double omega,
                                    double scale, const void *r, void *z, int dtype, void *work, size_t work_bytes, hipk_stream_t stream) {
-    HIPK_TRY(hipk_mg_gtail_check(levels_host, nlev, degree, dtype));
-    HIPK_REQUIRE(levels_dev && r && z && work, HIPK_ERR_ARG, "null argument");
-    HIPK_REQUIRE(hipk_aligned16(r) && hipk_aligned16(z) && hipk_aligned16(levels_dev) && (((uintptr_t)work) & 255u) == 0, HIPK_ERR_ALIGN,
-                 "r, z and the level blob must be 16-byte aligned, work 256-byte aligned");
-    HIPK_REQUIRE(r != z, HIPK_ERR_ARG, "r and z must be distinct");
-    HIPK_REQUIRE(work_bytes >= hipk_mg_gtail_work_bytes(levels_host, nlev, dtype), HIPK_ERR_WORKSPACE, "work buffer too small");
-    const hipk_mg_glevel *lv = (const hipk_mg_glevel *)levels_dev;
-    if (dtype == HIPK_F64)
-        hipk_mg_gtail_kernel<double><<<1, HIPK_THREADS, 0, (hipStream_t)stream>>>(lv, nlev, degree, omega, scale, (const double *)r, (double *)z,
-                                                                                  (double *)work);
-    else
-        hipk_mg_gtail_kernel<float><<<1, HIPK_THREADS, 0, (hipStream_t)stream>>>(lv, nlev, degree, (float)omega, (float)scale, (const float *)r,
-                                                                                 (float *)z, (float *)work);
-    HIPK_CHECK_HIP(hipGetLastError());
-    return HIPK_OK;
+    HIPK_TRY(hipk_mg_gtail_check(levels_host, nlev, nlev, degree, dtype, "hipk_mg_gtail_apply takes at most 32 levels",
+                                 "hipk_mg_gtail_apply takes levels of at most 4096 unknowns and 32 stored entries per row"));
+    return hipk_mg_tail_launch(levels_host, levels_dev, nlev, HIPK_MG_GTAIL_MAX_LEVELS, r, z, dtype, work, work_bytes, [&](auto tag) {
+        typedef decltype(tag) T;
+        hipk_mg_gtail_kernel<T><<<1, HIPK_THREADS, 0, (hipStream_t)stream>>>((const hipk_mg_glevel *)levels_dev, nlev, degree, (T)omega, (T)scale,
+                                                                             (const T *)r, (T *)z, (T *)work);
+    });
 }

@@ -769,48 +769,71 @@ MG_TAIL_MAX_N = 4096      # the envelope of hipk_mg_tail_apply: unknowns per lev
 MG_TAIL_MAX_ROW = 32      # ... and stored entries per row (the batch kernels')
 
 
-class MgTail:
-    """The descriptors of hipk_mg_tail_apply for a run of levels, on the host and as one device blob, and the tensors they point
-    into.  `levels`: per level a dict with int32 `crow` / `col`, `val`, `dinv` (contiguous device tensors of one dtype), `dims`
-    (2 or 3 entries), `max_row` and the smoother's `c0`, `c1`, `c2` (None on the last level, which has one unknown)."""
+class _MgDescriptors:
+    """What `MgTail` and `MgGTail` share: the descriptors of a run of levels on the host (`host`) and as one device blob (`blob`),
+    the tensors they point into, and `work_bytes` of the entry point that takes them."""
 
-    def __init__(self, levels, degree: int):
-        self.nlev, self.degree = len(levels), int(degree)
-        self.dtype, self.device = levels[0]["val"].dtype, levels[0]["val"].device
-        self.host = (MgLevel * self.nlev)()
+    def _build(self, struct, levels, nsparse: int, degree: int, dtype, device, work_bytes: str) -> None:
+        """Levels [0, nsparse) are dicts with int32 `crow` / `col`, `val`, `dinv` (contiguous device tensors of one dtype),
+        `max_row` and the smoother's `c0`, `c1`, `c2` (absent or None where there is no smoother): the fields both descriptor
+        structs have.  A level past them is a dict of which only `n` is read.  `self._level(j, d, lev, nc)` then fills what only
+        one kind of level has; `nc` is the next level's size, None on the last."""
+        self.nlev, self.degree, self.dtype, self.device = len(levels), int(degree), dtype, device
+        sizes = [int(lev["dinv"].numel()) for lev in levels[:nsparse]] + [int(lev["n"]) for lev in levels[nsparse:]]
+        self.host = (struct * self.nlev)()
         self._keep = []
-        for d, lev in zip(self.host, levels):
+        for j, (d, lev) in enumerate(zip(self.host, levels)):
+            d.n = sizes[j]
+            if j >= nsparse:
+                continue
             for name in ("crow", "col", "val", "dinv"):
                 t = lev[name]
-                assert t.is_cuda and t.is_contiguous() and t.device == self.device
-                assert t.dtype == (torch.int32 if name in ("crow", "col") else self.dtype)
+                assert t.is_cuda and t.is_contiguous() and t.device == device
+                assert t.dtype == (torch.int32 if name in ("crow", "col") else dtype)
                 self._keep.append(t)
                 setattr(d, name, t.data_ptr())
-            d.n0, d.n1, d.n2 = _grid3(lev["dims"])
-            d.n = d.n0 * d.n1 * d.n2
-            assert lev["crow"].numel() == d.n + 1 and lev["dinv"].numel() == d.n and lev["col"].numel() == lev["val"].numel()
+            assert lev["crow"].numel() == d.n + 1 and lev["col"].numel() == lev["val"].numel()
             d.max_row = int(lev["max_row"])
             if lev.get("c0") is not None:
                 d.c0 = float(lev["c0"])
                 for k in range(self.degree):
                     d.c1[k], d.c2[k] = float(lev["c1"][k]), float(lev["c2"][k])
+            self._level(j, d, lev, sizes[j + 1] if j + 1 < self.nlev else None)
         raw = torch.frombuffer(bytearray(bytes(self.host)), dtype=torch.uint8)
-        self.blob = raw.to(self.device)
-        self.work_bytes = int(lib().hipk_mg_tail_work_bytes(self.host, self.nlev, _dtype_code(self.dtype)))
+        self.blob = raw.to(device)
+        self.work_bytes = int(getattr(lib(), work_bytes)(self.host, self.nlev, _dtype_code(dtype)))
 
 
-def mg_tail_apply(tail: MgTail, omega: float, scale: float, r: torch.Tensor, z: torch.Tensor,
-                  work: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """z = scale * V(0, r) over the tail's levels in one launch (hipk_mg_tail_apply), on the current stream."""
+class MgTail(_MgDescriptors):
+    """The descriptors of hipk_mg_tail_apply for a run of levels, on the host and as one device blob, and the tensors they point
+    into.  `levels`: per level a dict with int32 `crow` / `col`, `val`, `dinv` (contiguous device tensors of one dtype), `dims`
+    (2 or 3 entries), `max_row` and the smoother's `c0`, `c1`, `c2` (None on the last level, which has one unknown)."""
+
+    def __init__(self, levels, degree: int):
+        self._build(MgLevel, levels, len(levels), degree, levels[0]["val"].dtype, levels[0]["val"].device, "hipk_mg_tail_work_bytes")
+
+    def _level(self, j, d, lev, nc) -> None:
+        d.n0, d.n1, d.n2 = _grid3(lev["dims"])
+        assert d.n == d.n0 * d.n1 * d.n2
+
+
+def _mg_tail_call(symbol: str, tail, omega: float, scale: float, r: torch.Tensor, z: torch.Tensor, work, *last) -> torch.Tensor:
+    """The call of a tail entry point `symbol`; `last` are its arguments between `scale` and `r`."""
     n = int(tail.host[0].n)
     for v in (r, z):
         assert v.is_cuda and v.is_contiguous() and v.dtype == tail.dtype and v.device == tail.device and v.numel() == n
     work = _workspace(work, tail.device, tail.work_bytes)
     with torch.cuda.device(tail.device):
-        _check(lib().hipk_mg_tail_apply(tail.host, tail.blob.data_ptr(), tail.nlev, tail.degree, float(omega), float(scale),
-                                        r.data_ptr(), z.data_ptr(), _dtype_code(tail.dtype), work.data_ptr(), tail.work_bytes,
-                                        _stream(tail.device)), "hipk_mg_tail_apply")
+        _check(getattr(lib(), symbol)(tail.host, tail.blob.data_ptr(), tail.nlev, tail.degree, float(omega), float(scale), *last,
+                                      r.data_ptr(), z.data_ptr(), _dtype_code(tail.dtype), work.data_ptr(), tail.work_bytes,
+                                      _stream(tail.device)), symbol)
     return z
+
+
+def mg_tail_apply(tail: MgTail, omega: float, scale: float, r: torch.Tensor, z: torch.Tensor,
+                  work: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """z = scale * V(0, r) over the tail's levels in one launch (hipk_mg_tail_apply), on the current stream."""
+    return _mg_tail_call("hipk_mg_tail_apply", tail, omega, scale, r, z, work)
 
 
 def _check_index(name: str, a: torch.Tensor, numel: int, like: torch.Tensor) -> None:
@@ -846,7 +869,7 @@ def mg_prolong_add_agg(agg: torch.Tensor, omega: float, e: torch.Tensor, z: torc
 MG_GTAIL_MAX_LEVELS = 32  # the envelope of hipk_mg_gtail_apply beyond MG_TAIL_MAX_N / MG_TAIL_MAX_ROW: levels
 
 
-class MgGTail:
+class MgGTail(_MgDescriptors):
     """`MgTail` for hipk_mg_gtail_apply: per level a dict with int32 `crow` / `col`, `val`, `dinv`, `max_row`, the smoother's `c0`,
     `c1`, `c2` and the int32 index arrays `agg`, `aptr`, `amem` to the next level (all four absent or None on the last level).
 
@@ -854,56 +877,27 @@ class MgGTail:
     a dict of which only `n` is read, and `cinv` its stored inverse (`mg_dense_apply`'s layout)."""
 
     def __init__(self, levels, degree: int, cinv: Optional[torch.Tensor] = None, ld: int = 0):
-        self.nlev, self.degree = len(levels), int(degree)
         self.cinv, self.ld = cinv, int(ld)
-        sizes = [int(lev["dinv"].numel()) for lev in levels[:-1 if cinv is not None else None]] + ([int(levels[-1]["n"])] if cinv is not None else [])
         if cinv is not None:
-            self.dtype, self.device = cinv.dtype, cinv.device
-            _check_cinv(cinv, sizes[-1], self.ld)
-        else:
-            self.dtype, self.device = levels[0]["val"].dtype, levels[0]["val"].device
-        self.host = (MgGLevel * self.nlev)()
-        self._keep = []
-        for j, (d, lev) in enumerate(zip(self.host, levels)):
-            d.n = sizes[j]
-            if cinv is not None and j == self.nlev - 1:
-                break
-            for name in ("crow", "col", "val", "dinv"):
-                t = lev[name]
-                assert t.is_cuda and t.is_contiguous() and t.device == self.device
-                assert t.dtype == (torch.int32 if name in ("crow", "col") else self.dtype)
-                self._keep.append(t)
-                setattr(d, name, t.data_ptr())
-            assert lev["crow"].numel() == d.n + 1 and lev["col"].numel() == lev["val"].numel()
-            d.max_row = int(lev["max_row"])
-            if j + 1 < self.nlev:
-                nc = sizes[j + 1]
-                for name, numel in (("agg", d.n), ("aptr", nc + 1), ("amem", d.n)):
-                    _check_index(name, lev[name], numel, lev["val"])
-                    self._keep.append(lev[name])
-                    setattr(d, name, lev[name].data_ptr())
-                d.c0 = float(lev["c0"])
-                for k in range(self.degree):
-                    d.c1[k], d.c2[k] = float(lev["c1"][k]), float(lev["c2"][k])
-        raw = torch.frombuffer(bytearray(bytes(self.host)), dtype=torch.uint8)
-        self.blob = raw.to(self.device)
-        work_bytes = lib().hipk_mg_gtail_work_bytes if cinv is None else lib().hipk_mg_gtail_dense_work_bytes
-        self.work_bytes = int(work_bytes(self.host, self.nlev, _dtype_code(self.dtype)))
+            _check_cinv(cinv, int(levels[-1]["n"]), self.ld)
+        like = levels[0]["val"] if cinv is None else cinv
+        self._build(MgGLevel, levels, len(levels) - (cinv is not None), degree, like.dtype, like.device,
+                    "hipk_mg_gtail_work_bytes" if cinv is None else "hipk_mg_gtail_dense_work_bytes")
+
+    def _level(self, j, d, lev, nc) -> None:
+        if nc is not None:
+            assert lev.get("c0") is not None, "a level that has a next one needs the smoother's coefficients"
+            for name, numel in (("agg", d.n), ("aptr", nc + 1), ("amem", d.n)):
+                _check_index(name, lev[name], numel, lev["val"])
+                self._keep.append(lev[name])
+                setattr(d, name, lev[name].data_ptr())
 
 
 def mg_gtail_apply(tail: MgGTail, omega: float, scale: float, r: torch.Tensor, z: torch.Tensor,
                    work: Optional[torch.Tensor] = None) -> torch.Tensor:
     """z = scale * V(0, r) over the tail's index-array levels in one launch (hipk_mg_gtail_apply), on the current stream."""
     assert tail.cinv is None, "the tail was built with a dense level: mg_gtail_dense_apply"
-    n = int(tail.host[0].n)
-    for v in (r, z):
-        assert v.is_cuda and v.is_contiguous() and v.dtype == tail.dtype and v.device == tail.device and v.numel() == n
-    work = _workspace(work, tail.device, tail.work_bytes)
-    with torch.cuda.device(tail.device):
-        _check(lib().hipk_mg_gtail_apply(tail.host, tail.blob.data_ptr(), tail.nlev, tail.degree, float(omega), float(scale),
-                                         r.data_ptr(), z.data_ptr(), _dtype_code(tail.dtype), work.data_ptr(), tail.work_bytes,
-                                         _stream(tail.device)), "hipk_mg_gtail_apply")
-    return z
+    return _mg_tail_call("hipk_mg_gtail_apply", tail, omega, scale, r, z, work)
 
 
 MG_DENSE_MAX_N = 2048     # the envelope of hipk_mg_dense_apply: unknowns of the dense level ...
@@ -932,15 +926,7 @@ def mg_gtail_dense_apply(tail: MgGTail, omega: float, scale: float, r: torch.Ten
                          work: Optional[torch.Tensor] = None) -> torch.Tensor:
     """z = scale * V(0, r) over the tail's index-array levels and its dense last level in one launch (hipk_mg_gtail_dense_apply)."""
     assert tail.cinv is not None, "the tail was built without a dense level"
-    n = int(tail.host[0].n)
-    for v in (r, z):
-        assert v.is_cuda and v.is_contiguous() and v.dtype == tail.dtype and v.device == tail.device and v.numel() == n
-    work = _workspace(work, tail.device, tail.work_bytes)
-    with torch.cuda.device(tail.device):
-        _check(lib().hipk_mg_gtail_dense_apply(tail.host, tail.blob.data_ptr(), tail.nlev, tail.degree, float(omega), float(scale),
-                                               tail.cinv.data_ptr(), tail.ld, r.data_ptr(), z.data_ptr(), _dtype_code(tail.dtype),
-                                               work.data_ptr(), tail.work_bytes, _stream(tail.device)), "hipk_mg_gtail_dense_apply")
-    return z
+    return _mg_tail_call("hipk_mg_gtail_dense_apply", tail, omega, scale, r, z, work, tail.cinv.data_ptr(), tail.ld)
 
 
 # -------------------------------------------------------------------- whole solves

@@ -373,29 +373,18 @@ class AggregationMultigridPreconditioner:
                 self.levels.append(lev)
                 self.dense = True
                 break
-            if self.graph:
-                agg, n, rounds = _pairwise_aggregates(csr, *graph)
-                last = n == lev.n
-            else:
-                last = lev.n == 1
-            self._set_up_smoother(lev, len(self.levels), last)
+            below = self._coarsen(csr, dims, graph)
+            self._set_up_smoother(lev, len(self.levels), below is None)
             self.levels.append(lev)
-            if last:
+            if below is None:
                 break
-            if self.graph:
-                if len(self.levels) == MG_GRAPH_MAX_LEVELS:
-                    raise ValueError(f"AggregationMultigridPreconditioner.from_graph: the coarsening has stalled, level "
-                                     f"{len(self.levels) - 1} still has {lev.n} unknowns and more than {MG_GRAPH_MAX_LEVELS} "
-                                     f"levels would be needed (sizes {[v.n for v in self.levels[:4]]} ...)")
-                lev.agg = agg
+            if self.graph and len(self.levels) == MG_GRAPH_MAX_LEVELS:
+                raise ValueError(f"AggregationMultigridPreconditioner.from_graph: the coarsening has stalled, level "
+                                 f"{len(self.levels) - 1} still has {lev.n} unknowns and more than {MG_GRAPH_MAX_LEVELS} "
+                                 f"levels would be needed (sizes {[v.n for v in self.levels[:4]]} ...)")
+            lev.agg, rounds, csr, dims = below
+            if rounds is not None:
                 self.handshake_rounds.append(rounds)
-                crow, col, val = _galerkin_agg(csr.crow_indices(), csr.col_indices(), csr.values(), agg, n)
-                dims = (n,)
-            else:
-                crow, col, val = _galerkin(csr.crow_indices(), csr.col_indices(), csr.values(), dims)
-                dims = _coarse_dims(dims)
-                n = math.prod(dims)
-            csr = torch.sparse_csr_tensor(crow, col, val, size=(n, n))
         L = len(self.levels) - 1
         # the tail: the levels from the first one of at most `tail_rows` unknowns on, when they all fit the kernel's envelope
         tail_rows = MG_TAIL_MAX_ROWS if tail_rows is None else int(tail_rows)
@@ -423,6 +412,27 @@ class AggregationMultigridPreconditioner:
                 v = w / lam
             self.scale = 1.0 / lam
             self.applies = 0
+
+    @staticmethod
+    def _coarsen(csr, dims, graph):
+        """One coarsening step from the level (`csr`, `dims`): None when it is the last level, else (`agg`, the handshake rounds,
+        the next level's csr, its dims).  On a grid (`graph` None) the boxes follow from `dims` and the first two are None; on
+        a graph (`graph` = (passes, theta)) `agg` is the int64 map from the rows to the next level's."""
+        crow, col, val = csr.crow_indices(), csr.col_indices(), csr.values()
+        if graph is None:
+            if csr.shape[0] == 1:
+                return None
+            agg = rounds = None
+            crow, col, val = _galerkin(crow, col, val, dims)
+            dims = _coarse_dims(dims)
+        else:
+            agg, n, rounds = _pairwise_aggregates(csr, *graph)
+            if n == csr.shape[0]:
+                return None
+            crow, col, val = _galerkin_agg(crow, col, val, agg, n)
+            dims = (n,)
+        n = math.prod(dims)
+        return agg, rounds, torch.sparse_csr_tensor(crow, col, val, size=(n, n)), dims
 
     def _set_up_smoother(self, lev: _Level, l: int, last: bool) -> None:
         csr = lev.csr
@@ -535,6 +545,9 @@ class AggregationMultigridPreconditioner:
 
     # ------------------------------------------------------------------ device: one launch per step
     def _dev_state(self):
+        """Per level: the work vectors and, above the tail, the handle and the two transfers of the launch sequence as callables
+        `restrict(t, rc)` and `prolong_add(omega, e, z)`; `self._end(omega, scale, r, z)` is the launch the sequence ends in.  The
+        callables look the `_hipk` wrappers up at every call and hold no reference to the object."""
         if self._dev is None:
             from .. import _hipk
             dev, dt = self.device, self.dtype
@@ -544,11 +557,8 @@ class AggregationMultigridPreconditioner:
                 vec = lambda: torch.empty(lev.n, dtype=dt, device=dev)
                 if lev.cinv is not None:         # the dense last level: nothing but its inverse
                     s = {"n": lev.n, "cinv": _hipk.aligned(lev.cinv.to(device=dev, dtype=dt)).reshape(-1), "ld": lev.ld}
-                    if l and l <= tf:
-                        s["r"], s["z"] = vec(), vec()
-                    st.append(s)
-                    continue
-                s = {"dinv": _hipk.aligned(lev.dinv.to(device=dev, dtype=dt))}
+                else:
+                    s = {"dinv": _hipk.aligned(lev.dinv.to(device=dev, dtype=dt))}
                 if l and l <= tf:
                     s["r"], s["z"] = vec(), vec()
                 if lev.agg is not None:          # the transfers' index arrays: agg, and the members aggregate by aggregate
@@ -557,23 +567,38 @@ class AggregationMultigridPreconditioner:
                     s["agg"] = _hipk.aligned(agg.to(torch.int32))
                     s["amem"] = _hipk.aligned(torch.sort(agg, stable=True)[1].to(torch.int32))
                     s["aptr"] = _hipk.aligned(torch.cat([counts.new_zeros(1), torch.cumsum(counts, 0)]).to(torch.int32))
-                if l >= tf:          # a level of the tail kernel: int32 CSR arrays for its descriptor
-                    c = lev.csr
+                c = lev.csr
+                if l >= tf and lev.cinv is None:          # a level of the tail kernel: int32 CSR arrays for its descriptor
                     s.update(crow=_hipk.aligned(c.crow_indices().to(torch.int32)), col=_hipk.aligned(c.col_indices().to(torch.int32)),
                              val=_hipk.aligned(c.values()), dims=lev.dims, max_row=lev.max_row, c0=lev.c0, c1=lev.c1, c2=lev.c2)
-                elif l < len(self.levels) - 1:
-                    c = lev.csr
+                elif l < min(tf, len(self.levels) - 1):   # a level of the launch sequence that has a next one
                     s["h"] = _hipk.handle_for(self._A) if l == 0 else \
                         _hipk.CsrHandle(c.crow_indices(), c.col_indices(), c.values(), c.shape)
                     s["t"], s["d"] = vec(), vec()
                     s["work"] = torch.empty(2 * ((lev.n + 3) & ~3) * c.values().element_size(), dtype=torch.uint8, device=dev)
+                    if lev.agg is None:
+                        s["restrict"] = lambda t, rc, dims=lev.dims: _hipk.mg_restrict(dims, t, rc)
+                        s["prolong_add"] = lambda omega, e, z, dims=lev.dims: _hipk.mg_prolong_add(dims, omega, e, z)
+                    else:
+                        s["restrict"] = lambda t, rc, aptr=s["aptr"], amem=s["amem"]: _hipk.mg_restrict_agg(aptr, amem, t, rc)
+                        s["prolong_add"] = lambda omega, e, z, agg=s["agg"]: _hipk.mg_prolong_add_agg(agg, omega, e, z)
                 st.append(s)
+            last = st[-1]
             if tf < len(self.levels):
                 if self.dense:
-                    self._tail = _hipk.MgGTail(st[tf:], self.degree, cinv=st[-1]["cinv"], ld=st[-1]["ld"])
+                    tail = _hipk.MgGTail(st[tf:], self.degree, cinv=last["cinv"], ld=last["ld"])
+                    self._end = lambda omega, scale, r, z: _hipk.mg_gtail_dense_apply(tail, omega, scale, r, z, work=work)
+                elif self.graph:
+                    tail = _hipk.MgGTail(st[tf:], self.degree)
+                    self._end = lambda omega, scale, r, z: _hipk.mg_gtail_apply(tail, omega, scale, r, z, work=work)
                 else:
-                    self._tail = (_hipk.MgGTail if self.graph else _hipk.MgTail)(st[tf:], self.degree)
-                self._tail_work = torch.empty(self._tail.work_bytes, dtype=torch.uint8, device=dev)
+                    tail = _hipk.MgTail(st[tf:], self.degree)
+                    self._end = lambda omega, scale, r, z: _hipk.mg_tail_apply(tail, omega, scale, r, z, work=work)
+                self._tail, work = tail, torch.empty(tail.work_bytes, dtype=torch.uint8, device=dev)
+            elif self.dense:
+                self._end = lambda omega, scale, r, z: _hipk.mg_dense_apply(last["cinv"], last["ld"], scale, r, z)
+            else:
+                self._end = lambda omega, scale, r, z: _hipk.mg_diag(scale, last["dinv"], r, z)
             self._dev = st
         return self._dev
 
@@ -587,25 +612,13 @@ class AggregationMultigridPreconditioner:
         z = lambda l: out if l == 0 else st[l]["z"]
         smooth = lambda l, src, dst: _hipk.cheb_apply(st[l]["h"], self.degree, st[l]["dinv"], levels[l].smoother._coef, src,
                                                       work=st[l]["work"], out=dst)
-        for l in range(L):
+        for l in range(L):                                                      # steps 1 - 3
             smooth(l, r(l), z(l))
             _hipk.spmv_residual(st[l]["h"], z(l), r(l), st[l]["t"])
-            if self.graph:
-                _hipk.mg_restrict_agg(st[l]["aptr"], st[l]["amem"], st[l]["t"], r(l + 1))
-            else:
-                _hipk.mg_restrict(levels[l].dims, st[l]["t"], r(l + 1))
-        if self.tail_from is None and self.dense:
-            _hipk.mg_dense_apply(st[L]["cinv"], st[L]["ld"], self.scale if L == 0 else 1.0, r(L), z(L))
-        elif self.tail_from is None:
-            _hipk.mg_diag(self.scale if L == 0 else 1.0, st[L]["dinv"], r(L), z(L))
-        else:
-            tail_apply = _hipk.mg_gtail_dense_apply if self.dense else _hipk.mg_gtail_apply if self.graph else _hipk.mg_tail_apply
-            tail_apply(self._tail, self.omega, self.scale if L == 0 else 1.0, r(L), z(L), work=self._tail_work)
-        for l in range(L - 1, -1, -1):
-            if self.graph:
-                _hipk.mg_prolong_add_agg(st[l]["agg"], self.omega, z(l + 1), z(l))
-            else:
-                _hipk.mg_prolong_add(levels[l].dims, self.omega, z(l + 1), z(l))
+            st[l]["restrict"](st[l]["t"], r(l + 1))
+        self._end(self.omega, self.scale if L == 0 else 1.0, r(L), z(L))        # step 4: level L, or the tail from it on
+        for l in range(L - 1, -1, -1):                                          # steps 5 - 6
+            st[l]["prolong_add"](self.omega, z(l + 1), z(l))
             _hipk.spmv_residual(st[l]["h"], z(l), r(l), st[l]["t"])
             smooth(l, st[l]["t"], st[l]["d"])
             _hipk.mg_correct(self.scale if l == 0 else 1.0, st[l]["d"], z(l))

@@ -5,7 +5,8 @@
    thousand chunks, each thread several rounds of its chunk's loop);
 2. hipk_mg_tail_apply: the launch sequence's and the mirror's bits on small grids, Poisson / variable-coefficient / shuffled-row
    matrices, degrees 1 - 3, both dtypes; the workspace in the four states of tests/_arena.py, a side stream, the error codes, and a
-   matrix with rows of 49 entries that the tail must refuse;
+   matrix with rows of 49 entries that the tail must refuse; hipk_mg_gtail_apply on the boxes written out as index arrays, which
+   must return the same bits;
 3. the whole apply at tail_rows 0 / 256 / 1024 / 4096 with levels above the tail, and `launches_per_apply`;
 4. whole cg / bicgstab / gmres solves against the same solve whose M is a Python callable around the mirror;
 5. one user-sized cg solve: a tenth of plain cg's iterations."""
@@ -21,6 +22,7 @@ from _batch_patterns import build_pattern
 from _order_cases import TRANSFORMS
 from pytorch_sparse_solver.module_a import AggregationMultigridPreconditioner as MG
 from pytorch_sparse_solver.module_a import bicgstab, cg, get_last_stats, gmres
+from pytorch_sparse_solver.module_a.multigrid import _aggregate_of
 from pytorch_sparse_solver.utils.matrix_utils import create_convdiff_2d_csr, create_poisson_2d_csr, create_variable_diffusion_2d_csr
 
 pytestmark = pytest.mark.gpu
@@ -210,6 +212,38 @@ def test_tail_kernel_at_the_32_entry_edge(hipk, oracle, pattern, transform, grid
     rd = torch.from_numpy(r).to(DEV)
     ref = MM.apply(oracle, Ms, r)
     assert MM.same_bits(Ms(rd).cpu().numpy(), ref) and MM.same_bits(Mt(rd).cpu().numpy(), ref)
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=["fp64", "fp32"])
+@pytest.mark.parametrize("grid, sizes, members", [((17, 13), [221, 63, 20, 6, 2, 1], 4), ((5, 4, 3), [60, 12, 2, 1], 8)], ids=["17x13", "5x4x3"])
+def test_box_and_index_levels_are_one_walk(hipk, grid, sizes, members, dtype):
+    """hipk_mg_tail_kernel and hipk_mg_gtail_kernel differ in the two transfers only: given the boxes as index arrays -- members in
+    ascending fine index are exactly the box order -- the index-array tail returns the box tail's bits, and both the launch
+    sequence's.  Odd and even extents: aggregates of 1, 2 and 4 (in three dimensions up to 8) members."""
+    A = MM.csr_tensor(*_matrix("poisson", grid, dtype), device=DEV)
+    Mt = MG(A, grid, degree=2, normalize=False, tail_rows=4096)
+    Ms = MG(A, grid, degree=2, normalize=False, tail_rows=0)
+    assert [lev.n for lev in Mt.levels] == sizes and Mt.tail_from == 0 and Ms.tail_from is None
+    levels = [dict(s) for s in Mt._dev_state()]          # the dicts Mt._tail was built from
+    for s, lev in zip(levels[:-1], Mt.levels):
+        agg = _aggregate_of(torch.arange(lev.n, device=DEV), lev.dims)
+        counts = torch.bincount(agg)
+        assert 1 <= int(counts.min()) and int(counts.max()) <= members
+        s["agg"] = hipk.aligned(agg.to(torch.int32))
+        s["amem"] = hipk.aligned(torch.sort(agg, stable=True)[1].to(torch.int32))
+        s["aptr"] = hipk.aligned(torch.cat([counts.new_zeros(1), torch.cumsum(counts, 0)]).to(torch.int32))
+    assert int(torch.bincount(levels[0]["agg"].to(torch.int64)).max()) == members
+    gtail = hipk.MgGTail(levels, 2)
+    rd = torch.from_numpy(np.random.default_rng([11, sizes[0]]).standard_normal(sizes[0]).astype(dtype)).to(DEV)
+    omega, scale = 1.8, 0.37
+    zb = hipk.mg_tail_apply(Mt._tail, omega, scale, rd, torch.full_like(rd, float("nan"))).cpu().numpy()
+    zi = hipk.mg_gtail_apply(gtail, omega, scale, rd, torch.full_like(rd, float("nan"))).cpu().numpy()
+    Ms.scale = scale
+    zs = Ms(rd).cpu().numpy()
+    assert Ms.omega == omega and np.isfinite(zs).all()
+    assert MM.same_bits(zi, zb), f"{np.count_nonzero(MM.bits(zi) != MM.bits(zb))} of {zb.size} entries differ between the two tails"
+    assert MM.same_bits(zb, zs), f"{np.count_nonzero(MM.bits(zb) != MM.bits(zs))} of {zs.size} entries differ from the launch sequence"
+    assert MM.same_bits(zi, zs)
 
 
 def test_rows_beyond_the_envelope_fall_back_to_launches(hipk, oracle):
