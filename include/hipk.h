@@ -492,6 +492,30 @@ int hipk_mg_gtail_dense_apply(const hipk_mg_glevel *levels_host, const void *lev
                               const void *cinv, int64_t ld, const void *r, void *z, int dtype, void *work, size_t work_bytes,
                               hipk_stream_t stream);
 
+/* ---- aggregation multigrid: the refresh of a hierarchy (csrc/hipk_mg_refresh.hip) ----------------------
+ * `AggregationMultigridPreconditioner.update(A_new)` keeps the aggregates and every index array of a hierarchy and recomputes
+ * its numbers.  The Galerkin values of the next level are hipk_mg_restrict_agg over the stored sort order of the entries
+ * ((n, nc, aptr, amem, t, rc) = (nnz_l, nnz_{l+1}, gptr, gsrc, val_l, val_{l+1})); what a level then needs from its values is
+ *   hipk_mg_level_scan : for a level of n rows (1 <= n < 2^31, else HIPK_ERR_ARG) given by int32 crow (n + 1 entries) / col and
+ *                        val of `dtype` (device, read only; their CONTENTS are the caller's responsibility), for every row i
+ *                            d_i = 0;  d_i = d_i + a    over the stored entries with col == i, in stored order
+ *                            s_i = 0;  s_i = s_i + |a|  over all stored entries of the row, in stored order
+ *                            dinv[i] = 1 / d_i          the correctly rounded quotient (inf for d_i = 0)
+ *                            q_i = (double)s_i / (double)d_i
+ *                        one rounding per operation in `dtype`, no fma, a row of any length; dinv has n elements and nothing at or
+ *                        beyond n is written.  out (device, two doubles): out[0] = max_i q_i, NaN when a q_i is NaN (torch.max);
+ *                        out[1] = the number of rows with d_i <= 0.  want_lmax = 0 forms neither s_i nor q_i and writes
+ *                        out[0] = 0 (the level that only needs dinv); another value than 0 / 1 is HIPK_ERR_ARG.
+ * Two launches enqueued on `stream`: the scan walks dinv in the library's chunk form, 16-byte groups, and leaves one pair of
+ * doubles per workgroup in `work`; one workgroup folds them into `out`.  No atomics, no hand-off between workgroups, every byte
+ * of `work` read has been written by the launch before, the same bits whatever `work` held.  crow, col, val, dinv, out, work
+ * 16-byte aligned, else HIPK_ERR_ALIGN; a null pointer or val == dinv: HIPK_ERR_ARG; another dtype: HIPK_ERR_UNSUPPORTED;
+ * `work` >= hipk_mg_level_scan_work_bytes(n) (pure host code; 0 for n out of range), else HIPK_ERR_WORKSPACE.  A call that
+ * returns an error has launched nothing and written nothing.  Never synchronises. */
+size_t hipk_mg_level_scan_work_bytes(int64_t n);
+int hipk_mg_level_scan(int64_t n, const int32_t *crow, const int32_t *col, const void *val, int dtype, int want_lmax, void *dinv,
+                       double *out, void *work, size_t work_bytes, hipk_stream_t stream);
+
 /* ---- step API: externally driven loops (row-partitioned multi-GPU CG) ------------
  * The reference is single-device; the row-partitioned solver (north_star) drives the
  * SAME fused kernels from the host side of each rank and exchanges (a) the x-vector

@@ -70,6 +70,8 @@ SYMBOLS = [
     "hipk_mg_restrict_agg", "hipk_mg_prolong_add_agg", "hipk_mg_gtail_work_bytes", "hipk_mg_gtail_apply",
     # ... with a dense coarsest level: z = cinv r as a launch, and as the tail's last level
     "hipk_mg_dense_apply", "hipk_mg_gtail_dense_work_bytes", "hipk_mg_gtail_dense_apply",
+    # ... the refresh of a hierarchy for new matrix values: one level's dinv, Gershgorin bound and diagonal check
+    "hipk_mg_level_scan_work_bytes", "hipk_mg_level_scan",
 ]
 
 
@@ -336,6 +338,9 @@ def lib():
     L.hipk_mg_gtail_dense_work_bytes.argtypes = [ctypes.POINTER(MgGLevel), i32, i32]
     L.hipk_mg_gtail_dense_work_bytes.restype = ctypes.c_size_t
     L.hipk_mg_gtail_dense_apply.argtypes = [ctypes.POINTER(MgGLevel), vp, i32, i32, dbl, dbl, vp, i64, vp, vp, i32, vp, ctypes.c_size_t, vp]
+    L.hipk_mg_level_scan_work_bytes.argtypes = [i64]
+    L.hipk_mg_level_scan_work_bytes.restype = ctypes.c_size_t
+    L.hipk_mg_level_scan.argtypes = [i64, vp, vp, vp, i32, i32, vp, vp, vp, ctypes.c_size_t, vp]
     _lib = L
     return L
 
@@ -927,6 +932,30 @@ def mg_gtail_dense_apply(tail: MgGTail, omega: float, scale: float, r: torch.Ten
     """z = scale * V(0, r) over the tail's index-array levels and its dense last level in one launch (hipk_mg_gtail_dense_apply)."""
     assert tail.cinv is not None, "the tail was built without a dense level"
     return _mg_tail_call("hipk_mg_gtail_dense_apply", tail, omega, scale, r, z, work, tail.cinv.data_ptr(), tail.ld)
+
+
+def mg_level_scan_work_bytes(n: int) -> int:
+    """The workspace of `mg_level_scan` for a level of n rows (hipk_mg_level_scan_work_bytes; 0 for n out of range)."""
+    return int(lib().hipk_mg_level_scan_work_bytes(int(n)))
+
+
+def mg_level_scan(crow: torch.Tensor, col: torch.Tensor, val: torch.Tensor, want_lmax: bool, dinv: torch.Tensor, out: torch.Tensor,
+                  work: torch.Tensor) -> torch.Tensor:
+    """One level of a hierarchy's refresh (hipk_mg_level_scan), on the current stream without synchronisation: from int32 `crow` /
+    `col` and `val`, dinv[i] = 1 / (the stored diagonal of row i summed in stored order), out[0] = max_i sum_j |a_ij| / d_i in
+    fp64 (0 when `want_lmax` is False) and out[1] = the number of rows with d_i <= 0.  `out`: two fp64 device elements, `work`: at
+    least `mg_level_scan_work_bytes(n)` bytes; both 16-byte aligned."""
+    n = dinv.numel()
+    assert val.is_cuda and val.is_contiguous() and dinv.is_contiguous() and dinv.dtype == val.dtype and dinv.device == val.device
+    assert out.is_contiguous() and out.dtype == torch.float64 and out.numel() == 2 and out.device == val.device
+    assert work.is_contiguous() and work.dtype == torch.uint8 and work.device == val.device
+    _check_index("crow", crow, n + 1, val)
+    _check_index("col", col, val.numel(), val)
+    with torch.cuda.device(val.device):
+        _check(lib().hipk_mg_level_scan(n, crow.data_ptr(), col.data_ptr(), val.data_ptr(), _dtype_code(val.dtype), 1 if want_lmax else 0,
+                                        dinv.data_ptr(), out.data_ptr(), work.data_ptr(), work.numel(), _stream(val.device)),
+               "hipk_mg_level_scan")
+    return out
 
 
 # -------------------------------------------------------------------- whole solves

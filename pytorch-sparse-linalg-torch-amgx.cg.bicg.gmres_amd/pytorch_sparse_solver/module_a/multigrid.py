@@ -87,18 +87,29 @@ def _galerkin_agg(crow: torch.Tensor, col: torch.Tensor, val: torch.Tensor, agg:
 
 def _galerkin_keys(key: torch.Tensor, val: torch.Tensor, nc: int):
     """The sum of `_galerkin` over the stored entries keyed I * nc + J."""
-    skey, order = torch.sort(key, stable=True)              # stable: a segment keeps A's storage order
-    v = val[order]
-    ukey, counts = torch.unique_consecutive(skey, return_counts=True)
-    start = torch.cumsum(counts, 0) - counts
-    s = v[start]
-    for k in range(1, int(counts.max()) if counts.numel() else 0):   # one pass per rank within a segment
-        has = counts > k
-        s = torch.where(has, s + v[torch.where(has, start + k, start)], s)
+    order, start, counts, ukey = _galerkin_order(key)
+    s = _segment_sums(val[order], start, counts, int(counts.max()) if counts.numel() else 0)
     I = torch.div(ukey, nc, rounding_mode="floor")
     crow_c = torch.zeros(nc + 1, dtype=torch.int64, device=val.device)
     crow_c[1:] = torch.cumsum(torch.bincount(I, minlength=nc), 0)
     return crow_c, ukey % nc, s
+
+
+def _galerkin_order(key: torch.Tensor):
+    """What the sum over keyed entries needs beside the values: (`order`, the stable sort of the keys -- a segment keeps A's
+    storage order --, the start and the length of every segment of equal keys in it, the segments' keys ascending)."""
+    skey, order = torch.sort(key, stable=True)
+    ukey, counts = torch.unique_consecutive(skey, return_counts=True)
+    return order, torch.cumsum(counts, 0) - counts, counts, ukey
+
+
+def _segment_sums(v: torch.Tensor, start: torch.Tensor, counts: torch.Tensor, longest: int) -> torch.Tensor:
+    """s = v[start], s = s + v[start + k] for k = 1 .. counts - 1: one pass per rank within a segment, `longest` = max(counts)."""
+    s = v[start]
+    for k in range(1, longest):
+        has = counts > k
+        s = torch.where(has, s + v[torch.where(has, start + k, start)], s)
+    return s
 
 
 def _abs_row_sums(crow: torch.Tensor, val: torch.Tensor) -> torch.Tensor:
@@ -278,6 +289,8 @@ class AggregationMultigridPreconditioner:
     exactly the order above, with `_SpecSpmv` for the row sums.
 
     `from_graph(A, ...)` builds the same object without a grid, from aggregates of the matrix graph (see there).
+    `update(A_new)` refreshes an object from either constructor for new values on the same sparsity pattern: the aggregates and
+    index arrays stay, the numbers are recomputed (see there; `normalize`, `updates`, `refresh_plan_bytes`).
 
     Attributes: `levels` (per level `csr`, `dims`, `n`, `dinv`, `c0`, `c1`, `c2`, `agg`, `cinv`), `graph` (True for `from_graph`),
     `coarse_rows` and `dense` (`from_graph(coarse_rows=K)`: K, and whether the last level is solved with `levels[-1].cinv`),
@@ -398,20 +411,30 @@ class AggregationMultigridPreconditioner:
         self.launches_per_apply = (L if self.tail_from is None else self.tail_from) * (2 * self.degree + 7) + 1
         self._cpu = None      # per level: (spec SpMV, the aggregate of every row, step 3's gather indices)
         self._dev = None      # per level: handle and work vectors of the device apply
+        self._keep = {}       # what an `update` reuses: the device index arrays and work vectors, by (level, name)
+        self._plan = None     # the refresh plan, built by the first `update`
+        self.normalize, self.updates = bool(normalize), 0
         self.scale = 1.0
         self.applies = 0
         if normalize:
-            v = torch.full((self.shape[0],), 1.0 / math.sqrt(self.shape[0]), dtype=self.dtype, device=self.device)
-            lam = 1.0
-            for _ in range(8):
-                w = self(v)
-                lam = float(torch.linalg.vector_norm(w.to(torch.float64)))
-                if not (lam > 0.0 and math.isfinite(lam)):
-                    raise ValueError("AggregationMultigridPreconditioner: the norm estimate of the V-cycle broke down "
-                                     f"(||M v|| = {lam}); is the matrix symmetric positive definite?")
-                v = w / lam
-            self.scale = 1.0 / lam
-            self.applies = 0
+            self._estimate_scale()
+
+    def _estimate_scale(self) -> None:
+        """`scale` of `normalize=True`: eight steps of the power iteration on the unscaled cycle.  The norm is taken in fp64 on the
+        host whatever the device and v = w / lambda is an element-wise quotient (a device divides by a Python number through its
+        reciprocal): the applies have the same bits on CPU and device, so the two objects get the same `scale`."""
+        self.scale = 1.0
+        v = torch.full((self.shape[0],), 1.0 / math.sqrt(self.shape[0]), dtype=self.dtype, device=self.device)
+        lam = 1.0
+        for _ in range(8):
+            w = self(v)
+            lam = float(torch.linalg.vector_norm(w.cpu().to(torch.float64)))
+            if not (lam > 0.0 and math.isfinite(lam)):
+                raise ValueError("AggregationMultigridPreconditioner: the norm estimate of the V-cycle broke down "
+                                 f"(||M v|| = {lam}); is the matrix symmetric positive definite?")
+            v = w / torch.tensor(lam, dtype=w.dtype, device=w.device)      # a tensor: an element-wise quotient on every device
+        self.scale = 1.0 / lam
+        self.applies = 0
 
     @staticmethod
     def _coarsen(csr, dims, graph):
@@ -460,16 +483,21 @@ class AggregationMultigridPreconditioner:
         crow, col, val = _galerkin_agg(csr.crow_indices(), csr.col_indices(), csr.values(), torch.arange(n, device=csr.device), n)
         dense = torch.zeros((n, n), dtype=val.dtype, device=val.device)
         dense[_rows_of(crow), col] = val                          # coalesced: every (row, col) once
+        self._invert_dense(lev, l, dense)
+
+    def _invert_dense(self, lev: _Level, l: int, dense: torch.Tensor) -> None:
+        """`lev.cinv` and `lev.ld` from the level's matrix written out densely, in the storage dtype on the matrix's device."""
+        n = lev.n
         where = f"AggregationMultigridPreconditioner.from_graph, dense level {l} ({n})"
         try:
             inv = torch.linalg.inv(dense.to(device="cpu", dtype=torch.float64))
         except RuntimeError as e:
             raise ValueError(f"{where}: the matrix is singular ({e})") from None
-        inv = inv.to(val.dtype)
+        inv = inv.to(dense.dtype)
         if not bool(torch.isfinite(inv).all()):
             raise ValueError(f"{where}: the inverse is not finite; is the matrix singular?")
         lev.ld = (n + 3) & ~3
-        cinv = torch.zeros((n, lev.ld), dtype=val.dtype)
+        cinv = torch.zeros((n, lev.ld), dtype=dense.dtype)
         cinv[:, :n] = inv.T                                       # row j of the tensor is column j of the inverse
         lev.cinv = cinv.to(self.device)
 
@@ -554,28 +582,33 @@ class AggregationMultigridPreconditioner:
             st = []
             tf = len(self.levels) if self.tail_from is None else self.tail_from
             for l, lev in enumerate(self.levels):
-                vec = lambda: torch.empty(lev.n, dtype=dt, device=dev)
+                # work vectors and index arrays depend on the pattern alone: an `update` finds them in `_keep`
+                vec = lambda name: self._kept(l, name, lambda: torch.empty(lev.n, dtype=dt, device=dev))
                 if lev.cinv is not None:         # the dense last level: nothing but its inverse
                     s = {"n": lev.n, "cinv": _hipk.aligned(lev.cinv.to(device=dev, dtype=dt)).reshape(-1), "ld": lev.ld}
                 else:
                     s = {"dinv": _hipk.aligned(lev.dinv.to(device=dev, dtype=dt))}
                 if l and l <= tf:
-                    s["r"], s["z"] = vec(), vec()
+                    s["r"], s["z"] = vec("r"), vec("z")
                 if lev.agg is not None:          # the transfers' index arrays: agg, and the members aggregate by aggregate
-                    agg = lev.agg.to(dev)
-                    counts = torch.bincount(agg, minlength=self.levels[l + 1].n)
-                    s["agg"] = _hipk.aligned(agg.to(torch.int32))
-                    s["amem"] = _hipk.aligned(torch.sort(agg, stable=True)[1].to(torch.int32))
-                    s["aptr"] = _hipk.aligned(torch.cat([counts.new_zeros(1), torch.cumsum(counts, 0)]).to(torch.int32))
+                    if (l, "agg") not in self._keep:
+                        agg = lev.agg.to(dev)
+                        counts = torch.bincount(agg, minlength=self.levels[l + 1].n)
+                        self._keep[l, "agg"] = _hipk.aligned(agg.to(torch.int32))
+                        self._keep[l, "amem"] = _hipk.aligned(torch.sort(agg, stable=True)[1].to(torch.int32))
+                        self._keep[l, "aptr"] = _hipk.aligned(torch.cat([counts.new_zeros(1), torch.cumsum(counts, 0)]).to(torch.int32))
+                    s.update({name: self._keep[l, name] for name in ("agg", "amem", "aptr")})
                 c = lev.csr
                 if l >= tf and lev.cinv is None:          # a level of the tail kernel: int32 CSR arrays for its descriptor
-                    s.update(crow=_hipk.aligned(c.crow_indices().to(torch.int32)), col=_hipk.aligned(c.col_indices().to(torch.int32)),
+                    crow, col = self._int32_pattern(l)
+                    s.update(crow=crow, col=col,
                              val=_hipk.aligned(c.values()), dims=lev.dims, max_row=lev.max_row, c0=lev.c0, c1=lev.c1, c2=lev.c2)
                 elif l < min(tf, len(self.levels) - 1):   # a level of the launch sequence that has a next one
                     s["h"] = _hipk.handle_for(self._A) if l == 0 else \
                         _hipk.CsrHandle(c.crow_indices(), c.col_indices(), c.values(), c.shape)
-                    s["t"], s["d"] = vec(), vec()
-                    s["work"] = torch.empty(2 * ((lev.n + 3) & ~3) * c.values().element_size(), dtype=torch.uint8, device=dev)
+                    s["t"], s["d"] = vec("t"), vec("d")
+                    s["work"] = self._kept(l, "work", lambda: torch.empty(2 * ((lev.n + 3) & ~3) * c.values().element_size(),
+                                                                          dtype=torch.uint8, device=dev))
                     if lev.agg is None:
                         s["restrict"] = lambda t, rc, dims=lev.dims: _hipk.mg_restrict(dims, t, rc)
                         s["prolong_add"] = lambda omega, e, z, dims=lev.dims: _hipk.mg_prolong_add(dims, omega, e, z)
@@ -594,7 +627,8 @@ class AggregationMultigridPreconditioner:
                 else:
                     tail = _hipk.MgTail(st[tf:], self.degree)
                     self._end = lambda omega, scale, r, z: _hipk.mg_tail_apply(tail, omega, scale, r, z, work=work)
-                self._tail, work = tail, torch.empty(tail.work_bytes, dtype=torch.uint8, device=dev)
+                self._tail = tail
+                work = self._kept(tf, "tail work", lambda: torch.empty(tail.work_bytes, dtype=torch.uint8, device=dev))
             elif self.dense:
                 self._end = lambda omega, scale, r, z: _hipk.mg_dense_apply(last["cinv"], last["ld"], scale, r, z)
             else:
@@ -640,3 +674,212 @@ class AggregationMultigridPreconditioner:
                 z = torch.tensor(self.scale, dtype=v.dtype) * z
         self.applies += 1
         return z
+
+    # ------------------------------------------------------------------ update: new values on the same pattern
+    def _kept(self, l: int, name: str, make):
+        """The device tensor (`l`, `name`) of `_keep`, made on first use: index arrays and work vectors, which follow from the
+        sparsity patterns alone and so outlive every `update`."""
+        if (l, name) not in self._keep:
+            self._keep[l, name] = make()
+        return self._keep[l, name]
+
+    def _int32_pattern(self, l: int):
+        """Level l's row pointers and columns as aligned int32 device arrays (the tail's descriptors and the level scan read them)."""
+        from .. import _hipk
+        c = self.levels[l].csr
+        return (self._kept(l, "crow", lambda: _hipk.aligned(c.crow_indices().to(torch.int32))),
+                self._kept(l, "col", lambda: _hipk.aligned(c.col_indices().to(torch.int32))))
+
+    def update(self, A_new: torch.Tensor) -> "AggregationMultigridPreconditioner":
+        """Refresh the hierarchy for a matrix with the SAME sparsity pattern and new values, and return self: what AMG packages
+        call a re-setup.  The aggregates of every level (the boxes of a grid, `agg` of a graph hierarchy) and every index array
+        stay; the numbers are recomputed under the constructors' rounding rules, so the object is the one the constructor would
+        have produced for `A_new` with every level's aggregates held fixed:
+          values    `levels[l + 1].csr` holds the Galerkin sum of `levels[l].csr`, s = first, s = s + next over the fine storage
+                    order, on the unchanged pattern;
+          smoother  every level's `dinv`, the Gershgorin bound (rows summed in stored order) and `c0`, `c1`, `c2` with the
+                    constructor's `degree` and `ratio`; the last level of a graph hierarchy stays z = dinv r from its diagonal;
+          dense     `cinv` of a dense last level from the fp64 inversion on the CPU, rounded once, in the same layout;
+          scale     re-estimated by the same eight power-iteration steps when the object was built with `normalize=True`;
+          counters  `applies` goes back to 0, `updates` counts the successful calls.
+        `agg`, `dims`, `max_row`, `tail_rows`, `tail_from`, `launches_per_apply`, `handshake_rounds`, `dense` and `coarse_rows` do
+        not change.  A CPU object and a device object refreshed with the same values hold the same bits.
+
+        `A_new` has the shape, dtype and device of the matrix the object was built from and goes through the same conversion to
+        CSR (CSR taken as it is, COO coalesced); its `crow_indices` / `col_indices` must equal level 0's, stored zeros counting
+        as pattern.  Anything else is a ValueError that names what differs.
+
+        All or nothing: the new state is built beside the old one and swapped in at the end.  When the call raises -- a
+        non-positive diagonal on some level, 0 < lmin < lmax violated, a singular dense level or a broken-down norm estimate,
+        each with the constructor's message --, the object is exactly what it was.
+
+        The first call builds the refresh plan (`refresh_plan_bytes`): per level with a next one the stable sort order of the
+        Galerkin keys, `gsrc`, and the segment starts `gptr` (int32 on a device object, which needs nnz < 2^31; int64 on a CPU
+        object), and for a dense level the slot of each stored entry.  Later calls sort nothing.  On the device the Galerkin sums
+        are `hipk_mg_restrict_agg` over (gptr, gsrc), every level's dinv / bound / diagonal check is one `hipk_mg_level_scan`,
+        and the bounds of all levels come back in one copy; coarse levels get new `CsrHandle`s, level 0 `_hipk.handle_for(A_new)`,
+        and the tail's descriptors are rebuilt, while index arrays and work vectors are reused."""
+        what = "AggregationMultigridPreconditioner.update"
+        self._check_matrix(A_new)
+        if tuple(A_new.shape) != self.shape:
+            raise ValueError(f"{what}: the matrix has shape {tuple(A_new.shape)}, the object was built from one of shape {self.shape}")
+        if A_new.dtype != self.dtype:
+            raise ValueError(f"{what}: the matrix is {A_new.dtype}, the object was built from a {self.dtype} matrix")
+        if A_new.device != self.device:
+            raise ValueError(f"{what}: the matrix is on {A_new.device}, the object was built from a matrix on {self.device}")
+        A = A_new.detach()
+        csr = A if A.layout == torch.sparse_csr else (A.coalesce() if A.layout == torch.sparse_coo else A).to_sparse_csr()
+        old = self.levels[0].csr
+        if csr.values().numel() != old.values().numel():
+            raise ValueError(f"{what}: the sparsity pattern differs, the matrix stores {csr.values().numel()} entries and the one "
+                             f"the object was built from {old.values().numel()}")
+        for name in ("crow_indices", "col_indices"):
+            if not torch.equal(getattr(csr, name)().to(torch.int64), getattr(old, name)().to(torch.int64)):
+                raise ValueError(f"{what}: the sparsity pattern differs, {name} are not those of the matrix the object was built from")
+        state = self._refreshed(A, csr, self._refresh_plan()).__dict__
+        self.__dict__.clear()
+        self.__dict__.update(state)
+        return self
+
+    @property
+    def refresh_plan_bytes(self) -> int:
+        """The memory of the refresh plan on the matrix's device: `gsrc`, `gptr`, the dense level's slots and, on a device, the
+        scan's results and workspace and the int32 patterns it reads (which the tail's levels share).  0 before the first `update`."""
+        if self._plan is None:
+            return 0
+        held = list(self._plan["tensors"]) + [t for (_, name), t in self._keep.items() if name in ("crow", "col")]
+        return sum(t.numel() * t.element_size() for t in held)
+
+    def _refresh_plan(self):
+        """The plan of `update`, built once: {"steps": per level with a next one {"gsrc", "gptr", "longest"} -- the stable sort
+        order of the keys agg(row) nc + agg(col), the segment starts (nnz_{l+1} + 1 entries) and the longest segment --, "dense":
+        None or {"slots", "gsrc", "gptr", "longest"} -- the index of each entry in the flattened dense matrix, and the order /
+        segments of its coalescing where an entry is stored more than once (None otherwise) --, "res" / "work": the level
+        scans' results and workspace on a device, "tensors": everything above that holds memory}."""
+        if self._plan is not None:
+            return self._plan
+        on_dev = self.device.type == "cuda"
+        if on_dev:
+            from .. import _hipk
+        index = lambda t: _hipk.aligned(t.to(torch.int32)) if on_dev else t
+        tensors = []
+
+        def ordered(key):
+            if on_dev and key.numel() >= 2 ** 31:
+                raise ValueError("AggregationMultigridPreconditioner.update: the device refresh plan needs nnz < 2^31 on every level, "
+                                 f"got {key.numel()}")
+            order, start, counts, ukey = _galerkin_order(key)
+            step = {"gsrc": index(order), "gptr": index(torch.cat([start, start.new_full((1,), key.numel())])),
+                    "longest": int(counts.max()) if counts.numel() else 0}
+            tensors.extend([step["gsrc"], step["gptr"]])
+            return step, ukey
+
+        steps = []
+        for lev, nxt in zip(self.levels[:-1], self.levels[1:]):
+            crow, col = lev.csr.crow_indices().to(torch.int64), lev.csr.col_indices().to(torch.int64)
+            if lev.agg is None:
+                key = _aggregate_of(_rows_of(crow), lev.dims) * nxt.n + _aggregate_of(col, lev.dims)
+            else:
+                key = lev.agg[_rows_of(crow)] * nxt.n + lev.agg[col]
+            steps.append(ordered(key)[0])
+        dense = None
+        if self.dense:
+            lev = self.levels[-1]
+            crow, col = lev.csr.crow_indices().to(torch.int64), lev.csr.col_indices().to(torch.int64)
+            key = _rows_of(crow) * lev.n + col
+            dense = {"slots": key, "gsrc": None}
+            if len(self.levels) == 1:          # the caller's matrix: an entry may be stored more than once
+                step, ukey = ordered(key)
+                if step["longest"] > 1:
+                    dense = dict(step, slots=ukey)
+            tensors.append(dense["slots"])
+        plan = {"steps": steps, "dense": dense, "tensors": tensors}
+        if on_dev:
+            plan["res"] = torch.zeros((len(self.levels), 2), dtype=torch.float64, device=self.device)
+            plan["work"] = torch.empty(max(_hipk.mg_level_scan_work_bytes(lev.n) for lev in self.levels), dtype=torch.uint8,
+                                       device=self.device)
+            tensors.extend([plan["res"], plan["work"]])
+        self._plan = plan
+        return plan
+
+    def _segment_sum(self, step, v: torch.Tensor) -> torch.Tensor:
+        """The sums of `v` over the segments of a plan step, each s = first, s = s + next in the stored sort order."""
+        if v.is_cuda:
+            from .. import _hipk
+            out = torch.empty(step["gptr"].numel() - 1, dtype=v.dtype, device=v.device)
+            return _hipk.mg_restrict_agg(step["gptr"], step["gsrc"], _hipk.aligned(v), out)
+        start = step["gptr"][:-1]
+        return _segment_sums(v[step["gsrc"]], start, step["gptr"][1:] - start, step["longest"])
+
+    def _refreshed(self, A, csr, plan):
+        """The object `update` swaps in: a shallow copy of this one with new levels, `_A` and device state, built without touching
+        this one (the plan, the kept index arrays and work vectors and the CPU gather indices are shared: none holds a value)."""
+        new = object.__new__(type(self))
+        new.__dict__.update(self.__dict__)
+        new._A, new._dev, new.scale, new.applies, new.updates = A, None, 1.0, 0, self.updates + 1
+        new.__dict__.pop("_tail", None)
+        new.__dict__.pop("_end", None)
+        L = len(self.levels) - 1
+        new.levels = []
+        val = csr.values()
+        for l, old in enumerate(self.levels):
+            lev = _Level.__new__(_Level)
+            lev.__dict__.update(old.__dict__)
+            c = old.csr
+            lev.csr = csr if l == 0 else torch.sparse_csr_tensor(c.crow_indices(), c.col_indices(), val, size=c.shape)
+            lev.smoother = lev.dinv = lev.c0 = lev.c1 = lev.c2 = lev.cinv = None
+            new.levels.append(lev)
+            if l < L:
+                val = self._segment_sum(plan["steps"][l], val)
+        if self.device.type == "cuda" and L > 0:
+            new._scan_levels(plan)
+        else:      # torch ops through the plan (a one-level device object has nothing to enqueue: the constructor's path)
+            for l, lev in enumerate(new.levels):
+                if self.dense and l == L:
+                    new._refresh_dense(lev, l, plan)
+                else:
+                    new._set_up_smoother(lev, l, l == L)
+        if self.normalize:
+            new._estimate_scale()
+        return new
+
+    def _refresh_dense(self, lev: _Level, l: int, plan) -> None:
+        """`_set_up_dense` through the plan's slots: an indexed store instead of the coalescing sort."""
+        d, val = plan["dense"], lev.csr.values()
+        if d["gsrc"] is not None:
+            val = self._segment_sum(d, val)
+        dense = torch.zeros(lev.n * lev.n, dtype=val.dtype, device=val.device)
+        dense[d["slots"]] = val
+        self._invert_dense(lev, l, dense.view(lev.n, lev.n))
+
+    def _scan_levels(self, plan) -> None:
+        """The device form of the per-level set-up: one `hipk_mg_level_scan` per sparse level, all enqueued before the one copy
+        that brings every level's (bound, non-positive diagonal entries) back; the coefficients are formed on the host."""
+        from .. import _hipk
+        L = len(self.levels) - 1
+        res = plan["res"]
+        for l, lev in enumerate(self.levels):
+            if self.dense and l == L:
+                continue
+            crow, col = self._int32_pattern(l)
+            lev.dinv = torch.empty(lev.n, dtype=self.dtype, device=self.device)
+            # the bound is needed where there is a smoother; the one unknown of a grid's last level takes it as its NaN check
+            _hipk.mg_level_scan(crow, col, _hipk.aligned(lev.csr.values()), l < L or not self.graph, lev.dinv, res[l], plan["work"])
+        host = res.cpu()
+        for l, lev in enumerate(self.levels):
+            if self.dense and l == L:
+                self._refresh_dense(lev, l, plan)
+                continue
+            where = f"AggregationMultigridPreconditioner, level {l} ({'x'.join(map(str, lev.dims))})"
+            lmax, bad = float(host[l, 0]), float(host[l, 1])
+            if bad > 0 or (l == L and math.isnan(lmax)):
+                raise ValueError(f"{where}: zero or negative entry on the diagonal")
+            if l == L:
+                continue
+            sm = ChebyshevPreconditioner.__new__(ChebyshevPreconditioner)
+            sm.degree, sm.shape, sm._A, sm.dinv, sm._cpu, sm._dev = self.degree, tuple(lev.csr.shape), lev.csr, lev.dinv, None, None
+            try:
+                sm._set_coefficients(lmax, None, self.ratio, False, 0.0)
+            except ValueError as e:
+                raise ValueError(f"{where}: {e}") from None
+            lev.smoother, lev.c0, lev.c1, lev.c2 = sm, sm.c0, sm.c1, sm.c2

@@ -29,6 +29,16 @@ the one-workgroup tail `hipk_mg_gtail_dense_apply` on that level alone.  A last 
 256 / 512 / 1024 / 2048 rows.  profiles/mg_dense_probe.txt is the output of
 
   python tools/mg_probe.py --graph --reps 2 --applies 0 --configs plain mg1 gmg1 gmg1c256 gmg1c512 gmg1c1024 gmg1c2048
+
+`--refresh`: `update()` against a fresh construction, on Poisson 2000^2, variable diffusion 2000^2 and 7-point 128^3 (`--systems`)
+under the grid class, `from_graph()` and `from_graph(coarse_rows=2048)` (`--configs grid graph graph_c2048`).  Per line: the wall
+clock of a fresh construction in the same process (the yardstick), of the first `update` (the plan's build included), the mean of
+five later ones, and the split of one later update into Galerkin sums, scans, handles, dense inverse and norm estimate (measured
+with a synchronised clock around each step, so its total is above an unclocked update).  Then ten steps of changing coefficients
+(D A D for a moving diagonal D) three ways: rebuild + solve, update + solve, and the stale object + solve (capped at 500
+iterations), with the iteration counts.  The lines also go to profiles/mg_refresh_probe.txt (`--out`), stamped with the build id.
+
+  python tools/mg_probe.py --refresh
 """
 import argparse
 import json
@@ -214,14 +224,120 @@ def run_system(name, make, grid, reps, configs, applies, graph=False):
     return row
 
 
+REFRESH_KINDS = {"grid": lambda P, A, grid: P(A, grid), "graph": lambda P, A, grid: P.from_graph(A),
+                 "graph_c2048": lambda P, A, grid: P.from_graph(A, coarse_rows=2048)}
+REFRESH_SYSTEMS = ("poisson2000", "vardiff2000", "poisson3d128")
+STALE_MAXITER = 500
+
+
+def _rescaled(A, t):
+    """D A D on A's pattern, D = diag(exp(1.5 sin(2 pi (3 i / n + t)))): the coefficients of step t of the sequence (SPD with A)."""
+    import math
+    n = A.shape[0]
+    crow, col = A.crow_indices(), A.col_indices()
+    d = torch.exp(1.5 * torch.sin(2.0 * math.pi * (3.0 * torch.arange(n, device=A.device, dtype=torch.float64) / n + t)))
+    rows = torch.repeat_interleave(torch.arange(n, device=A.device), crow[1:] - crow[:-1])
+    return torch.sparse_csr_tensor(crow, col, A.values() * d[rows] * d[col], size=A.shape)
+
+
+def _update_split(P, M, A):
+    """One `update` with a synchronised clock around its steps: ms of the Galerkin sums, the level scans (with the read-back and
+    the coefficients), the dense inverse (with its copies), the handles and descriptors, and the norm estimate."""
+    spent, saved = {}, {}
+
+    def clocked(name):
+        fn = getattr(P, name)
+        saved[name] = fn
+
+        def wrapper(*a, **kw):
+            out, t = _timed(lambda: fn(*a, **kw))
+            spent[name] = spent.get(name, 0.0) + t
+            return out
+        setattr(P, name, wrapper)
+
+    for name in ("_segment_sum", "_scan_levels", "_invert_dense", "_dev_state", "_estimate_scale"):
+        clocked(name)
+    try:
+        _, total = _timed(lambda: M.update(A))
+    finally:
+        for name, fn in saved.items():
+            setattr(P, name, fn)
+    g = lambda k: spent.get(k, 0.0)
+    ms = lambda v: round(1e3 * v, 2)
+    return {"total": ms(total), "galerkin_sums": ms(g("_segment_sum")), "scans": ms(g("_scan_levels") - g("_invert_dense")),
+            "dense_inverse": ms(g("_invert_dense")), "handles": ms(g("_dev_state")), "norm_estimate": ms(g("_estimate_scale") - g("_dev_state"))}
+
+
+def run_refresh(name, make, grid, kind):
+    """Set-up against re-setup for one system and one kind of hierarchy, then ten steps of changing coefficients three ways."""
+    from pytorch_sparse_solver.module_a import AggregationMultigridPreconditioner as P, cg, get_last_stats
+    A = make()
+    n = A.shape[0]
+    b = torch.ones(n, dtype=torch.float64, device=DEV)
+    build = lambda X: REFRESH_KINDS[kind](P, X, grid)
+    try:
+        build(A)                                              # warm-up: code objects, allocator
+    except ValueError as e:                                   # the 48-level stall of a graph hierarchy without a cut
+        return {"system": name, "kind": kind, "n": n, "refused": str(e)}
+    M, fresh = _timed(lambda: build(A))
+    row = {"system": name, "kind": kind, "n": n, "levels": [lev.n for lev in M.levels], "tail_from": M.tail_from,
+           "fresh_build_ms": round(1e3 * fresh, 1)}
+    steps = [_rescaled(A, 0.05 * (k + 1)) for k in range(10)]
+    _, first = _timed(lambda: M.update(steps[0]))
+    later = [_timed(lambda: M.update(steps[1 + k % 2]))[1] for k in range(5)]
+    row.update(first_update_ms=round(1e3 * first, 1), later_update_ms_mean=round(1e3 * sum(later) / len(later), 1),
+               later_update_ms_min_max=[round(1e3 * min(later), 1), round(1e3 * max(later), 1)], refresh_plan_bytes=M.refresh_plan_bytes,
+               later_update_split_ms=_update_split(P, M, steps[0]))
+    stale = build(A)
+    M.update(A)
+    ways = {"rebuild": [], "update": [], "stale": []}
+    for Ak in steps:
+        for way in ways:
+            def step():
+                Mk = build(Ak) if way == "rebuild" else M.update(Ak) if way == "update" else stale
+                return cg(Ak, b, tol=1e-6, M=Mk, maxiter=STALE_MAXITER if way == "stale" else None)
+            (x, info), t = _timed(step)
+            ways[way].append((t, get_last_stats().iterations, int(info)))
+    row["ten_steps"] = {way: {"ms_total": round(1e3 * sum(v[0] for v in r), 1), "iterations": [v[1] for v in r],
+                              "not_converged": sum(v[2] != 0 for v in r)} for way, r in ways.items()}
+    row["ten_steps"]["stale"]["maxiter"] = STALE_MAXITER
+    return row
+
+
+def main_refresh(a):
+    from pytorch_sparse_solver import _hipk
+    out = open(a.out, "w")
+
+    def emit(obj):
+        line = json.dumps(obj)
+        print(line, flush=True)
+        out.write(line + "\n")
+        out.flush()
+
+    emit({"hipk_build_id": _hipk.lib().hipk_build_id().decode(), "device": torch.cuda.get_device_name(0), "mode": "refresh",
+          "dtype": "float64", "tol": 1e-6, "sequence": "D A D, D = diag(exp(1.5 sin(2 pi (3 i / n + t)))), t = 0.05 .. 0.5"})
+    table = systems()
+    for name in a.systems or REFRESH_SYSTEMS:
+        make, grid = table[name]
+        for kind in a.configs or list(REFRESH_KINDS):
+            emit(run_refresh(name, make, grid, kind))
+            _hipk.clear_cache()
+            torch.cuda.empty_cache()
+    out.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--refresh", action="store_true", help="update() against a fresh construction: set-up times, their split, ten steps")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mg_refresh_probe.txt"), help="--refresh: the file the lines also go to")
     ap.add_argument("--systems", nargs="*", default=None)
     ap.add_argument("--configs", nargs="*", default=None, help="default: plain cheb3 mg1 mg2; with --graph: plain mg1 gmg1 gmg2 gmg1c256 gmg1c512 gmg1c1024 gmg1c2048")
     ap.add_argument("--graph", action="store_true", help="from_graph beside the grid class; the tail_rows sweep on the graph hierarchy")
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--applies", type=int, default=20)
     a = ap.parse_args()
+    if a.refresh:
+        return main_refresh(a)
     a.configs = a.configs or (["plain", "mg1", "gmg1", "gmg2"] + [f"gmg1c{k}" for k in CUTS] if a.graph else ["plain", "cheb3", "mg1", "mg2"])
     from pytorch_sparse_solver import _hipk
     from pytorch_sparse_solver.module_a import multigrid
