@@ -492,6 +492,33 @@ int hipk_mg_gtail_dense_apply(const hipk_mg_glevel *levels_host, const void *lev
                               const void *cinv, int64_t ld, const void *r, void *z, int dtype, void *work, size_t work_bytes,
                               hipk_stream_t stream);
 
+/* ---- aggregation multigrid: the W-cycle (csrc/hipk_mg_w.hip) -------------------------------------------
+ * `AggregationMultigridPreconditioner(cycle="W")`: W(l, r) is V(l, r) whose step 4 reads, where level l + 1 is smoothed (it is
+ * not the last level),
+ *     e = W(l + 1, rc);  rc2 = rc - A_{l+1} e;  e2 = W(l + 1, rc2);  e = e + e2
+ * every step one rounding, no fma; the last level is visited once per visit of the level above it.
+ *   hipk_mg_add : e[i] = e[i] + e2[i], i < n (the last line above), in hipk_mg_correct's form: 16-byte groups, one ragged group,
+ *                 nothing at or beyond n touched.  n >= 1 and two distinct non-null vectors, else HIPK_ERR_ARG; 16-byte aligned,
+ *                 else HIPK_ERR_ALIGN; another dtype: HIPK_ERR_UNSUPPORTED.
+ *   hipk_mg_tail_apply_w, hipk_mg_gtail_apply_w, hipk_mg_gtail_dense_apply_w : hipk_mg_tail_apply, hipk_mg_gtail_apply and
+ *                 hipk_mg_gtail_dense_apply with the W-cycle: the same descriptors, arguments, checks and error codes, ONE launch
+ *                 of one 256-thread workgroup that runs the whole W walk over its levels (level j >= 1 of nlev is visited
+ *                 2^min(j, nlev - 2) times), bit for bit the W launch sequence.  nlev <= 2 is the V entry's result bit for bit.
+ *                 More than 12 levels: HIPK_ERR_UNSUPPORTED.  The slab holds SIX vectors per level, r | z | t | d | w | e: `work`
+ *                 >= the entry's *_work_bytes_w (pure host code; 0 for bad arguments or more than 12 levels), else
+ *                 HIPK_ERR_WORKSPACE.  A call that returns an error has launched nothing and written nothing. */
+int hipk_mg_add(int64_t n, const void *e2, void *e, int dtype, hipk_stream_t stream);
+size_t hipk_mg_tail_work_bytes_w(const hipk_mg_level *levels_host, int nlev, int dtype);
+int hipk_mg_tail_apply_w(const hipk_mg_level *levels_host, const void *levels_dev, int nlev, int degree, double omega, double scale,
+                         const void *r, void *z, int dtype, void *work, size_t work_bytes, hipk_stream_t stream);
+size_t hipk_mg_gtail_work_bytes_w(const hipk_mg_glevel *levels_host, int nlev, int dtype);
+int hipk_mg_gtail_apply_w(const hipk_mg_glevel *levels_host, const void *levels_dev, int nlev, int degree, double omega, double scale,
+                          const void *r, void *z, int dtype, void *work, size_t work_bytes, hipk_stream_t stream);
+size_t hipk_mg_gtail_dense_work_bytes_w(const hipk_mg_glevel *levels_host, int nlev, int dtype);
+int hipk_mg_gtail_dense_apply_w(const hipk_mg_glevel *levels_host, const void *levels_dev, int nlev, int degree, double omega, double scale,
+                                const void *cinv, int64_t ld, const void *r, void *z, int dtype, void *work, size_t work_bytes,
+                                hipk_stream_t stream);
+
 /* ---- aggregation multigrid: the refresh of a hierarchy (csrc/hipk_mg_refresh.hip) ----------------------
  * `AggregationMultigridPreconditioner.update(A_new)` keeps the aggregates and every index array of a hierarchy and recomputes
  * its numbers.  The Galerkin values of the next level are hipk_mg_restrict_agg over the stored sort order of the entries

@@ -209,32 +209,14 @@ __global__ __launch_bounds__(HIPK_THREADS) void hipk_mg_tail_kernel(const hipk_m
     hipk_mg_walk_up<T, hipk_mg_level, hipk_mg_box_xf>(lv, nlev, m, omega, scale, rin, zout, slab, xs);
 }
 
-static int hipk_mg_tail_check(const hipk_mg_level *lv, int nlev, int degree, int dtype) {
-    HIPK_REQUIRE(lv && nlev >= 1 && nlev <= HIPK_MG_TAIL_MAX_LEVELS, HIPK_ERR_ARG, "1 .. 16 levels");
-    HIPK_REQUIRE(degree >= 1 && degree <= 32, HIPK_ERR_ARG, "degree must be in [1, 32]");
-    HIPK_REQUIRE(dtype == HIPK_F64 || dtype == HIPK_F32, HIPK_ERR_UNSUPPORTED, "dtype must be HIPK_F32 or HIPK_F64");
-    for (int j = 0; j < nlev; ++j) {
-        const hipk_mg_level &L = lv[j];
-        HIPK_REQUIRE(L.n0 >= 1 && L.n1 >= 1 && L.n2 >= 1 && L.n >= 1 && (int64_t)L.n0 * L.n1 * L.n2 == L.n, HIPK_ERR_ARG,
-                     "a level's n is not the product of its dimensions");
-        HIPK_REQUIRE(L.n <= HIPK_MG_TAIL_MAX_N && L.max_row <= HIPK_MG_TAIL_MAX_ROW, HIPK_ERR_UNSUPPORTED,
-                     "hipk_mg_tail_apply takes levels of at most 4096 unknowns and 32 stored entries per row");
-        HIPK_REQUIRE(L.crow && L.col && L.val && L.dinv, HIPK_ERR_ARG, "null pointer in a level");
-        if (j + 1 < nlev)
-            HIPK_REQUIRE(lv[j + 1].n0 == (L.n0 + 1) / 2 && lv[j + 1].n1 == (L.n1 + 1) / 2 && lv[j + 1].n2 == (L.n2 + 1) / 2, HIPK_ERR_ARG,
-                         "a level's dimensions are not ceil(d / 2) of the level above");
-    }
-    HIPK_REQUIRE(lv[nlev - 1].n == 1, HIPK_ERR_ARG, "the last level must have one unknown");
-    return HIPK_OK;
-}
-
 extern "C" size_t hipk_mg_tail_work_bytes(const hipk_mg_level *levels_host, int nlev, int dtype) {
     return hipk_mg_work_bytes(levels_host, nlev, HIPK_MG_TAIL_MAX_LEVELS, dtype);
 }
 
 extern "C" int hipk_mg_tail_apply(const hipk_mg_level *levels_host, const void *levels_dev, int nlev, int degree, double omega,
                                   double scale, const void *r, void *z, int dtype, void *work, size_t work_bytes, hipk_stream_t stream) {
-    HIPK_TRY(hipk_mg_tail_check(levels_host, nlev, degree, dtype));
+    HIPK_TRY(hipk_mg_tail_check(levels_host, nlev, degree, dtype,
+                                "hipk_mg_tail_apply takes levels of at most 4096 unknowns and 32 stored entries per row"));
     return hipk_mg_tail_launch(levels_host, levels_dev, nlev, HIPK_MG_TAIL_MAX_LEVELS, r, z, dtype, work, work_bytes, [&](auto tag) {
         typedef decltype(tag) T;
         hipk_mg_tail_kernel<T><<<1, HIPK_THREADS, 0, (hipStream_t)stream>>>((const hipk_mg_level *)levels_dev, nlev, degree, (T)omega, (T)scale,

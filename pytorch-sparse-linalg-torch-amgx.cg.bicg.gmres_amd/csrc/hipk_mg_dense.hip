@@ -15,51 +15,6 @@
 #include "hipk_common.h"
 #include "hipk_mg_tail.h"
 
-#define HIPK_MG_DENSE_MAX_N 2048
-#define HIPK_MG_DENSE_TAIL_N 512
-#define HIPK_MG_DENSE_SEG 64
-#define HIPK_MG_DENSE_BATCH 16   // loads of cinv a thread has in flight (it divides the segment)
-
-// Rows [row0, row0 + nr) of z = cinv rs by the workgroup: rs holds r, complete in LDS behind a barrier; ps takes the
-// nr * ceil(n / 64) partials, p_q of row i at ps[q nr + i].  Thread t owns rows t, t + 256, ... of the block in the last step.
-template <typename T>
-__device__ __forceinline__ void hipk_mg_dense_rows(int n, int ld, const T *__restrict__ cinv, int row0, int nr, bool scaled, T scale, const T *rs,
-                                                   T *ps, T *z) {
-    const int nseg = (n + HIPK_MG_DENSE_SEG - 1) / HIPK_MG_DENSE_SEG;
-    const int items = nr * nseg;
-    for (int w = threadIdx.x; w < items; w += HIPK_THREADS) {
-        const int q = w / nr, i = w - q * nr;
-        const int j0 = q * HIPK_MG_DENSE_SEG;
-        const T *__restrict__ c = cinv + (int64_t)j0 * ld + (row0 + i);
-        T p = (T)0;
-        if (j0 + HIPK_MG_DENSE_SEG <= n) {   // a whole segment: HIPK_MG_DENSE_BATCH loads in flight, then their sums in order
-#pragma unroll 1
-            for (int j = 0; j < HIPK_MG_DENSE_SEG; j += HIPK_MG_DENSE_BATCH, c += (int64_t)HIPK_MG_DENSE_BATCH * ld) {
-                T a[HIPK_MG_DENSE_BATCH];
-#pragma unroll
-                for (int k = 0; k < HIPK_MG_DENSE_BATCH; ++k) a[k] = c[(int64_t)k * ld];
-#pragma unroll
-                for (int k = 0; k < HIPK_MG_DENSE_BATCH; ++k) {
-                    const T prod = a[k] * rs[j0 + j + k];
-                    p = p + prod;
-                }
-            }
-        } else {
-            for (int j = j0; j < n; ++j, c += ld) {
-                const T prod = *c * rs[j];
-                p = p + prod;
-            }
-        }
-        ps[w] = p;
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < nr; i += HIPK_THREADS) {
-        T s = (T)0;
-        for (int q = 0; q < nseg; ++q) s = s + ps[q * nr + i];
-        z[row0 + i] = scaled ? scale * s : s;
-    }
-}
-
 // z = scale * (cinv r): a workgroup owns 128 bytes of every column (16 rows fp64, 32 fp32), so a 2048-row fp64 inverse (32 MB) is
 // read by 128 workgroups, each line once.
 template <typename T>
@@ -91,16 +46,6 @@ __global__ __launch_bounds__(HIPK_THREADS) void hipk_mg_gtail_dense_kernel(const
         __syncthreads();
     }
     hipk_mg_walk_up<T, hipk_mg_glevel, hipk_mg_index_xf>(lv, nlev, m, omega, scale, rin, zout, slab, xs);
-}
-
-static int hipk_mg_dense_check(int64_t n, int64_t max_n, int64_t ld, const void *cinv, int dtype, const char *envelope) {
-    HIPK_REQUIRE(dtype == HIPK_F64 || dtype == HIPK_F32, HIPK_ERR_UNSUPPORTED, "dtype must be HIPK_F32 or HIPK_F64");
-    HIPK_REQUIRE(n >= 1, HIPK_ERR_ARG, "the dense level has no unknowns");
-    HIPK_REQUIRE(n <= max_n, HIPK_ERR_UNSUPPORTED, envelope);
-    HIPK_REQUIRE(cinv, HIPK_ERR_ARG, "null argument");
-    HIPK_REQUIRE(ld >= n && ld <= INT32_MAX, HIPK_ERR_ARG, "ld >= n is required");
-    HIPK_REQUIRE(ld % 4 == 0 && hipk_aligned16(cinv), HIPK_ERR_ALIGN, "cinv must be 16-byte aligned and ld a multiple of 4");
-    return HIPK_OK;
 }
 
 extern "C" int hipk_mg_dense_apply(int64_t n, int64_t ld, const void *cinv, double scale, const void *r, void *z, int dtype, hipk_stream_t stream) {

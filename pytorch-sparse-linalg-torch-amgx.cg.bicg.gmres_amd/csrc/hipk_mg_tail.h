@@ -22,16 +22,24 @@
 #define HIPK_MG_TAIL_MAX_N 4096
 #define HIPK_MG_TAIL_MAX_ROW 32
 
+// the dense last level (hipk_mg_dense.hip): its envelope as a launch and inside a tail, and the segments of its rounding spec
+#define HIPK_MG_DENSE_MAX_N 2048
+#define HIPK_MG_DENSE_TAIL_N 512
+#define HIPK_MG_DENSE_SEG 64
+#define HIPK_MG_DENSE_BATCH 16   // loads of cinv a thread has in flight (it divides the segment)
+
 #ifdef __HIPCC__
 template <typename T>
 struct hipk_mg_vecs {
     T *r, *z, *t, *d, *w;
+    T *e;   // the W walk's sixth vector (NV == 6): the first visit's z, kept while the second runs
 };
 
-template <typename T, typename LV>
+// NV: the vectors a level has in the slab, 5 for the V walks and 6 for the W walk
+template <typename T, typename LV, int NV = 5>
 __device__ __forceinline__ hipk_mg_vecs<T> hipk_mg_level_vecs(const LV *lv, int j, const T *rin, T *zout, T *slab) {
     int64_t off = 0;
-    for (int i = 0; i < j; ++i) off += 5 * (int64_t)((lv[i].n + 3) & ~3);
+    for (int i = 0; i < j; ++i) off += NV * (int64_t)((lv[i].n + 3) & ~3);
     const int nvp = (lv[j].n + 3) & ~3;
     T *b = slab + off;
     hipk_mg_vecs<T> v;
@@ -40,6 +48,7 @@ __device__ __forceinline__ hipk_mg_vecs<T> hipk_mg_level_vecs(const LV *lv, int 
     v.t = b + 2 * nvp;
     v.d = b + 3 * nvp;
     v.w = b + 4 * nvp;
+    v.e = (NV > 5) ? b + 5 * nvp : nullptr;
     return v;
 }
 
@@ -145,21 +154,65 @@ struct hipk_mg_index_xf {   // index arrays: amem[aptr[I] .. aptr[I + 1]) the me
     }
 };
 
+// Rows [row0, row0 + nr) of z = cinv rs by the workgroup: rs holds r, complete in LDS behind a barrier; ps takes the
+// nr * ceil(n / 64) partials, p_q of row i at ps[q nr + i].  Thread t owns rows t, t + 256, ... of the block in the last step.
+template <typename T>
+__device__ __forceinline__ void hipk_mg_dense_rows(int n, int ld, const T *__restrict__ cinv, int row0, int nr, bool scaled, T scale, const T *rs,
+                                                   T *ps, T *z) {
+    const int nseg = (n + HIPK_MG_DENSE_SEG - 1) / HIPK_MG_DENSE_SEG;
+    const int items = nr * nseg;
+    for (int w = threadIdx.x; w < items; w += HIPK_THREADS) {
+        const int q = w / nr, i = w - q * nr;
+        const int j0 = q * HIPK_MG_DENSE_SEG;
+        const T *__restrict__ c = cinv + (int64_t)j0 * ld + (row0 + i);
+        T p = (T)0;
+        if (j0 + HIPK_MG_DENSE_SEG <= n) {   // a whole segment: HIPK_MG_DENSE_BATCH loads in flight, then their sums in order
+#pragma unroll 1
+            for (int j = 0; j < HIPK_MG_DENSE_SEG; j += HIPK_MG_DENSE_BATCH, c += (int64_t)HIPK_MG_DENSE_BATCH * ld) {
+                T a[HIPK_MG_DENSE_BATCH];
+#pragma unroll
+                for (int k = 0; k < HIPK_MG_DENSE_BATCH; ++k) a[k] = c[(int64_t)k * ld];
+#pragma unroll
+                for (int k = 0; k < HIPK_MG_DENSE_BATCH; ++k) {
+                    const T prod = a[k] * rs[j0 + j + k];
+                    p = p + prod;
+                }
+            }
+        } else {
+            for (int j = j0; j < n; ++j, c += ld) {
+                const T prod = *c * rs[j];
+                p = p + prod;
+            }
+        }
+        ps[w] = p;
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < nr; i += HIPK_THREADS) {
+        T s = (T)0;
+        for (int q = 0; q < nseg; ++q) s = s + ps[q * nr + i];
+        z[row0 + i] = scaled ? scale * s : s;
+    }
+}
+
 // The walks leave and expect the last level's r and z in its slab (the caller's vectors when nlev == 1), every element written
 // and read by the thread that owns its row.
+// steps 1 - 3 on level j < nlev - 1: r of level j + 1 is complete behind the barrier it ends in
+template <typename T, typename LV, typename XF, int NV = 5>
+__device__ __forceinline__ void hipk_mg_step_down(const LV *lv, int j, int m, const T *rin, T *zout, T *slab, T *xs) {
+    const LV &L = lv[j];
+    const hipk_mg_vecs<T> v = hipk_mg_level_vecs<T, LV, NV>(lv, j, rin, zout, slab);
+    T *rc = hipk_mg_level_vecs<T, LV, NV>(lv, j + 1, rin, zout, slab).r;
+    hipk_mg_smooth<T>(L, m, v.r, v.z, v.w, xs);
+    hipk_mg_residual<T>(L, v.z, v.r, v.t, xs);
+    hipk_mg_stage(L.n, v.t, xs);
+    XF::template restrict_to<T>(L, lv[j + 1].n, xs, rc);
+    __syncthreads();
+}
+
 // down: steps 1 - 3 on levels 0 .. nlev - 2
 template <typename T, typename LV, typename XF>
 __device__ __forceinline__ void hipk_mg_walk_down(const LV *lv, int nlev, int m, const T *rin, T *zout, T *slab, T *xs) {
-    for (int j = 0; j + 1 < nlev; ++j) {
-        const LV &L = lv[j];
-        const hipk_mg_vecs<T> v = hipk_mg_level_vecs<T>(lv, j, rin, zout, slab);
-        T *rc = hipk_mg_level_vecs<T>(lv, j + 1, rin, zout, slab).r;
-        hipk_mg_smooth<T>(L, m, v.r, v.z, v.w, xs);
-        hipk_mg_residual<T>(L, v.z, v.r, v.t, xs);
-        hipk_mg_stage(L.n, v.t, xs);
-        XF::template restrict_to<T>(L, lv[j + 1].n, xs, rc);
-        __syncthreads();
-    }
+    for (int j = 0; j + 1 < nlev; ++j) hipk_mg_step_down<T, LV, XF>(lv, j, m, rin, zout, slab, xs);
 }
 
 // the last level where no off-diagonal entry is left: z = dinv r on any number of rows
@@ -173,22 +226,66 @@ __device__ __forceinline__ void hipk_mg_last_diag(const LV *lv, int nlev, T scal
     }
 }
 
+// steps 5 - 6 on level j < nlev - 1 from z of level j + 1; no barrier behind the last loop, which touches own rows only
+template <typename T, typename LV, typename XF, int NV = 5>
+__device__ __forceinline__ void hipk_mg_step_up(const LV *lv, int j, int m, T omega, T scale, const T *rin, T *zout, T *slab, T *xs) {
+    const LV &L = lv[j];
+    const hipk_mg_vecs<T> v = hipk_mg_level_vecs<T, LV, NV>(lv, j, rin, zout, slab);
+    const T *e = hipk_mg_level_vecs<T, LV, NV>(lv, j + 1, rin, zout, slab).z;
+    hipk_mg_stage(lv[j + 1].n, e, xs);
+    XF::template prolong_add<T>(L, xs, omega, v.z);
+    __syncthreads();
+    hipk_mg_residual<T>(L, v.z, v.r, v.t, xs);
+    hipk_mg_smooth<T>(L, m, v.t, v.d, v.w, xs);
+    for (int row = threadIdx.x; row < L.n; row += HIPK_THREADS) {
+        const T zz = v.z[row] + v.d[row];
+        v.z[row] = (j == 0) ? scale * zz : zz;
+    }
+}
+
 // up: steps 5 - 6 on levels nlev - 2 .. 0
 template <typename T, typename LV, typename XF>
 __device__ __forceinline__ void hipk_mg_walk_up(const LV *lv, int nlev, int m, T omega, T scale, const T *rin, T *zout, T *slab, T *xs) {
-    for (int j = nlev - 2; j >= 0; --j) {
-        const LV &L = lv[j];
-        const hipk_mg_vecs<T> v = hipk_mg_level_vecs<T>(lv, j, rin, zout, slab);
-        const T *e = hipk_mg_level_vecs<T>(lv, j + 1, rin, zout, slab).z;
-        hipk_mg_stage(lv[j + 1].n, e, xs);
-        XF::template prolong_add<T>(L, xs, omega, v.z);
-        __syncthreads();
-        hipk_mg_residual<T>(L, v.z, v.r, v.t, xs);
-        hipk_mg_smooth<T>(L, m, v.t, v.d, v.w, xs);
-        for (int row = threadIdx.x; row < L.n; row += HIPK_THREADS) {
-            const T zz = v.z[row] + v.d[row];
-            v.z[row] = (j == 0) ? scale * zz : zz;
+    for (int j = nlev - 2; j >= 0; --j) hipk_mg_step_up<T, LV, XF>(lv, j, m, omega, scale, rin, zout, slab, xs);
+}
+
+// The W walk (cycle = "W"): V(j, r) with step 4 done twice wherever level j + 1 is smoothed, that is j + 1 < nlev - 1:
+//     e = V(j + 1, rc);  rc2 = rc - A_{j+1} e;  e2 = V(j + 1, rc2);  e = e + e2
+// and once where level j + 1 is the last one.  No recursion: j is the level the workgroup stands on and bit j of `second` says
+// that level j is on the second of its two visits -- both live in SGPRs, uniform across the workgroup, so every barrier is
+// reached by all threads.  The slab has SIX vectors per level, r | z | t | d | w | e: when the first visit of level j ends, z is
+// saved in e and rc2 OVERWRITES r (out[row] = r[row] - (A z)[row], own rows, z staged in LDS), so the second visit is the
+// first one's code on the same vectors; when it ends, z = e + z.  Level 0 is visited once, so the caller's r is only read.
+// `last(NV-vectors of level nlev - 1)` is the kernel's last level -- z = dinv r or the dense step --; it is entered by all threads
+// with every earlier reader of xs behind a barrier, and must leave xs free in the same way.  nlev <= 2 is the V walk bit for bit.
+// A level j >= 1 of nlev is visited 2^(min(j, nlev - 2)) times: the entries refuse more than HIPK_MG_TAIL_W_MAX_LEVELS levels.
+template <typename T, typename LV, typename XF, typename LAST>
+__device__ __forceinline__ void hipk_mg_walk_w(const LV *lv, int nlev, int m, T omega, T scale, const T *rin, T *zout, T *slab, T *xs,
+                                               LAST last) {
+    unsigned second = 0u;
+    int j = 0;
+    for (;;) {
+        for (; j + 1 < nlev; ++j) hipk_mg_step_down<T, LV, XF, 6>(lv, j, m, rin, zout, slab, xs);
+        last(hipk_mg_level_vecs<T, LV, 6>(lv, nlev - 1, rin, zout, slab));
+        // level j is complete: up, until a smoothed level ends its first visit
+        bool again = false;
+        while (j > 0) {
+            if (j + 1 < nlev) {
+                const hipk_mg_vecs<T> v = hipk_mg_level_vecs<T, LV, 6>(lv, j, rin, zout, slab);
+                if (!(second & (1u << j))) {
+                    for (int row = threadIdx.x; row < lv[j].n; row += HIPK_THREADS) v.e[row] = v.z[row];
+                    hipk_mg_residual<T>(lv[j], v.z, v.r, v.r, xs);
+                    second |= 1u << j;
+                    again = true;
+                    break;
+                }
+                for (int row = threadIdx.x; row < lv[j].n; row += HIPK_THREADS) v.z[row] = v.e[row] + v.z[row];
+                second &= ~(1u << j);
+            }
+            --j;
+            hipk_mg_step_up<T, LV, XF, 6>(lv, j, m, omega, scale, rin, zout, slab, xs);
         }
+        if (!again) break;
     }
 }
 #endif
@@ -220,12 +317,46 @@ static inline int hipk_mg_gtail_check(const hipk_mg_glevel *lv, int nsparse, int
     return HIPK_OK;
 }
 
-// the bytes of `work` for levels of n_j unknowns: five vectors per level, rounded up to 256; 0 for bad arguments
+// the same for nlev box levels (hipk_mg_tail_apply and its W twin; `envelope` names the entry)
+static inline int hipk_mg_tail_check(const hipk_mg_level *lv, int nlev, int degree, int dtype, const char *envelope) {
+    HIPK_REQUIRE(lv && nlev >= 1 && nlev <= HIPK_MG_TAIL_MAX_LEVELS, HIPK_ERR_ARG, "1 .. 16 levels");
+    HIPK_REQUIRE(degree >= 1 && degree <= 32, HIPK_ERR_ARG, "degree must be in [1, 32]");
+    HIPK_REQUIRE(dtype == HIPK_F64 || dtype == HIPK_F32, HIPK_ERR_UNSUPPORTED, "dtype must be HIPK_F32 or HIPK_F64");
+    for (int j = 0; j < nlev; ++j) {
+        const hipk_mg_level &L = lv[j];
+        HIPK_REQUIRE(L.n0 >= 1 && L.n1 >= 1 && L.n2 >= 1 && L.n >= 1 && (int64_t)L.n0 * L.n1 * L.n2 == L.n, HIPK_ERR_ARG,
+                     "a level's n is not the product of its dimensions");
+        HIPK_REQUIRE(L.n <= HIPK_MG_TAIL_MAX_N && L.max_row <= HIPK_MG_TAIL_MAX_ROW, HIPK_ERR_UNSUPPORTED, envelope);
+        HIPK_REQUIRE(L.crow && L.col && L.val && L.dinv, HIPK_ERR_ARG, "null pointer in a level");
+        if (j + 1 < nlev)
+            HIPK_REQUIRE(lv[j + 1].n0 == (L.n0 + 1) / 2 && lv[j + 1].n1 == (L.n1 + 1) / 2 && lv[j + 1].n2 == (L.n2 + 1) / 2, HIPK_ERR_ARG,
+                         "a level's dimensions are not ceil(d / 2) of the level above");
+    }
+    HIPK_REQUIRE(lv[nlev - 1].n == 1, HIPK_ERR_ARG, "the last level must have one unknown");
+    return HIPK_OK;
+}
+
+// the dense last level of hipk_mg_dense_apply (max_n 2048) and of the tails that end in one (512); `envelope` names the entry
+static inline int hipk_mg_dense_check(int64_t n, int64_t max_n, int64_t ld, const void *cinv, int dtype, const char *envelope) {
+    HIPK_REQUIRE(dtype == HIPK_F64 || dtype == HIPK_F32, HIPK_ERR_UNSUPPORTED, "dtype must be HIPK_F32 or HIPK_F64");
+    HIPK_REQUIRE(n >= 1, HIPK_ERR_ARG, "the dense level has no unknowns");
+    HIPK_REQUIRE(n <= max_n, HIPK_ERR_UNSUPPORTED, envelope);
+    HIPK_REQUIRE(cinv, HIPK_ERR_ARG, "null argument");
+    HIPK_REQUIRE(ld >= n && ld <= INT32_MAX, HIPK_ERR_ARG, "ld >= n is required");
+    HIPK_REQUIRE(ld % 4 == 0 && hipk_aligned16(cinv), HIPK_ERR_ALIGN, "cinv must be 16-byte aligned and ld a multiple of 4");
+    return HIPK_OK;
+}
+
+// the W entries (hipk_mg_w.hip) take fewer levels: the last one of nlev is visited 2^(nlev - 2) times in one launch
+#define HIPK_MG_TAIL_W_MAX_LEVELS 12
+
+// the bytes of `work` for levels of n_j unknowns: `nv` vectors per level -- five, six for the W walk --, rounded up to 256; 0 for
+// bad arguments
 template <typename LV>
-static inline size_t hipk_mg_work_bytes(const LV *lv, int nlev, int max_levels, int dtype) {
+static inline size_t hipk_mg_work_bytes(const LV *lv, int nlev, int max_levels, int dtype, int nv = 5) {
     if (!lv || nlev < 1 || nlev > max_levels) return 0;
     size_t el = 0;
-    for (int j = 0; j < nlev; ++j) el += 5 * (size_t)(((int64_t)lv[j].n + 3) & ~(int64_t)3);
+    for (int j = 0; j < nlev; ++j) el += (size_t)nv * (size_t)(((int64_t)lv[j].n + 3) & ~(int64_t)3);
     return (el * (dtype == HIPK_F64 ? 8 : 4) + 255) & ~(size_t)255;
 }
 
@@ -233,12 +364,12 @@ static inline size_t hipk_mg_work_bytes(const LV *lv, int nlev, int max_levels, 
 // caller's pointers, then launch(T()) with T = double or float, which starts the one workgroup of the entry's kernel<T>.
 template <typename LV, typename F>
 static inline int hipk_mg_tail_launch(const LV *levels_host, const void *levels_dev, int nlev, int max_levels, const void *r, void *z, int dtype,
-                                      void *work, size_t work_bytes, F launch) {
+                                      void *work, size_t work_bytes, F launch, int nv = 5) {
     HIPK_REQUIRE(levels_dev && r && z && work, HIPK_ERR_ARG, "null argument");
     HIPK_REQUIRE(hipk_aligned16(r) && hipk_aligned16(z) && hipk_aligned16(levels_dev) && (((uintptr_t)work) & 255u) == 0, HIPK_ERR_ALIGN,
                  "r, z and the level blob must be 16-byte aligned, work 256-byte aligned");
     HIPK_REQUIRE(r != z, HIPK_ERR_ARG, "r and z must be distinct");
-    HIPK_REQUIRE(work_bytes >= hipk_mg_work_bytes(levels_host, nlev, max_levels, dtype), HIPK_ERR_WORKSPACE, "work buffer too small");
+    HIPK_REQUIRE(work_bytes >= hipk_mg_work_bytes(levels_host, nlev, max_levels, dtype, nv), HIPK_ERR_WORKSPACE, "work buffer too small");
     if (dtype == HIPK_F64)
         launch(double());
     else

@@ -72,6 +72,9 @@ SYMBOLS = [
     "hipk_mg_dense_apply", "hipk_mg_gtail_dense_work_bytes", "hipk_mg_gtail_dense_apply",
     # ... the refresh of a hierarchy for new matrix values: one level's dinv, Gershgorin bound and diagonal check
     "hipk_mg_level_scan_work_bytes", "hipk_mg_level_scan",
+    # ... the W-cycle: the sum of the two coarse corrections, and the three tails with the W walk in one launch
+    "hipk_mg_add", "hipk_mg_tail_work_bytes_w", "hipk_mg_tail_apply_w", "hipk_mg_gtail_work_bytes_w", "hipk_mg_gtail_apply_w",
+    "hipk_mg_gtail_dense_work_bytes_w", "hipk_mg_gtail_dense_apply_w",
 ]
 
 
@@ -341,6 +344,11 @@ def lib():
     L.hipk_mg_level_scan_work_bytes.argtypes = [i64]
     L.hipk_mg_level_scan_work_bytes.restype = ctypes.c_size_t
     L.hipk_mg_level_scan.argtypes = [i64, vp, vp, vp, i32, i32, vp, vp, vp, ctypes.c_size_t, vp]
+    L.hipk_mg_add.argtypes = [i64, vp, vp, i32, vp]
+    for name in ("hipk_mg_tail", "hipk_mg_gtail", "hipk_mg_gtail_dense"):      # the W twins: their V entries' signatures
+        getattr(L, name + "_work_bytes_w").argtypes = getattr(L, name + "_work_bytes").argtypes
+        getattr(L, name + "_work_bytes_w").restype = ctypes.c_size_t
+        getattr(L, name + "_apply_w").argtypes = getattr(L, name + "_apply").argtypes
     _lib = L
     return L
 
@@ -778,12 +786,14 @@ class _MgDescriptors:
     """What `MgTail` and `MgGTail` share: the descriptors of a run of levels on the host (`host`) and as one device blob (`blob`),
     the tensors they point into, and `work_bytes` of the entry point that takes them."""
 
-    def _build(self, struct, levels, nsparse: int, degree: int, dtype, device, work_bytes: str) -> None:
+    def _build(self, struct, levels, nsparse: int, degree: int, dtype, device, work_bytes: str, cycle: str = "V") -> None:
         """Levels [0, nsparse) are dicts with int32 `crow` / `col`, `val`, `dinv` (contiguous device tensors of one dtype),
         `max_row` and the smoother's `c0`, `c1`, `c2` (absent or None where there is no smoother): the fields both descriptor
         structs have.  A level past them is a dict of which only `n` is read.  `self._level(j, d, lev, nc)` then fills what only
-        one kind of level has; `nc` is the next level's size, None on the last."""
-        self.nlev, self.degree, self.dtype, self.device = len(levels), int(degree), dtype, device
+        one kind of level has; `nc` is the next level's size, None on the last.  `cycle` "W": `work_bytes` of the entry's W twin
+        (six vectors per level, at most `MG_TAIL_W_MAX_LEVELS` levels)."""
+        assert cycle in ("V", "W"), cycle
+        self.nlev, self.degree, self.dtype, self.device, self.cycle = len(levels), int(degree), dtype, device, cycle
         sizes = [int(lev["dinv"].numel()) for lev in levels[:nsparse]] + [int(lev["n"]) for lev in levels[nsparse:]]
         self.host = (struct * self.nlev)()
         self._keep = []
@@ -806,7 +816,7 @@ class _MgDescriptors:
             self._level(j, d, lev, sizes[j + 1] if j + 1 < self.nlev else None)
         raw = torch.frombuffer(bytearray(bytes(self.host)), dtype=torch.uint8)
         self.blob = raw.to(device)
-        self.work_bytes = int(getattr(lib(), work_bytes)(self.host, self.nlev, _dtype_code(dtype)))
+        self.work_bytes = int(getattr(lib(), work_bytes + ("_w" if cycle == "W" else ""))(self.host, self.nlev, _dtype_code(dtype)))
 
 
 class MgTail(_MgDescriptors):
@@ -814,8 +824,8 @@ class MgTail(_MgDescriptors):
     into.  `levels`: per level a dict with int32 `crow` / `col`, `val`, `dinv` (contiguous device tensors of one dtype), `dims`
     (2 or 3 entries), `max_row` and the smoother's `c0`, `c1`, `c2` (None on the last level, which has one unknown)."""
 
-    def __init__(self, levels, degree: int):
-        self._build(MgLevel, levels, len(levels), degree, levels[0]["val"].dtype, levels[0]["val"].device, "hipk_mg_tail_work_bytes")
+    def __init__(self, levels, degree: int, cycle: str = "V"):
+        self._build(MgLevel, levels, len(levels), degree, levels[0]["val"].dtype, levels[0]["val"].device, "hipk_mg_tail_work_bytes", cycle)
 
     def _level(self, j, d, lev, nc) -> None:
         d.n0, d.n1, d.n2 = _grid3(lev["dims"])
@@ -824,6 +834,7 @@ class MgTail(_MgDescriptors):
 
 def _mg_tail_call(symbol: str, tail, omega: float, scale: float, r: torch.Tensor, z: torch.Tensor, work, *last) -> torch.Tensor:
     """The call of a tail entry point `symbol`; `last` are its arguments between `scale` and `r`."""
+    assert tail.cycle == ("W" if symbol.endswith("_w") else "V"), f"the tail was built for cycle {tail.cycle!r}: its workspace is another"
     n = int(tail.host[0].n)
     for v in (r, z):
         assert v.is_cuda and v.is_contiguous() and v.dtype == tail.dtype and v.device == tail.device and v.numel() == n
@@ -839,6 +850,23 @@ def mg_tail_apply(tail: MgTail, omega: float, scale: float, r: torch.Tensor, z: 
                   work: Optional[torch.Tensor] = None) -> torch.Tensor:
     """z = scale * V(0, r) over the tail's levels in one launch (hipk_mg_tail_apply), on the current stream."""
     return _mg_tail_call("hipk_mg_tail_apply", tail, omega, scale, r, z, work)
+
+
+MG_TAIL_W_MAX_LEVELS = 12  # the W entries' level count: the last of nlev levels is visited 2^(nlev - 2) times in the one launch
+
+
+def mg_tail_apply_w(tail: MgTail, omega: float, scale: float, r: torch.Tensor, z: torch.Tensor,
+                    work: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """z = scale * W(0, r) over the levels of a tail built with cycle="W", in one launch (hipk_mg_tail_apply_w)."""
+    return _mg_tail_call("hipk_mg_tail_apply_w", tail, omega, scale, r, z, work)
+
+
+def mg_add(e2: torch.Tensor, e: torch.Tensor) -> torch.Tensor:
+    """e = e + e2 in place (hipk_mg_add): the sum of the W-cycle's two coarse corrections."""
+    assert e.is_cuda and e.is_contiguous() and e2.is_contiguous() and e2.dtype == e.dtype and e2.device == e.device and e2.numel() == e.numel()
+    with torch.cuda.device(e.device):
+        _check(lib().hipk_mg_add(e.numel(), e2.data_ptr(), e.data_ptr(), _dtype_code(e.dtype), _stream(e.device)), "hipk_mg_add")
+    return e
 
 
 def _check_index(name: str, a: torch.Tensor, numel: int, like: torch.Tensor) -> None:
@@ -881,13 +909,13 @@ class MgGTail(_MgDescriptors):
     `cinv` (with `ld`): the descriptors of hipk_mg_gtail_dense_apply instead.  The last entry of `levels` is then the dense level,
     a dict of which only `n` is read, and `cinv` its stored inverse (`mg_dense_apply`'s layout)."""
 
-    def __init__(self, levels, degree: int, cinv: Optional[torch.Tensor] = None, ld: int = 0):
+    def __init__(self, levels, degree: int, cinv: Optional[torch.Tensor] = None, ld: int = 0, cycle: str = "V"):
         self.cinv, self.ld = cinv, int(ld)
         if cinv is not None:
             _check_cinv(cinv, int(levels[-1]["n"]), self.ld)
         like = levels[0]["val"] if cinv is None else cinv
         self._build(MgGLevel, levels, len(levels) - (cinv is not None), degree, like.dtype, like.device,
-                    "hipk_mg_gtail_work_bytes" if cinv is None else "hipk_mg_gtail_dense_work_bytes")
+                    "hipk_mg_gtail_work_bytes" if cinv is None else "hipk_mg_gtail_dense_work_bytes", cycle)
 
     def _level(self, j, d, lev, nc) -> None:
         if nc is not None:
@@ -903,6 +931,13 @@ def mg_gtail_apply(tail: MgGTail, omega: float, scale: float, r: torch.Tensor, z
     """z = scale * V(0, r) over the tail's index-array levels in one launch (hipk_mg_gtail_apply), on the current stream."""
     assert tail.cinv is None, "the tail was built with a dense level: mg_gtail_dense_apply"
     return _mg_tail_call("hipk_mg_gtail_apply", tail, omega, scale, r, z, work)
+
+
+def mg_gtail_apply_w(tail: MgGTail, omega: float, scale: float, r: torch.Tensor, z: torch.Tensor,
+                     work: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """z = scale * W(0, r) over the index-array levels of a tail built with cycle="W", in one launch (hipk_mg_gtail_apply_w)."""
+    assert tail.cinv is None, "the tail was built with a dense level: mg_gtail_dense_apply_w"
+    return _mg_tail_call("hipk_mg_gtail_apply_w", tail, omega, scale, r, z, work)
 
 
 MG_DENSE_MAX_N = 2048     # the envelope of hipk_mg_dense_apply: unknowns of the dense level ...
@@ -932,6 +967,13 @@ def mg_gtail_dense_apply(tail: MgGTail, omega: float, scale: float, r: torch.Ten
     """z = scale * V(0, r) over the tail's index-array levels and its dense last level in one launch (hipk_mg_gtail_dense_apply)."""
     assert tail.cinv is not None, "the tail was built without a dense level"
     return _mg_tail_call("hipk_mg_gtail_dense_apply", tail, omega, scale, r, z, work, tail.cinv.data_ptr(), tail.ld)
+
+
+def mg_gtail_dense_apply_w(tail: MgGTail, omega: float, scale: float, r: torch.Tensor, z: torch.Tensor,
+                           work: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """z = scale * W(0, r) over a tail built with cycle="W" and a dense last level, in one launch (hipk_mg_gtail_dense_apply_w)."""
+    assert tail.cinv is not None, "the tail was built without a dense level"
+    return _mg_tail_call("hipk_mg_gtail_dense_apply_w", tail, omega, scale, r, z, work, tail.cinv.data_ptr(), tail.ld)
 
 
 def mg_level_scan_work_bytes(n: int) -> int:

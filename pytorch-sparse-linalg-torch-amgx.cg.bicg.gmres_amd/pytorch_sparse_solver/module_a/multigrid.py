@@ -19,7 +19,7 @@ import torch
 from .preconditioners import ChebyshevPreconditioner, _diagonal
 
 __all__ = ["AggregationMultigridPreconditioner", "MG_TAIL_MAX_ROWS", "MG_GRAPH_MAX_LEVELS", "MG_DENSE_MAX_ROWS", "MG_DENSE_TAIL_ROWS",
-           "pairwise_aggregates"]
+           "MG_W_MAX_LEVELS", "pairwise_aggregates"]
 
 # The default of `tail_rows`: levels of at most this many unknowns run inside the one-launch tail kernel (0: none do).
 # Measured (tools/mg_probe.py, profiles/mg_probe.txt, MI355X, fp64, 5-point Poisson 2000 x 2000, degree 1, device time per apply):
@@ -41,6 +41,11 @@ MG_GRAPH_MAX_LEVELS = 48
 MG_DENSE_MAX_ROWS = 2048
 MG_DENSE_TAIL_ROWS = 512
 DENSE_SEGMENT = 64        # the columns of one partial sum of the dense step
+
+# `cycle="W"`: a hierarchy of more levels than this is refused.  Level l is visited 2^l times, as launches wherever the one-launch
+# tail does not take the level (`_hipk.MG_TAIL_W_MAX_LEVELS`, 12): at 16 levels the last one is visited 2^14 times per apply, and
+# `from_graph` without `coarse_rows` builds 33 - 39 levels on 1000^2 ... 4000^2 grids, where an apply would never end
+MG_W_MAX_LEVELS = 16
 
 
 def _grid3(dims):
@@ -273,6 +278,18 @@ class AggregationMultigridPreconditioner:
         6. t = r - A_l z;  d = S_l(t);  z = z + d
     and M(r) = scale * V(0, r) when scale != 1.
 
+    `cycle` ("V", the default, or "W"; the attribute `cycle`).  "W" changes step 4 where level l + 1 is a smoothed level -- not
+    the last one, which is exact or diagonal and is visited once --:
+        4.  e   = V(l + 1, rc)
+        4a. rc2 = rc - A_{l+1} e                  (the SpMV's residual form, as step 2)
+        4b. e2  = V(l + 1, rc2)
+        4c. e   = e + e2                          (one rounding)
+    so level l is visited 2^l times.  The V-cycle's iteration count grows with the grid over unsmoothed aggregates; the W-cycle's
+    is nearly independent of it.  `omega`, `scale`, `normalize` (the estimate uses the selected cycle), `applies` and `update`
+    (which keeps the cycle) are unchanged, and `cycle="V"` is the object without the keyword bit for bit.  A W hierarchy of more
+    than `MG_W_MAX_LEVELS` (16) levels is a ValueError: `from_graph` without `coarse_rows` coarsens by two unknowns per level near
+    the bottom and builds dozens of levels on large matrices, so `cycle="W"` there needs `coarse_rows`.
+
     `normalize`.  The reference decides `info` from ||M (b - A x)|| <= tol ||b|| (TSL:1007-1014) and this M approximates A^-1, norm
     about 1 / lambda_min(A): unscaled, a converged solve mostly returns info = -1.  `normalize=True` estimates the norm of the
     unscaled cycle by eight steps of the power iteration from v = ones / sqrt(n) (w = M_1 v, lambda = ||w||, v = w / lambda; the
@@ -286,7 +303,11 @@ class AggregationMultigridPreconditioner:
     result; when one of them has a row of more than 32 stored entries the kernel's envelope is left and they all stay launches.
     `tail_from` is the first level the tail kernel runs, or None.  Level 0 uses `_hipk.handle_for(A)`, the handle a solve of `A` holds; the object owns a `CsrHandle` per coarse level
     (the handle cache holds eight entries, a deep hierarchy would flush it) and all work vectors.  CPU vectors run torch ops in
-    exactly the order above, with `_SpecSpmv` for the row sums.
+    exactly the order above, with `_SpecSpmv` for the row sums.  With `cycle="W"` step 4a is the SpMV's residual form on level
+    l + 1's handle and 4c `hipk_mg_add`; the tail is `hipk_mg_tail_apply_w` (or its `gtail` / `gtail_dense` twin), which runs the
+    whole W walk over its levels in its one launch and takes at most `_hipk.MG_TAIL_W_MAX_LEVELS` (12) levels, else they stay launches.
+    The tail is launched once per visit of its first level: twice per visit of level `tail_from - 1` when that first level is
+    smoothed, with 4a and 4c between and behind the two launches.
 
     `from_graph(A, ...)` builds the same object without a grid, from aggregates of the matrix graph (see there).
     `update(A_new)` refreshes an object from either constructor for new values on the same sparsity pattern: the aggregates and
@@ -296,10 +317,17 @@ class AggregationMultigridPreconditioner:
     `coarse_rows` and `dense` (`from_graph(coarse_rows=K)`: K, and whether the last level is solved with `levels[-1].cinv`),
     `handshake_rounds` (graph: per level the rounds of each matching pass), `scale`, `applies`, `tail_rows`, `tail_from`,
     `launches_per_apply` (the launches of one device apply, a Chebyshev step counted as the one launch it is where the SpMV has
-    the Chebyshev epilogue: 2 degree + 7 per level above the tail -- above L without one --, then one)."""
+    the Chebyshev epilogue: 2 degree + 7 per level above the tail -- above L without one --, then one).
+
+    `launches_per_apply` with `cycle="W"`.  k = 2 degree + 7, L the last level, T = `tail_from`, or L without a tail.  Level
+    l < T is visited 2^l times at k launches; each second visit (2^(l-1) of them on level l >= 1) adds 4a and 4c; the end -- the
+    tail or the last level -- is one launch per visit of level T:
+        (2^T - 1) k + max(2^T - 2, 0) + E,    E = 1 if T == 0;  2^(T-1) if T == L;  2^T + 2^T otherwise
+    (T == L: the last level, once per visit of level L - 1; otherwise the tail's first level is smoothed: 2^T launches of the
+    tail and 2^(T-1) times 4a and 4c around them)."""
 
     def __init__(self, A: torch.Tensor, grid, degree: int = 1, ratio: float = 4.0, omega: float = 1.8, normalize: bool = True,
-                 tail_rows=None):
+                 tail_rows=None, cycle="V"):
         self._check_matrix(A)
         try:
             dims = tuple(int(v) for v in grid)
@@ -309,11 +337,11 @@ class AggregationMultigridPreconditioner:
             raise ValueError(f"grid must have 2 or 3 dimensions, got {len(dims)}")
         if min(dims) < 1 or math.prod(dims) != A.shape[0]:
             raise ValueError(f"grid {dims} does not have the matrix's {A.shape[0]} points")
-        self._set_up(A, dims, degree, ratio, omega, normalize, tail_rows, None, None)
+        self._set_up(A, dims, degree, ratio, omega, normalize, tail_rows, None, None, cycle)
 
     @classmethod
     def from_graph(cls, A: torch.Tensor, degree: int = 1, ratio: float = 4.0, omega: float = 1.8, normalize: bool = True,
-                   tail_rows=None, passes: int = 2, theta: float = 0.25, coarse_rows=None):
+                   tail_rows=None, passes: int = 2, theta: float = 0.25, coarse_rows=None, cycle="V"):
         """The same preconditioner for ANY square `A`: the aggregates come from the matrix graph, not from a grid.
 
         Level l's aggregates are `pairwise_aggregates(A_l, passes, theta)` (pairwise matching on strong couplings, aggregates of
@@ -322,7 +350,7 @@ class AggregationMultigridPreconditioner:
         Coarsening ends at the first level whose graph has no pair left, which is the level without a non-zero off-diagonal entry
         -- one unknown for a connected graph, one per component otherwise --; that level is z = dinv r.  More than
         `MG_GRAPH_MAX_LEVELS` (48) levels is a ValueError: the coarsening has stalled (a star graph loses one pair per pass).
-        Smoother, V-cycle, `normalize`, `tail_rows`, `applies` and `launches_per_apply` are the grid object's; every level has
+        Smoother, cycle (`cycle`), `normalize`, `tail_rows`, `applies` and `launches_per_apply` are the grid object's; every level has
         `dims == (n,)` and, except the last, `agg` (int64, the map to the next level).  The device transfers are
         `hipk_mg_restrict_agg` / `hipk_mg_prolong_add_agg`, the tail `hipk_mg_gtail_apply` (at most 32 levels, else launches).
 
@@ -350,7 +378,7 @@ class AggregationMultigridPreconditioner:
             raise ValueError(f"passes must be 1, 2, 3 or 4, got {passes}")
         if not 0.0 <= float(theta) <= 1.0:
             raise ValueError(f"theta must be in [0, 1], got {theta}")
-        self._set_up(A, (int(A.shape[0]),), degree, ratio, omega, normalize, tail_rows, (int(passes), float(theta)), coarse_rows)
+        self._set_up(A, (int(A.shape[0]),), degree, ratio, omega, normalize, tail_rows, (int(passes), float(theta)), coarse_rows, cycle)
         return self
 
     @staticmethod
@@ -362,9 +390,12 @@ class AggregationMultigridPreconditioner:
         if A.dtype not in (torch.float64, torch.float32):
             raise ValueError(f"AggregationMultigridPreconditioner needs a float64 or float32 matrix, not {A.dtype}")
 
-    def _set_up(self, A, dims, degree, ratio, omega, normalize, tail_rows, graph, coarse_rows) -> None:
+    def _set_up(self, A, dims, degree, ratio, omega, normalize, tail_rows, graph, coarse_rows, cycle) -> None:
         """Everything after the argument checks of the two constructors.  `graph`: None on a grid, else (passes, theta);
         `coarse_rows`: None, or on a graph the largest dense last level."""
+        if not (isinstance(cycle, str) and cycle in ("V", "W")):
+            raise ValueError(f'cycle must be "V" or "W", got {cycle!r}')
+        self.cycle = cycle
         if not 1 <= int(degree) <= 32:
             raise ValueError("degree must be in [1, 32]")
         if not float(omega) > 0.0:
@@ -399,6 +430,11 @@ class AggregationMultigridPreconditioner:
             if rounds is not None:
                 self.handshake_rounds.append(rounds)
         L = len(self.levels) - 1
+        if cycle == "W" and len(self.levels) > MG_W_MAX_LEVELS:
+            raise ValueError(f'AggregationMultigridPreconditioner: cycle="W" takes at most {MG_W_MAX_LEVELS} levels (level l is visited '
+                             f"2^l times), this hierarchy has {len(self.levels)} (sizes {[v.n for v in self.levels[:4]]} ...); "
+                             "from_graph(coarse_rows=K) cuts the small levels off")
+        from .. import _hipk          # constants only: the library is not loaded
         # the tail: the levels from the first one of at most `tail_rows` unknowns on, when they all fit the kernel's envelope
         tail_rows = MG_TAIL_MAX_ROWS if tail_rows is None else int(tail_rows)
         if tail_rows < 0:
@@ -406,9 +442,15 @@ class AggregationMultigridPreconditioner:
         self.tail_rows = min(tail_rows, 4096)
         first = next((l for l, lev in enumerate(self.levels) if lev.n <= self.tail_rows), None)
         fits = first is not None and all(lev.max_row <= 32 for lev in self.levels[first:len(self.levels) - self.dense]) and \
-            (not self.graph or len(self.levels) - first <= 32) and (not self.dense or self.levels[-1].n <= MG_DENSE_TAIL_ROWS)
+            (not self.graph or len(self.levels) - first <= 32) and (not self.dense or self.levels[-1].n <= MG_DENSE_TAIL_ROWS) and \
+            (cycle == "V" or len(self.levels) - first <= _hipk.MG_TAIL_W_MAX_LEVELS)
         self.tail_from = first if fits else None
-        self.launches_per_apply = (L if self.tail_from is None else self.tail_from) * (2 * self.degree + 7) + 1
+        T, k = L if self.tail_from is None else self.tail_from, 2 * self.degree + 7
+        if cycle == "V":
+            self.launches_per_apply = T * k + 1
+        else:
+            end = 1 if T == 0 else (2 ** (T - 1) if T == L else 2 ** T + 2 ** T)
+            self.launches_per_apply = (2 ** T - 1) * k + max(2 ** T - 2, 0) + end
         self._cpu = None      # per level: (spec SpMV, the aggregate of every row, step 3's gather indices)
         self._dev = None      # per level: handle and work vectors of the device apply
         self._keep = {}       # what an `update` reuses: the device index arrays and work vectors, by (level, name)
@@ -550,6 +592,9 @@ class AggregationMultigridPreconditioner:
         for has, idx in members[1:]:
             rc = torch.where(has, rc + t[idx], rc)
         e = self._v_torch(l + 1, rc)
+        if self.cycle == "W" and l + 1 < len(self.levels) - 1:      # steps 4a - 4c: the smoothed level l + 1 a second time
+            rc2 = rc - self.levels[l + 1].smoother._cpu[0](e)
+            e = e + self._v_torch(l + 1, rc2)
         z = z + (torch.tensor(self.omega, dtype=r.dtype) * e[agg])
         t = r - spmv(z)
         return z + S(t)
@@ -590,6 +635,8 @@ class AggregationMultigridPreconditioner:
                     s = {"dinv": _hipk.aligned(lev.dinv.to(device=dev, dtype=dt))}
                 if l and l <= tf:
                     s["r"], s["z"] = vec("r"), vec("z")
+                    if self.cycle == "W" and l < len(self.levels) - 1:      # a smoothed level: rc2 and e2 of its second visit
+                        s["r2"], s["z2"] = vec("r2"), vec("z2")
                 if lev.agg is not None:          # the transfers' index arrays: agg, and the members aggregate by aggregate
                     if (l, "agg") not in self._keep:
                         agg = lev.agg.to(dev)
@@ -603,6 +650,8 @@ class AggregationMultigridPreconditioner:
                     crow, col = self._int32_pattern(l)
                     s.update(crow=crow, col=col,
                              val=_hipk.aligned(c.values()), dims=lev.dims, max_row=lev.max_row, c0=lev.c0, c1=lev.c1, c2=lev.c2)
+                    if "r2" in s:                         # the W-cycle's step 4a on the tail's first level is a launch
+                        s["h"] = _hipk.CsrHandle(c.crow_indices(), c.col_indices(), c.values(), c.shape)
                 elif l < min(tf, len(self.levels) - 1):   # a level of the launch sequence that has a next one
                     s["h"] = _hipk.handle_for(self._A) if l == 0 else \
                         _hipk.CsrHandle(c.crow_indices(), c.col_indices(), c.values(), c.shape)
@@ -618,17 +667,18 @@ class AggregationMultigridPreconditioner:
                 st.append(s)
             last = st[-1]
             if tf < len(self.levels):
+                w = "_w" if self.cycle == "W" else ""      # the W tails: the same descriptors, a larger workspace
                 if self.dense:
-                    tail = _hipk.MgGTail(st[tf:], self.degree, cinv=last["cinv"], ld=last["ld"])
-                    self._end = lambda omega, scale, r, z: _hipk.mg_gtail_dense_apply(tail, omega, scale, r, z, work=work)
+                    tail = _hipk.MgGTail(st[tf:], self.degree, cinv=last["cinv"], ld=last["ld"], cycle=self.cycle)
+                    self._end = lambda omega, scale, r, z: getattr(_hipk, "mg_gtail_dense_apply" + w)(tail, omega, scale, r, z, work=work)
                 elif self.graph:
-                    tail = _hipk.MgGTail(st[tf:], self.degree)
-                    self._end = lambda omega, scale, r, z: _hipk.mg_gtail_apply(tail, omega, scale, r, z, work=work)
+                    tail = _hipk.MgGTail(st[tf:], self.degree, cycle=self.cycle)
+                    self._end = lambda omega, scale, r, z: getattr(_hipk, "mg_gtail_apply" + w)(tail, omega, scale, r, z, work=work)
                 else:
-                    tail = _hipk.MgTail(st[tf:], self.degree)
-                    self._end = lambda omega, scale, r, z: _hipk.mg_tail_apply(tail, omega, scale, r, z, work=work)
+                    tail = _hipk.MgTail(st[tf:], self.degree, cycle=self.cycle)
+                    self._end = lambda omega, scale, r, z: getattr(_hipk, "mg_tail_apply" + w)(tail, omega, scale, r, z, work=work)
                 self._tail = tail
-                work = self._kept(tf, "tail work", lambda: torch.empty(tail.work_bytes, dtype=torch.uint8, device=dev))
+                work = self._kept(tf, "tail work" + w, lambda: torch.empty(tail.work_bytes, dtype=torch.uint8, device=dev))
             elif self.dense:
                 self._end = lambda omega, scale, r, z: _hipk.mg_dense_apply(last["cinv"], last["ld"], scale, r, z)
             else:
@@ -642,20 +692,28 @@ class AggregationMultigridPreconditioner:
         L = len(levels) - 1 if self.tail_from is None else self.tail_from      # the last level the launches reach
         v = _hipk.aligned(v)
         out = torch.empty_like(v)
-        r = lambda l: v if l == 0 else st[l]["r"]
-        z = lambda l: out if l == 0 else st[l]["z"]
         smooth = lambda l, src, dst: _hipk.cheb_apply(st[l]["h"], self.degree, st[l]["dinv"], levels[l].smoother._coef, src,
                                                       work=st[l]["work"], out=dst)
-        for l in range(L):                                                      # steps 1 - 3
-            smooth(l, r(l), z(l))
-            _hipk.spmv_residual(st[l]["h"], z(l), r(l), st[l]["t"])
-            st[l]["restrict"](st[l]["t"], r(l + 1))
-        self._end(self.omega, self.scale if L == 0 else 1.0, r(L), z(L))        # step 4: level L, or the tail from it on
-        for l in range(L - 1, -1, -1):                                          # steps 5 - 6
-            st[l]["prolong_add"](self.omega, z(l + 1), z(l))
-            _hipk.spmv_residual(st[l]["h"], z(l), r(l), st[l]["t"])
-            smooth(l, st[l]["t"], st[l]["d"])
-            _hipk.mg_correct(self.scale if l == 0 else 1.0, st[l]["d"], z(l))
+
+        def visit(l, r, z):          # z = V(l, r), scaled on level 0
+            if l == L:               # level L, or the tail from it on
+                self._end(self.omega, self.scale if L == 0 else 1.0, r, z)
+                return
+            s, c = st[l], st[l + 1]
+            smooth(l, r, z)                                                     # steps 1 - 3
+            _hipk.spmv_residual(s["h"], z, r, s["t"])
+            s["restrict"](s["t"], c["r"])
+            visit(l + 1, c["r"], c["z"])                                        # step 4
+            if "r2" in c:                                                       # steps 4a - 4c of the W-cycle
+                _hipk.spmv_residual(c["h"], c["z"], c["r"], c["r2"])
+                visit(l + 1, c["r2"], c["z2"])
+                _hipk.mg_add(c["z2"], c["z"])
+            s["prolong_add"](self.omega, c["z"], z)                             # steps 5 - 6
+            _hipk.spmv_residual(s["h"], z, r, s["t"])
+            smooth(l, s["t"], s["d"])
+            _hipk.mg_correct(self.scale if l == 0 else 1.0, s["d"], z)
+
+        visit(0, v, out)
         return out
 
     def __call__(self, v):

@@ -39,6 +39,12 @@ with a synchronised clock around each step, so its total is above an unclocked u
 iterations), with the iteration counts.  The lines also go to profiles/mg_refresh_probe.txt (`--out`), stamped with the build id.
 
   python tools/mg_probe.py --refresh
+
+`--cycle W`: every multigrid configuration is built with `cycle="W"`; a configuration name that ends in `w` (mg1w, gmg1c2048w) is the
+W-cycle whatever `--cycle` says, so V and W of one hierarchy are solved in the same alternation of the same process.  Every
+multigrid configuration records its cycle, `launches_per_apply` and `tail_from`.  profiles/mg_wcycle_probe.txt is the output of
+
+  python tools/mg_probe.py --graph --reps 2 --applies 0 --configs plain mg1 mg1w gmg1c2048 gmg1c2048w --out profiles/mg_wcycle_probe.txt
 """
 import argparse
 import json
@@ -140,7 +146,12 @@ def _timed(fn):
     return out, time.perf_counter() - t0
 
 
-def run_system(name, make, grid, reps, configs, applies, graph=False):
+def _cycle_of(cfg, default):
+    """(the configuration's name without a trailing `w`, its cycle)."""
+    return (cfg[:-1], "W") if cfg.endswith("w") else (cfg, default)
+
+
+def run_system(name, make, grid, reps, configs, applies, graph=False, cycle="V"):
     from pytorch_sparse_solver.module_a import AggregationMultigridPreconditioner, ChebyshevPreconditioner, cg, get_last_stats
     A = make()
     n = A.shape[0]
@@ -152,11 +163,13 @@ def run_system(name, make, grid, reps, configs, applies, graph=False):
         if cfg == "cheb3":
             Ms[cfg], setup[cfg] = _timed(lambda: ChebyshevPreconditioner(A, degree=3))
         elif cfg.startswith("mg"):
-            Ms[cfg], setup[cfg] = _timed(lambda: AggregationMultigridPreconditioner(A, grid, degree=int(cfg[2:])))
+            base, cyc = _cycle_of(cfg, cycle)
+            Ms[cfg], setup[cfg] = _timed(lambda: AggregationMultigridPreconditioner(A, grid, degree=int(base[2:]), cycle=cyc))
         elif cfg.startswith("gmg"):
-            degree, _, cut = cfg[3:].partition("c")
+            base, cyc = _cycle_of(cfg, cycle)
+            degree, _, cut = base[3:].partition("c")
             try:
-                Ms[cfg], setup[cfg] = _timed(lambda: AggregationMultigridPreconditioner.from_graph(A, degree=int(degree),
+                Ms[cfg], setup[cfg] = _timed(lambda: AggregationMultigridPreconditioner.from_graph(A, degree=int(degree), cycle=cyc,
                                                                                                      coarse_rows=int(cut) if cut else None))
             except ValueError as e:                       # the 48-level stall: recorded, the other configurations go on
                 row[cfg] = {"refused": str(e)}
@@ -177,8 +190,11 @@ def run_system(name, make, grid, reps, configs, applies, graph=False):
     row["hierarchy"] = {}
     for cfg in configs:
         M = Ms[cfg]
+        if cfg.startswith("mg"):
+            row["hierarchy"][cfg] = {"levels": len(M.levels), "cycle": M.cycle, "launches": M.launches_per_apply, "tail_from": M.tail_from}
         if cfg.startswith("gmg"):
-            row["hierarchy"][cfg] = {"levels": len(M.levels), "last": M.levels[-1].n, "launches": M.launches_per_apply, "tail_from": M.tail_from,
+            row["hierarchy"][cfg] = {"levels": len(M.levels), "last": M.levels[-1].n, "cycle": M.cycle, "launches": M.launches_per_apply,
+                                     "tail_from": M.tail_from,
                                      "longest_row_above_the_last": max([lev.max_row for lev in M.levels[:-1]] or [0])}
             if M.dense:
                 M(b)                                       # builds the device state
@@ -203,8 +219,8 @@ def run_system(name, make, grid, reps, configs, applies, graph=False):
         row["apply_us_by_tail_rows"] = {}
         ref = None
         for tail in TAILS:
-            M = AggregationMultigridPreconditioner.from_graph(A, degree=1, tail_rows=tail) if graph else \
-                AggregationMultigridPreconditioner(A, grid, degree=1, tail_rows=tail)
+            M = AggregationMultigridPreconditioner.from_graph(A, degree=1, tail_rows=tail, cycle=cycle) if graph else \
+                AggregationMultigridPreconditioner(A, grid, degree=1, tail_rows=tail, cycle=cycle)
             for _ in range(3):
                 z = M(v)
             ref = z if ref is None else ref
@@ -306,7 +322,7 @@ def run_refresh(name, make, grid, kind):
 
 def main_refresh(a):
     from pytorch_sparse_solver import _hipk
-    out = open(a.out, "w")
+    out = open(a.out or os.path.join(ROOT, "profiles", "mg_refresh_probe.txt"), "w")
 
     def emit(obj):
         line = json.dumps(obj)
@@ -329,9 +345,11 @@ def main_refresh(a):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--refresh", action="store_true", help="update() against a fresh construction: set-up times, their split, ten steps")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mg_refresh_probe.txt"), help="--refresh: the file the lines also go to")
+    ap.add_argument("--out", default=None, help="the file the lines also go to (--refresh: profiles/mg_refresh_probe.txt unless given)")
+    ap.add_argument("--cycle", choices=["V", "W"], default="V", help="the cycle of every multigrid configuration whose name does not end in w")
     ap.add_argument("--systems", nargs="*", default=None)
-    ap.add_argument("--configs", nargs="*", default=None, help="default: plain cheb3 mg1 mg2; with --graph: plain mg1 gmg1 gmg2 gmg1c256 gmg1c512 gmg1c1024 gmg1c2048")
+    ap.add_argument("--configs", nargs="*", default=None, help="default: plain cheb3 mg1 mg2; with --graph: plain mg1 gmg1 gmg2 gmg1c256 gmg1c512 gmg1c1024 gmg1c2048; "
+                    "a trailing w (mg1w, gmg1c2048w): the W-cycle of that configuration")
     ap.add_argument("--graph", action="store_true", help="from_graph beside the grid class; the tail_rows sweep on the graph hierarchy")
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--applies", type=int, default=20)
@@ -341,17 +359,26 @@ def main():
     a.configs = a.configs or (["plain", "mg1", "gmg1", "gmg2"] + [f"gmg1c{k}" for k in CUTS] if a.graph else ["plain", "cheb3", "mg1", "mg2"])
     from pytorch_sparse_solver import _hipk
     from pytorch_sparse_solver.module_a import multigrid
-    print(json.dumps({"hipk_build_id": _hipk.lib().hipk_build_id().decode(), "device": torch.cuda.get_device_name(0), "reps": a.reps,
-                      "applies": a.applies, "tol": 1e-6, "dtype": "float64", "MG_TAIL_MAX_ROWS": multigrid.MG_TAIL_MAX_ROWS,
-                      "mode": "graph" if a.graph else "grid", "configs": a.configs}), flush=True)
+    out = open(a.out, "w") if a.out else None
+
+    def emit(obj):
+        line = json.dumps(obj)
+        print(line, flush=True)
+        if out is not None:
+            out.write(line + "\n")
+            out.flush()
+
+    emit({"hipk_build_id": _hipk.lib().hipk_build_id().decode(), "device": torch.cuda.get_device_name(0), "reps": a.reps,
+          "applies": a.applies, "tol": 1e-6, "dtype": "float64", "MG_TAIL_MAX_ROWS": multigrid.MG_TAIL_MAX_ROWS,
+          "mode": "graph" if a.graph else "grid", "cycle": a.cycle, "configs": a.configs})
     table = graph_systems() if a.graph else systems()
     for name in a.systems or list(table):
         make, grid = table[name]
         try:
-            row = run_system(name, make, grid, a.reps, a.configs, a.applies, graph=a.graph)
+            row = run_system(name, make, grid, a.reps, a.configs, a.applies, graph=a.graph, cycle=a.cycle)
         except torch.cuda.OutOfMemoryError as e:
             row = {"system": name, "skipped": f"does not fit: {str(e).splitlines()[0]}"}
-        print(json.dumps(row), flush=True)
+        emit(row)
         _hipk.clear_cache()
         torch.cuda.empty_cache()
     if a.graph and a.systems is None:                     # the dense step alone on random matrices, both forms
@@ -359,7 +386,7 @@ def main():
         for n in CUTS:
             ld = (n + 3) & ~3
             steps.append(dense_step_us(torch.randn(n * ld, dtype=torch.float64, device=DEV), n, ld))
-        print(json.dumps({"dense_step_us_random_fp64": steps}), flush=True)
+        emit({"dense_step_us_random_fp64": steps})
 
 
 if __name__ == "__main__":
