@@ -1194,11 +1194,11 @@ struct hipk_cg_layout {
     bool fourth_vector;
     size_t p2;
     // The fused SpMV + update launch (hipk_cg_fuse.h) keeps Ap on chip, so the head of Ap is its own: the chunks' flagged <p,Ap>
-    // words, then the collector's replicas, then the same again for the <r,r> of the direction tail (the kernel finds the second
-    // pair behind the first) -- one region, cleared by one memset when the sequence begins.  (Not in the partial
+    // words, then the collectors' eight hand-out lines, then the same again for the <r,r> of the direction tail (the kernel finds
+    // the lines behind the words and the second pair behind the first) -- one region, cleared by one memset when the sequence begins.  (Not in the partial
     // slots: hipk_cg_direction_kernel folds the plain <p,Ap> partials from part_a, which the fused launch therefore still writes.)
     // A sequence of the separate kernels that takes over after a give-up writes Ap again; the fused form is not tried again then.
-    size_t fuse_words, fuse_ctl;
+    size_t fuse_words;
     size_t total;
 };
 static constexpr size_t kFuseBytes = 2 * (kFuseWordsBytes + kFuseCtlBytes);   // <p,Ap>'s words and replicas, then <r,r>'s (the direction tail)
@@ -1244,7 +1244,6 @@ static hipk_cg_layout hipk_cg_make_layout(int64_t n, int dtype, bool pre) {
     if (second_p) take(vec);
     L.fourth_vector = !pre && (L.mid || second_p);
     L.fuse_words = L.Ap;
-    L.fuse_ctl = L.Ap + kFuseWordsBytes;
     L.total = take.o;
     return L;
 }
@@ -2079,14 +2078,17 @@ struct hipk_cg_steps {
     }
 
     // ---- hipk_cg_fuse_update_kernel in place of the SpMV and the update launch (hipk_cg_path_fuse)
-    // the sequence begins: the flagged words and the collector's replicas (one region, the head of Ap) and the give-up word
+    // the sequence begins: the flagged words and the collectors' hand-out lines (one region, the head of Ap) and the give-up word
     int fuse_begin() {
         HIPK_CHECK_HIP(hipMemsetAsync(hipk_at<char>(work, lay.fuse_words), 0, kFuseBytes, stream));
         HIPK_CHECK_HIP(hipMemsetAsync(&scal->ctl, 0, sizeof(hipk_lds_ctl), stream));
-        // tests: HIPK_TEST_CG_FUSE_GIVE_UP=k makes the collector of iteration k behave as if its poll had run out
+        // tests: HIPK_TEST_CG_FUSE_GIVE_UP=k makes the collectors of iteration k behave as if their poll had run out
         fuse_give_up_at = hipk_sw_present("HIPK_TEST_CG_FUSE_GIVE_UP") ? hipk_sw_int("HIPK_TEST_CG_FUSE_GIVE_UP", -1) : -1;
-        // ... HIPK_TEST_CG_FUSE_DIR_GIVE_UP=k the collector of its second hand-off (the direction tail)
+        // ... HIPK_TEST_CG_FUSE_DIR_GIVE_UP=k those of its second hand-off (the direction tail)
         fuse_dir_give_up_at = hipk_sw_present("HIPK_TEST_CG_FUSE_DIR_GIVE_UP") ? hipk_sw_int("HIPK_TEST_CG_FUSE_DIR_GIVE_UP", -1) : -1;
+        // ... HIPK_TEST_CG_FUSE_GIVE_UP_WHO=s only collector s of the eight, at either
+        const int64_t who = hipk_sw_present("HIPK_TEST_CG_FUSE_GIVE_UP_WHO") ? hipk_sw_int("HIPK_TEST_CG_FUSE_GIVE_UP_WHO", -1) : -1;
+        fuse_give_up_who = who >= 0 && who < (int64_t)kFuseCollectors ? 1 << (int)who : (1 << kFuseCollectors) - 1;
         fuse_note();
         return HIPK_OK;
     }
@@ -2108,20 +2110,18 @@ struct hipk_cg_steps {
         ff.part_rr = part_b;
         ff.part_pap = part_a;
         ff.words = hipk_at<char>(work, lay.fuse_words);
-        ff.ctl = hipk_at<char>(work, lay.fuse_ctl);
         ff.seq = (unsigned)(it - it0) + 1u;
-        ff.give_up = it == fuse_give_up_at ? 1 : 0;
+        ff.give_up = (it == fuse_give_up_at ? fuse_give_up_who : 0) | (p_next != nullptr && it == fuse_dir_give_up_at ? fuse_give_up_who << 8 : 0);
         ff.p_next = (double *)p_next;
         ff.x = (double *)xq;
         ff.maxiter = maxiter;
         ff.keep_p = p_next != nullptr && path.fuse_keep_p ? 1 : 0;
-        ff.dir_give_up = p_next != nullptr && it == fuse_dir_give_up_at ? 1 : 0;
         path.fuse_kern<<<hipk_xcd_grid(gm.g), HIPK_THREADS, 0, stream>>>(fa, ff);
     }
-    // the sequence has ended: HIPK_OK, or HIPK_HANDED_BACK when the collector gave up at some iteration -- the state is that
+    // the sequence has ended: HIPK_OK, or HIPK_HANDED_BACK when a collector gave up at some iteration -- the state is that
     // iteration's, the latch is set on the handle, the stop word and the pacer are rearmed, and the caller goes on from `it` with
     // the separate kernels.  deferred: the flush has brought x up to date; p of that iteration is where its parity put it
-    // The collector of the direction tail gave up (ctl.redo = kFuseDirGaveUp) at iteration K = stop_it, j = K - it0 into the sequence:
+    // A collector of the direction tail gave up (ctl.redo = kFuseDirGaveUp) at iteration K = stop_it, j = K - it0 into the sequence:
     // r, part_rr and alpha_K are K's, p_{K+1} is not stored, the flush has done nothing.  hipk_cg_pdir_kernel finishes K from
     // pbuf[j & 1] into the other buffer (and does its bookkeeping), and the caller goes on at K + 1 with p_{K+1} there.  x: odd j,
     // the tail's x part has brought it up to date through K; even j, it lacks alpha_K p_K only, which the flush kernel adds as
@@ -2135,7 +2135,7 @@ struct hipk_cg_steps {
         if (path.fuse_dir) hipk_cg_fused_directions += ran > 0 ? ran : 0;
         if (path.fuse_keep_p) hipk_cg_fused_kept_p += ran > 0 ? ran : 0;
         if (hs.ctl.redo == -3) {
-            hipk_set_error("hipk_cg_solve: the collector of the fused SpMV + update launch stopped arriving");
+            hipk_set_error("hipk_cg_solve: a collector of the fused SpMV + update launch stopped arriving");
             return HIPK_ERR_HIP;
         }
         const bool dir_gave_up = path.fuse_dir && hs.ctl.redo == kFuseDirGaveUp;
@@ -2159,6 +2159,7 @@ struct hipk_cg_steps {
         return HIPK_HANDED_BACK;
     }
     int64_t fuse_give_up_at = -1, fuse_dir_give_up_at = -1;
+    int fuse_give_up_who = (1 << kFuseCollectors) - 1;   // bit s: collector s obeys them
 
     // the kernels of the plain three-launch sequence (hipk_cg_path: small / streams / flat_dir) and the form they make
     hipk_cg_kernels<T> pick() const {

@@ -55,8 +55,9 @@ static constexpr hipk_sw_row hipk_switches[] = {
     {"HIPK_CG_FUSE_UPDATE", HIPK_SW_FORCE01, "automatic", "each plain CG solve", "0 | 1: the SpMV and the update step as two launches | as hipk_cg_fuse_update_kernel where the form applies (unset: fused where it applies)", "test, tools A/B"},
     {"HIPK_CG_FUSE_DIRECTION", HIPK_SW_FORCE01, "automatic", "each plain CG solve", "0 | 1: the direction step of the fused deferred-x sequence as hipk_cg_pdir_kernel / hipk_cg_xdir_kernel launches | as the tail of hipk_cg_fuse_update_kernel where the form applies (unset: the tail where it applies)", "test, tools A/B"},
     {"HIPK_CG_FUSE_KEEP_P", HIPK_SW_OFF_IF_0, "on", "each plain CG solve", "0: the direction tail of hipk_cg_fuse_update_kernel loads all of p_k again instead of keeping the uniform tiles' rows in the walk's registers (same bits)", "test, tools A/B"},
-    {"HIPK_TEST_CG_FUSE_DIR_GIVE_UP", HIPK_SW_INT, "unset", "each fused CG sequence", "k: the collector of the direction tail's hand-off at iteration k behaves as if its poll had run out (the solve goes on with the separate kernels)", "test"},
-    {"HIPK_TEST_CG_FUSE_GIVE_UP", HIPK_SW_INT, "unset", "each fused CG sequence", "k: the collector of hipk_cg_fuse_update_kernel at iteration k behaves as if its poll had run out (the solve goes on with the separate kernels)", "test"},
+    {"HIPK_TEST_CG_FUSE_DIR_GIVE_UP", HIPK_SW_INT, "unset", "each fused CG sequence", "k: the collectors of the direction tail's hand-off at iteration k behave as if their poll had run out (the solve goes on with the separate kernels)", "test"},
+    {"HIPK_TEST_CG_FUSE_GIVE_UP", HIPK_SW_INT, "unset", "each fused CG sequence", "k: the collectors of hipk_cg_fuse_update_kernel at iteration k behave as if their poll had run out (the solve goes on with the separate kernels)", "test"},
+    {"HIPK_TEST_CG_FUSE_GIVE_UP_WHO", HIPK_SW_INT, "unset", "each fused CG sequence", "s: only collector s (0 .. 7) obeys HIPK_TEST_CG_FUSE_GIVE_UP / HIPK_TEST_CG_FUSE_DIR_GIVE_UP; outside 0 .. 7: ignored (all eight do)", "test"},
     {"HIPK_CG_STREAMS", HIPK_SW_FORCE01, "automatic", "each plain CG solve", "0 | 1: force the vector kernels' cache policy (unset: streams when x, r, p, Ap exceed 384 MiB)", "test"},
     {"HIPK_CG_FLAT_DIRECTION", HIPK_SW_FORCE01, "automatic", "each plain CG solve", "0 | 1: with the streaming policy, the direction step per chunk | as scalars launch + flat grid (unset: flat when a vector exceeds 256 MiB)", "test, tools A/B"},
     // ---- BiCGStab (hipk_bicgstab.hip)
