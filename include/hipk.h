@@ -183,6 +183,28 @@ size_t hipk_csr_transpose_work_bytes(hipk_csr_t h);
 int hipk_csr_transpose(hipk_csr_t h, int32_t *crow_t_dev, int32_t *col_t_dev, void *val_t_dev, void *work,
                        size_t work_bytes, hipk_stream_t stream);
 
+/* ---- matrix gradient of a solve (csrc/hipk_vgrad.hip) -----------------------------
+ * With x = A^-1 b, g = dL/dx and lam = A^-T g, the gradient of L with respect to the stored entry k of A, in row row(k) and
+ * column col(k), is  G[k] = -(lam[row(k)] * x[col(k)]):  one multiplication in T, then a negation.  A column stored twice in a
+ * row gives both entries the same value, a stored zero gets a gradient like any other entry, rows may have any length.
+ *   hipk_batch_grad_values : G[s ldg + k] = -(L[s ldl + row(k)] * X[s ldx + col(k)]),  k < nnz, s < batch, for `batch` systems
+ *                            of n rows with ONE pattern (int32 crow [n + 1] / col [nnz] on the device).  No n or row-length
+ *                            envelope.
+ *   hipk_csr_grad_values   : the same for one matrix through its handle (the handle's int32 index copies; rectangular handles:
+ *                            lam has n_rows, x n_cols elements, gvals nnz).
+ * One launch of hipk_csr_vgrad_kernel<T> either way; every element G[s ldg + k], k < nnz, is written exactly once and elements
+ * of a row at and beyond nnz are never written.  Neither entry synchronises or reads crow on the host.  nnz == 0 or batch == 0:
+ * HIPK_OK without a launch.  A null pointer, a negative size, n or nnz >= 2^31, an ld shorter than its row (ldl, ldx < n,
+ * ldg < nnz) or g equal to lam or x: HIPK_ERR_ARG; a dtype other than HIPK_F32 / HIPK_F64: HIPK_ERR_UNSUPPORTED; a pointer that
+ * is not 16-byte aligned or, with batch > 1, an ld * sizeof(T) that is no multiple of 16: HIPK_ERR_ALIGN.  A call that returns
+ * an error has launched nothing.  hipk_last_grad_values_launches(): the launches the calling thread's last call of either
+ * entry took (0 or 1). */
+int hipk_batch_grad_values(int64_t n, int64_t nnz, const int32_t *crow_dev, const int32_t *col_dev, int batch,
+                           const void *lam, int64_t ldl, const void *x, int64_t ldx, void *g, int64_t ldg,
+                           int dtype, hipk_stream_t stream);
+int hipk_csr_grad_values(hipk_csr_t h, const void *lam, const void *x, void *gvals, hipk_stream_t stream);
+int hipk_last_grad_values_launches(void);
+
 /* ---- reduction geometry ------------------------------------------------------
  * Every dot/norm is a two-level fixed tree: the vector is cut in `count` chunks
  * of `chunk` elements (chunk = 2048 * 2^k, count <= 2048); see DESIGN.md. */

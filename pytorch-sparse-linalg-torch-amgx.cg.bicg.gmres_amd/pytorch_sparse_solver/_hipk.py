@@ -30,6 +30,8 @@ SYMBOLS = [
     "hipk_csr_create", "hipk_csr_destroy", "hipk_csr_rows", "hipk_csr_nnz", "hipk_csr_spmv_bytes",
     "hipk_csr_spmv_path", "hipk_last_spmv_kernel", "hipk_last_solve_path", "hipk_last_solve_form", "hipk_last_cg_fused_directions", "hipk_last_cg_fused_kept_p", "hipk_solve_form_count", "hipk_solve_form_name", "hipk_csr_set_path", "hipk_csr_format_bytes",
     "hipk_csr_transpose_work_bytes", "hipk_csr_transpose",
+    # the matrix gradient of a solve: G[k] = -(lam[row(k)] * x[col(k)]) for one matrix and for a batch on one pattern
+    "hipk_batch_grad_values", "hipk_csr_grad_values", "hipk_last_grad_values_launches",
     "hipk_chunk_size", "hipk_chunk_count", "hipk_scratch_bytes",
     "hipk_spmv", "hipk_spmv_dot", "hipk_dot", "hipk_axpy", "hipk_xpby", "hipk_block_jacobi_apply",
     "hipk_cheb_apply",
@@ -228,6 +230,9 @@ def lib():
     L.hipk_csr_transpose_work_bytes.argtypes = [vp]
     L.hipk_csr_transpose_work_bytes.restype = ctypes.c_size_t
     L.hipk_csr_transpose.argtypes = [vp, vp, vp, vp, vp, ctypes.c_size_t, vp]
+    L.hipk_batch_grad_values.argtypes = [i64, i64, vp, vp, i32, vp, i64, vp, i64, vp, i64, i32, vp]
+    L.hipk_csr_grad_values.argtypes = [vp, vp, vp, vp, vp]
+    L.hipk_last_grad_values_launches.restype = i32
     L.hipk_csr_spmv_path.argtypes = [vp]
     L.hipk_csr_set_path.argtypes = [vp, i32]
     L.hipk_chunk_size.argtypes = [i64]
@@ -719,6 +724,88 @@ def cheb_apply(h: CsrHandle, degree: int, dinv: torch.Tensor, coef, v: torch.Ten
         _check(lib().hipk_cheb_apply(h.ptr, int(degree), dinv.data_ptr(), coef, v.data_ptr(), out.data_ptr(), work.data_ptr(),
                                      _stream(v.device)), "hipk_cheb_apply")
     return out
+
+
+@dataclass
+class GradStats:
+    """Side channel of the matrix-gradient step of a backward pass (`get_last_grad_stats()`): the route that formed the gradient
+    ("kernel": hipk_csr_vgrad_kernel, or "torch": the torch expression of the same formula), the kernel launches it took (0 on the
+    torch route), the stored entries per matrix and the number of systems.  One per process, NOT per thread: autograd runs backward
+    on a thread of its own, where a thread-local record would be invisible to the caller."""
+    route: str
+    launches: int
+    nnz: int
+    batch: int
+
+
+_last_grad_stats: Optional[GradStats] = None
+
+
+def last_grad_stats() -> Optional[GradStats]:
+    return _last_grad_stats
+
+
+def set_grad_stats(route: str, launches: int, nnz: int, batch: int) -> None:
+    global _last_grad_stats
+    _last_grad_stats = GradStats(route=route, launches=int(launches), nnz=int(nnz), batch=int(batch))
+
+
+def csr_grad_values(h: CsrHandle, lam: torch.Tensor, x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """hipk_csr_grad_values: out[k] = -(lam[row(k)] * x[col(k)]) for the nnz stored entries of the handle's matrix, in the handle's
+    dtype (lam of n_rows, x of n_cols elements are cast to it).  `out`, if given, receives the values (through an aligned
+    temporary when it is a misaligned or strided view)."""
+    lam = aligned(lam.detach().to(device=h.device, dtype=h.dtype))
+    x = aligned(x.detach().to(device=h.device, dtype=h.dtype))
+    if lam.dim() != 1 or x.dim() != 1 or lam.numel() != h.shape[0] or x.numel() != h.shape[1]:
+        raise HipkError(f"csr_grad_values: lam must have {h.shape[0]} and x {h.shape[1]} elements, got {tuple(lam.shape)} and {tuple(x.shape)}")
+    if out is not None and (out.dim() != 1 or out.numel() != h.nnz or out.dtype != h.dtype or out.device != h.device):
+        raise HipkError(f"csr_grad_values: out must be a {h.dtype} vector of {h.nnz} elements on {h.device}")
+    direct = out is not None and out.is_contiguous() and out.data_ptr() % 16 == 0
+    g = out if direct else torch.empty(h.nnz, dtype=h.dtype, device=h.device)
+    L = lib()
+    with torch.cuda.device(h.device):
+        rc = L.hipk_csr_grad_values(h.ptr, lam.data_ptr(), x.data_ptr(), g.data_ptr(), _stream(h.device))
+    _check(rc, "hipk_csr_grad_values")
+    set_grad_stats("kernel", L.hipk_last_grad_values_launches(), h.nnz, 1)
+    if out is not None and not direct:
+        out.copy_(g)
+        return out
+    return g
+
+
+def batch_grad_values(n: int, nnz: int, crow32: torch.Tensor, col32: torch.Tensor, lam: torch.Tensor, x: torch.Tensor,
+                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """hipk_batch_grad_values: out[s, k] = -(lam[s, row(k)] * x[s, col(k)]) for S systems of n rows on one pattern (int32 crow (n + 1,),
+    col (nnz,)); lam, x (S, n) of one dtype (fp64 or fp32) on one device, out (S, nnz).  Rows that do not start 16-byte aligned go
+    through padded copies, as in the batch solves."""
+    from .module_a.batch import _aligned_rows, _pad_rows
+    dev, dt = lam.device, lam.dtype
+    if lam.dim() != 2 or x.dim() != 2 or lam.shape != x.shape or lam.shape[1] != n or x.dtype != dt or x.device != dev:
+        raise HipkError(f"batch_grad_values: lam and x must both be (S, {n}) tensors of one dtype on one device")
+    S = int(lam.shape[0])
+    assert crow32.dtype == torch.int32 and col32.dtype == torch.int32 and crow32.numel() == n + 1 and col32.numel() == nnz
+    assert crow32.device == dev and col32.device == dev
+    if out is not None and (tuple(out.shape) != (S, nnz) or out.dtype != dt or out.device != dev):
+        raise HipkError(f"batch_grad_values: out must be a ({S}, {nnz}) {dt} tensor on {dev}")
+    crow32, col32 = aligned(crow32), aligned(col32)
+    lam, x = _pad_rows(lam.detach()), _pad_rows(x.detach())
+    direct = out is not None and _aligned_rows(out)
+    if direct:
+        g = out
+    else:       # a fresh buffer whose rows start 16-byte aligned: allocated padded, never initialised (the kernel writes every [s, k < nnz])
+        per = 16 // lam.element_size()
+        g = torch.empty((S, (nnz + per - 1) // per * per), dtype=dt, device=dev)[:, :nnz]
+    ld = lambda t: int(t.stride(0)) if t.shape[0] > 1 else max(int(t.stride(0)), int(t.shape[1]))
+    L = lib()
+    with torch.cuda.device(dev):
+        rc = L.hipk_batch_grad_values(int(n), int(nnz), crow32.data_ptr(), col32.data_ptr(), S, lam.data_ptr(), ld(lam), x.data_ptr(), ld(x),
+                                      g.data_ptr(), ld(g), _dtype_code(dt), _stream(dev))
+    _check(rc, "hipk_batch_grad_values")
+    set_grad_stats("kernel", L.hipk_last_grad_values_launches(), nnz, S)
+    if out is not None and not direct:
+        out.copy_(g)
+        return out
+    return g
 
 
 def spmv_residual(h: CsrHandle, x: torch.Tensor, b: torch.Tensor, out: torch.Tensor) -> torch.Tensor:

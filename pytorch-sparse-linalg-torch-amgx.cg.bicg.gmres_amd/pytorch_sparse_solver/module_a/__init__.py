@@ -7,7 +7,9 @@ reference's `M` hook that the fast path runs device-resident), `ChebyshevPrecond
 run in the SpMV kernels' epilogue), `AggregationMultigridPreconditioner` (a V-cycle of aggregation multigrid for a matrix on a
 structured grid or, `from_graph`, for any matrix, with `pairwise_aggregates` from the matrix graph), `cg_multi` / `bicgstab_multi` (k right-hand sides per matrix read) and `cg_batch` /
 `bicgstab_batch` / `gmres_batch` (many small systems with one sparsity pattern, one workgroup per system; point- or block-Jacobi
-preconditioned) are the additions.
+preconditioned) are the additions, and so are matrix gradients: a solve through a real CSR, COO or dense `A` that requires grad
+returns dL/dA on A's pattern (module_a/matrix_grad.py, `get_last_grad_stats()`), and `cg_batch_differentiable` /
+`bicgstab_batch_differentiable` / `gmres_batch_differentiable` differentiate the batch solves with respect to per-system values.
 """
 from .torch_sparse_linalg import (
     cg, bicgstab, gmres,
@@ -16,6 +18,8 @@ from .torch_sparse_linalg import (
 )
 from .multi_rhs import cg_multi, bicgstab_multi
 from .batch import BatchedCSR, BatchedJacobiPreconditioner, BatchedBlockJacobiPreconditioner, cg_batch, bicgstab_batch, gmres_batch
+from .batch import cg_batch_differentiable, bicgstab_batch_differentiable, gmres_batch_differentiable
+from .matrix_grad import get_last_grad_stats
 from .torch_tree_util import tree_leaves, tree_map, tree_flatten, tree_unflatten, Partial
 from .preconditioners import BlockJacobiPreconditioner, ChebyshevPreconditioner, JacobiPreconditioner
 from .multigrid import AggregationMultigridPreconditioner, pairwise_aggregates
@@ -24,6 +28,7 @@ __all__ = [
     'cg', 'bicgstab', 'gmres', 'cg_multi', 'bicgstab_multi',
     'BatchedCSR', 'BatchedJacobiPreconditioner', 'BatchedBlockJacobiPreconditioner', 'cg_batch', 'bicgstab_batch', 'gmres_batch',
     'cg_differentiable', 'bicgstab_differentiable', 'gmres_differentiable',
+    'cg_batch_differentiable', 'bicgstab_batch_differentiable', 'gmres_batch_differentiable', 'get_last_grad_stats',
     'LinearSolveFunction',
     'tree_leaves', 'tree_map', 'tree_flatten', 'tree_unflatten', 'Partial',
     'get_last_stats', 'JacobiPreconditioner', 'BlockJacobiPreconditioner', 'ChebyshevPreconditioner',

@@ -12,6 +12,11 @@ tensor A_s of system s, bit for bit.  Two routes compute them:
 
 `M` is None, a `BatchedJacobiPreconditioner` or a `BatchedBlockJacobiPreconditioner` (csrc/hipk_batch_bj.hip; gmres_batch runs the
 latter on the loop only).
+
+The three solves refuse operands that require grad.  `cg_batch_differentiable` / `bicgstab_batch_differentiable` /
+`gmres_batch_differentiable` (at the end of this file) return X only and differentiate it with respect to B and to per-system values on
+A's pattern: the same batch solve of the transposed systems gives Lam = A^-T dL/dX, then grad_B = Lam and
+grad_values[s, k] = -(Lam[s, row(k)] * X[s, col(k)]) (csrc/hipk_vgrad.hip).
 """
 from __future__ import annotations
 
@@ -89,6 +94,63 @@ class BatchedCSR:
         self.crow32 = _hipk.aligned(crow.to(torch.int32))
         self.col32 = _hipk.aligned(col.to(torch.int32))
         self._kernel_values = None
+        self._pattern_cache = {}      # what depends on crow / col alone (the transposed pattern); shared by `with_values` objects
+
+    @classmethod
+    def _on_pattern(cls, src: "BatchedCSR", values: torch.Tensor) -> "BatchedCSR":
+        new = cls.__new__(cls)
+        new.crow, new.col, new.values = src.crow, src.col, values
+        new.n, new.nnz, new.batch = src.n, src.nnz, int(values.shape[0])
+        new.shape = (new.batch, src.n, src.n)
+        new.max_row_len = src.max_row_len
+        new.crow32, new.col32 = src.crow32, src.col32
+        new._kernel_values = None
+        new._pattern_cache = src._pattern_cache
+        return new
+
+    def with_values(self, values: torch.Tensor) -> "BatchedCSR":
+        """A BatchedCSR of `values` (S', nnz) on THIS object's pattern: the pattern is not validated again and nothing is read back
+        from the device; crow / col, their int32 copies and the cached transposed pattern are shared, not copied."""
+        if not isinstance(values, torch.Tensor) or values.dim() != 2 or values.shape[0] < 1 or values.shape[1] != self.nnz:
+            raise ValueError(f"BatchedCSR.with_values: values must have shape (S, nnz) with S >= 1 and nnz = {self.nnz}, got "
+                             f"{tuple(getattr(values, 'shape', ()))}")
+        if values.dtype not in (torch.float64, torch.float32):
+            raise ValueError(f"BatchedCSR.with_values: values must be float64 or float32, got {values.dtype}")
+        if values.device != self.crow.device:
+            raise ValueError(f"BatchedCSR.with_values: values are on {values.device}, the pattern on {self.crow.device}")
+        if values.requires_grad:
+            raise ValueError("BatchedCSR: the batch solves are not differentiable (see cg_batch_differentiable(..., values=...))")
+        return BatchedCSR._on_pattern(self, values)
+
+    def transpose_pattern(self) -> Tuple["BatchedCSR", torch.Tensor]:
+        """(P, perm): the pattern of A_s^T as a value-less BatchedCSR and the entry permutation with values(A_s^T) = values[s, perm].
+        A stable sort of the entries by column, so every row of A^T lists its entries by source row, in stored order for a column
+        stored twice; computed once per pattern and cached."""
+        hit = self._pattern_cache.get("transpose")
+        if hit is None:
+            from .. import _hipk
+            n = self.n
+            rows = torch.repeat_interleave(torch.arange(n, device=self.crow.device), (self.crow[1:] - self.crow[:-1]).to(torch.int64))
+            col = self.col.to(torch.int64)
+            perm = torch.argsort(col, stable=True)
+            crow_t = torch.zeros(n + 1, dtype=self.crow.dtype, device=self.crow.device)
+            crow_t[1:] = torch.cumsum(torch.bincount(col, minlength=n), 0)
+            P = BatchedCSR.__new__(BatchedCSR)
+            P.crow, P.col, P.values = crow_t, rows[perm].to(self.col.dtype), None
+            P.n, P.nnz, P.batch = n, self.nnz, 0
+            P.shape = (0, n, n)
+            P.max_row_len = int((crow_t[1:] - crow_t[:-1]).max()) if n else 0
+            P.crow32 = _hipk.aligned(P.crow.to(torch.int32))
+            P.col32 = _hipk.aligned(P.col.to(torch.int32))
+            P._kernel_values = None
+            P._pattern_cache = {}
+            hit = self._pattern_cache["transpose"] = (P, perm)
+        return hit
+
+    def transposed(self) -> "BatchedCSR":
+        """The BatchedCSR of the S matrices A_s^T: the cached transposed pattern with the values gathered as `values[:, perm]`."""
+        P, perm = self.transpose_pattern()
+        return BatchedCSR._on_pattern(P, self.values[:, perm])
 
     @property
     def device(self):
@@ -207,6 +269,13 @@ class BatchedBlockJacobiPreconditioner:
         P.shape = (self.shape[1], self.shape[2])
         P.binv = self.binv[s]
         return P
+
+    def transposed(self) -> "BatchedBlockJacobiPreconditioner":
+        """The preconditioner of the transposed systems: blockdiag(A_s^T)^-1 = (blockdiag(A_s)^-1)^T, the blocks transposed."""
+        T = BatchedBlockJacobiPreconditioner.__new__(BatchedBlockJacobiPreconditioner)
+        T.block_size, T.shape = self.block_size, self.shape
+        T.binv = self.binv.transpose(-1, -2).contiguous()
+        return T
 
 
 BatchedPreconditioner = Union[BatchedJacobiPreconditioner, BatchedBlockJacobiPreconditioner]
@@ -354,3 +423,100 @@ def gmres_batch(A: BatchedCSR, B: torch.Tensor, X0: Optional[torch.Tensor] = Non
                                                            solve_method=solve_method)
     _set_stats(st)
     return X, torch.tensor([int(i) for i in st.info], dtype=torch.int64)
+
+
+# ------------------------------------------------------------------------- differentiable batch solves
+def _batch_grad_values(A: BatchedCSR, Lam: torch.Tensor, X: torch.Tensor) -> torch.Tensor:
+    """(S, nnz): G[s, k] = -(Lam[s, row(k)] * X[s, col(k)]) in the dtype of the matrices (module_a/matrix_grad.py): hipk_batch_grad_values
+    on the device, for any n and row length, the torch expression of the same formula on CPU."""
+    from .. import _hipk
+    from . import matrix_grad
+    Lam, X = Lam.to(A.dtype), X.to(A.dtype)
+    if A.values.is_cuda:
+        return _hipk.batch_grad_values(A.n, A.nnz, A.crow32, A.col32, Lam, X)   # (S, nnz), rows 16-byte aligned: a view when padded
+    G = matrix_grad.grad_values_torch(matrix_grad.csr_rows(A.crow), A.col, Lam, X, A.dtype)
+    _hipk.set_grad_stats("torch", 0, A.nnz, A.batch)
+    return G
+
+
+class BatchSolveFunction(torch.autograd.Function):
+    """X = solve(A(values), B) for the S systems of a BatchedCSR pattern, with the implicit-function backward: ONE batch solve of the
+    transposed systems, Lam = A^-T dL/dX, gives grad_B = Lam and grad_values[s, k] = -(Lam[s, row(k)] * X[s, col(k)])."""
+
+    @staticmethod
+    def forward(ctx, values, B, A, X0, M, solve, opts):
+        X, _ = solve(A.with_values(values.detach()), B.detach(), None if X0 is None else X0.detach(), M=M, **opts)
+        # the values go through save_for_backward: an in-place update between forward and backward (an optimiser step) is then an
+        # error, not an adjoint solve on the new coefficients
+        ctx.save_for_backward(values, X)
+        ctx.A, ctx.M, ctx.solve, ctx.opts = A, M, solve, opts
+        return X
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        if not (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]):
+            return (None,) * 7
+        values, X = ctx.saved_tensors
+        M = ctx.M
+        Aw = ctx.A.with_values(values.detach())          # on the cached pattern: no validation, no host sync
+        At = Aw.transposed()
+        opts = ctx.opts
+        if opts["route"] == "kernel" and not At.in_envelope():
+            # A's longest COLUMN is the transposed pattern's longest row: it may exceed the batch kernels' 32 entries although no
+            # row of A does.  The forward ran, so backward must: the adjoint solve then picks its route itself
+            opts = dict(opts, route="auto")
+        Mt = M.transposed() if isinstance(M, BatchedBlockJacobiPreconditioner) else M     # the point Jacobi M serves A^T unchanged
+        Lam, _ = ctx.solve(At, grad_output.detach().to(Aw.dtype).contiguous(), None, M=Mt, **opts)
+        grad_values = _batch_grad_values(Aw, Lam, X) if ctx.needs_input_grad[0] else None
+        return (grad_values, Lam if ctx.needs_input_grad[1] else None) + (None,) * 5
+
+
+def _batch_differentiable(name, solve, A, B, X0, values, M, opts):
+    if not isinstance(A, BatchedCSR):
+        raise ValueError(f"{name}: A must be a BatchedCSR")
+    if values is None:
+        values = A.values
+    elif (not isinstance(values, torch.Tensor) or tuple(values.shape) != (A.batch, A.nnz) or values.dtype != A.dtype
+          or values.device != A.device):
+        raise ValueError(f"{name}: values must be a {A.dtype} tensor of shape (S, nnz) = ({A.batch}, {A.nnz}) on {A.device}, got "
+                         f"{getattr(values, 'dtype', None)} {tuple(getattr(values, 'shape', ()))}")
+    if not isinstance(B, torch.Tensor):
+        raise ValueError(f"{name}: B must be a tensor")
+    if X0 is not None and isinstance(X0, torch.Tensor) and X0.requires_grad:
+        raise ValueError(f"{name}: X0 is not differentiated; pass X0.detach()")
+    return BatchSolveFunction.apply(values, B, A, X0, M, solve, opts)
+
+
+def cg_batch_differentiable(A: BatchedCSR, B: torch.Tensor, X0: Optional[torch.Tensor] = None, *, values: Optional[torch.Tensor] = None,
+                            tol: float = 1e-5, atol: float = 0.0, maxiter: Optional[int] = None,
+                            M: Optional[BatchedPreconditioner] = None, route: str = "auto") -> torch.Tensor:
+    """`cg_batch` returning only X, differentiable with respect to `B` and to `values`, an (S, nnz) tensor that stands in for
+    `A.values` on A's validated pattern (None: A.values, which carries no gradient).  The forward is `cg_batch` on the detached
+    operands: the same routes and bits, `get_last_stats()` as there.  Backward: one `cg_batch` of the transposed systems (same tol,
+    atol, maxiter, M and route; its start vector is X0 = None, whatever the forward's X0 was) gives Lam = A^-T dL/dX; grad_B = Lam
+    and grad_values[s, k] = -(Lam[s, row(k)] * X[s, col(k)]) (hipk_batch_grad_values on the device, for any n; `get_last_grad_stats()`).
+    With route='kernel' the adjoint solve takes the kernel too, unless a COLUMN of the pattern holds more than 32 entries (a row of
+    the transposed pattern outside the kernels' envelope): it then runs with route='auto' instead of failing in backward.  `values`
+    must not be modified in place between forward and backward (autograd raises if it was)."""
+    return _batch_differentiable("cg_batch_differentiable", cg_batch, A, B, X0, values, M,
+                                 dict(tol=tol, atol=atol, maxiter=maxiter, route=route))
+
+
+def bicgstab_batch_differentiable(A: BatchedCSR, B: torch.Tensor, X0: Optional[torch.Tensor] = None, *,
+                                  values: Optional[torch.Tensor] = None, tol: float = 1e-5, atol: float = 0.0,
+                                  maxiter: Optional[int] = None, M: Optional[BatchedPreconditioner] = None,
+                                  route: str = "auto") -> torch.Tensor:
+    """`bicgstab_batch` returning only X, differentiable with respect to `B` and `values` (see `cg_batch_differentiable`; the adjoint
+    solve starts from X0 = None)."""
+    return _batch_differentiable("bicgstab_batch_differentiable", bicgstab_batch, A, B, X0, values, M,
+                                 dict(tol=tol, atol=atol, maxiter=maxiter, route=route))
+
+
+def gmres_batch_differentiable(A: BatchedCSR, B: torch.Tensor, X0: Optional[torch.Tensor] = None, *, values: Optional[torch.Tensor] = None,
+                               tol: float = 1e-5, atol: float = 0.0, restart: int = 20, maxiter: Optional[int] = None,
+                               M: Optional[BatchedPreconditioner] = None, solve_method: str = "batched",
+                               route: str = "auto") -> torch.Tensor:
+    """`gmres_batch` returning only X, differentiable with respect to `B` and `values` (see `cg_batch_differentiable`; the adjoint
+    solve uses the same restart and solve_method and starts from X0 = None)."""
+    return _batch_differentiable("gmres_batch_differentiable", gmres_batch, A, B, X0, values, M,
+                                 dict(tol=tol, atol=atol, restart=restart, maxiter=maxiter, solve_method=solve_method, route=route))

@@ -533,45 +533,53 @@ def _transpose_of(A: torch.Tensor) -> torch.Tensor:
     return At.conj() if torch.is_complex(A) else At
 
 
+def _adjoint_backward(ctx, grad_output):
+    """(grad_A, grad_b) of a solve: ONE adjoint solve lam = A^-T grad_x -- the call the reference makes (TSL:1237-1248), with the
+    forward's arguments, its x0 included -- serves both: grad_b = lam, and grad_A[k] = -(lam[row(k)] * x[col(k)]) on A's pattern
+    (module_a/matrix_grad.py) when A requires grad and is a real CSR, COO or strided matrix."""
+    from . import matrix_grad
+    A_matrix, x = ctx.saved_tensors
+    want_A = ctx.needs_input_grad[0] and matrix_grad.supported(A_matrix)
+    if not (want_A or ctx.needs_input_grad[1]):
+        return None, None
+    lam, _ = ctx.transpose_solve_fn(_transpose_of(A_matrix.detach()), grad_output.detach(), *ctx.solve_args)
+    grad_A = matrix_grad.matrix_grad(A_matrix, lam, x) if want_A else None
+    return grad_A, (lam if ctx.needs_input_grad[1] else None)
+
+
 class ImplicitAdjointFunction(torch.autograd.Function):
     """Gives an already computed solution x = A^-1 b its implicit-function backward:
-    grad_b = A^-T grad_x, obtained with one more solve (TSL:1227-1248)."""
+    grad_b = A^-T grad_x, obtained with one more solve (TSL:1227-1248), and the gradient of A from the same solve."""
 
     @staticmethod
     def forward(ctx, A_matrix, b, x, transpose_solve_fn, *solve_args):
-        ctx.save_for_backward(A_matrix)
+        ctx.save_for_backward(A_matrix, x)
         ctx.transpose_solve_fn = transpose_solve_fn
         ctx.solve_args = solve_args
         return x
 
     @staticmethod
     def backward(ctx, grad_output):
-        (A_matrix,) = ctx.saved_tensors
-        grad_b = None
-        if ctx.needs_input_grad[1]:
-            grad_b, _ = ctx.transpose_solve_fn(_transpose_of(A_matrix.detach()), grad_output.detach(), *ctx.solve_args)
-        return (None, grad_b, None, None) + (None,) * len(ctx.solve_args)
+        grad_A, grad_b = _adjoint_backward(ctx, grad_output)
+        return (grad_A, grad_b, None, None) + (None,) * len(ctx.solve_args)
 
 
 class LinearSolveFunction(torch.autograd.Function):
     """x = solve_fn(A, b, *args) with backward grad_b = transpose_solve_fn(A^T, grad_x, *args)
-    (TSL:1161-1224). Gradient w.r.t. A is not produced, as in the reference."""
+    (TSL:1161-1224).  The reference produces no gradient w.r.t. A here; this one does, from the same adjoint solve."""
 
     @staticmethod
     def forward(ctx, A_matrix, b, solve_fn, transpose_solve_fn, *solve_args):
         x, _ = solve_fn(A_matrix.detach(), b.detach(), *solve_args)
-        ctx.save_for_backward(A_matrix)
+        ctx.save_for_backward(A_matrix, x)
         ctx.transpose_solve_fn = transpose_solve_fn
         ctx.solve_args = solve_args
         return x
 
     @staticmethod
     def backward(ctx, grad_output):
-        (A_matrix,) = ctx.saved_tensors
-        grad_b = None
-        if ctx.needs_input_grad[1]:
-            grad_b, _ = ctx.transpose_solve_fn(_transpose_of(A_matrix.detach()), grad_output.detach(), *ctx.solve_args)
-        return (None, grad_b, None, None) + (None,) * len(ctx.solve_args)
+        grad_A, grad_b = _adjoint_backward(ctx, grad_output)
+        return (grad_A, grad_b, None, None) + (None,) * len(ctx.solve_args)
 
 
 def cg(A: Union[torch.Tensor, Callable[[Any], Any]], b: Any, x0: Optional[Any] = None,
