@@ -104,7 +104,8 @@ int hipk_device_count(void);
  * Replaces the tensor `A` captured by `_normalize_matvec` (TSL:176-208).
  * crow/col are device arrays of idx_bytes (4 or 8) wide integers as torch stores
  * them (int64); they are narrowed once to int32 (SURVEY 7.2 "index width").
- * `val` is BORROWED: it must stay alive and unchanged until hipk_csr_destroy.
+ * `val` is BORROWED: it must stay alive until hipk_csr_destroy, and unchanged unless
+ * hipk_csr_update_values is called afterwards -- the one lawful way to change values.
  * A row is summed in STORED order: its products are rounded and added in the order
  * of its entries in col/val (rows of more than 32 entries: 64 lane-strided partial
  * sums of the stored sequence).  Column indices need not be sorted within a row, and
@@ -130,7 +131,7 @@ int64_t hipk_csr_spmv_bytes(hipk_csr_t h);
  *   CODED     : the matrix has at most 256 distinct (col - row, value) pairs and short rows (finite-difference /
  *               finite-volume stencils, e.g. matrix_utils.py:193-257 and ldc_solver_common.py:90-135): the handle
  *               keeps one byte per entry + one byte per row + the dictionary and streams those instead of
- *               col/val/crow.  The values are SNAPSHOTTED at creation (`val` must not change anyway, see above).
+ *               col/val/crow.  The values are SNAPSHOTTED at creation and by hipk_csr_update_values.
  *   OFFSET_CODED : too many distinct values, but at most 255 distinct column OFFSETS and short rows (variable-coefficient
  *               stencils): one offset-code byte + the value per entry in coalesced planes, 9 instead of 12 bytes
  *               per entry and no row pointers.  Values snapshotted as for CODED. */
@@ -172,6 +173,33 @@ const char *hipk_solve_form_name(int i);
 int hipk_csr_set_path(hipk_csr_t h, int mode);
 /* Bytes one SpMV has to move in the format the selected path streams (= hipk_csr_spmv_bytes unless CODED). */
 int64_t hipk_csr_format_bytes(hipk_csr_t h);
+/* New values on the same pattern.  After HIPK_OK the handle is the one hipk_csr_create_ex would have built from the same crow,
+ * col, chunk_rows and `val_dev` under the same HIPK_* switches: the same hipk_csr_spmv_path, hipk_csr_format_bytes, coded layout
+ * and uniform-tile decision, so every hipk_spmv_ex mode and every solve selects the same kernel and solve form and produces the
+ * same bits as on a fresh handle (dictionary numbering may differ; no result depends on it).  Creation and update run ONE
+ * decision function (hipk_decide_coded, csrc/hipk_api.hip).  `val_dev` (nnz values of the handle's dtype, 16-byte aligned) is
+ * BORROWED from then on; it may be the pointer the handle already holds, after an in-place change.  Everything that follows from
+ * crow / col alone is kept -- the int32 copies, the row / tile maxima, the huge-row list, the scratch, the tile widths and plane
+ * offsets, the offset dictionary and code planes of the OFFSET_CODED form, the window plan of the one-launch loops,
+ * hipk_csr_set_path's mode -- and what follows from the numbers is recomputed into the buffers the handle owns: the pair dictionary
+ * attempt, the code bytes and uniform-tile words of the CODED form, the value planes of the OFFSET_CODED form (hipk_csr_revalue_*
+ * kernels).  While the form stays the same nothing is allocated or freed; a form the handle leaves has its buffers freed.  The host
+ * waits only for the dictionary verdicts: 0 for a matrix with a row of more than 32 entries, else 1 - 3.
+ * Every transition between CODED, OFFSET_CODED and the plain kernels is allowed.
+ * hipk_last_csr_update_kind(): of the calling thread's last successful update -- 1 values only (plain stayed plain, or OFFSET_CODED
+ * stayed and its value planes were rewritten), 2 re-encoded in place (CODED stayed in its layout), 3 the form changed; 0 before
+ * the first update.
+ * A null val_dev: HIPK_ERR_ARG; a misaligned one: HIPK_ERR_ALIGN; a matrix-free handle (hipk_op_create): HIPK_ERR_UNSUPPORTED; each
+ * leaves the handle exactly as it was.  A HIP error part-way leaves a valid handle on the plain kernels with the new values.
+ * NOT safe against a solve or product running on the same handle: the caller serialises. */
+int hipk_csr_update_values(hipk_csr_t h, const void *val_dev, hipk_stream_t stream);
+int hipk_last_csr_update_kind(void);
+/* Host synchronisations the calling thread's last successful update took (measurement: tools/handle_update_probe.py). */
+int hipk_last_csr_update_syncs(void);
+/* Measurement hook: one launch of the value-plane rewrite of an OFFSET_CODED handle from the values it holds, in the given
+ * form -- 1: one row per lane from global memory, 2: the tile's CSR value range staged through LDS with 16-byte loads (the
+ * library's choice where the range fits 64 KB).  Both write the same elements.  Another handle: HIPK_ERR_UNSUPPORTED. */
+int hipk_csr_revalue_probe(hipk_csr_t h, int form, hipk_stream_t stream);
 
 /* ---- transpose (adjoint solves) ------------------------------------------------
  * The implicit-diff backward of the reference solves with A^T (`ImplicitAdjointFunction.backward`, TSL:1237-1248; `A.T`,

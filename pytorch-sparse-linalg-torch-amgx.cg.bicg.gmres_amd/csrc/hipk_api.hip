@@ -124,17 +124,87 @@ __global__ void hipk_huge_rows_kernel(const int *__restrict__ crow, int64_t n_ro
 }
 
 
-// Try to build the coded form (hipk_coded.h).  Failure of any kind just leaves the handle on the plain kernels.
+// ------------------------------------------------------------------ the coded forms: creation and hipk_csr_update_values
+// hipk_decide_coded is the ONE decision path of both: which form (pair-coded, then offset-coded, then plain), which layout,
+// uniform tiles or not.  Creation runs it on an empty handle; an update runs it on a handle that already owns the buffers of a
+// form, and the same code then writes into them: a buffer is allocated (and its padding set) only where the handle has none,
+// and a form the handle leaves is freed first (hipk_drop_coded), so a buffer that is present always has its form's size.
+static void hipk_drop_coded(hipk_csr_s *h);
+static hipError_t hipk_own(void **p, size_t bytes, bool *fresh) {   // the handle's buffer, allocated now if it has none
+    *fresh = false;
+    if (*p) return hipSuccess;
+    const hipError_t e = hipMalloc(p, bytes);
+    if (e == hipSuccess) *fresh = true; else *p = nullptr;
+    return e;
+}
+
+// The sliced-ELL plan: tile widths -> plane offsets, and whether the planes pay.  It reads crow alone, so it is made once per
+// handle (one host synchronisation for the widths, a second for the offsets' upload when the planes pay) and serves both dictionary attempts and every later update.
+static hipError_t hipk_sell_plan(hipk_csr_s *h, hipStream_t stream, int *syncs) {
+    if (h->plan_sell != 0) return hipSuccess;
+    const int ntiles = (int)((h->n_rows + HIPK_TILE - 1) / HIPK_TILE);
+    int *tw = nullptr;
+    hipError_t e = hipMalloc((void **)&tw, sizeof(int) * (size_t)(ntiles + 1));
+    if (e != hipSuccess) return e;
+    std::vector<int> toff((size_t)ntiles + 1);
+    hipk_tile_width_kernel<<<ntiles, HIPK_THREADS, 0, stream>>>(h->crow, h->n_rows, tw);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(toff.data(), tw, sizeof(int) * (size_t)ntiles, hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    ++*syncs;
+    if (e != hipSuccess) {
+        (void)hipFree(tw);
+        return e;
+    }
+    int64_t planes = 0;
+    int wmin = INT32_MAX, wmax = 0;
+    for (int i = 0; i < ntiles; ++i) {
+        const int w = hipk_sell_units(toff[i]);  // tile size in units of 256 B
+        wmin = w < wmin ? w : wmin;
+        wmax = w > wmax ? w : wmax;
+        toff[i] = (int)planes;
+        planes += w;
+    }
+    toff[ntiles] = (int)planes;
+    // nearly uniform sizes (a stencil's first/last grid line is narrower): pad every tile to the largest,
+    // so that a tile is found without the offset table (one dependent load less per workgroup)
+    const int64_t planes_u = (int64_t)ntiles * wmax;
+    if (wmin != wmax && planes_u <= planes + planes / 50 + 8) {
+        for (int i = 0; i <= ntiles; ++i) toff[i] = i * wmax;
+        planes = planes_u;
+        wmin = wmax;
+    }
+    const bool sell = planes * HIPK_TILE <= 2 * h->nnz + 65536 && planes < (int64_t)INT32_MAX / HIPK_TILE * 64;
+    if (sell) {
+        e = hipMemcpyAsync(tw, toff.data(), sizeof(int) * (size_t)(ntiles + 1), hipMemcpyHostToDevice, stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(stream);   // toff dies with this frame
+        ++*syncs;
+        if (e != hipSuccess) {
+            (void)hipFree(tw);
+            return e;
+        }
+        h->plan_tile_off = tw;
+        h->plan_sell_w = (wmin == wmax) ? wmax : 0;
+        h->plan_sell_bytes = planes * HIPK_TILE;
+        h->plan_sell = 1;
+    } else {
+        (void)hipFree(tw);
+        h->plan_sell = -1;
+    }
+    return hipSuccess;
+}
+
+// Try to build the coded form (hipk_coded.h) from h->val.  *built: the handle now carries it.  Anything else -- the dictionary's
+// verdict, a HIP error -- leaves *built false and the caller drops what the attempt may have left.  An attempt whose dictionary
+// does not fit returns BEFORE it touches any buffer of the form the handle holds (the pair attempt on an offset-coded handle).
 // OFFS_ONLY: dictionary of column offsets only + per-entry value planes (variable-coefficient stencils; layout 3).
 template <typename T, bool OFFS_ONLY>
-static hipError_t hipk_build_coded(hipk_csr_s *h, hipStream_t stream) {
-    hipk_dict_table *tb = nullptr;
-    hipError_t e = hipMalloc((void **)&tb, sizeof(hipk_dict_table));
+static hipError_t hipk_build_coded(hipk_csr_s *h, hipStream_t stream, bool *built, int *syncs) {
+    *built = false;
+    bool fresh = false;
+    hipError_t e = hipk_own(&h->dict_tb, sizeof(hipk_dict_table), &fresh);
     if (e != hipSuccess) return e;
-    struct guard {
-        hipk_dict_table *p;
-        ~guard() { (void)hipFree(p); }
-    } g{tb};
+    hipk_dict_table *tb = (hipk_dict_table *)h->dict_tb;
     e = hipMemsetAsync(tb, 0, sizeof(hipk_dict_table), stream);
     if (e != hipSuccess) return e;
     int grid = (int)((h->n_rows + 255) / 256);
@@ -147,6 +217,7 @@ static hipError_t hipk_build_coded(hipk_csr_s *h, hipStream_t stream) {
         e = hipGetLastError();
         if (e == hipSuccess) e = hipMemcpyAsync(head, &tb->count, sizeof(head), hipMemcpyDeviceToHost, stream);
         if (e == hipSuccess) e = hipStreamSynchronize(stream);
+        ++*syncs;
         if (e != hipSuccess) return e;
         if (head[1] || head[0] > HIPK_CODED_MAX) return hipSuccess;
     }
@@ -161,6 +232,7 @@ static hipError_t hipk_build_coded(hipk_csr_s *h, hipStream_t stream) {
     } hg{ht};
     e = hipMemcpyAsync(ht, tb, sizeof(hipk_dict_table), hipMemcpyDeviceToHost, stream);
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    ++*syncs;
     if (e != hipSuccess) return e;
     if (ht->overflow || ht->count > HIPK_CODED_MAX || ht->count <= 0) return hipSuccess;
     // number the occupied slots; the order is irrelevant to the results (a lookup returns the exact pair)
@@ -184,12 +256,6 @@ static hipError_t hipk_build_coded(hipk_csr_s *h, hipStream_t stream) {
         ++nc;
     }
     if (nc != ht->count) return hipSuccess;  // a claimed slot whose count was not yet added cannot happen after the sync
-    e = hipMemcpyAsync(tb->slot_code, ht->slot_code, sizeof(ht->slot_code), hipMemcpyHostToDevice, stream);
-    if (e == hipSuccess) e = hipMalloc((void **)&h->dict_off, sizeof(int) * HIPK_CODED_MAX);
-    if (e == hipSuccess) e = hipMalloc((void **)&h->dict_val, sizeof(T) * HIPK_CODED_MAX);
-    if (e == hipSuccess) e = hipMemcpyAsync(h->dict_off, off_h, sizeof(off_h), hipMemcpyHostToDevice, stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(h->dict_val, val_h, sizeof(val_h), hipMemcpyHostToDevice, stream);
-    if (e != hipSuccess) return e;
 
     // layout of the code bytes: sliced-ELL planes when the padding stays small, else CSR order + row lengths
     const bool lay_csr = hipk_sw_word_is("HIPK_SPMV_CODED_LAYOUT", "csr");
@@ -198,104 +264,95 @@ static hipError_t hipk_build_coded(hipk_csr_s *h, hipStream_t stream) {
                            h->n_rows <= h->n_cols && (uint64_t)h->n_cols * sizeof(T) < (1ull << 32);
     if (OFFS_ONLY && !want_sell) return hipSuccess;  // the offset-coded form exists in the sliced-ELL layout only
     const int ntiles = (int)((h->n_rows + HIPK_TILE - 1) / HIPK_TILE);
-    std::vector<int> toff;
     bool sell = false;
     if (want_sell) {
-        int *tw = nullptr;
-        e = hipMalloc((void **)&tw, sizeof(int) * (size_t)(ntiles + 1));
-        if (e != hipSuccess) return e;
-        hipk_tile_width_kernel<<<ntiles, HIPK_THREADS, 0, stream>>>(h->crow, h->n_rows, tw);
-        toff.resize((size_t)ntiles + 1);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(toff.data(), tw, sizeof(int) * (size_t)ntiles, hipMemcpyDeviceToHost, stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(stream);
-        if (e != hipSuccess) {
-            (void)hipFree(tw);
-            return e;
+        if (h->plan_sell == 0) {
+            e = hipk_sell_plan(h, stream, syncs);
+            if (e != hipSuccess) return e;
         }
-        int64_t planes = 0;
-        int wmin = INT32_MAX, wmax = 0;
-        for (int i = 0; i < ntiles; ++i) {
-            const int w = hipk_sell_units(toff[i]);  // tile size in units of 256 B
-            wmin = w < wmin ? w : wmin;
-            wmax = w > wmax ? w : wmax;
-            toff[i] = (int)planes;
-            planes += w;
+        sell = h->plan_sell == 1;
+    }
+    if (OFFS_ONLY && !sell) return hipSuccess;  // planes mostly padding: no offset-coded form
+    // from here on the handle's buffers are written.  Those of another layout are freed first: what stays has this layout's sizes
+    const int layout = OFFS_ONLY ? 3 : (sell ? 2 : 1);
+    if (h->coded_layout != layout) hipk_drop_coded(h);
+    h->n_codes = 0;   // (until the encode pass has succeeded)
+    h->tile_ucode = nullptr;
+    h->n_uniform_tiles = 0;
+    h->uniform_units = 0;
+    h->n_masked_tiles = 0;
+    h->masked_units = 0;
+    e = hipMemcpyAsync(tb->slot_code, ht->slot_code, sizeof(ht->slot_code), hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) e = hipk_own((void **)&h->dict_off, sizeof(int) * HIPK_CODED_MAX, &fresh);
+    if (e == hipSuccess) e = hipk_own(&h->dict_val, sizeof(T) * HIPK_CODED_MAX, &fresh);
+    if (e == hipSuccess) e = hipMemcpyAsync(h->dict_off, off_h, sizeof(off_h), hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(h->dict_val, val_h, sizeof(val_h), hipMemcpyHostToDevice, stream);
+    if (e != hipSuccess) return e;
+    if (sell) {
+        h->tile_off = h->plan_tile_off;
+        h->sell_w = h->plan_sell_w;
+        h->sell_bytes = h->plan_sell_bytes;
+        // the padding of the planes follows from crow alone: it is set when a plane is allocated and never again
+        e = hipk_own((void **)&h->code, (size_t)h->sell_bytes + 256, &fresh);
+        if (e == hipSuccess && fresh) e = hipMemsetAsync(h->code, HIPK_SELL_PAD, (size_t)h->sell_bytes + 256, stream);
+        if (OFFS_ONLY) {
+            if (e == hipSuccess) e = hipk_own(&h->sell_vals, ((size_t)h->sell_bytes + 256) * sizeof(T), &fresh);
+            if (e == hipSuccess && fresh) e = hipMemsetAsync(h->sell_vals, 0, ((size_t)h->sell_bytes + 256) * sizeof(T), stream);
         }
-        toff[ntiles] = (int)planes;
-        // nearly uniform sizes (a stencil's first/last grid line is narrower): pad every tile to the largest,
-        // so that a tile is found without the offset table (one dependent load less per workgroup)
-        const int64_t planes_u = (int64_t)ntiles * wmax;
-        if (wmin != wmax && planes_u <= planes + planes / 50 + 8) {
-            for (int i = 0; i <= ntiles; ++i) toff[i] = i * wmax;
-            planes = planes_u;
-            wmin = wmax;
+        if (e == hipSuccess) {
+            hipk_dict_encode_sell_kernel<T, OFFS_ONLY><<<grid, HIPK_THREADS, 0, stream>>>(
+                h->crow, h->col, (const T *)h->val, h->n_rows, tb, h->tile_off, h->code, (T *)h->sell_vals);
+            e = hipGetLastError();
         }
-        sell = planes * HIPK_TILE <= 2 * h->nnz + 65536 && planes < (int64_t)INT32_MAX / HIPK_TILE * 64;
-        if (sell) {
-            h->tile_off = tw;
-            h->sell_w = (wmin == wmax) ? wmax : 0;
-            h->sell_bytes = planes * HIPK_TILE;
-            e = hipMemcpyAsync(tw, toff.data(), sizeof(int) * (size_t)(ntiles + 1), hipMemcpyHostToDevice, stream);
-            if (e == hipSuccess) e = hipMalloc((void **)&h->code, (size_t)h->sell_bytes + 256);
-            if (e == hipSuccess) e = hipMemsetAsync(h->code, HIPK_SELL_PAD, (size_t)h->sell_bytes + 256, stream);
-            if (OFFS_ONLY) {
-                if (e == hipSuccess) e = hipMalloc(&h->sell_vals, ((size_t)h->sell_bytes + 256) * sizeof(T));
-                if (e == hipSuccess) e = hipMemsetAsync(h->sell_vals, 0, ((size_t)h->sell_bytes + 256) * sizeof(T), stream);
+        // tiles whose rows all carry the same code bytes (constant-coefficient stencils: all but the grid-line ends)
+        if (e == hipSuccess && hipk_sw_enabled("HIPK_SPMV_UNIFORM")) {
+            int *ucount = nullptr;
+            e = hipk_own((void **)&h->ucode_buf, sizeof(unsigned long long) * (size_t)ntiles + 2 * sizeof(int), &fresh);
+            if (e == hipSuccess) {
+                ucount = (int *)(h->ucode_buf + ntiles);
+                e = hipMemsetAsync(ucount, 0, 2 * sizeof(int), stream);
             }
             if (e == hipSuccess) {
-                hipk_dict_encode_sell_kernel<T, OFFS_ONLY><<<grid, HIPK_THREADS, 0, stream>>>(
-                    h->crow, h->col, (const T *)h->val, h->n_rows, tb, h->tile_off, h->code, (T *)h->sell_vals);
+                hipk_tile_uniform_kernel<<<(ntiles + 15) / 16, HIPK_THREADS, 0, stream>>>(h->code, h->tile_off, ntiles, h->ucode_buf,
+                                                                              ucount);
                 e = hipGetLastError();
             }
-            // tiles whose rows all carry the same code bytes (constant-coefficient stencils: all but the grid-line ends)
-            if (e == hipSuccess && hipk_sw_enabled("HIPK_SPMV_UNIFORM")) {
-                int *ucount = nullptr;
-                e = hipMalloc((void **)&h->tile_ucode, sizeof(unsigned long long) * (size_t)ntiles + 2 * sizeof(int));
+            if (e == hipSuccess)
+                e = hipMemcpyAsync(&h->n_uniform_tiles, ucount, sizeof(int), hipMemcpyDeviceToHost, stream);
+            if (e == hipSuccess)
+                e = hipMemcpyAsync(&h->uniform_units, ucount + 1, sizeof(int), hipMemcpyDeviceToHost, stream);
+            if (e == hipSuccess) h->tile_ucode = h->ucode_buf;   // (until the counts are in)
+            // masked tiles (hipk_tile_masked_kernel): pair codes in fp64 only (the two-rows-per-lane kernel's domain), code 254
+            // free for the marker.  OPT-IN (HIPK_SPMV_MASKED=1): bit-identical, but measured SLOWER where it was meant to help
+            // (N = 4 M: 15.7-16.2 vs 14.6-14.9 us stand-alone, CG 17.6 vs 17.97 k it/s; N = 1.96 M: equal;
+            // profiles/r03_spmv_wide_stamps.md section 4)
+            if (e == hipSuccess && !OFFS_ONLY && sizeof(T) == 8 && nc <= 254 && hipk_sw_force("HIPK_SPMV_MASKED", false)) {
+                int *mcount = nullptr;
+                e = hipk_own((void **)&h->tile_wcode, sizeof(unsigned long long) * (size_t)ntiles + 2 * sizeof(int), &fresh);
+                if (e == hipSuccess) e = hipk_own((void **)&h->row_mask, (size_t)ntiles * HIPK_TILE + 16, &fresh);
                 if (e == hipSuccess) {
-                    ucount = (int *)(h->tile_ucode + ntiles);
-                    e = hipMemsetAsync(ucount, 0, 2 * sizeof(int), stream);
+                    mcount = (int *)(h->tile_wcode + ntiles);
+                    e = hipMemsetAsync(mcount, 0, 2 * sizeof(int), stream);
                 }
                 if (e == hipSuccess) {
-                    hipk_tile_uniform_kernel<<<(ntiles + 15) / 16, HIPK_THREADS, 0, stream>>>(h->code, h->tile_off, ntiles, h->tile_ucode,
-                                                                                  ucount);
+                    hipk_tile_masked_kernel<<<(ntiles + 15) / 16, HIPK_THREADS, 0, stream>>>(h->code, h->tile_off, ntiles, h->n_rows,
+                                                                                 h->dict_off, h->ucode_buf, h->tile_wcode,
+                                                                                 h->row_mask, mcount);
                     e = hipGetLastError();
                 }
-                if (e == hipSuccess)
-                    e = hipMemcpyAsync(&h->n_uniform_tiles, ucount, sizeof(int), hipMemcpyDeviceToHost, stream);
-                if (e == hipSuccess)
-                    e = hipMemcpyAsync(&h->uniform_units, ucount + 1, sizeof(int), hipMemcpyDeviceToHost, stream);
-                // masked tiles (hipk_tile_masked_kernel): pair codes in fp64 only (the two-rows-per-lane kernel's domain), code 254
-                // free for the marker.  OPT-IN (HIPK_SPMV_MASKED=1): bit-identical, but measured SLOWER where it was meant to help
-                // (N = 4 M: 15.7-16.2 vs 14.6-14.9 us stand-alone, CG 17.6 vs 17.97 k it/s; N = 1.96 M: equal;
-                // profiles/r03_spmv_wide_stamps.md section 4)
-                if (e == hipSuccess && !OFFS_ONLY && sizeof(T) == 8 && nc <= 254 && hipk_sw_force("HIPK_SPMV_MASKED", false)) {
-                    int *mcount = nullptr;
-                    e = hipMalloc((void **)&h->tile_wcode, sizeof(unsigned long long) * (size_t)ntiles + 2 * sizeof(int));
-                    if (e == hipSuccess) e = hipMalloc((void **)&h->row_mask, (size_t)ntiles * HIPK_TILE + 16);
-                    if (e == hipSuccess) {
-                        mcount = (int *)(h->tile_wcode + ntiles);
-                        e = hipMemsetAsync(mcount, 0, 2 * sizeof(int), stream);
-                    }
-                    if (e == hipSuccess) {
-                        hipk_tile_masked_kernel<<<(ntiles + 15) / 16, HIPK_THREADS, 0, stream>>>(h->code, h->tile_off, ntiles, h->n_rows,
-                                                                                     h->dict_off, h->tile_ucode, h->tile_wcode,
-                                                                                     h->row_mask, mcount);
-                        e = hipGetLastError();
-                    }
-                    if (e == hipSuccess) e = hipMemcpyAsync(&h->n_masked_tiles, mcount, sizeof(int), hipMemcpyDeviceToHost, stream);
-                    if (e == hipSuccess) e = hipMemcpyAsync(&h->masked_units, mcount + 1, sizeof(int), hipMemcpyDeviceToHost, stream);
-                }
+                if (e == hipSuccess) e = hipMemcpyAsync(&h->n_masked_tiles, mcount, sizeof(int), hipMemcpyDeviceToHost, stream);
+                if (e == hipSuccess) e = hipMemcpyAsync(&h->masked_units, mcount + 1, sizeof(int), hipMemcpyDeviceToHost, stream);
+            } else if (h->tile_wcode) {   // (an update under another HIPK_SPMV_MASKED than the creation's)
+                (void)hipFree(h->tile_wcode);
+                if (h->row_mask) (void)hipFree(h->row_mask);
+                h->tile_wcode = nullptr;
+                h->row_mask = nullptr;
             }
-        } else {
-            (void)hipFree(tw);
         }
-    }
-    if (OFFS_ONLY && !sell) return e;  // planes mostly padding: no offset-coded form
-    if (!sell) {
-        if (e == hipSuccess) e = hipMalloc((void **)&h->code, (size_t)h->nnz + 32);
-        if (e == hipSuccess) e = hipMalloc((void **)&h->rowlen, (size_t)h->n_rows + 16);
-        if (e == hipSuccess) e = hipMemsetAsync(h->code + h->nnz, 0, 32, stream);
+    } else {
+        e = hipk_own((void **)&h->code, (size_t)h->nnz + 32, &fresh);
+        if (e == hipSuccess && fresh) e = hipMemsetAsync(h->code + h->nnz, 0, 32, stream);
+        if (e == hipSuccess) e = hipk_own((void **)&h->rowlen, (size_t)h->n_rows + 16, &fresh);
         if (e == hipSuccess) {
             hipk_dict_encode_kernel<T><<<grid, HIPK_THREADS, 0, stream>>>(h->crow, h->col, (const T *)h->val, h->n_rows,
                                                                          tb, h->code, h->rowlen);
@@ -305,14 +362,18 @@ static hipError_t hipk_build_coded(hipk_csr_s *h, hipStream_t stream) {
     int fail = 1;
     if (e == hipSuccess) e = hipMemcpyAsync(&fail, &tb->fail, sizeof(int), hipMemcpyDeviceToHost, stream);
     if (e == hipSuccess) e = hipStreamSynchronize(stream);  // also keeps the host staging arrays alive until the copies are done
-    if (e != hipSuccess) return e;
+    ++*syncs;
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(stream);   // the staging arrays of copies already enqueued die with this frame
+        return e;
+    }
     if (!fail) {
         h->n_codes = nc;
-        h->coded_layout = OFFS_ONLY ? 3 : (sell ? 2 : 1);
+        h->coded_layout = layout;
+        *built = true;
     }
-    if (h->tile_ucode && (fail || 4 * (int64_t)h->n_uniform_tiles < ntiles)) {  // too few uniform tiles to pay for the test
-        (void)hipFree(h->tile_ucode);
-        h->tile_ucode = nullptr;
+    if (h->tile_ucode && (fail || 4 * (int64_t)h->n_uniform_tiles < ntiles)) {  // too few uniform tiles to pay for the test:
+        h->tile_ucode = nullptr;                                                //   the words stay in ucode_buf, unread
         h->n_uniform_tiles = 0;
         h->uniform_units = 0;
     }
@@ -327,13 +388,14 @@ static hipError_t hipk_build_coded(hipk_csr_s *h, hipStream_t stream) {
     return hipSuccess;
 }
 
+// the buffers of the form the handle carries (not what follows from the pattern alone: dict_tb, the sliced-ELL plan)
 static void hipk_drop_coded(hipk_csr_s *h) {
     if (h->code) (void)hipFree(h->code);
     if (h->rowlen) (void)hipFree(h->rowlen);
     if (h->dict_off) (void)hipFree(h->dict_off);
     if (h->dict_val) (void)hipFree(h->dict_val);
-    if (h->tile_off) (void)hipFree(h->tile_off);
-    if (h->tile_ucode) (void)hipFree(h->tile_ucode);
+    if (h->ucode_buf) (void)hipFree(h->ucode_buf);
+    h->ucode_buf = nullptr;
     h->tile_ucode = nullptr;
     h->n_uniform_tiles = 0;
     h->uniform_units = 0;
@@ -345,12 +407,64 @@ static void hipk_drop_coded(hipk_csr_s *h) {
     h->masked_units = 0;
     if (h->sell_vals) (void)hipFree(h->sell_vals);
     h->sell_vals = nullptr;
-    h->tile_off = nullptr;
+    h->tile_off = nullptr;   // (plan_tile_off stays)
+    h->sell_w = 0;
+    h->sell_bytes = 0;
     h->coded_layout = 0;
     h->code = h->rowlen = nullptr;
     h->dict_off = nullptr;
     h->dict_val = nullptr;
     h->n_codes = 0;
+}
+
+// New values into the value planes of an offset-coded handle (layout 3): its offset dictionary, code planes, uniform-tile words
+// and plane offsets follow from crow / col and stay.  form 0: the library's choice; 1 rows, 2 staged (hipk_csr_revalue_probe).
+template <typename T>
+static hipError_t hipk_revalue(hipk_csr_s *h, hipStream_t stream, int form) {
+    constexpr int VEC = hipk_vec<T>::VEC;
+    const int ntiles = (int)((h->n_rows + HIPK_TILE - 1) / HIPK_TILE);
+    const int cap = ((h->max_tile_nnz + VEC - 1) / VEC + 1) * VEC;
+    const size_t lds = (size_t)cap * sizeof(T);
+    const bool staged = form == 2 || (form == 0 && HIPK_REVALUE_STAGED);
+    if (staged && lds <= HIPK_REVALUE_LDS_MAX)
+        hipk_csr_revalue_staged_kernel<T><<<ntiles, HIPK_THREADS, lds, stream>>>(h->crow, (const T *)h->val, h->n_rows, h->nnz, h->tile_off,
+                                                                                 (T *)h->sell_vals, cap);
+    else
+        hipk_csr_revalue_rows_kernel<T><<<ntiles, HIPK_THREADS, 0, stream>>>(h->crow, (const T *)h->val, h->n_rows, h->tile_off,
+                                                                             (T *)h->sell_vals);
+    return hipGetLastError();
+}
+
+// The decision path of hipk_csr_create_ex and hipk_csr_update_values: pair-coded, then offset-coded, then plain, from h->val and
+// the HIPK_* switches.  Returns the host synchronisations it took.
+template <typename T>
+static int hipk_decide_coded(hipk_csr_s *h, hipStream_t stream) {
+    int syncs = 0;
+    h->n_plans = 0;   // the SpMV dispatch plans depend on the form
+    // coded form: short rows everywhere, mean row below the row-per-wavefront threshold, not disabled by the environment
+    if (!(h->n_rows > 0 && h->nnz > 0 && h->max_row_len <= HIPK_LONG_ROW && hipk_sw_enabled("HIPK_SPMV_CODED"))) {
+        hipk_drop_coded(h);
+        return syncs;
+    }
+    bool built = false;
+    hipError_t e = hipk_build_coded<T, false>(h, stream, &built, &syncs);
+    if (e != hipSuccess) (void)hipGetLastError();  // e.g. out of memory: stay on the plain kernels
+    if (built) return syncs;
+    // too many distinct (offset, value) pairs: try offsets alone, values kept per entry (9 B instead of 12 B per
+    // entry, no row pointers) -- HIPK_SPMV_OFFSET_CODED=0 skips it
+    if (h->coded_layout != 3) hipk_drop_coded(h);   // (what a pair-coded handle held, or what the failed attempt left)
+    if (hipk_sw_enabled("HIPK_SPMV_OFFSET_CODED") && !h->offs_failed) {
+        if (h->coded_layout == 3) {   // an update: everything but the value planes follows from the pattern
+            e = hipk_revalue<T>(h, stream, 0);
+            built = e == hipSuccess;
+        } else {
+            e = hipk_build_coded<T, true>(h, stream, &built, &syncs);
+            if (e == hipSuccess && !built) h->offs_failed = 1;
+        }
+        if (e != hipSuccess) (void)hipGetLastError();
+    }
+    if (!built) hipk_drop_coded(h);
+    return syncs;
 }
 
 extern "C" int hipk_csr_create(hipk_csr_t *out, int64_t n_rows, int64_t n_cols, int64_t nnz,
@@ -466,21 +580,41 @@ extern "C" int hipk_csr_create_ex(hipk_csr_t *out, int64_t n_rows, int64_t n_col
         h->n_cu = (hipGetDeviceProperties(&prop, h->device) == hipSuccess && prop.multiProcessorCount > 0)
                       ? prop.multiProcessorCount : 256;
     }
-    if (n_rows > 0 && nnz > 0 && h->max_row_len <= HIPK_LONG_ROW && hipk_sw_enabled("HIPK_SPMV_CODED")) {
-        e = (dtype == HIPK_F64) ? hipk_build_coded<double, false>(h, stream) : hipk_build_coded<float, false>(h, stream);
-        if (e != hipSuccess) (void)hipGetLastError();  // e.g. out of memory: stay on the plain kernels
-        if (h->n_codes == 0) {
-            // too many distinct (offset, value) pairs: try offsets alone, values kept per entry (9 B instead of 12 B per
-            // entry, no row pointers) -- HIPK_SPMV_OFFSET_CODED=0 skips it
-            hipk_drop_coded(h);
-            if (hipk_sw_enabled("HIPK_SPMV_OFFSET_CODED")) {
-                e = (dtype == HIPK_F64) ? hipk_build_coded<double, true>(h, stream) : hipk_build_coded<float, true>(h, stream);
-                if (e != hipSuccess) (void)hipGetLastError();
-            }
-            if (h->n_codes == 0) hipk_drop_coded(h);
-        }
-    }
+    (void)((dtype == HIPK_F64) ? hipk_decide_coded<double>(h, stream) : hipk_decide_coded<float>(h, stream));
     *out = h;
+    return HIPK_OK;
+}
+
+static thread_local int g_update_kind = 0;
+static thread_local int g_update_syncs = 0;
+extern "C" int hipk_last_csr_update_kind(void) { return g_update_kind; }
+extern "C" int hipk_last_csr_update_syncs(void) { return g_update_syncs; }
+
+extern "C" int hipk_csr_update_values(hipk_csr_t h, const void *val_dev, hipk_stream_t stream_) {
+    HIPK_REQUIRE(h != nullptr, HIPK_ERR_ARG, "null handle");
+    HIPK_REQUIRE(h->op_cb == nullptr, HIPK_ERR_UNSUPPORTED, "a matrix-free handle has no values to update");
+    HIPK_REQUIRE(val_dev != nullptr, HIPK_ERR_ARG, "val is null");
+    HIPK_REQUIRE(hipk_aligned16(val_dev), HIPK_ERR_ALIGN, "val must be 16-byte aligned");
+    hipStream_t stream = (hipStream_t)stream_;
+    const int before = h->coded_layout;
+    h->val = val_dev;
+    g_update_syncs = (h->dtype == HIPK_F64) ? hipk_decide_coded<double>(h, stream) : hipk_decide_coded<float>(h, stream);
+    const int after = h->coded_layout;
+    g_update_kind = after != before ? 3 : ((after == 1 || after == 2) ? 2 : 1);
+    return HIPK_OK;
+}
+
+// measurement hook (tools/handle_update_probe.py): one launch of the value-plane rewrite of an offset-coded handle in the given
+// form, 1 rows / 2 staged, from the values the handle holds.  HIPK_ERR_UNSUPPORTED on any other handle.
+extern "C" int hipk_csr_revalue_probe(hipk_csr_t h, int form, hipk_stream_t stream_) {
+    HIPK_REQUIRE(h != nullptr && (form == 1 || form == 2), HIPK_ERR_ARG, "null handle or form not 1 / 2");
+    HIPK_REQUIRE(h->coded_layout == 3 && h->n_codes > 0, HIPK_ERR_UNSUPPORTED, "not an offset-coded handle");
+    const hipError_t e = (h->dtype == HIPK_F64) ? hipk_revalue<double>(h, (hipStream_t)stream_, form)
+                                                : hipk_revalue<float>(h, (hipStream_t)stream_, form);
+    if (e != hipSuccess) {
+        hipk_set_error("hipk_csr_revalue_probe: %s", hipGetErrorString(e));
+        return HIPK_ERR_HIP;
+    }
     return HIPK_OK;
 }
 
@@ -552,6 +686,8 @@ extern "C" int hipk_csr_destroy(hipk_csr_t h) {
     if (h->huge_rows) (void)hipFree(h->huge_rows);
     if (h->mid_plan_mem) (void)hipFree(h->mid_plan_mem);
     hipk_drop_coded(h);
+    if (h->dict_tb) (void)hipFree(h->dict_tb);
+    if (h->plan_tile_off) (void)hipFree(h->plan_tile_off);
     if (h->host_poll) (void)hipHostFree(h->host_poll);
     delete h;
     return HIPK_OK;

@@ -555,6 +555,69 @@ __global__ __launch_bounds__(HIPK_THREADS) void hipk_dict_encode_sell_kernel(
     }
 }
 
+// ------------------------------------------------------------------ hipk_csr_update_values: new values into the planes of layout 3
+// The offset codes of layout 3 follow from crow / col alone, so new values only rewrite the value planes: element
+// (tile_off[tile] + k) * 256 + t = val[crow[r] + k] for every stored entry k of row r = 256 tile + t -- exactly the elements
+// hipk_dict_encode_sell_kernel<T, true> writes, no pad element (they keep the 0 creation gave them), no dictionary look-up.
+// One workgroup per tile in both forms.
+//   rows   : one row per lane straight from global memory, the encode kernel's access: the lanes of a wavefront read addresses
+//            one row apart (40 B on a 5-point stencil in fp64).
+//   staged : the tile's contiguous CSR range val[crow[r0] .. crow[r0 + nr]) comes in with 16-byte loads, coalesced, into LDS
+//            (dynamic, `cap` elements: the handle's max_tile_nnz rounded up to a 16-byte group + one group of slack for the
+//            aligned start; at most 256 x 32 entries); the planes are then written from LDS.  The range is read from its
+//            16-byte group at or below crow[r0]; the last group is read element by element where it would pass nnz.
+// Plane stores are non-temporal in both: 8 or 4 B per lane, 2 KB / 1 KB contiguous per wavefront store, never read again
+// before the next product.
+#ifndef HIPK_REVALUE_STAGED
+#define HIPK_REVALUE_STAGED 1          // the library's choice between the two forms (tools/handle_update_probe.py measures both)
+#endif
+#define HIPK_REVALUE_LDS_MAX 65536     // the staged form's LDS bound: denser tiles take the row form
+template <typename T>
+__global__ __launch_bounds__(HIPK_THREADS) void hipk_csr_revalue_rows_kernel(const int *__restrict__ crow, const T *__restrict__ val,
+                                                                             int64_t n_rows, const int *__restrict__ tile_off,
+                                                                             T *__restrict__ vals) {
+    const int t = threadIdx.x;
+    const int64_t r = (int64_t)blockIdx.x * HIPK_TILE + t;
+    if (r >= n_rows) return;
+    const int lo = crow[r], len = crow[r + 1] - lo;
+    const int o0 = tile_off[blockIdx.x], cap = tile_off[blockIdx.x + 1] - o0;   // a tile of U units holds U entries per row
+    T *vp = vals + (size_t)o0 * HIPK_TILE + t;
+    for (int k = 0; k < len && k < cap; ++k) __builtin_nontemporal_store(val[lo + k], vp + (size_t)k * HIPK_TILE);
+}
+
+template <typename T>
+__global__ __launch_bounds__(HIPK_THREADS) void hipk_csr_revalue_staged_kernel(const int *__restrict__ crow, const T *__restrict__ val,
+                                                                               int64_t n_rows, int64_t nnz, const int *__restrict__ tile_off,
+                                                                               T *__restrict__ vals, int cap_lds) {
+    constexpr int VEC = hipk_vec<T>::VEC;
+    typedef T V __attribute__((ext_vector_type(hipk_vec<T>::VEC)));
+    extern __shared__ __attribute__((aligned(16))) unsigned char hipk_revalue_smem[];
+    T *buf = (T *)hipk_revalue_smem;
+    const int t = threadIdx.x;
+    const int64_t r0 = (int64_t)blockIdx.x * HIPK_TILE;
+    const int nr = (int)((n_rows - r0 < HIPK_TILE) ? (n_rows - r0) : HIPK_TILE);
+    const int j0 = __builtin_amdgcn_readfirstlane(crow[r0]);
+    const int j1 = __builtin_amdgcn_readfirstlane(crow[r0 + nr]);
+    const int a0 = j0 & ~(VEC - 1);
+    int nv = (j1 - a0 + VEC - 1) / VEC;
+    if (nv * VEC > cap_lds) nv = cap_lds / VEC;   // (cannot happen: cap_lds covers max_tile_nnz + one group; keeps LDS in bounds)
+    for (int v = t; v < nv; v += HIPK_THREADS) {
+        const int64_t j = (int64_t)a0 + (int64_t)v * VEC;
+        if (j + VEC <= nnz) {
+            ((V *)buf)[v] = __builtin_nontemporal_load((const V *)(val + j));
+        } else {
+            for (int i = 0; i < VEC; ++i) buf[v * VEC + i] = (j + i < nnz) ? val[j + i] : (T)0;
+        }
+    }
+    __syncthreads();
+    if (t >= nr) return;
+    const int lo = crow[r0 + t], len = crow[r0 + t + 1] - lo;
+    const int o0 = tile_off[blockIdx.x], cap = tile_off[blockIdx.x + 1] - o0;
+    T *vp = vals + (size_t)o0 * HIPK_TILE + t;
+    const int b = lo - a0;
+    for (int k = 0; k < len && k < cap && b + k < nv * VEC; ++k) __builtin_nontemporal_store(buf[b + k], vp + (size_t)k * HIPK_TILE);
+}
+
 // Persistent kernel.  A one-tile-per-workgroup kernel is bound by what every workgroup does ONCE (kernel
 // arguments, dictionary -> LDS, barrier, stop word) plus two dependent waits per tile (codes, x gather): ~3 us
 // per wavefront for ~5 KB of traffic.  Here the grid is the number of resident workgroups; each walks its share

@@ -147,6 +147,14 @@ struct hipk_csr_s {
     // matrix-free operator (hipk_op_create): every product is op_cb(op_user, x, y) + an epilogue kernel; no CSR arrays
     int (*op_cb)(void *user, const void *x_dev, void *y_dev);
     void *op_user;
+    // what hipk_csr_update_values keeps between the coded attempts (hipk_api.hip: hipk_decide_coded); all of it follows from crow / col
+    void *dict_tb;          // device, owned: the hipk_dict_table the dictionary attempts build in (cleared before each)
+    int *plan_tile_off;     // device, owned, ntiles + 1: the sliced-ELL plane offsets; tile_off points here while layout 2 / 3 is active
+    int plan_sell;          // 0 not computed, 1 the planes pay (<= 2 x nnz bytes), -1 mostly padding
+    int plan_sell_w;        //   sell_w / sell_bytes of the plan
+    int64_t plan_sell_bytes;
+    unsigned long long *ucode_buf;  // device, owned, ntiles + one pair of counters: tile_ucode is this or null (too few uniform tiles)
+    int offs_failed;        // the offset-coded attempt was made and found no form: never again for this pattern
     int cg_fuse_failed;     // hipk_cg_solve: the collector of the fused SpMV + update launch once gave up on this handle (hipk_cg_fuse.h)
     mutable hipk_spmv_plan plans[12];
     mutable int n_plans;

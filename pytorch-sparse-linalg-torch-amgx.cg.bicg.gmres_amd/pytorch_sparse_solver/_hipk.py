@@ -29,6 +29,8 @@ SYMBOLS = [
     "hipk_version", "hipk_build_id", "hipk_op_create", "hipk_placement_probe", "hipk_last_error", "hipk_device_count",
     "hipk_csr_create", "hipk_csr_destroy", "hipk_csr_rows", "hipk_csr_nnz", "hipk_csr_spmv_bytes",
     "hipk_csr_spmv_path", "hipk_last_spmv_kernel", "hipk_last_solve_path", "hipk_last_solve_form", "hipk_last_cg_fused_directions", "hipk_last_cg_fused_kept_p", "hipk_solve_form_count", "hipk_solve_form_name", "hipk_csr_set_path", "hipk_csr_format_bytes",
+    # new values on the pattern of an existing handle
+    "hipk_csr_update_values", "hipk_last_csr_update_kind", "hipk_last_csr_update_syncs", "hipk_csr_revalue_probe",
     "hipk_csr_transpose_work_bytes", "hipk_csr_transpose",
     # the matrix gradient of a solve: G[k] = -(lam[row(k)] * x[col(k)]) for one matrix and for a batch on one pattern
     "hipk_batch_grad_values", "hipk_csr_grad_values", "hipk_last_grad_values_launches",
@@ -235,6 +237,10 @@ def lib():
     L.hipk_last_grad_values_launches.restype = i32
     L.hipk_csr_spmv_path.argtypes = [vp]
     L.hipk_csr_set_path.argtypes = [vp, i32]
+    L.hipk_csr_update_values.argtypes = [vp, vp, vp]
+    L.hipk_last_csr_update_kind.restype = i32
+    L.hipk_last_csr_update_syncs.restype = i32
+    L.hipk_csr_revalue_probe.argtypes = [vp, i32, vp]
     L.hipk_chunk_size.argtypes = [i64]
     L.hipk_chunk_count.argtypes = [i64]
     L.hipk_scratch_bytes.restype = ctypes.c_size_t
@@ -507,7 +513,37 @@ class CsrHandle:
         b += 4 * (n + 1) + 4 * nnz + 64 * ((n + 255) // 256 + 1)
         if self.path() in ("coded", "offset_coded"):
             b += max(0, self.format_bytes() - 2 * n * sv)
+        # what the handle keeps for `update_values`: the dictionary build table (hipk_dict_table: 2048 slots of 24 bytes + three
+        # counters; kept by every handle that made a dictionary attempt, counted for all: a bound for those with a row of more than
+        # 32 entries) and, with a coded form, the sliced-ELL plane offsets and the uniform-tile words whether or not the SpMV reads them
+        if n > 0 and nnz > 0:
+            b += 2048 * 24 + 12
+            if self.path() in ("coded", "offset_coded"):
+                b += 12 * ((n + 255) // 256 + 1) + 8
         return int(b)
+
+    def update_values(self, values: torch.Tensor) -> "CsrHandle":
+        """New values on this handle's pattern (hipk_csr_update_values): afterwards the handle is the one a fresh `CsrHandle` on
+        the same index tensors and `values` would be -- same path, same kernels, same bits -- without the pattern-dependent half of
+        a creation.  `values` may be the tensor the handle already holds, changed in place.  Returns self."""
+        if not isinstance(values, torch.Tensor) or values.dtype != self.dtype:
+            raise ValueError(f"update_values: dtype {getattr(values, 'dtype', type(values))} differs from the handle's {self.dtype}")
+        if values.device != self.device:
+            raise ValueError(f"update_values: device {values.device} differs from the handle's {self.device}")
+        if values.dim() != 1 or values.numel() != self.val.numel():
+            raise ValueError(f"update_values: {tuple(values.shape)} values differ from the handle's nnz {self.val.numel()}")
+        val = aligned(values)       # a misaligned view's values are copied, as in the constructor
+        with self._lock, torch.cuda.device(self.device):
+            rc = lib().hipk_csr_update_values(self._h, val.data_ptr(), _stream(self.device))
+            _check(rc, "hipk_csr_update_values")
+            self.val = val
+            self._transposed = None     # it holds a gathered copy of the old values
+        return self
+
+    @staticmethod
+    def last_update_kind() -> int:
+        """1 values only, 2 re-encoded in place, 3 the form changed (hipk_last_csr_update_kind); 0 before this thread's first."""
+        return int(lib().hipk_last_csr_update_kind())
 
     def transposed(self) -> "CsrHandle":
         """Handle of A^T, built on the device from this handle's int32 arrays (hipk_csr_transpose: stable sort of the entries
@@ -633,6 +669,67 @@ def handle_for(A: torch.Tensor) -> CsrHandle:
     h = CsrHandle(csr.crow_indices(), csr.col_indices(), csr.values(), csr.shape)
     _store(key, h, src)
     return h
+
+
+def _no_version(part_key):
+    return part_key[:1] + part_key[2:]
+
+
+def _same_but_version(k1, k2) -> bool:
+    """Two cache keys that agree in everything but the version counters (field 1 of a part key).  `crow_indices()`,
+    `col_indices()` and `values()` of a sparse tensor all report the SPARSE tensor's counter, so an in-place change of the values
+    moves all three: the counter cannot say which component was written, the caller of refresh_matrix does."""
+    return len(k1) == len(k2) and k1[:4] == k2[:4] and all(_no_version(a) == _no_version(b) for a, b in zip(k1[4:], k2[4:]))
+
+
+def refresh_matrix(A: torch.Tensor, like: Optional[torch.Tensor] = None) -> bool:
+    """Give the cached handle of a CSR matrix new values instead of letting the next solve build a new handle.
+
+    like=None: `A`'s values were changed in place (`A.values().mul_(2)`).  The cache entry whose key equals A's in everything but
+    the version counter is updated (`CsrHandle.update_values`) and re-keyed, and entries of other views of the same values (the transpose an
+    adjoint solve cached) are dropped; True.  No such entry: False, and the next solve
+    builds a handle as it always did.
+    like=A_old: `A` is a CSR tensor on A_old's index tensors -- `crow_indices()` / `col_indices()` the same tensors, compared by
+    identity (pointer, size, view: their part keys without the version counter, which is the sparse tensor's, not theirs), never by contents -- with values of its own.  A takes over A_old's cached handle; a later
+    solve with A_old builds a new one.  True, or False when A_old has no cached handle.  Another layout, shape, dtype or device,
+    or index tensors of their own: ValueError."""
+    if not isinstance(A, torch.Tensor) or A.layout != torch.sparse_csr:
+        raise ValueError(f"refresh_matrix: A must be a sparse CSR tensor, not {getattr(A, 'layout', type(A))}")
+    key = _cache_key(A)
+    if like is None:
+        if key in _CACHE:
+            return True                 # nothing changed since the handle was built or refreshed
+        stale = [k for k in _CACHE if _same_but_version(k, key)]       # A solved at several versions: every one of them is stale
+        old_key = stale[-1] if stale else None                         # the most recently used takes the new values ...
+        for k in stale[:-1]:                                           # ... the others are dropped
+            del _CACHE[k]
+    else:
+        if not isinstance(like, torch.Tensor) or like.layout != torch.sparse_csr:
+            raise ValueError(f"refresh_matrix: like must be a sparse CSR tensor, not {getattr(like, 'layout', type(like))}")
+        for what, a, b in (("shape", tuple(A.shape), tuple(like.shape)), ("dtype", A.dtype, like.dtype),
+                           ("device", A.device, like.device)):
+            if a != b:
+                raise ValueError(f"refresh_matrix: {what} {a} differs from like's {b}")
+        old_key = _cache_key(like)
+        if [_no_version(p) for p in old_key[4:6]] != [_no_version(p) for p in key[4:6]]:
+            raise ValueError("refresh_matrix: A must share like's crow_indices() and col_indices() tensors (the same storage, "
+                             "same view); it has index tensors of its own")
+        if old_key == key:
+            return key in _CACHE
+    hit = _CACHE.get(old_key) if old_key is not None else None
+    if hit is None:
+        return False
+    h = hit[0]
+    h.update_values(A.values().detach())
+    if like is None:
+        # other entries on the same values -- the transposed view an adjoint solve asked for, and the CSR tensor handle_for made of
+        # it, which counts its own versions -- hold handles of the old numbers: dropped, the next backward pass rebuilds them
+        vptr = A.values().data_ptr()
+        for k in [k for k in _CACHE if k not in (key, old_key) and any(p[0] == vptr for p in k[4:])]:
+            del _CACHE[k]
+    del _CACHE[old_key]
+    _store(key, h, A.detach())
+    return True
 
 
 def clear_cache() -> None:

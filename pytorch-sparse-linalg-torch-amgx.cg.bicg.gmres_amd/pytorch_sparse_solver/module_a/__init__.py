@@ -24,7 +24,17 @@ from .torch_tree_util import tree_leaves, tree_map, tree_flatten, tree_unflatten
 from .preconditioners import BlockJacobiPreconditioner, ChebyshevPreconditioner, JacobiPreconditioner
 from .multigrid import AggregationMultigridPreconditioner, pairwise_aggregates
 
+
+def refresh_matrix(A, like=None) -> bool:
+    """New values on the pattern of a matrix the solvers have seen: the cached handle of `A` (changed in place), or of `like`
+    (a CSR tensor whose index tensors `A` shares), takes A's values instead of being rebuilt by the next solve.  True when a
+    handle was updated, False when there was none (the next solve then builds one as always).  See `_hipk.refresh_matrix`."""
+    from .. import _hipk
+    return _hipk.refresh_matrix(A, like)
+
+
 __all__ = [
+    'refresh_matrix',
     'cg', 'bicgstab', 'gmres', 'cg_multi', 'bicgstab_multi',
     'BatchedCSR', 'BatchedJacobiPreconditioner', 'BatchedBlockJacobiPreconditioner', 'cg_batch', 'bicgstab_batch', 'gmres_batch',
     'cg_differentiable', 'bicgstab_differentiable', 'gmres_differentiable',

@@ -651,10 +651,9 @@ class AggregationMultigridPreconditioner:
                     s.update(crow=crow, col=col,
                              val=_hipk.aligned(c.values()), dims=lev.dims, max_row=lev.max_row, c0=lev.c0, c1=lev.c1, c2=lev.c2)
                     if "r2" in s:                         # the W-cycle's step 4a on the tail's first level is a launch
-                        s["h"] = _hipk.CsrHandle(c.crow_indices(), c.col_indices(), c.values(), c.shape)
+                        s["h"] = self._level_handle(l)
                 elif l < min(tf, len(self.levels) - 1):   # a level of the launch sequence that has a next one
-                    s["h"] = _hipk.handle_for(self._A) if l == 0 else \
-                        _hipk.CsrHandle(c.crow_indices(), c.col_indices(), c.values(), c.shape)
+                    s["h"] = _hipk.handle_for(self._A) if l == 0 else self._level_handle(l)
                     s["t"], s["d"] = vec("t"), vec("d")
                     s["work"] = self._kept(l, "work", lambda: torch.empty(2 * ((lev.n + 3) & ~3) * c.values().element_size(),
                                                                           dtype=torch.uint8, device=dev))
@@ -748,6 +747,35 @@ class AggregationMultigridPreconditioner:
         return (self._kept(l, "crow", lambda: _hipk.aligned(c.crow_indices().to(torch.int32))),
                 self._kept(l, "col", lambda: _hipk.aligned(c.col_indices().to(torch.int32))))
 
+    def _level_handle(self, l: int):
+        """The `CsrHandle` of coarse level l: constructed once and kept in `_keep` -- its pattern-dependent half outlives every
+        `update` --, and given the level's values (`CsrHandle.update_values`) when it holds others."""
+        from .. import _hipk
+        c = self.levels[l].csr
+        h = self._keep.get((l, "h"))
+        if h is None:
+            h = self._keep[l, "h"] = _hipk.CsrHandle(c.crow_indices(), c.col_indices(), c.values(), c.shape)
+        else:
+            val = _hipk.aligned(c.values())
+            if h.val.data_ptr() != val.data_ptr():        # (h.val keeps its tensor alive: an equal address is the same tensor)
+                h.update_values(val)
+        return h
+
+    def _handles_back(self, A_new) -> None:
+        """After an `update` that raised: the kept handles that already took the new values (the norm estimate applies the new
+        hierarchy before the swap) are updated back to this object's values, and level 0's cached handle, if `A_new` took it over,
+        goes back to `_A`.  An updated handle is the fresh handle of its values, so the object is bit for bit what it was."""
+        if self.device.type != "cuda":
+            return
+        from .. import _hipk
+        for (l, name) in [k for k in self._keep if k[1] == "h"]:
+            self._level_handle(l)
+        if A_new.layout == torch.sparse_csr and self._A.layout == torch.sparse_csr:
+            try:
+                _hipk.refresh_matrix(self._A, like=A_new)
+            except ValueError:                            # index tensors of its own: the handle never moved
+                pass
+
     def update(self, A_new: torch.Tensor) -> "AggregationMultigridPreconditioner":
         """Refresh the hierarchy for a matrix with the SAME sparsity pattern and new values, and return self: what AMG packages
         call a re-setup.  The aggregates of every level (the boxes of a grid, `agg` of a graph hierarchy) and every index array
@@ -775,8 +803,11 @@ class AggregationMultigridPreconditioner:
         Galerkin keys, `gsrc`, and the segment starts `gptr` (int32 on a device object, which needs nnz < 2^31; int64 on a CPU
         object), and for a dense level the slot of each stored entry.  Later calls sort nothing.  On the device the Galerkin sums
         are `hipk_mg_restrict_agg` over (gptr, gsrc), every level's dinv / bound / diagonal check is one `hipk_mg_level_scan`,
-        and the bounds of all levels come back in one copy; coarse levels get new `CsrHandle`s, level 0 `_hipk.handle_for(A_new)`,
-        and the tail's descriptors are rebuilt, while index arrays and work vectors are reused."""
+        and the bounds of all levels come back in one copy; the coarse levels' `CsrHandle`s are kept and given the new values
+        (`CsrHandle.update_values`: nothing that follows from a level's pattern is rebuilt), level 0's cached handle moves to
+        `A_new` (`refresh_matrix(A_new, like=` the old matrix`)`) when `A_new` is a CSR tensor on the old matrix's index tensors and
+        is `_hipk.handle_for(A_new)` otherwise; the tail's descriptors are rebuilt, index arrays and work vectors are reused.  When
+        the call raises after handles took the new values, they are updated back."""
         what = "AggregationMultigridPreconditioner.update"
         self._check_matrix(A_new)
         if tuple(A_new.shape) != self.shape:
@@ -794,7 +825,11 @@ class AggregationMultigridPreconditioner:
         for name in ("crow_indices", "col_indices"):
             if not torch.equal(getattr(csr, name)().to(torch.int64), getattr(old, name)().to(torch.int64)):
                 raise ValueError(f"{what}: the sparsity pattern differs, {name} are not those of the matrix the object was built from")
-        state = self._refreshed(A, csr, self._refresh_plan()).__dict__
+        try:
+            state = self._refreshed(A, csr, self._refresh_plan()).__dict__
+        except BaseException:
+            self._handles_back(A)
+            raise
         self.__dict__.clear()
         self.__dict__.update(state)
         return self
@@ -871,7 +906,13 @@ class AggregationMultigridPreconditioner:
 
     def _refreshed(self, A, csr, plan):
         """The object `update` swaps in: a shallow copy of this one with new levels, `_A` and device state, built without touching
-        this one (the plan, the kept index arrays and work vectors and the CPU gather indices are shared: none holds a value)."""
+        this one.  The plan, the kept index arrays and work vectors and the CPU gather indices are shared and hold no value.  The
+        `CsrHandle`s of `_keep` are shared too and DO hold values: the new object's first apply (the norm estimate below, when
+        there is one) gives them the new levels' values while this object still refers to them, which is why `update` calls
+        `_handles_back` when this function raises.  `_level_handle` takes a handle for current when it borrows the level's own
+        values tensor (equal `data_ptr`); that holds because every level of the new object gets a values tensor of its own
+        below (`A_new`'s for level 0, a fresh Galerkin sum for each coarse level) while the old levels keep theirs alive, so two
+        levels' values never share an address."""
         new = object.__new__(type(self))
         new.__dict__.update(self.__dict__)
         new._A, new._dev, new.scale, new.applies, new.updates = A, None, 1.0, 0, self.updates + 1
@@ -897,6 +938,12 @@ class AggregationMultigridPreconditioner:
                     new._refresh_dense(lev, l, plan)
                 else:
                     new._set_up_smoother(lev, l, l == L)
+        if self.device.type == "cuda" and A.layout == torch.sparse_csr and self._A.layout == torch.sparse_csr and A is not self._A:
+            from .. import _hipk
+            try:                                          # level 0: the handle the solves of the old matrix hold goes to the new one
+                _hipk.refresh_matrix(A, like=self._A)
+            except ValueError:                            # index tensors of its own: `handle_for` builds A's handle as it always did
+                pass
         if self.normalize:
             new._estimate_scale()
         return new
