@@ -300,3 +300,65 @@ def test_multi_device_route_errors(hipk):
     from pytorch_sparse_solver.module_a.multi_rhs import _block_solve
     with pytest.raises(RuntimeError, match="size mismatch"):
         _block_solve("cg", A, _rhs(63, 2, 1), None, 1e-5, 0.0, None, None)
+
+
+# ------------------------------------------------------------------ a special right-hand side between two ordinary ones
+def _special_cases():
+    import _special_cases as S
+    out = []
+    for dtn in (S.F64, S.F32):
+        for name in ("nan-b", "inf-b", "b-overflow", "b-underflow", "zero-chunk"):
+            if name in S.REGIME_NAMES[dtn]:       # 2^520 and 2^-540 are no fp32 numbers
+                out.append((dtn, name))
+    return out
+
+
+@pytest.mark.parametrize("jacobi", [False, True], ids=["plain", "jacobi"])
+@pytest.mark.parametrize("kind", ["cg", "bicgstab"])
+@pytest.mark.parametrize("dtn, name", _special_cases(), ids=[f"{d}-{n}" for d, n in _special_cases()])
+def test_multi_neighbours_of_a_special_column(hipk, oracle, kind, jacobi, dtn, name):
+    """Three right-hand sides on one matrix of 2049 rows (two reduction chunks), the middle one in a special regime of b
+    (tests/_special_cases.py): NaN, inf, <b, b> overflowing or underflowing, a zero chunk.  Every column -- the special one and its
+    ordinary neighbours -- is its own single-right-hand-side oracle solve bit for bit (NaNs as one pattern: the sign of a produced
+    NaN is the implementation's), with its own info, iterations, matvecs and breakdown."""
+    import _special_cases as S
+    from _oracle_cases import _band
+    from pytorch_sparse_solver import _hipk
+    from pytorch_sparse_solver.module_a import JacobiPreconditioner, get_last_stats
+    from pytorch_sparse_solver.module_a.multi_rhs import _block_solve
+    wdt, ndt = (torch.float64, np.float64) if dtn == S.F64 else (torch.float32, np.float32)
+    n = 2049
+    Msp = _band(n, (1, 2)) if kind == "cg" else _band(n, (1, 2), sym=False, seed=1)
+    A = torch.sparse_csr_tensor(torch.from_numpy(Msp.indptr.astype(np.int64)), torch.from_numpy(Msp.indices.astype(np.int64)),
+                                torch.from_numpy(Msp.data.astype(ndt)), size=Msp.shape).to(DEV)
+    reg = S.regime(name, dtn)
+    Bh = _rhs(n, 3, 40, wdt).cpu().numpy()
+    Bh[:, 1] = S.special_b(S.scaled(np.ascontiguousarray(Bh[:, 1]), reg[3]), reg[4])
+    B = torch.from_numpy(Bh).to(DEV)
+    M = JacobiPreconditioner(A) if jacobi else None
+    kw = dict(tol=1e-8 if dtn == S.F64 else 1e-4, atol=0.0, maxiter=S.NAN_MAXITER if name == "nan-b" else S.MAXITER_CAP)
+    X, info = _block_solve(kind, A, B, None, kw["tol"], kw["atol"], kw["maxiter"], M)
+    st = get_last_stats()
+    assert _hipk.last_solve_path() == f"hipk_{kind}_multi launch sequence"
+    dinv = None if M is None else M.dinv.to(wdt).cpu().numpy()
+    Xh = X.cpu().numpy()
+
+    def canon(a):
+        a = np.array(a, copy=True)
+        a[np.isnan(a)] = np.nan
+        return a.view(np.int64 if a.dtype == np.float64 else np.int32)
+
+    seen = []
+    for j in range(3):
+        ref = _oracle_solve(oracle, kind, A, dinv, np.ascontiguousarray(Bh[:, j]), None, wdt, kw)
+        c = st.columns[j]
+        got, want = (int(info[j]), c.iterations, c.matvecs, c.breakdown), (ref.info, ref.iterations, ref.matvecs, ref.breakdown)
+        seen.append(want)
+        assert got == want, (j, got, want)
+        assert np.array_equal(canon(Xh[:, j]), canon(ref.x)), f"column {j} differs from its own oracle solve"
+    # the neighbours are ordinary solves, the middle column took a branch of its own
+    assert seen[0][1] > 0 and seen[2][1] > 0 and np.isfinite(Xh[:, [0, 2]]).all(), seen
+    if name == "nan-b":
+        assert seen[1][1] == S.NAN_MAXITER and np.isnan(Xh[:, 1]).all(), seen
+    elif name != "zero-chunk":
+        assert seen[1][1] == 0 and not Xh[:, 1].any(), seen

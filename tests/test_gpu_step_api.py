@@ -251,3 +251,110 @@ def test_gather(hipk, m, dtype):
     want[:m] = src[idx[:m]]
     assert np.array_equal(sc.bits(d.read()), sc.bits(want))
     assert np.array_equal(sc.bits(s.read()), sc.bits(src)) and np.array_equal(i.read(), idx)
+
+
+# --------------------------------------------------------------------------------------------------------- special values
+SPECIAL_N = (1, 2049, 70_001)
+SPECIAL_KINDS = ("+inf", "-inf", "both-inf", "nan", "negzero", "subnormal")
+
+
+def _special(kind, n, dtype, seed):
+    """(a, b) of n standard-normal entries with the kind's special entries: one infinity, two of opposite sign (inf - inf in a sum),
+    one NaN, every entry of a a negative zero (the sign of a zero sum), or both vectors scaled until products are subnormal or 0."""
+    rng = np.random.default_rng(seed)
+    a, b = rng.standard_normal(n).astype(dtype), rng.standard_normal(n).astype(dtype)
+    k = n // 2
+    if kind in ("+inf", "-inf"):
+        a[k] = np.inf if kind == "+inf" else -np.inf
+    elif kind == "both-inf":
+        a[k], a[0], b[k], b[0] = np.inf, -np.inf, 1.0, 1.0          # n = 1: the second assignment wins, one -inf
+    elif kind == "nan":
+        b[n - 1] = np.nan
+    elif kind == "negzero":
+        a[:] = -0.0
+    else:
+        e = -530 if dtype == np.float64 else -70                      # products near 2^-1060 / 2^-140: subnormal, or rounded to 0
+        a, b = np.ldexp(a, e).astype(dtype), np.ldexp(b, e).astype(dtype)
+        a[k] = -0.0
+    return a, b
+
+
+def _canon_bits(a):
+    """sc.bits with every NaN as one pattern: the sign and payload of a NaN an operation produces are the implementation's."""
+    a = np.array(a, copy=True)
+    a[np.isnan(a)] = np.nan
+    return sc.bits(a)
+
+
+@pytest.mark.parametrize("dtype", sc.DTYPES, ids=["f64", "f32"])
+@pytest.mark.parametrize("n", SPECIAL_N)
+def test_dot_on_special_values(hipk, oracle, n, dtype):
+    L = hipk.lib()
+    scratch = hipk.scratch(torch.device(DEV))
+    for kind in SPECIAL_KINDS:
+        a, b = _special(kind, n, dtype, n)
+        x, y, out = Guarded(a), Guarded(b), Guarded(np.full(1, sc.SENTINEL_PART))
+        hipk._check(L.hipk_dot(n, x.ptr, y.ptr, code(hipk, dtype), out.ptr, scratch.data_ptr(), stream(hipk)), "hipk_dot")
+        want = oracle.dot(a, b) if dtype == np.float64 else oracle.dot32(a, b)
+        got = out.read()
+        assert _canon_bits(got)[0] == _canon_bits(np.array([want]))[0], (kind, n, got[0], want)
+        assert np.array_equal(sc.bits(x.read()), sc.bits(a)) and np.array_equal(sc.bits(y.read()), sc.bits(b))
+
+
+@pytest.mark.parametrize("dtype", sc.DTYPES, ids=["f64", "f32"])
+@pytest.mark.parametrize("n", SPECIAL_N)
+def test_dot_parts_on_special_values(hipk, oracle, n, dtype):
+    """A special entry reaches the partial of its own chunk only."""
+    L = hipk.lib()
+    ch = 2048
+    for kind in SPECIAL_KINDS:
+        a, b = _special(kind, n, dtype, n + 1)
+        x, y = Guarded(a), Guarded(b)
+        part = Guarded(np.full(sm.MAX_PARTS, sc.SENTINEL_PART))
+        hipk._check(L.hipk_dot_parts(n, ch, x.ptr, y.ptr, code(hipk, dtype), part.ptr, stream(hipk)), "hipk_dot_parts")
+        q = oracle.dot_parts_ch(a, b, ch) if dtype == np.float64 else oracle.dot_parts_ch32(a, b, ch)
+        got = part.read()
+        assert np.array_equal(_canon_bits(got[:q.size]), _canon_bits(q)), (kind, n)
+        assert np.array_equal(sc.bits(got[q.size:]), sc.bits(np.full(sm.MAX_PARTS - q.size, sc.SENTINEL_PART)))
+        if kind in ("+inf", "-inf", "both-inf", "nan"):
+            special = np.unique(np.flatnonzero(~np.isfinite(a) | ~np.isfinite(b)) // ch)
+            assert np.array_equal(np.flatnonzero(~np.isfinite(got[:q.size])), special), (kind, n)
+
+
+@pytest.mark.parametrize("dtype", sc.DTYPES, ids=["f64", "f32"])
+@pytest.mark.parametrize("n", SPECIAL_N)
+def test_axpy_xpby_on_special_values(hipk, n, dtype):
+    L = hipk.lib()
+    a = np.dtype(dtype).type(SCALAR)
+    for kind in SPECIAL_KINDS:
+        xh, yh = _special(kind, n, dtype, n + 2)
+        x, y = Guarded(xh), Guarded(yh)
+        hipk._check(L.hipk_axpy(n, SCALAR, x.ptr, y.ptr, code(hipk, dtype), stream(hipk)), "hipk_axpy")
+        with np.errstate(all="ignore"):
+            want = yh + a * xh
+        assert np.array_equal(_canon_bits(y.read()), _canon_bits(want)), (kind, n)
+        y = Guarded(yh)
+        hipk._check(L.hipk_xpby(n, x.ptr, SCALAR, y.ptr, code(hipk, dtype), stream(hipk)), "hipk_xpby")
+        with np.errstate(all="ignore"):
+            want = xh + a * yh
+        assert np.array_equal(_canon_bits(y.read()), _canon_bits(want)), (kind, n)
+        assert np.array_equal(sc.bits(x.read()), sc.bits(xh))
+
+
+@pytest.mark.parametrize("dtype", sc.DTYPES, ids=["f64", "f32"])
+@pytest.mark.parametrize("n", SPECIAL_N)
+def test_gather_on_special_values(hipk, n, dtype):
+    """A copy: every bit arrives, the sign and payload of a NaN included."""
+    L = hipk.lib()
+    for kind in SPECIAL_KINDS:
+        src, _ = _special(kind, n, dtype, n + 3)
+        if kind == "nan":
+            src[0] = np.array([-np.nan], dtype=dtype)[0]
+            src[n // 2] = np.nan
+        idx = np.random.default_rng(n).integers(0, n, size=n).astype(np.int32)
+        idx[0], idx[-1] = n // 2, 0
+        s, i = Guarded(src), Guarded(idx)
+        d = Guarded(np.full(n, sentinel(dtype), dtype=dtype))
+        hipk._check(L.hipk_gather(n, i.ptr, s.ptr, d.ptr, code(hipk, dtype), stream(hipk)), "hipk_gather")
+        assert np.array_equal(sc.bits(d.read()), sc.bits(src[idx])), (kind, n)
+        assert np.array_equal(sc.bits(s.read()), sc.bits(src))
